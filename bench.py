@@ -20,6 +20,10 @@
   roofline: K7 (fused Jacobian + normal-equation kernel), algorithmic bytes / HIP-event time.
   cpu_baseline: the CPU oracle (oracle/ptam_oracle.cc, a single-thread restatement of the
             reference's loops — kind "port") on the same problem, rank 0, N = 1 only.
+  --full  : a plain run sets up, warms up, times the K steps and prints the line; every other leg (tracking, roofline,
+            per-kernel times, cold call, end-to-end call, deterministic mode, global and local BA, cpu_baseline; at N > 1
+            the per-kernel times, the same problem on one GPU and the tracking replicas) runs only with --full.
+  --dump-outputs DIR: what the timed Compute() returned to its caller after its last trial, as DIR/<name>.npy (float64).
 """
 import argparse
 import ctypes
@@ -52,7 +56,33 @@ def parse():
     ap.add_argument("--no-replicas", action="store_true", help="tracking: one context only (no k-thread replica runs; used under rocprofv3)")
     ap.add_argument("--deterministic", action="store_true", help="ptam_ba_opts.deterministic = 1 (camera sums in a fixed order): what the mode costs")
     ap.add_argument("--jac-reps", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="also every leg beside the headline (the --no-* switches and --jac-reps select among them); "
+                         "a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed Compute() returned to its caller as DIR/<name>.npy, float64: cameras [n, 12], "
+                         "points [n, 3] (global ids), outliers [n, 2] (point, camera; sorted); at most 64 MB, larger outputs as a "
+                         "seeded sample of rows")
     return ap.parse_args()
+
+
+DUMP_CAP_BYTES = 60_000_000   # (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> array, written as float64.  If they exceed DUMP_CAP_BYTES in all, the arrays of 1 MB and more keep the
+    same fraction of their rows, chosen with a fixed seed (the same rows for the same shapes, so that two builds compare row
+    for row); smaller ones are written whole"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    big = sum(a.nbytes for a in arrays.values() if a.nbytes >= 1 << 20)
+    small = sum(a.nbytes for a in arrays.values()) - big
+    frac = min(1.0, (DUMP_CAP_BYTES - small) / max(1, big))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if frac < 1.0 and a.nbytes >= 1 << 20:
+            rows = np.sort(np.random.default_rng(0x5EED).choice(len(a), size=max(1, int(len(a) * frac)), replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def tracking_bench(hip, host, synth, seq, frames=250, replicas=True):
@@ -509,11 +539,12 @@ def main():
         sb.close()
         return spin
 
-    def timed_compute(problem, steps, warmup, sharded=True, sync_ranks=True):
+    def timed_compute(problem, steps, warmup, sharded=True, sync_ranks=True, fetch=None):
         """W warm-up trials in their own Compute(), then ONE timed Compute() of exactly `steps` trials, bracketed by
         barrier + synchronise on both sides.  All bundles are built and made resident first, so that the warm-up runs
         IMMEDIATELY before the timed region (building a bundle is ~100 ms of host work with nothing queued).  DESIGN.md
-        section 5 lists what once made this bench bimodal and what was changed."""
+        section 5 lists what once made this bench bimodal and what was changed.  fetch(bundle), if given, is called on
+        the timed bundle after the clock has stopped."""
         wb = new_bundle(warmup, problem, sharded) if warmup > 0 else None
         ba = new_bundle(steps, problem, sharded)
         spin = spin_up(problem)
@@ -532,6 +563,8 @@ def main():
         trials = ba.trials()
         assert len(trials) == steps, (len(trials), steps)
         counts = ba.counts()
+        if fetch is not None:
+            fetch(ba)
         ba.close()
         if wb is not None:
             wb.close()
@@ -572,7 +605,14 @@ def main():
             kb.close()
         return out
 
-    dt, trials, (n_cams, n_free, n_points, n_meas), spin = timed_compute(prob, args.steps, args.warmup)
+    final = {}
+
+    def keep_final(ba):   # what a caller of the timed Compute() receives (Get*, GetOutlierMeasurements)
+        final["cameras"], final["points"] = ba.get_all()
+        final["outliers"] = ba.GetOutlierMeasurements()
+
+    dt, trials, (n_cams, n_free, n_points, n_meas), spin = timed_compute(prob, args.steps, args.warmup,
+                                                                         fetch=keep_final if args.dump_outputs else None)
     prepare_headline_ms = min(prepare_ms) if prepare_ms else None   # (the bundles of the timed workload; later legs append more)
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if one_gpu else "cuda")
@@ -604,8 +644,26 @@ def main():
             "deterministic": bool(args.deterministic),
             "source_sha16": source_sha16(),   # fingerprint of the library sources this run was built from (profiles/ are keyed by it)
             "prepare_ms": prepare_headline_ms,   # upload + device-built index structures of one Bundle of this workload: outside the timed region
+            "full": bool(args.full),   # (the legs beside the headline ran)
         }
-    if world > 1:
+    if args.dump_outputs:
+        # the shards' points and outliers re-assembled in global point ids (every rank takes part); cameras and trials are replicated
+        if world > 1:
+            from ptam_cg_amd.sharding import gather_points, merge_outliers
+
+            def all_gather(obj):
+                objs = [None] * world
+                dist.all_gather_object(objs, obj)
+                return objs
+            final["points"] = gather_points(final["points"], prob["global_point_ids"], len(prob_full["points"]), all_gather)
+            final["outliers"] = merge_outliers(final["outliers"], prob["global_point_ids"], all_gather)
+        # (not the trial records: diagnostics, and once lambda has overflowed at the noise floor — the convergence test is off —
+        #  they hold inf / NaN for trials that committed nothing)
+        if rank == 0:
+            ol = np.asarray(final["outliers"], dtype=np.int64).reshape(-1, 2)
+            dump_outputs(args.dump_outputs, {
+                "cameras": final["cameras"], "points": final["points"], "outliers": ol[np.lexsort((ol[:, 1], ol[:, 0]))]})
+    if world > 1 and args.full:
         # per-kernel breakdown of the sharded run (HIP events, separate Compute; every rank takes part in its collectives)
         kms = kernel_breakdown(prob, args.steps)
         if rank == 0:
@@ -637,7 +695,7 @@ def main():
                 if rank == 0:
                     out["tracking_replicas"] = {"error": repr(e)}
         barrier()
-    if world == 1:
+    if world == 1 and args.full:
         # ---- steady accepted-trial rate: a Compute() of exactly the leading accepted trials of this problem ----------
         n_lead = 0
         for a in trials["accepted"]:
@@ -803,7 +861,7 @@ def main():
             try:
                 out["cpu_baseline"], otr = cpu_baseline(args, host, synth, prob, seq)
                 # parity of the timed workload itself (oracle as checker, cheap: it already ran)
-                rel = abs(otr["err_new"][-1] - trials["err_new"][-1]) / abs(otr["err_new"][-1])
+                rel = abs(otr["err_new"][-1] - trials["err_new"][len(otr) - 1]) / abs(otr["err_new"][-1])
                 out["parity_rel_err_final_trial"] = float(rel)
             except Exception as e:   # noqa: BLE001
                 out["cpu_baseline"] = {"error": repr(e)}
@@ -833,13 +891,17 @@ def main():
         dist.destroy_process_group()
 
 
+CPU_MAX_TRIALS = 20
+
+
 def cpu_baseline(args, host, synth, prob, seq=None):
     """the oracle (kind "port") on the host cores: one thread on the timed problem (a bounded sample: at most 20 trials),
     a tracked-frame loop, and one independent replica per PHYSICAL core for the per-node figure"""
     from tests.oracle_lib import load_oracle
     oracle = load_oracle()
     octx = host.Context(lib=oracle)
-    ob = synth.load_into(host.Bundle(octx, max_iterations=args.steps, update_sq_conv_limit=0.0), prob)
+    n_trials = min(args.steps, CPU_MAX_TRIALS)   # (one oracle trial of the headline takes ~0.17 s)
+    ob = synth.load_into(host.Bundle(octx, max_iterations=n_trials, update_sq_conv_limit=0.0), prob)
     t0 = time.perf_counter()
     ob.Compute()
     cdt = time.perf_counter() - t0
@@ -927,7 +989,7 @@ def cpu_baseline(args, host, synth, prob, seq=None):
     reps = []
     for _ in range(n_rep):
         rc = host.Context(lib=oracle)
-        reps.append((rc, synth.load_into(host.Bundle(rc, max_iterations=args.steps, update_sq_conv_limit=0.0), prob)))
+        reps.append((rc, synth.load_into(host.Bundle(rc, max_iterations=n_trials, update_sq_conv_limit=0.0), prob)))
     th = [threading.Thread(target=b.Compute) for _, b in reps]   # ctypes drops the GIL inside the call
     t0 = time.perf_counter()
     for t_ in th:

@@ -7,8 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from ptam_cg_amd import _abi, host
-from tests import dist_util
+from ptam_cg_amd import _abi, host, synth
+from tests import dist_util, util
 
 pytestmark = pytest.mark.gpu
 
@@ -95,10 +95,11 @@ def test_rccl_single_rank_allreduce(hip):
     hip.rccl_destroy(comm)
 
 
-def test_bench_n2_path_prints_one_json_line():
+def test_bench_n2_path_prints_one_json_line(oracle, tmp_path):
     """bench.py's N > 1 code (rank bookkeeping, MAX over ranks, the one-device run of the same problem in the
     same line) must have executed before the driver's first multi-GPU run does it.  Two ranks under torch.distributed.run,
-    both on the one GPU (PTAM_BENCH_ONE_GPU=1: gloo with host staging instead of RCCL — the numbers mean nothing)."""
+    both on the one GPU (PTAM_BENCH_ONE_GPU=1: gloo with host staging instead of RCCL — the numbers mean nothing).
+    --dump-outputs: the shards' points re-assembled in global ids."""
     import json
     import os
     import subprocess
@@ -108,7 +109,8 @@ def test_bench_n2_path_prints_one_json_line():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(dist_util.free_port()), os.path.join(dist_util.ROOT, "bench.py"), "--gpus", "2", "--cams", "24",
-           "--points", "900", "--window", "8", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-tracking"]
+           "--points", "900", "--window", "8", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-tracking", "--full",
+           "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, env=env, cwd=dist_util.ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -120,6 +122,10 @@ def test_bench_n2_path_prints_one_json_line():
     assert one["workload"] == "bundle_24kf_x_900pts_window8" and one["value"] > 0
     assert abs(rec["speedup_vs_single_gpu"] - rec["value"] / one["value"]) < 1e-12
     assert set(rec["kernel_ms_per_trial"]) >= {"jacobian", "schur", "solve"}
+    ref = util.run_ba(oracle, synth.make_ba_problem(24, 900, synth.SEED_BA_HEADLINE, window=8), max_iterations=4, update_sq_conv_limit=0.0)
+    pts, cams = (np.load(tmp_path / f"{k}.npy") for k in ("points", "cameras"))
+    assert pts.shape == (900, 3) and cams.shape == (24, 12)
+    assert np.allclose(pts, ref["points"], atol=1e-9) and np.allclose(cams, ref["poses"], atol=1e-9)
 
 
 def test_solve_fault_on_one_rank_is_repeated_by_every_rank(oracle):

@@ -1,5 +1,5 @@
-import numpy as np, sys
-sys.path.insert(0,'/root/repo')
+import numpy as np, sys, os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from ptam_cg_amd._lib import load
 from tests.oracle_lib import load_oracle
 import tests.test_gpu_trackmap as T

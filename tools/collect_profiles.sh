@@ -1,16 +1,16 @@
 #!/bin/bash
 # Everything profiles/ holds for a round, in one GPU call:  tools/collect_profiles.sh <tag>
-#   gpurun_out/<tag>/bench.json            python bench.py (default flags)
+#   <tag>/bench.json (in the output folder) python bench.py --full (default flags otherwise)
 #   gpurun_out/<tag>/kernel_stats.csv      rocprofv3 --kernel-trace --stats of the same command
 #   gpurun_out/pmc_<tag>_headline/...      PMC passes of the roofline kernel (tools/profile_k7.sh)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-r01}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-cd $R && python bench.py > $OUT/bench.json 2> $OUT/bench.err
+cd $R && python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 for attempt in 1 2; do   # (rocprofv3 segfaulted once in a tool thread while tracing this command; the second attempt passed)
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o ba -- python $R/bench.py --no-cpu-baseline --no-replicas > $OUT/trace.log 2>&1 && break
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o ba -- python $R/bench.py --full --no-cpu-baseline --no-replicas > $OUT/trace.log 2>&1 && break
 done
 cp $OUT/trace/ba_kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null
 bash $R/tools/profile_k7.sh ${TAG}_headline 50 5000 20 > $OUT/pmc_headline.txt 2>&1
@@ -19,7 +19,7 @@ bash $R/tools/profile_k7.sh ${TAG}_config5 200 50000 20 16 > $OUT/pmc_config5.tx
 for pass in "sq1 SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_LDS" \
             "sq2 SQ_INSTS_VALU_MFMA_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU GRBM_GUI_ACTIVE"; do
   set -- $pass; name=$1; shift
-  timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_ba -o $name -- python $R/bench.py --no-cpu-baseline --no-tracking --no-global --steps 10 --warmup 1 > $OUT/pmc_ba_$name.log 2>&1 || echo "pass $name failed"
+  timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_ba -o $name -- python $R/bench.py --full --no-cpu-baseline --no-tracking --no-global --steps 10 --warmup 1 > $OUT/pmc_ba_$name.log 2>&1 || echo "pass $name failed"
 done
 python3 - <<PY | tee $OUT/pmc_schur_ldlt.txt
 import csv, glob, collections

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-.}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/bt
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/bt -o bt -- python $R/bench.py --no-cpu-baseline --no-tracking --no-global --no-local --steps 10 --jac-reps 1 $BA_TIMELINE_ARGS > /tmp/bt.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/bt -o bt -- python $R/bench.py --full --no-cpu-baseline --no-tracking --no-global --no-local --steps 10 --jac-reps 1 $BA_TIMELINE_ARGS > /tmp/bt.log 2>&1
 python3 - "$@" <<PY
 import csv, glob, sys
 f = glob.glob("/tmp/bt/**/bt_kernel_trace.csv", recursive=True)[0]

@@ -5,7 +5,7 @@ TAG=${1:-ks}; RE=${2:-.}
 OUT=$R/gpurun_out/ks_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ba -- python $R/bench.py --no-cpu-baseline --no-tracking > $OUT/log.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ba -- python $R/bench.py --full --no-cpu-baseline --no-tracking > $OUT/log.txt 2>&1
 python3 - <<PY
 import csv, re
 for r in csv.DictReader(open("$OUT/ba_kernel_stats.csv")):

@@ -10,7 +10,7 @@ for pass in "sq1 SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_
             "sq2 SQ_INSTS_VALU_MFMA_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_ANY SQ_INSTS_SALU GRBM_GUI_ACTIVE SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VMEM" \
             "tc1 TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum"; do
   set -- $pass; name=$1; shift
-  timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -o $name -- python $R/bench.py --no-cpu-baseline --no-tracking --no-global --steps 10 --warmup 1 $EXTRA > $OUT/$name.log 2>&1 || echo "pass $name failed"
+  timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -o $name -- python $R/bench.py --full --no-cpu-baseline --no-tracking --no-global --steps 10 --warmup 1 $EXTRA > $OUT/$name.log 2>&1 || echo "pass $name failed"
 done
 python3 - <<PY | tee $OUT/summary.txt
 import csv, glob, collections, re

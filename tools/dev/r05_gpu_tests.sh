@@ -6,7 +6,7 @@ shift
 cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q "$@" > $O/pytest.txt 2>&1
 tail -5 $O/pytest.txt
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err
 python3 - <<PY
 import json
 j=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

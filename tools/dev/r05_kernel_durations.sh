@@ -3,7 +3,7 @@
 # usage (GPU box): bash tools/dev/r05_kernel_durations.sh <regex>
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/kd; timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kd -o kd -- python $R/bench.py --no-cpu-baseline --no-tracking --no-global --no-local > /tmp/kd.log 2>&1
+rm -rf /tmp/kd; timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kd -o kd -- python $R/bench.py --full --no-cpu-baseline --no-tracking --no-global --no-local > /tmp/kd.log 2>&1
 python3 - "${1:-.}" <<PY
 import csv, glob, re, sys, collections
 f = glob.glob("/tmp/kd/**/kd_kernel_trace.csv", recursive=True)[0]

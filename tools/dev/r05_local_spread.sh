@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd $R
 for i in $(seq ${1:-6}); do
-  python bench.py --no-global --no-tracking --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  python bench.py --full --no-global --no-tracking --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read()); l=j['local_ba_config4']
 k=l['kernel_ms_per_trial']

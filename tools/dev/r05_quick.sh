@@ -5,7 +5,7 @@ O=$R/gpurun_out/${1:-quick}; mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "bundle" 2>&1 | tail -2
 for rep in $(seq ${2:-3}); do
-  timeout 300 python bench.py --no-cpu-baseline --no-tracking > $O/log.txt 2>&1
+  timeout 300 python bench.py --full --no-cpu-baseline --no-tracking > $O/log.txt 2>&1
   python3 - <<PY | tee -a $O/out.txt
 import json
 b = json.loads([l for l in open("$O/log.txt") if l.startswith("{")][-1])

@@ -10,7 +10,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "bundle" >
 tail -3 $O/pytest.txt
 for rep in 1 2; do
 for cfg in "$@"; do
-  env PTAM_HIP_LIB=$R/tools/_ab/libptam_hip.so $cfg timeout 300 python bench.py --no-cpu-baseline --no-tracking > $O/log.txt 2>&1
+  env PTAM_HIP_LIB=$R/tools/_ab/libptam_hip.so $cfg timeout 300 python bench.py --full --no-cpu-baseline --no-tracking > $O/log.txt 2>&1
   python3 - "$cfg" <<PY | tee -a $O/out.txt
 import json, sys
 b = json.loads([l for l in open("$O/log.txt") if l.startswith("{")][-1])
@@ -20,5 +20,5 @@ print("%-70s schur us: headline %.1f  config5 %.1f  config4 %.1f | it/s %.0f %.0
 PY
 done
 done
-PTAM_HIP_LIB=$R/tools/_exp/schur_stamps/libptam_hip.so timeout 300 python bench.py --no-cpu-baseline --no-tracking --no-global --no-local --steps 6 --warmup 1 --jac-reps 5 > $O/stamps_log.txt 2>&1
+PTAM_HIP_LIB=$R/tools/_exp/schur_stamps/libptam_hip.so timeout 300 python bench.py --full --no-cpu-baseline --no-tracking --no-global --no-local --steps 6 --warmup 1 --jac-reps 5 > $O/stamps_log.txt 2>&1
 python3 tools/dev/schur_fit.py $O/stamps_log.txt | tee $O/fit.txt

@@ -7,7 +7,7 @@ O=$R/gpurun_out/$T; mkdir -p $O
 cd $R
 for rep in $(seq $N); do
 for cfg in "$@"; do
-  env PTAM_HIP_LIB=$R/tools/_ab/libptam_hip.so $cfg timeout 300 python bench.py --no-cpu-baseline --no-tracking > $O/log.txt 2>&1
+  env PTAM_HIP_LIB=$R/tools/_ab/libptam_hip.so $cfg timeout 300 python bench.py --full --no-cpu-baseline --no-tracking > $O/log.txt 2>&1
   python3 - "$cfg" <<PY | tee -a $O/out.txt
 import json, sys
 b = json.loads([l for l in open("$O/log.txt") if l.startswith("{")][-1])

@@ -7,7 +7,7 @@ O=$R/gpurun_out/r05_schur_sched; mkdir -p $O
 cd $R
 for rep in 1 2; do
 for cfg in "$@"; do
-  env $cfg timeout 300 python bench.py --no-cpu-baseline --no-tracking > $O/log.txt 2>&1
+  env $cfg timeout 300 python bench.py --full --no-cpu-baseline --no-tracking > $O/log.txt 2>&1
   python3 - "$cfg" <<PY | tee -a $O/out.txt
 import json, sys
 b = json.loads([l for l in open("$O/log.txt") if l.startswith("{")][-1])

@@ -9,7 +9,7 @@ cd $R
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env PTAM_HIP_LIB=$R/tools/_exp/schur_stamps_ab/libptam_hip.so $cfg timeout 300 python bench.py --cams $C --points $P --no-cpu-baseline --no-tracking --no-global --no-local --steps 6 --warmup 1 --jac-reps 5 > $O/stamps_$i.txt 2>&1
+  env PTAM_HIP_LIB=$R/tools/_exp/schur_stamps_ab/libptam_hip.so $cfg timeout 300 python bench.py --full --cams $C --points $P --no-cpu-baseline --no-tracking --no-global --no-local --steps 6 --warmup 1 --jac-reps 5 > $O/stamps_$i.txt 2>&1
   echo "=== $cfg" | tee -a $O/fit.txt
   python3 tools/dev/schur_fit.py $O/stamps_$i.txt $F 2>&1 | grep -v "^(" | grep -A3 "per CU" | tee -a $O/fit.txt
   python3 tools/dev/schur_fit.py $O/stamps_$i.txt $F 2>&1 | grep "^(\|by XCD" > $O/cus_$i.txt

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "bundle" >
 tail -3 $O/pytest.txt
 for rep in 1 2; do
 for cfg in "$@"; do
-  env PTAM_HIP_LIB=$R/tools/_ab/libptam_hip.so $cfg timeout 300 python bench.py --no-cpu-baseline --no-tracking > $O/log.txt 2> $O/err.txt
+  env PTAM_HIP_LIB=$R/tools/_ab/libptam_hip.so $cfg timeout 300 python bench.py --full --no-cpu-baseline --no-tracking > $O/log.txt 2> $O/err.txt
   grep "two-phase" $O/err.txt | head -3
   python3 - "$cfg" <<PY | tee -a $O/out.txt
 import json, sys

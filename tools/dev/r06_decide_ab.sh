@@ -10,7 +10,7 @@ for rep in 1 2 3; do
 for sep in 0 1; do
   if [ $sep = 1 ]; then export PTAM_SEPARATE_FINALIZE=1; else unset PTAM_SEPARATE_FINALIZE; fi
   echo "separate_finalize=$sep: $(python tools/dev/r06_trial_times.py 12 2>&1 | head -1)" >> $OUT
-  timeout 300 python bench.py --no-cpu-baseline --no-tracking --no-global > /tmp/ab_log.txt 2>&1
+  timeout 300 python bench.py --full --no-cpu-baseline --no-tracking --no-global > /tmp/ab_log.txt 2>&1
   python3 - "$sep" >> $OUT <<PY
 import json, sys
 b = json.loads([l for l in open("/tmp/ab_log.txt") if l.startswith("{")][-1])

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/k7_trace
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/k7_trace -o t -- python $R/bench.py --no-cpu-baseline --no-tracking --no-global --no-local > /tmp/k7_trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/k7_trace -o t -- python $R/bench.py --full --no-cpu-baseline --no-tracking --no-global --no-local > /tmp/k7_trace.log 2>&1
 python3 - > $OUT/r06_k7_in_situ.txt <<PY
 import csv, glob, statistics
 f = glob.glob("/tmp/k7_trace/**/t_kernel_trace.csv", recursive=True)[0]

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/r06_lag_ab.txt
 : > $OUT
 for rep in 1 2; do
 for lag in "$@"; do
-  env PTAM_HIP_LIB=$R/tools/_ab/libptam_hip.so PTAM_SCHUR_LAG=$lag timeout 300 python bench.py --no-cpu-baseline --no-tracking > /tmp/ab_log.txt 2>&1
+  env PTAM_HIP_LIB=$R/tools/_ab/libptam_hip.so PTAM_SCHUR_LAG=$lag timeout 300 python bench.py --full --no-cpu-baseline --no-tracking > /tmp/ab_log.txt 2>&1
   python3 - "$lag" >> $OUT <<PY
 import json, sys
 b = json.loads([l for l in open("/tmp/ab_log.txt") if l.startswith("{")][-1])

@@ -10,7 +10,7 @@ for rep in 1 2 3; do
 for off in 0 1; do
   if [ $off = 1 ]; then export PTAM_NO_K7_PREFETCH=1; else unset PTAM_NO_K7_PREFETCH; fi
   echo "no_prefetch=$off: $(python tools/dev/r06_trial_times.py 12 2>&1 | head -1)" >> $OUT
-  timeout 300 python bench.py --no-cpu-baseline --no-tracking --no-global --no-local > /tmp/ab_log.txt 2>&1
+  timeout 300 python bench.py --full --no-cpu-baseline --no-tracking --no-global --no-local > /tmp/ab_log.txt 2>&1
   python3 - "$off" >> $OUT <<PY
 import json, sys
 b = json.loads([l for l in open("/tmp/ab_log.txt") if l.startswith("{")][-1])

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/r06_queue_ab.txt
 for rep in 1 2 3 4; do
 for one in 0 1; do
   if [ $one = 1 ]; then unset PTAM_TWO_QUEUES; else export PTAM_TWO_QUEUES=1; fi
-  timeout 300 python bench.py --no-cpu-baseline --no-tracking --no-global --no-local > /tmp/ab_log.txt 2>&1
+  timeout 300 python bench.py --full --no-cpu-baseline --no-tracking --no-global --no-local > /tmp/ab_log.txt 2>&1
   python3 - "$one" >> $OUT <<PY
 import json, sys
 b = json.loads([l for l in open("/tmp/ab_log.txt") if l.startswith("{")][-1])

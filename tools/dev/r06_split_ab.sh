@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/r06_split_ab.txt
 for rep in 1 2 3; do
 for gr in 0 1; do
   if [ $gr = 1 ]; then export PTAM_SPLIT_GREEDY=1; else unset PTAM_SPLIT_GREEDY; fi
-  timeout 300 python bench.py --no-cpu-baseline --no-tracking > /tmp/ab_log.txt 2>&1
+  timeout 300 python bench.py --full --no-cpu-baseline --no-tracking > /tmp/ab_log.txt 2>&1
   python3 - "$gr" >> $OUT <<PY
 import json, sys
 b = json.loads([l for l in open("/tmp/ab_log.txt") if l.startswith("{")][-1])

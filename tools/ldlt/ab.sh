@@ -18,7 +18,7 @@ done
 cd $R
 for v in default PTAM_LDLT_NO_CHAIN; do
   if [ $v = default ]; then unset PTAM_LDLT_NO_CHAIN; else export PTAM_LDLT_NO_CHAIN=1; fi
-  python bench.py --no-tracking --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  python bench.py --full --no-tracking --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read()); g=j['global_ba_single_gpu']; l=j['local_ba_config4']
 print('$v: headline %.0f trials/s, accepted trial %.1f us, solve %.1f us | config 5: %.0f trials/s, solve %.1f us | config 4: %.0f trials/s, solve %.1f us' % (j['value'], j['accepted_trial_us'], 1e3*j['kernel_ms_per_trial']['solve'], g['value'], 1e3*g['kernel_ms_per_trial']['solve'], l['value'], 1e3*l['kernel_ms_per_trial']['solve']))"
