@@ -184,7 +184,8 @@ int ptam_make_templates_batch(ptam_ctx* ctx, int n, const ptam_template_query* q
                               ptam_template_result* results);
 
 /* ---- MapMaker::AddPointEpipolar: the corner scan (src/MapMaker.cc:598-637)   --------------
- * The line geometry (:541-596) stays with the caller — it is per-candidate scalar code on poses and depth
+ * (ptam_add_map_points_epipolar below runs the whole of AddSomeMapPoints on the device; this batch call is its scan alone.)
+ * Here the line geometry (:541-596) stays with the caller — it is per-candidate scalar code on poses and depth
  * statistics; what moves to the device is the O(candidates x corners) part: MakeTemplateCoarseNoWarp of the
  * candidate in the source keyframe (:599, src/PatchFinder.cc:137-148), the in-plane corner table of the target
  * level (:604-614), the band / segment test of every target corner (:620-630) and ZMSSDAtPoint of the survivors
@@ -295,6 +296,71 @@ typedef struct {
 /* template_kept (nullable): 1 where the finder searched with the template it already had */
 int ptam_refind_pairs(ptam_ctx* ctx, ptam_refinder* finder, int n, const ptam_refind_pair* pairs, ptam_refind_result* out,
                       int32_t* template_kept);
+
+/* ---- MapMaker::AddSomeMapPoints (src/MapMaker.cc:448-457) for a list of levels: per visited level ThinCandidates (:415-441)
+ *      and AddPointEpipolar (:529-688) for every remaining candidate, all on the device (the rest of SURVEY §8f rank 4).
+ *      kSrc is the newest keyframe (:450), kTarget the caller's ClosestKeyFrame (:451).  Per visited level L:
+ *        - candidates: the maximal corners of ptam_make_keyframe_rest with Shi-Tomasi score > min_shi_tomasi, raster order
+ *          (src/KeyFrame.cc:66-76);
+ *        - thinning: a candidate is kept iff (irB - irC).mag_squared() >= 100 for every busy position irB at level L or L + 1,
+ *          irB = ir_rounded(v2RootPos / LevelScale(L)) (rounding half away from zero).  The busy positions are kSrc's
+ *          measurements (nLevel, v2RootPos) passed by the caller, plus the SRC_ROOT measurement of every point this call has
+ *          made at an earlier visited level (:679-683) — level 2 is thinned by the points just made at level 3;
+ *        - per kept candidate, in the reference's order: the ray and line geometry with its early returns (:541-596, fp64,
+ *          the reference's operation order without FMA contraction), the 0.001 push of a ray start behind kTarget (:573-574),
+ *          the LargestRadiusInImage test (:588-589), MakeTemplateCoarseNoWarp and the corner scan (:598-637, as
+ *          ptam_epipolar_search_batch), MakeSubPixTemplate + IterateSubPixToConvergence(kTarget, subpix_max_its) from
+ *          LevelZeroPos(vIR[nBest]) (:640-645, as ptam_subpix_batch), Triangulate (:171-189: smallest right singular vector of
+ *          the 4x4 system, v4[3] == 0 -> 1e-5) mapped to the world by kTarget^-1 (:649), the _NC vectors (:661-667) and
+ *          MapPoint::RefreshPixelVectors (src/Map.cc:40-65).
+ *      Points come out in visiting order of levels, then candidate order: the order of vpPoints / mqNewQueue, which
+ *      ReFindNewlyMade (:1046-1066) walks.  The thinned candidate list is NOT written back into kSrc: the reference never
+ *      reuses it (kSrc is always the newest keyframe, and its next keyframe becomes kSrc in turn).
+ *      Synchronous like the other batch calls: one host sync, at the end. */
+typedef struct {
+    double depth_mean, depth_sigma;  /* kSrc.dSceneDepthMean / Sigma: ptam_motion_model.scene_depth_mean / _sigma (Tracker.cc:692-696) */
+    double wiggle_scale;             /* MapMaker::mdWiggleScale (MapMaker.WiggleScale, 0.1) */
+    double min_shi_tomasi;           /* MapMaker.CandidateMinShiTomasiScore: 70 (src/KeyFrame.cc:63), 400 in config/settings.cfg:27 */
+    int32_t subpix_max_its;          /* IterateSubPixToConvergence(kTarget, 10) (:642) */
+    int32_t n_levels;                /* 1..4 */
+    int32_t levels[4];               /* visiting order: {3,0,1,2} AddKeyFrameFromTopOfQueue (:511-514), {0,3,1,2} InitFromStereo (:382-385) */
+} ptam_epipolar_opts;
+void ptam_epipolar_opts_default(ptam_epipolar_opts* o);   /* depth 1 +- 1, 0.1, 70, 10, {3,0,1,2} */
+
+typedef struct {
+    ptam_pvs_point point;            /* v3WorldPos, v3PixelRight_W, v3PixelDown_W: feeds ptam_tracker_update_map / refind as is */
+    double center_nc[3], one_right_nc[3], one_down_nc[3];   /* v3Center_NC, v3OneRightFromCenter_NC, v3OneDownFromCenter_NC
+                                                               (normalised); v3Normal_NC is (0,0,-1) */
+    double src_root_pos[2];          /* kSrc measurement (SRC_ROOT, bSubPix): v2RootPos = LevelZeroPos(irCenter, level) */
+    double target_pos[2];            /* kTarget measurement (SRC_EPIPOLAR) = Finder.GetSubPixPos() */
+    int32_t level;                   /* nSourceLevel = nLevel of both measurements */
+    int32_t center_x, center_y;      /* irCenter = candidate.irLevelPos */
+    int32_t candidate;               /* index into the level's candidates BEFORE thinning */
+    int32_t target_corner;           /* nBest in kTarget.aLevels[level].vCorners */
+    int32_t best_zmssd;              /* nBestZMSSD */
+} ptam_new_map_point;
+
+typedef struct {                     /* per visited level, one count per return path of AddPointEpipolar */
+    int32_t candidates;              /* vCandidates before ThinCandidates */
+    int32_t kept_after_thinning;
+    int32_t ray_rejected;            /* :569-572 facing backwards / ray end behind kTarget */
+    int32_t line_rejected;           /* :581-584 projected line too short, :588-589 line outside LargestRadiusInImage */
+    int32_t template_bad;            /* :600-601 */
+    int32_t no_match;                /* :636-637 nBest == -1 */
+    int32_t subpix_failed;           /* :643-644 */
+    int32_t made;
+} ptam_epipolar_level_stats;
+
+/* src_pose / target_pose: kSrc.se3CfromW, kTarget.se3CfromW.  busy (n_busy >= 0): kSrc.mMeasurements' nLevel (0..3) and
+ * v2RootPos (2 doubles each).  out: room for cap points; cap must be at least the sum of ptam_kf_rest_info over the visited
+ * levels, else PTAM_E_ARG and nothing is written.  stats (nullable): opts->n_levels entries, in visiting order.
+ * PTAM_E_STATE: src has had no ptam_make_keyframe_rest since its last ptam_make_keyframe_lite.  PTAM_E_ARG also for keyframes
+ * of another device, repeated or out-of-range levels, n_levels outside 1..4 and busy levels outside 0..3. */
+int ptam_add_map_points_epipolar(ptam_ctx* ctx, const ptam_kf* src, const double src_pose[12],
+                                 ptam_kf* target, const double target_pose[12], const ptam_epipolar_opts* opts,
+                                 int n_busy, const int32_t* busy_level, const double* busy_root_xy,
+                                 ptam_new_map_point* out, int cap, int32_t* n_out,
+                                 ptam_epipolar_level_stats* stats);
 
 /* ---- Tracker pose Gauss-Newton (src/Tracker.cc:613-643 driver, :928-1005 CalcPoseUpdate,
  *      include/Tracker.h:125-142 CalcJacobian/LinearUpdate) ---------------------------------------- */

@@ -245,6 +245,46 @@ private:
     Vec<2> mv2CoarsePos{0, 0}, mv2SubPixPos{0, 0};
 };
 
+// void MapMaker::AddSomeMapPoints(int nLevel)   src/MapMaker.cc:448-457, for every level of opts.levels in turn, in ONE device call
+// (ptam_add_map_points_epipolar; beside PatchFinder::EpipolarSearchBatch, whose corner scan it shares): ThinCandidates against
+// kSrc's measurements `busy` and the points made at earlier levels, then AddPointEpipolar for every kept candidate.  The new
+// points come back in the order the reference pushes them onto vpPoints / mqNewQueue; the map bookkeeping stays the caller's.
+struct BusyMeasurement {   // kSrc.mMeasurements: (nLevel, v2RootPos)
+    int nLevel;
+    Vec<2> v2RootPos;
+};
+inline std::vector<ptam_new_map_point> AddMapPointsEpipolar(Context& c, KeyFrame& kSrc, const SE3& se3Src, KeyFrame& kTarget,
+                                                           const SE3& se3Target, const ptam_epipolar_opts& opts,
+                                                           const std::vector<BusyMeasurement>& busy,
+                                                           std::vector<ptam_epipolar_level_stats>* stats = nullptr) {
+    int cap = 0;
+    for (int i = 0; i < opts.n_levels && i < PTAM_LEVELS; i++) {
+        int n = 0;
+        if (opts.levels[i] >= 0 && opts.levels[i] < PTAM_LEVELS)
+            check(ptam_kf_rest_info(c.handle(), kSrc.handle(), opts.levels[i], &n), "ptam_kf_rest_info");
+        cap += n;
+    }
+    std::vector<int32_t> lv(busy.size());
+    std::vector<double> xy(2 * busy.size());
+    for (size_t i = 0; i < busy.size(); i++) {
+        lv[i] = busy[i].nLevel;
+        xy[2 * i] = busy[i].v2RootPos[0];
+        xy[2 * i + 1] = busy[i].v2RootPos[1];
+    }
+    double ps[12], pt[12];
+    se3Src.to12(ps);
+    se3Target.to12(pt);
+    std::vector<ptam_new_map_point> out((size_t)cap);
+    std::vector<ptam_epipolar_level_stats> st(PTAM_LEVELS);
+    int32_t n = 0;
+    check(ptam_add_map_points_epipolar(c.handle(), kSrc.handle(), ps, kTarget.handle(), pt, &opts, (int)busy.size(), lv.data(), xy.data(),
+                                       out.data(), cap, &n, st.data()),
+          "ptam_add_map_points_epipolar");
+    out.resize((size_t)n);
+    if (stats) stats->assign(st.begin(), st.begin() + opts.n_levels);
+    return out;
+}
+
 // TrackMap's potentially-visible-set loop (src/Tracker.cc:453-478): TData.Project + GetProjectionDerivs
 // + Finder.CalcSearchLevelAndWarpMatrix for every map point, one launch.
 inline void TrackMapPVS(Context& c, const std::vector<ptam_pvs_point>& vMapPoints, const SE3& se3CamFromWorld,

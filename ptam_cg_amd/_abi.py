@@ -71,6 +71,23 @@ class PvsPoint(C.Structure):
     _fields_ = [("world", C.c_double * 3), ("pixel_right_w", C.c_double * 3), ("pixel_down_w", C.c_double * 3)]
 
 
+class EpipolarOpts(C.Structure):
+    """ptam_epipolar_opts (MapMaker::AddSomeMapPoints, src/MapMaker.cc:448-457)"""
+    _fields_ = [("depth_mean", C.c_double), ("depth_sigma", C.c_double), ("wiggle_scale", C.c_double), ("min_shi_tomasi", C.c_double),
+                ("subpix_max_its", C.c_int32), ("n_levels", C.c_int32), ("levels", C.c_int32 * 4)]
+
+
+class NewMapPoint(C.Structure):
+    _fields_ = [("point", PvsPoint), ("center_nc", C.c_double * 3), ("one_right_nc", C.c_double * 3), ("one_down_nc", C.c_double * 3),
+                ("src_root_pos", C.c_double * 2), ("target_pos", C.c_double * 2), ("level", C.c_int32), ("center_x", C.c_int32),
+                ("center_y", C.c_int32), ("candidate", C.c_int32), ("target_corner", C.c_int32), ("best_zmssd", C.c_int32)]
+
+
+class EpipolarLevelStats(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("candidates", "kept_after_thinning", "ray_rejected", "line_rejected", "template_bad",
+                                         "no_match", "subpix_failed", "made")]
+
+
 class PoseMeas(C.Structure):
     _fields_ = [("world", C.c_double * 3), ("found", C.c_double * 2), ("sqrt_inv_noise", C.c_double)]
 
@@ -181,6 +198,8 @@ PROTOTYPES = {
     "refinder_create": (_i, [_vp, C.POINTER(_vp)]),
     "refinder_destroy": (_i, [_vp]),
     "refind_pairs": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "epipolar_opts_default": (None, [C.POINTER(EpipolarOpts)]),
+    "add_map_points_epipolar": (_i, [_vp, _vp, _pd, _vp, _pd, C.POINTER(EpipolarOpts), _i, _vp, _vp, _vp, _i, C.POINTER(C.c_int32), _vp]),
     "pose_gn_state": (_i, [_vp, _i, _vp, _vp, _pd, _vp, _vp, _vp, _vp]),
     "trackmap_opts_default": (None, [_vp]),
     "tracker_create": (_i, [_vp, _i, _ppv]),

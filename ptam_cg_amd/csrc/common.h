@@ -82,6 +82,7 @@ void ba_preload_kernels();
 void solve_preload_kernels();
 void pose_preload_kernels();
 void patch_preload_kernels();
+void mapmaker_preload_kernels();
 void kf_preload_kernels();
 void pvs_preload_kernels();
 void trackmap_preload_kernels();

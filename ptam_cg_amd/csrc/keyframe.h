@@ -30,6 +30,7 @@ struct ptam_kf {
     int counts_valid;
     int n_max[PTAM_LEVELS];       // host copy, valid iff rest_valid
     int rest_valid;
+    int rest_made;                // a ptam_make_keyframe_rest since the last MakeKeyFrame_Lite (the candidates exist)
     size_t off_rest_clear, bytes_rest_clear;   // score maps + maximal-corner masks: zeroed per call
     // Level::vImplaneCorners (src/MapMaker.cc:605-614), built on first use by the epipolar search
     double2* implane[PTAM_LEVELS];

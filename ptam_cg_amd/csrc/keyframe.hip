@@ -322,6 +322,7 @@ void kf_lite_begin(ptam_kf* kf, const uint8_t* d_src, PyrArgs* a_out, int* gx, i
     *gy = (nby + 3) / 4;
     kf->counts_valid = 0;
     kf->rest_valid = 0;
+    kf->rest_made = 0;
 }
 void kf_launch_detect(ptam_kf* kf, hipStream_t stream) { hipLaunchKernelGGL(fast_detect_kernel, dim3(kf->n_blocks), dim3(256), 0, stream, kf->L); }
 
@@ -409,6 +410,7 @@ int ptam_make_keyframe_rest(ptam_ctx* ctx, ptam_kf* kf) {
     }
     HIP_TRY(hipGetLastError());
     kf->rest_valid = 0;
+    kf->rest_made = 1;
     return PTAM_OK;
 }
 
@@ -454,6 +456,7 @@ int ptam_kf_clone(ptam_ctx* ctx, const ptam_kf* src, ptam_kf** out) {
     HIP_TRY(hipMemcpyAsync(kf->base, src->base, src->bytes_total, hipMemcpyDeviceToDevice, ctx->stream));
     kf->counts_valid = 0;
     kf->rest_valid = 0;
+    kf->rest_made = src->rest_made;
     *out = kf;
     return PTAM_OK;
 }

@@ -113,16 +113,6 @@ __global__ void __launch_bounds__(256) make_templates_kernel(int n, const Templa
 // =================================================================================================
 // AddPointEpipolar: in-plane corner table and the corner scan (src/MapMaker.cc:598-637)
 // =================================================================================================
-// ATANCamera::UnProject (src/ATANCamera.cc:125-140)
-__device__ __forceinline__ void cam_unproject(const DevCam& c, double u, double v, double& x, double& y) {
-    const double dx = (u - c.cx) * c.inv_fx, dy = (v - c.cy) * c.inv_fy;
-    const double dr = sqrt(dx * dx + dy * dy);
-    const double rr = (c.w == 0.0) ? dr : tan(dr * c.w) * c.one_over_two_tan;   // invrtrans include/ATANCamera.h:152-157
-    const double f = dr > 0.01 ? rr / dr : 1.0;
-    x = f * dx;
-    y = f * dy;
-}
-
 // vv2Corners.push_back(imUnProj[ir(Level::LevelZeroPos(vIR[i], nLevel))])  :611-612
 __global__ void __launch_bounds__(256) implane_corners_kernel(DevCam cam, KfLevels L, int lev, double2* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -135,8 +125,7 @@ __global__ void __launch_bounds__(256) implane_corners_kernel(DevCam cam, KfLeve
     out[i] = make_double2(x, y);
 }
 
-// one wave per candidate: template = the 8x8 window of the source level (lane = pixel), then the target level's
-// corners 64 at a time through the band / segment test, the survivors scored in corner order
+// one wave per candidate: wave_epipolar_scan (patch_device.h)
 __global__ void __launch_bounds__(256) epipolar_search_kernel(KfLevels S, KfLevels T, int lev, const double2* __restrict__ implane,
                                                               int n, const ptam_epipolar_query* __restrict__ queries,
                                                               ptam_epipolar_result* __restrict__ results) {
@@ -145,64 +134,7 @@ __global__ void __launch_bounds__(256) epipolar_search_kernel(KfLevels S, KfLeve
     if (qi >= n) return;
     const ptam_epipolar_query q = queries[qi];
     ptam_epipolar_result res;
-    res.best = -1;
-    res.best_zmssd = PTAM_MAX_SSD + 1;
-    res.n_scored = 0;
-    res.template_bad = 0;
-    const int sw = S.w[lev], sh = S.h[lev];
-    // MakeTemplateCoarseNoWarp: in_image_with_border(irLevelPos, mnPatchSize / 2 + 1)
-    if (!(q.level_x >= 5 && q.level_y >= 5 && q.level_x < sw - 5 && q.level_y < sh - 5)) {
-        res.template_bad = 1;
-        if (lane == 0) results[qi] = res;
-        return;
-    }
-    const int Tp = S.im[lev][(size_t)(q.level_y - 4 + (lane >> 3)) * sw + (q.level_x - 4 + (lane & 7))];
-    const int tsum = wave_sum_i32(Tp), tsumsq = wave_sum_i32(Tp * Tp);
-    const unsigned T4 = wave_pack_template4(Tp, lane);
-    const int tw = T.w[lev], th = T.h[lev];
-    const uint8_t* im = T.im[lev];
-    const ptam_int2* corners = T.corners[lev];
-    const int nc = T.ncorners[lev];
-    int best = PTAM_MAX_SSD + 1, bi = -1, nsc = 0;
-    for (int base = 0; base < nc; base += 64) {
-        const int idx = base + lane;
-        bool pass = false;
-        ptam_int2 c = {0, 0};
-        if (idx < nc) {
-            const double2 v = implane[idx];
-            const double dd = q.norm_dist - (v.x * q.normal[0] + v.y * q.normal[1]);   // :623
-            const double al = v.x * q.along[0] + v.y * q.along[1];
-            pass = !(dd * dd > q.max_dist_sq) && !(al < q.min_len) && !(al > q.max_len);
-            c = corners[idx];
-        }
-        unsigned long long m = __ballot(pass);
-        while (m) {   // four candidates per pass (wave_zmssd4), judged in corner order
-            int cx[4] = {0, 0, 0, 0}, cy[4] = {0, 0, 0, 0}, bb[4] = {0, 0, 0, 0}, nn = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (m) {   // (wave-uniform)
-                    bb[k] = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    cx[k] = __builtin_amdgcn_readlane(c.x, bb[k]);
-                    cy[k] = __builtin_amdgcn_readlane(c.y, bb[k]);
-                    nn = k + 1;
-                }
-            const int ssd_l = wave_zmssd4(im, tw, th, cx, cy, nn, T4, tsum, tsumsq, lane);
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (k < nn) {
-                    const int ssd = __builtin_amdgcn_readlane(ssd_l, 16 * k + 15);
-                    nsc++;
-                    if (ssd < best) {
-                        best = ssd;
-                        bi = base + bb[k];
-                    }
-                }
-        }
-    }
-    res.best = bi;
-    res.best_zmssd = best;
-    res.n_scored = nsc;
+    wave_epipolar_scan(S, T, lev, implane, q, lane, res);
     if (lane == 0) results[qi] = res;
 }
 
@@ -227,6 +159,29 @@ int patch_launch_subpix_dev(ptam_ctx* ctx, const ptam_kf* kf, int n_cap, const p
     hipLaunchKernelGGL(subpix_kernel, dim3((n_cap + 3) / 4), dim3(256), 0, ctx->stream, kf->L, n_cap, (const ptam_subpix_query*)nullptr,
                        d_tmpl, d_sr, d_range, d_q, d_pr, max_its);
     HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
+// Level::vImplaneCorners of one level (track_internal.h)
+int kf_build_implane(ptam_ctx* ctx, ptam_kf* kf, int level) {
+    int rc = kf_fetch_counts(ctx, kf);
+    if (rc) return rc;
+    const int nc = kf->n_corners[level];
+    if (kf->implane_valid[level]) return PTAM_OK;
+    if (nc > kf->implane_cap[level]) {
+        HIP_TRY(ptam_stream_wait(ctx->stream));
+        if (kf->implane[level]) HIP_TRY(hipFree(kf->implane[level]));
+        kf->implane[level] = nullptr;
+        kf->implane_cap[level] = 0;
+        const int cap = nc + nc / 4 + 64;
+        HIP_TRY(hipMalloc((void**)&kf->implane[level], (size_t)cap * sizeof(double2)));
+        kf->implane_cap[level] = cap;
+    }
+    if (nc > 0)
+        hipLaunchKernelGGL(implane_corners_kernel, dim3((nc + 255) / 256), dim3(256), 0, ctx->stream, ctx->cam, kf->L, level,
+                           kf->implane[level]);
+    HIP_TRY(hipGetLastError());
+    kf->implane_valid[level] = 1;
     return PTAM_OK;
 }
 
@@ -348,28 +303,6 @@ int ptam_make_templates_batch(ptam_ctx* ctx, int n, const ptam_template_query* q
     HIP_TRY(hipMemcpyAsync(templates_out, d_t, bt, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(results, d_r, br, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ptam_stream_wait(ctx->stream));   // (jobs[] is pageable: the H2D copy above has been staged by now)
-    return PTAM_OK;
-}
-
-static int kf_build_implane(ptam_ctx* ctx, ptam_kf* kf, int level) {
-    int rc = kf_fetch_counts(ctx, kf);
-    if (rc) return rc;
-    const int nc = kf->n_corners[level];
-    if (kf->implane_valid[level]) return PTAM_OK;
-    if (nc > kf->implane_cap[level]) {
-        HIP_TRY(ptam_stream_wait(ctx->stream));
-        if (kf->implane[level]) HIP_TRY(hipFree(kf->implane[level]));
-        kf->implane[level] = nullptr;
-        kf->implane_cap[level] = 0;
-        const int cap = nc + nc / 4 + 64;
-        HIP_TRY(hipMalloc((void**)&kf->implane[level], (size_t)cap * sizeof(double2)));
-        kf->implane_cap[level] = cap;
-    }
-    if (nc > 0)
-        hipLaunchKernelGGL(implane_corners_kernel, dim3((nc + 255) / 256), dim3(256), 0, ctx->stream, ctx->cam, kf->L, level,
-                           kf->implane[level]);
-    HIP_TRY(hipGetLastError());
-    kf->implane_valid[level] = 1;
     return PTAM_OK;
 }
 

@@ -1,5 +1,6 @@
 // patch_device.h — the per-wave routines of the patch pipeline (one wave = one 8x8 patch, lane = pixel), shared by the batch
-// kernels of patch.hip and the fused search kernel of the resident TrackMap chain (trackmap.hip).
+// kernels of patch.hip, the fused search kernel of the resident TrackMap chain (trackmap.hip) and the epipolar point maker
+// (mapmaker.hip).
 #pragma once
 #include "common.h"
 #include "keyframe.h"
@@ -528,4 +529,80 @@ __device__ __forceinline__ int wave_make_template(const TemplateJob& jb, int lan
     r.sum_sq = s2;
     r.m2[0] = m00, r.m2[1] = m01, r.m2[2] = m10, r.m2[3] = m11;
     return v;
+}
+
+// ATANCamera::UnProject (src/ATANCamera.cc:125-140)
+__device__ __forceinline__ void cam_unproject(const DevCam& c, double u, double v, double& x, double& y) {
+    const double dx = (u - c.cx) * c.inv_fx, dy = (v - c.cy) * c.inv_fy;
+    const double dr = sqrt(dx * dx + dy * dy);
+    const double rr = (c.w == 0.0) ? dr : tan(dr * c.w) * c.one_over_two_tan;   // invrtrans include/ATANCamera.h:152-157
+    const double f = dr > 0.01 ? rr / dr : 1.0;
+    x = f * dx;
+    y = f * dy;
+}
+
+// MakeTemplateCoarseNoWarp + the corner scan of MapMaker::AddPointEpipolar (src/MapMaker.cc:599-637) by one wave, shared by
+// ptam_epipolar_search_batch (patch.hip) and ptam_add_map_points_epipolar (mapmaker.hip): template = the 8x8 window of the
+// source level around the candidate (lane = pixel; returned, for the sub-pixel step), then the target level's corners 64 at a
+// time through the band / segment test, the survivors scored in corner order.  Returns 0 in every lane when the template is bad.
+__device__ __forceinline__ int wave_epipolar_scan(const KfLevels& S, const KfLevels& T, int lev, const double2* __restrict__ implane,
+                                                  const ptam_epipolar_query& q, int lane, ptam_epipolar_result& res) {
+    res.best = -1;
+    res.best_zmssd = PTAM_MAX_SSD + 1;
+    res.n_scored = 0;
+    res.template_bad = 0;
+    const int sw = S.w[lev], sh = S.h[lev];
+    // MakeTemplateCoarseNoWarp: in_image_with_border(irLevelPos, mnPatchSize / 2 + 1)
+    if (!(q.level_x >= 5 && q.level_y >= 5 && q.level_x < sw - 5 && q.level_y < sh - 5)) {
+        res.template_bad = 1;
+        return 0;
+    }
+    const int Tp = S.im[lev][(size_t)(q.level_y - 4 + (lane >> 3)) * sw + (q.level_x - 4 + (lane & 7))];
+    const int tsum = wave_sum_i32(Tp), tsumsq = wave_sum_i32(Tp * Tp);
+    const unsigned T4 = wave_pack_template4(Tp, lane);
+    const int tw = T.w[lev], th = T.h[lev];
+    const uint8_t* im = T.im[lev];
+    const ptam_int2* corners = T.corners[lev];
+    const int nc = T.ncorners[lev];
+    int best = PTAM_MAX_SSD + 1, bi = -1, nsc = 0;
+    for (int base = 0; base < nc; base += 64) {
+        const int idx = base + lane;
+        bool pass = false;
+        ptam_int2 c = {0, 0};
+        if (idx < nc) {
+            const double2 v = implane[idx];
+            const double dd = q.norm_dist - (v.x * q.normal[0] + v.y * q.normal[1]);   // :623
+            const double al = v.x * q.along[0] + v.y * q.along[1];
+            pass = !(dd * dd > q.max_dist_sq) && !(al < q.min_len) && !(al > q.max_len);
+            c = corners[idx];
+        }
+        unsigned long long m = __ballot(pass);
+        while (m) {   // four candidates per pass (wave_zmssd4), judged in corner order
+            int cx[4] = {0, 0, 0, 0}, cy[4] = {0, 0, 0, 0}, bb[4] = {0, 0, 0, 0}, nn = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (m) {   // (wave-uniform)
+                    bb[k] = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    cx[k] = __builtin_amdgcn_readlane(c.x, bb[k]);
+                    cy[k] = __builtin_amdgcn_readlane(c.y, bb[k]);
+                    nn = k + 1;
+                }
+            const int ssd_l = wave_zmssd4(im, tw, th, cx, cy, nn, T4, tsum, tsumsq, lane);
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (k < nn) {
+                    const int ssd = __builtin_amdgcn_readlane(ssd_l, 16 * k + 15);
+                    nsc++;
+                    if (ssd < best) {
+                        best = ssd;
+                        bi = base + bb[k];
+                    }
+                }
+        }
+    }
+    res.best = bi;
+    res.best_zmssd = best;
+    res.n_scored = nsc;
+    return Tp;
 }

@@ -15,6 +15,8 @@ struct TemplateJob {          // device-side form of ptam_template_query (keyfra
 };
 
 // patch.hip
+// Level::vImplaneCorners of one level of kf, built on the context's stream unless cached (bImplaneCornersCached)
+int kf_build_implane(ptam_ctx* ctx, ptam_kf* kf, int level);
 int patch_launch_templates_dev(ptam_ctx* ctx, int n_cap, const TemplateJob* d_jobs, uint8_t* d_tmpl, ptam_template_result* d_res,
                                const int* d_range);
 // d_tres (nullable): a query whose template came out bad (Finder.TemplateBad(), src/Tracker.cc:876) is not searched

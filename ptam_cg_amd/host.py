@@ -10,8 +10,8 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (BaOpts, BaTrial, CamParams, GnOpts, Int2, MotionModel, PatchQuery, PatchResult, PoseMeas,
-                   PoseUpdateMeas, Projection)
+from ._abi import (BaOpts, BaTrial, CamParams, EpipolarLevelStats, EpipolarOpts, GnOpts, Int2, MotionModel, NewMapPoint, PatchQuery,
+                   PatchResult, PoseMeas, PoseUpdateMeas, Projection)
 
 # config/camera.cfg:7
 DEFAULT_CAMERA = (1.0803, 1.43987, 0.519983, 0.548655, 0.244943)
@@ -40,6 +40,13 @@ REFIND_RESULT_DT = np.dtype([("found", "<i4"), ("level", "<i4"), ("sub_pix", "<i
 REFIND_PAIR_DT = np.dtype([("kf", "<u8"), ("kf_pose", "<f8", (12,)), ("point", PVS_POINT_DT), ("source", TEMPLATE_QUERY_DT),
                            ("point_id", "<i8"), ("skip", "<i4"), ("pad_", "<i4")])
 assert REFIND_PAIR_DT.itemsize == 248
+NEW_MAP_POINT_DT = np.dtype([("point", PVS_POINT_DT), ("center_nc", "<f8", (3,)), ("one_right_nc", "<f8", (3,)),
+                             ("one_down_nc", "<f8", (3,)), ("src_root_pos", "<f8", (2,)), ("target_pos", "<f8", (2,)), ("level", "<i4"),
+                             ("center_x", "<i4"), ("center_y", "<i4"), ("candidate", "<i4"), ("target_corner", "<i4"), ("best_zmssd", "<i4")])
+EPIPOLAR_STATS_FIELDS = ("candidates", "kept_after_thinning", "ray_rejected", "line_rejected", "template_bad", "no_match",
+                         "subpix_failed", "made")
+EPIPOLAR_STATS_DT = np.dtype([(f, "<i4") for f in EPIPOLAR_STATS_FIELDS])
+assert NEW_MAP_POINT_DT.itemsize == C.sizeof(NewMapPoint) == 200 and EPIPOLAR_STATS_DT.itemsize == C.sizeof(EpipolarLevelStats)
 TRACKMAP_OPTS_DT = np.dtype([("try_coarse", "<i4"), ("coarse_min", "<u4"), ("coarse_max", "<u4"), ("coarse_range", "<u4"),
                              ("coarse_subpix_its", "<i4"), ("max_patches", "<i4"), ("estimator", "<i4"), ("pad_", "<i4")])
 TRACKMAP_RESULT_DT = np.dtype([("pose", "<f8", (12,)), ("did_coarse", "<i4"), ("n_pvs", "<i4", (4,)), ("attempted", "<i4", (4,)),
@@ -336,6 +343,53 @@ class PatchFinder:
         self.ctx._check(self.lib.zmssd_at_points(self.ctx.h, kf.h, level, len(points), _ptr(points),
                                                  _ptr(template), _ptr(out)), "zmssd_at_points")
         return out
+
+
+class MapMaker:
+    """MapMaker::AddSomeMapPoints (src/MapMaker.cc:448-457) for a list of levels in ONE device call
+    (ptam_add_map_points_epipolar): ThinCandidates + AddPointEpipolar of every kept candidate"""
+
+    def __init__(self, ctx):
+        self.ctx, self.lib = ctx, ctx.lib
+        if not self.lib.has("add_map_points_epipolar"):
+            raise PtamError("this library has no ptam_add_map_points_epipolar")
+
+    def opts(self, **kw):
+        o = EpipolarOpts()
+        self.lib.epipolar_opts_default(C.byref(o))
+        for k, v in kw.items():
+            if k == "levels":
+                o.n_levels = len(v)
+                for i, l in enumerate(v):
+                    o.levels[i] = l
+            else:
+                setattr(o, k, v)
+        return o
+
+    def AddSomeMapPoints(self, src_kf, src_pose, target_kf, target_pose, opts=None, busy_level=None, busy_root=None, cap=None):
+        """-> (points NEW_MAP_POINT_DT[n], stats EPIPOLAR_STATS_DT[n_levels]).  busy_level / busy_root: kSrc's measurements
+        (nLevel, v2RootPos).  cap: room for points (default: the sum of the visited levels' maximal corners)."""
+        opts = opts if opts is not None else self.opts()
+        lv = [opts.levels[i] for i in range(min(max(opts.n_levels, 0), _abi.LEVELS))]
+        if cap is None:
+            cap = 0
+            for l in lv:
+                n = C.c_int()
+                if 0 <= l < _abi.LEVELS:
+                    self.ctx._check(self.lib.kf_rest_info(self.ctx.h, src_kf.h, l, C.byref(n)), "kf_rest_info")
+                cap += n.value
+        bl = np.ascontiguousarray(busy_level if busy_level is not None else [], dtype=np.int32)
+        br = np.ascontiguousarray(busy_root if busy_root is not None else np.zeros((0, 2)), dtype=np.float64).reshape(-1, 2)
+        assert len(bl) == len(br)
+        sp = np.ascontiguousarray(src_pose, dtype=np.float64).reshape(12)
+        tp = np.ascontiguousarray(target_pose, dtype=np.float64).reshape(12)
+        out = np.zeros(max(cap, 1), dtype=NEW_MAP_POINT_DT)
+        stats = np.zeros(max(opts.n_levels, 1), dtype=EPIPOLAR_STATS_DT)
+        n = C.c_int32()
+        self.ctx._check(self.lib.add_map_points_epipolar(self.ctx.h, src_kf.h, _pd(sp), target_kf.h, _pd(tp), C.byref(opts), len(bl),
+                                                         _ptr(bl) if len(bl) else None, _ptr(br) if len(bl) else None, _ptr(out), cap,
+                                                         C.byref(n), _ptr(stats)), "add_map_points_epipolar")
+        return out[:n.value].copy(), stats[:opts.n_levels].copy()
 
 
 class DevBuf:
