@@ -652,6 +652,50 @@ int ptam_ba_kernel_time(const ptam_ba* ba, int kernel, double* total_ms, int* la
 int ptam_ba_prepare(ptam_ba* ba);
 /* (measurement-only entry points — the K7 launch bracket, the native frame drivers — are declared in ptam_hip_bench.h) */
 
+/* ---- MapMaker::BundleAdjustRecent / BundleAdjustAll / BundleAdjust (src/MapMaker.cc:768-933) as ONE call on flat map tables ----
+ *      The caller keeps its map and hands over: every keyframe's se3CfromW and bFixed (vpKeyFrames order, the newest last =
+ *      vpKeyFrames.back()), every point's v3WorldPos (vpPoints order) and the table of all keyframes' mMeasurements, sorted by
+ *      (kf, point) with no repeated pair — the vpKeyFrames x std::map<MapPoint*> walk of :871-882 with index order in place of
+ *      pointer order.  On the device:
+ *        RECENT (:788-828): KeyFrameLinearDist (:696-703: camera centres of se3CfromW.inverse(), fp64, the reference's operation
+ *          order without FMA contraction) from the newest keyframe to every other one, the 4 nearest by (distance, index)
+ *          (partial_sort, :711-730; ties by index where the reference breaks them by KeyFrame*); adjust set = the newest
+ *          keyframe + the non-fixed ones of the 4; points = every point an adjust keyframe measures; fixed set = every other
+ *          keyframe that measures one of them.  A map of fewer than 8 keyframes: ran = 0 and nothing else happens (:790-793).
+ *        ALL (:768-783): adjust = the non-fixed keyframes, fixed = the fixed ones, points = all points.
+ *        Bundle order (:851-882): adjust cameras ascending by kf with their own bFixed, then the fixed cameras ascending
+ *          (fixed = 1), the points ascending, the measurements in table order with sigma^2 = LevelScale(level)^2.
+ *      Compute(abort_flag) runs with *opts as ptam_ba_compute does.  accepted > 0: the adjusted points and the poses of every
+ *      bundle camera are written into points3 / kf_poses12 (:895-904); otherwise the tables are not touched.
+ *      Outliers in GetOutlierMeasurements order (src/Bundle.cc:540, :623) with the routing of :916-932: GoodMeasCount starts as
+ *      the point's number of table rows; <= 2 or SRC_ROOT -> POINT_BAD (count unchanged), else FAILURE_QUEUE for TRACKER /
+ *      EPIPOLAR and NEVER_RETRY for the other sources, and the point's count drops by one.  The caller applies the actions
+ *      (bBad, mvFailureQueue, sNeverRetryKFs, the erase from mMeasurements / sMeasurementKFs); the call erases nothing.
+ *      PTAM_E_ARG, with nothing written: a table row out of order or repeated, an index out of range, a level outside 0..3,
+ *      a source outside 0..4, outliers != NULL with outlier_cap < n_meas.  Single device only (no communicator).
+ *      Synchronous: one host wait after the selection (sizes), those of Compute(), one at the end. */
+typedef struct {
+    int32_t kf, point;        /* index into the keyframe / point tables */
+    int32_t level;            /* Measurement::nLevel 0..3 */
+    int32_t source;           /* Measurement::Source (include/KeyFrame.h:50): TRACKER, REFIND, ROOT, TRAIL, EPIPOLAR = 0..4 */
+    double root_pos[2];       /* Measurement::v2RootPos */
+} ptam_map_meas;
+enum { PTAM_MAP_BA_ALL = 0, PTAM_MAP_BA_RECENT = 1 };
+enum { PTAM_MAP_SRC_TRACKER = 0, PTAM_MAP_SRC_REFIND = 1, PTAM_MAP_SRC_ROOT = 2, PTAM_MAP_SRC_TRAIL = 3, PTAM_MAP_SRC_EPIPOLAR = 4 };
+enum { PTAM_MAP_OUT_POINT_BAD = 1, PTAM_MAP_OUT_FAILURE_QUEUE = 2, PTAM_MAP_OUT_NEVER_RETRY = 3 };
+typedef struct { int32_t point, kf, action, meas; } ptam_map_outlier;   /* meas = row of the table */
+typedef struct {
+    int32_t ran;              /* 0: RECENT on a map of < 8 keyframes, nothing else happened */
+    int32_t accepted;         /* Compute()'s mnAccepted */
+    int32_t converged;        /* Bundle::Converged() */
+    int32_t n_adjust, n_fixed, n_points, n_meas, n_outliers;   /* the bundle's cameras (adjust set, fixed set), points, measurements */
+} ptam_map_ba_result;
+/* cam_kf (nullable, room for n_kf): bundle camera id -> keyframe; point_ids (nullable, room for n_points): bundle point id -> point */
+int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, int n_kf, double* kf_poses12, const uint8_t* kf_fixed,
+                           int n_points, double* points3, int n_meas, const ptam_map_meas* meas,
+                           const volatile unsigned char* abort_flag, ptam_map_ba_result* res, ptam_map_outlier* outliers,
+                           int outlier_cap, int32_t* cam_kf, int32_t* point_ids);
+
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,
  * ordered on `stream` (hipStream_t).  Return 0 on success. */

@@ -285,6 +285,35 @@ inline std::vector<ptam_new_map_point> AddMapPointsEpipolar(Context& c, KeyFrame
     return out;
 }
 
+// void MapMaker::BundleAdjustRecent() / BundleAdjustAll()   src/MapMaker.cc:768-933, set choice + Bundle + write-back in ONE device
+// call (ptam_map_bundle_adjust) on the map as flat tables: vKFPoses / vFixed in vpKeyFrames order (the newest last), vPoints in
+// vpPoints order, vMeas = every keyframe's mMeasurements sorted by (kf, point).  With accepted > 0 the poses and points are updated
+// in place; the outliers come back in GetOutlierMeasurements order with the action the caller applies (ptam_hip.h).
+struct MapBundleAdjustResult {
+    ptam_map_ba_result result;
+    std::vector<ptam_map_outlier> outliers;
+    std::vector<int32_t> cam_kf, point_ids;   // bundle camera / point id -> table index
+};
+static_assert(sizeof(SE3) == 96 && sizeof(Vec<3>) == 24, "tables are handed over as flat doubles");
+inline MapBundleAdjustResult MapBundleAdjust(Context& c, int mode, std::vector<SE3>& vKFPoses, const std::vector<uint8_t>& vFixed,
+                                             std::vector<Vec<3>>& vPoints, const std::vector<ptam_map_meas>& vMeas,
+                                             bool* pbAbortSignal = nullptr, const ptam_ba_opts* opts = nullptr) {
+    if (vFixed.size() != vKFPoses.size()) throw std::runtime_error("MapBundleAdjust: one bFixed per keyframe");
+    MapBundleAdjustResult r{};
+    r.outliers.resize(vMeas.size());
+    r.cam_kf.resize(vKFPoses.size());
+    r.point_ids.resize(vPoints.size());
+    check(ptam_map_bundle_adjust(c.handle(), opts, mode, (int)vKFPoses.size(), reinterpret_cast<double*>(vKFPoses.data()), vFixed.data(),
+                                 (int)vPoints.size(), reinterpret_cast<double*>(vPoints.data()), (int)vMeas.size(), vMeas.data(),
+                                 reinterpret_cast<const volatile unsigned char*>(pbAbortSignal), &r.result, r.outliers.data(),
+                                 (int)vMeas.size(), r.cam_kf.data(), r.point_ids.data()),
+          "ptam_map_bundle_adjust");
+    r.outliers.resize((size_t)r.result.n_outliers);
+    r.cam_kf.resize((size_t)(r.result.n_adjust + r.result.n_fixed));
+    r.point_ids.resize((size_t)r.result.n_points);
+    return r;
+}
+
 // TrackMap's potentially-visible-set loop (src/Tracker.cc:453-478): TData.Project + GetProjectionDerivs
 // + Finder.CalcSearchLevelAndWarpMatrix for every map point, one launch.
 inline void TrackMapPVS(Context& c, const std::vector<ptam_pvs_point>& vMapPoints, const SE3& se3CamFromWorld,

@@ -123,6 +123,16 @@ class BaTrial(C.Structure):
                 ("accepted", C.c_int32)]
 
 
+MAP_BA_ALL, MAP_BA_RECENT = 0, 1
+SRC_TRACKER, SRC_REFIND, SRC_ROOT, SRC_TRAIL, SRC_EPIPOLAR = range(5)   # Measurement::Source, include/KeyFrame.h:50
+OUT_POINT_BAD, OUT_FAILURE_QUEUE, OUT_NEVER_RETRY = 1, 2, 3
+
+
+class MapBaResult(C.Structure):
+    """ptam_map_ba_result (MapMaker::BundleAdjust, src/MapMaker.cc:838-933)"""
+    _fields_ = [(f, C.c_int32) for f in ("ran", "accepted", "converged", "n_adjust", "n_fixed", "n_points", "n_meas", "n_outliers")]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p)
 
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
@@ -226,6 +236,7 @@ PROTOTYPES = {
     "ba_schur_index_map": (_i, [_i, _vp, _i]),
     "ba_debug_lists": (_i, [_vp, _i, _vp, C.c_size_t]),
     "ba_set_comm": (_i, [_vp, _i, _i, ALLREDUCE_FN, _vp]),
+    "map_bundle_adjust": (_i, [_vp, C.POINTER(BaOpts), _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(MapBaResult), _vp, _i, _vp, _vp]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

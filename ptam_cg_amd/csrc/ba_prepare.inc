@@ -84,19 +84,7 @@ struct PrepDev {
     int* h_pt_orig;
 };
 
-// The measurements as they are added: chunks of MS_CH = 32 768, each 1 MB = [cam int32 x MS_CH | point int32 x MS_CH | found
-// double2 x MS_CH | sigma^2 double x MS_CH] — the same layout in pinned host memory and on the device, so a chunk goes up as ONE
-// copy the moment it is full, while the host is still adding the next (sigma^2 as given to AddMeas: dSqrtInvNoise = sqrt(1 / sigma^2),
-// src/Bundle.cc:91, is formed when the measurements are sorted).
-#define MS_LOG 15
-#define MS_CH (1 << MS_LOG)
-#define MS_CH_BYTES ((size_t)MS_CH * 32)
-template <class B>
-__host__ __device__ __forceinline__ B* ms_chunk(B* base, size_t i) { return base + (i >> MS_LOG) * MS_CH_BYTES; }
-__host__ __device__ __forceinline__ const int& ms_cam(const char* base, size_t i) { return ((const int*)ms_chunk(base, i))[i & (MS_CH - 1)]; }
-__host__ __device__ __forceinline__ const int& ms_pt(const char* base, size_t i) { return ((const int*)(ms_chunk(base, i) + (size_t)MS_CH * 4))[i & (MS_CH - 1)]; }
-__host__ __device__ __forceinline__ const double2& ms_found(const char* base, size_t i) { return ((const double2*)(ms_chunk(base, i) + (size_t)MS_CH * 8))[i & (MS_CH - 1)]; }
-__host__ __device__ __forceinline__ const double& ms_sig(const char* base, size_t i) { return ((const double*)(ms_chunk(base, i) + (size_t)MS_CH * 24))[i & (MS_CH - 1)]; }
+// (the raw measurement chunks, MS_CH / ms_cam ..., are laid out in bundle.h)
 
 __device__ __forceinline__ void prep_pair_ab(int pr, int& a, int& b) {
     a = (int)((sqrt(8.0 * pr + 1.0) - 1.0) * 0.5);

@@ -186,6 +186,39 @@ __host__ __device__ __forceinline__ int se_band(const BaDev& d) {
 }
 __host__ __device__ __forceinline__ double* se_E(const BaDev& d) { return d.SE + se_size(d.npad / SOLVE_NB, se_band(d)); }
 
+// The measurements as they are added: chunks of MS_CH = 32 768, each 1 MB = [cam int32 x MS_CH | point int32 x MS_CH | found
+// double2 x MS_CH | sigma^2 double x MS_CH] — the same layout in pinned host memory and on the device, so a chunk goes up as ONE
+// copy the moment it is full, while the host is still adding the next (sigma^2 as given to AddMeas: dSqrtInvNoise = sqrt(1 / sigma^2),
+// src/Bundle.cc:91, is formed when the measurements are sorted).
+#define MS_LOG 15
+#define MS_CH (1 << MS_LOG)
+#define MS_CH_BYTES ((size_t)MS_CH * 32)
+template <class B>
+__host__ __device__ __forceinline__ B* ms_chunk(B* base, size_t i) { return base + (i >> MS_LOG) * MS_CH_BYTES; }
+__host__ __device__ __forceinline__ const int& ms_cam(const char* base, size_t i) { return ((const int*)ms_chunk(base, i))[i & (MS_CH - 1)]; }
+__host__ __device__ __forceinline__ const int& ms_pt(const char* base, size_t i) { return ((const int*)(ms_chunk(base, i) + (size_t)MS_CH * 4))[i & (MS_CH - 1)]; }
+__host__ __device__ __forceinline__ const double2& ms_found(const char* base, size_t i) { return ((const double2*)(ms_chunk(base, i) + (size_t)MS_CH * 8))[i & (MS_CH - 1)]; }
+__host__ __device__ __forceinline__ const double& ms_sig(const char* base, size_t i) { return ((const double*)(ms_chunk(base, i) + (size_t)MS_CH * 24))[i & (MS_CH - 1)]; }
+
+// bundle.hip: a bundle whose inputs the caller's kernels write on the device (mapba.hip, ptam_map_bundle_adjust).
+//   ba_dev_meas_chunks  device MeasStore chunks for up to n_max measurements (fill them in the layout above)
+//   ba_dev_ingest       C cameras (host, O(C)), P points in the device array d_pts (read by prepare, device to device) and the
+//                       first M measurements of the chunks; then ptam_ba_compute runs as usual, ONCE
+//   ba_dev_result       after Compute(): the device state the results are read from
+int ba_dev_meas_chunks(ptam_ba* ba, size_t n_max, char** d_chunks);
+int ba_dev_ingest(ptam_ba* ba, int C, const double* poses12, const uint8_t* fixed, int P, const double* d_pts, int M);
+struct BaDevResult {
+    const double* pose;     // [C][12] final poses (bundle camera order)
+    const double* pt;       // [P_live][3] final positions of the points with a live measurement
+    const int* pt_orig;     // [P_live] the bundle point id of each
+    int C, P_live;
+    const int* outliers;    // [n_out] measurement indices (insertion order) in purge order
+    int n_out;
+    const int* step_end;    // host: [n_steps] outliers purged up to the end of each LM step (cumulative)
+    int n_steps;
+};
+int ba_dev_result(const ptam_ba* ba, BaDevResult* r);
+
 // solve.hip
 int ba_solve(ptam_ctx* ctx, BaDev& d, int cur);   // also writes the trial poses pose[cur^1] and |da|^2
 #define CH_SPIN_DEFAULT (1 << 18)   // BaDev::spin_limit unless PTAM_CH_SPIN_LIMIT says otherwise (ldlt_chain.inc)

@@ -239,6 +239,8 @@ struct ptam_ba {
     int k7_threads = BA_CHUNK;
     bool k7_loop = false;
     std::vector<int> pt_orig;       // device point id -> original point id (the points with a live measurement, ascending)
+    int* d_pt_orig = nullptr;       // the same on the device (a piece of the block)
+    const double* pts_dev = nullptr;   // ba_dev_ingest: the points are already on the device (pts is then sized but not filled)
     // gather buffers (sharded mode)
     double* d_gather = nullptr;
     size_t gather_cap = 0;
@@ -689,7 +691,10 @@ static int ba_prepare_impl(ptam_ba* ba) {
         std::memcpy(hp + h_dead, ba->m_dead.data(), (size_t)Mall);
         UP(base + o_rdead, hp + h_dead, (size_t)Mall);
     }
-    UP(base + o_ptsraw, ba->pts.data(), (size_t)P_all * 24);
+    if (ba->pts_dev) {
+        if (P_all > 0) HIP_TRY(hipMemcpyAsync(base + o_ptsraw, ba->pts_dev, (size_t)P_all * 24, hipMemcpyDeviceToDevice, ctx->stream));
+    } else
+        UP(base + o_ptsraw, ba->pts.data(), (size_t)P_all * 24);
     PrepDev q;
     std::memset(&q, 0, sizeof q);
     q.C = C, q.F = F, q.P_all = P_all, q.Mall = Mall, q.M = M;
@@ -701,6 +706,7 @@ static int ba_prepare_impl(ptam_ba* ba) {
     q.start = (int*)(base + o_start);
     q.dense_of = (int*)(base + o_denseof);
     q.pt_orig = (int*)(base + o_ptorig);
+    ba->d_pt_orig = q.pt_orig;
     q.arr = (int*)(base + o_arr);
     q.tmp_i = (int*)(base + o_tmpi);
     q.tmp_key = (int*)(base + o_tmpkey);
@@ -1305,6 +1311,44 @@ static void ba_finish_outliers(ptam_ba* ba) {
     }
     ba->raw_out_done = begin;
     ba->raw_out_ends.clear();
+}
+
+// ---- a bundle whose inputs are already on the device (mapba.hip) ----------------------------------------------------------------
+// The measurements go straight into the device chunks of the MeasStore and the points stay in a device array; the host mirrors
+// they replace (ms.h, the contents of pts) are not filled.  Such a bundle is built, computed once and read through ba_dev_result:
+// Get*, GetOutlierMeasurements and a second Compute() would read those mirrors, and are not called on it.
+int ba_dev_meas_chunks(ptam_ba* ba, size_t n_max, char** d_chunks) {
+    if (int rc = ba->ms.reserve_dev((n_max + MS_CH - 1) >> MS_LOG)) return rc;
+    *d_chunks = ba->ms.d;
+    return PTAM_OK;
+}
+int ba_dev_ingest(ptam_ba* ba, int C, const double* poses12, const uint8_t* fixed, int P, const double* d_pts, int M) {
+    ba->cam_pose.assign(poses12, poses12 + (size_t)12 * C);
+    ba->cam_fixed.assign(fixed, fixed + C);
+    ba->pts.n = 0;
+    if (int rc = ba->pts.reserve((size_t)3 * P)) return rc;
+    ba->pts.n = (size_t)3 * P;   // (Compute()'s read-back writes the adjusted points here)
+    ba->pts_dev = d_pts;
+    ba->ms.n = (size_t)M;
+    ba->ms.up_chunks = ((size_t)M + MS_CH - 1) >> MS_LOG;   // written on the device: nothing to upload
+    ba->m_dead.assign((size_t)M, 0);
+    ba->n_dead = 0;
+    ba->prepared = false;
+    return PTAM_OK;
+}
+int ba_dev_result(const ptam_ba* ba, BaDevResult* r) {
+    if (!ba->prepared && ba->raw_out.empty()) return PTAM_E_STATE;
+    const BaDev& d = ba->d;
+    r->pose = d.pose[ba->cur];
+    r->pt = d.pt[ba->cur];
+    r->pt_orig = ba->d_pt_orig;
+    r->C = d.C;
+    r->P_live = d.P;
+    r->outliers = d.outliers;
+    r->n_out = (int)ba->raw_out.size();
+    r->step_end = ba->raw_out_ends.data();
+    r->n_steps = (int)ba->raw_out_ends.size();
+    return PTAM_OK;
 }
 
 extern "C" {

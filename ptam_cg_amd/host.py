@@ -392,6 +392,37 @@ class MapMaker:
         return out[:n.value].copy(), stats[:opts.n_levels].copy()
 
 
+MAP_MEAS_DT = np.dtype([("kf", "<i4"), ("point", "<i4"), ("level", "<i4"), ("source", "<i4"), ("root_pos", "<f8", (2,))])
+MAP_OUTLIER_DT = np.dtype([("point", "<i4"), ("kf", "<i4"), ("action", "<i4"), ("meas", "<i4")])
+
+
+def map_bundle_adjust(ctx, mode, poses, fixed, points, meas, abort=None, **ba_opts):
+    """MapMaker::BundleAdjustRecent (mode _abi.MAP_BA_RECENT) / BundleAdjustAll (_abi.MAP_BA_ALL) in ONE device call
+    (ptam_map_bundle_adjust, src/MapMaker.cc:768-933) on the map tables: poses (K, 12) se3CfromW with the newest keyframe last,
+    fixed (K,) bFixed, points (N, 3), meas MAP_MEAS_DT sorted by (kf, point).  The inputs are not modified; -> dict with the
+    result counts, the tables after the call ("poses", "points"), "outliers" (MAP_OUTLIER_DT, GetOutlierMeasurements order,
+    with the action the host applies) and the id maps "cam_kf" / "point_ids" (bundle id -> table index)."""
+    o = BaOpts()
+    ctx.lib.ba_opts_default(C.byref(o))
+    for k, v in ba_opts.items():
+        setattr(o, k, v)
+    poses = np.array(poses, dtype=np.float64).reshape(-1, 12)
+    points = np.array(points, dtype=np.float64).reshape(-1, 3)
+    fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+    meas = np.ascontiguousarray(meas, dtype=MAP_MEAS_DT)
+    K, N, M = len(poses), len(points), len(meas)
+    res = _abi.MapBaResult()
+    out = np.zeros(max(M, 1), MAP_OUTLIER_DT)
+    cam_kf = np.zeros(max(K, 1), np.int32)
+    point_ids = np.zeros(max(N, 1), np.int32)
+    ctx._check(ctx.lib.map_bundle_adjust(ctx.h, C.byref(o), int(mode), K, _ptr(poses), _ptr(fixed), N, _ptr(points), M, _ptr(meas),
+                                         _ptr(abort), C.byref(res), _ptr(out), M, _ptr(cam_kf), _ptr(point_ids)), "map_bundle_adjust")
+    d = {f: getattr(res, f) for f, _ in _abi.MapBaResult._fields_}
+    d.update(poses=poses, points=points, outliers=out[:res.n_outliers].copy(), cam_kf=cam_kf[:res.n_adjust + res.n_fixed].copy(),
+             point_ids=point_ids[:res.n_points].copy())
+    return d
+
+
 class DevBuf:
     """A device allocation of the context (ptam_dev_alloc / upload / download / free)."""
 
