@@ -200,6 +200,16 @@ __host__ __device__ __forceinline__ const int& ms_pt(const char* base, size_t i)
 __host__ __device__ __forceinline__ const double2& ms_found(const char* base, size_t i) { return ((const double2*)(ms_chunk(base, i) + (size_t)MS_CH * 8))[i & (MS_CH - 1)]; }
 __host__ __device__ __forceinline__ const double& ms_sig(const char* base, size_t i) { return ((const double*)(ms_chunk(base, i) + (size_t)MS_CH * 24))[i & (MS_CH - 1)]; }
 
+// carves one allocation into 256-byte aligned pieces: take() returns the piece's offset, `off` ends as the size of the whole
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
 // bundle.hip: a bundle whose inputs the caller's kernels write on the device (mapba.hip, ptam_map_bundle_adjust).
 //   ba_dev_meas_chunks  device MeasStore chunks for up to n_max measurements (fill them in the layout above)
 //   ba_dev_ingest       C cameras (host, O(C)), P points in the device array d_pts (read by prepare, device to device) and the

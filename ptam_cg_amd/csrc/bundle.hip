@@ -23,8 +23,6 @@
 #include <chrono>
 #include <climits>
 #include <atomic>
-#include <map>
-#include <mutex>
 #include <numeric>
 #include <utility>
 
@@ -127,7 +125,12 @@ struct MeasStore {
             nbytes = chunks * MS_CH_BYTES;
         }
         if (n) std::memcpy(np, h, ((n + MS_CH - 1) >> MS_LOG) * MS_CH_BYTES);
-        if (in_flight) HIP_TRY(ptam_stream_wait(ctx->stream));   // (copies out of the old chunks)
+        if (in_flight && ptam_stream_wait(ctx->stream) != hipSuccess) {   // (copies out of the old chunks)
+            void* drop = ctx_cache_give(ctx->pin_cache, CTX_NCACHE(ctx->pin_cache), np, nbytes);
+            if (drop) hipHostFree(drop);
+            ptam_set_error("the device queue failed under a growing measurement store");
+            return PTAM_E_HIP;
+        }
         in_flight = false;
         release_host();
         h = (char*)np;
@@ -284,61 +287,83 @@ static void ba_free_device(ptam_ba* ba) {
     ba->prepared = false;
 }
 
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
+// digest the purged-measurement indices of finished Compute() calls: per LM step sorted by insertion index, appended
+// to the (point, camera) list, and the measurements marked erased for the next prepare
+static void ba_finish_outliers(ptam_ba* ba) {
+    int begin = ba->raw_out_done;
+    for (size_t k = 0; k < ba->raw_out_ends.size(); k++) {
+        const int end = ba->raw_out_ends[k];
+        if (end <= begin) continue;
+        std::sort(ba->raw_out.begin() + begin, ba->raw_out.begin() + end);
+        for (int i = begin; i < end; i++) {
+            const int o = ba->raw_out[i];
+            ba->outliers.push_back(std::make_pair(ba->ms.pt((size_t)o), ba->ms.cam((size_t)o)));
+            if (!ba->m_dead[o]) ba->n_dead++;
+            ba->m_dead[o] = 1;
+        }
+        begin = end;
     }
-};
+    ba->raw_out_done = begin;
+    ba->raw_out_ends.clear();
+}
 
-static void ba_finish_outliers(ptam_ba* ba);
-// Wait for a stamp a kernel writes into host-mapped memory behind its results (ptam_stream_wait sleeps on an interrupt: up to
-// milliseconds to wake up); every now and then ask the runtime whether the stream died instead.
-static int ba_wait_stamp(ptam_ctx* ctx, volatile unsigned long long* slot, unsigned long long seq) {
-    unsigned spins = 0;
-    while (*slot != seq) {
-        if (++spins == 100000) {
-            spins = 0;
-            const hipError_t q = hipStreamQuery(ctx->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) {
-                ptam_set_error("the device queue failed while the bundle was being prepared: %s", hipGetErrorString(q));
-                return PTAM_E_HIP;
-            }
-            if (q == hipSuccess && *slot != seq) {
-                ptam_set_error("bundle prepare: the queue drained without its stamp");
-                return PTAM_E_HIP;
-            }
+// The PTAM_DEBUG_* diagnostics (they only print), read once per process.
+struct BaDebug { bool wait, stall, trial_times, select, solve; };
+static const BaDebug& ba_debug() {
+    static const BaDebug d = {getenv("PTAM_DEBUG_WAIT") != nullptr, getenv("PTAM_DEBUG_STALL") != nullptr, getenv("PTAM_DEBUG_TRIAL_TIMES") != nullptr,
+                              getenv("PTAM_DEBUG_SELECT") != nullptr, getenv("PTAM_DEBUG_SOLVE") != nullptr};
+    return d;
+}
+
+#include "ba_debug_host.inc"
+
+// Wait until arrived() holds for words a kernel writes into host-mapped memory behind its results (ptam_stream_wait sleeps on an
+// interrupt: up to milliseconds to wake up); every 100 000 looks ask the runtime whether the queue died instead.  A queue that has
+// drained without the words gets 50 more polls, then it is a logic error, not a wait.  report(drained): PTAM_DEBUG_WAIT=1, every
+// 100th poll.
+template <class Arrived, class Report>
+static int ba_wait_mapped(ptam_ctx* ctx, const char* what, Arrived arrived, Report report) {
+    unsigned spins = 0, polls = 0, idle_polls = 0;
+    while (!arrived()) {
+        if (++spins < 100000) continue;
+        spins = 0;
+        const hipError_t q = hipStreamQuery(ctx->stream);
+        if (q != hipSuccess && q != hipErrorNotReady) {
+            ptam_set_error("the device queue failed while the host waited for %s: %s", what, hipGetErrorString(q));
+            return PTAM_E_HIP;
+        }
+        if ((++polls % 100) == 0 && ba_debug().wait) report(q == hipSuccess);
+        if (q == hipSuccess && !arrived() && ++idle_polls > 50) {
+            ptam_set_error("the device queue drained and %s never arrived", what);
+            return PTAM_E_STATE;
         }
     }
-    (void)hipGetLastError();   // (hipErrorNotReady is sticky in the last-error slot)
+    if (polls) (void)hipGetLastError();   // (the runtime was asked: hipErrorNotReady is sticky in the last-error slot)
     std::atomic_thread_fence(std::memory_order_acquire);
     return PTAM_OK;
 }
+static int ba_wait_stamp(ptam_ctx* ctx, volatile unsigned long long* slot, unsigned long long seq, const char* what) {
+    return ba_wait_mapped(ctx, what, [&] { return *slot == seq; }, [](bool) {});
+}
 
-// launch shape of K7 for (threads, LDS bytes): asked of the runtime once per process and shape (each query is 10 - 40 us)
-static int ba_k7_occupancy(const void* k7, int threads, size_t smem, int* per_cu) {
-    struct Key {
-        const void* f;
-        int t;
-        size_t s;
-        bool operator<(const Key& o) const { return f != o.f ? f < o.f : (t != o.t ? t < o.t : s < o.s); }
-    };
-    static std::mutex mu;
-    static std::map<Key, std::pair<int, int>> known;
-    std::lock_guard<std::mutex> lock(mu);
-    const Key key{k7, threads, smem};
-    auto it = known.find(key);
-    if (it == known.end()) {
-        int rc = PTAM_OK, n = 0;
-        if (smem > 64 * 1024 && hipFuncSetAttribute(k7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) rc = PTAM_E_HIP;
-        if (!rc && hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k7, threads, smem) != hipSuccess) rc = PTAM_E_HIP;
-        if (rc) (void)hipGetLastError();
-        it = known.emplace(key, std::make_pair(rc, n)).first;
+// launch shape of K7 for (threads, LDS bytes): asked of the runtime once per context and shape (each query is 10 - 40 us; the
+// opt-in to more than 64 KB of LDS belongs to the device, so a table of the process would leave a second device without it)
+static int ba_k7_occupancy(ptam_ctx* ctx, const void* k7, int threads, size_t smem, int* per_cu) {
+    const unsigned n_known = std::min<unsigned>(ctx->n_k7_shapes, CTX_NCACHE(ctx->k7_shapes));
+    for (unsigned i = 0; i < n_known; i++) {
+        const ptam_ctx::K7Shape& k = ctx->k7_shapes[i];
+        if (k.fn == k7 && k.threads == threads && k.smem == smem) {
+            *per_cu = k.per_cu;
+            return k.rc;
+        }
     }
-    *per_cu = it->second.second;
-    return it->second.first;
+    int rc = PTAM_OK, n = 0;
+    if (smem > 64 * 1024 && hipFuncSetAttribute(k7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) rc = PTAM_E_HIP;
+    if (!rc && hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k7, threads, smem) != hipSuccess) rc = PTAM_E_HIP;
+    if (rc) (void)hipGetLastError();
+    ctx->k7_shapes[ctx->n_k7_shapes++ % CTX_NCACHE(ctx->k7_shapes)] = ptam_ctx::K7Shape{k7, threads, smem, rc, n};
+    *per_cu = n;
+    return rc;
 }
 
 static int ba_prepare_impl(ptam_ba* ba) {
@@ -436,7 +461,7 @@ static int ba_prepare_impl(ptam_ba* ba) {
     if (!ba->k7_loop && ba->opts.deterministic == 0 && n64_all < 16 * 128) ba->k7_threads = 512;
     const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
     auto k7_fn = [&](int threads) -> const void* { return k7_wave_fn(threads, ba->k7_loop, ba->opts.estimator, ba->k7_big, ba->det); };
-    auto k7_occupancy = [&](int threads, int* per_cu) -> int { return ba_k7_occupancy(k7_fn(threads), threads, k7_smem(threads), per_cu); };
+    auto k7_occupancy = [&](int threads, int* per_cu) -> int { return ba_k7_occupancy(ctx, k7_fn(threads), threads, k7_smem(threads), per_cu); };
     int per_cu = 0;
     {
         // the workgroup's LDS — camera partials F * 216 B + poses C * 96 B + 3 KB per wave — must fit the CU's 160 KB: many
@@ -522,17 +547,7 @@ static int ba_prepare_impl(ptam_ba* ba) {
     } else
         d.grid_acc = 1;
     const int n_dtiles = (M + DET_TILE - 1) / DET_TILE;
-    if (ba->det) {
-        static const hipError_t det_attr = hipFuncSetAttribute((const void*)reduce_det_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                               (int)((size_t)14 * (DET_TILE + 1) * sizeof(double)));
-        HIP_TRY(det_attr);
-    }
     d.u_rows = ba->det ? n_dtiles : (ba->k7_big || !ba->use_wave) ? 1 : d.grid_acc;
-    {
-        static const hipError_t schur_attr =
-            hipFuncSetAttribute((const void*)schur_tile_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SCHUR_RED_BYTES);
-        HIP_TRY(schur_attr);
-    }
     lap("launch shape");
 
     // ---- carve the main device allocation (sizes the host knows: M exactly, the points by their upper bound) --------------------
@@ -740,7 +755,7 @@ static int ba_prepare_impl(ptam_ba* ba) {
     hipLaunchKernelGGL(prep_publish_kernel, dim3(1), dim3(64), 0, ctx->stream, q, (volatile unsigned long long*)dp, seq);
     HIP_TRY(hipGetLastError());
     lap("phase 1 enqueued");
-    if (int rc = ba_wait_stamp(ctx, stamp, seq)) return rc;
+    if (int rc = ba_wait_stamp(ctx, stamp, seq, "the first phase of the bundle's prepare")) return rc;
     lap("phase 1 wait");
     PrepScalars ps = *ps_host;
     ba->dups_refused = ps.dup;
@@ -882,7 +897,7 @@ static int ba_prepare_impl(ptam_ba* ba) {
     hipLaunchKernelGGL(prep_publish_kernel, dim3(1), dim3(64), 0, ctx->stream, q, (volatile unsigned long long*)dp, seq);
     HIP_TRY(hipGetLastError());
     lap("phase 2 enqueued");
-    if (int rc = ba_wait_stamp(ctx, stamp, seq)) return rc;
+    if (int rc = ba_wait_stamp(ctx, stamp, seq, "the second phase of the bundle's prepare")) return rc;
     lap("phase 2 wait");
     ps = *ps_host;
     if (ps.bad) {
@@ -1226,13 +1241,6 @@ static int ba_enqueue_speculative(ptam_ba* ba, double lambda_next, double lambda
     return PTAM_OK;
 }
 
-static int ba_publish_scalars(ptam_ba* ba);
-static int ba_wait_scalars(ptam_ba* ba, BaScalars* out);
-static int ba_read_scalars(ptam_ba* ba, BaScalars* out) {
-    const int rc = ba_publish_scalars(ba);
-    return rc ? rc : ba_wait_scalars(ba, out);
-}
-
 static int ba_publish_scalars(ptam_ba* ba) {
     ptam_ctx* ctx = ba->ctx;
     int rc = ba_ensure_mailbox(ba);
@@ -1260,26 +1268,12 @@ static int ba_wait_scalars(ptam_ba* ba, BaScalars* out) {
     if (ba->prof) {
         HIP_TRY(ptam_stream_wait(ctx->stream));   // the profiling events must have completed as well
     } else {
-        // spin on the sequence words; every now and then ask the runtime whether the stream died instead
-        unsigned spins = 0, idle_polls = 0, dbg_polls = 0;
-        while (!arrived()) {
-            if (++spins == 100000) {
-                spins = 0;
-                const hipError_t q = hipStreamQuery(ctx->stream);
-                if (q != hipSuccess && q != hipErrorNotReady) return PTAM_E_HIP;
-                if (getenv("PTAM_DEBUG_WAIT") && (++dbg_polls % 100) == 0) {
-                    std::fprintf(stderr, "[ptam] waiting for seq %llu: stream %s, slots", seq, q == hipSuccess ? "drained" : "busy");
-                    for (unsigned i = 0; i < NW; i++) std::fprintf(stderr, " %llu", (unsigned long long)ba->mbox->slot[i].seq);
-                    std::fprintf(stderr, "\n");
-                }
-                if (q == hipSuccess && !arrived() && ++idle_polls > 50) {
-                    // the stream has drained and nothing published this sequence number: a logic error, not a wait
-                    ptam_set_error("scalar mailbox: sequence %llu never arrived (slot 0 holds %llu)", seq,
-                                   (unsigned long long)ba->mbox->slot[0].seq);
-                    return PTAM_E_STATE;
-                }
-            }
-        }
+        const int rc = ba_wait_mapped(ctx, "a trial's scalars", arrived, [&](bool drained) {
+            std::fprintf(stderr, "[ptam] waiting for seq %llu: stream %s, slots", seq, drained ? "drained" : "busy");
+            for (unsigned i = 0; i < NW; i++) std::fprintf(stderr, " %llu", (unsigned long long)ba->mbox->slot[i].seq);
+            std::fprintf(stderr, "\n");
+        });
+        if (rc) return rc;
     }
     unsigned long long words[NW];
     for (;;) {
@@ -1293,24 +1287,9 @@ static int ba_wait_scalars(ptam_ba* ba, BaScalars* out) {
     return PTAM_OK;
 }
 
-// digest the purged-measurement indices of finished Compute() calls: per LM step sorted by insertion index, appended
-// to the (point, camera) list, and the measurements marked erased for the next prepare
-static void ba_finish_outliers(ptam_ba* ba) {
-    int begin = ba->raw_out_done;
-    for (size_t k = 0; k < ba->raw_out_ends.size(); k++) {
-        const int end = ba->raw_out_ends[k];
-        if (end <= begin) continue;
-        std::sort(ba->raw_out.begin() + begin, ba->raw_out.begin() + end);
-        for (int i = begin; i < end; i++) {
-            const int o = ba->raw_out[i];
-            ba->outliers.push_back(std::make_pair(ba->ms.pt((size_t)o), ba->ms.cam((size_t)o)));
-            if (!ba->m_dead[o]) ba->n_dead++;
-            ba->m_dead[o] = 1;
-        }
-        begin = end;
-    }
-    ba->raw_out_done = begin;
-    ba->raw_out_ends.clear();
+static int ba_read_scalars(ptam_ba* ba, BaScalars* out) {
+    const int rc = ba_publish_scalars(ba);
+    return rc ? rc : ba_wait_scalars(ba, out);
 }
 
 // ---- a bundle whose inputs are already on the device (mapba.hip) ----------------------------------------------------------------
@@ -1348,6 +1327,162 @@ int ba_dev_result(const ptam_ba* ba, BaDevResult* r) {
     r->n_out = (int)ba->raw_out.size();
     r->step_end = ba->raw_out_ends.data();
     r->n_steps = (int)ba->raw_out_ends.size();
+    return PTAM_OK;
+}
+
+// The persistent camera solve spins on flags between workgroups that must all be resident.  One bundle's launch is a dozen
+// workgroups on an idle XCD; two bundles of this process adjusting on one device at the same moment could each be granted
+// part of theirs.  So only the first one in uses that form; a second one takes the launch-per-block-column form for this call.
+struct ChainTurn {
+    static std::atomic<int>& busy(int dev) {
+        static std::atomic<int> b[64];
+        return b[dev & 63];   // (device ids 64 apart would share a counter: one node has at most 8)
+    }
+    BaDev& d;
+    int dev, was;
+    bool forced;
+    ChainTurn(BaDev& d_, int dev_) : d(d_), dev(dev_), was(d_.chain_off), forced(false) {
+        if (busy(dev).fetch_add(1) > 0 && !d.chain_off) {
+            d.chain_off = 1;
+            forced = true;
+        }
+    }
+    ~ChainTurn() {
+        busy(dev).fetch_sub(1);
+        if (forced && d.chain_off == 1) d.chain_off = was;   // (a fault during the call sets 2: that one stays)
+    }
+};
+
+// The up-front exchange of a sharded bundle:
+// every rank must walk the same sequence of collectives: a rank without measurements, or one whose prepare failed
+// (a point with more than BA_CHUNK cameras, a duplicate measurement, an allocation failure — all of them local to a
+// shard), would return at once and the others would wait for it for ever.  One tiny all-reduce up front makes the
+// refusal unanimous and carries the first abort sample.
+// The same exchange settles the block bandwidth of the camera system: every rank marks the bandwidth its own
+// points need (one-hot, the collective only sums), the widest one wins — S is the sum of all ranks' parts.
+// (the layout of this vector only depends on the cameras, which every rank holds, never on the outcome of prepare)
+static int ba_sharded_handshake(ptam_ba* ba, int rc_prepare, bool abort_local, bool* abort_all, ChainTurn& chain_turn) {
+    ptam_ctx* ctx = ba->ctx;
+    BaDev& d = ba->d;
+    int n_free = 0;
+    for (uint8_t x : ba->cam_fixed) n_free += x ? 0 : 1;
+    const int nblk_x = (6 * n_free + SOLVE_NB - 1) / SOLVE_NB;
+    // ... and the FORM of the replicated camera solve: a rank that may not use the persistent launch for this call (another
+    // bundle of its process is adjusting on the same device — ranks that are threads of one process sharing a GPU —, or an
+    // earlier solve of it timed out) says so, and then NO rank uses it: every rank solves with the same code, the pose copies
+    // stay bit-identical (the two forms agree to 1e-6 only)
+    constexpr int XF = 5;   // fixed slots in front of the bandwidth marks
+    const bool band_fits = nblk_x + XF <= 512;   // d_xchg holds 512 doubles
+    std::vector<double> mine(band_fits ? XF + nblk_x : XF, 0.0), all(mine.size(), 0.0);
+    mine[0] = (!rc_prepare && d.M == 0) ? 1.0 : 0.0;
+    mine[1] = (double)d.M;
+    mine[2] = rc_prepare ? 1.0 : 0.0;
+    mine[3] = abort_local ? 1.0 : 0.0;
+    mine[4] = d.chain_off ? 1.0 : 0.0;
+    if (!rc_prepare && band_fits && nblk_x > 0) mine[XF + std::min(ba->band_local, nblk_x - 1)] = 1.0;
+    if (!ba->d_xchg) {   // (a failed prepare has not carved it)
+        HIP_TRY(hipMalloc((void**)&ba->d_xchg, 4096));
+        ba->xchg_owned = true;
+    }
+    HIP_TRY(hipMemcpyAsync(ba->d_xchg, mine.data(), mine.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = ba_allreduce(ba, ba->d_xchg, mine.size());
+    if (rc) return rc_prepare ? rc_prepare : rc;
+    HIP_TRY(hipMemcpyAsync(all.data(), ba->d_xchg, all.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ptam_stream_wait(ctx->stream));
+    if (all[2] > 0.5) {
+        if (rc_prepare) return rc_prepare;   // (this rank's own error message stands)
+        ptam_set_error("sharded bundle: %d of %d ranks could not prepare their shard; nothing was computed on any rank",
+                       (int)(all[2] + 0.5), ba->world);
+        return PTAM_E_STATE;
+    }
+    *abort_all = all[3] > 0.5;
+    if (all[4] > 0.5 && !d.chain_off) {   // (for this call only: chain_turn puts a forced value back)
+        d.chain_off = 1;
+        chain_turn.forced = true;
+    }
+    ba->d.band = std::max(0, nblk_x - 1);
+    if (band_fits)
+        for (int b = nblk_x - 1; b >= 0; b--)
+            if (all[XF + b] > 0.5) {
+                ba->d.band = b;
+                break;
+            }
+    if (all[0] > 0.5) {
+        ptam_set_error("sharded bundle: %d of %d ranks hold no measurement (shard the points so that every rank gets some)",
+                       (int)(all[0] + 0.5), ba->world);
+        return PTAM_E_STATE;
+    }
+    return PTAM_OK;
+}
+
+// host time since t0 in ms; PTAM_DEBUG_STALL=1 reports a trial that spent more than 3 ms of it
+static double ba_stall_ms(std::chrono::steady_clock::time_point t0, int trial, const char* did, const char* what) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ms > 3.0 && ba_debug().stall) std::fprintf(stderr, "[ptam] stall: trial %d %s %.2f ms %s\n", trial, did, ms, what);
+    return ms;
+}
+
+// A workgroup of the persistent factorisation gave up waiting for another one (ldlt_chain.inc): it cannot happen
+// while all of them are resident — a launch of a dozen workgroups on an otherwise idle XCD — but a device shared
+// with another process' persistent solve can leave each with half of its workgroups.  Nothing was committed (the
+// trial's finalize kernel saw the fault and armed none of the guarded kernels; a sharded bundle has summed the
+// fault over the ranks, so every rank is here): the rest of this adjustment uses the launch-per-block-column form,
+// which waits for nobody, and the trial is run again.
+static int ba_solve_fallback(ptam_ba* ba, int trial) {
+    ptam_ctx* ctx = ba->ctx;
+    BaDev& d = ba->d;
+    if (d.chain_off) {   // (that form raises no fault: something else is wrong)
+        ptam_set_error("bundle adjustment: the camera solve reports a fault in its launch-per-block form");
+        return PTAM_E_HIP;
+    }
+    d.chain_off = 2;
+    ba->solve_fallbacks++;
+    HIP_TRY(hipMemsetAsync(&d.sc->solve_fault, 0, sizeof(int), ctx->stream));
+    // (the launch's error word too: where the right-hand-side workgroup substitutes backwards inside the launch it takes
+    //  the word down itself, and a workgroup that gives up AFTER that would leave it up for the per-column form's
+    //  backward kernel to find; behind the launch, in stream order, nobody is left to raise it)
+    if (d.sflags) HIP_TRY(hipMemsetAsync(d.sflags, 0, sizeof(unsigned), ctx->stream));
+    if (ba_debug().solve) std::fprintf(stderr, "[ptam] rank %d: persistent camera solve timed out at trial %d; repeating it with the launch-per-column form\n", ba->rank, trial);
+    return PTAM_OK;
+}
+
+// PTAM_DEBUG_TRIAL_TIMES=1
+static void ba_report_trial_times(const ptam_ba* ba, const std::vector<double>& trial_read_us) {
+    if (trial_read_us.empty()) return;
+    // per trial: a(ccepted) / r(ejected) / s(tay: new == old error) and the time since the previous verdict (the first: since the call began)
+    std::fprintf(stderr, "[ptam] trial times (us):");
+    for (size_t i = 0; i < trial_read_us.size() && i < ba->trials.size(); i++) {
+        const ptam_ba_trial& t = ba->trials[i];
+        std::fprintf(stderr, " %c%.1f", t.accepted ? 'a' : (t.err_new > t.err_old ? 'r' : 's'), trial_read_us[i] - (i ? trial_read_us[i - 1] : 0.0));
+    }
+    std::fprintf(stderr, "\n");
+}
+
+// ---- read back results: one pinned staging buffer, one synchronisation (pageable destinations cost ~100 us each) ----
+static int ba_readback(ptam_ba* ba, int n_out, std::vector<int>& out_idx) {
+    ptam_ctx* ctx = ba->ctx;
+    const BaDev& d = ba->d;
+    const size_t b_pose = (size_t)d.C * 96, b_pts = (size_t)d.P * 24, b_out = (size_t)n_out * 4;
+    void* pin = nullptr;
+    int rc = ctx_pinned(ctx, 64 + b_pose + b_pts + b_out + 64, &pin);
+    if (rc) return rc;
+    char* hp = (char*)pin + 64;   // [sequence word | poses | points | outlier indices]
+    char* dp = (char*)ctx->d_pinned + 64;
+    volatile unsigned long long* slot = (volatile unsigned long long*)pin;
+    const unsigned long long seq = ++ctx->pose_seq;
+    *slot = 0;
+    const size_t n_all = (size_t)d.C * 12 + (size_t)d.P * 3 + (size_t)n_out;
+    hipLaunchKernelGGL(readback_kernel, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n_all + 255) / 256, 1024))), dim3(256), 0,
+                       ctx->stream, (const double*)d.pose[ba->cur], (size_t)d.C * 12, (const double*)d.pt[ba->cur], (size_t)d.P * 3,
+                       (const int*)d.outliers, (size_t)n_out, (double*)dp, (double*)(dp + b_pose), (int*)(dp + b_pose + b_pts));
+    hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, ctx->stream, (volatile unsigned long long*)ctx->d_pinned, seq);
+    HIP_TRY(hipGetLastError());
+    rc = ba_wait_stamp(ctx, slot, seq, "the bundle's results");
+    if (rc) return rc;
+    std::memcpy(ba->cam_pose.data(), hp, b_pose);
+    for (int q = 0; q < d.P; q++)   // (device point q is original point pt_orig[q]; unobserved points keep their position)
+        std::memcpy(&ba->pts[(size_t)3 * ba->pt_orig[(size_t)q]], hp + b_pose + (size_t)q * 24, 24);
+    if (n_out > 0) std::memcpy(out_idx.data(), hp + b_pose + b_pts, b_out);
     return PTAM_OK;
 }
 
@@ -1441,12 +1576,14 @@ int ptam_ba_add_meas(ptam_ba* ba, int cam, int point, const double found[2], dou
 
 int ptam_ba_add_cameras(ptam_ba* ba, int n, const double* poses12, const uint8_t* fixed) {
     ARG_TRY(ba && n >= 0 && (n == 0 || (poses12 && fixed)));
-    for (int i = 0; i < n; i++) ptam_ba_add_camera(ba, poses12 + 12 * i, fixed[i]);
+    for (int i = 0; i < n; i++)
+        if (const int rc = ptam_ba_add_camera(ba, poses12 + 12 * i, fixed[i]); rc < 0) return rc;
     return PTAM_OK;
 }
 int ptam_ba_add_points(ptam_ba* ba, int n, const double* pos3) {
     ARG_TRY(ba && n >= 0 && (n == 0 || pos3));
-    for (int i = 0; i < n; i++) ptam_ba_add_point(ba, pos3 + 3 * i);
+    for (int i = 0; i < n; i++)
+        if (const int rc = ptam_ba_add_point(ba, pos3 + 3 * i); rc < 0) return rc;
     return PTAM_OK;
 }
 int ptam_ba_add_measurements(ptam_ba* ba, int n, const int32_t* cam, const int32_t* point, const double* found2,
@@ -1477,7 +1614,6 @@ int ptam_ba_add_measurements(ptam_ba* ba, int n, const int32_t* cam, const int32
     return PTAM_OK;
 }
 
-static int ba_ensure_mailbox(ptam_ba* ba);
 int ptam_ba_prepare(ptam_ba* ba) {
     ARG_TRY(ba);
     if (ba->prepared) return PTAM_OK;
@@ -1531,11 +1667,11 @@ int ptam_ba_set_comm(ptam_ba* ba, int rank, int world, ptam_allreduce_f64_fn fn,
 }
 
 // Bundle::Compute src/Bundle.cc:116-158
-#define BA_DBG(...) do { if (dbg_) { std::fprintf(stderr, "[ptam] " __VA_ARGS__); std::fprintf(stderr, "\n"); } } while (0)
+#define BA_DBG(...) do { if (dbg.wait) { std::fprintf(stderr, "[ptam] " __VA_ARGS__); std::fprintf(stderr, "\n"); } } while (0)
 int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* accepted_out) {
     ARG_TRY(ba);
     ptam_ctx* ctx = ba->ctx;
-    const bool dbg_ = getenv("PTAM_DEBUG_WAIT") != nullptr;
+    const BaDebug& dbg = ba_debug();
     HIP_TRY(hipSetDevice(ctx->device));
     BA_DBG("compute: prepare");
     const bool sharded = ba->comm && ba->world > 1;
@@ -1545,55 +1681,10 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
     BA_DBG("compute: prepared M=%d P=%d F=%d chunks=%d wchunks=%d grid_acc=%d schur_wg=%d", ba->d.M, ba->d.P, ba->d.F, ba->d.n_chunks,
            ba->d.n_wchunks, ba->d.grid_acc, ba->d.n_schur_wg);
     BaDev& d = ba->d;
-    // The persistent camera solve spins on flags between workgroups that must all be resident.  One bundle's launch is a dozen
-    // workgroups on an idle XCD; two bundles of this process adjusting on one device at the same moment could each be granted
-    // part of theirs.  So only the first one in uses that form; a second one takes the launch-per-block-column form for this call.
-    struct ChainTurn {
-        static std::atomic<int>& busy(int dev) {
-            static std::atomic<int> b[64];
-            return b[dev & 63];   // (device ids 64 apart would share a counter: one node has at most 8)
-        }
-        BaDev& d;
-        int dev, was;
-        bool forced;
-        ChainTurn(BaDev& d_, int dev_) : d(d_), dev(dev_), was(d_.chain_off), forced(false) {
-            if (busy(dev).fetch_add(1) > 0 && !d.chain_off) {
-                d.chain_off = 1;
-                forced = true;
-            }
-        }
-        ~ChainTurn() {
-            busy(dev).fetch_sub(1);
-            if (forced && d.chain_off == 1) d.chain_off = was;   // (a fault during the call sets 2: that one stays)
-        }
-    } chain_turn(d, ctx->device);
-    // (PTAM_TWO_QUEUES=1 only, see below.)  A REJECTED trial's continuation — the same step again with a larger lambda — does not
-    // queue behind the guarded kernels that were enqueued for the other outcome (each leaves at once, but a kernel that only reads
-    // its guard still costs its launch and its first memory access: ~4.4 us each): it goes to the context's second queue, which is empty.  Nothing on the queue left behind writes (the guards' sequence word also stops a leftover that is late), the
-    // trial's own kernels were all complete when its finalize kernel published the verdict the host has just read.  The context's
-    // queues are swapped for the rest of this call and put back at its end.
-    struct QueueTurn {
-        ptam_ctx* c;
-        bool flipped = false, ever = false;
-        void flip() {
-            std::swap(c->stream, c->stream_alt);
-            flipped = !flipped;
-            ever = true;
-        }
-        ~QueueTurn() {
-            // (whatever is left on the queue that is not the current one are guarded kernels of trials long decided: wait them out —
-            //  a query in practice — so that none of them outlives the call and meets the block in another bundle's hands)
-            if (ever) (void)ptam_stream_wait(c->stream_alt);
-            if (flipped) std::swap(c->stream, c->stream_alt);
-        }
-    } queue_turn{ctx};
+    ChainTurn chain_turn(d, ctx->device);
     double lambda = 0.0001, lambda_factor = 2.0;   // :125-126
-    ba->converged = false;
-    ba->published_by_finalize = false;
-    ba->cur_pending = false;
-    ba->slow_select = false;
-    ba->trial_is_current = false;
-    ba->e2_is_current = false;
+    ba->converged = ba->published_by_finalize = ba->cur_pending = ba->slow_select = false;
+    ba->trial_is_current = ba->e2_is_current = false;
     bool hit_max = false;
     int counter = 0;
     ba->accepted = 0;
@@ -1610,85 +1701,18 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
     BaScalars sc;
     std::memset(&sc, 0, sizeof sc);
     double dbg_enq_ms = 0, dbg_wait_ms = 0;   // host time spent enqueueing trials / waiting for their scalars (PTAM_DEBUG_STALL)
-    static const bool dbg_times = getenv("PTAM_DEBUG_TRIAL_TIMES") != nullptr;   // print when each trial's verdict reached the host
-    std::vector<double> trial_read_us;
+    std::vector<double> trial_read_us;        // when each trial's verdict reached the host (PTAM_DEBUG_TRIAL_TIMES)
     const auto dbg_t0 = std::chrono::steady_clock::now();
-#ifdef K7_TIMING
-    auto now_us = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double ht0 = now_us();
-    double ht_first = 0;
-    (void)hipMemsetAsync(ba->d.dbg + TL_BASE, 0, 8, ba->ctx->stream);
-#endif
-    if (sharded) {
-        // every rank must walk the same sequence of collectives: a rank without measurements, or one whose prepare failed
-        // (a point with more than BA_CHUNK cameras, a duplicate measurement, an allocation failure — all of them local to a
-        // shard), would return at once and the others would wait for it for ever.  One tiny all-reduce up front makes the
-        // refusal unanimous and carries the first abort sample.
-        // The same exchange settles the block bandwidth of the camera system: every rank marks the bandwidth its own
-        // points need (one-hot, the collective only sums), the widest one wins — S is the sum of all ranks' parts.
-        // (the layout of this vector only depends on the cameras, which every rank holds, never on the outcome of prepare)
-        int n_free = 0;
-        for (uint8_t x : ba->cam_fixed) n_free += x ? 0 : 1;
-        const int nblk_x = (6 * n_free + SOLVE_NB - 1) / SOLVE_NB;
-        // ... and the FORM of the replicated camera solve: a rank that may not use the persistent launch for this call (another
-        // bundle of its process is adjusting on the same device — ranks that are threads of one process sharing a GPU —, or an
-        // earlier solve of it timed out) says so, and then NO rank uses it: every rank solves with the same code, the pose copies
-        // stay bit-identical (the two forms agree to 1e-6 only)
-        constexpr int XF = 5;   // fixed slots in front of the bandwidth marks
-        const bool band_fits = nblk_x + XF <= 512;   // d_xchg holds 512 doubles
-        std::vector<double> mine(band_fits ? XF + nblk_x : XF, 0.0), all(mine.size(), 0.0);
-        mine[0] = (!rc_prepare && d.M == 0) ? 1.0 : 0.0;
-        mine[1] = (double)d.M;
-        mine[2] = rc_prepare ? 1.0 : 0.0;
-        mine[3] = abort_local() ? 1.0 : 0.0;
-        mine[4] = d.chain_off ? 1.0 : 0.0;
-        if (!rc_prepare && band_fits && nblk_x > 0) mine[XF + std::min(ba->band_local, nblk_x - 1)] = 1.0;
-        if (!ba->d_xchg) {   // (a failed prepare has not carved it)
-            HIP_TRY(hipMalloc((void**)&ba->d_xchg, 4096));
-            ba->xchg_owned = true;
-        }
-        HIP_TRY(hipMemcpyAsync(ba->d_xchg, mine.data(), mine.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        rc = ba_allreduce(ba, ba->d_xchg, mine.size());
-        if (rc) return rc_prepare ? rc_prepare : rc;
-        HIP_TRY(hipMemcpyAsync(all.data(), ba->d_xchg, all.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ptam_stream_wait(ctx->stream));
-        if (all[2] > 0.5) {
-            if (rc_prepare) return rc_prepare;   // (this rank's own error message stands)
-            ptam_set_error("sharded bundle: %d of %d ranks could not prepare their shard; nothing was computed on any rank",
-                           (int)(all[2] + 0.5), ba->world);
-            return PTAM_E_STATE;
-        }
-        abort_all = all[3] > 0.5;
-        if (all[4] > 0.5 && !d.chain_off) {   // (for this call only: chain_turn puts a forced value back)
-            d.chain_off = 1;
-            chain_turn.forced = true;
-        }
-        ba->d.band = std::max(0, nblk_x - 1);
-        if (band_fits)
-            for (int b = nblk_x - 1; b >= 0; b--)
-                if (all[XF + b] > 0.5) {
-                    ba->d.band = b;
-                    break;
-                }
-        if (all[0] > 0.5) {
-            ptam_set_error("sharded bundle: %d of %d ranks hold no measurement (shard the points so that every rank gets some)",
-                           (int)(all[0] + 0.5), ba->world);
-            return PTAM_E_STATE;
-        }
-    }
+    BaHostTimes ht;
+    ba_dbg_begin(ba, ht);
+    if (sharded && (rc = ba_sharded_handshake(ba, rc_prepare, abort_local(), &abort_all, chain_turn))) return rc;
     const bool empty = d.M == 0;
     // speculative step prologue (ba_enqueue_speculative): single device, not while per-kernel events are being taken
     const bool spec = !sharded && !ba->prof && d.n_chunks > 0 && !ptam_ab_env("PTAM_NO_SPECULATION");
     bool spec_ready = false;   // pass 1 .. V*^-1 of the coming step are already running behind the device-side flag
-    // Two ways to shorten the chain behind a trial, and they exclude each other.  (1) The trial's decision inside the next step's first
-    // launch (default): one dependent launch less per trial, 2.3 us.  (2) PTAM_TWO_QUEUES=1: a rejected trial's continuation on the
-    // context's second queue, 6 us per REJECTED trial — safe only while the kernel that publishes the verdict is over when the host
-    // reads it (finalize_new_kernel: one workgroup, the mailbox is its last act).  purge_pass1_decide_kernel publishes from
-    // workgroup 0 while its other workgroups may still be summing: a continuation on another queue could overwrite those sums
-    // (the solve's |da|^2, the point update's per-chunk errors) under a workgroup that is late, which would then decide differently.
-    // On one queue everything is in order.
-    static const bool two_queues = getenv("PTAM_TWO_QUEUES") != nullptr;
-    const bool fused_decision = !two_queues && !ptam_ab_env("PTAM_SEPARATE_FINALIZE");   // (A/B: the decision as a launch of its own, rounds 2-5)
+    // The trial's decision inside the next step's first launch: one dependent launch less per trial, 2.3 us.  (purge_pass1_decide_kernel
+    // publishes from workgroup 0 while its other workgroups may still be summing: in order only because the context has one queue.)
+    const bool fused_decision = !ptam_ab_env("PTAM_SEPARATE_FINALIZE");   // (A/B: the decision as a launch of its own, rounds 2-5)
     while (!empty && !ba->converged && !hit_max && !aborted()) {
         // ---- Do_LM_Step :209-551 ----
         bool skip_vinv = false;
@@ -1696,10 +1720,8 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
             spec_ready = false;
             skip_vinv = true;
         } else {
-            rc = ba_pass1_sigma(ba);
-            if (rc) return rc;
-            rc = ba_pass2(ba);
-            if (rc) return rc;
+            if ((rc = ba_pass1_sigma(ba))) return rc;
+            if ((rc = ba_pass2(ba))) return rc;
         }
         bool have_cur = false;
         double cur_err = 0, new_err = 0;
@@ -1711,35 +1733,21 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
             BA_DBG("trial %d lambda %g", counter, lambda);
             const auto q0 = std::chrono::steady_clock::now();
             rc = ba_trial(ba, lambda, skip_vinv, counter + 1 >= ba->opts.max_iterations ? 1 : 0, abort_local() ? 1 : 0, spec && fused_decision);
-            {
-                const double qms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - q0).count();
-                dbg_enq_ms += qms;
-                if (qms > 3.0 && getenv("PTAM_DEBUG_STALL"))
-                    std::fprintf(stderr, "[ptam] stall: trial %d took %.2f ms to enqueue\n", counter, qms);
-            }
+            dbg_enq_ms += ba_stall_ms(q0, counter, "took", "to enqueue");
             skip_vinv = false;
             if (rc) return rc;
-            rc = ba_publish_scalars(ba);
-            if (rc) return rc;
+            if ((rc = ba_publish_scalars(ba))) return rc;
             if (spec) {   // what follows an accepted trial, queued while the host waits for the verdict
-                rc = ba_enqueue_speculative(ba, lambda * 0.3, lambda);
-                if (rc) return rc;
+                if ((rc = ba_enqueue_speculative(ba, lambda * 0.3, lambda))) return rc;
             }
             BA_DBG("trial %d enqueued, waiting", counter);
-            {
-                const auto w0 = std::chrono::steady_clock::now();
-                rc = ba_wait_scalars(ba, &sc);
-                const double wms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-                dbg_wait_ms += wms;
-                if (wms > 3.0 && getenv("PTAM_DEBUG_STALL"))
-                    std::fprintf(stderr, "[ptam] stall: trial %d waited %.2f ms for its scalars\n", counter, wms);
-            }
+            const auto w0 = std::chrono::steady_clock::now();
+            rc = ba_wait_scalars(ba, &sc);
+            dbg_wait_ms += ba_stall_ms(w0, counter, "waited", "for its scalars");
             if (rc) return rc;
             BA_DBG("trial %d read: cur %g new %g sigma2 %g median %g n_valid %lld n_bad %d sumsq %g %g", counter, sc.cur_err, sc.new_err,
                    sc.sigma_sq, sc.median, sc.n_valid, sc.n_bad, sc.sumsq_cam, sc.sumsq_pt);
-#ifdef K7_TIMING
-            if (ht_first == 0) ht_first = now_us();
-#endif
+            ba_dbg_first_read(ht);
             if (!have_cur) {
                 // (every step runs at least one trial: this first read of step s also carries the outlier-list
                 //  length left by the purge that closed step s-1 — no separate read-back for it)
@@ -1751,7 +1759,7 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
                     // sharded select: a rank's exchange slot overflowed (thousands of bit-identical errors), so this
                     // step ran with a wrong sigma^2.  Nothing has been committed: repeat it with the gather path.
                     ba->slow_select = true;
-                    if (getenv("PTAM_DEBUG_SELECT")) std::fprintf(stderr, "[ptam] rank %d: select overflow, repeating the step on the gather path\n", ba->rank);
+                    if (dbg.select) std::fprintf(stderr, "[ptam] rank %d: select overflow, repeating the step on the gather path\n", ba->rank);
                     redo_step = true;
                     break;
                 }
@@ -1765,29 +1773,12 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
                     break;
                 }
             }
-            if (sc.solve_fault) {
-                // A workgroup of the persistent factorisation gave up waiting for another one (ldlt_chain.inc): it cannot happen
-                // while all of them are resident — a launch of a dozen workgroups on an otherwise idle XCD — but a device shared
-                // with another process' persistent solve can leave each with half of its workgroups.  Nothing was committed (the
-                // trial's finalize kernel saw the fault and armed none of the guarded kernels; a sharded bundle has summed the
-                // fault over the ranks, so every rank is here): the rest of this adjustment uses the launch-per-block-column form,
-                // which waits for nobody, and the trial is run again.
-                if (d.chain_off) {   // (that form raises no fault: something else is wrong)
-                    ptam_set_error("bundle adjustment: the camera solve reports a fault in its launch-per-block form");
-                    return PTAM_E_HIP;
-                }
-                d.chain_off = 2;
-                ba->solve_fallbacks++;
-                HIP_TRY(hipMemsetAsync(&d.sc->solve_fault, 0, sizeof(int), ctx->stream));
-                // (the launch's error word too: where the right-hand-side workgroup substitutes backwards inside the launch it takes
-                //  the word down itself, and a workgroup that gives up AFTER that would leave it up for the per-column form's
-                //  backward kernel to find; behind the launch, in stream order, nobody is left to raise it)
-                if (d.sflags) HIP_TRY(hipMemsetAsync(d.sflags, 0, sizeof(unsigned), ctx->stream));
-                if (getenv("PTAM_DEBUG_SOLVE")) std::fprintf(stderr, "[ptam] rank %d: persistent camera solve timed out at trial %d; repeating it with the launch-per-column form\n", ba->rank, counter);
+            if (sc.solve_fault) {   // nothing was committed: the trial is run again with the other form of the camera solve
+                if ((rc = ba_solve_fallback(ba, counter))) return rc;
                 continue;
             }
             ran_any = true;
-            if (dbg_times) trial_read_us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - dbg_t0).count());
+            if (dbg.trial_times) trial_read_us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - dbg_t0).count());
             if (sharded) abort_all = abort_all || sc.abort_any != 0;
             new_err = sc.new_err;
             const double sumsq = sc.sumsq_cam + sc.sumsq_pt;
@@ -1805,8 +1796,6 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
             if (new_err > cur_err) {   // ModifyLambda_BadStep :607-611
                 lambda = lambda * lambda_factor;
                 lambda_factor = lambda_factor * 2;
-                if (spec && two_queues && ctx->stream_alt && !ba->converged && counter + 1 < ba->opts.max_iterations && !aborted())
-                    queue_turn.flip();   // (the retry starts on the empty queue)
             }
             counter++;
             if (counter >= ba->opts.max_iterations) hit_max = true;   // :518-520
@@ -1825,8 +1814,7 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
             ba->trial_is_current = true;
         }
         if (prev_end_pending) {   // a step that ran no trial (abort raised in between): read the length the slow way
-            rc = ba_read_scalars(ba, &sc);
-            if (rc) return rc;
+            if ((rc = ba_read_scalars(ba, &sc))) return rc;
             step_outlier_end.push_back(sc.n_outliers);
         }
         // the device took the same decision for the guarded kernels: accepted and the loop goes on -> they ran
@@ -1842,73 +1830,19 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
         n_steps++;
     }
     BA_DBG("loop done, steps %d", n_steps);
-    if (dbg_times && !trial_read_us.empty()) {
-        // per trial: a(ccepted) / r(ejected) / s(tay: new == old error) and the time since the previous verdict (the first: since the call began)
-        std::fprintf(stderr, "[ptam] trial times (us):");
-        for (size_t i = 0; i < trial_read_us.size() && i < ba->trials.size(); i++) {
-            const ptam_ba_trial& t = ba->trials[i];
-            std::fprintf(stderr, " %c%.1f", t.accepted ? 'a' : (t.err_new > t.err_old ? 'r' : 's'), trial_read_us[i] - (i ? trial_read_us[i - 1] : 0.0));
-        }
-        std::fprintf(stderr, "\n");
-    }
-    if (getenv("PTAM_DEBUG_STALL"))
+    ba_report_trial_times(ba, trial_read_us);
+    if (dbg.stall)
         std::fprintf(stderr, "[ptam] compute loop: %zu trials in %.3f ms; host enqueueing trials %.3f ms, waiting for scalars %.3f ms\n",
                      ba->trials.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg_t0).count(),
                      dbg_enq_ms, dbg_wait_ms);
     if (n_steps > 0) {   // the last step's purge
-        rc = ba_read_scalars(ba, &sc);
-        if (rc) return rc;
+        if ((rc = ba_read_scalars(ba, &sc))) return rc;
         step_outlier_end.push_back(sc.n_outliers);
     }
-#ifdef K7_TIMING
-    const double ht_loop = now_us();
-#endif
-#ifdef K7_TIMING
-    {
-        long long h[16];
-        HIP_TRY(hipMemcpy(h, d.dbg, sizeof h, hipMemcpyDeviceToHost));
-        std::printf("LDLT step2 wg0: loop %lld tail %lld | last wg (role %lld): loop %lld tail %lld\n", h[1] - h[0], h[2] - h[1], h[7],
-                    h[5] - h[4], h[6] - h[5]);
-        long long q[8];
-        HIP_TRY(hipMemcpy(q, d.dbg + 32, sizeof q, hipMemcpyDeviceToHost));
-        std::printf("LDLT step2 wg0 iteration 3 (cycles): micro factor %lld | my rows %lld | next panel columns %lld | publish %lld | barrier %lld | "
-                    "operand reads issued %lld | off-chain updates %lld\n", q[1] - q[0], q[2] - q[1], q[3] - q[2], q[4] - q[3], q[5] - q[4], q[6] - q[5], q[7] - q[6]);
-    }
-#endif
-    // ---- read back results: one pinned staging buffer, one synchronisation (pageable destinations cost ~100 us each) ----
+    if ((rc = ba_dbg_loop_end(ba, ht))) return rc;
     const int n_out = step_outlier_end.empty() ? 0 : step_outlier_end.back();
     std::vector<int> out_idx(std::max(n_out, 1));
-    {
-        const size_t b_pose = (size_t)d.C * 96, b_pts = (size_t)d.P * 24, b_out = (size_t)n_out * 4;
-        void* pin = nullptr;
-        rc = ctx_pinned(ctx, 64 + b_pose + b_pts + b_out + 64, &pin);
-        if (rc) return rc;
-        char* hp = (char*)pin + 64;   // [sequence word | poses | points | outlier indices]
-        char* dp = (char*)ctx->d_pinned + 64;
-        volatile unsigned long long* slot = (volatile unsigned long long*)pin;
-        const unsigned long long seq = ++ctx->pose_seq;
-        *slot = 0;
-        const size_t n_all = (size_t)d.C * 12 + (size_t)d.P * 3 + (size_t)n_out;
-        hipLaunchKernelGGL(readback_kernel, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n_all + 255) / 256, 1024))), dim3(256), 0,
-                           ctx->stream, (const double*)d.pose[ba->cur], (size_t)d.C * 12, (const double*)d.pt[ba->cur], (size_t)d.P * 3,
-                           (const int*)d.outliers, (size_t)n_out, (double*)dp, (double*)(dp + b_pose), (int*)(dp + b_pose + b_pts));
-        hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, ctx->stream, (volatile unsigned long long*)ctx->d_pinned, seq);
-        HIP_TRY(hipGetLastError());
-        unsigned spins = 0;
-        while (*slot != seq) {
-            if (++spins == 100000) {
-                spins = 0;
-                const hipError_t q = hipStreamQuery(ctx->stream);
-                if (q != hipSuccess && q != hipErrorNotReady) return PTAM_E_HIP;
-                if (q == hipSuccess && *slot != seq) return PTAM_E_HIP;   // drained without the stamp: something failed
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        std::memcpy(ba->cam_pose.data(), hp, b_pose);
-        for (int q = 0; q < d.P; q++)   // (device point q is original point pt_orig[q]; unobserved points keep their position)
-            std::memcpy(&ba->pts[(size_t)3 * ba->pt_orig[(size_t)q]], hp + b_pose + (size_t)q * 24, 24);
-        if (n_out > 0) std::memcpy(out_idx.data(), hp + b_pose + b_pts, b_out);
-    }
+    if ((rc = ba_readback(ba, n_out, out_idx))) return rc;
     // the outlier list (reference order: LM step, then insertion order) is put together when somebody asks for it
     // (ba_finish_outliers): sorting ~10 k indices costs as much as a whole lambda trial
     ba->raw_out.insert(ba->raw_out.end(), out_idx.begin(), out_idx.begin() + n_out);
@@ -1916,82 +1850,9 @@ int ptam_ba_compute(ptam_ba* ba, const volatile unsigned char* abort_flag, int* 
     ba->raw_out_base += n_out;
     // the device copy stays valid for another Compute(): poses/points are current in pose[cur]; the
     // outlier counter restarts
-    if (n_out > 0) {
-        ba->prepared = false;   // rebuild without the erased measurements on the next Compute
-    }
-#ifdef K7_TIMING
-    std::printf("HOST Compute: first trial read at %.1f us, loop end %.1f us, total %.1f us (%zu trials)\n", ht_first - ht0, ht_loop - ht0,
-                now_us() - ht0, ba->trials.size());
-    {
-        long long c[4];
-        HIP_TRY(hipMemcpy(c, d.dbg + 5000, sizeof c, hipMemcpyDeviceToHost));
-        if (c[3] > c[1])
-            std::printf("K7 INSIDE Compute() (its last launch, block 100): %lld shader cycles in %.2f us = %.2f GHz\n", c[2] - c[0], (c[3] - c[1]) * 0.01,
-                        (double)(c[2] - c[0]) / ((c[3] - c[1]) * 10.0));
-    }
-    if (getenv("PTAM_TIMELINE")) {
-        std::vector<long long> tl(2 + 2 * TL_MAX);
-        HIP_TRY(hipMemcpy(tl.data(), d.dbg + TL_BASE, tl.size() * 8, hipMemcpyDeviceToHost));
-        const long long n_tl = std::min<long long>(tl[0], TL_MAX);
-        static const char* nm[] = {"?", "purge_pass1", "select_compact", "select_final", "K7", "reduce_vinv", "vinv", "schur_tile", "schur_reduce",
-                                   "ldlt_step0", "backward", "point_update", "finalize", "project_e2", "pass1_trial", "purge", "reduce_partials", "publish"};
-        for (long long i = 0; i < n_tl; i++)
-            std::printf("TL %4lld %-16s start %9.2f us  (+%.2f)\n", i, nm[tl[2 + 2 * i] < 18 ? tl[2 + 2 * i] : 0], (tl[3 + 2 * i] - tl[3]) * 0.01,
-                        i ? (tl[3 + 2 * i] - tl[1 + 2 * i]) * 0.01 : 0.0);
-    }
-#endif
-#ifdef SCHUR_STAMPS
-    {
-        std::vector<long long> wt(1024);
-        HIP_TRY(hipMemcpy(wt.data(), d.dbg + 3072, wt.size() * 8, hipMemcpyDeviceToHost));
-        const int nw = std::min(512, d.n_schur_wg);
-        const long long M40 = (1ll << 40) - 1, M56 = (1ll << 56) - 1;
-        long long e0 = wt[0] & M40, x1 = 0;
-        for (int i = 0; i < nw; i++) e0 = std::min(e0, wt[2 * i] & M40), x1 = std::max(x1, wt[2 * i + 1] & M56 & M40);
-        std::printf("SCHUR workgroups %d: makespan %.2f us; per workgroup (entry, exit in us from the first entry, segments, hw id):\n", nw, (x1 - e0) * 0.01);
-        for (int i = 0; i < nw; i++)
-            std::printf("%s[%d %.1f %.1f %d %llx]", i % 8 ? " " : "\n  ", i, ((wt[2 * i] & M40) - e0) * 0.01, ((wt[2 * i + 1] & M40) - e0) * 0.01, (int)(wt[2 * i + 1] >> 56),
-                        (unsigned long long)(wt[2 * i] >> 40));
-        std::printf("\n");
-        // the schedule: per workgroup its segments as pair:groups
-        std::vector<int> wseg((size_t)d.n_schur_wg + 1);
-        HIP_TRY(hipMemcpy(wseg.data(), d.s_wg_seg, wseg.size() * 4, hipMemcpyDeviceToHost));
-        std::vector<SchurWG> segs((size_t)wseg.back());
-        HIP_TRY(hipMemcpy(segs.data(), d.s_segs, segs.size() * sizeof(SchurWG), hipMemcpyDeviceToHost));
-        std::vector<SchurEntry> ents((size_t)std::max(1, d.n_schur_entries));
-        HIP_TRY(hipMemcpy(ents.data(), d.s_entries, (size_t)d.n_schur_entries * sizeof(SchurEntry), hipMemcpyDeviceToHost));
-        std::printf("SCHUR schedule:");   // per segment  pair : groups : model cost of its entries (the split's units)
-        for (int i = 0; i < nw; i++) {
-            std::printf("%s{%d", i % 8 ? " " : "\n  ", i);
-            for (int sg = wseg[i]; sg < wseg[i + 1]; sg++) {
-                long long cost = 0;
-                for (int e = segs[sg].e_begin; e < segs[sg].e_end; e++) cost += ents[(size_t)e].pad & 0xffff;
-                std::printf(" %d:%d:%lld", segs[sg].pair, (segs[sg].e_end - segs[sg].e_begin + 3) / 4, cost);
-            }
-            std::printf("}");
-        }
-        std::printf("\n");
-    }
-    {
-        std::vector<long long> st(1024);
-        HIP_TRY(hipMemcpy(st.data(), d.dbg + 2048, st.size() * 8, hipMemcpyDeviceToHost));
-        for (int sel = 0; sel < 2; sel++) {
-            const long long* b = st.data() + sel * 512;
-            long long t0 = b[0];
-            for (int w = 0; w < 4; w++) if (b[w * 64] && b[w * 64] < t0) t0 = b[w * 64];
-            std::printf("SCHUR stamps wg %d (groups %lld): per wave, per group: top, loads issued, data there, MFMAs issued (cycles from the first top)\n", sel ? 150 : 0, b[260]);
-            for (int w = 0; w < 4; w++) {
-                std::printf("  w%d:", w);
-                for (int i = 0; i < 16 && b[(w * 16 + i) * 4]; i++)
-                    std::printf(" [%lld %lld %lld %lld]", b[(w * 16 + i) * 4] - t0, b[(w * 16 + i) * 4 + 1] - t0, b[(w * 16 + i) * 4 + 2] - t0, b[(w * 16 + i) * 4 + 3] - t0);
-                std::printf(" end %lld\n", b[256 + w] - t0);
-            }
-            std::printf("  kernel entry %lld, exit %lld, segments %lld; last segment's epilogue (wave 0): loop end %lld, barrier 1 %lld, 2 %lld, 3 %lld, laid out %lld, stores issued %lld\n",
-                        b[264] - t0, b[265] - t0, b[266], b[268] - t0, b[269] - t0, b[270] - t0, b[271] - t0, b[272] - t0, b[273] - t0);
-        }
-    }
-#endif
-    if (getenv("PTAM_DEBUG_STALL"))
+    if (n_out > 0) ba->prepared = false;   // rebuild without the erased measurements on the next Compute
+    if ((rc = ba_dbg_dump(ba, ht))) return rc;
+    if (dbg.stall)
         std::fprintf(stderr, "[ptam] compute total %.3f ms\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg_t0).count());
     if (accepted_out) *accepted_out = ba->accepted;
@@ -2085,36 +1946,7 @@ int ptam_ba_bench_jacobian(ptam_ba* ba, int reps, double* avg_ms, double* algori
     hipEventDestroy(e0);
     hipEventDestroy(e1);
     ba->prof = prof;
-#ifdef K7_TIMING
-    {
-        long long h[16];
-        HIP_TRY(hipMemcpy(h, d.dbg, sizeof h, hipMemcpyDeviceToHost));
-        {
-            long long c[4];
-            HIP_TRY(hipMemcpy(c, d.dbg + 5000, sizeof c, hipMemcpyDeviceToHost));
-            if (c[3] > c[1])
-                std::printf("K7 BACK TO BACK (last of %d launches, block 100): %lld shader cycles in %.2f us = %.2f GHz\n", reps, c[2] - c[0], (c[3] - c[1]) * 0.01,
-                            (double)(c[2] - c[0]) / ((c[3] - c[1]) * 10.0));
-        }
-        std::printf("K7 stamps (10 ns ticks since kernel-body start):");
-        for (int i = 1; i < 10; i++) std::printf(" [%d] %lld", i, h[i] - h[0]);
-        std::printf("\n");
-        const int nb = std::min(ba->d.grid_acc, 2000);
-        std::vector<long long> w(2 * nb);
-        HIP_TRY(hipMemcpy(w.data(), d.dbg + 16, w.size() * 8, hipMemcpyDeviceToHost));
-        long long t0 = w[0];
-        for (int b = 0; b < nb; b++) t0 = std::min(t0, w[2 * b]);
-        std::vector<long long> st(nb), en(nb), du(nb);
-        for (int b = 0; b < nb; b++) st[b] = w[2 * b] - t0, en[b] = w[2 * b + 1] - t0, du[b] = en[b] - st[b];
-        std::sort(st.begin(), st.end());
-        std::sort(en.begin(), en.end());
-        std::sort(du.begin(), du.end());
-        std::printf("K7 block 7: body starts %lld ticks after the block's first instruction\n", h[0] - w[14]);
-        std::printf("K7 wall (10 ns ticks, %d blocks): start p0/p50/p90/p100 %lld %lld %lld %lld | end %lld %lld %lld %lld | dur %lld %lld %lld %lld\n",
-                    nb, st[0], st[nb / 2], st[nb * 9 / 10], st[nb - 1], en[0], en[nb / 2], en[nb * 9 / 10], en[nb - 1], du[0], du[nb / 2],
-                    du[nb * 9 / 10], du[nb - 1]);
-    }
-#endif
+    if ((rc = ba_dbg_k7_stamps(ba, reps))) return rc;
     if (avg_ms) *avg_ms = total / reps;
     if (algorithmic_bytes)   // 8 idx + 24 found/s + 1 state + 144 W per measurement,
                              // 96 B/camera pose read, 24 read + 72 write per point, 216 B/free camera
@@ -2221,9 +2053,9 @@ int ptam_ba_bench_jacobian_rotating(ptam_ba** bas, int n, int reps, double* avg_
 
 }   // extern "C"
 
-// every kernel of this file resolved once, when a context is created: the first launch of a kernel otherwise pays for
+// every kernel of this file resolved once, when a context is created (the device is current): the first launch of a kernel otherwise pays for
 // loading the code object / resolving the function — 10-28 ms in the middle of the first frame or the first adjustment
-void ba_preload_kernels() {
+int ba_preload_kernels() {
     ptam_preload((const void*)project_e2_kernel);
     ptam_preload((const void*)pass1_from_trial_kernel);
     ptam_preload((const void*)pass1_keep_kernel);
@@ -2266,4 +2098,8 @@ void ba_preload_kernels() {
         ptam_preload(k7_wave_fn(512, true, est ? PTAM_EST_CAUCHY : PTAM_EST_TUKEY));
         ptam_preload(k7_wave_fn(1024, true, est ? PTAM_EST_CAUCHY : PTAM_EST_TUKEY));
     }
+    // the two fixed opt-ins to more than 64 KB of dynamic LDS, per device like the loaded code (K7's depends on the bundle: ba_k7_occupancy)
+    HIP_TRY(hipFuncSetAttribute((const void*)reduce_det_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)14 * (DET_TILE + 1) * sizeof(double))));
+    HIP_TRY(hipFuncSetAttribute((const void*)schur_tile_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SCHUR_RED_BYTES));
+    return PTAM_OK;
 }

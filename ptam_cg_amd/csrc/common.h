@@ -45,8 +45,7 @@ struct DevCam {
 
 struct ptam_ctx {
     int device;
-    hipStream_t stream;
-    hipStream_t stream_alt;   // second queue, created when a bundle's rejected trial first needs it (bundle.hip: QueueTurn)
+    hipStream_t stream;   // the context's one queue; nothing changes it after ptam_ctx_create (a released block's next owner only touches it through this queue)
     ptam_cam_params params;
     DevCam cam;
     int halfsample;
@@ -57,6 +56,7 @@ struct ptam_ctx {
     void* d_pinned;          // device address of h_pinned (host-mapped): kernels publish small results into it
     size_t h_pinned_cap;
     unsigned long long pose_seq;
+    // The caches below belong, like the rest of the context, to the one thread that uses it: none of them is locked.
     // Released bundle memory is kept for the next bundle of this context (MapMaker builds a new Bundle for every
     // adjustment, src/MapMaker.cc:838-845): hipMalloc / hipFree / hipHostMalloc around queued work cost far more than their
     // own time here — mapping memory into the GPU's address space makes the driver evict and restore the queues (10-28 ms).
@@ -69,6 +69,9 @@ struct ptam_ctx {
     Cached pin_cache[12];   // pinned host arrays of released bundles (the measurements as they are added: PinVec, bundle.hip)
     unsigned* d_smap;       // the Schur tile kernel's index maps (schur_index_map_device: a compile-time constant, uploaded once)
     int n_cu;               // compute units of the device
+    // launch shapes of the accumulation kernel (bundle.hip: ba_k7_occupancy), asked of the runtime once per context and shape
+    struct K7Shape { const void* fn; int threads; size_t smem; int rc, per_cu; } k7_shapes[16];
+    unsigned n_k7_shapes;   // shapes asked so far (slot n % 16: a full table forgets its oldest entry, which is then asked again)
 };
 #define CTX_NCACHE(a) ((int)(sizeof(a) / sizeof((a)[0])))
 int ctx_cache_take(ptam_ctx::Cached* c, int slots, size_t bytes, void** out, size_t* cap);   // smallest cached block >= bytes, or null
@@ -78,7 +81,7 @@ void* ctx_cache_give(ptam_ctx::Cached* c, int slots, void* p, size_t bytes);    
 // of this library end within microseconds to a few milliseconds, so every one of them polls first (2 ms) and only then sleeps.
 hipError_t ptam_stream_wait(hipStream_t stream);
 void ptam_preload(const void* kernel);   // hipFuncGetAttributes: forces the kernel's code object to be loaded
-void ba_preload_kernels();
+int ba_preload_kernels();   // also raises the dynamic-LDS limits of the bundle's kernels on the current device
 void solve_preload_kernels();
 void pose_preload_kernels();
 void patch_preload_kernels();
@@ -95,7 +98,7 @@ int ctx_pinned(ptam_ctx* ctx, size_t bytes, void** out);      // pinned host sta
 // Measurement switches (kernel shapes, work splits, forms of a stage side by side) are read from the environment only in the
 // instrumented builds of tools/ (-DPTAM_AB_SWITCHES: `make ab` -> tools/_ab/libptam_hip.so); the product library has none of them.
 // What the product does read: PTAM_LDLT_NO_CHAIN (launch-per-block-column camera solve only), PTAM_CH_SPIN_LIMIT (how long a
-// workgroup of the persistent solve waits for another one) and PTAM_TWO_QUEUES (a second queue for a rejected trial's continuation) — operating switches, documented in ptam_hip.h — and the PTAM_DEBUG_*
+// workgroup of the persistent solve waits for another one) — operating switches, documented in ptam_hip.h — and the PTAM_DEBUG_*
 // diagnostics, which only print.
 #ifdef PTAM_AB_SWITCHES
 #define ptam_ab_env(name) getenv(name)

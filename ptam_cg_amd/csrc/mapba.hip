@@ -339,7 +339,6 @@ struct BaGuard {   // the call's own bundle, destroyed on every return path
         if (ba) ptam_ba_destroy(ba);
     }
 };
-inline size_t mba_up(size_t b) { return (b + 255) & ~(size_t)255; }
 }   // namespace
 
 extern "C" {
@@ -364,22 +363,17 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
     if (int rc = ba_dev_meas_chunks(g.ba, (size_t)M, &d_ms)) return rc;
     // device scratch (the bundle keeps its own memory): [cleared: header | role | point marks | rows per point] then the rest
     const size_t Kz = std::max(K, 1), Nz = std::max(N, 1), Mz = std::max(M, 1);
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        const size_t o = off;
-        off += mba_up(b);
-        return o;
-    };
-    const size_t o_hdr = take(sizeof(MbaHdr)), o_role = take(Kz * 4), o_mark = take(Nz * 4), o_rows = take(Nz * 4);
-    const size_t clear = off;
-    const size_t o_pose = take(Kz * 96), o_fixed = take(Kz), o_pts = take(Nz * 24), o_meas = take(Mz * sizeof(ptam_map_meas)),
-                 o_camid = take(Kz * 4), o_camkf = take(Kz * 4), o_ptid = take(Nz * 4), o_ptof = take(Nz * 4), o_ptsel = take(Nz * 24),
-                 o_blk = take(((size_t)nb + 1) * 4), o_selrow = take(Mz * 4);
+    Carver cv;
+    const size_t o_hdr = cv.take(sizeof(MbaHdr)), o_role = cv.take(Kz * 4), o_mark = cv.take(Nz * 4), o_rows = cv.take(Nz * 4);
+    const size_t clear = cv.off;
+    const size_t o_pose = cv.take(Kz * 96), o_fixed = cv.take(Kz), o_pts = cv.take(Nz * 24), o_meas = cv.take(Mz * sizeof(ptam_map_meas)),
+                 o_camid = cv.take(Kz * 4), o_camkf = cv.take(Kz * 4), o_ptid = cv.take(Nz * 4), o_ptof = cv.take(Nz * 4), o_ptsel = cv.take(Nz * 24),
+                 o_blk = cv.take(((size_t)nb + 1) * 4), o_selrow = cv.take(Mz * 4);
     // outlier routing (outliers <= bundle measurements <= M)
-    const size_t o_ord = take(Mz * 4), o_orow = take(Mz * 4), o_opt = take(Mz * 4), o_first = take(Nz * 4),
-                 o_out = take(Mz * sizeof(ptam_map_outlier));
+    const size_t o_ord = cv.take(Mz * 4), o_orow = cv.take(Mz * 4), o_opt = cv.take(Mz * 4), o_first = cv.take(Nz * 4),
+                 o_out = cv.take(Mz * sizeof(ptam_map_outlier));
     void* s = nullptr;
-    if (int rc = ctx_scratch(ctx, off, &s)) return rc;
+    if (int rc = ctx_scratch(ctx, cv.off, &s)) return rc;
     char* b = (char*)s;
     MbaDev a;
     a.mode = mode, a.K = K, a.N = N, a.M = M, a.nb = nb;
