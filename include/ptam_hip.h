@@ -362,6 +362,76 @@ int ptam_add_map_points_epipolar(ptam_ctx* ctx, const ptam_kf* src, const double
                                  ptam_new_map_point* out, int cap, int32_t* n_out,
                                  ptam_epipolar_level_stats* stats);
 
+/* ---- Tracker::TrackForInitialMap: TrailTracking_Start / TrailTracking_Advance (src/Tracker.cc:352-432) with
+ *      MiniPatch::SampleFromImage / FindPatch / SSDAtPoint (src/ImageProcess.cc:57-80, 196-252), on device-resident keyframes.
+ *      A trail is a 9x9 byte patch (MiniPatch::mirPatchSize) sampled in the first frame, its position there and its position
+ *      in the newest frame.  Every value is an integer: the device list is the reference's list, to the bit.
+ *      The object belongs to the context it was created with (its queue, its staging) and to that context's image size
+ *      (ptam_cam_params.width / height); all its memory is allocated by ptam_trails_create.  Every call is synchronous: one
+ *      host wait, at the end. */
+typedef struct ptam_trails ptam_trails;
+typedef struct { int32_t initial_x, initial_y, current_x, current_y; } ptam_trail;   /* Trail::irInitialPos, irCurrentPos (include/Tracker.h) */
+/* HomographyMatch (include/HomographyInit.h): v2CamPlaneFirst, v2CamPlaneSecond, m2PixelProjectionJac row-major */
+typedef struct { double first[2], second[2], jac[4]; } ptam_homography_match;
+
+/* max_trails >= 1: room for that many trails (Tracker.MaxInitialTrails is 1000) */
+int ptam_trails_create(ptam_ctx* ctx, int max_trails, ptam_trails** out);
+int ptam_trails_destroy(ptam_trails* t);
+/* TrailTracking_Start (src/Tracker.cc:352-370) after the caller's ptam_make_keyframe_rest(first) (:354; PTAM_E_STATE without
+ * it): the level-0 candidates — maximal corners >= 10 pixels inside the image with Shi-Tomasi score > min_shi_tomasi
+ * (src/KeyFrame.cc:66-76) — in std::sort's order of pair<-score, ImageRef> (:356-359: descending score, ties by ascending
+ * y, then x: libCVD's ImageRef::operator<); the first min(max_initial, max_trails) become trails (:360-368), each with its
+ * patch around its position and irCurrentPos = irInitialPos.  The object keeps ITS OWN copy of first's level-0 image,
+ * corners and row LUT as the previous frame (mPreviousFrameKF = mFirstKF, :369): the caller may reuse `first` for the next
+ * frame.  A start on a started object begins again.  *n_trails: the trails made. */
+int ptam_trails_start(ptam_trails* t, const ptam_kf* first, double min_shi_tomasi, int max_initial, int* n_trails);
+/* TrailTracking_Advance (src/Tracker.cc:376-432).  Per trail, in list order: FindPatch(irEnd = irCurrentPos, current level-0
+ * image, nRange 10, current vCorners) — the corners of the closed box +-10 in raster order (started from the row LUT entry
+ * of the clamped top row: the same corners as the reference's linear start, :216-220), SSDAtPoint of each (nMaxSSD + 1 =
+ * 100001 for a corner nearer than 4 pixels to a border), the first strictly smaller SSD wins, found iff the best is below
+ * 100000.  Not found: the trail is erased.  Found: it counts in *n_good and irCurrentPos = irEnd; then a 9x9 patch sampled at
+ * irEnd in the current frame is searched the same way in the previous frame from irEnd, and the trail stays iff that search
+ * found something and (irBackWardsFound - irStart).mag_squared() <= 2 (:402-407).  A trail that fails this married-matches
+ * check is erased although it was counted (:409-410): *n_good is the reference's return value — the caller's
+ * `nGoodTrails < 10 -> Reset()` (:329) — and *n_alive the length of the list afterwards.  Survivors keep their order.  The
+ * current frame's level-0 data is then copied into the object as the previous frame (:430).  Two kernel launches. */
+int ptam_trails_advance(ptam_trails* t, const ptam_kf* current, int* n_good, int* n_alive);
+/* mlTrails in list order.  cap < the live count: PTAM_E_ARG and nothing is written. */
+int ptam_trails_read(ptam_trails* t, ptam_trail* out, int cap, int* n);
+/* Trail::mPatch.mimOrigPatch of the live trails in list order: 81 bytes each (9 rows of 9); cap in trails */
+int ptam_trails_read_patches(ptam_trails* t, uint8_t* out, int cap, int* n);
+/* The first loop of MapMaker::InitFromStereo (src/MapMaker.cc:272-279) for the live trails: first = UnProject(irInitialPos),
+ * second = UnProject(irCurrentPos) (src/ATANCamera.cc:125-140), jac = GetProjectionDerivs() (:179-209) as the camera's cache
+ * stands after the SECOND UnProject — mvLastCam = second, mdLastR = the undistorted radius, mdLastFactor = 1 / dFactor: the
+ * derivative at the second point.  fp64 in the reference's operation order, no FMA contraction.  This is the input of the
+ * host's HomographyInit::Compute (src/HomographyInit.cc), which stays the reference's code. */
+int ptam_trails_matches(ptam_trails* t, ptam_homography_match* out, int cap, int* n);
+/* PTAM_E_ARG: a null pointer, max_trails < 1, a keyframe of another device or of another image size than the object's,
+ * cap smaller than the live count.  PTAM_E_STATE: advance / read / read_patches / matches before start. */
+
+/* ---- MapMaker::InitFromStereo, the point loop (src/MapMaker.cc:310-367): per match, in order, a level-0 map point in the
+ *      first keyframe (whose pose is the identity, :305) centred on `initial`: the _NC vectors (:321-326),
+ *      MakeTemplateCoarseNoWarp(first, 0, initial) (src/PatchFinder.cc:137-148), MakeSubPixTemplate, SetSubPixPos(vec(current)),
+ *      IterateSubPixToConvergence(second, subpix_max_its) (:330-333, the code of ptam_subpix_batch),
+ *      Triangulate(se3, UnProject(sub-pixel position), UnProject(initial)) (:342 -> :171-189: the 4x4 system, the same routine
+ *      as ptam_add_map_points_epipolar; the reference's 6x4 TriangulateNew, :216-258, is not called by InitFromStereo), and
+ *      MapPoint::RefreshPixelVectors (src/Map.cc:40-65).  The point is dropped when the alignment fails (:334-337) or its
+ *      world z is negative (:343-346).
+ *      Two places where the reference reads memory it has not written are given a defined meaning here.  (1) A centre nearer
+ *      than 5 pixels to a border makes MakeTemplateCoarseNoWarp return with mbTemplateBad set, which InitFromStereo does not
+ *      look at: it aligns the previous point's template.  Here the match is dropped as template_bad (a trail's initial
+ *      position is >= 10 pixels inside, so the reference's own flow never gets there).  (2) :327 calls RefreshPixelVectors before
+ *      v3WorldPos is assigned (:342); the vectors are computed again after the first accepted bundle step.  Here they are
+ *      computed from the triangulated position.
+ *      se3_second_from_first: HomographyInit's pose with its translation already scaled to WiggleScale (:296-297).
+ *      out: room for n records; the made points come out in match order with level = 0, center = initial,
+ *      src_root_pos = vec(initial) (the SRC_ROOT measurement, :352-357), target_pos = the sub-pixel position (the SRC_TRAIL
+ *      measurement, :360-365), candidate = the match index, target_corner = -1, best_zmssd = 0.  status: n entries. */
+enum { PTAM_INIT_MADE = 0, PTAM_INIT_SUBPIX_FAILED = 1, PTAM_INIT_BEHIND_CAMERA = 2, PTAM_INIT_TEMPLATE_BAD = 3 };
+int ptam_init_points_from_trails(ptam_ctx* ctx, const ptam_kf* first, ptam_kf* second, const double se3_second_from_first[12],
+                                 int n, const ptam_trail* matches, int subpix_max_its /* 10 (:333) */,
+                                 ptam_new_map_point* out, int32_t* status, int32_t* n_out);
+
 /* ---- Tracker pose Gauss-Newton (src/Tracker.cc:613-643 driver, :928-1005 CalcPoseUpdate,
  *      include/Tracker.h:125-142 CalcJacobian/LinearUpdate) ---------------------------------------- */
 typedef struct {

@@ -111,6 +111,8 @@ public:
         check(ptam_make_keyframe_lite(ctx_->handle(), h_, im, stride), "ptam_make_keyframe_lite");
         fetched_ = 0;
     }
+    // void MakeKeyFrame_Rest()   include/KeyFrame.h:142, src/KeyFrame.cc:61-82 (without the SmallBlurryImage)
+    void MakeKeyFrame_Rest() { check(ptam_make_keyframe_rest(ctx_->handle(), h_), "ptam_make_keyframe_rest"); }
     // aLevels[l] host view (pixels, vCorners, vCornerRowLUT)
     const Level& aLevels(int l) {
         if (!(fetched_ & (1u << l))) {
@@ -282,6 +284,72 @@ inline std::vector<ptam_new_map_point> AddMapPointsEpipolar(Context& c, KeyFrame
           "ptam_add_map_points_epipolar");
     out.resize((size_t)n);
     if (stats) stats->assign(st.begin(), st.begin() + opts.n_levels);
+    return out;
+}
+
+// Tracker::TrailTracking_Start() / int TrailTracking_Advance()   src/Tracker.cc:352-432, with the list mlTrails and
+// mPreviousFrameKF kept on the device (ptam_trails_*).  The caller's TrackForInitialMap (:311-347) keeps its stage enum, the
+// `nGoodTrails < 10 -> Reset()` test and the spacebar; Matches() is the vMatches table of InitFromStereo (src/MapMaker.cc:272-279)
+// for the host's HomographyInit::Compute.
+class TrailTracker {
+public:
+    explicit TrailTracker(Context& c, int nMaxInitialTrails = 1000 /* Tracker.MaxInitialTrails */, double dMinShiTomasi = 70.0)
+        : max_(nMaxInitialTrails), min_st_(dMinShiTomasi) {
+        check(ptam_trails_create(c.handle(), nMaxInitialTrails, &h_), "ptam_trails_create");
+    }
+    ~TrailTracker() { ptam_trails_destroy(h_); }
+    TrailTracker(const TrailTracker&) = delete;
+    TrailTracker& operator=(const TrailTracker&) = delete;
+    // kf must have had MakeKeyFrame_Rest (:354); returns the number of trails
+    int Start(KeyFrame& kf) {
+        int n = 0;
+        check(ptam_trails_start(h_, kf.handle(), min_st_, max_, &n), "ptam_trails_start");
+        return n;
+    }
+    // returns nGoodTrails; the trails alive afterwards: Alive()
+    int Advance(KeyFrame& kf) {
+        int good = 0;
+        check(ptam_trails_advance(h_, kf.handle(), &good, &alive_), "ptam_trails_advance");
+        return good;
+    }
+    int Alive() const { return alive_; }
+    std::vector<ptam_trail> Trails() {   // mlTrails: irInitialPos, irCurrentPos
+        std::vector<ptam_trail> v((size_t)max_);
+        int n = 0;
+        check(ptam_trails_read(h_, v.data(), max_, &n), "ptam_trails_read");
+        v.resize((size_t)n);
+        return v;
+    }
+    std::vector<ptam_homography_match> Matches() {
+        std::vector<ptam_homography_match> v((size_t)max_);
+        int n = 0;
+        check(ptam_trails_matches(h_, v.data(), max_, &n), "ptam_trails_matches");
+        v.resize((size_t)n);
+        return v;
+    }
+
+private:
+    ptam_trails* h_ = nullptr;
+    int max_, alive_ = 0;
+    double min_st_;
+};
+
+// The point loop of MapMaker::InitFromStereo (src/MapMaker.cc:310-367) in ONE device call (ptam_init_points_from_trails):
+// se3 = HomographyInit's pose scaled to WiggleScale (:296-297).  The made points come back in vpPoints order with both
+// measurements (src_root_pos: SRC_ROOT in kF, target_pos: SRC_TRAIL in kS); pvStatus (nullable): PTAM_INIT_* per match.
+inline std::vector<ptam_new_map_point> InitPointsFromTrails(Context& c, KeyFrame& kF, KeyFrame& kS, const SE3& se3,
+                                                           const std::vector<ptam_trail>& vTrailMatches,
+                                                           std::vector<int32_t>* pvStatus = nullptr, int nSubPixMaxIts = 10) {
+    double p[12];
+    se3.to12(p);
+    std::vector<ptam_new_map_point> out(vTrailMatches.size());
+    std::vector<int32_t> st(vTrailMatches.size());
+    int32_t n = 0;
+    check(ptam_init_points_from_trails(c.handle(), kF.handle(), kS.handle(), p, (int)vTrailMatches.size(), vTrailMatches.data(),
+                                       nSubPixMaxIts, out.data(), st.data(), &n),
+          "ptam_init_points_from_trails");
+    out.resize((size_t)n);
+    if (pvStatus) *pvStatus = st;
     return out;
 }
 

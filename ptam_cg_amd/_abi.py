@@ -83,6 +83,19 @@ class NewMapPoint(C.Structure):
                 ("center_y", C.c_int32), ("candidate", C.c_int32), ("target_corner", C.c_int32), ("best_zmssd", C.c_int32)]
 
 
+class Trail(C.Structure):
+    """ptam_trail (Trail::irInitialPos / irCurrentPos, src/Tracker.cc:352-432)"""
+    _fields_ = [("initial_x", C.c_int32), ("initial_y", C.c_int32), ("current_x", C.c_int32), ("current_y", C.c_int32)]
+
+
+class HomographyMatch(C.Structure):
+    """ptam_homography_match (HomographyMatch, include/HomographyInit.h:23-29)"""
+    _fields_ = [("first", C.c_double * 2), ("second", C.c_double * 2), ("jac", C.c_double * 4)]
+
+
+INIT_MADE, INIT_SUBPIX_FAILED, INIT_BEHIND_CAMERA, INIT_TEMPLATE_BAD = range(4)   # ptam_init_points_from_trails status
+
+
 class EpipolarLevelStats(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ("candidates", "kept_after_thinning", "ray_rejected", "line_rejected", "template_bad",
                                          "no_match", "subpix_failed", "made")]
@@ -210,6 +223,14 @@ PROTOTYPES = {
     "refind_pairs": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "epipolar_opts_default": (None, [C.POINTER(EpipolarOpts)]),
     "add_map_points_epipolar": (_i, [_vp, _vp, _pd, _vp, _pd, C.POINTER(EpipolarOpts), _i, _vp, _vp, _vp, _i, C.POINTER(C.c_int32), _vp]),
+    "trails_create": (_i, [_vp, _i, _ppv]),
+    "trails_destroy": (_i, [_vp]),
+    "trails_start": (_i, [_vp, _vp, _d, _i, C.POINTER(_i)]),
+    "trails_advance": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "trails_read": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
+    "trails_read_patches": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
+    "trails_matches": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
+    "init_points_from_trails": (_i, [_vp, _vp, _vp, _pd, _i, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "pose_gn_state": (_i, [_vp, _i, _vp, _vp, _pd, _vp, _vp, _vp, _vp]),
     "trackmap_opts_default": (None, [_vp]),
     "tracker_create": (_i, [_vp, _i, _ppv]),

@@ -86,6 +86,7 @@ void solve_preload_kernels();
 void pose_preload_kernels();
 void patch_preload_kernels();
 void mapmaker_preload_kernels();
+void trails_preload_kernels();
 void mapba_preload_kernels();
 void kf_preload_kernels();
 void pvs_preload_kernels();

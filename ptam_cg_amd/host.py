@@ -392,6 +392,75 @@ class MapMaker:
         return out[:n.value].copy(), stats[:opts.n_levels].copy()
 
 
+TRAIL_DT = np.dtype([("initial_x", "<i4"), ("initial_y", "<i4"), ("current_x", "<i4"), ("current_y", "<i4")])
+HOMOGRAPHY_MATCH_DT = np.dtype([("first", "<f8", (2,)), ("second", "<f8", (2,)), ("jac", "<f8", (4,))])
+assert TRAIL_DT.itemsize == C.sizeof(_abi.Trail) == 16 and HOMOGRAPHY_MATCH_DT.itemsize == C.sizeof(_abi.HomographyMatch) == 64
+
+
+class Trails:
+    """Tracker::TrailTracking_Start / TrailTracking_Advance (src/Tracker.cc:352-432) on device keyframes: the trail list of
+    TrackForInitialMap, and the match table InitFromStereo hands to HomographyInit (src/MapMaker.cc:272-279)"""
+
+    def __init__(self, ctx, max_trails=1000):
+        self.ctx, self.lib = ctx, ctx.lib
+        if not self.lib.has("trails_create"):
+            raise PtamError("this library has no ptam_trails_create")
+        self.max_trails = max_trails
+        h = C.c_void_p()
+        ctx._check(self.lib.trails_create(ctx.h, max_trails, C.byref(h)), "trails_create")
+        self.h = h
+
+    def start(self, kf, min_shi_tomasi=70.0, max_initial=1000):
+        """TrailTracking_Start on a keyframe that has had MakeKeyFrame_Rest -> the number of trails"""
+        n = C.c_int()
+        self.ctx._check(self.lib.trails_start(self.h, kf.h, float(min_shi_tomasi), int(max_initial), C.byref(n)), "trails_start")
+        return n.value
+
+    def advance(self, kf):
+        """TrailTracking_Advance -> (nGoodTrails, trails alive afterwards)"""
+        g, a = C.c_int(), C.c_int()
+        self.ctx._check(self.lib.trails_advance(self.h, kf.h, C.byref(g), C.byref(a)), "trails_advance")
+        return g.value, a.value
+
+    def _table(self, fn, what, dtype, cap):
+        cap = self.max_trails if cap is None else cap
+        out = np.zeros(max(cap, 1), dtype=dtype)
+        n = C.c_int()
+        self.ctx._check(fn(self.h, _ptr(out), cap, C.byref(n)), what)
+        return out[:n.value].copy()
+
+    def read(self, cap=None):
+        """mlTrails in list order (TRAIL_DT)"""
+        return self._table(self.lib.trails_read, "trails_read", TRAIL_DT, cap)
+
+    def patches(self, cap=None):
+        """the live trails' 9x9 patches, (n, 9, 9) uint8"""
+        return self._table(self.lib.trails_read_patches, "trails_read_patches", np.dtype(("u1", (9, 9))), cap)
+
+    def matches(self, cap=None):
+        """vMatches of InitFromStereo (HOMOGRAPHY_MATCH_DT)"""
+        return self._table(self.lib.trails_matches, "trails_matches", HOMOGRAPHY_MATCH_DT, cap)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.trails_destroy(self.h)
+            self.h = None
+
+
+def init_points_from_trails(ctx, first_kf, second_kf, se3_second_from_first, matches, subpix_max_its=10):
+    """the point loop of MapMaker::InitFromStereo (src/MapMaker.cc:310-367) in one device call: matches TRAIL_DT (initial in
+    the first keyframe, current in the second) -> (points NEW_MAP_POINT_DT in match order, status (n,) of _abi.INIT_*)"""
+    m = np.ascontiguousarray(matches, dtype=TRAIL_DT)
+    n = len(m)
+    se3 = np.ascontiguousarray(se3_second_from_first, dtype=np.float64).reshape(12)
+    out = np.zeros(max(n, 1), dtype=NEW_MAP_POINT_DT)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    made = C.c_int32()
+    ctx._check(ctx.lib.init_points_from_trails(ctx.h, first_kf.h, second_kf.h, _pd(se3), n, _ptr(m), int(subpix_max_its), _ptr(out),
+                                               _ptr(status), C.byref(made)), "init_points_from_trails")
+    return out[:made.value].copy(), status[:n].copy()
+
+
 MAP_MEAS_DT = np.dtype([("kf", "<i4"), ("point", "<i4"), ("level", "<i4"), ("source", "<i4"), ("root_pos", "<f8", (2,))])
 MAP_OUTLIER_DT = np.dtype([("point", "<i4"), ("kf", "<i4"), ("action", "<i4"), ("meas", "<i4")])
 
