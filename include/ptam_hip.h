@@ -40,8 +40,9 @@ extern "C" {
 enum {
     PTAM_OK = 0,
     PTAM_E_ARG = -1,      /* bad argument */
-    PTAM_E_HIP = -2,      /* HIP runtime error (see ptam_last_error) */
-    PTAM_E_STATE = -3,    /* call out of order */
+    PTAM_E_HIP = -2,      /* HIP runtime error (see ptam_last_error); a call that waits for a result: the device queue failed */
+    PTAM_E_STATE = -3,    /* call out of order; a call that waits for a result (ptam_track_map*, ptam_track_frame, ptam_pose_gn*,
+                             ptam_ba_compute): the device queue drained and the result never arrived — ptam_last_error names it */
     PTAM_E_LIMIT = -4,    /* size above a documented limit */
     PTAM_E_COMM = -5      /* collective failed */
 };

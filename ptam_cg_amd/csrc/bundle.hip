@@ -27,6 +27,7 @@
 #include <utility>
 
 #include "bundle.h"
+#include "wait_mapped.h"
 #include "../../include/ptam_hip_bench.h"
 
 #include "ba_math.inc"
@@ -317,33 +318,8 @@ static const BaDebug& ba_debug() {
 
 #include "ba_debug_host.inc"
 
-// Wait until arrived() holds for words a kernel writes into host-mapped memory behind its results (ptam_stream_wait sleeps on an
-// interrupt: up to milliseconds to wake up); every 100 000 looks ask the runtime whether the queue died instead.  A queue that has
-// drained without the words gets 50 more polls, then it is a logic error, not a wait.  report(drained): PTAM_DEBUG_WAIT=1, every
-// 100th poll.
-template <class Arrived, class Report>
-static int ba_wait_mapped(ptam_ctx* ctx, const char* what, Arrived arrived, Report report) {
-    unsigned spins = 0, polls = 0, idle_polls = 0;
-    while (!arrived()) {
-        if (++spins < 100000) continue;
-        spins = 0;
-        const hipError_t q = hipStreamQuery(ctx->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) {
-            ptam_set_error("the device queue failed while the host waited for %s: %s", what, hipGetErrorString(q));
-            return PTAM_E_HIP;
-        }
-        if ((++polls % 100) == 0 && ba_debug().wait) report(q == hipSuccess);
-        if (q == hipSuccess && !arrived() && ++idle_polls > 50) {
-            ptam_set_error("the device queue drained and %s never arrived", what);
-            return PTAM_E_STATE;
-        }
-    }
-    if (polls) (void)hipGetLastError();   // (the runtime was asked: hipErrorNotReady is sticky in the last-error slot)
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return PTAM_OK;
-}
 static int ba_wait_stamp(ptam_ctx* ctx, volatile unsigned long long* slot, unsigned long long seq, const char* what) {
-    return ba_wait_mapped(ctx, what, [&] { return *slot == seq; }, [](bool) {});
+    return ptam_wait_mapped(ctx->stream, what, [&] { return *slot == seq; });
 }
 
 // launch shape of K7 for (threads, LDS bytes): asked of the runtime once per context and shape (each query is 10 - 40 us; the
@@ -1268,7 +1244,8 @@ static int ba_wait_scalars(ptam_ba* ba, BaScalars* out) {
     if (ba->prof) {
         HIP_TRY(ptam_stream_wait(ctx->stream));   // the profiling events must have completed as well
     } else {
-        const int rc = ba_wait_mapped(ctx, "a trial's scalars", arrived, [&](bool drained) {
+        const int rc = ptam_wait_mapped(ctx->stream, "a trial's scalars", arrived, [&](bool drained) {
+            if (!ba_debug().wait) return;   // PTAM_DEBUG_WAIT=1
             std::fprintf(stderr, "[ptam] waiting for seq %llu: stream %s, slots", seq, drained ? "drained" : "busy");
             for (unsigned i = 0; i < NW; i++) std::fprintf(stderr, " %llu", (unsigned long long)ba->mbox->slot[i].seq);
             std::fprintf(stderr, "\n");

@@ -7,10 +7,10 @@
 // pose lives in LDS, per-measurement state in an L2-resident scratch array, the median is an exact
 // 8x8-bit MSB radix select over LDS histograms, the 27 normal-equation sums are reduced by wavefront
 // shuffles + a fixed-order cross-wave pass (deterministic), thread 0 solves and applies exp().
-#include <atomic>
 
 #include "common.h"
 #include "track_internal.h"
+#include "wait_mapped.h"
 #include "pose_device.h"
 
 struct PoseState {
@@ -449,6 +449,21 @@ void ptam_gn_opts_default(ptam_gn_opts* o) {
     o->prior = 100.0;            // :974
 }
 
+// the fast kernel publishes the refined pose into host-mapped memory as twelve (word, sequence) pairs: wait for them, read the pose
+static int pose_wait_slots(ptam_ctx* ctx, volatile unsigned long long* slots, unsigned long long seq, double* pose_out) {
+    const int rc = ptam_wait_mapped(ctx->stream, "the refined pose", [&] {
+        for (int i = 0; i < 12; i++)
+            if (slots[2 * i + 1] != seq) return false;
+        return true;
+    });
+    if (rc) return rc;
+    for (int i = 0; i < 12; i++) {
+        const unsigned long long w = slots[2 * i];
+        std::memcpy(&pose_out[i], &w, 8);
+    }
+    return PTAM_OK;
+}
+
 static int pose_gn_host(ptam_ctx* ctx, int n, const ptam_pose_meas* meas, const ptam_projection* entry,
                         double pose_inout[12], const ptam_gn_opts* opts, int32_t* outlier_flags, double* updates_out,
                         ptam_projection* state_out) {
@@ -522,28 +537,7 @@ static int pose_gn_host(ptam_ctx* ctx, int n, const ptam_pose_meas* meas, const 
     const bool extras = outlier_flags || updates_out || state_out;
     if (outlier_flags) HIP_TRY(hipMemcpyAsync(hf, d_f, bf, hipMemcpyDeviceToHost, ctx->stream));
     if (updates_out) HIP_TRY(hipMemcpyAsync(hu, d_u, b_upd, hipMemcpyDeviceToHost, ctx->stream));
-    if (small && !extras) {
-        // only the pose is wanted: spin on the twelve (word, sequence) pairs the kernel writes into host-mapped memory
-        auto arrived = [&]() {
-            for (int i = 0; i < 12; i++)
-                if (slots[2 * i + 1] != seq) return false;
-            return true;
-        };
-        unsigned spins = 0;
-        while (!arrived()) {
-            if (++spins == 100000) {
-                spins = 0;
-                const hipError_t q = hipStreamQuery(ctx->stream);
-                if (q != hipSuccess && q != hipErrorNotReady) return PTAM_E_HIP;
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        for (int i = 0; i < 12; i++) {
-            const unsigned long long w = slots[2 * i];
-            std::memcpy(&pose_inout[i], &w, 8);
-        }
-        return PTAM_OK;
-    }
+    if (small && !extras) return pose_wait_slots(ctx, slots, seq, pose_inout);   // only the pose is wanted
     if (!small) HIP_TRY(hipMemcpyAsync(hp + o_slots, d_pose, 96, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ptam_stream_wait(ctx->stream));
     if (small) {
@@ -626,26 +620,7 @@ static int pose_gn_dev_impl(ptam_ctx* ctx, int n, const int32_t* d_n, const ptam
         std::memcpy(pose_host_out, (const void*)slots, 96);
         return PTAM_OK;
     }
-    auto arrived = [&]() {
-        for (int i = 0; i < 12; i++)
-            if (slots[2 * i + 1] != seq) return false;
-        return true;
-    };
-    unsigned spins = 0;
-    while (!arrived()) {
-        if (++spins == 100000) {
-            spins = 0;
-            const hipError_t q = hipStreamQuery(ctx->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) return PTAM_E_HIP;
-            if (q == hipSuccess && !arrived()) return PTAM_E_HIP;   // the stream drained without the kernel publishing
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    for (int i = 0; i < 12; i++) {
-        const unsigned long long w = slots[2 * i];
-        std::memcpy(&pose_host_out[i], &w, 8);
-    }
-    return PTAM_OK;
+    return pose_wait_slots(ctx, slots, seq, pose_host_out);
 }
 
 }   // extern "C"

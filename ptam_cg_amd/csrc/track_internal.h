@@ -14,6 +14,12 @@ struct TemplateJob {          // device-side form of ptam_template_query (keyfra
     double wi[4];
 };
 
+struct TmSrc {   // MapPoint::pPatchSourceKF / nSourceLevel / irCenter, resolved to the level image
+    const uint8_t* im;
+    int w, h;
+    int cx, cy;
+};
+
 // patch.hip
 // Level::vImplaneCorners of one level of kf, built on the context's stream unless cached (bImplaneCornersCached)
 int kf_build_implane(ptam_ctx* ctx, ptam_kf* kf, int level);

@@ -17,22 +17,15 @@
 // (:617), so a point found in the coarse stage enters it with the state the coarse loop left, a point of the later sets
 // with its re-projection at the post-coarse pose and the camera derivatives of the PVS pass (ProjectAndDerivs only
 // refreshes them for found points, include/Tracker.h:89-94).
-#include <atomic>
-#include <chrono>
-#include <thread>
+#include <climits>
 
 #include "track_internal.h"
+#include "wait_mapped.h"
 #include "../../include/ptam_hip_bench.h"
 #include "patch_device.h"
 #include "keyframe_device.h"
 #include "pvs_device.h"
 #include "pose_device.h"
-
-struct TmSrc {   // MapPoint::pPatchSourceKF / nSourceLevel / irCenter, resolved to the level image
-    const uint8_t* im;
-    int w, h;
-    int cx, cy;
-};
 
 struct TmCtl {
     int n_lvl[4];           // avPVS[l].size() after the PVS loop
@@ -806,327 +799,13 @@ __global__ void __launch_bounds__(THREADS) tm_pose_kernel(DevCam cam, TmDev d, i
     tm_pose_body<MPT, THREADS>(cam, d, stage, coarse_min, mbox, opts, io, updates, long_seq);
 }
 typedef void (*tm_pose_fn)(DevCam, TmDev, int, unsigned, TmMailbox*, ptam_gn_opts, PoseChainIo, double*, unsigned long long);
-struct TmBatchItem;
-// instantiation for a list of at most cap slots (<= GS_LIMIT): one wave up to 64, one slot per thread up to GS_THREADS (512), GS_MPT (two) up to GS_LIMIT (1024)
-static tm_pose_fn tm_pose_pick(int cap, int* threads) {
-    if (cap <= GS_WAVE_LIMIT) {
-        *threads = GS_WAVE_LIMIT;
-        return tm_pose_kernel<1, GS_WAVE_LIMIT>;
-    }
-    *threads = GS_THREADS;
-    return cap <= GS_THREADS ? tm_pose_kernel<1, GS_THREADS> : tm_pose_kernel<GS_MPT, GS_THREADS>;
+// shape of the fused pose kernels for a list of at most cap slots (<= GS_LIMIT): 0 = one wave up to 64, 1 = one slot per thread up to
+// GS_THREADS (512), 2 = GS_MPT (two) per thread up to GS_LIMIT (1024); the kernel tables below are in this order
+static int tm_pose_shape(int cap, int* threads) {
+    *threads = cap <= GS_WAVE_LIMIT ? GS_WAVE_LIMIT : GS_THREADS;
+    return cap <= GS_WAVE_LIMIT ? 0 : cap <= GS_THREADS ? 1 : 2;
 }
-
-// ---- MapMaker::ReFind_Common (src/MapMaker.cc:943-1020), batched over the map points of one keyframe ----
-// stage 1: projection + visibility tests (:950-975), derivatives, CalcSearchLevelAndWarpMatrix (:979, verdict unused),
-// the template job at the level its loop stopped at, and the search query ir(v2Image), range 4 (:988)
-__global__ void __launch_bounds__(256) refind_prep_kernel(DevCam cam, int n, const ptam_pvs_point* __restrict__ pts,
-                                                          const TmSrc* __restrict__ src, const double* __restrict__ pose,
-                                                          TemplateJob* __restrict__ jobs, ptam_patch_query* __restrict__ q) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    double T[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) T[k] = pose[k];
-    const ptam_pvs_point p = pts[i];
-    TemplateJob j;
-    j.im = nullptr;
-    j.w = j.h = 0;
-    j.search_level = -1;
-    j.cx = j.cy = 0;
-    j.wi[0] = j.wi[1] = j.wi[2] = j.wi[3] = 0;
-    ptam_patch_query qq;
-    qq.x = qq.y = 0;
-    qq.level = -1;
-    qq.range = 4;
-    double X, Y, Z;
-    se3_apply(T, p.world[0], p.world[1], p.world[2], X, Y, Z);
-    if (!(Z < 0.001)) {
-        const double x = X / Z, y = Y / Z;
-        if (!(x * x + y * y > cam.largest_radius * cam.largest_radius)) {
-            double u, v, rr, f;
-            cam_project(cam, x, y, u, v, rr, f);
-            if (!(rr > cam.max_r) && !(u < 0 || v < 0 || u > cam.width || v > cam.height)) {
-                double D[4];
-                cam_derivs(cam, x, y, rr, f, D);
-                double det = pvs_warp_matrix(T, X, Y, Z, D, p, j.wi);
-                int l = 0;
-                while (det > 3 && l < PTAM_LEVELS - 1) {
-                    l++;
-                    det *= 0.25;
-                }
-                const TmSrc sr = src[i];
-                j.im = sr.im;
-                j.w = sr.w;
-                j.h = sr.h;
-                j.cx = sr.cx;
-                j.cy = sr.cy;
-                j.search_level = l;
-                qq.x = (int)u;   // ir(): truncation
-                qq.y = (int)v;
-                qq.level = l;
-            }
-        }
-    }
-    jobs[i] = j;
-    q[i] = qq;
-}
-// stage 2: Finder.TemplateBad() (:982-986) takes the point out of the search
-__global__ void __launch_bounds__(256) refind_mask_kernel(int n, const ptam_template_result* __restrict__ tres, ptam_patch_query* __restrict__ q) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n && q[i].level >= 0 && tres[i].bad) q[i].level = -2 - q[i].level;   // (remembers the level for the report)
-}
-// stage 3: the measurement (:995-1011)
-__global__ void __launch_bounds__(256) refind_finish_kernel(int n, const ptam_patch_query* __restrict__ q, const ptam_patch_result* __restrict__ r,
-                                                            const ptam_subpix_result* __restrict__ sr, ptam_refind_result* __restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    ptam_refind_result o;
-    const int lv = q[i].level;
-    o.found = 0;
-    o.level = lv >= 0 ? lv : (lv <= -2 ? -2 - lv : -1);
-    o.sub_pix = 0;
-    o.never_retry = 1;
-    o.root_pos[0] = o.root_pos[1] = 0;
-    if (lv >= 0 && r[i].found) {
-        o.found = 1;
-        o.never_retry = 0;
-        if (lv > 0) {   // sub-pixel position whether or not the iteration converged (:1000-1006)
-            o.sub_pix = 1;
-            o.root_pos[0] = sr[i].pos[0];
-            o.root_pos[1] = sr[i].pos[1];
-        } else {
-            o.root_pos[0] = r[i].pos[0];
-            o.root_pos[1] = r[i].pos[1];
-        }
-    }
-    out[i] = o;
-}
-
-// ---- ReFind_Common over a list of (keyframe, point) pairs through ONE PatchFinder (src/MapMaker.cc:977, :1046-1082) ----
-// The finder's state makes the list a sequence: whether pair i re-makes the template depends on the last pair that did.
-// But only inside a RUN of consecutive pairs (of those that reach the finder) with the same map point: another point always
-// re-makes it (src/PatchFinder.cc:103).  So: (1) every pair's exits, level, warp and m2 in parallel; (2) one workgroup
-// compacts the reaching pairs and walks each run with one thread — which pair re-makes, which template a kept one uses,
-// whether a rejected warp has raised mbTemplateBad since; (3) the re-made templates; (4) one wave per pair searches with its
-// template; (5) the finder's state after the last pair.
-struct RpPair {
-    ptam_pvs_point pt;
-    TmSrc src;
-    double pose[12];
-    long long id;
-    int skip, kf;
-};
-struct RpFinder {   // the state of the reference's static PatchFinder that outlives a call
-    long long pt;          // mpLastTemplateMapPoint
-    double m2[4];          // mm2LastWarpMatrix {m00, m01, m10, m11}
-    int valid, bad;        // mpLastTemplateMapPoint != NULL, mbTemplateBad
-    uint8_t tpl[64];       // mimTemplate
-};
-struct RpDev {
-    int n;
-    const RpPair* pairs;
-    const KfLevels* Ls;
-    TemplateJob* jobs;
-    ptam_patch_query* q;
-    double* m2;            // [n][4]
-    int* reach;            // the pair gets as far as the finder
-    int* detbad;           // CalcSearchLevelAndWarpMatrix rejects the warp
-    int* R;                // reaching pairs, in order
-    int* nr;
-    int* refresh;          // the finder re-makes its template for this pair
-    int* srcp;             // pair whose template this pair searches with (-1: the template the finder brought along)
-    int* dacc;             // a warp was rejected since that template was made (this pair's included)
-    int* bad;              // Finder.TemplateBad() for this pair
-    uint8_t* tm;           // [n][64]
-    ptam_template_result* tres;
-    RpFinder* st;
-    ptam_refind_result* out;
-    int* kept;
-};
-__global__ void __launch_bounds__(256) rp_prep_kernel(DevCam cam, RpDev d) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= d.n) return;
-    const RpPair& pr = d.pairs[i];
-    double T[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) T[k] = pr.pose[k];
-    const ptam_pvs_point p = pr.pt;
-    TemplateJob j;
-    j.im = nullptr;
-    j.w = j.h = 0;
-    j.search_level = -1;
-    j.cx = j.cy = 0;
-    j.wi[0] = j.wi[1] = j.wi[2] = j.wi[3] = 0;
-    ptam_patch_query qq;
-    qq.x = qq.y = 0;
-    qq.level = -1;
-    qq.range = 4;
-    int reach = 0, detbad = 0;
-    double m2[4] = {0, 0, 0, 0};
-    double X, Y, Z;
-    se3_apply(T, p.world[0], p.world[1], p.world[2], X, Y, Z);
-    if (!pr.skip && !(Z < 0.001)) {                                                     // :947-955
-        const double x = X / Z, y = Y / Z;
-        if (!(x * x + y * y > cam.largest_radius * cam.largest_radius)) {               // :957-961
-            double u, v, rr, f;
-            cam_project(cam, x, y, u, v, rr, f);
-            if (!(rr > cam.max_r) && !(u < 0 || v < 0 || u > cam.width || v > cam.height)) {   // :963-975
-                double D[4];
-                cam_derivs(cam, x, y, rr, f, D);
-                double det = pvs_warp_matrix(T, X, Y, Z, D, p, j.wi);
-                int l = 0;
-                while (det > 3 && l < PTAM_LEVELS - 1) {
-                    l++;
-                    det *= 0.25;
-                }
-                detbad = (det > 3 || det < 0.25) ? 1 : 0;                               // src/PatchFinder.cc:78-81
-                j.im = pr.src.im;
-                j.w = pr.src.w;
-                j.h = pr.src.h;
-                j.cx = pr.src.cx;
-                j.cy = pr.src.cy;
-                j.search_level = l;
-                template_m2(j, m2);
-                qq.x = (int)u;   // ir(): truncation
-                qq.y = (int)v;
-                qq.level = l;
-                reach = 1;
-            }
-        }
-    }
-    d.jobs[i] = j;
-    d.q[i] = qq;
-    d.reach[i] = reach;
-    d.detbad[i] = detbad;
-#pragma unroll
-    for (int k = 0; k < 4; k++) d.m2[4 * i + k] = m2[k];
-}
-__global__ void __launch_bounds__(1024) rp_scan_kernel(RpDev d) {
-    __shared__ int wsum[16];
-    __shared__ int base_s;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < d.n; b0 += 1024) {   // stable compaction of the reaching pairs
-        const int i = b0 + tid;
-        const int f = i < d.n ? d.reach[i] : 0;
-        const int incl = wave_incl_scan_i32(f);
-        if (lane == 63) wsum[wid] = incl;
-        __syncthreads();
-        int off = base_s, tot = 0;
-        for (int w = 0; w < 16; w++) {
-            if (w < wid) off += wsum[w];
-            tot += wsum[w];
-        }
-        if (f) d.R[off + incl - 1] = i;
-        __syncthreads();
-        if (tid == 0) base_s += tot;
-        __syncthreads();
-    }
-    const int nr = base_s;
-    if (tid == 0) *d.nr = nr;
-    __threadfence_block();
-    __syncthreads();
-    const RpFinder st = *d.st;
-    const double lim = 0.07 * 0.07;
-    for (int k = tid; k < nr; k += 1024) {
-        const int i0 = d.R[k];
-        const long long id = d.pairs[i0].id;
-        const bool head = k == 0 ? !(st.valid && st.pt == id) : d.pairs[d.R[k - 1]].id != id;
-        if (!head && k != 0) continue;   // (a run is walked by the thread of its first pair)
-        int cur = head ? i0 : -1, acc = 0;
-        double l0 = st.m2[0], l1 = st.m2[1], l2 = st.m2[2], l3 = st.m2[3];
-        for (int kk = k; kk < nr; kk++) {
-            const int i = d.R[kk];
-            if (kk > k && d.pairs[i].id != id) break;
-            const double* m = d.m2 + 4 * i;
-            bool refresh = kk == k && head;
-            if (!refresh) {
-                const double ax = m[0] - l0, ay = m[2] - l2, bx = m[1] - l1, by = m[3] - l3;   // columns m2.T()[0], m2.T()[1]
-                refresh = ax * ax + ay * ay > lim || bx * bx + by * by > lim;
-            }
-            if (refresh) {
-                cur = i;
-                l0 = m[0], l1 = m[1], l2 = m[2], l3 = m[3];
-                acc = 0;
-            } else
-                acc |= d.detbad[i];
-            d.refresh[i] = refresh;
-            d.srcp[i] = cur;
-            d.dacc[i] = acc;
-        }
-    }
-}
-__global__ void __launch_bounds__(256) rp_template_kernel(RpDev d) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= d.n || !d.reach[i] || !d.refresh[i]) return;
-    ptam_template_result tr;
-    const int T = wave_make_template(d.jobs[i], lane, tr);
-    d.tm[(size_t)i * 64 + lane] = (uint8_t)T;
-    if (lane == 0) d.tres[i] = tr;
-}
-__global__ void __launch_bounds__(256) rp_search_kernel(RpDev d) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= d.n) return;
-    ptam_refind_result o;
-    o.found = 0;
-    o.level = -1;
-    o.sub_pix = 0;
-    o.never_retry = d.pairs[i].skip ? 0 : 1;
-    o.root_pos[0] = o.root_pos[1] = 0;
-    int kept = 0;
-    if (d.reach[i]) {
-        const int src = d.srcp[i], refresh = d.refresh[i];
-        const int T = src >= 0 ? d.tm[(size_t)src * 64 + lane] : d.st->tpl[lane];
-        const int bad = refresh ? d.tres[i].bad : (((src >= 0 ? d.tres[src].bad : d.st->bad) != 0) || d.dacc[i]);
-        kept = !refresh;
-        const ptam_patch_query q = d.q[i];
-        o.level = q.level;
-        if (lane == 0) d.bad[i] = bad;
-        const KfLevels& L = d.Ls[d.pairs[i].kf];
-        ptam_patch_result res;
-        __shared__ __attribute__((aligned(16))) unsigned rp_win[4][SW_BYTES / 4];
-        wave_find_patch_coarse(L, q, !bad, T, lane, res, rp_win[threadIdx.x >> 6]);   // :982-988 (range 4)
-        if (!bad && res.found) {
-            o.found = 1;
-            o.never_retry = 0;
-            if (q.level > 0) {                                                          // :1000-1006 (convergence is not looked at)
-                ptam_subpix_query sq;
-                sq.level = q.level;
-                sq.max_its = 8;
-                sq.coarse_pos[0] = res.pos[0];
-                sq.coarse_pos[1] = res.pos[1];
-                ptam_subpix_result sres;
-                wave_subpix(L, sq, T, lane, sres, (uint8_t*)rp_win[threadIdx.x >> 6]);   // (the search is done with the buffer)
-                o.sub_pix = 1;
-                o.root_pos[0] = sres.pos[0];
-                o.root_pos[1] = sres.pos[1];
-            } else {
-                o.root_pos[0] = res.pos[0];
-                o.root_pos[1] = res.pos[1];
-            }
-        }
-    }
-    if (lane == 0) {
-        d.out[i] = o;
-        d.kept[i] = kept;
-    }
-}
-__global__ void __launch_bounds__(64) rp_state_kernel(RpDev d) {
-    const int nr = *d.nr, lane = threadIdx.x;
-    if (nr == 0) return;
-    const int last = d.R[nr - 1], src = d.srcp[last];
-    if (src >= 0) {
-        d.st->tpl[lane] = d.tm[(size_t)src * 64 + lane];
-        if (lane == 0) {
-            d.st->pt = d.pairs[last].id;
-            for (int k = 0; k < 4; k++) d.st->m2[k] = d.m2[4 * src + k];
-            d.st->valid = 1;
-        }
-    }
-    if (lane == 0) d.st->bad = d.bad[last];
-}
+static const tm_pose_fn tm_pose_fns[3] = {tm_pose_kernel<1, GS_WAVE_LIMIT>, tm_pose_kernel<1, GS_THREADS>, tm_pose_kernel<GS_MPT, GS_THREADS>};
 
 // =================================================================================================
 // ---- a batch of frames in ONE chain of launches (ptam_track_map_frames_batch) ----
@@ -1178,15 +857,9 @@ __global__ void __launch_bounds__(THREADS) tm_pose_batch_kernel(DevCam cam, cons
     const PoseBatchItem& pi = pitems[blockIdx.x];
     tm_pose_body<MPT, THREADS>(cam, it.d, stage, coarse_min, it.mbox, opts, pi.io, pi.updates, 0ull);
 }
-static void tm_pose_launch_batch(ptam_ctx* ctx, int nb, int cap, const TmBatchItem* d_it, const PoseBatchItem* d_p, int stage, unsigned coarse_min,
-                                 const ptam_gn_opts& g) {
-    if (cap <= GS_WAVE_LIMIT)
-        hipLaunchKernelGGL((tm_pose_batch_kernel<1, GS_WAVE_LIMIT>), dim3(nb), dim3(GS_WAVE_LIMIT), 0, ctx->stream, ctx->cam, d_it, d_p, stage, coarse_min, g);
-    else if (cap <= GS_THREADS)
-        hipLaunchKernelGGL((tm_pose_batch_kernel<1, GS_THREADS>), dim3(nb), dim3(GS_THREADS), 0, ctx->stream, ctx->cam, d_it, d_p, stage, coarse_min, g);
-    else
-        hipLaunchKernelGGL((tm_pose_batch_kernel<GS_MPT, GS_THREADS>), dim3(nb), dim3(GS_THREADS), 0, ctx->stream, ctx->cam, d_it, d_p, stage, coarse_min, g);
-}
+typedef void (*tm_pose_batch_fn)(DevCam, const TmBatchItem*, const PoseBatchItem*, int, unsigned, ptam_gn_opts);
+static const tm_pose_batch_fn tm_pose_batch_fns[3] = {tm_pose_batch_kernel<1, GS_WAVE_LIMIT>, tm_pose_batch_kernel<1, GS_THREADS>,
+                                                      tm_pose_batch_kernel<GS_MPT, GS_THREADS>};
 
 struct ptam_tracker {
     ptam_ctx* ctx;
@@ -1211,6 +884,70 @@ struct ptam_tracker {
     double stage_ms[PTAM_TS_COUNT];
     int stage_frames;
 };
+
+// ---- what the two ways of launching a frame share (track_map_impl passes the frame by value, ptam_track_map_frames_batch uploads
+//      an array of frames) ----
+// (A/B builds, `make ab`: the pyramid | FAST as two launches; the gather pass + pose kernel of rounds 2-3 instead of the fused one)
+static const bool tm_kf_two = ptam_ab_env("PTAM_TM_KF_TWO_LAUNCHES") != nullptr;
+static const bool tm_no_fuse = ptam_ab_env("PTAM_TM_NO_FUSE") != nullptr;
+
+// the instantiation of a kernel template for the context's halfSample variant
+#define TM_HS_KERNEL(ctx, kernel) ((ctx)->halfsample == PTAM_HALFSAMPLE_T ? kernel<PTAM_HALFSAMPLE_T> : kernel<PTAM_HALFSAMPLE_R>)
+
+// the caller's options, or the reference's, checked
+static int tm_opts(const ptam_trackmap_opts* opts, ptam_trackmap_opts* o) {
+    ptam_trackmap_opts_default(o);
+    if (opts) *o = *opts;
+    ARG_TRY(o->max_patches >= 0 && o->coarse_subpix_its >= 0 && o->coarse_subpix_its <= 64);
+    // (coarse_max / coarse_min become ints on the device and size the coarse search grid: a value past INT_MAX / 2 turned the
+    //  set sizes negative and the set choice wrote outside its lists; the range is a pixel radius inside a 640-pixel image)
+    ARG_TRY(o->coarse_max <= (unsigned)INT_MAX / 2 && o->coarse_min <= (unsigned)INT_MAX / 2 && o->coarse_range <= 4096u);
+    ARG_TRY(o->estimator == PTAM_EST_TUKEY || o->estimator == PTAM_EST_CAUCHY || o->estimator == PTAM_EST_HUBER);
+    return PTAM_OK;
+}
+// the pose loop's schedule: stage 0 coarse (:554-568), stage 1 fine (:613-643)
+static ptam_gn_opts tm_gn_opts(int stage, int estimator) {
+    ptam_gn_opts g;
+    ptam_gn_opts_default(&g);           // the fine schedule
+    g.estimator = estimator;
+    if (stage == 0) {
+        g.nonlinear_mask = 0x3ff;       // every coarse iteration re-projects (:556-562)
+        g.override_sigma_sq = 1.0;      // :565
+        g.mark_outliers_iter = -1;      // CalcPoseUpdate(vIterationSet, dOverrideSigma): bMarkOutliers defaults to false
+    }
+    return g;
+}
+// what a tracker's pose loop leaves behind: the coarse one the TrackerData state of its measurements, the fine one the depth sums and
+// — its last act — pose, depth sums and the sequence word in the mailbox
+static PoseChainIo tm_chain_io(const ptam_tracker* t, int stage, unsigned long long seq) {
+    const TmDev& d = t->d;
+    PoseChainIo io{};
+    if (stage == 0) {
+        io.td_base = &d.pvs[0].proj;
+        io.td_index = d.midx;
+        io.td_stride = (int)sizeof(ptam_pvs_result);
+    } else {
+        io.depth_out = d.ctl->depth;
+        io.result_pose = t->mbox_dev->res.pose;
+        io.result_depth = t->mbox_dev->depth3;
+        io.result_seq = &t->mbox_dev->seq;
+        io.seq = seq;
+    }
+    return io;
+}
+// wait until the tracker's mailbox carries sequence number seq; *word (nullable): the word as read, POSE_CHAIN_LONG included
+static int tm_wait_seq(const ptam_tracker* t, hipStream_t st, unsigned long long seq, const char* what, unsigned long long* word = nullptr) {
+    unsigned long long v = 0;
+    const int rc = ptam_wait_mapped(st, what, [&] { return ((v = *(volatile unsigned long long*)&t->mbox->seq) & ~POSE_CHAIN_LONG) == seq; });
+    if (word) *word = v;
+    return rc;
+}
+static void tm_read_result(const ptam_tracker* t, ptam_trackmap_result* out) {
+    std::memcpy(out, (const void*)&t->mbox->res, sizeof *out);
+    out->depth_sum = t->mbox->depth3[0];
+    out->depth_sum_sq = t->mbox->depth3[1];
+    out->depth_n = (int)t->mbox->depth3[2];
+}
 
 extern "C" {
 
@@ -1456,28 +1193,29 @@ int ptam_tracker_set_shuffle(ptam_tracker* t, const int32_t* shuffle_levels, con
 // d_new_frame (nullable): the current keyframe is made first — KeyFrame::MakeKeyFrame_Lite of this device-resident image, in
 // the same queue.  (Measured and dropped: the keyframe kernels on a second queue beside the PVS pass and the set choice, which
 // do not look at the image — the two cross-queue event waits cost more than the 13 us of overlap: 207-218 vs 193-200 us.)
+// The frame's arguments ride in the launches: nothing is uploaded.
 static int track_map_impl(ptam_tracker* t, ptam_kf* cur, const uint8_t* d_new_frame, const double pose_in[12],
                           const ptam_trackmap_opts* opts, ptam_trackmap_result* out) {
     ARG_TRY(t && cur && pose_in && out);
     ptam_ctx* ctx = t->ctx;
     ARG_TRY(cur->device == ctx->device);
     ptam_trackmap_opts o;
-    if (opts)
-        o = *opts;
-    else
-        ptam_trackmap_opts_default(&o);
-    ARG_TRY(o.max_patches >= 0 && o.coarse_subpix_its >= 0 && o.coarse_subpix_its <= 64);
-    // (coarse_max / coarse_min become ints on the device and size the coarse search grid: a value past INT_MAX / 2 turned the
-    //  set sizes negative and the set choice wrote outside its lists; the range is a pixel radius inside a 640-pixel image)
-    ARG_TRY(o.coarse_max <= (unsigned)INT_MAX / 2 && o.coarse_min <= (unsigned)INT_MAX / 2 && o.coarse_range <= 4096u);
-    ARG_TRY(o.estimator == PTAM_EST_TUKEY || o.estimator == PTAM_EST_CAUCHY || o.estimator == PTAM_EST_HUBER);
+    int rc = tm_opts(opts, &o);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const TmDev& d = t->d;
-    const int n = d.n;
+    const int n = d.n, n_fine = std::max(n, 1);
     hipStream_t st = ctx->stream;
-    int rc = PTAM_OK;
     const bool prof = t->prof && d_new_frame;
-    if (prof) hipEventRecord(t->ev[PTAM_TS_PYR_PVS], st);
+    auto mark = [&](int stage) {   // stage timing (ptam_tracker_set_profiling): the launches that follow belong to `stage`
+        if (prof) hipEventRecord(t->ev[stage], st);
+    };
+    auto gather = [&](int cap, int stage) {
+        hipLaunchKernelGGL(tm_gather_kernel, dim3(std::max(1, (cap + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS)), dim3(TM_GATHER_THREADS), 0, st, d, stage,
+                           o.coarse_subpix_its, o.coarse_min, t->mbox_dev);
+    };
+    // ---- keyframe + PVS + set choice ----
+    mark(PTAM_TS_PYR_PVS);
     if (d_new_frame) {
         // KeyFrame::MakeKeyFrame_Lite (src/KeyFrame.cc:18-54) of the new image, the PVS pass (:453-478, the pose rides in as an
         // argument) and the set choice (:480-611) in three launches
@@ -1488,139 +1226,95 @@ static int track_map_impl(ptam_tracker* t, ptam_kf* cur, const uint8_t* d_new_fr
         std::memcpy(pv.v, pose_in, 96);
         pv.use = 1;
         const int n_pyr = gx * gy, n_pvs = std::max(1, (n + 255) / 256);
-        static const bool kf_two = ptam_ab_env("PTAM_TM_KF_TWO_LAUNCHES") != nullptr;   // (A/B builds: pyramid | FAST as two launches)
-        if (!kf_two) {
+        if (!tm_kf_two) {
             const int n_tiles = cur->n_blocks;
-            if (ctx->halfsample == PTAM_HALFSAMPLE_T)
-                hipLaunchKernelGGL(tm_kf_pvs_kernel<PTAM_HALFSAMPLE_T>, dim3(n_tiles + n_pvs), dim3(256), 0, st, pa, cur->L, n_tiles, ctx->cam, std::max(n, 0),
-                                   (const ptam_pvs_point*)d.pts, d.pvs, pv, d.pose, &d.finder->bad);
-            else
-                hipLaunchKernelGGL(tm_kf_pvs_kernel<PTAM_HALFSAMPLE_R>, dim3(n_tiles + n_pvs), dim3(256), 0, st, pa, cur->L, n_tiles, ctx->cam, std::max(n, 0),
-                                   (const ptam_pvs_point*)d.pts, d.pvs, pv, d.pose, &d.finder->bad);
-            if (prof) hipEventRecord(t->ev[PTAM_TS_DETECT], st);
+            hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_kf_pvs_kernel), dim3(n_tiles + n_pvs), dim3(256), 0, st, pa, cur->L, n_tiles, ctx->cam, std::max(n, 0),
+                               (const ptam_pvs_point*)d.pts, d.pvs, pv, d.pose, &d.finder->bad);
+            mark(PTAM_TS_DETECT);
         } else {
-            if (ctx->halfsample == PTAM_HALFSAMPLE_T)
-                hipLaunchKernelGGL(tm_pyr_pvs_kernel<PTAM_HALFSAMPLE_T>, dim3(n_pyr + n_pvs), dim3(256), 0, st, pa, gx, n_pyr, ctx->cam, std::max(n, 0),
-                                   (const ptam_pvs_point*)d.pts, d.pvs, pv, d.pose, &d.finder->bad);
-            else
-                hipLaunchKernelGGL(tm_pyr_pvs_kernel<PTAM_HALFSAMPLE_R>, dim3(n_pyr + n_pvs), dim3(256), 0, st, pa, gx, n_pyr, ctx->cam, std::max(n, 0),
-                                   (const ptam_pvs_point*)d.pts, d.pvs, pv, d.pose, &d.finder->bad);
-            if (prof) hipEventRecord(t->ev[PTAM_TS_DETECT], st);
+            hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_pyr_pvs_kernel), dim3(n_pyr + n_pvs), dim3(256), 0, st, pa, gx, n_pyr, ctx->cam, std::max(n, 0),
+                               (const ptam_pvs_point*)d.pts, d.pvs, pv, d.pose, &d.finder->bad);
+            mark(PTAM_TS_DETECT);
             kf_launch_detect(cur, st);
         }
-        if (prof) hipEventRecord(t->ev[PTAM_TS_COMPACT_SELECT], st);
+        mark(PTAM_TS_COMPACT_SELECT);
         hipLaunchKernelGGL(tm_compact_select_kernel, dim3(1 + fast_compact_blocks(cur->L)), dim3(1024), 0, st, cur->L, d, o);
     } else {
-        rc = pvs_launch_dev(ctx, n, d.pts, d.pose, pose_in, d.pvs, &d.finder->bad, (int)sizeof(TmFinder));                         // :453-478 (the pose rides in as an argument)
+        rc = pvs_launch_dev(ctx, n, d.pts, d.pose, pose_in, d.pvs, &d.finder->bad, (int)sizeof(TmFinder));   // :453-478 (the pose rides in as an argument)
         if (rc) return rc;
-        hipLaunchKernelGGL(tm_select_kernel, dim3(1), dim3(1024), 0, st, d, o);             // :480-611
+        hipLaunchKernelGGL(tm_select_kernel, dim3(1), dim3(1024), 0, st, d, o);   // :480-611
     }
     // ---- coarse stage :519-569 ----
     const int ncc = std::max(1, std::min(n, (int)o.coarse_max));
-    if (prof) hipEventRecord(t->ev[PTAM_TS_SEARCH_COARSE], st);
+    mark(PTAM_TS_SEARCH_COARSE);
     hipLaunchKernelGGL(tm_search_kernel, dim3((ncc + 3) / 4), dim3(256), 0, st, ctx->cam, cur->L, d, 0, o.coarse_range, o.coarse_subpix_its);
-    if (prof) hipEventRecord(t->ev[PTAM_TS_GATHER_COARSE], st);
-    static const bool no_fuse = ptam_ab_env("PTAM_TM_NO_FUSE") != nullptr;   // (A/B runs: the gather pass + pose kernel of rounds 2-3)
+    mark(PTAM_TS_GATHER_COARSE);
+    void* d_st;
     double* d_upd;
-    {
-        void* s_;
-        rc = pose_chain_scratch(ctx, std::max(n, 1), &s_, &d_upd);
+    rc = pose_chain_scratch(ctx, n_fine, &d_st, &d_upd);
+    if (rc) return rc;
+    int thr;
+    ptam_gn_opts g = tm_gn_opts(0, o.estimator);
+    PoseChainIo io = tm_chain_io(t, 0, 0);
+    if (ncc <= GS_LIMIT && !tm_no_fuse) {
+        // SearchForPoints' bookkeeping and the ten coarse iterations in one launch (the coarse set holds at most CoarseMax slots)
+        mark(PTAM_TS_POSE_COARSE);
+        const tm_pose_fn fn = tm_pose_fns[tm_pose_shape(ncc, &thr)];
+        hipLaunchKernelGGL(fn, dim3(1), dim3(thr), 0, st, ctx->cam, d, 0, o.coarse_min, t->mbox_dev, g, io, d_upd, 0ull);
+    } else {
+        gather(ncc, 0);
+        mark(PTAM_TS_POSE_COARSE);
+        rc = pose_launch_chain(ctx, ncc, &d.ctl->n_meas_coarse, d.meas, d.entry, d.pose, &g, nullptr, io);
         if (rc) return rc;
     }
-    {
-        ptam_gn_opts g;
-        ptam_gn_opts_default(&g);
-        g.nonlinear_mask = 0x3ff;       // every coarse iteration re-projects (:556-562)
-        g.override_sigma_sq = 1.0;      // :565
-        g.mark_outliers_iter = -1;      // CalcPoseUpdate(vIterationSet, dOverrideSigma): bMarkOutliers defaults to false
-        g.estimator = o.estimator;
-        PoseChainIo io{};
-        io.td_base = &d.pvs[0].proj;
-        io.td_index = d.midx;
-        io.td_stride = (int)sizeof(ptam_pvs_result);
-        if (ncc <= GS_LIMIT && !no_fuse) {
-            // SearchForPoints' bookkeeping and the ten coarse iterations in one launch (the coarse set holds at most CoarseMax slots)
-            if (prof) hipEventRecord(t->ev[PTAM_TS_POSE_COARSE], st);
-            int thr;
-            const tm_pose_fn fn = tm_pose_pick(ncc, &thr);
-            hipLaunchKernelGGL(fn, dim3(1), dim3(thr), 0, st, ctx->cam, d, 0, o.coarse_min, t->mbox_dev, g, io, d_upd, 0ull);
-        } else {
-            hipLaunchKernelGGL(tm_gather_kernel, dim3(std::max(1, (ncc + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS)), dim3(TM_GATHER_THREADS), 0, st, d, 0, o.coarse_subpix_its, o.coarse_min, t->mbox_dev);
-            if (prof) hipEventRecord(t->ev[PTAM_TS_POSE_COARSE], st);
-            rc = pose_launch_chain(ctx, ncc, &d.ctl->n_meas_coarse, d.meas, d.entry, d.pose, &g, nullptr, io);
-            if (rc) return rc;
-        }
-    }
     // ---- fine stage :571-643 ----
-    if (prof) hipEventRecord(t->ev[PTAM_TS_SEARCH_FINE], st);
+    mark(PTAM_TS_SEARCH_FINE);
     hipLaunchKernelGGL(tm_search_kernel, dim3(std::max(1, (n + 3) / 4)), dim3(256), 0, st, ctx->cam, cur->L, d, 1, 0u, 0);
-    if (prof) hipEventRecord(t->ev[PTAM_TS_GATHER_FINE], st);
+    mark(PTAM_TS_GATHER_FINE);
     const unsigned long long seq = ++t->seq;
     t->last_stream = st;
-    {
-        ptam_gn_opts g;
-        ptam_gn_opts_default(&g);       // fine schedule :613-643
-        g.estimator = o.estimator;
-        PoseChainIo io{};
-        io.depth_out = d.ctl->depth;
-        io.result_pose = t->mbox_dev->res.pose;      // the loop's last act: pose + depth sums + sequence word into the mailbox
-        io.result_depth = t->mbox_dev->depth3;
-        io.result_seq = &t->mbox_dev->seq;
-        io.seq = seq;
-        bool fused = !no_fuse;
-        if (fused) {
-            // bookkeeping + the ten fine iterations in one launch.  The iteration set holds at most max(MaxPatchesPerFrame, coarse
-            // + top-level set) slots: with more than the kernel's 1024 it says so instead (POSE_CHAIN_LONG) and the gather pass
-            // and the general kernel follow
-            if (prof) hipEventRecord(t->ev[PTAM_TS_POSE_FINE], st);
-            int thr;
-            const tm_pose_fn fn = tm_pose_pick(std::min(std::max(n, 1), GS_LIMIT), &thr);
-            hipLaunchKernelGGL(fn, dim3(1), dim3(thr), 0, st, ctx->cam, d, 1, o.coarse_min, t->mbox_dev, g, io, d_upd, n > GS_LIMIT ? seq : 0ull);
-        } else {
-            hipLaunchKernelGGL(tm_gather_kernel, dim3(std::max(1, (n + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS)), dim3(TM_GATHER_THREADS), 0, st, d, 1, o.coarse_subpix_its, o.coarse_min, t->mbox_dev);
-            if (prof) hipEventRecord(t->ev[PTAM_TS_POSE_FINE], st);
-            rc = pose_launch_chain(ctx, std::max(n, 1), &d.ctl->n_meas, d.meas, d.entry, d.pose, &g, d.outlier, io, 1);
-            if (rc) return rc;
-        }
-        if (prof) hipEventRecord(t->ev[PTAM_TS_COUNT], st);
-        HIP_TRY(hipGetLastError());
-        // the frame's last kernel publishes the sequence number — or, for a list of more than 1024 entries, asks for the
-        // general path, which then publishes it
-        for (int pass = 0; pass < 3; pass++) {
-            unsigned spins = 0;
-            unsigned long long v;
-            while (((v = *(volatile unsigned long long*)&t->mbox->seq) & ~POSE_CHAIN_LONG) != seq) {
-                if (++spins == 100000) {
-                    spins = 0;
-                    const hipError_t q = hipStreamQuery(st);
-                    if (q != hipSuccess && q != hipErrorNotReady) {
-                        ptam_set_error("track_map: stream failed: %s", hipGetErrorString(q));
-                        return PTAM_E_HIP;
-                    }
-                    if (q == hipSuccess && (*(volatile unsigned long long*)&t->mbox->seq & ~POSE_CHAIN_LONG) != seq) return PTAM_E_HIP;
-                }
-            }
-            if (!(v & POSE_CHAIN_LONG)) break;
-            if (pass == 2) return PTAM_E_STATE;
-            t->mbox->seq = 0;   // (the stream is idle: nobody else writes the word until the next kernel does)
-            if (fused) {
-                // more slots than the fused kernel holds: compact them, then the register-resident kernel if the FOUND ones fit
-                // (it says so otherwise: next pass)
-                fused = false;
-                hipLaunchKernelGGL(tm_gather_kernel, dim3(std::max(1, (n + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS)), dim3(TM_GATHER_THREADS), 0, st, d, 1, o.coarse_subpix_its, o.coarse_min, t->mbox_dev);
-                rc = pose_launch_chain(ctx, std::max(n, 1), &d.ctl->n_meas, d.meas, d.entry, d.pose, &g, d.outlier, io, 1);
-            } else {
-                rc = pose_launch_chain(ctx, std::max(n, 1), &d.ctl->n_meas, d.meas, d.entry, d.pose, &g, d.outlier, io, 2);
-            }
-            if (rc) return rc;
-            HIP_TRY(hipGetLastError());
-        }
+    g = tm_gn_opts(1, o.estimator);
+    io = tm_chain_io(t, 1, seq);
+    auto fine_chain = [&](int mode) { return pose_launch_chain(ctx, n_fine, &d.ctl->n_meas, d.meas, d.entry, d.pose, &g, d.outlier, io, mode); };
+    bool fused = !tm_no_fuse;
+    if (fused) {
+        // bookkeeping + the ten fine iterations in one launch.  The iteration set holds at most max(MaxPatchesPerFrame, coarse
+        // + top-level set) slots: with more than the kernel's 1024 it says so instead (POSE_CHAIN_LONG) and the gather pass
+        // and the general kernel follow
+        mark(PTAM_TS_POSE_FINE);
+        const tm_pose_fn fn = tm_pose_fns[tm_pose_shape(std::min(n_fine, GS_LIMIT), &thr)];
+        hipLaunchKernelGGL(fn, dim3(1), dim3(thr), 0, st, ctx->cam, d, 1, o.coarse_min, t->mbox_dev, g, io, d_upd, n > GS_LIMIT ? seq : 0ull);
+    } else {
+        gather(n, 1);
+        mark(PTAM_TS_POSE_FINE);
+        rc = fine_chain(1);
+        if (rc) return rc;
     }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    std::memcpy(out, (const void*)&t->mbox->res, sizeof *out);
-    out->depth_sum = t->mbox->depth3[0];
-    out->depth_sum_sq = t->mbox->depth3[1];
-    out->depth_n = (int)t->mbox->depth3[2];
+    mark(PTAM_TS_COUNT);
+    HIP_TRY(hipGetLastError());
+    // ---- wait: the frame's last kernel publishes the sequence number — or, for a list of more than 1024 entries, asks for the
+    // general path, which then publishes it ----
+    for (int pass = 0; pass < 3; pass++) {
+        unsigned long long v;
+        rc = tm_wait_seq(t, st, seq, "the frame's result", &v);
+        if (rc) return rc;
+        if (!(v & POSE_CHAIN_LONG)) break;
+        if (pass == 2) return PTAM_E_STATE;
+        t->mbox->seq = 0;   // (the stream is idle: nobody else writes the word until the next kernel does)
+        if (fused) {
+            // more slots than the fused kernel holds: compact them, then the register-resident kernel if the FOUND ones fit
+            // (it says so otherwise: next pass)
+            fused = false;
+            gather(n, 1);
+            rc = fine_chain(1);
+        } else {
+            rc = fine_chain(2);
+        }
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+    }
+    // ---- result ----
+    tm_read_result(t, out);
     if (prof) {
         HIP_TRY(hipEventSynchronize(t->ev[PTAM_TS_COUNT]));
         for (int i = 0; i < PTAM_TS_COUNT; i++) {
@@ -1664,6 +1358,23 @@ int ptam_track_map_frame(ptam_tracker* t, ptam_kf* cur, const uint8_t* d_frame, 
     return track_map_impl(t, cur, d_frame, pose_in, opts, out);
 }
 
+// one frame's pose loop of a batch: what pose_launch_chain takes as arguments (updates, st: the frame's own context's scratch)
+static PoseBatchItem tm_pose_item(const ptam_tracker* t, int stage, int n_cap, double* updates, void* st, unsigned long long seq) {
+    const TmDev& d = t->d;
+    PoseBatchItem p;
+    std::memset(&p, 0, sizeof p);
+    p.n_cap = n_cap;
+    p.n_dev = stage ? &d.ctl->n_meas : &d.ctl->n_meas_coarse;
+    p.meas = d.meas;
+    p.entry = d.entry;
+    p.pose_io = d.pose;
+    p.flags = stage ? d.outlier : nullptr;
+    p.updates = updates;
+    p.st = st;
+    p.io = tm_chain_io(t, stage, seq);
+    return p;
+}
+
 // nb frames of nb independent trackers — each with its own map, keyframe and motion-model prediction — as ONE chain of
 // launches on the first tracker's queue (see TmBatchItem).  Per frame the result is what ptam_track_map_frame gives (the same
 // kernel bodies on the same data).  All trackers must live on one device and share camera model, image geometry and
@@ -1675,15 +1386,8 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
     ptam_tracker* lead = ts[0];
     ptam_ctx* ctx = lead->ctx;
     ptam_trackmap_opts o;
-    if (opts)
-        o = *opts;
-    else
-        ptam_trackmap_opts_default(&o);
-    ARG_TRY(o.max_patches >= 0 && o.coarse_subpix_its >= 0 && o.coarse_subpix_its <= 64);
-    // (coarse_max / coarse_min become ints on the device and size the coarse search grid: a value past INT_MAX / 2 turned the
-    //  set sizes negative and the set choice wrote outside its lists; the range is a pixel radius inside a 640-pixel image)
-    ARG_TRY(o.coarse_max <= (unsigned)INT_MAX / 2 && o.coarse_min <= (unsigned)INT_MAX / 2 && o.coarse_range <= 4096u);
-    ARG_TRY(o.estimator == PTAM_EST_TUKEY || o.estimator == PTAM_EST_CAUCHY || o.estimator == PTAM_EST_HUBER);
+    int rc = tm_opts(opts, &o);
+    if (rc) return rc;
     const KfLevels& L0 = curs[0]->L;
     for (int i = 0; i < nb; i++) {
         ARG_TRY(ts[i]->ctx->device == ctx->device && curs[i]->device == ctx->device);
@@ -1700,7 +1404,7 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
     // ---- the argument arrays: [nb TmBatchItem | nb PoseBatchItem (coarse) | nb PoseBatchItem (fine)] ----
     const size_t b_items = (size_t)nb * sizeof(TmBatchItem), b_pose = (size_t)nb * sizeof(PoseBatchItem), b_all = b_items + 2 * b_pose;
     void* pin;
-    int rc = ctx_pinned(ctx, b_all + 64, &pin);
+    rc = ctx_pinned(ctx, b_all + 64, &pin);
     if (rc) return rc;
     if (lead->batch_cap < b_all) {
         HIP_TRY(ptam_stream_wait(st));
@@ -1717,7 +1421,6 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
     const PoseBatchItem* d_pc = (const PoseBatchItem*)((const char*)lead->batch_dev + b_items);
     const PoseBatchItem* d_pf = d_pc + nb;
     int gx = 0, gy = 0, n_max = 0, ncc_max = 1;
-    std::vector<unsigned long long> seqs((size_t)nb);
     for (int i = 0; i < nb; i++) {
         ptam_tracker* t = ts[i];
         TmBatchItem& it = h_it[i];
@@ -1737,104 +1440,57 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
         double* su;
         rc = pose_chain_scratch(t->ctx, std::max(n, 1), &sst, &su);   // (sized for the fine loop; the coarse one uses its start)
         if (rc) return rc;
-        PoseBatchItem& pc = h_pc[i];
-        std::memset(&pc, 0, sizeof pc);
-        pc.n_cap = ncc;
-        pc.n_dev = &t->d.ctl->n_meas_coarse;
-        pc.meas = t->d.meas;
-        pc.entry = t->d.entry;
-        pc.pose_io = t->d.pose;
-        pc.flags = nullptr;
-        pc.updates = su;
-        pc.st = sst;
-        pc.io.td_base = &t->d.pvs[0].proj;
-        pc.io.td_index = t->d.midx;
-        pc.io.td_stride = (int)sizeof(ptam_pvs_result);
-        PoseBatchItem& pf = h_pf[i];
-        std::memset(&pf, 0, sizeof pf);
-        pf.n_cap = std::max(n, 1);
-        pf.n_dev = &t->d.ctl->n_meas;
-        pf.meas = t->d.meas;
-        pf.entry = t->d.entry;
-        pf.pose_io = t->d.pose;
-        pf.flags = t->d.outlier;
-        pf.updates = su;
-        pf.st = sst;
-        seqs[(size_t)i] = ++t->seq;
+        h_pc[i] = tm_pose_item(t, 0, ncc, su, sst, 0);
+        h_pf[i] = tm_pose_item(t, 1, std::max(n, 1), su, sst, ++t->seq);
         t->last_stream = st;
-        pf.io.depth_out = t->d.ctl->depth;
-        pf.io.result_pose = t->mbox_dev->res.pose;
-        pf.io.result_depth = t->mbox_dev->depth3;
-        pf.io.result_seq = &t->mbox_dev->seq;
-        pf.io.seq = seqs[(size_t)i];
     }
     HIP_TRY(hipMemcpyAsync(lead->batch_dev, pin, b_all, hipMemcpyHostToDevice, st));
+    const int n_fine = std::max(n_max, 1);
+    auto gather = [&](int cap, int stage) {
+        hipLaunchKernelGGL(tm_gather_batch_kernel, dim3(std::max(1, (cap + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS), nb), dim3(TM_GATHER_THREADS), 0, st,
+                           d_it, stage, (int)o.coarse_subpix_its, o.coarse_min);
+    };
+    // ---- keyframe + PVS + set choice ----
     const int n_pyr = gx * gy, n_pvs = std::max(1, (n_max + 255) / 256);
-    if (ctx->halfsample == PTAM_HALFSAMPLE_T)
-        hipLaunchKernelGGL(tm_pyr_pvs_batch_kernel<PTAM_HALFSAMPLE_T>, dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, gx, ctx->cam);
-    else
-        hipLaunchKernelGGL(tm_pyr_pvs_batch_kernel<PTAM_HALFSAMPLE_R>, dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, gx, ctx->cam);
+    hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_pyr_pvs_batch_kernel), dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, gx, ctx->cam);
     kf_launch_detect_batch(nb, L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L), st);
     hipLaunchKernelGGL(tm_compact_select_batch_kernel, dim3(1 + fast_compact_blocks(L0), nb), dim3(1024), 0, st, d_it, o);
-    // ---- coarse stage :519-569 ----
-    hipLaunchKernelGGL(tm_search_batch_kernel, dim3((ncc_max + 3) / 4, nb), dim3(256), 0, st, ctx->cam, d_it, 0, o.coarse_range, o.coarse_subpix_its);
     // (fused bookkeeping + pose loop per stage when no frame's list can outgrow the register-resident kernel: maps of at most
     //  1024 points; larger maps keep the gather pass and the small / general kernel pair)
-    static const bool no_fuse = ptam_ab_env("PTAM_TM_NO_FUSE") != nullptr;
-    const bool fuse = !no_fuse && n_max <= GS_LIMIT && ncc_max <= GS_LIMIT;
-    {
-        ptam_gn_opts g;
-        ptam_gn_opts_default(&g);
-        g.nonlinear_mask = 0x3ff;       // every coarse iteration re-projects (:556-562)
-        g.override_sigma_sq = 1.0;      // :565
-        g.mark_outliers_iter = -1;
-        g.estimator = o.estimator;
-        if (fuse)
-            tm_pose_launch_batch(ctx, nb, ncc_max, d_it, d_pc, 0, o.coarse_min, g);
-        else {
-            hipLaunchKernelGGL(tm_gather_batch_kernel, dim3(std::max(1, (ncc_max + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS), nb), dim3(TM_GATHER_THREADS), 0, st,
-                               d_it, 0, (int)o.coarse_subpix_its, o.coarse_min);
-            rc = pose_launch_chain_batch(ctx, nb, ncc_max, d_pc, &g);
-            if (rc) return rc;
-        }
+    const bool fuse = !tm_no_fuse && n_max <= GS_LIMIT && ncc_max <= GS_LIMIT;
+    int thr;
+    // ---- coarse stage :519-569 ----
+    hipLaunchKernelGGL(tm_search_batch_kernel, dim3((ncc_max + 3) / 4, nb), dim3(256), 0, st, ctx->cam, d_it, 0, o.coarse_range, o.coarse_subpix_its);
+    ptam_gn_opts g = tm_gn_opts(0, o.estimator);
+    if (fuse) {
+        const tm_pose_batch_fn fn = tm_pose_batch_fns[tm_pose_shape(ncc_max, &thr)];
+        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_pc, 0, o.coarse_min, g);
+    } else {
+        gather(ncc_max, 0);
+        rc = pose_launch_chain_batch(ctx, nb, ncc_max, d_pc, &g);
+        if (rc) return rc;
     }
     // ---- fine stage :571-643 ----
     hipLaunchKernelGGL(tm_search_batch_kernel, dim3(std::max(1, (n_max + 3) / 4), nb), dim3(256), 0, st, ctx->cam, d_it, 1, 0u, 0);
-    {
-        ptam_gn_opts g;
-        ptam_gn_opts_default(&g);       // fine schedule :613-643
-        g.estimator = o.estimator;
-        if (fuse)
-            tm_pose_launch_batch(ctx, nb, std::max(n_max, 1), d_it, d_pf, 1, o.coarse_min, g);
-        else {
-            hipLaunchKernelGGL(tm_gather_batch_kernel, dim3(std::max(1, (n_max + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS), nb), dim3(TM_GATHER_THREADS), 0, st,
-                               d_it, 1, (int)o.coarse_subpix_its, o.coarse_min);
-            rc = pose_launch_chain_batch(ctx, nb, std::max(n_max, 1), d_pf, &g);
-            if (rc) return rc;
-        }
+    g = tm_gn_opts(1, o.estimator);
+    if (fuse) {
+        const tm_pose_batch_fn fn = tm_pose_batch_fns[tm_pose_shape(n_fine, &thr)];
+        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_pf, 1, o.coarse_min, g);
+    } else {
+        gather(n_max, 1);
+        rc = pose_launch_chain_batch(ctx, nb, n_fine, d_pf, &g);
+        if (rc) return rc;
     }
     HIP_TRY(hipGetLastError());
+    // ---- wait + result, frame by frame (no frame of a batch asks for the general path: POSE_CHAIN_LONG is never set) ----
     for (int i = 0; i < nb; i++) {
-        ptam_tracker* t = ts[i];
-        const unsigned long long seq = seqs[(size_t)i];
-        unsigned spins = 0;
-        while (*(volatile unsigned long long*)&t->mbox->seq != seq) {
-            if (++spins == 100000) {
-                spins = 0;
-                const hipError_t q = hipStreamQuery(st);
-                if (q != hipSuccess && q != hipErrorNotReady) {
-                    ptam_set_error("track_map_frames_batch: stream failed: %s", hipGetErrorString(q));
-                    return PTAM_E_HIP;
-                }
-                if (q == hipSuccess && *(volatile unsigned long long*)&t->mbox->seq != seq) return PTAM_E_HIP;
-            }
+        rc = tm_wait_seq(ts[i], st, ts[i]->seq, "a frame's result");
+        if (rc) {
+            const std::string e = ptam_last_error();
+            ptam_set_error("frame %d of the batch: %s", i, e.c_str());
+            return rc;
         }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        ptam_trackmap_result* out = outs + i;
-        std::memcpy(out, (const void*)&t->mbox->res, sizeof *out);
-        out->depth_sum = t->mbox->depth3[0];
-        out->depth_sum_sq = t->mbox->depth3[1];
-        out->depth_n = (int)t->mbox->depth3[2];
+        tm_read_result(ts[i], outs + i);
     }
     return PTAM_OK;
 }
@@ -1885,280 +1541,6 @@ int ptam_tracker_read_iteration_set(ptam_tracker* t, ptam_trackmap_meas* out, in
     return PTAM_OK;
 }
 
-int ptam_refind_batch(ptam_ctx* ctx, const ptam_kf* kf, const double kf_pose[12], int n, const ptam_pvs_point* points,
-                      const ptam_template_query* sources, ptam_refind_result* out) {
-    ARG_TRY(ctx && kf && kf_pose && n >= 0);
-    if (n == 0) return PTAM_OK;
-    ARG_TRY(points && sources && out);
-    ARG_TRY(kf->device == ctx->device);
-    HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<TmSrc> hs((size_t)n);
-    for (int i = 0; i < n; i++) {
-        const ptam_template_query& q = sources[i];
-        ARG_TRY(q.src_kf && q.src_level >= 0 && q.src_level < PTAM_LEVELS && q.src_kf->device == ctx->device);
-        hs[(size_t)i].im = q.src_kf->L.im[q.src_level];
-        hs[(size_t)i].w = q.src_kf->L.w[q.src_level];
-        hs[(size_t)i].h = q.src_kf->L.h[q.src_level];
-        hs[(size_t)i].cx = q.center_x;
-        hs[(size_t)i].cy = q.center_y;
-    }
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t N = (size_t)n;
-    const size_t o_pts = take(N * sizeof(ptam_pvs_point)), o_src = take(N * sizeof(TmSrc)), o_pose = take(96),
-                 o_jobs = take(N * sizeof(TemplateJob)), o_tm = take(N * 64), o_tr = take(N * sizeof(ptam_template_result)),
-                 o_q = take(N * sizeof(ptam_patch_query)), o_r = take(N * sizeof(ptam_patch_result)),
-                 o_sr = take(N * sizeof(ptam_subpix_result)), o_out = take(N * sizeof(ptam_refind_result));
-    void* s;
-    int rc = ctx_scratch(ctx, off, &s);
-    if (rc) return rc;
-    char* b = (char*)s;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(b + o_pts, points, N * sizeof(ptam_pvs_point), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b + o_src, hs.data(), N * sizeof(TmSrc), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b + o_pose, kf_pose, 96, hipMemcpyHostToDevice, st));
-    const int g = (n + 255) / 256;
-    TemplateJob* d_jobs = (TemplateJob*)(b + o_jobs);
-    ptam_patch_query* d_q = (ptam_patch_query*)(b + o_q);
-    ptam_patch_result* d_r = (ptam_patch_result*)(b + o_r);
-    ptam_subpix_result* d_sr = (ptam_subpix_result*)(b + o_sr);
-    ptam_template_result* d_tr = (ptam_template_result*)(b + o_tr);
-    uint8_t* d_tm = (uint8_t*)(b + o_tm);
-    hipLaunchKernelGGL(refind_prep_kernel, dim3(g), dim3(256), 0, st, ctx->cam, n, (const ptam_pvs_point*)(b + o_pts), (const TmSrc*)(b + o_src),
-                       (const double*)(b + o_pose), d_jobs, d_q);
-    rc = patch_launch_templates_dev(ctx, n, d_jobs, d_tm, d_tr, nullptr);
-    if (rc) return rc;
-    hipLaunchKernelGGL(refind_mask_kernel, dim3(g), dim3(256), 0, st, n, (const ptam_template_result*)d_tr, d_q);
-    rc = patch_launch_search_dev(ctx, kf, n, d_q, d_tm, d_r, nullptr, nullptr);
-    if (rc) return rc;
-    rc = patch_launch_subpix_dev(ctx, kf, n, d_q, d_r, d_tm, d_sr, nullptr, 8);
-    if (rc) return rc;
-    hipLaunchKernelGGL(refind_finish_kernel, dim3(g), dim3(256), 0, st, n, (const ptam_patch_query*)d_q, (const ptam_patch_result*)d_r,
-                       (const ptam_subpix_result*)d_sr, (ptam_refind_result*)(b + o_out));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, b + o_out, N * sizeof(ptam_refind_result), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ptam_stream_wait(st));   // (also keeps hs[] alive until its pageable copy has been staged)
-    return PTAM_OK;
-}
-
-struct ptam_refinder {
-    ptam_ctx* ctx;
-    RpFinder* st;   // device
-};
-int ptam_refinder_create(ptam_ctx* ctx, ptam_refinder** out) {
-    ARG_TRY(ctx && out);
-    HIP_TRY(hipSetDevice(ctx->device));
-    ptam_refinder* f = new ptam_refinder();
-    f->ctx = ctx;
-    if (hipMalloc((void**)&f->st, sizeof(RpFinder)) != hipSuccess || hipMemset(f->st, 0, sizeof(RpFinder)) != hipSuccess) {
-        if (f->st) hipFree(f->st);
-        delete f;
-        ptam_set_error("ptam_refinder_create: allocation failed");
-        return PTAM_E_HIP;
-    }
-    *out = f;
-    return PTAM_OK;
-}
-int ptam_refinder_destroy(ptam_refinder* f) {
-    if (!f) return PTAM_OK;
-    hipSetDevice(f->ctx->device);
-    ptam_stream_wait(f->ctx->stream);
-    hipFree(f->st);
-    delete f;
-    return PTAM_OK;
-}
-int ptam_refind_pairs(ptam_ctx* ctx, ptam_refinder* finder, int n, const ptam_refind_pair* pairs, ptam_refind_result* out,
-                      int32_t* template_kept) {
-    ARG_TRY(ctx && finder && finder->ctx->device == ctx->device && n >= 0);
-    if (n == 0) return PTAM_OK;
-    ARG_TRY(pairs && out);
-    HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<RpPair> hp((size_t)n);
-    std::vector<KfLevels> hl;
-    std::vector<const ptam_kf*> seen;
-    for (int i = 0; i < n; i++) {
-        const ptam_refind_pair& p = pairs[i];
-        const ptam_template_query& q = p.source;
-        ARG_TRY(p.kf && p.kf->device == ctx->device);
-        ARG_TRY(q.src_kf && q.src_level >= 0 && q.src_level < PTAM_LEVELS && q.src_kf->device == ctx->device);
-        RpPair& r = hp[(size_t)i];
-        r.pt = p.point;
-        r.src.im = q.src_kf->L.im[q.src_level];
-        r.src.w = q.src_kf->L.w[q.src_level];
-        r.src.h = q.src_kf->L.h[q.src_level];
-        r.src.cx = q.center_x;
-        r.src.cy = q.center_y;
-        std::memcpy(r.pose, p.kf_pose, 96);
-        r.id = (long long)p.point_id;
-        r.skip = p.skip != 0;
-        int k = -1;   // (lists name few keyframes, mostly in runs: a linear search from the back finds the last one at once)
-        for (int s = (int)seen.size() - 1; s >= 0; s--)
-            if (seen[(size_t)s] == p.kf) {
-                k = s;
-                break;
-            }
-        if (k < 0) {
-            k = (int)seen.size();
-            seen.push_back(p.kf);
-            hl.push_back(p.kf->L);
-        }
-        r.kf = k;
-    }
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t N = (size_t)n;
-    const size_t o_pairs = take(N * sizeof(RpPair)), o_ls = take(hl.size() * sizeof(KfLevels)), o_jobs = take(N * sizeof(TemplateJob)),
-                 o_q = take(N * sizeof(ptam_patch_query)), o_m2 = take(N * 32), o_reach = take(N * 4), o_det = take(N * 4), o_R = take(N * 4),
-                 o_nr = take(4), o_ref = take(N * 4), o_src = take(N * 4), o_dacc = take(N * 4), o_bad = take(N * 4), o_tm = take(N * 64),
-                 o_tr = take(N * sizeof(ptam_template_result)), o_out = take(N * sizeof(ptam_refind_result)), o_kept = take(N * 4);
-    void* sc;
-    int rc = ctx_scratch(ctx, off, &sc);
-    if (rc) return rc;
-    char* b = (char*)sc;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(b + o_pairs, hp.data(), N * sizeof(RpPair), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b + o_ls, hl.data(), hl.size() * sizeof(KfLevels), hipMemcpyHostToDevice, st));
-    RpDev d;
-    d.n = n;
-    d.pairs = (const RpPair*)(b + o_pairs);
-    d.Ls = (const KfLevels*)(b + o_ls);
-    d.jobs = (TemplateJob*)(b + o_jobs);
-    d.q = (ptam_patch_query*)(b + o_q);
-    d.m2 = (double*)(b + o_m2);
-    d.reach = (int*)(b + o_reach);
-    d.detbad = (int*)(b + o_det);
-    d.R = (int*)(b + o_R);
-    d.nr = (int*)(b + o_nr);
-    d.refresh = (int*)(b + o_ref);
-    d.srcp = (int*)(b + o_src);
-    d.dacc = (int*)(b + o_dacc);
-    d.bad = (int*)(b + o_bad);
-    d.tm = (uint8_t*)(b + o_tm);
-    d.tres = (ptam_template_result*)(b + o_tr);
-    d.st = finder->st;
-    d.out = (ptam_refind_result*)(b + o_out);
-    d.kept = (int*)(b + o_kept);
-    hipLaunchKernelGGL(rp_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->cam, d);
-    hipLaunchKernelGGL(rp_scan_kernel, dim3(1), dim3(1024), 0, st, d);
-    hipLaunchKernelGGL(rp_template_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d);
-    hipLaunchKernelGGL(rp_search_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d);
-    hipLaunchKernelGGL(rp_state_kernel, dim3(1), dim3(64), 0, st, d);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, d.out, N * sizeof(ptam_refind_result), hipMemcpyDeviceToHost, st));
-    if (template_kept) HIP_TRY(hipMemcpyAsync(template_kept, d.kept, N * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ptam_stream_wait(st));   // (also keeps the staging vectors alive until their pageable copies have been staged)
-    return PTAM_OK;
-}
-
-// Measurement helper (like ptam_ba_bench_jacobian): the "replicas" axis of the tracking path driven natively.
-// n independent trackers — each with its own context (stream, scratch, mailbox), map and keyframes — are run by n host
-// threads, frames_each frames per thread: per frame the two permutations are handed over (ptam_tracker_set_shuffle) and
-// ptam_track_map_frame is called exactly as the reference's tracker thread would.  The threads start together; *seconds_out
-// is the wall time from that start to the last thread's return, n * frames_each frames in all.
-int ptam_bench_track_frames(int n, ptam_tracker* const* trackers, ptam_kf* const* current, const uint8_t* const* d_frames,
-                            const double pose_in[12], const ptam_trackmap_opts* opts, const int32_t* shuffle_levels,
-                            const int32_t* shuffle_fine, int frames_each, double* seconds_out) {
-    ARG_TRY(n >= 1 && n <= 1024 && trackers && current && d_frames && pose_in && shuffle_levels && shuffle_fine && frames_each >= 1 && seconds_out);
-    for (int i = 0; i < n; i++) ARG_TRY(trackers[i] && current[i] && d_frames[i]);
-    std::atomic<int> ready{0}, failed{0};
-    std::atomic<bool> go{false};
-    std::vector<std::string> errs((size_t)n);
-    std::vector<std::thread> th;
-    th.reserve((size_t)n);
-    for (int i = 0; i < n; i++)
-        th.emplace_back([&, i]() {
-            ptam_trackmap_result res;
-            ready.fetch_add(1);
-            while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
-            for (int f = 0; f < frames_each; f++) {
-                int rc = ptam_tracker_set_shuffle(trackers[i], shuffle_levels, shuffle_fine);
-                if (!rc) rc = ptam_track_map_frame(trackers[i], current[i], d_frames[i], pose_in, opts, &res);
-                if (rc) {
-                    errs[(size_t)i] = ptam_last_error();
-                    failed.store(rc);
-                    return;
-                }
-            }
-        });
-    while (ready.load() < n) std::this_thread::yield();
-    const auto t0 = std::chrono::steady_clock::now();
-    go.store(true, std::memory_order_release);
-    for (auto& t : th) t.join();
-    *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (failed.load()) {
-        for (const auto& e : errs)
-            if (!e.empty()) {
-                ptam_set_error("ptam_bench_track_frames: a worker failed: %s", e.c_str());
-                break;
-            }
-        return failed.load();
-    }
-    return PTAM_OK;
-}
-
-// Measurement helper: `rounds` rounds of nb frames as batches (ptam_track_map_frames_batch).  groups == 1: one host thread, one
-// batch of nb per round.  groups > 1: the trackers are dealt into that many groups, each driven by its own host thread on its
-// own queue (the group's first tracker leads), so that one group's single-workgroup pose loops run beside another group's
-// searches.  Per round every tracker is handed its permutations first, as a caller tracking nb cameras would.
-// *seconds_out = wall time from the common start to the last thread's return.
-int ptam_bench_track_batch(int nb, ptam_tracker* const* trackers, ptam_kf* const* current, const uint8_t* const* d_frames,
-                           const double pose_in[12], const ptam_trackmap_opts* opts, const int32_t* shuffle_levels,
-                           const int32_t* shuffle_fine, int rounds, int groups, double* seconds_out) {
-    ARG_TRY(nb >= 1 && nb <= 4096 && trackers && current && d_frames && pose_in && shuffle_levels && shuffle_fine && rounds >= 1 && seconds_out);
-    ARG_TRY(groups >= 1 && groups <= nb);
-    std::atomic<int> ready{0}, failed{0};
-    std::atomic<bool> go{false};
-    std::vector<std::string> errs((size_t)groups);
-    auto work = [&](int g) {
-        const int per = (nb + groups - 1) / groups, i0 = g * per, i1 = std::min(nb, i0 + per), m = i1 - i0;
-        if (m <= 0) return;
-        std::vector<double> poses((size_t)m * 12);
-        for (int i = 0; i < m; i++) std::memcpy(&poses[(size_t)i * 12], pose_in, 96);
-        std::vector<ptam_trackmap_result> res((size_t)m);
-        ready.fetch_add(1);
-        while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
-        for (int r = 0; r < rounds; r++) {
-            int rc = PTAM_OK;
-            for (int i = i0; i < i1 && !rc; i++) rc = ptam_tracker_set_shuffle(trackers[i], shuffle_levels, shuffle_fine);
-            if (!rc) rc = ptam_track_map_frames_batch(m, trackers + i0, current + i0, d_frames + i0, poses.data(), opts, res.data());
-            if (rc) {
-                errs[(size_t)g] = ptam_last_error();
-                failed.store(rc);
-                return;
-            }
-        }
-    };
-    std::vector<std::thread> th;
-    int n_threads = 0;
-    for (int g = 0; g < groups; g++)
-        if (g * ((nb + groups - 1) / groups) < nb) {
-            th.emplace_back(work, g);
-            n_threads++;
-        }
-    while (ready.load() < n_threads && !failed.load()) std::this_thread::yield();
-    const auto t0 = std::chrono::steady_clock::now();
-    go.store(true, std::memory_order_release);
-    for (auto& t : th) t.join();
-    *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (failed.load()) {
-        for (const auto& e : errs)
-            if (!e.empty()) {
-                ptam_set_error("ptam_bench_track_batch: a group failed: %s", e.c_str());
-                break;
-            }
-        return failed.load();
-    }
-    return PTAM_OK;
-}
-
 }   // extern "C"
 
 int pose_hazards_read_trackmap(hipStream_t st, unsigned long long* out) {   // (this translation unit's copy of the counter)
@@ -2166,14 +1548,6 @@ int pose_hazards_read_trackmap(hipStream_t st, unsigned long long* out) {   // (
     return PTAM_OK;
 }
 void trackmap_preload_kernels() {
-    ptam_preload((const void*)refind_prep_kernel);
-    ptam_preload((const void*)refind_mask_kernel);
-    ptam_preload((const void*)refind_finish_kernel);
-    ptam_preload((const void*)rp_prep_kernel);
-    ptam_preload((const void*)rp_scan_kernel);
-    ptam_preload((const void*)rp_template_kernel);
-    ptam_preload((const void*)rp_search_kernel);
-    ptam_preload((const void*)rp_state_kernel);
     ptam_preload((const void*)tm_select_kernel);
     ptam_preload((const void*)tm_pyr_pvs_kernel<PTAM_HALFSAMPLE_R>);
     ptam_preload((const void*)tm_pyr_pvs_kernel<PTAM_HALFSAMPLE_T>);

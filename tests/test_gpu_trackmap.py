@@ -293,6 +293,49 @@ def test_batch_keyframes_and_degenerate_maps(hip, size):
         tr.close()
 
 
+def test_stage_profiling_counts_frames_and_leaves_the_result_alone(hip):
+    """ptam_tracker_set_profiling / ptam_tracker_stage_time: the events of a profiled frame change nothing in its result — the same
+    frame from the same pose with profiling off, on, off again, bit for bit — and the stage times cover exactly the frames profiled
+    since the last switch.  163x121 with the empty map of test_batch_keyframes_and_degenerate_maps: the suite's smallest frame chain."""
+    import ctypes as C
+    from ptam_cg_amd import _abi
+    size = (163, 121)
+    a, _ = synth.make_frame_pair()
+    im = np.ascontiguousarray(a[:size[1], :size[0]])
+    cx = host.Context(lib=hip, size=size)
+    tr = host.Tracker(cx, 32)
+    ka = host.KeyFrame(cx).MakeKeyFrame_Lite(im)
+    tr.set_map(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3)), ka, np.zeros(0, np.int32), np.zeros((0, 2), np.int32))
+    kb, di = host.KeyFrame(cx), host.DevBuf(cx, im)
+    pose = np.concatenate([np.eye(3).reshape(9), [0.0, 0.0, 1.5]])
+    opts = tr.opts()
+
+    def frames_profiled():
+        got = set()
+        for i in range(len(_abi.TRACK_STAGE_NAMES)):
+            ms, n = C.c_double(), C.c_int()
+            cx._check(hip.tracker_stage_time(tr.h, i, C.byref(ms), C.byref(n)), "tracker_stage_time")
+            got.add(n.value)
+        assert len(got) == 1   # every stage reports the same count
+        return got.pop()
+
+    off = tr.TrackFrame(kb, di, pose, opts).copy()
+    assert frames_profiled() == 0
+    tr.set_profiling(True)
+    on = tr.TrackFrame(kb, di, pose, opts).copy()
+    assert frames_profiled() == 1
+    times = tr.stage_times()
+    tr.set_profiling(False)   # (every switch starts the sums again)
+    off_again = tr.TrackFrame(kb, di, pose, opts).copy()
+    assert frames_profiled() == 0
+    assert off.tobytes() == on.tobytes() == off_again.tobytes()
+    assert np.array_equal(off["pose"], pose) and off["n_meas"] == 0
+    assert list(times) == list(_abi.TRACK_STAGE_NAMES)
+    vals = np.array(list(times.values()))
+    assert np.isfinite(vals).all() and (vals >= 0).all() and vals.sum() > 0
+    tr.close()
+
+
 @pytest.mark.parametrize("variant", ["R", "T"])
 @pytest.mark.parametrize("size", [(640, 480), (608, 407), (322, 243), (163, 121), (96, 64)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_track_frame_keyframe_is_make_keyframe_lite(hip, size, variant):
