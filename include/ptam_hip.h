@@ -404,11 +404,67 @@ int ptam_trails_read_patches(ptam_trails* t, uint8_t* out, int cap, int* n);
 /* The first loop of MapMaker::InitFromStereo (src/MapMaker.cc:272-279) for the live trails: first = UnProject(irInitialPos),
  * second = UnProject(irCurrentPos) (src/ATANCamera.cc:125-140), jac = GetProjectionDerivs() (:179-209) as the camera's cache
  * stands after the SECOND UnProject — mvLastCam = second, mdLastR = the undistorted radius, mdLastFactor = 1 / dFactor: the
- * derivative at the second point.  fp64 in the reference's operation order, no FMA contraction.  This is the input of the
- * host's HomographyInit::Compute (src/HomographyInit.cc), which stays the reference's code. */
+ * derivative at the second point.  fp64 in the reference's operation order, no FMA contraction.  This is the input of
+ * HomographyInit::Compute (src/HomographyInit.cc): ptam_trails_homography below runs it on this table without the download;
+ * a caller that keeps the reference's own Compute reads the table here. */
 int ptam_trails_matches(ptam_trails* t, ptam_homography_match* out, int cap, int* n);
 /* PTAM_E_ARG: a null pointer, max_trails < 1, a keyframe of another device or of another image size than the object's,
  * cap smaller than the live count.  PTAM_E_STATE: advance / read / read_patches / matches before start. */
+
+/* ---- HomographyInit::Compute (src/HomographyInit.cc:35-63), stage (1) of MapMaker::InitFromStereo (src/MapMaker.cc:281-293),
+ *      fp64 throughout, two kernel launches, one host wait at the end:
+ *      BestHomographyFromMatches_MLESAC (:179-230): fewer than ten matches -> one DLT over all of them (HomographyFromMatches
+ *      :65-115, with the zeroed ninth row when 2n < 9); otherwise `trials` hypotheses, each the DLT of four matches scored by the
+ *      sum of MLESACScore (:23-33) over all matches; the strictly smaller score wins, among equal scores the lowest trial.  The
+ *      DLT's null vector is the right singular vector of the smallest singular value by one-sided Jacobi (the reference:
+ *      TooN SVD over LAPACK; a singular vector's sign is free and nothing below depends on it).
+ *      Inliers: IsHomographyInlier (:14-21, squared pixel error strictly below max_pixel_error^2), then five
+ *      RefineHomographyWithInliers (:120-177): WLS<9> with the prior 1.0, Tukey::FindSigmaSquared (the median is sorted[n / 2],
+ *      2n - 6 in size_t arithmetic) and Tukey::Weight (include/Tools.h), the 9x9 system solved by Cholesky (L D L^T).
+ *      One place where the reference divides zero by zero is given a defined meaning: a match whose error is exactly zero
+ *      has weight 1 (with a zero median, which four exactly fitted matches can produce, Tukey::Weight is 1 - 0 / 0 and the
+ *      reference's pose is NaN).
+ *      DecomposeHomography (:232-339): the eight solutions in the reference's push order; bit-equal singular values
+ *      (nCase != 1) end the call with PTAM_HOMOG_DEGENERATE.  ChooseBestDecomposition (:363-435): the two visibility counts,
+ *      each followed by a stable sort (std::sort on eight elements is an insertion sort), the ratio test
+ *      (double)s1 / (double)s0 < 0.9, else the Sampson sums over ALL matches, capped at 4 max_pixel_error^2, `<=` choosing the
+ *      first.  An empty inlier set (the reference asserts in FindSigmaSquared) ends the call with PTAM_HOMOG_NO_INLIERS.
+ *      The draw: the reference calls rand() (:198-211); here the quadruples are an input.  opts->samples: trials x 4 match
+ *      indices; NULL: the table ptam_homography_samples(opts->seed, n, trials) — splitmix64 (state += 0x9E3779B97F4A7C15;
+ *      z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; next = z ^ z >> 31) started from
+ *      state = seed, every index next() % n_matches, an index already in its quadruple drawn again (the while(!isUnique) loop).
+ *      Sums over matches are reduced in a fixed order: two calls on the same input give the same bits. */
+enum { PTAM_HOMOG_OK = 0, PTAM_HOMOG_DEGENERATE = 1, PTAM_HOMOG_NO_INLIERS = 2 };
+typedef struct {
+    double   max_pixel_error;   /* 5.0: src/MapMaker.cc, the Compute(vMatches, 5.0, se3) call */
+    int32_t  trials;            /* 300: src/HomographyInit.cc:195 */
+    uint64_t seed;              /* used when samples == NULL */
+    const int32_t* samples;     /* trials x 4 match indices, or NULL */
+} ptam_homography_opts;
+typedef struct {
+    int32_t status, n_matches, n_inliers, best_trial /* -1 on the < 10 path */, ambiguous /* dRatio >= 0.9 */;
+    double  best_score;         /* dBestError; 0 on the < 10 path */
+    double  homography[9];      /* mm3BestHomography after the five refinements, row-major (NO_INLIERS: before them) */
+    double  sampson[2];         /* adSampsonusScores when ambiguous, else 0; in the order of the two surviving decompositions,
+                                   which between equal counts is their push order and follows the SVD's signs */
+} ptam_homography_info;
+void ptam_homography_opts_default(ptam_homography_opts*);
+/* out: trials x 4.  PTAM_E_ARG: out == NULL, n_matches < 4, trials < 1.  Host only. */
+int  ptam_homography_samples(uint64_t seed, int n_matches, int trials, int32_t* out);
+/* se3_second_from_first = mvDecompositions[0].se3SecondFromFirst (R row-major, then t), written only when info->status ==
+ * PTAM_HOMOG_OK (the reference's `return true`); info always; inlier_out (nullable): n bytes, 1 = mvHomographyInliers holds
+ * the match.  The workspace is the context's scratch, which grows on demand and stays. */
+int  ptam_homography_init(ptam_ctx*, int n, const ptam_homography_match* matches /* host */,
+                          const ptam_homography_opts*, double se3_second_from_first[12],
+                          ptam_homography_info* info, uint8_t* inlier_out);
+/* The same on the live trails: ptam_trails_matches' kernel (the same bits) into the object's memory, then the kernels of
+ * ptam_homography_init on that table; nothing comes down but the result.  ptam_trails_create reserves the workspace of a
+ * call with max_trails matches and 300 trials.  inlier_out: one byte per live trail, in list order. */
+int  ptam_trails_homography(ptam_trails*, const ptam_homography_opts*, double se3_second_from_first[12],
+                            ptam_homography_info* info, uint8_t* inlier_out);
+/* PTAM_E_ARG, with nothing written: a null pointer (inlier_out excepted), n < 4 (fewer than four live trails), trials < 1,
+ * max_pixel_error <= 0, a sample index outside [0, n) or repeated inside its quadruple.  PTAM_E_STATE:
+ * ptam_trails_homography before ptam_trails_start. */
 
 /* ---- MapMaker::InitFromStereo, the point loop (src/MapMaker.cc:310-367): per match, in order, a level-0 map point in the
  *      first keyframe (whose pose is the identity, :305) centred on `initial`: the _NC vectors (:321-326),

@@ -289,8 +289,8 @@ inline std::vector<ptam_new_map_point> AddMapPointsEpipolar(Context& c, KeyFrame
 
 // Tracker::TrailTracking_Start() / int TrailTracking_Advance()   src/Tracker.cc:352-432, with the list mlTrails and
 // mPreviousFrameKF kept on the device (ptam_trails_*).  The caller's TrackForInitialMap (:311-347) keeps its stage enum, the
-// `nGoodTrails < 10 -> Reset()` test and the spacebar; Matches() is the vMatches table of InitFromStereo (src/MapMaker.cc:272-279)
-// for the host's HomographyInit::Compute.
+// `nGoodTrails < 10 -> Reset()` test and the spacebar; Matches() is the vMatches table of InitFromStereo (src/MapMaker.cc:272-279),
+// Homography() the Compute call on it (:281-293) without the download.
 class TrailTracker {
 public:
     explicit TrailTracker(Context& c, int nMaxInitialTrails = 1000 /* Tracker.MaxInitialTrails */, double dMinShiTomasi = 70.0)
@@ -327,11 +327,72 @@ public:
         v.resize((size_t)n);
         return v;
     }
+    // HomographyInit::Compute(vMatches, dMaxPixelError, se3) on the match table of the live trails, which stays on the device
+    // (ptam_trails_homography); opts (nullable): the number of trials and the draw.  pInfo (nullable): scores, counts, status.
+    bool Homography(double dMaxPixelError, SE3& se3SecondFromFirst, const ptam_homography_opts* opts = nullptr,
+                    ptam_homography_info* pInfo = nullptr) {
+        ptam_homography_opts o;
+        if (opts)
+            o = *opts;
+        else
+            ptam_homography_opts_default(&o);
+        o.max_pixel_error = dMaxPixelError;
+        double p[12];
+        ptam_homography_info info;
+        check(ptam_trails_homography(h_, &o, p, &info, nullptr), "ptam_trails_homography");
+        if (pInfo) *pInfo = info;
+        if (info.status != PTAM_HOMOG_OK) return false;
+        se3SecondFromFirst = SE3::from12(p);
+        return true;
+    }
 
 private:
     ptam_trails* h_ = nullptr;
     int max_, alive_ = 0;
     double min_st_;
+};
+
+// class HomographyInit (include/HomographyInit.h:39-66): bool Compute(std::vector<HomographyMatch> vMatches, double dMaxPixelError,
+// SE3<>& se3SecondFromFirst), src/HomographyInit.cc:35-63, in one device call (ptam_homography_init).  HomographyMatch is
+// ptam_homography_match (v2CamPlaneFirst, v2CamPlaneSecond, m2PixelProjectionJac row-major).  The reference draws its quadruples
+// with rand(); here the draw is seeded (SetSeed, splitmix64: ptam_hip.h) or handed in (SetSamples: 4 indices per trial).
+using HomographyMatch = ptam_homography_match;
+class HomographyInit {
+public:
+    explicit HomographyInit(Context& c) : ctx_(&c) { ptam_homography_opts_default(&opts_); }
+    void SetSeed(uint64_t seed) {
+        opts_.seed = seed;
+        samples_.clear();
+    }
+    void SetTrials(int nTrials) {
+        opts_.trials = nTrials;
+        samples_.clear();
+    }
+    void SetSamples(const std::vector<int32_t>& vSamples) {
+        samples_ = vSamples;
+        opts_.trials = (int)(samples_.size() / 4);
+    }
+    bool Compute(std::vector<HomographyMatch> vMatches, double dMaxPixelError, SE3& se3SecondFromFirst) {
+        ptam_homography_opts o = opts_;
+        o.max_pixel_error = dMaxPixelError;
+        o.samples = samples_.empty() ? nullptr : samples_.data();
+        double p[12];
+        inliers_.assign(vMatches.size(), 0);
+        check(ptam_homography_init(ctx_->handle(), (int)vMatches.size(), vMatches.data(), &o, p, &info_, inliers_.data()),
+              "ptam_homography_init");
+        if (info_.status != PTAM_HOMOG_OK) return false;
+        se3SecondFromFirst = SE3::from12(p);
+        return true;
+    }
+    const ptam_homography_info& Info() const { return info_; }        // of the last Compute
+    const std::vector<uint8_t>& Inliers() const { return inliers_; }   // 1: the match is in mvHomographyInliers
+
+private:
+    Context* ctx_;
+    ptam_homography_opts opts_;
+    ptam_homography_info info_{};
+    std::vector<int32_t> samples_;
+    std::vector<uint8_t> inliers_;
 };
 
 // The point loop of MapMaker::InitFromStereo (src/MapMaker.cc:310-367) in ONE device call (ptam_init_points_from_trails):

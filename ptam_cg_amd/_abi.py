@@ -93,6 +93,17 @@ class HomographyMatch(C.Structure):
     _fields_ = [("first", C.c_double * 2), ("second", C.c_double * 2), ("jac", C.c_double * 4)]
 
 
+class HomographyOpts(C.Structure):
+    """ptam_homography_opts (HomographyInit::Compute, src/HomographyInit.cc)"""
+    _fields_ = [("max_pixel_error", C.c_double), ("trials", C.c_int32), ("seed", C.c_uint64), ("samples", C.POINTER(C.c_int32))]
+
+
+class HomographyInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("n_inliers", C.c_int32), ("best_trial", C.c_int32),
+                ("ambiguous", C.c_int32), ("best_score", C.c_double), ("homography", C.c_double * 9), ("sampson", C.c_double * 2)]
+
+
+HOMOG_OK, HOMOG_DEGENERATE, HOMOG_NO_INLIERS = range(3)
 INIT_MADE, INIT_SUBPIX_FAILED, INIT_BEHIND_CAMERA, INIT_TEMPLATE_BAD = range(4)   # ptam_init_points_from_trails status
 
 
@@ -230,6 +241,10 @@ PROTOTYPES = {
     "trails_read": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "trails_read_patches": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "trails_matches": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
+    "homography_opts_default": (None, [C.POINTER(HomographyOpts)]),
+    "homography_samples": (_i, [C.c_uint64, _i, _i, _vp]),
+    "homography_init": (_i, [_vp, _i, _vp, C.POINTER(HomographyOpts), _pd, C.POINTER(HomographyInfo), _vp]),
+    "trails_homography": (_i, [_vp, C.POINTER(HomographyOpts), _pd, C.POINTER(HomographyInfo), _vp]),
     "init_points_from_trails": (_i, [_vp, _vp, _vp, _pd, _i, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "pose_gn_state": (_i, [_vp, _i, _vp, _vp, _pd, _vp, _vp, _vp, _vp]),
     "trackmap_opts_default": (None, [_vp]),

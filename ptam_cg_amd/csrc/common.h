@@ -87,6 +87,7 @@ void pose_preload_kernels();
 void patch_preload_kernels();
 void mapmaker_preload_kernels();
 void trails_preload_kernels();
+void homography_preload_kernels();
 void mapba_preload_kernels();
 void kf_preload_kernels();
 void pvs_preload_kernels();

@@ -242,6 +242,7 @@ int ptam_ctx_create(const ptam_cam_params* cam, int device, ptam_ctx** out) {
     patch_preload_kernels();
     mapmaker_preload_kernels();
     trails_preload_kernels();
+    homography_preload_kernels();
     mapba_preload_kernels();
     kf_preload_kernels();
     pvs_preload_kernels();

@@ -19,10 +19,13 @@
 // A trail's patch never moves: the trail record carries its slot in the patch table.
 #include "common.h"
 
+#include <algorithm>
+
 #include "keyframe.h"
 #include "track_internal.h"
 #include "patch_device.h"
 #include "mapmaker_device.h"
+#include "homography.h"
 
 #define TRAIL_MAX_SSD 100000   // MiniPatch::FindPatch's default nMaxSSD (include/ImageProcess.h)
 #define TRAIL_RANGE 10         // src/Tracker.cc:400
@@ -393,8 +396,11 @@ int ptam_trails_create(ptam_ctx* ctx, int max_trails, ptam_trails** out) {
     t->patches = (uint8_t*)(p += b_slot);
     t->newpos = (ptam_int2*)(p += b_patch);
     t->out = (void*)(p += b_pos);
-    void* hp;   // the staging every later call needs, so that none of them allocates
-    int rc = ctx_pinned(ctx, 256 + b_out + n * sizeof(ptam_trail), &hp);
+    void *hp, *hs;   // the staging and the scratch every later call needs, so that none of them allocates
+    size_t homog_scratch, homog_pinned;   // (ptam_trails_homography on max_trails matches with the reference's 300 trials)
+    homog_sizes(max_trails, 300, &homog_scratch, &homog_pinned);
+    int rc = ctx_pinned(ctx, std::max(256 + b_out + n * sizeof(ptam_trail), homog_pinned), &hp);
+    if (!rc) rc = ctx_scratch(ctx, homog_scratch, &hs);
     if (rc) {
         hipFree(t->base);
         delete t;
@@ -538,6 +544,20 @@ int ptam_trails_matches(ptam_trails* t, ptam_homography_match* out, int cap, int
     if (rc) return rc;
     *n = t->n_live;
     return PTAM_OK;
+}
+
+int ptam_trails_homography(ptam_trails* t, const ptam_homography_opts* opts, double se3_second_from_first[12], ptam_homography_info* info,
+                           uint8_t* inlier_out) {
+    ARG_TRY(t && opts && se3_second_from_first && info);
+    int rc = trails_need_start(t, "trails_homography");
+    if (rc) return rc;
+    rc = homog_check(t->n_live, opts);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(t->ctx->device));
+    hipLaunchKernelGGL(trails_matches_kernel, dim3((t->n_live + 255) / 256), dim3(256), 0, t->ctx->stream, t->ctx->cam, t->n_live,
+                       (const ptam_trail*)t->trails[t->cur], (ptam_homography_match*)t->out);
+    HIP_TRY(hipGetLastError());
+    return homog_run(t->ctx, t->n_live, (const ptam_homography_match*)t->out, nullptr, opts, se3_second_from_first, info, inlier_out);
 }
 
 int ptam_init_points_from_trails(ptam_ctx* ctx, const ptam_kf* first, ptam_kf* second, const double se3_second_from_first[12], int n,

@@ -441,10 +441,64 @@ class Trails:
         """vMatches of InitFromStereo (HOMOGRAPHY_MATCH_DT)"""
         return self._table(self.lib.trails_matches, "trails_matches", HOMOGRAPHY_MATCH_DT, cap)
 
+    def homography(self, max_pixel_error=5.0, seed=0, samples=None, trials=300):
+        """HomographyInit::Compute on the live trails' match table without downloading it (ptam_trails_homography)
+        -> (ok, se3 (12,) or None, info dict, inliers (n,) bool)"""
+        opts, keep = _homography_opts(max_pixel_error, seed, samples, trials)
+        return _homography_call(self.ctx, lambda *a: self.lib.trails_homography(self.h, *a), "trails_homography", opts, self.max_trails)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.trails_destroy(self.h)
             self.h = None
+
+
+def homography_samples(lib, seed, n_matches, trials=300):
+    """the quadruples ptam_homography_init draws from `seed` (ptam_homography_samples): (trials, 4) int32"""
+    out = np.zeros((trials, 4), np.int32)
+    rc = lib.homography_samples(int(seed), int(n_matches), int(trials), _ptr(out))
+    if rc < 0:
+        raise PtamError(f"homography_samples failed ({rc}): {lib.last_error().decode()}")
+    return out
+
+
+def _homography_opts(max_pixel_error, seed, samples, trials):
+    opts = _abi.HomographyOpts(float(max_pixel_error), int(trials), int(seed), None)
+    keep = None
+    if samples is not None:
+        keep = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 4)
+        opts.trials = len(keep)
+        opts.samples = keep.ctypes.data_as(C.POINTER(C.c_int32))
+    opts._keep = keep          # (the table lives as long as the options)
+    return opts, keep
+
+
+def _homography_call(ctx, fn, what, opts, n):
+    se3 = np.zeros(12)
+    info = _abi.HomographyInfo()
+    inl = np.zeros(max(n, 1), np.uint8)
+    ctx._check(fn(C.byref(opts), _pd(se3), C.byref(info), _ptr(inl)), what)
+    d = {f: getattr(info, f) for f in ("status", "n_matches", "n_inliers", "best_trial", "ambiguous", "best_score")}
+    d["homography"] = np.array(info.homography).reshape(3, 3)
+    d["sampson"] = np.array(info.sampson)
+    ok = info.status == _abi.HOMOG_OK
+    return ok, (se3 if ok else None), d, inl[:info.n_matches].astype(bool)
+
+
+class HomographyInit:
+    """HomographyInit (include/HomographyInit.h, src/HomographyInit.cc) in one device call: ptam_homography_init"""
+
+    def __init__(self, ctx):
+        self.ctx, self.lib = ctx, ctx.lib
+        if not self.lib.has("homography_init"):
+            raise PtamError("this library has no ptam_homography_init")
+
+    def compute(self, matches, max_pixel_error=5.0, seed=0, samples=None, trials=300):
+        """Compute(vMatches, dMaxPixelError, se3) -> (ok, se3 (12,) or None, info dict, inliers (n,) bool); matches
+        HOMOGRAPHY_MATCH_DT; the draw is `samples` ((trials, 4) match indices) or splitmix64 on `seed`"""
+        m = np.ascontiguousarray(matches, dtype=HOMOGRAPHY_MATCH_DT)
+        opts, keep = _homography_opts(max_pixel_error, seed, samples, trials)
+        return _homography_call(self.ctx, lambda *a: self.lib.homography_init(self.ctx.h, len(m), _ptr(m), *a), "homography_init", opts, len(m))
 
 
 def init_points_from_trails(ctx, first_kf, second_kf, se3_second_from_first, matches, subpix_max_its=10):
