@@ -1,6 +1,8 @@
-// ba_debug_host.inc — host side of the instrumented builds (`make timing`: -DK7_TIMING; tools/dev/build_variant.sh: -DSCHUR_STAMPS):
-// what ptam_ba_compute and ptam_ba_bench_jacobian print from the cycle stamps the kernels leave in BaDev::dbg.  tools/dev/schur_fit.py,
-// schur_fit2.py and schur_wg_timeline.py parse this text.  In the product build every function here is empty.
+// ba_debug_host.inc — host side of the instrumented builds (`make timing`: -DK7_TIMING; tools/dev/build_variant.sh: -DSCHUR_STAMPS,
+// -DPREP_STAMPS): what ptam_ba_compute and ptam_ba_bench_jacobian print from the cycle stamps the kernels leave in BaDev::dbg, and
+// ba_prepare_impl from those in PrepScalars.  tools/dev/schur_fit.py, schur_fit2.py and schur_wg_timeline.py parse this text.  In the
+// product build every ba_dbg_* function up to ba_dbg_prep_stamps is empty; behind them, what prepare prints under PTAM_DEBUG_PREPARE
+// and PTAM_DEBUG_SCHUR (tests/test_gpu_parity.py parses the latter).
 // Included by bundle.hip behind ptam_ba.
 struct BaHostTimes {
     double t0 = 0, first = 0, loop = 0;   // us: Compute() began, read its first trial's verdict, left its loop
@@ -147,4 +149,45 @@ static inline int ba_dbg_k7_stamps(ptam_ba* ba, int reps) {
                 du[nb * 9 / 10], du[nb - 1]);
 #endif
     return PTAM_OK;
+}
+// -DPREP_STAMPS: the phases of prep_split_kernel per XCD list
+static inline void ba_dbg_prep_stamps(const PrepScalars& ps) {
+#ifdef PREP_STAMPS
+    for (int x = 0; x < 8; x++) {
+        std::fprintf(stderr, "[ptam] split kernel, list %d (us from its start): lists built %.1f | in LDS %.1f | round 1 done %.1f | search done %.1f | cut written %.1f\n", x,
+                     (ps.stamp[x][1] - ps.stamp[x][0]) * 0.01, (ps.stamp[x][2] - ps.stamp[x][0]) * 0.01, (ps.stamp[x][3] - ps.stamp[x][0]) * 0.01,
+                     (ps.stamp[x][4] - ps.stamp[x][0]) * 0.01, (ps.stamp[x][5] - ps.stamp[x][0]) * 0.01);
+        std::fprintf(stderr, "[ptam]    the search: %lld shader cycles in %.1f us = %.2f GHz\n", ps.stamp[x][7] - ps.stamp[x][6], (ps.stamp[x][4] - ps.stamp[x][2]) * 0.01,
+                     (double)(ps.stamp[x][7] - ps.stamp[x][6]) / ((ps.stamp[x][4] - ps.stamp[x][2]) * 10.0));
+    }
+#endif
+}
+// PTAM_DEBUG_SCHUR=1
+static void ba_dbg_schur_lists(const PrepScalars& ps) {
+    if (!getenv("PTAM_DEBUG_SCHUR")) return;
+    std::fprintf(stderr, "[ptam] schur: %d segments, %d workgroups; %lld entries in %d (XCD, pair) lists, budgets", ps.n_segs, ps.n_schur_wg,
+                 ps.n_entries, ps.n_xp);
+    for (int x = 0; x < 8; x++) std::fprintf(stderr, " %lld", ps.t_cut[x]);
+    std::fprintf(stderr, "; workgroups per XCD");
+    for (int x = 0; x < 8; x++) std::fprintf(stderr, " %d", ps.n_wgs[x]);
+    std::fprintf(stderr, "\n");
+}
+// PTAM_DEBUG_PREPARE=1: host time of the phases of ba_prepare_impl, and the sizes it asked for
+static bool ba_dbg_prepare_on() {
+    static const bool on = getenv("PTAM_DEBUG_PREPARE") != nullptr;
+    return on;
+}
+struct PrepLaps {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        if (!ba_dbg_prepare_on()) return;
+        const auto t = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[ptam] prepare: %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t0).count());
+        t0 = t;
+    }
+};
+static void ba_dbg_prepare_sizes(const ptam_ba* ba, size_t clear_bytes, size_t staging_bytes) {
+    if (!ba_dbg_prepare_on()) return;
+    std::fprintf(stderr, "[ptam] prepare: block_bytes %zu clear_bytes %zu sblock_bytes %zu staging_bytes %zu\n", ba->block_bytes, clear_bytes,
+                 ba->sblock ? ba->sblock_bytes : (size_t)0, staging_bytes);
 }

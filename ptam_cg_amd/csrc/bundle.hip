@@ -57,14 +57,9 @@ struct PinVec {
     const T& operator[](size_t i) const { return p[i]; }
     int reserve(size_t want) {
         if (want <= cap) return PTAM_OK;
-        const size_t bytes = std::max<size_t>(want * sizeof(T), 4096);
         void* np = nullptr;
         size_t nbytes = 0;
-        if (!ctx_cache_take(ctx->pin_cache, CTX_NCACHE(ctx->pin_cache), bytes, &np, &nbytes)) {
-            HIP_TRY(hipSetDevice(ctx->device));
-            HIP_TRY(hipHostMalloc(&np, bytes, hipHostMallocDefault));
-            nbytes = bytes;
-        }
+        if (int rc = ctx_block_take(ctx, CTX_MEM_PINNED, std::max<size_t>(want * sizeof(T), 4096), &np, &nbytes)) return rc;
         if (n) std::memcpy(np, p, n * sizeof(T));
         release();
         p = (T*)np;
@@ -89,10 +84,7 @@ struct PinVec {
         return PTAM_OK;
     }
     void release() {   // (keeps n: reserve() re-points the array)
-        if (p) {
-            void* drop = ctx_cache_give(ctx->pin_cache, CTX_NCACHE(ctx->pin_cache), p, cap_bytes);
-            if (drop) hipHostFree(drop);
-        }
+        ctx_block_give(ctx, CTX_MEM_PINNED, p, cap_bytes);
         p = nullptr;
         cap = cap_bytes = 0;
     }
@@ -120,15 +112,10 @@ struct MeasStore {
         chunks = std::max(chunks, 2 * h_chunks);
         void* np = nullptr;
         size_t nbytes = 0;
-        if (!ctx_cache_take(ctx->pin_cache, CTX_NCACHE(ctx->pin_cache), chunks * MS_CH_BYTES, &np, &nbytes)) {
-            HIP_TRY(hipSetDevice(ctx->device));
-            HIP_TRY(hipHostMalloc(&np, chunks * MS_CH_BYTES, hipHostMallocDefault));
-            nbytes = chunks * MS_CH_BYTES;
-        }
+        if (int rc = ctx_block_take(ctx, CTX_MEM_PINNED, chunks * MS_CH_BYTES, &np, &nbytes)) return rc;
         if (n) std::memcpy(np, h, ((n + MS_CH - 1) >> MS_LOG) * MS_CH_BYTES);
         if (in_flight && ptam_stream_wait(ctx->stream) != hipSuccess) {   // (copies out of the old chunks)
-            void* drop = ctx_cache_give(ctx->pin_cache, CTX_NCACHE(ctx->pin_cache), np, nbytes);
-            if (drop) hipHostFree(drop);
+            ctx_block_give(ctx, CTX_MEM_PINNED, np, nbytes);
             ptam_set_error("the device queue failed under a growing measurement store");
             return PTAM_E_HIP;
         }
@@ -144,11 +131,7 @@ struct MeasStore {
         chunks = std::max(std::max(chunks, 2 * d_chunks), h_chunks);
         void* np = nullptr;
         size_t nbytes = 0;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (!ctx_cache_take(ctx->dev_cache, CTX_NCACHE(ctx->dev_cache), chunks * MS_CH_BYTES, &np, &nbytes)) {
-            HIP_TRY(hipMalloc(&np, chunks * MS_CH_BYTES));
-            nbytes = chunks * MS_CH_BYTES;
-        }
+        if (int rc = ctx_block_take(ctx, CTX_MEM_DEVICE, chunks * MS_CH_BYTES, &np, &nbytes)) return rc;
         release_dev();   // (queued copies into the old block: its next owner only touches it through the same queue)
         d = (char*)np;
         d_bytes = nbytes;
@@ -173,22 +156,28 @@ struct MeasStore {
         return PTAM_OK;
     }
     void release_host() {
-        if (h) {
-            void* drop = ctx_cache_give(ctx->pin_cache, CTX_NCACHE(ctx->pin_cache), h, h_bytes);
-            if (drop) hipHostFree(drop);
-        }
+        ctx_block_give(ctx, CTX_MEM_PINNED, h, h_bytes);
         h = nullptr;
         h_chunks = h_bytes = 0;
     }
     void release_dev() {
-        if (d) {
-            void* drop = ctx_cache_give(ctx->dev_cache, CTX_NCACHE(ctx->dev_cache), d, d_bytes);
-            if (drop) hipFree(drop);
-        }
+        ctx_block_give(ctx, CTX_MEM_DEVICE, d, d_bytes);
         d = nullptr;
         d_chunks = d_bytes = 0;
         up_chunks = 0;
     }
+};
+
+// The form and launch shape of K7, decided once per prepare (ba_k7_shape).
+struct K7Launch {
+    bool det = false;    // ptam_ba_opts.deterministic: K7 stores A / epsilon per measurement, reduce_det_kernel sums per camera
+    bool big = false;    // camera partials + poses of K7 in global memory (more cameras than a workgroup's LDS holds)
+    bool loop = false;   // persistent workgroups looping over `per_wave` consecutive chunks (false: one chunk per wave)
+    int threads = BA_CHUNK;
+    int per_cu = 0;      // workgroups of that width a CU holds
+    size_t smem = 0;     // LDS bytes of a workgroup
+    int per_wave = 1, extra_waves = 0;
+    int grid = 1, u_rows = 1;   // BaDev::grid_acc, BaDev::u_rows
 };
 
 struct ptam_ba {
@@ -222,11 +211,8 @@ struct ptam_ba {
     bool e2_is_current = false;   // m_e2 / m_state hold pass 1 of the CURRENT poses and points (the last step accepted nothing)
     int band_local = 0;     // block bandwidth of S needed by THIS process' points (ba->d.band: the one in force)
     int cur = 0;
-    size_t smem_acc = 0;
     bool use_wave = false;
-    bool det = false;        // ptam_ba_opts.deterministic: K7 stores A / epsilon per measurement, reduce_det_kernel sums per camera
-    bool k7_big = false;     // camera partials + poses of K7 in global memory (more cameras than a workgroup's LDS holds)
-    int per_wave = 1, extra_waves = 0;
+    K7Launch k7;   // the form and launch shape of the accumulation kernel (ba_k7_shape)
     // host-mapped mailbox the device publishes BaScalars into (the LM loop's one host decision per trial)
     struct Mailbox {
         struct Slot {
@@ -240,8 +226,6 @@ struct ptam_ba {
     bool decide_pending = false;     // the trial's decision is left to the first launch of the speculative prologue (purge_pass1_decide_kernel)
     int decide_last_allowed = 0;
     bool trial_is_current = false;   // the last trial was accepted: its new-error pass == pass 1 of the next step
-    int k7_threads = BA_CHUNK;
-    bool k7_loop = false;
     std::vector<int> pt_orig;       // device point id -> original point id (the points with a live measurement, ascending)
     int* d_pt_orig = nullptr;       // the same on the device (a piece of the block)
     const double* pts_dev = nullptr;   // ba_dev_ingest: the points are already on the device (pts is then sized but not filled)
@@ -267,14 +251,9 @@ struct ptam_ba {
 };
 
 static void ba_free_device(ptam_ba* ba) {
-    for (int k = 0; k < 2; k++) {
-        void* blk = k ? ba->sblock : ba->block;
-        if (blk) {
-            // the block's kernels may still be queued: the next owner only touches it through the same stream
-            void* drop = ctx_cache_give(ba->ctx->dev_cache, CTX_NCACHE(ba->ctx->dev_cache), blk, k ? ba->sblock_cap : ba->block_cap);
-            if (drop) hipFree(drop);
-        }
-    }
+    // the blocks' kernels may still be queued: the next owner only touches them through the same stream
+    ctx_block_give(ba->ctx, CTX_MEM_DEVICE, ba->block, ba->block_cap);
+    ctx_block_give(ba->ctx, CTX_MEM_DEVICE, ba->sblock, ba->sblock_cap);
     if (ba->d_gather) hipFree(ba->d_gather);
     if (ba->d_xchg && ba->xchg_owned) hipFree(ba->d_xchg);   // (otherwise a piece of the block)
     ba->xchg_owned = false;
@@ -342,288 +321,362 @@ static int ba_k7_occupancy(ptam_ctx* ctx, const void* k7, int threads, size_t sm
     return rc;
 }
 
-static int ba_prepare_impl(ptam_ba* ba) {
+// ---- read back results: one pinned staging buffer, one synchronisation (pageable destinations cost ~100 us each) ----
+// the staging it needs: [sequence word (64 bytes) | poses | points | outlier indices | 64 bytes].  ptam_ba_prepare asks for it up front,
+// for as many indices as there are live measurements: growing the staging inside Compute() re-maps host memory under queued kernels.
+static size_t ba_readback_bytes(int C, int P, int n_out) { return 64 + (size_t)C * 96 + (size_t)P * 24 + (size_t)n_out * 4 + 64; }
+static int ba_readback(ptam_ba* ba, int n_out, std::vector<int>& out_idx) {
     ptam_ctx* ctx = ba->ctx;
-    // PTAM_DEBUG_PREPARE=1: host time of the phases of this function
-    static const bool dbg_prep = getenv("PTAM_DEBUG_PREPARE") != nullptr;
-    auto pt0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!dbg_prep) return;
-        const auto t = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[ptam] prepare: %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - pt0).count());
-        pt0 = t;
-    };
-    ba_finish_outliers(ba);   // erased measurements of earlier Compute() calls leave the problem here
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ptam_stream_wait(ctx->stream));
-    ba_free_device(ba);
-    BaDev& d = ba->d;
-    std::memset(&d, 0, sizeof d);
-    const int C = (int)ba->cam_fixed.size(), P_all = (int)(ba->pts.size() / 3);
-    const int Mall = (int)ba->ms.size();
-    const int M = Mall - ba->n_dead;
-    // free-camera indices in insertion order  (nStartRow, src/Bundle.cc:52-57)
-    std::vector<int> cam_free(C, -1);
-    int F = 0;
-    for (int c = 0; c < C; c++)
-        if (!ba->cam_fixed[c]) cam_free[c] = F++;
-    const int n_tiles = (F + SCHUR_TC - 1) / SCHUR_TC;
-    const int n_pairs = n_tiles * (n_tiles + 1) / 2;
-    const bool lists = F > 0 && M > 0;   // Schur work lists exist
-    d.C = C;
-    d.F = F;
-    d.M = M;
-    d.n = 6 * F;
-    d.npad = ((d.n + SOLVE_NB - 1) / SOLVE_NB) * SOLVE_NB;
-    d.n_wchunks = M > 0 ? 1 : 0;
-    ba->use_wave = M > 0;   // (false: no live measurement at all — K7 is then a memset of its outputs)
-    d.n_tiles = n_tiles;
-    d.n_pairs = n_pairs;
+    const BaDev& d = ba->d;
+    const size_t b_pose = (size_t)d.C * 96, b_pts = (size_t)d.P * 24, b_out = (size_t)n_out * 4;
+    void* pin = nullptr;
+    int rc = ctx_pinned(ctx, ba_readback_bytes(d.C, d.P, n_out), &pin);
+    if (rc) return rc;
+    char* hp = (char*)pin + 64;   // [sequence word | poses | points | outlier indices]
+    char* dp = (char*)ctx->d_pinned + 64;
+    volatile unsigned long long* slot = (volatile unsigned long long*)pin;
+    const unsigned long long seq = ++ctx->pose_seq;
+    *slot = 0;
+    const size_t n_all = (size_t)d.C * 12 + (size_t)d.P * 3 + (size_t)n_out;
+    hipLaunchKernelGGL(readback_kernel, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n_all + 255) / 256, 1024))), dim3(256), 0,
+                       ctx->stream, (const double*)d.pose[ba->cur], (size_t)d.C * 12, (const double*)d.pt[ba->cur], (size_t)d.P * 3,
+                       (const int*)d.outliers, (size_t)n_out, (double*)dp, (double*)(dp + b_pose), (int*)(dp + b_pose + b_pts));
+    hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, ctx->stream, (volatile unsigned long long*)ctx->d_pinned, seq);
+    HIP_TRY(hipGetLastError());
+    rc = ba_wait_stamp(ctx, slot, seq, "the bundle's results");
+    if (rc) return rc;
+    std::memcpy(ba->cam_pose.data(), hp, b_pose);
+    for (int q = 0; q < d.P; q++)   // (device point q is original point pt_orig[q]; unobserved points keep their position)
+        std::memcpy(&ba->pts[(size_t)3 * ba->pt_orig[(size_t)q]], hp + b_pose + (size_t)q * 24, 24);
+    if (n_out > 0) std::memcpy(out_idx.data(), hp + b_pose + b_pts, b_out);
+    return PTAM_OK;
+}
+
+// =================================================================================================
+// prepare: the bundle's device blocks and index structures (ba_prepare.inc).  ba_prepare_impl, at the end, is the sequence of the
+// steps below.
+// =================================================================================================
+// The small tables the host fills, one upload: [initial PrepScalars | poses | free-camera indices | both pair orders] — a piece of
+// the main block and, in the same layout, a piece of the pinned staging.
+struct PrepSmall {
+    PrepScalars* ps;
+    double* pose;
+    int* cam_free;
+    int* pair_order;
+};
+static PrepSmall ba_layout_small(Carver& sm, size_t Cz, size_t n_order) {
+    PrepSmall s;
+    s.ps = sm.piece<PrepScalars>(1);
+    s.pose = sm.piece<double>(Cz * 12);
+    s.cam_free = sm.piece<int>(Cz);
+    s.pair_order = sm.piece<int>(n_order);
+    return s;
+}
+
+// pinned staging: [stamp | scalars read back | rowptr | dense point ids | small tables | chunks | erased marks]
+struct PrepStage {
+    volatile unsigned long long* stamp;
+    PrepScalars* ps;
+    int* rowptr;
+    int* pt_orig;
+    char* small;
+    BaChunk* chunks;
+    uint8_t* dead;
+};
+
+// One prepare's working set: the bundle's sizes, what the host computes for the device, and the pieces of the blocks that BaDev
+// does not keep.
+struct Prep {
+    int C = 0, F = 0, P_all = 0, Mall = 0, M = 0;   // cameras, free cameras, points, measurements as added, live measurements
+    int n_dead = 0, n_tiles = 0, n_pairs = 0;
+    int nw = 1;            // 64-bit words of tile codes per point (32 tiles each)
+    int n_dtiles = 0;      // tiles of DET_TILE measurements (deterministic mode)
+    bool lists = false;    // Schur work lists exist
+    size_t chunks_cap = 0;
+    SplitCfg cfg;
+    std::vector<int> cam_free;     // free-camera indices in insertion order, -1: fixed
+    std::vector<int> pair_order;   // [2][n_pairs] natural | by fragment products
+    PrepDev q = {};                // the builder kernels' argument
+    // main block
+    size_t small_bytes = 0, clear_bytes = 0;
+    char* small = nullptr;        // the small tables
+    uint8_t* r_dead = nullptr;    // raw input: erased marks, points (insertion order)
+    double* pts_raw = nullptr;
+    double* xchg = nullptr;       // ptam_ba::d_xchg
+    int* tile_free = nullptr;     // deterministic lists: measurements by free cameras per tile
+    // pinned staging: the size asked of the context, the pieces at their host and at their device addresses (host-mapped)
+    size_t staging_bytes = 0;
+    PrepStage h, hd;
+    PrepLaps lap;
+};
+
+static PrepStage ba_layout_stage(Carver& hs, const Prep& p) {
+    const size_t Pz = std::max(p.P_all, 1), Maz = std::max(p.Mall, 1);
+    PrepStage h;
+    h.stamp = hs.piece<unsigned long long>(8);
+    h.ps = hs.piece<PrepScalars>(1);
+    h.rowptr = hs.piece<int>(Pz + 1);
+    h.pt_orig = hs.piece<int>(Pz);
+    h.small = hs.piece<char>(p.small_bytes);
+    h.chunks = hs.piece<BaChunk>(p.chunks_cap);
+    h.dead = hs.piece<uint8_t>(p.n_dead > 0 ? Maz : 1);
+    return h;
+}
+
+static int ba_upload(ptam_ctx* ctx, void* dst, const void* src, size_t bytes) {
+    if (bytes > 0) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return PTAM_OK;
+}
+
+// ---- the Schur split's configuration and the two pair orders -------------------------------------------------------------------
+static void ba_prep_split_config(Prep& p) {
     // The tile kernel's work split (ba_split.h): cost model fitted to the kernel's per-workgroup stamps at 50 x 5000
     // (tools/dev/schur_fit.py, docs/LOG_r05.md) — a group of four entries takes 10 f + 36 units (f: the 16x16 fragment products of
     // its pattern; the 36 are its loads), a SEGMENT costs as much as ~10 full groups (pipeline fill: three dependent round trips;
     // cross-wave reduction; partial tile out), and the SECOND workgroup of a CU — its waves are the younger ones, the issue arbiter
     // prefers the older — ends 4.5 - 9 us behind the first for the same work, so it gets 7 us less.
-    SplitCfg cfg;
+    SplitCfg& cfg = p.cfg;
     cfg.cost_model = 36;
     cfg.seg_cost = 4900;
     cfg.second_lag = 7000;
     cfg.min_seg = 16;
     cfg.slots = 256 * SCHUR_WG_PER_CU / 8;   // workgroups one XCD holds at once (block b runs on XCD b % 8)
     cfg.n_first = SCHUR_WG_PER_CU == 2 ? cfg.slots / 2 : cfg.slots;
-    if (const char* e = ptam_ab_env("PTAM_SCHUR_COST")) cfg.cost_model = atoi(e);   // A/B runs
-    if (const char* e = ptam_ab_env("PTAM_SCHUR_SEGCOST")) cfg.seg_cost = atoi(e);
-    if (const char* e = ptam_ab_env("PTAM_SCHUR_LAG")) cfg.second_lag = atoi(e);
-    cfg.greedy = ptam_ab_env("PTAM_SPLIT_GREEDY") ? 1 : 0;   // (A/B: the greedy fill + budget search, this round's first form)
+    cfg.greedy = 0;
     cfg.min_room = cfg.seg_cost;   // a workgroup begins another segment only for at least this much work
+    // A/B runs
+    if (const char* e = ptam_ab_env("PTAM_SCHUR_COST")) cfg.cost_model = atoi(e);
+    if (const char* e = ptam_ab_env("PTAM_SCHUR_SEGCOST")) cfg.seg_cost = cfg.min_room = atoi(e);
+    if (const char* e = ptam_ab_env("PTAM_SCHUR_LAG")) cfg.second_lag = atoi(e);
+    if (ptam_ab_env("PTAM_SPLIT_GREEDY")) cfg.greedy = 1;   // (the greedy fill + budget search, this round's first form)
     if (const char* e = ptam_ab_env("PTAM_SCHUR_MINROOM")) cfg.min_room = atoi(e);
     // Order of the pairs in an XCD's list, both candidates (the device picks: by products only where both slots of the CUs are
     // in use).  By products = the fewest fragment products first: the list's first half becomes the FIRST workgroup of each CU,
     // whose (older) waves the issue arbiter prefers — a load-bound pair there (a last tile of one or two cameras: 3 products a step
     // against 21 loads) leaves the matrix pipe to the younger product-bound partner, while in the second slot it starved behind the
     // partner's products and then ran on alone for 12 us (stamps: docs/LOG_r05.md).
-    std::vector<int> pair_order((size_t)2 * std::max(n_pairs, 1), 0);
-    {
-        std::vector<int> pa(n_pairs), pb(n_pairs);
-        for (int a = 0, pr = 0; a < n_tiles; a++)
-            for (int b = 0; b <= a; b++, pr++) pa[pr] = a, pb[pr] = b;
-        for (int pr = 0; pr < n_pairs; pr++) pair_order[pr] = pair_order[(size_t)n_pairs + pr] = pr;
-        std::stable_sort(pair_order.begin() + n_pairs, pair_order.begin() + 2 * (size_t)n_pairs,
-                         [&](int p, int q) { return split_full_products(F, pa[p], pb[p]) < split_full_products(F, pa[q], pb[q]); });
-    }
-    // persistent grid of the accumulate kernel: bounded by LDS residency, 2 x 256 CUs by default
-    // (wave variant: + one 3 KB W transposition buffer per wave, K7_WT_DOUBLES)
-    ba->k7_big = false;
-    ba->det = ba->opts.deterministic != 0 && M > 0;
-    auto k7_smem = [&](int threads) {
-        const size_t wt = (size_t)(threads / 64) * K7_WT_DOUBLES * sizeof(double);
-        if (ba->k7_big) return wt;   // (camera partials and poses in global memory)
-        if (ba->det) return ((size_t)C * 12 + 2) * sizeof(double) + wt;   // (no camera partials at all)
-        return ((((size_t)F * 27 + 1) & ~(size_t)1) + (size_t)C * 12 + 2) * sizeof(double) + wt;
-    };
-    // wave variant, two shapes:
-    //  - few chunks (every 64-measurement chunk can be resident at once: <= 24 waves per CU):
-    //    straight-line kernel, ONE chunk per wave, 1024-thread workgroups (79 VGPRs);
-    //  - many chunks: persistent 256-thread workgroups looping over `per_wave` consecutive chunks,
-    //    which amortises the LDS prologue and the camera-partial flush.
-    const int n64_all = (M + 63) / 64;
-    ba->k7_loop = ba->use_wave && n64_all > 256 * 24;
-    if (const char* e = ptam_ab_env("PTAM_K7_LOOP")) ba->k7_loop = ba->use_wave && atoi(e) != 0;   // shape sweeps (tools/k7_only.py)
-    ba->k7_threads = ba->k7_loop ? 256 : 1024;   // (one chunk per wave: 1024-thread workgroups halve the
-                                                                                 //  camera-partial flush — 12.0 vs 12.3 us at 50 x 5000)
+    const int F = p.F, n_tiles = p.n_tiles, n_pairs = p.n_pairs;
+    p.pair_order.assign((size_t)2 * std::max(n_pairs, 1), 0);
+    std::vector<int> pa(n_pairs), pb(n_pairs);
+    for (int a = 0, pr = 0; a < n_tiles; a++)
+        for (int b = 0; b <= a; b++, pr++) pa[pr] = a, pb[pr] = b;
+    for (int pr = 0; pr < n_pairs; pr++) p.pair_order[pr] = p.pair_order[(size_t)n_pairs + pr] = pr;
+    std::stable_sort(p.pair_order.begin() + n_pairs, p.pair_order.begin() + 2 * (size_t)n_pairs,
+                     [&](int x, int y) { return split_full_products(F, pa[x], pb[x]) < split_full_products(F, pa[y], pb[y]); });
+}
+
+// ---- the launch shape of K7 ----------------------------------------------------------------------------------------------------
+// persistent grid of the accumulate kernel: bounded by LDS residency, 2 x 256 CUs by default
+// (wave variant: + one 3 KB W transposition buffer per wave, K7_WT_DOUBLES)
+static size_t ba_k7_smem(const K7Launch& k, const Prep& p, int threads) {
+    const size_t wt = (size_t)(threads / 64) * K7_WT_DOUBLES * sizeof(double);
+    if (k.big) return wt;   // (camera partials and poses in global memory)
+    if (k.det) return ((size_t)p.C * 12 + 2) * sizeof(double) + wt;   // (no camera partials at all)
+    return ((((size_t)p.F * 27 + 1) & ~(size_t)1) + (size_t)p.C * 12 + 2) * sizeof(double) + wt;
+}
+static int ba_k7_per_cu(ptam_ba* ba, const Prep& p, const K7Launch& k, int threads, int* per_cu) {
+    return ba_k7_occupancy(ba->ctx, k7_wave_fn(threads, k.loop, ba->opts.estimator, k.big, k.det), threads, ba_k7_smem(k, p, threads), per_cu);
+}
+
+// The product's rules for K7's form and workgroup width.  `loop`: the bundle has more chunks than can be resident at once —
+// wave variant, two shapes:
+//  - few chunks (every 64-measurement chunk can be resident at once: <= 24 waves per CU):
+//    straight-line kernel, ONE chunk per wave, 1024-thread workgroups (79 VGPRs);
+//  - many chunks: persistent 256-thread workgroups looping over `per_wave` consecutive chunks,
+//    which amortises the LDS prologue and the camera-partial flush.
+static int ba_k7_rules(ptam_ba* ba, const Prep& p, bool loop, K7Launch& k) {
+    const int n64_all = (p.M + 63) / 64;
+    k.big = false;
+    k.det = ba->opts.deterministic != 0 && p.M > 0;
+    k.loop = loop;
+    k.threads = k.loop ? 256 : 1024;   // (one chunk per wave: 1024-thread workgroups halve the
+                                       //  camera-partial flush — 12.0 vs 12.3 us at 50 x 5000)
     // (a small bundle in 1024-thread workgroups leaves most CUs idle — 20 x 3 000: 58 workgroups, four waves per SIMD on 58 CUs —
     //  and its waves share a SIMD for nothing: 512 threads, 13.5 instead of 14.6 us per launch there; not in deterministic mode,
     //  which has no such instantiation)
-    if (!ba->k7_loop && ba->opts.deterministic == 0 && n64_all < 16 * 128) ba->k7_threads = 512;
-    const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
-    auto k7_fn = [&](int threads) -> const void* { return k7_wave_fn(threads, ba->k7_loop, ba->opts.estimator, ba->k7_big, ba->det); };
-    auto k7_occupancy = [&](int threads, int* per_cu) -> int { return ba_k7_occupancy(ctx, k7_fn(threads), threads, k7_smem(threads), per_cu); };
-    int per_cu = 0;
-    {
-        // the workgroup's LDS — camera partials F * 216 B + poses C * 96 B + 3 KB per wave — must fit the CU's 160 KB: many
-        // cameras take narrower workgroups (fewer transposition buffers), and beyond ~600 free cameras the BIG form, whose
-        // partials and poses stay in global memory (ba_jacobian.inc)
-        const size_t lds_max = 160 * 1024;
-        if (k7_smem(ba->k7_threads) > lds_max) {
-            for (int t : {512, 256})
-                if (k7_smem(t) <= lds_max) {
-                    ba->k7_threads = t;
-                    break;
-                }
-            if (k7_smem(ba->k7_threads) > lds_max) {
-                ba->k7_big = true;
-                ba->k7_loop = true;
-                ba->k7_threads = 256;
+    if (!k.loop && ba->opts.deterministic == 0 && n64_all < 16 * 128) k.threads = 512;
+    // the workgroup's LDS — camera partials F * 216 B + poses C * 96 B + 3 KB per wave — must fit the CU's 160 KB: many
+    // cameras take narrower workgroups (fewer transposition buffers), and beyond ~600 free cameras the BIG form, whose
+    // partials and poses stay in global memory (ba_jacobian.inc)
+    const size_t lds_max = 160 * 1024;
+    if (ba_k7_smem(k, p, k.threads) > lds_max) {
+        for (int t : {512, 256})
+            if (ba_k7_smem(k, p, t) <= lds_max) {
+                k.threads = t;
+                break;
             }
-        }
-        // (the deterministic instantiations are the one-chunk-per-wave form at 1024 threads and the looping form at 256; where the
-        //  former does not fit the CU's LDS — the reason a narrower workgroup was picked above — the looping form runs)
-        if (ba->det && !ba->k7_big && ba->k7_threads != (ba->k7_loop ? 256 : 1024)) {
-            ba->k7_loop = true;
-            ba->k7_threads = 256;
+        if (ba_k7_smem(k, p, k.threads) > lds_max) {
+            k.big = true;
+            k.loop = true;
+            k.threads = 256;
         }
     }
-    if (int rc = k7_occupancy(ba->k7_threads, &per_cu)) {
-        ptam_set_error("the accumulation kernel cannot be launched with %zu bytes of LDS (%d free cameras)", k7_smem(ba->k7_threads), F);
+    // (the deterministic instantiations are the one-chunk-per-wave form at 1024 threads and the looping form at 256; where the
+    //  former does not fit the CU's LDS — the reason a narrower workgroup was picked above — the looping form runs)
+    if (k.det && !k.big && k.threads != (k.loop ? 256 : 1024)) k.loop = true, k.threads = 256;
+    if (int rc = ba_k7_per_cu(ba, p, k, k.threads, &k.per_cu)) {
+        ptam_set_error("the accumulation kernel cannot be launched with %zu bytes of LDS (%d free cameras)", ba_k7_smem(k, p, k.threads), p.F);
         return rc;
     }
-    if (ba->k7_loop && !ba->k7_big && !ba->det) {
+    if (k.loop && !k.big && !k.det) {
         // many cameras: the LDS partials (F*27 + C*12 doubles per workgroup) bound the workgroups per CU,
         // so a wider workgroup keeps more waves resident (200 cameras: 62 KB + 3 KB per wave -> ONE workgroup per CU
         // whatever its width, and only the 1024-thread one fills the four waves per SIMD the loop needs)
         for (int t : {512, 1024}) {
             int per_cu_t = 0;
-            if (int rc = k7_occupancy(t, &per_cu_t)) return rc;
-            if (per_cu_t * t > per_cu * ba->k7_threads) {
-                ba->k7_threads = t;
-                per_cu = per_cu_t;
+            if (int rc = ba_k7_per_cu(ba, p, k, t, &per_cu_t)) return rc;
+            if (per_cu_t * t > k.per_cu * k.threads) {
+                k.threads = t;
+                k.per_cu = per_cu_t;
             }
         }
     }
-    per_cu = std::max(1, std::min(per_cu, 8));
-    if (ba->use_wave && ba->k7_loop && !ba->k7_big) {
+    k.per_cu = std::max(1, std::min(k.per_cu, 8));
+    return PTAM_OK;
+}
+
+// The shape in force: the rules, then the A/B overrides of the measurement build (the product compiles them to nothing), then the
+// grid that follows from the form and the width.
+static int ba_k7_shape(ptam_ba* ba, const Prep& p, K7Launch* out) {
+    const bool use_wave = p.M > 0;
+    const int n64 = (p.M + 63) / 64;
+    const size_t lds_max = 160 * 1024;
+    K7Launch k;
+    bool loop = use_wave && n64 > 256 * 24;
+    if (const char* e = ptam_ab_env("PTAM_K7_LOOP")) loop = use_wave && atoi(e) != 0;   // shape sweeps (tools/k7_only.py)
+    if (int rc = ba_k7_rules(ba, p, loop, k)) return rc;
+    if (use_wave && k.loop && !k.big) {
         if (const char* e = ptam_ab_env("PTAM_K7_THREADS")) {
             const int t = atoi(e);
-            // (A/B override; never 512 in deterministic mode, which has no such instantiation, and never a width whose LDS does not fit)
-            if ((t == 256 || t == 512 || t == 1024) && !(ba->det && t != 256) && k7_smem(t) <= 160 * 1024) {
-                ba->k7_threads = t;
-                if (int rc = k7_occupancy(t, &per_cu)) return rc;
-                per_cu = std::max(1, std::min(per_cu, 8));
+            // (never 512 in deterministic mode, which has no such instantiation, and never a width whose LDS does not fit)
+            if ((t == 256 || t == 512 || t == 1024) && !(k.det && t != 256) && ba_k7_smem(k, p, t) <= lds_max) {
+                k.threads = t;
+                if (int rc = ba_k7_per_cu(ba, p, k, t, &k.per_cu)) return rc;
+                k.per_cu = std::max(1, std::min(k.per_cu, 8));
             }
         }
-        if (const char* e = ptam_ab_env("PTAM_K7_WG_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(e)));
+        if (const char* e = ptam_ab_env("PTAM_K7_WG_PER_CU")) k.per_cu = std::max(1, std::min(k.per_cu, atoi(e)));
     }
-    if (ba->use_wave && !ba->k7_loop) {
-        if (const char* e = ptam_ab_env("PTAM_K7_THREADS1")) {   // (A/B of the one-chunk-per-wave shape: 512 / 1024-thread workgroups)
+    if (use_wave && !k.loop) {
+        if (const char* e = ptam_ab_env("PTAM_K7_THREADS1")) {   // (the one-chunk-per-wave shape: 512 / 1024-thread workgroups)
             const int t = atoi(e);
-            if ((t == 512 || t == 1024) && !(ba->det && t != 1024) && k7_smem(t) <= 160 * 1024) {
-                ba->k7_threads = t;
-                if (int rc = k7_occupancy(t, &per_cu)) return rc;
+            if ((t == 512 || t == 1024) && !(k.det && t != 1024) && ba_k7_smem(k, p, t) <= lds_max) {
+                k.threads = t;
+                if (int rc = ba_k7_per_cu(ba, p, k, t, &k.per_cu)) return rc;
             }
         }
     }
-    ba->smem_acc = k7_smem(ba->k7_threads);
-    if (ba->use_wave) {
+    k.smem = ba_k7_smem(k, p, k.threads);
+    if (use_wave) {
         // every wave gets the same number of consecutive 64-measurement chunks
         // one 64-measurement chunk per wave (straight-line kernel body: 68 VGPRs instead of ~160 for the
         // looping form, i.e. every chunk of a 250 k-measurement problem is resident at once)
-        const int n64 = (M + 63) / 64;
-        const int wpb = ba->k7_threads / 64;
-        if (ba->k7_loop) {
+        const int wpb = k.threads / 64;
+        if (k.loop) {
             // every resident slot gets a workgroup; chunks are dealt out evenly (q or q + 1 per wave)
-            d.grid_acc = std::max(1, std::min(n_cu * per_cu, n64 / wpb));
-            const int waves = d.grid_acc * wpb;
-            ba->per_wave = n64 / waves;
-            ba->extra_waves = n64 - ba->per_wave * waves;
-        } else {
-            ba->per_wave = 1;
-            ba->extra_waves = 0;
-            d.grid_acc = std::max(1, (n64 + wpb - 1) / wpb);
-        }
-    } else
-        d.grid_acc = 1;
-    const int n_dtiles = (M + DET_TILE - 1) / DET_TILE;
-    d.u_rows = ba->det ? n_dtiles : (ba->k7_big || !ba->use_wave) ? 1 : d.grid_acc;
-    lap("launch shape");
+            const int n_cu = ba->ctx->n_cu > 0 ? ba->ctx->n_cu : 256;
+            k.grid = std::max(1, std::min(n_cu * k.per_cu, n64 / wpb));
+            const int waves = k.grid * wpb;
+            k.per_wave = n64 / waves;
+            k.extra_waves = n64 - k.per_wave * waves;
+        } else   // (per_wave 1, no extra waves)
+            k.grid = std::max(1, (n64 + wpb - 1) / wpb);
+    }
+    k.u_rows = k.det ? p.n_dtiles : (k.big || !use_wave) ? 1 : k.grid;
+    *out = k;
+    return PTAM_OK;
+}
 
-    // ---- carve the main device allocation (sizes the host knows: M exactly, the points by their upper bound) --------------------
-    Carver cv;
-    const size_t Mz = std::max(M, 1), Pz = std::max(P_all, 1), Cz = std::max(C, 1), Fz = std::max(F, 1), Maz = std::max(Mall, 1);
-    // chunks: consecutive whole points, at most BA_CHUNK measurements — two neighbours together exceed BA_CHUNK measurements or
-    // BA_CHUNK points, or one of them is a long point
-    const size_t chunks_cap = std::min<size_t>(Pz, (size_t)M / 64 + (size_t)P_all / 128 + 8);
-    const size_t o_pose0 = cv.take(Cz * 96), o_pose1 = cv.take(Cz * 96);
-    const size_t o_pt0 = cv.take(Pz * 24), o_pt1 = cv.take(Pz * 24), o_V = cv.take(Pz * 48), o_epsB = cv.take(Pz * 24),
-                 o_Vinv = cv.take(Pz * 72), o_rowptr = cv.take((Pz + 1) * 4),
-                 o_cut = cv.take(ba->use_wave ? (size_t)((M + 63) / 64) * 2 * 72 : 8);
-    const size_t o_mcam = cv.take(Mz * 4), o_mpt = cv.take(Mz * 4), o_mfound = cv.take(Mz * 16), o_ms = cv.take(Mz * 8),
-                 o_morig = cv.take(Mz * 4), o_mfidx = cv.take(Mz * 4), o_mstate = cv.take(Mz), o_me2 = cv.take(Mz * 8), o_me2t = cv.take(Mz * 8), o_zbad = cv.take(Mz), o_W = cv.take((Mz + 1) * 144);
-    const size_t o_U = cv.take(Fz * 27 * 8 * 16), o_Upart = cv.take((size_t)std::max(d.grid_acc, ba->det ? n_dtiles : 1) * Fz * 27 * 8);
-    const size_t o_adet = cv.take(ba->det ? Mz * 14 * 8 : 8), o_camptr = cv.take(ba->det ? (size_t)n_dtiles * (Fz + 1) * 4 : 8), o_cammeas = cv.take(ba->det ? Mz * 4 : 8),
-                 o_tilefree = cv.take(ba->det ? ((size_t)n_dtiles + 1) * 4 : 8);
-    const size_t n_part = std::max<size_t>(chunks_cap, (size_t)d.grid_acc);
-    const size_t o_errp = cv.take(n_part * 16 + 16), o_badp = cv.take((size_t)d.grid_acc * 4 + 16);
-    const size_t o_chunks = cv.take(chunks_cap * sizeof(BaChunk));
-    const size_t o_wchunks = cv.take(sizeof(BaChunk));
-    const size_t o_hist = cv.take(2 * HIST_BINS * 4), o_cand = cv.take(Mz * 8);
-    const size_t npad = std::max(d.npad, SOLVE_NB);
+// ---- the main block (sizes the host knows: M exactly, the points by their upper bound) --------------------------------------------
+// Every piece of the block, once, in the block's order: the members of BaDev, the builder's tables (PrepDev) and the few pieces
+// Prep keeps.  Everything before `clear_bytes` is cleared; what follows is written before it is read.
+static void ba_layout_main(Carver& cv, const ptam_ba* ba, BaDev& d, Prep& p) {
+    PrepDev& q = p.q;
+    const bool det = ba->k7.det;
+    const size_t Mz = std::max(p.M, 1), Pz = std::max(p.P_all, 1), Cz = std::max(p.C, 1), Fz = std::max(p.F, 1), Maz = std::max(p.Mall, 1);
+    const size_t n_dtiles = (size_t)p.n_dtiles;
+    (void)cv.take(Cz * 96);   // (a piece nobody uses: the current poses are uploaded with the small tables, below)
+    d.pose[1] = cv.piece<double>(Cz * 12);
+    d.pt[0] = cv.piece<double>(Pz * 3), d.pt[1] = cv.piece<double>(Pz * 3);
+    d.V = cv.piece<double>(Pz * 6);
+    d.epsB = cv.piece<double>(Pz * 3);
+    d.Vinv = cv.piece<double>(Pz * 9);
+    d.rowptr = cv.piece<int>(Pz + 1);
+    d.cut = cv.piece<double>(ba->use_wave ? (size_t)((p.M + 63) / 64) * 2 * 9 : 1);
+    if (!ba->use_wave) d.cut = nullptr;
+    d.m_cam = cv.piece<int>(Mz), d.m_pt = cv.piece<int>(Mz);
+    d.m_found = cv.piece<double2>(Mz);
+    d.m_s = cv.piece<double>(Mz);
+    d.m_orig = cv.piece<int>(Mz), d.m_fidx = cv.piece<int>(Mz);
+    d.m_state = cv.piece<uint8_t>(Mz);
+    d.m_e2 = cv.piece<double>(Mz), d.m_e2t = cv.piece<double>(Mz);
+    d.m_zbad_t = cv.piece<uint8_t>(Mz);
+    d.W = cv.piece<double>((Mz + 1) * 18);   // (slot M of every plane stays zero: the block is cleared and nobody writes it)
+    d.Usplit = cv.piece<double>(Fz * 27 * 16);
+    d.Upart = cv.piece<double>((size_t)std::max(d.grid_acc, det ? p.n_dtiles : 1) * Fz * 27);
+    d.Adet = cv.piece<double>(det ? Mz * 14 : 1);
+    if (!det) d.Adet = nullptr;
+    d.cam_ptr = cv.piece<int>(det ? n_dtiles * (Fz + 1) : 2), d.cam_meas = cv.piece<int>(det ? Mz : 2);
+    p.tile_free = cv.piece<int>(det ? n_dtiles + 1 : 2);
+    d.err_part = cv.piece<double>(std::max<size_t>(p.chunks_cap, (size_t)d.grid_acc) * 2 + 2);
+    d.bad_part = cv.piece<int>((size_t)d.grid_acc + 4);
+    d.chunks = cv.piece<BaChunk>(p.chunks_cap), d.wchunks = cv.piece<BaChunk>(1);
+    d.hist = cv.piece<unsigned>(2 * HIST_BINS);
+    d.cand = cv.piece<double>(Mz);
     // S and L block-banded (bundle.h: se_blk); sized for the full lower triangle, because a sharded bundle only learns the
     // bandwidth in force (the widest over all ranks) in Compute()'s first exchange
-    const size_t se_full = se_size((int)(npad / SOLVE_NB), (int)(npad / SOLVE_NB) - 1);
-    const size_t o_SE = cv.take((se_full + npad + 8) * 8), o_L = cv.take(se_full * 8), o_Dg = cv.take(npad * 8),
-                 o_y = cv.take(npad * 8), o_da = cv.take(npad * 8), o_sq2 = cv.take(16),
-                 o_bws = cv.take(npad * 8 * 12), o_sflags = cv.take(ba_solve_flag_bytes((int)(npad / SOLVE_NB))),
-                 o_sflags2 = cv.take(ba_solve_flag_bytes((int)(npad / SOLVE_NB))), o_SE2 = cv.take((se_full + npad + 8) * 8),
-                 o_L2 = cv.take(se_full * 8), o_Dg2 = cv.take(npad * 8), o_y2 = cv.take(npad * 8);
-    const size_t o_out = cv.take(Mz * 4), o_sc = cv.take(sizeof(BaScalars)), o_dbg = cv.take(65536), o_xchg = cv.take(4096);
+    const size_t npad = std::max(d.npad, SOLVE_NB), nblk = npad / SOLVE_NB;
+    const size_t se_full = se_size((int)nblk, (int)nblk - 1), n_flags = ba_solve_flag_bytes((int)nblk) / sizeof(unsigned);
+    d.SE = cv.piece<double>(se_full + npad + 8);
+    d.L = cv.piece<double>(se_full);
+    d.Dg = cv.piece<double>(npad), d.y = cv.piece<double>(npad), d.da = cv.piece<double>(npad);
+    d.sumsq2 = cv.piece<double>(2);
+    d.bw_scratch = cv.piece<double>(npad * 12);
+    d.sflags = cv.piece<unsigned>(n_flags), d.sflags2 = cv.piece<unsigned>(n_flags);   // (cleared with the block: sequence numbers start at 1)
+    d.SE2 = cv.piece<double>(se_full + npad + 8);
+    d.L2 = cv.piece<double>(se_full);
+    d.Dg2 = cv.piece<double>(npad), d.y2 = cv.piece<double>(npad);
+    d.outliers = cv.piece<int>(Mz);
+    d.sc = cv.piece<BaScalars>(1), d.dbg = cv.piece<long long>(8192);
+    p.xchg = cv.piece<double>(512);
     // the builder's cleared tables: live measurements per point, tile codes, (XCD, pair, pattern) counts
-    const int nw = std::max(1, (n_tiles + 31) / 32);
-    const size_t hist_n = (size_t)8 * std::max(n_pairs, 1) * 16;
-    const size_t o_cnt = cv.take(Pz * 4), o_tcode = cv.take(Pz * (size_t)nw * 8), o_phist = cv.take(hist_n * 4);
-    const size_t clear_bytes = cv.off;   // ---- everything up to here is cleared; what follows is written before it is read ----
-    // small tables the host fills, one upload: [initial PrepScalars | poses | free-camera indices | both pair orders]
-    Carver sm;
-    const size_t s_ps = sm.take(sizeof(PrepScalars)), s_pose = sm.take(Cz * 96), s_camfree = sm.take(Cz * 4),
-                 s_porder = sm.take(pair_order.size() * 4);
-    const size_t o_small = cv.take(sm.off);
+    const size_t hist_n = (size_t)8 * std::max(p.n_pairs, 1) * 16;
+    q.cnt = cv.piece<int>(Pz);
+    q.tcode = cv.piece<unsigned long long>(Pz * (size_t)p.nw);
+    q.hist = cv.piece<int>(hist_n);
+    p.clear_bytes = cv.off;   // ---- everything up to here is cleared; what follows is written before it is read ----
+    p.small = cv.piece<char>(p.small_bytes);
+    Carver sm{p.small};
+    const PrepSmall s = ba_layout_small(sm, Cz, p.pair_order.size());
+    q.ps = s.ps, d.pose[0] = s.pose, d.cam_free = s.cam_free, q.pair_order = s.pair_order;
     // raw input (insertion order) and the builder's temporaries
-    const size_t o_rdead = cv.take(Maz), o_ptsraw = cv.take(Pz * 24);
-    const size_t o_start = cv.take((Pz + 1) * 4), o_denseof = cv.take(Pz * 4), o_ptorig = cv.take(Pz * 4), o_arr = cv.take(Maz * 4),
-                 o_tmpi = cv.take(Mz * 4), o_tmpkey = cv.take(Mz * 4), o_ptile = cv.take(Mz * 16), o_kp = cv.take(Pz * 4),
-                 o_costp = cv.take(Pz * 4), o_entpre = cv.take((Pz + 1) * 8), o_costpre = cv.take((Pz + 1) * 8), o_ebase = cv.take(hist_n * 4);
-    ba->block_bytes = cv.off;
-    if (!ctx_cache_take(ctx->dev_cache, CTX_NCACHE(ctx->dev_cache), ba->block_bytes, &ba->block, &ba->block_cap)) {   // (a released bundle's block, if it fits)
-        HIP_TRY(hipMalloc(&ba->block, ba->block_bytes));
-        ba->block_cap = ba->block_bytes;
-    }
-    HIP_TRY(hipMemsetAsync(ba->block, 0, clear_bytes, ctx->stream));
-    char* base = (char*)ba->block;
-    d.pose[0] = (double*)(base + o_small + s_pose);   // (uploaded with the small tables)
-    d.pose[1] = (double*)(base + o_pose1);
-    (void)o_pose0;
-    d.cam_free = (int*)(base + o_small + s_camfree);
-    d.pt[0] = (double*)(base + o_pt0);
-    d.pt[1] = (double*)(base + o_pt1);
-    d.V = (double*)(base + o_V);
-    d.epsB = (double*)(base + o_epsB);
-    d.Vinv = (double*)(base + o_Vinv);
-    d.cut = ba->use_wave ? (double*)(base + o_cut) : nullptr;
-    d.rowptr = (int*)(base + o_rowptr);
-    d.m_cam = (int*)(base + o_mcam);
-    d.m_pt = (int*)(base + o_mpt);
-    d.m_found = (double2*)(base + o_mfound);
-    d.m_s = (double*)(base + o_ms);
-    d.m_orig = (int*)(base + o_morig);
-    d.m_fidx = (int*)(base + o_mfidx);
-    d.m_state = (uint8_t*)(base + o_mstate);
-    d.m_e2 = (double*)(base + o_me2);
-    d.m_e2t = (double*)(base + o_me2t);
-    d.m_zbad_t = (uint8_t*)(base + o_zbad);
-    d.W = (double*)(base + o_W);   // (slot M of every plane stays zero: the block is cleared and nobody writes it)
-    d.Usplit = (double*)(base + o_U);
-    d.Upart = (double*)(base + o_Upart);
-    d.Adet = ba->det ? (double*)(base + o_adet) : nullptr;
-    d.cam_ptr = (int*)(base + o_camptr);
-    d.cam_meas = (int*)(base + o_cammeas);
-    d.err_part = (double*)(base + o_errp);
-    d.bad_part = (int*)(base + o_badp);
-    d.chunks = (BaChunk*)(base + o_chunks);
-    d.wchunks = (BaChunk*)(base + o_wchunks);
-    d.hist = (unsigned*)(base + o_hist);
-    d.cand = (double*)(base + o_cand);
-    d.SE = (double*)(base + o_SE);
-    d.L = (double*)(base + o_L);
-    d.Dg = (double*)(base + o_Dg);
-    d.y = (double*)(base + o_y);
-    d.da = (double*)(base + o_da);
-    d.sumsq2 = (double*)(base + o_sq2);
-    d.bw_scratch = (double*)(base + o_bws);
-    d.sflags = (unsigned*)(base + o_sflags);   // (cleared with the block: sequence numbers start at 1)
-    d.sflags2 = (unsigned*)(base + o_sflags2);
-    d.SE2 = (double*)(base + o_SE2);
-    d.L2 = (double*)(base + o_L2);
-    d.Dg2 = (double*)(base + o_Dg2);
-    d.y2 = (double*)(base + o_y2);
+    p.r_dead = cv.piece<uint8_t>(Maz);
+    p.pts_raw = cv.piece<double>(Pz * 3);
+    q.start = cv.piece<int>(Pz + 1), q.dense_of = cv.piece<int>(Pz);
+    q.pt_orig = cv.piece<int>(Pz);
+    q.arr = cv.piece<int>(Maz);
+    q.tmp_i = cv.piece<int>(Mz), q.tmp_key = cv.piece<int>(Mz);
+    q.ptile = cv.piece<int4>(Mz);
+    q.kp = cv.piece<int>(Pz), q.costp = cv.piece<int>(Pz);
+    q.ent_pre = cv.piece<long long>(Pz + 1), q.cost_pre = cv.piece<long long>(Pz + 1);
+    q.ebase = cv.piece<int>(hist_n);
+}
+
+// layout, allocation, clear — and what a fresh block's owner is told once: its XCD, its spin limit, the tile kernel's index maps
+static int ba_prep_main_block(ptam_ba* ba, Prep& p) {
+    ptam_ctx* ctx = ba->ctx;
+    BaDev& d = ba->d;
+    Carver small_size, size;
+    ba_layout_small(small_size, std::max(p.C, 1), p.pair_order.size());
+    p.small_bytes = small_size.off;
+    BaDev sized = d;   // (the sizing run's pointers mean nothing: they go to a copy, and a failed take leaves the bundle without any)
+    ba_layout_main(size, ba, sized, p);
+    ba->block_bytes = size.off;
+    if (int rc = ctx_block_take(ctx, CTX_MEM_DEVICE, ba->block_bytes, &ba->block, &ba->block_cap)) return rc;   // (a released bundle's block, if it fits)
+    HIP_TRY(hipMemsetAsync(ba->block, 0, p.clear_bytes, ctx->stream));
+    Carver cv{(char*)ba->block};
+    ba_layout_main(cv, ba, d, p);
+    ba->d_xchg = p.xchg, ba->d_pt_orig = p.q.pt_orig;
     d.solve_seq = 0;
     d.chain_off = 0;
     {
@@ -637,245 +690,216 @@ static int ba_prepare_impl(ptam_ba* ba) {
         }();
         d.spin_limit = lim;
     }
-    d.outliers = (int*)(base + o_out);
-    d.sc = (BaScalars*)(base + o_sc);
-    d.dbg = (long long*)(base + o_dbg);
-    ba->d_xchg = (double*)(base + o_xchg);
     if (!ctx->d_smap) {   // the tile kernel's index maps: a constant of the build, one device copy per context
         static const std::vector<unsigned> s_map = schur_index_map_device();
         HIP_TRY(hipMalloc((void**)&ctx->d_smap, s_map.size() * 4));
         HIP_TRY(hipMemcpy(ctx->d_smap, s_map.data(), s_map.size() * 4, hipMemcpyHostToDevice));
     }
     d.s_map = ctx->d_smap;
-    lap("alloc + clear");
+    return PTAM_OK;
+}
 
-    // ---- pinned staging: [stamp | scalars read back | rowptr | dense point ids | small tables | chunks] -------------------------
-    Carver hs;
-    const size_t h_stamp = hs.take(64), h_psrb = hs.take(sizeof(PrepScalars)), h_rowptr = hs.take((Pz + 1) * 4), h_ptorig = hs.take(Pz * 4),
-                 h_small = hs.take(sm.off), h_chunks = hs.take(chunks_cap * sizeof(BaChunk)), h_dead = hs.take(ba->n_dead > 0 ? Maz : 1);
-    (void)h_stamp;
+// ---- the pinned staging, the small tables, the uploads -------------------------------------------------------------------------
+static int ba_prep_upload(ptam_ba* ba, Prep& p) {
+    ptam_ctx* ctx = ba->ctx;
+    Carver size;
+    ba_layout_stage(size, p);
+    // (also what Compute()'s read-back will need: growing the staging later would re-map host memory under queued kernels)
+    p.staging_bytes = std::max(size.off, ba_readback_bytes(p.C, p.P_all, p.M));
     void* pin = nullptr;
-    {
-        // (also what Compute()'s read-back will need: growing the staging later would re-map host memory under queued kernels)
-        const size_t later = 64 + (size_t)C * 96 + (size_t)P_all * 24 + (size_t)M * 4 + 64;
-        const int rc_p = ctx_pinned(ctx, std::max(hs.off, later), &pin);
-        if (rc_p) return rc_p;
-    }
-    char* hp = (char*)pin;
-    char* dp = (char*)ctx->d_pinned;
-    volatile unsigned long long* stamp = (volatile unsigned long long*)hp;
-    PrepScalars* ps_host = (PrepScalars*)(hp + h_psrb);
-    {
-        PrepScalars init;
-        std::memset(&init, 0, sizeof init);
-        init.dup_key = ~0ull;
-        std::memcpy(hp + h_small + s_ps, &init, sizeof init);
-        std::memcpy(hp + h_small + s_pose, ba->cam_pose.data(), (size_t)C * 96);
-        std::memcpy(hp + h_small + s_camfree, cam_free.data(), (size_t)C * 4);
-        std::memcpy(hp + h_small + s_porder, pair_order.data(), pair_order.size() * 4);
-    }
-#define UP(dst, src, bytes)                                                                        \
-    if ((bytes) > 0) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream))
-    UP(base + o_small, hp + h_small, sm.off);
-    if (int rc_f = ba->ms.flush(true)) return rc_f;   // (the complete chunks went up while they were added: only the last one is left)
-    if (ba->n_dead > 0) {
-        std::memcpy(hp + h_dead, ba->m_dead.data(), (size_t)Mall);
-        UP(base + o_rdead, hp + h_dead, (size_t)Mall);
+    if (int rc = ctx_pinned(ctx, p.staging_bytes, &pin)) return rc;
+    Carver hs{(char*)pin}, ds{(char*)ctx->d_pinned}, sm;
+    p.h = ba_layout_stage(hs, p);
+    p.hd = ba_layout_stage(ds, p);
+    sm.base = p.h.small;
+    const PrepSmall s = ba_layout_small(sm, std::max(p.C, 1), p.pair_order.size());
+    PrepScalars init;
+    std::memset(&init, 0, sizeof init);
+    init.dup_key = ~0ull;
+    std::memcpy(s.ps, &init, sizeof init);
+    std::memcpy(s.pose, ba->cam_pose.data(), (size_t)p.C * 96);
+    std::memcpy(s.cam_free, p.cam_free.data(), (size_t)p.C * 4);
+    std::memcpy(s.pair_order, p.pair_order.data(), p.pair_order.size() * 4);
+    if (int rc = ba_upload(ctx, p.small, p.h.small, p.small_bytes)) return rc;
+    if (int rc = ba->ms.flush(true)) return rc;   // (the complete chunks went up while they were added: only the last one is left)
+    if (p.n_dead > 0) {
+        std::memcpy(p.h.dead, ba->m_dead.data(), (size_t)p.Mall);
+        if (int rc = ba_upload(ctx, p.r_dead, p.h.dead, (size_t)p.Mall)) return rc;
     }
     if (ba->pts_dev) {
-        if (P_all > 0) HIP_TRY(hipMemcpyAsync(base + o_ptsraw, ba->pts_dev, (size_t)P_all * 24, hipMemcpyDeviceToDevice, ctx->stream));
-    } else
-        UP(base + o_ptsraw, ba->pts.data(), (size_t)P_all * 24);
-    PrepDev q;
-    std::memset(&q, 0, sizeof q);
-    q.C = C, q.F = F, q.P_all = P_all, q.Mall = Mall, q.M = M;
-    q.n_tiles = n_tiles, q.n_pairs = n_pairs, q.nw = nw;
+        if (p.P_all > 0) HIP_TRY(hipMemcpyAsync(p.pts_raw, ba->pts_dev, (size_t)p.P_all * 24, hipMemcpyDeviceToDevice, ctx->stream));
+    } else if (int rc = ba_upload(ctx, p.pts_raw, ba->pts.data(), (size_t)p.P_all * 24))
+        return rc;
+    PrepDev& q = p.q;
+    q.C = p.C, q.F = p.F, q.P_all = p.P_all, q.Mall = p.Mall, q.M = p.M;
+    q.n_tiles = p.n_tiles, q.n_pairs = p.n_pairs, q.nw = p.nw;
     q.r_base = ba->ms.d;
-    q.r_dead = ba->n_dead > 0 ? (const uint8_t*)(base + o_rdead) : nullptr;
-    q.pts_raw = (const double*)(base + o_ptsraw);
-    q.cnt = (int*)(base + o_cnt);
-    q.start = (int*)(base + o_start);
-    q.dense_of = (int*)(base + o_denseof);
-    q.pt_orig = (int*)(base + o_ptorig);
-    ba->d_pt_orig = q.pt_orig;
-    q.arr = (int*)(base + o_arr);
-    q.tmp_i = (int*)(base + o_tmpi);
-    q.tmp_key = (int*)(base + o_tmpkey);
-    q.ptile = (int4*)(base + o_ptile);
-    q.tcode = (unsigned long long*)(base + o_tcode);
-    q.kp = (int*)(base + o_kp);
-    q.costp = (int*)(base + o_costp);
-    q.ent_pre = (long long*)(base + o_entpre);
-    q.cost_pre = (long long*)(base + o_costpre);
-    q.hist = (int*)(base + o_phist);
-    q.ebase = (int*)(base + o_ebase);
-    q.pair_order = (const int*)(base + o_small + s_porder);
-    q.ps = (PrepScalars*)(base + o_small + s_ps);
-    q.h_ps = (PrepScalars*)(dp + h_psrb);
-    q.h_rowptr = (int*)(dp + h_rowptr);
-    q.h_pt_orig = (int*)(dp + h_ptorig);
-    // ---- phase 1: point-major sort, rowptr, per-point tiles, XCD ranges, pattern counts ------------------------------------------
-    if (Mall > 0) hipLaunchKernelGGL(prep_count_kernel, dim3((Mall + 255) / 256), dim3(256), 0, ctx->stream, q);
-    hipLaunchKernelGGL(prep_scan_points_kernel, dim3(1), dim3(1024), 0, ctx->stream, q, d);
-    if (M > 0) {
-        hipLaunchKernelGGL(prep_scatter_kernel, dim3((Mall + 255) / 256), dim3(256), 0, ctx->stream, q, (const int*)d.cam_free);
-        hipLaunchKernelGGL(prep_rank_kernel, dim3((M + 255) / 256), dim3(256), 0, ctx->stream, q, d);
-    }
-    if (lists) {
-        hipLaunchKernelGGL(prep_tiles_kernel, dim3((P_all + 63) / 64), dim3(64), 0, ctx->stream, q, d, cfg.cost_model);
-        hipLaunchKernelGGL(prep_scan_cost_kernel, dim3(1), dim3(1024), 0, ctx->stream, q, cfg.min_seg, cfg.slots);
-        hipLaunchKernelGGL(prep_hist_kernel, dim3(n_pairs, 8), dim3(256), 0, ctx->stream, q);
-    }
-    unsigned long long seq = ++ctx->pose_seq;
-    *stamp = 0;
-    hipLaunchKernelGGL(prep_publish_kernel, dim3(1), dim3(64), 0, ctx->stream, q, (volatile unsigned long long*)dp, seq);
+    q.r_dead = p.n_dead > 0 ? p.r_dead : nullptr;
+    q.pts_raw = p.pts_raw;
+    q.h_ps = p.hd.ps, q.h_rowptr = p.hd.rowptr, q.h_pt_orig = p.hd.pt_orig;
+    return PTAM_OK;
+}
+
+// the end of a phase: the device publishes its scalars and lists into the staging and stamps it; the host waits for the stamp
+static int ba_prep_publish_wait(ptam_ba* ba, Prep& p, const char* lap_enqueued, const char* lap_wait, const char* what) {
+    ptam_ctx* ctx = ba->ctx;
+    const unsigned long long seq = ++ctx->pose_seq;
+    *p.h.stamp = 0;
+    hipLaunchKernelGGL(prep_publish_kernel, dim3(1), dim3(64), 0, ctx->stream, p.q, p.hd.stamp, seq);
     HIP_TRY(hipGetLastError());
-    lap("phase 1 enqueued");
-    if (int rc = ba_wait_stamp(ctx, stamp, seq, "the first phase of the bundle's prepare")) return rc;
-    lap("phase 1 wait");
-    PrepScalars ps = *ps_host;
+    p.lap(lap_enqueued);
+    if (int rc = ba_wait_stamp(ctx, p.h.stamp, seq, what)) return rc;
+    p.lap(lap_wait);
+    return PTAM_OK;
+}
+
+// ---- phase 1: point-major sort, rowptr, per-point tiles, XCD ranges, pattern counts ----------------------------------------------
+static int ba_prep_phase1(ptam_ba* ba, Prep& p, PrepScalars& ps) {
+    ptam_ctx* ctx = ba->ctx;
+    BaDev& d = ba->d;
+    const PrepDev& q = p.q;
+    if (p.Mall > 0) hipLaunchKernelGGL(prep_count_kernel, dim3((p.Mall + 255) / 256), dim3(256), 0, ctx->stream, q);
+    hipLaunchKernelGGL(prep_scan_points_kernel, dim3(1), dim3(1024), 0, ctx->stream, q, d);
+    if (p.M > 0) {
+        hipLaunchKernelGGL(prep_scatter_kernel, dim3((p.Mall + 255) / 256), dim3(256), 0, ctx->stream, q, (const int*)d.cam_free);
+        hipLaunchKernelGGL(prep_rank_kernel, dim3((p.M + 255) / 256), dim3(256), 0, ctx->stream, q, d);
+    }
+    if (p.lists) {
+        hipLaunchKernelGGL(prep_tiles_kernel, dim3((p.P_all + 63) / 64), dim3(64), 0, ctx->stream, q, d, p.cfg.cost_model);
+        hipLaunchKernelGGL(prep_scan_cost_kernel, dim3(1), dim3(1024), 0, ctx->stream, q, p.cfg.min_seg, p.cfg.slots);
+        hipLaunchKernelGGL(prep_hist_kernel, dim3(p.n_pairs, 8), dim3(256), 0, ctx->stream, q);
+    }
+    if (int rc = ba_prep_publish_wait(ba, p, "phase 1 enqueued", "phase 1 wait", "the first phase of the bundle's prepare")) return rc;
+    ps = *p.h.ps;
     ba->dups_refused = ps.dup;
     if (ps.dup > 0) {
         ptam_set_error("duplicate measurement of point %d by camera %d", (int)(ps.dup_key >> 32), (int)(ps.dup_key & 0xffffffffu));
         return PTAM_E_ARG;
     }
-    if (ps.M != M || ps.P > P_all || ps.n_entries >= (1ll << 31)) {
-        ptam_set_error("bundle prepare: inconsistent counts (live measurements %d / %d, points %d / %d, Schur entries %lld)", ps.M, M, ps.P,
-                       P_all, ps.n_entries);
+    if (ps.M != p.M || ps.P > p.P_all || ps.n_entries >= (1ll << 31)) {
+        ptam_set_error("bundle prepare: inconsistent counts (live measurements %d / %d, points %d / %d, Schur entries %lld)", ps.M, p.M, ps.P,
+                       p.P_all, ps.n_entries);
         return PTAM_E_STATE;
     }
-    const int P = ps.P;
-    d.P = P;
+    d.P = ps.P;
     d.band = ba->band_local = ps.band;
-    const int* rowptr = (const int*)(hp + h_rowptr);
-    ba->pt_orig.assign((const int*)(hp + h_ptorig), (const int*)(hp + h_ptorig) + P);
-    // chunks: consecutive whole points, at most BA_CHUNK measurements — or ONE point with more than that (a point seen by
-    // more than 256 keyframes: the kernels that own whole points walk such a chunk BA_CHUNK measurements at a time;
-    // src/Bundle.cc:75-93 puts no bound on the measurements of a point).  (The one walk over the points the host keeps: a chunk
-    // begins where the previous one ends.)
-    BaChunk* chunks = (BaChunk*)(hp + h_chunks);
+    ba->pt_orig.assign(p.h.pt_orig, p.h.pt_orig + ps.P);
+    return PTAM_OK;
+}
+
+// ---- the chunk walk --------------------------------------------------------------------------------------------------------------
+// chunks: consecutive whole points, at most BA_CHUNK measurements — or ONE point with more than that (a point seen by
+// more than 256 keyframes: the kernels that own whole points walk such a chunk BA_CHUNK measurements at a time;
+// src/Bundle.cc:75-93 puts no bound on the measurements of a point).  (The one walk over the points the host keeps: a chunk
+// begins where the previous one ends.)
+static int ba_prep_chunks(ptam_ba* ba, Prep& p) {
+    BaDev& d = ba->d;
+    const int P = d.P;
+    const int* rowptr = p.h.rowptr;
+    BaChunk* chunks = p.h.chunks;
     size_t n_chunks = 0;
-    {
-        int p = 0;
-        while (p < P) {
-            BaChunk ch;
-            ch.pt_begin = p;
-            ch.m_begin = rowptr[p];
-            int cnt = 0, np = 0;
-            while (p < P && cnt + (rowptr[p + 1] - rowptr[p]) <= BA_CHUNK && np < BA_CHUNK) {
-                cnt += rowptr[p + 1] - rowptr[p];
-                p++;
-                np++;
-            }
-            if (np == 0) p++;   // a long point, alone in its chunk
-            ch.pt_end = p;
-            ch.m_end = rowptr[p];
-            if (n_chunks >= chunks_cap) {
-                ptam_set_error("bundle prepare: more chunks than their bound (%zu)", chunks_cap);
-                return PTAM_E_STATE;
-            }
-            chunks[n_chunks++] = ch;
+    for (int pt = 0; pt < P;) {
+        BaChunk ch;
+        ch.pt_begin = pt;
+        ch.m_begin = rowptr[pt];
+        int cnt = 0, np = 0;
+        while (pt < P && cnt + (rowptr[pt + 1] - rowptr[pt]) <= BA_CHUNK && np < BA_CHUNK) {
+            cnt += rowptr[pt + 1] - rowptr[pt];
+            pt++;
+            np++;
         }
+        if (np == 0) pt++;   // a long point, alone in its chunk
+        ch.pt_end = pt;
+        ch.m_end = rowptr[pt];
+        if (n_chunks >= p.chunks_cap) {
+            ptam_set_error("bundle prepare: more chunks than their bound (%zu)", p.chunks_cap);
+            return PTAM_E_STATE;
+        }
+        chunks[n_chunks++] = ch;
     }
     d.n_chunks = (int)n_chunks;
     // K7's wave variant walks the point-major list 64 measurements at a time whatever the points' lengths: a point cut by a
     // chunk edge — or covering whole chunks, when more than 64 cameras measure it — leaves one piece per chunk, which K8a adds in
     // chunk order.  (Rounds 1-2 also had a block variant whose workgroups owned whole points: removed in round 3.)
-    UP(d.chunks, chunks, n_chunks * sizeof(BaChunk));
-    lap("chunks");
-    // ---- phase 2: the Schur work lists ----------------------------------------------------------------------------------------
+    return ba_upload(ba->ctx, d.chunks, chunks, n_chunks * sizeof(BaChunk));
+}
+
+// ---- phase 2: the Schur work lists -----------------------------------------------------------------------------------------------
+// The Schur block, sized after the device has counted the entries, in its two forms: the work lists and the split's temporaries
+// (the first *clear bytes are cleared), or — free cameras but no entry — what the reduction still reads: the pairs' (empty) slot
+// ranges (all of it cleared).
+static void ba_layout_schur(Carver& sv, BaDev& d, Prep& p, const PrepScalars& ps, size_t* clear) {
+    PrepDev& q = p.q;
+    const size_t n_pairs = (size_t)p.n_pairs;
+    if (!(p.lists && ps.n_entries > 0)) {
+        d.s_pair_wg_begin = sv.piece<int>(n_pairs + 1);
+        d.s_part = sv.piece<double>(SCHUR_TILE_ELEMS);
+        char* one = sv.piece<char>(256);
+        d.s_entries = (SchurEntry*)one, d.s_segs = (SchurWG*)one;
+        d.s_wg_seg = d.s_wg_head = (int*)one;
+        *clear = sv.off;
+        return;
+    }
+    const SplitCfg& cfg = p.cfg;
+    const int cap_pl = std::max(1, std::min(p.n_pairs, ps.n_xp));
+    const int cap_cut = cfg.slots + cap_pl;
+    const size_t cap_segs = (size_t)8 * cfg.slots + (size_t)ps.n_xp;
+    const size_t nb_max = (size_t)8 * cfg.slots;
+    q.cap_pl = cap_pl, q.cap_cut = cap_cut;
+    d.s_entries = sv.piece<SchurEntry>((size_t)ps.n_entries);
+    d.s_segs = sv.piece<SchurWG>(cap_segs);
+    d.s_wg_seg = sv.piece<int>(nb_max + 1);
+    d.s_pair_wg_begin = sv.piece<int>(n_pairs + 1);
+    d.s_wg_head = sv.piece<int>(nb_max * 8);
+    d.s_part = sv.piece<double>(cap_segs * SCHUR_TILE_ELEMS);
+    q.cpx = sv.piece<int>(n_pairs * 8 + 1);
+    *clear = sv.off;
+    q.run_cnt = sv.piece<int>((size_t)8 * 16 * cap_pl), q.run_cost = sv.piece<int>((size_t)8 * 16 * cap_pl);
+    q.pl_pair = sv.piece<int>((size_t)8 * cap_pl), q.pl_n = sv.piece<int>((size_t)8 * cap_pl);
+    q.pl_run0 = sv.piece<int>((size_t)8 * (cap_pl + 1));
+    q.pl_e0 = sv.piece<int>((size_t)8 * cap_pl);
+    q.pl_e = sv.piece<int>((size_t)8 * (cap_pl + 1));
+    q.pl_h = sv.piece<long long>((size_t)8 * (cap_pl + 1));
+    q.cut_pair = sv.piece<int>((size_t)8 * cap_cut), q.cut_e0 = sv.piece<int>((size_t)8 * cap_cut);
+    q.cut_e1 = sv.piece<int>((size_t)8 * cap_cut), q.cut_wg = sv.piece<int>((size_t)8 * cap_cut);
+    q.wg_first = sv.piece<int>((size_t)8 * (cfg.slots + 1));
+    q.pair_first = sv.piece<int>(n_pairs * 8);
+    q.wseg_tmp = sv.piece<int>(nb_max + 1);
+    // every lane of the budget search keeps the cut its budget makes, unless that would be more than 64 MB
+    const size_t n_rec = (size_t)8 * 512 * cap_cut;
+    const bool with_rec = cfg.greedy && n_rec * sizeof(int4) <= ((size_t)64 << 20);   // (the greedy form's lanes only)
+    q.rec = with_rec ? sv.piece<int4>(n_rec) : nullptr;
+}
+
+static int ba_prep_phase2(ptam_ba* ba, Prep& p, PrepScalars& ps) {
+    ptam_ctx* ctx = ba->ctx;
+    BaDev& d = ba->d;
+    PrepDev& q = p.q;
     d.n_schur_entries = (int)ps.n_entries;
     d.n_schur_wg = 0;
-    if (lists && ps.n_entries > 0) {
-        const int cap_pl = std::max(1, std::min(n_pairs, ps.n_xp));
-        const int cap_cut = cfg.slots + cap_pl;
-        const size_t cap_segs = (size_t)8 * cfg.slots + (size_t)ps.n_xp;
-        const int nb_max = 8 * cfg.slots;
-        Carver sv;
-        const size_t o_sent = sv.take((size_t)ps.n_entries * sizeof(SchurEntry)), o_swg = sv.take(cap_segs * sizeof(SchurWG)),
-                     o_swgseg = sv.take(((size_t)nb_max + 1) * 4), o_spw = sv.take((size_t)(n_pairs + 1) * 4),
-                     o_swghead = sv.take((size_t)nb_max * 32), o_spart = sv.take(cap_segs * SCHUR_TILE_ELEMS * 8),
-                     o_cpx = sv.take(((size_t)n_pairs * 8 + 1) * 4);
-        const size_t sclear = sv.off;
-        const size_t o_runcnt = sv.take((size_t)8 * 16 * cap_pl * 4), o_runcost = sv.take((size_t)8 * 16 * cap_pl * 4),
-                     o_plpair = sv.take((size_t)8 * cap_pl * 4), o_pln = sv.take((size_t)8 * cap_pl * 4),
-                     o_plrun0 = sv.take((size_t)8 * (cap_pl + 1) * 4), o_ple0 = sv.take((size_t)8 * cap_pl * 4),
-                     o_ple = sv.take((size_t)8 * (cap_pl + 1) * 4), o_plh = sv.take((size_t)8 * (cap_pl + 1) * 8),
-                     o_cutpair = sv.take((size_t)8 * cap_cut * 4), o_cute0 = sv.take((size_t)8 * cap_cut * 4),
-                     o_cute1 = sv.take((size_t)8 * cap_cut * 4), o_cutwg = sv.take((size_t)8 * cap_cut * 4),
-                     o_wgfirst = sv.take((size_t)8 * (cfg.slots + 1) * 4), o_pairfirst = sv.take((size_t)n_pairs * 8 * 4),
-                     o_wsegtmp = sv.take(((size_t)nb_max + 1) * 4);
-        // every lane of the budget search keeps the cut its budget makes, unless that would be more than 64 MB
-        const size_t rec_bytes = (size_t)8 * 512 * cap_cut * sizeof(int4);
-        const bool with_rec = cfg.greedy && rec_bytes <= ((size_t)64 << 20);   // (the greedy form's lanes only)
-        const size_t o_rec = with_rec ? sv.take(rec_bytes) : 0;
-        ba->sblock_bytes = sv.off;
-        if (!ctx_cache_take(ctx->dev_cache, CTX_NCACHE(ctx->dev_cache), ba->sblock_bytes, &ba->sblock, &ba->sblock_cap)) {
-            HIP_TRY(hipMalloc(&ba->sblock, ba->sblock_bytes));
-            ba->sblock_cap = ba->sblock_bytes;
-        }
+    if (p.F > 0) {
+        size_t sclear = 0;
+        Carver size;
+        BaDev sized = d;
+        ba_layout_schur(size, sized, p, ps, &sclear);
+        ba->sblock_bytes = size.off;
+        if (int rc = ctx_block_take(ctx, CTX_MEM_DEVICE, ba->sblock_bytes, &ba->sblock, &ba->sblock_cap)) return rc;
         HIP_TRY(hipMemsetAsync(ba->sblock, 0, sclear, ctx->stream));
-        char* sb = (char*)ba->sblock;
-        d.s_entries = (SchurEntry*)(sb + o_sent);
-        d.s_segs = (SchurWG*)(sb + o_swg);
-        d.s_wg_seg = (int*)(sb + o_swgseg);
-        d.s_pair_wg_begin = (int*)(sb + o_spw);
-        d.s_wg_head = (int*)(sb + o_swghead);
-        d.s_part = (double*)(sb + o_spart);
-        q.cap_pl = cap_pl, q.cap_cut = cap_cut;
-        q.cpx = (int*)(sb + o_cpx);
-        q.run_cnt = (int*)(sb + o_runcnt);
-        q.run_cost = (int*)(sb + o_runcost);
-        q.pl_pair = (int*)(sb + o_plpair);
-        q.pl_n = (int*)(sb + o_pln);
-        q.pl_run0 = (int*)(sb + o_plrun0);
-        q.pl_e0 = (int*)(sb + o_ple0);
-        q.pl_e = (int*)(sb + o_ple);
-        q.pl_h = (long long*)(sb + o_plh);
-        q.cut_pair = (int*)(sb + o_cutpair);
-        q.cut_e0 = (int*)(sb + o_cute0);
-        q.cut_e1 = (int*)(sb + o_cute1);
-        q.cut_wg = (int*)(sb + o_cutwg);
-        q.wg_first = (int*)(sb + o_wgfirst);
-        q.pair_first = (int*)(sb + o_pairfirst);
-        q.wseg_tmp = (int*)(sb + o_wsegtmp);
-        q.rec = with_rec ? (int4*)(sb + o_rec) : nullptr;
-        hipLaunchKernelGGL(prep_split_kernel, dim3(8), dim3(512), 0, ctx->stream, q, cfg);
-        hipLaunchKernelGGL(prep_entries_kernel, dim3(n_pairs, 8), dim3(256), 0, ctx->stream, q, d, cfg.cost_model);
-        hipLaunchKernelGGL(prep_finish_kernel, dim3(1), dim3(1024), 0, ctx->stream, q, d, cfg.slots);
-    } else if (F > 0) {
-        // free cameras but no entry: the reduction still reads the pairs' (empty) slot ranges
-        Carver sv;
-        const size_t o_spw = sv.take((size_t)(n_pairs + 1) * 4), o_spart = sv.take(SCHUR_TILE_ELEMS * 8), o_one = sv.take(256);
-        ba->sblock_bytes = sv.off;
-        if (!ctx_cache_take(ctx->dev_cache, CTX_NCACHE(ctx->dev_cache), ba->sblock_bytes, &ba->sblock, &ba->sblock_cap)) {
-            HIP_TRY(hipMalloc(&ba->sblock, ba->sblock_bytes));
-            ba->sblock_cap = ba->sblock_bytes;
-        }
-        HIP_TRY(hipMemsetAsync(ba->sblock, 0, ba->sblock_bytes, ctx->stream));
-        char* sb = (char*)ba->sblock;
-        d.s_pair_wg_begin = (int*)(sb + o_spw);
-        d.s_part = (double*)(sb + o_spart);
-        d.s_entries = (SchurEntry*)(sb + o_one);
-        d.s_segs = (SchurWG*)(sb + o_one);
-        d.s_wg_seg = (int*)(sb + o_one);
-        d.s_wg_head = (int*)(sb + o_one);
+        Carver sv{(char*)ba->sblock};
+        ba_layout_schur(sv, d, p, ps, &sclear);
     }
-    if (ba->det) {
-        int* tile_free = (int*)(base + o_tilefree);
-        hipLaunchKernelGGL(prep_det_count_kernel, dim3(n_dtiles), dim3(256), 0, ctx->stream, d, tile_free);
-        hipLaunchKernelGGL(prep_det_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tile_free, n_dtiles);
-        hipLaunchKernelGGL(prep_det_lists_kernel, dim3(n_dtiles), dim3(256), 0, ctx->stream, d, (const int*)tile_free);
+    if (p.lists && ps.n_entries > 0) {
+        hipLaunchKernelGGL(prep_split_kernel, dim3(8), dim3(512), 0, ctx->stream, q, p.cfg);
+        hipLaunchKernelGGL(prep_entries_kernel, dim3(p.n_pairs, 8), dim3(256), 0, ctx->stream, q, d, p.cfg.cost_model);
+        hipLaunchKernelGGL(prep_finish_kernel, dim3(1), dim3(1024), 0, ctx->stream, q, d, p.cfg.slots);
     }
-#undef UP
-    seq = ++ctx->pose_seq;
-    *stamp = 0;
-    hipLaunchKernelGGL(prep_publish_kernel, dim3(1), dim3(64), 0, ctx->stream, q, (volatile unsigned long long*)dp, seq);
-    HIP_TRY(hipGetLastError());
-    lap("phase 2 enqueued");
-    if (int rc = ba_wait_stamp(ctx, stamp, seq, "the second phase of the bundle's prepare")) return rc;
-    lap("phase 2 wait");
-    ps = *ps_host;
+    if (ba->k7.det) {
+        hipLaunchKernelGGL(prep_det_count_kernel, dim3(p.n_dtiles), dim3(256), 0, ctx->stream, d, p.tile_free);
+        hipLaunchKernelGGL(prep_det_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, p.tile_free, p.n_dtiles);
+        hipLaunchKernelGGL(prep_det_lists_kernel, dim3(p.n_dtiles), dim3(256), 0, ctx->stream, d, (const int*)p.tile_free);
+    }
+    if (int rc = ba_prep_publish_wait(ba, p, "phase 2 enqueued", "phase 2 wait", "the second phase of the bundle's prepare")) return rc;
+    ps = *p.h.ps;
     if (ps.bad) {
         ptam_set_error("bundle prepare: a Schur work list outgrew its bound (%d; workgroups per list %d %d %d %d %d %d %d %d, budgets %lld %lld, segments %d %d)", ps.bad,
                        ps.n_wgs[0], ps.n_wgs[1], ps.n_wgs[2], ps.n_wgs[3], ps.n_wgs[4], ps.n_wgs[5], ps.n_wgs[6], ps.n_wgs[7], ps.t_cut[0], ps.t_cut[1],
@@ -884,27 +908,56 @@ static int ba_prepare_impl(ptam_ba* ba) {
     }
     d.n_schur_wg = ps.n_schur_wg;
     ba->n_schur_segs = ps.n_segs;
-#ifdef PREP_STAMPS
-    for (int x = 0; x < 8; x++) {
-        std::fprintf(stderr, "[ptam] split kernel, list %d (us from its start): lists built %.1f | in LDS %.1f | round 1 done %.1f | search done %.1f | cut written %.1f\n", x,
-                     (ps.stamp[x][1] - ps.stamp[x][0]) * 0.01, (ps.stamp[x][2] - ps.stamp[x][0]) * 0.01, (ps.stamp[x][3] - ps.stamp[x][0]) * 0.01,
-                     (ps.stamp[x][4] - ps.stamp[x][0]) * 0.01, (ps.stamp[x][5] - ps.stamp[x][0]) * 0.01);
-        std::fprintf(stderr, "[ptam]    the search: %lld shader cycles in %.1f us = %.2f GHz\n", ps.stamp[x][7] - ps.stamp[x][6], (ps.stamp[x][4] - ps.stamp[x][2]) * 0.01,
-                     (double)(ps.stamp[x][7] - ps.stamp[x][6]) / ((ps.stamp[x][4] - ps.stamp[x][2]) * 10.0));
-    }
-#endif
-    if (getenv("PTAM_DEBUG_SCHUR")) {
-        std::fprintf(stderr, "[ptam] schur: %d segments, %d workgroups; %lld entries in %d (XCD, pair) lists, budgets", ps.n_segs, ps.n_schur_wg,
-                     ps.n_entries, ps.n_xp);
-        for (int x = 0; x < 8; x++) std::fprintf(stderr, " %lld", ps.t_cut[x]);
-        std::fprintf(stderr, "; workgroups per XCD");
-        for (int x = 0; x < 8; x++) std::fprintf(stderr, " %d", ps.n_wgs[x]);
-        std::fprintf(stderr, "\n");
-    }
-    {
-        const int rc_s = ba_solve_init();
-        if (rc_s) return rc_s;
-    }
+    return PTAM_OK;
+}
+
+static int ba_prepare_impl(ptam_ba* ba) {
+    ptam_ctx* ctx = ba->ctx;
+    Prep p;   // (its laps, PTAM_DEBUG_PREPARE=1, start here)
+    ba_finish_outliers(ba);   // erased measurements of earlier Compute() calls leave the problem here
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ptam_stream_wait(ctx->stream));
+    ba_free_device(ba);
+    BaDev& d = ba->d;
+    std::memset(&d, 0, sizeof d);
+    p.C = (int)ba->cam_fixed.size(), p.P_all = (int)(ba->pts.size() / 3);
+    p.Mall = (int)ba->ms.size();
+    p.n_dead = ba->n_dead;
+    p.M = p.Mall - ba->n_dead;
+    // free-camera indices in insertion order  (nStartRow, src/Bundle.cc:52-57)
+    p.cam_free.assign(p.C, -1);
+    for (int c = 0; c < p.C; c++)
+        if (!ba->cam_fixed[c]) p.cam_free[c] = p.F++;
+    p.n_tiles = (p.F + SCHUR_TC - 1) / SCHUR_TC;
+    p.n_pairs = p.n_tiles * (p.n_tiles + 1) / 2;
+    p.nw = std::max(1, (p.n_tiles + 31) / 32);
+    p.n_dtiles = (p.M + DET_TILE - 1) / DET_TILE;
+    p.lists = p.F > 0 && p.M > 0;
+    // chunks: consecutive whole points, at most BA_CHUNK measurements — two neighbours together exceed BA_CHUNK measurements or
+    // BA_CHUNK points, or one of them is a long point
+    p.chunks_cap = std::min<size_t>(std::max(p.P_all, 1), (size_t)p.M / 64 + (size_t)p.P_all / 128 + 8);
+    d.C = p.C, d.F = p.F, d.M = p.M;
+    d.n = 6 * p.F;
+    d.npad = ((d.n + SOLVE_NB - 1) / SOLVE_NB) * SOLVE_NB;
+    d.n_wchunks = p.M > 0 ? 1 : 0;
+    ba->use_wave = p.M > 0;   // (false: no live measurement at all — K7 is then a memset of its outputs)
+    d.n_tiles = p.n_tiles, d.n_pairs = p.n_pairs;
+    ba_prep_split_config(p);
+    if (int rc = ba_k7_shape(ba, p, &ba->k7)) return rc;
+    d.grid_acc = ba->k7.grid, d.u_rows = ba->k7.u_rows;
+    p.lap("launch shape");
+    if (int rc = ba_prep_main_block(ba, p)) return rc;
+    p.lap("alloc + clear");
+    if (int rc = ba_prep_upload(ba, p)) return rc;
+    PrepScalars ps;
+    if (int rc = ba_prep_phase1(ba, p, ps)) return rc;
+    if (int rc = ba_prep_chunks(ba, p)) return rc;
+    p.lap("chunks");
+    if (int rc = ba_prep_phase2(ba, p, ps)) return rc;
+    ba_dbg_prep_stamps(ps);
+    ba_dbg_schur_lists(ps);
+    ba_dbg_prepare_sizes(ba, p.clear_bytes, p.staging_bytes);
+    if (int rc = ba_solve_init()) return rc;
     ba->cur = 0;
     ba->prepared = true;
     return PTAM_OK;
@@ -1060,7 +1113,7 @@ static void launch_k7(ptam_ba* ba, int guard = 0) {
     d.guard = guard;
     d.guard_seq = (int)ba->mbox_seq;   // (the trial just enqueued)
     int cur = guard ? (ba->cur ^ 1) : ba->cur;   // a guarded launch belongs to the next step: the trial state is current there
-    if ((ba->k7_big && !ba->det) || !ba->use_wave)   // the one row of camera partials every wave adds to (or, without measurements, all there is)
+    if ((ba->k7.big && !ba->k7.det) || !ba->use_wave)   // the one row of camera partials every wave adds to (or, without measurements, all there is)
         (void)hipMemsetAsync(d.Upart, 0, std::max<size_t>(1, (size_t)d.F * 27) * sizeof(double), ctx->stream);
     if (!ba->use_wave) {   // no live measurement: zero error, zero bad count
         (void)hipMemsetAsync(d.err_part, 0, 16, ctx->stream);
@@ -1068,10 +1121,10 @@ static void launch_k7(ptam_ba* ba, int guard = 0) {
         return;
     }
     int est = ba->opts.estimator;
-    void* args[] = {&ctx->cam, &d, &cur, &est, &ba->per_wave, &ba->extra_waves};
-    (void)hipLaunchKernel(k7_wave_fn(ba->k7_threads, ba->k7_loop, est, ba->k7_big, ba->det), dim3(d.grid_acc), dim3(ba->k7_threads), args,
-                          ba->smem_acc, ctx->stream);
-    if (ba->det && d.F > 0)
+    void* args[] = {&ctx->cam, &d, &cur, &est, &ba->k7.per_wave, &ba->k7.extra_waves};
+    (void)hipLaunchKernel(k7_wave_fn(ba->k7.threads, ba->k7.loop, est, ba->k7.big, ba->k7.det), dim3(d.grid_acc), dim3(ba->k7.threads), args,
+                          ba->k7.smem, ctx->stream);
+    if (ba->k7.det && d.F > 0)
         hipLaunchKernelGGL(reduce_det_kernel, dim3(d.u_rows), dim3(256), (size_t)14 * (DET_TILE + 1) * sizeof(double), ctx->stream, d);
 }
 
@@ -1103,8 +1156,7 @@ static int ba_ensure_mailbox(ptam_ba* ba) {
     if (ba->mbox) return PTAM_OK;
     void* h = nullptr;
     size_t cap = 0;
-    if (!ctx_cache_take(ba->ctx->host_cache, CTX_NCACHE(ba->ctx->host_cache), sizeof(ptam_ba::Mailbox), &h, &cap))
-        HIP_TRY(hipHostMalloc(&h, sizeof(ptam_ba::Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
+    if (int rc = ctx_block_take(ba->ctx, CTX_MEM_MAPPED, sizeof(ptam_ba::Mailbox), &h, &cap)) return rc;
     std::memset(h, 0, sizeof(ptam_ba::Mailbox));
     void* dv = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dv, h, 0));
@@ -1435,34 +1487,6 @@ static void ba_report_trial_times(const ptam_ba* ba, const std::vector<double>& 
     std::fprintf(stderr, "\n");
 }
 
-// ---- read back results: one pinned staging buffer, one synchronisation (pageable destinations cost ~100 us each) ----
-static int ba_readback(ptam_ba* ba, int n_out, std::vector<int>& out_idx) {
-    ptam_ctx* ctx = ba->ctx;
-    const BaDev& d = ba->d;
-    const size_t b_pose = (size_t)d.C * 96, b_pts = (size_t)d.P * 24, b_out = (size_t)n_out * 4;
-    void* pin = nullptr;
-    int rc = ctx_pinned(ctx, 64 + b_pose + b_pts + b_out + 64, &pin);
-    if (rc) return rc;
-    char* hp = (char*)pin + 64;   // [sequence word | poses | points | outlier indices]
-    char* dp = (char*)ctx->d_pinned + 64;
-    volatile unsigned long long* slot = (volatile unsigned long long*)pin;
-    const unsigned long long seq = ++ctx->pose_seq;
-    *slot = 0;
-    const size_t n_all = (size_t)d.C * 12 + (size_t)d.P * 3 + (size_t)n_out;
-    hipLaunchKernelGGL(readback_kernel, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n_all + 255) / 256, 1024))), dim3(256), 0,
-                       ctx->stream, (const double*)d.pose[ba->cur], (size_t)d.C * 12, (const double*)d.pt[ba->cur], (size_t)d.P * 3,
-                       (const int*)d.outliers, (size_t)n_out, (double*)dp, (double*)(dp + b_pose), (int*)(dp + b_pose + b_pts));
-    hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, ctx->stream, (volatile unsigned long long*)ctx->d_pinned, seq);
-    HIP_TRY(hipGetLastError());
-    rc = ba_wait_stamp(ctx, slot, seq, "the bundle's results");
-    if (rc) return rc;
-    std::memcpy(ba->cam_pose.data(), hp, b_pose);
-    for (int q = 0; q < d.P; q++)   // (device point q is original point pt_orig[q]; unobserved points keep their position)
-        std::memcpy(&ba->pts[(size_t)3 * ba->pt_orig[(size_t)q]], hp + b_pose + (size_t)q * 24, 24);
-    if (n_out > 0) std::memcpy(out_idx.data(), hp + b_pose + b_pts, b_out);
-    return PTAM_OK;
-}
-
 extern "C" {
 
 void ptam_ba_opts_default(ptam_ba_opts* o) {
@@ -1498,10 +1522,7 @@ int ptam_ba_destroy(ptam_ba* ba) {
     hipSetDevice(ba->ctx->device);
     ptam_stream_wait(ba->ctx->stream);
     ba_free_device(ba);
-    if (ba->mbox) {
-        void* drop = ctx_cache_give(ba->ctx->host_cache, CTX_NCACHE(ba->ctx->host_cache), ba->mbox, sizeof(ptam_ba::Mailbox));
-        if (drop) hipHostFree(drop);
-    }
+    ctx_block_give(ba->ctx, CTX_MEM_MAPPED, ba->mbox, sizeof(ptam_ba::Mailbox));
     if (ba->ev_ok)
         for (int k = 0; k < PTAM_K_COUNT; k++) {
             hipEventDestroy(ba->ev[k][0]);
@@ -1602,7 +1623,7 @@ int ptam_ba_prepare(ptam_ba* ba) {
     rc = ba_ensure_mailbox(ba);
     if (rc) return rc;
     void* pin = nullptr;
-    return ctx_pinned(ba->ctx, 64 + (size_t)ba->d.C * 96 + (size_t)ba->d.P * 24 + (size_t)ba->d.M * 4 + 64, &pin);
+    return ctx_pinned(ba->ctx, ba_readback_bytes(ba->d.C, ba->d.P, ba->d.M), &pin);
 }
 
 int ptam_ba_set_profiling(ptam_ba* ba, int on) {
@@ -1973,9 +1994,9 @@ int ptam_ba_debug_lists(ptam_ba* ba, int which, void* out, size_t cap_bytes) {  
         case PTAM_BL_S_WG_SEG: src = d.s_wg_seg, bytes = d.n_schur_wg > 0 ? ((size_t)d.n_schur_wg + 1) * 4 : 0; break;
         case PTAM_BL_S_PAIR_BEGIN: src = d.s_pair_wg_begin, bytes = d.F > 0 ? ((size_t)d.n_pairs + 1) * 4 : 0; break;
         case PTAM_BL_S_WG_HEAD: src = d.s_wg_head, bytes = (size_t)d.n_schur_wg * 32; break;
-        case PTAM_BL_CAM_PTR: src = d.cam_ptr, bytes = ba->det ? (size_t)((d.M + DET_TILE - 1) / DET_TILE) * ((size_t)d.F + 1) * 4 : 0; break;
+        case PTAM_BL_CAM_PTR: src = d.cam_ptr, bytes = ba->k7.det ? (size_t)((d.M + DET_TILE - 1) / DET_TILE) * ((size_t)d.F + 1) * 4 : 0; break;
         case PTAM_BL_CAM_MEAS:
-            if (ba->det && d.M > 0) {   // its length is the last tile's last row end
+            if (ba->k7.det && d.M > 0) {   // its length is the last tile's last row end
                 const size_t last = (size_t)((d.M + DET_TILE - 1) / DET_TILE) * ((size_t)d.F + 1) - 1;
                 HIP_TRY(hipMemcpyAsync(&n_free_meas, d.cam_ptr + last, 4, hipMemcpyDeviceToHost, ctx->stream));
                 HIP_TRY(ptam_stream_wait(ctx->stream));

@@ -74,8 +74,13 @@ struct ptam_ctx {
     unsigned n_k7_shapes;   // shapes asked so far (slot n % 16: a full table forgets its oldest entry, which is then asked again)
 };
 #define CTX_NCACHE(a) ((int)(sizeof(a) / sizeof((a)[0])))
-int ctx_cache_take(ptam_ctx::Cached* c, int slots, size_t bytes, void** out, size_t* cap);   // smallest cached block >= bytes, or null
-void* ctx_cache_give(ptam_ctx::Cached* c, int slots, void* p, size_t bytes);                 // returns the pointer the caller must free (or null)
+// A block of one of the three cached kinds: taken from the context's cache (the smallest released block >= bytes; *cap is its size)
+// or allocated (hipMalloc | hipHostMalloc default | hipHostMalloc mapped and coherent; *cap = bytes), and given back to the cache,
+// which frees what it has no slot for.  A released block's kernels and copies may still be queued: its next owner only touches it
+// through the context's queue.
+enum CtxMem { CTX_MEM_DEVICE, CTX_MEM_PINNED, CTX_MEM_MAPPED };
+int ctx_block_take(ptam_ctx* ctx, CtxMem kind, size_t bytes, void** out, size_t* cap);
+void ctx_block_give(ptam_ctx* ctx, CtxMem kind, void* p, size_t cap);   // (p may be null)
 
 // hipStreamSynchronize sleeps on an interrupt, and waking from it was measured at up to 7 ms on this platform; the waits
 // of this library end within microseconds to a few milliseconds, so every one of them polls first (2 ms) and only then sleeps.

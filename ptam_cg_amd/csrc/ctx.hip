@@ -43,36 +43,53 @@ hipError_t ptam_stream_wait(hipStream_t stream) {
     return hipStreamSynchronize(stream);
 }
 
-int ctx_cache_take(ptam_ctx::Cached* c, int slots, size_t bytes, void** out, size_t* cap) {
-    int best = -1;
-    for (int i = 0; i < slots; i++)
+static ptam_ctx::Cached* ctx_cache_of(ptam_ctx* ctx, CtxMem kind, int* slots) {
+    switch (kind) {
+        case CTX_MEM_DEVICE: *slots = CTX_NCACHE(ctx->dev_cache); return ctx->dev_cache;
+        case CTX_MEM_PINNED: *slots = CTX_NCACHE(ctx->pin_cache); return ctx->pin_cache;
+        default: *slots = CTX_NCACHE(ctx->host_cache); return ctx->host_cache;
+    }
+}
+int ctx_block_take(ptam_ctx* ctx, CtxMem kind, size_t bytes, void** out, size_t* cap) {
+    int slots = 0, best = -1;
+    ptam_ctx::Cached* c = ctx_cache_of(ctx, kind, &slots);
+    for (int i = 0; i < slots; i++)   // the smallest released block that fits
         if (c[i].p && c[i].bytes >= bytes && (best < 0 || c[i].bytes < c[best].bytes)) best = i;
-    *out = nullptr;
-    *cap = 0;
     if (best >= 0) {
         *out = c[best].p;
         *cap = c[best].bytes;
         c[best].p = nullptr;
         c[best].bytes = 0;
+        return PTAM_OK;
     }
-    return best >= 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (kind == CTX_MEM_DEVICE)
+        HIP_TRY(hipMalloc(out, bytes));
+    else
+        HIP_TRY(hipHostMalloc(out, bytes, kind == CTX_MEM_PINNED ? hipHostMallocDefault : hipHostMallocMapped | hipHostMallocCoherent));
+    *cap = bytes;
+    return PTAM_OK;
 }
-void* ctx_cache_give(ptam_ctx::Cached* c, int slots, void* p, size_t bytes) {
-    if (!p) return nullptr;
+void ctx_block_give(ptam_ctx* ctx, CtxMem kind, void* p, size_t cap) {
+    if (!p) return;
+    int slots = 0, small = 0;
+    ptam_ctx::Cached* c = ctx_cache_of(ctx, kind, &slots);
     for (int i = 0; i < slots; i++)
         if (!c[i].p) {
             c[i].p = p;
-            c[i].bytes = bytes;
-            return nullptr;
+            c[i].bytes = cap;
+            return;
         }
-    int small = 0;   // every slot taken: keep the largest
-    for (int i = 1; i < slots; i++)
+    for (int i = 1; i < slots; i++)   // every slot taken: keep the largest
         if (c[i].bytes < c[small].bytes) small = i;
-    if (bytes <= c[small].bytes) return p;
-    void* drop = c[small].p;
-    c[small].p = p;
-    c[small].bytes = bytes;
-    return drop;
+    if (cap > c[small].bytes) {
+        std::swap(p, c[small].p);
+        c[small].bytes = cap;
+    }
+    if (kind == CTX_MEM_DEVICE)
+        hipFree(p);
+    else
+        hipHostFree(p);
 }
 
 int ctx_pinned(ptam_ctx* ctx, size_t bytes, void** out) {

@@ -342,6 +342,38 @@ def test_duplicate_measurement_is_refused_with_its_point_and_camera(hip):
     ctx.close()
 
 
+def test_a_refused_prepare_leaves_the_bundle_and_the_context_usable(hip, oracle):
+    """prepare() returns early — here with a duplicate, after the first phase — while the bundle already owns its main block:
+    the bundle can be asked again (same answer), its Compute() fails cleanly, close() gives the block back, and the next bundle
+    of the SAME context (it takes that block from the context's cache) computes what the checker computes."""
+    from tests import util
+    prob = synth.make_ba_problem(n_cams=9, n_pts=300, seed=10)
+    for k in ("cam_idx", "pt_idx", "found", "sigma_sq"):
+        prob[k] = np.concatenate([prob[k], prob[k][1234:1235]])
+    text = f"duplicate measurement of point {prob['pt_idx'][1234]} by camera {prob['cam_idx'][1234]}"
+    ctx = host.Context(lib=hip)
+    ba = synth.load_into(host.Bundle(ctx), prob)
+    first = []
+    for _ in range(2):
+        with pytest.raises(host.PtamError) as ei:
+            ba.prepare()
+        assert text in str(ei.value)
+        first.append(str(ei.value))
+    assert first[0] == first[1]
+    with pytest.raises(host.PtamError):
+        ba.Compute()
+    ba.close()
+    good = synth.make_ba_problem(8, 50, 1)
+    ba = synth.load_into(host.Bundle(ctx), good)
+    acc = ba.Compute()
+    poses, pts = ba.get_all()
+    res = {"accepted": acc, "converged": ba.Converged(), "trials": ba.trials(), "poses": poses, "points": pts,
+           "outliers": ba.GetOutlierMeasurements(), "solve_fallbacks": ba.solve_fallbacks()}
+    ba.close()
+    ctx.close()
+    util.assert_ba_equal(res, util.run_ba(oracle, good), rel=1e-6)
+
+
 def test_measurements_added_between_two_computes_and_exact_chunk_sizes(hip, oracle, split_ref):
     """The measurements go to the device in chunks of 32 768 while they are added (MeasStore): a bundle of exactly one chunk, one
     of a chunk + 1, and a bundle that is adjusted, given MORE measurements (the partial chunk goes up again) and adjusted again —
