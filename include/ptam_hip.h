@@ -820,6 +820,93 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
                            const volatile unsigned char* abort_flag, ptam_map_ba_result* res, ptam_map_outlier* outliers,
                            int outlier_cap, int32_t* cam_kf, int32_t* point_ids);
 
+/* ---- MapMaker::CalcPlaneAligner (src/MapMaker.cc:1100-1195), the first half of stage (8) of InitFromStereo (:397), on the point
+ *      table (v3WorldPos, vpPoints order), fp64 throughout, two kernel launches, one host wait at the end:
+ *      `trials` hypotheses (:1112-1149), each the plane through three points: v3Mean = 0.33333333 * (A + B + C) (that literal),
+ *      v3Normal = (C - A) ^ (B - A); a normal whose squared length is exactly 0 skips the trial (:1128-1129), else it is
+ *      normalised and the score is the sum over all points whose squared distance from v3Mean is not 0.0 (:1136-1137) of
+ *      min(|v3Diff * v3Normal|, max_dist); the strictly smaller score wins, among equal scores the lowest trial.
+ *      Inliers (:1152-1161): not at v3BestMean itself, and nearer the plane than max_dist (strictly).  Their mean, then their
+ *      covariance about that mean (:1164-1173, two passes).  The normal is the eigenvector of the covariance's smallest
+ *      eigenvalue by cyclic Jacobi (the reference: TooN SymEigen<3> over LAPACK, get_evectors()[0]), negated when its z is > 0
+ *      (:1180-1181); rotation rows as in :1183-1187 (row 2 the normal, row 0 = e_x - n (e_x . n) normalised, row 1 = row 2 ^ row 0),
+ *      translation -R * mean (:1189-1192).  max_dist stands for both literals 0.05 (:1140, :1159).
+ *      The reference's operation order without FMA contraction; every sum over points is reduced in a fixed order: two calls
+ *      on the same input give the same bits.
+ *      The draw: the reference calls rand() (:1113-1119); here the triples are an input.  opts->samples: trials x 3 point
+ *      indices; NULL: the table ptam_plane_samples(opts->seed, n, trials) — the splitmix64 of ptam_homography_samples started
+ *      from state = seed, nA = next() % n, nB drawn again while it equals nA, nC drawn again while it equals nA or nB.
+ *      Four places where the reference's behaviour is undefined are given a meaning here:
+ *        n_points < 10 (:1103-1106 returns SE3<>()): PTAM_PLANE_TOO_FEW, nothing is drawn or scored;
+ *        every trial skipped (:1146-1147 never run, :1154 reads an unassigned v3BestMean): PTAM_PLANE_DEGENERATE;
+ *        an empty inlier set (:1167 divides by zero): PTAM_PLANE_DEGENERATE;
+ *        a row 0 of zero length before normalize (:1186, the normal along x): PTAM_PLANE_DEGENERATE.
+ *      With a status other than PTAM_PLANE_OK the aligner is the identity. */
+enum { PTAM_PLANE_OK = 0, PTAM_PLANE_TOO_FEW = 1, PTAM_PLANE_DEGENERATE = 2 };
+typedef struct {
+    double   max_dist;          /* 0.05: src/MapMaker.cc:1140 and :1159 */
+    int32_t  trials;            /* 100: MapMaker.PlaneAlignerRansacs (:1111) */
+    uint64_t seed;              /* used when samples == NULL */
+    const int32_t* samples;     /* trials x 3 point indices, or NULL */
+} ptam_plane_opts;
+typedef struct {
+    int32_t status, n_points, n_inliers, best_trial /* -1: none */, trials_skipped, pad_;
+    double  best_score;         /* dBestDistSquared of the winning trial; 0 without one */
+    double  mean[3];            /* v3MeanOfInliers */
+    double  normal[3];          /* v3Normal after the sign rule = row 2 of the rotation */
+    double  eigenvalues[3];     /* of m3Cov, ascending */
+} ptam_plane_info;
+void ptam_plane_opts_default(ptam_plane_opts*);
+/* out: trials x 3.  PTAM_E_ARG: out == NULL, n_points < 3, trials < 1.  Host only. */
+int  ptam_plane_samples(uint64_t seed, int n_points, int trials, int32_t* out);
+/* se3_aligner: R row-major, then t; info always; inlier_out (nullable): n_points bytes, 1 = vv3Inliers holds the point (all 0
+ * where no inlier pass ran).  The workspace is the context's scratch, which grows on demand and stays.
+ * PTAM_E_ARG, with nothing written: a null pointer (inlier_out excepted; points3 may be null with n_points == 0), n_points < 0,
+ * trials < 1, max_dist <= 0, and with n_points >= 10 a sample index outside [0, n_points) or repeated inside its triple. */
+int  ptam_calc_plane_aligner(ptam_ctx*, int n_points, const double* points3 /* host */, const ptam_plane_opts*,
+                             double se3_aligner[12], ptam_plane_info* info, uint8_t* inlier_out);
+
+/* ---- MapMaker::ApplyGlobalTransformationToMap (src/MapMaker.cc:463-472) on the map tables, one launch (one thread per keyframe
+ *      and per point), one host wait: every se3CfromW becomes se3CfromW * se3NewFromOld.inverse() (TooN: the inverse is
+ *      (R^T, -(R^T t)), the product (Rl Rr, tl + Rl tr)), every v3WorldPos becomes se3NewFromOld * v3WorldPos, both in place.
+ *      With a source table MapPoint::RefreshPixelVectors (src/Map.cc:40-65) is then run per point against the NEW pose of its
+ *      source keyframe, with v3Normal_NC = (0,0,-1) as everywhere here, and the rows come out as ptam_pvs_point — what
+ *      ptam_tracker_set_map / ptam_tracker_update_map and the re-finder take as is.  `sources` and `out` are nullable together.
+ *      PTAM_E_ARG, with nothing written: a null aligner, a negative count, a null table with a non-zero count, one of
+ *      sources / out without the other, a src_kf outside [0, n_kf). */
+typedef struct {
+    int32_t src_kf, pad_;       /* pPatchSourceKF as an index into the keyframe table */
+    double center_nc[3], one_right_nc[3], one_down_nc[3];   /* as ptam_new_map_point returns them */
+} ptam_map_point_source;
+int  ptam_map_apply_global_transform(ptam_ctx*, const double se3_new_from_old[12], int n_kf, double* kf_poses12, int n_points,
+                                     double* points3, const ptam_map_point_source* sources, ptam_pvs_point* out);
+
+/* ---- stage (8) of MapMaker::InitFromStereo (src/MapMaker.cc:397), ApplyGlobalTransformationToMap(CalcPlaneAligner()), as ONE
+ *      call: the points go up once, the two kernels of ptam_calc_plane_aligner run, the kernel of
+ *      ptam_map_apply_global_transform reads the aligner from device memory, everything comes down together: three launches,
+ *      one host wait, the same bits as the two calls one after the other.  The tables are written only when info->status ==
+ *      PTAM_PLANE_OK.  PTAM_PLANE_TOO_FEW: the reference applies the identity, so the tables stay as they are and `out`, if
+ *      given, is filled from them.  PTAM_PLANE_DEGENERATE: nothing but se3_aligner (the identity), info and inlier_out is
+ *      written.  PTAM_E_ARG: the refusals of both calls. */
+int  ptam_map_align_to_plane(ptam_ctx*, const ptam_plane_opts*, int n_kf, double* kf_poses12, int n_points, double* points3,
+                             const ptam_map_point_source* sources, ptam_pvs_point* out, double se3_aligner[12],
+                             ptam_plane_info* info, uint8_t* inlier_out);
+
+/* ---- MapMaker::RefreshSceneDepth (src/MapMaker.cc:1202-1219), stage (5) of InitFromStereo (:378-380), for EVERY keyframe of the
+ *      table in one call: one launch (one workgroup per keyframe, its rows found in the sorted table, the sums in a fixed
+ *      order), one host wait.  meas: the table of ptam_map_bundle_adjust, sorted by (kf, point) with no repeated pair (only kf
+ *      and point are read).  Per keyframe, with z the third component of se3CfromW * v3WorldPos over its rows:
+ *      depth_mean = sum z / n, depth_sigma = sqrt(sum z^2 / n - depth_mean^2).  The reference asserts nMeas > 2 (:1216); here
+ *      n_meas tells the caller: a keyframe without a row gets 0 / 0 / 0, and a radicand that rounding made negative gives 0.
+ *      PTAM_E_ARG, with nothing written: a null table with a non-zero count, a negative count, an index out of range, a row
+ *      out of order or repeated. */
+typedef struct {
+    double  depth_mean, depth_sigma;   /* KeyFrame::dSceneDepthMean, dSceneDepthSigma */
+    int32_t n_meas, pad_;
+} ptam_scene_depth;
+int  ptam_map_scene_depth(ptam_ctx*, int n_kf, const double* kf_poses12, int n_points, const double* points3, int n_meas,
+                          const ptam_map_meas* meas, ptam_scene_depth* out /* n_kf */);
+
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,
  * ordered on `stream` (hipStream_t).  Return 0 on success. */

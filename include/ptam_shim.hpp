@@ -443,6 +443,80 @@ inline MapBundleAdjustResult MapBundleAdjust(Context& c, int mode, std::vector<S
     return r;
 }
 
+// SE3<> MapMaker::CalcPlaneAligner()   src/MapMaker.cc:1100-1195 on the point table in one device call (ptam_calc_plane_aligner).
+// The reference draws its triples with rand(); here the draw is opts->seed (splitmix64: ptam_hip.h) or opts->samples.  A status
+// other than PTAM_PLANE_OK comes with the identity, as the reference's "too few points" does.
+struct PlaneAligner {
+    SE3 se3 = SE3::Identity();
+    ptam_plane_info info{};
+    std::vector<uint8_t> inliers;   // 1: the point is in vv3Inliers
+};
+inline ptam_plane_opts PlaneOptsOrDefault(const ptam_plane_opts* opts) {
+    ptam_plane_opts o;
+    ptam_plane_opts_default(&o);
+    return opts ? *opts : o;
+}
+inline PlaneAligner CalcPlaneAligner(Context& c, const std::vector<Vec<3>>& vPoints, const ptam_plane_opts* opts = nullptr) {
+    const ptam_plane_opts o = PlaneOptsOrDefault(opts);
+    PlaneAligner r;
+    r.inliers.assign(vPoints.size(), 0);
+    double p[12];
+    check(ptam_calc_plane_aligner(c.handle(), (int)vPoints.size(), reinterpret_cast<const double*>(vPoints.data()), &o, p, &r.info,
+                                  r.inliers.data()),
+          "ptam_calc_plane_aligner");
+    r.se3 = SE3::from12(p);
+    return r;
+}
+
+// void MapMaker::ApplyGlobalTransformationToMap(SE3<> se3NewFromOld)   src/MapMaker.cc:463-472 on the map tables in one device call
+// (ptam_map_apply_global_transform): poses and points are updated in place.  With pvSources (pPatchSourceKF as an index, the _NC
+// vectors) every point's RefreshPixelVectors runs too and the rows ptam_tracker_set_map takes come back; without, nothing does.
+inline std::vector<ptam_pvs_point> ApplyGlobalTransformationToMap(Context& c, const SE3& se3NewFromOld, std::vector<SE3>& vKFPoses,
+                                                                 std::vector<Vec<3>>& vPoints,
+                                                                 const std::vector<ptam_map_point_source>* pvSources = nullptr) {
+    if (pvSources && pvSources->size() != vPoints.size()) throw std::runtime_error("ApplyGlobalTransformationToMap: one source per point");
+    std::vector<ptam_pvs_point> out(pvSources ? vPoints.size() : 0);
+    double p[12];
+    se3NewFromOld.to12(p);
+    check(ptam_map_apply_global_transform(c.handle(), p, (int)vKFPoses.size(), reinterpret_cast<double*>(vKFPoses.data()),
+                                          (int)vPoints.size(), reinterpret_cast<double*>(vPoints.data()),
+                                          pvSources ? pvSources->data() : nullptr, pvSources ? out.data() : nullptr),
+          "ptam_map_apply_global_transform");
+    return out;
+}
+
+// ApplyGlobalTransformationToMap(CalcPlaneAligner())   src/MapMaker.cc:397 as ONE device call (ptam_map_align_to_plane).  The tables
+// move only when the status is PTAM_PLANE_OK; pvOut (with pvSources) receives the refreshed rows unless it is PTAM_PLANE_DEGENERATE.
+inline PlaneAligner AlignMapToPlane(Context& c, std::vector<SE3>& vKFPoses, std::vector<Vec<3>>& vPoints,
+                                    const std::vector<ptam_map_point_source>* pvSources = nullptr,
+                                    std::vector<ptam_pvs_point>* pvOut = nullptr, const ptam_plane_opts* opts = nullptr) {
+    if ((pvSources == nullptr) != (pvOut == nullptr)) throw std::runtime_error("AlignMapToPlane: sources and rows come together");
+    if (pvSources && pvSources->size() != vPoints.size()) throw std::runtime_error("AlignMapToPlane: one source per point");
+    const ptam_plane_opts o = PlaneOptsOrDefault(opts);
+    PlaneAligner r;
+    r.inliers.assign(vPoints.size(), 0);
+    if (pvOut) pvOut->assign(vPoints.size(), ptam_pvs_point{});
+    double p[12];
+    check(ptam_map_align_to_plane(c.handle(), &o, (int)vKFPoses.size(), reinterpret_cast<double*>(vKFPoses.data()), (int)vPoints.size(),
+                                  reinterpret_cast<double*>(vPoints.data()), pvSources ? pvSources->data() : nullptr,
+                                  pvOut ? pvOut->data() : nullptr, p, &r.info, r.inliers.data()),
+          "ptam_map_align_to_plane");
+    r.se3 = SE3::from12(p);
+    return r;
+}
+
+// void MapMaker::RefreshSceneDepth(KeyFrame* pKF)   src/MapMaker.cc:1202-1219 for every keyframe of the table in one device call
+// (ptam_map_scene_depth): vMeas as MapBundleAdjust takes it.  dSceneDepthMean / dSceneDepthSigma per keyframe; n_meas where the
+// reference asserts.
+inline std::vector<ptam_scene_depth> RefreshSceneDepth(Context& c, const std::vector<SE3>& vKFPoses, const std::vector<Vec<3>>& vPoints,
+                                                       const std::vector<ptam_map_meas>& vMeas) {
+    std::vector<ptam_scene_depth> out(vKFPoses.size());
+    check(ptam_map_scene_depth(c.handle(), (int)vKFPoses.size(), reinterpret_cast<const double*>(vKFPoses.data()), (int)vPoints.size(),
+                               reinterpret_cast<const double*>(vPoints.data()), (int)vMeas.size(), vMeas.data(), out.data()),
+          "ptam_map_scene_depth");
+    return out;
+}
+
 // TrackMap's potentially-visible-set loop (src/Tracker.cc:453-478): TData.Project + GetProjectionDerivs
 // + Finder.CalcSearchLevelAndWarpMatrix for every map point, one launch.
 inline void TrackMapPVS(Context& c, const std::vector<ptam_pvs_point>& vMapPoints, const SE3& se3CamFromWorld,

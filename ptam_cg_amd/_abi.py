@@ -157,6 +157,31 @@ class MapBaResult(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ("ran", "accepted", "converged", "n_adjust", "n_fixed", "n_points", "n_meas", "n_outliers")]
 
 
+PLANE_OK, PLANE_TOO_FEW, PLANE_DEGENERATE = range(3)
+
+
+class PlaneOpts(C.Structure):
+    """ptam_plane_opts (MapMaker::CalcPlaneAligner, src/MapMaker.cc:1100-1195)"""
+    _fields_ = [("max_dist", C.c_double), ("trials", C.c_int32), ("seed", C.c_uint64), ("samples", C.POINTER(C.c_int32))]
+
+
+class PlaneInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_points", C.c_int32), ("n_inliers", C.c_int32), ("best_trial", C.c_int32),
+                ("trials_skipped", C.c_int32), ("pad_", C.c_int32), ("best_score", C.c_double), ("mean", C.c_double * 3),
+                ("normal", C.c_double * 3), ("eigenvalues", C.c_double * 3)]
+
+
+class MapPointSource(C.Structure):
+    """ptam_map_point_source (MapPoint::pPatchSourceKF and the _NC vectors, include/MapPoint.h)"""
+    _fields_ = [("src_kf", C.c_int32), ("pad_", C.c_int32), ("center_nc", C.c_double * 3), ("one_right_nc", C.c_double * 3),
+                ("one_down_nc", C.c_double * 3)]
+
+
+class SceneDepth(C.Structure):
+    """ptam_scene_depth (MapMaker::RefreshSceneDepth, src/MapMaker.cc:1202-1219)"""
+    _fields_ = [("depth_mean", C.c_double), ("depth_sigma", C.c_double), ("n_meas", C.c_int32), ("pad_", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p)
 
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
@@ -273,6 +298,12 @@ PROTOTYPES = {
     "ba_debug_lists": (_i, [_vp, _i, _vp, C.c_size_t]),
     "ba_set_comm": (_i, [_vp, _i, _i, ALLREDUCE_FN, _vp]),
     "map_bundle_adjust": (_i, [_vp, C.POINTER(BaOpts), _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(MapBaResult), _vp, _i, _vp, _vp]),
+    "plane_opts_default": (None, [C.POINTER(PlaneOpts)]),
+    "plane_samples": (_i, [C.c_uint64, _i, _i, _vp]),
+    "calc_plane_aligner": (_i, [_vp, _i, _vp, C.POINTER(PlaneOpts), _pd, C.POINTER(PlaneInfo), _vp]),
+    "map_apply_global_transform": (_i, [_vp, _pd, _i, _vp, _i, _vp, _vp, _vp]),
+    "map_align_to_plane": (_i, [_vp, C.POINTER(PlaneOpts), _i, _vp, _i, _vp, _vp, _vp, _pd, C.POINTER(PlaneInfo), _vp]),
+    "map_scene_depth": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

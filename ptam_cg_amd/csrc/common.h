@@ -94,6 +94,7 @@ void mapmaker_preload_kernels();
 void trails_preload_kernels();
 void homography_preload_kernels();
 void mapba_preload_kernels();
+void mapalign_preload_kernels();
 void kf_preload_kernels();
 void pvs_preload_kernels();
 void trackmap_preload_kernels();

@@ -261,6 +261,7 @@ int ptam_ctx_create(const ptam_cam_params* cam, int device, ptam_ctx** out) {
     trails_preload_kernels();
     homography_preload_kernels();
     mapba_preload_kernels();
+    mapalign_preload_kernels();
     kf_preload_kernels();
     pvs_preload_kernels();
     *out = c;

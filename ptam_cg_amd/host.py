@@ -546,6 +546,95 @@ def map_bundle_adjust(ctx, mode, poses, fixed, points, meas, abort=None, **ba_op
     return d
 
 
+MAP_POINT_SOURCE_DT = np.dtype([("src_kf", "<i4"), ("pad_", "<i4"), ("center_nc", "<f8", (3,)), ("one_right_nc", "<f8", (3,)),
+                                ("one_down_nc", "<f8", (3,))])
+SCENE_DEPTH_DT = np.dtype([("depth_mean", "<f8"), ("depth_sigma", "<f8"), ("n_meas", "<i4"), ("pad_", "<i4")])
+assert MAP_POINT_SOURCE_DT.itemsize == C.sizeof(_abi.MapPointSource) == 80 and SCENE_DEPTH_DT.itemsize == C.sizeof(_abi.SceneDepth) == 24
+
+
+def plane_samples(lib, seed, n_points, trials=100):
+    """the triples ptam_calc_plane_aligner draws from `seed` (ptam_plane_samples, host only): (trials, 3) int32"""
+    out = np.zeros((trials, 3), np.int32)
+    rc = lib.plane_samples(int(seed), int(n_points), int(trials), _ptr(out))
+    if rc < 0:
+        raise PtamError(f"plane_samples failed ({rc}): {lib.last_error().decode()}")
+    return out
+
+
+def _plane_opts(lib, max_dist, seed, samples, trials):
+    opts = _abi.PlaneOpts()
+    lib.plane_opts_default(C.byref(opts))
+    opts.max_dist, opts.trials, opts.seed = float(max_dist), int(trials), int(seed)
+    if samples is not None:
+        keep = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 3)
+        opts.trials = len(keep)
+        opts.samples = keep.ctypes.data_as(C.POINTER(C.c_int32))
+        opts._keep = keep      # (the table lives as long as the options)
+    return opts
+
+
+def _plane_info(info):
+    d = {f: getattr(info, f) for f in ("status", "n_points", "n_inliers", "best_trial", "trials_skipped", "best_score")}
+    d.update(mean=np.array(info.mean), normal=np.array(info.normal), eigenvalues=np.array(info.eigenvalues))
+    return d
+
+
+def calc_plane_aligner(ctx, points, max_dist=0.05, seed=0, samples=None, trials=100):
+    """MapMaker::CalcPlaneAligner (src/MapMaker.cc:1100-1195) in one device call (ptam_calc_plane_aligner): points (N, 3);
+    the draw is `samples` ((trials, 3) point indices) or splitmix64 on `seed` -> (se3 (12,), info dict, inliers (N,) bool)"""
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    opts = _plane_opts(ctx.lib, max_dist, seed, samples, trials)
+    se3, info, inl = np.zeros(12), _abi.PlaneInfo(), np.zeros(max(len(pts), 1), np.uint8)
+    ctx._check(ctx.lib.calc_plane_aligner(ctx.h, len(pts), _ptr(pts), C.byref(opts), _pd(se3), C.byref(info), _ptr(inl)), "calc_plane_aligner")
+    return se3, _plane_info(info), inl[:len(pts)].astype(bool)
+
+
+def _map_tables(poses, points, sources):
+    poses = np.array(poses, dtype=np.float64).reshape(-1, 12)
+    points = np.array(points, dtype=np.float64).reshape(-1, 3)
+    src = out = None
+    if sources is not None:
+        src = np.ascontiguousarray(sources, dtype=MAP_POINT_SOURCE_DT)
+        out = np.zeros(max(len(points), 1), PVS_POINT_DT)
+    return poses, points, src, out
+
+
+def map_apply_global_transform(ctx, se3_new_from_old, poses, points, sources=None):
+    """MapMaker::ApplyGlobalTransformationToMap (src/MapMaker.cc:463-472) in one device call on the map tables: poses (K, 12),
+    points (N, 3), sources MAP_POINT_SOURCE_DT or None.  The inputs are not modified -> (poses, points, pvs rows PVS_POINT_DT or
+    None)"""
+    poses, points, src, out = _map_tables(poses, points, sources)
+    se3 = np.ascontiguousarray(se3_new_from_old, dtype=np.float64).reshape(12)
+    ctx._check(ctx.lib.map_apply_global_transform(ctx.h, _pd(se3), len(poses), _ptr(poses), len(points), _ptr(points), _ptr(src), _ptr(out)),
+               "map_apply_global_transform")
+    return poses, points, (out[:len(points)] if out is not None else None)
+
+
+def map_align_to_plane(ctx, poses, points, sources=None, max_dist=0.05, seed=0, samples=None, trials=100):
+    """ApplyGlobalTransformationToMap(CalcPlaneAligner()) (src/MapMaker.cc:397) in ONE device call (ptam_map_align_to_plane).  The
+    inputs are not modified -> dict: "se3", "info", "inliers", and the tables after the call: "poses", "points", "pvs" (None
+    without sources; unwritten rows are zero)"""
+    poses, points, src, out = _map_tables(poses, points, sources)
+    opts = _plane_opts(ctx.lib, max_dist, seed, samples, trials)
+    se3, info, inl = np.zeros(12), _abi.PlaneInfo(), np.zeros(max(len(points), 1), np.uint8)
+    ctx._check(ctx.lib.map_align_to_plane(ctx.h, C.byref(opts), len(poses), _ptr(poses), len(points), _ptr(points), _ptr(src), _ptr(out),
+                                          _pd(se3), C.byref(info), _ptr(inl)), "map_align_to_plane")
+    return dict(se3=se3, info=_plane_info(info), inliers=inl[:len(points)].astype(bool), poses=poses, points=points,
+                pvs=(out[:len(points)] if out is not None else None))
+
+
+def map_scene_depth(ctx, poses, points, meas):
+    """MapMaker::RefreshSceneDepth (src/MapMaker.cc:1202-1219) for every keyframe in one device call (ptam_map_scene_depth):
+    meas MAP_MEAS_DT sorted by (kf, point) -> SCENE_DEPTH_DT, one row per keyframe"""
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    meas = np.ascontiguousarray(meas, dtype=MAP_MEAS_DT)
+    out = np.zeros(max(len(poses), 1), SCENE_DEPTH_DT)
+    ctx._check(ctx.lib.map_scene_depth(ctx.h, len(poses), _ptr(poses), len(points), _ptr(points), len(meas), _ptr(meas), _ptr(out)),
+               "map_scene_depth")
+    return out[:len(poses)]
+
+
 class DevBuf:
     """A device allocation of the context (ptam_dev_alloc / upload / download / free)."""
 
