@@ -17,6 +17,12 @@
 //   last role, the RIGHT-HAND SIDE: b in LDS; for m = 0, 1, ...: F[m] up -> z_m = (Lmm^-T)^T b_m (stored: d.y), then
 //     b_j -= L(j,m) z_m for the rows below as their XF[j][m] come up.  It follows the factorisation at a distance of one
 //     hop and ends ~1 us after the chain; on the chain the same work cost ~0.5 us PER BLOCK.
+//   behind them, systems of up to CH_FI_MAX_NB block rows (the FORWARD-INVERSE form, do_bw == 2 below): COLUMN WORKER j, one
+//     per block column: the 32 identity columns of block j carried down the factorisation like the right-hand side — its
+//     columns of L^-1, block row by block row, each multiplied into x_j as soon as the right-hand side has published that
+//     block's w = D^-1 z.  The backward substitution — 12 us on one compute unit behind the chain at 10 block rows — is gone;
+//     what follows the chain's last flag is 2.9 us: z of the last block, a hop, a tile product and a mat-vec in every column
+//     worker at once, a hop, the trial poses.
 // Hand-offs.  A hop "stores -> flag -> poll -> loads" costs 1.1-1.8 us with write-through (sc1) payload stores, wherever the
 // two workgroups sit, and 0.7-1.0 us with plain stores when both sit on the SAME XCD — whose L2 then serves the reader's
 // agent-scope loads; across XCDs plain stores are never seen (tools/pingpong).  The chain can only run ahead of its
@@ -27,8 +33,9 @@
 // was spread over several XCDs falls back to write-through stores — slower, never stale.  Flags themselves are always
 // agent-scope atomics, loads of handed-over data always agent-scope (never served by the reader's L1).  Flags are never
 // cleared: a flag is up when it holds THIS solve's sequence number.  Every working workgroup of the launch is resident at
-// once (at most nblk of them, 256 threads), which the spinning relies on; a spin is bounded all the same and raises
-// d.sflags[0] when it gives up (the backward kernel passes that on: BaScalars::solve_fault, ptam_ba_* returns PTAM_E_HIP).
+// once (at most nblk of them, 2 nblk <= 26 with column workers, 256 threads, a CU each), which the spinning relies on; a
+// spin is bounded all the same and raises d.sflags[0] when it gives up (the backward kernel passes that on:
+// BaScalars::solve_fault, ptam_ba_* returns PTAM_E_HIP).
 struct ChainLds {
     double PF[2][2][NB][6];  // the factor loop's panel (ldlt_factor2.inc: [buffer][K | I][row][4 columns + pad])
     double T0[NB * LDP];     // Lkk^-T
@@ -53,6 +60,12 @@ __host__ __device__ __forceinline__ size_t ch_lds_bytes_bw(int band, int nblk) {
     const size_t rhs = (size_t)(2 + CH_BW_SL) * nblk * NB + NB, tiles = (size_t)(band + 1) * CH_TS;
     return sizeof(ChainLds) + 8 + (rhs > tiles ? rhs : tiles) * sizeof(double);
 }
+// the same for the forward-inverse form (do_bw == 2): a column worker carries the block rows j .. nblk-1 of its 32 columns of L^-1,
+// at most nblk tiles (L^-1 is dense below the diagonal whatever the band of L); the right-hand side needs two vectors
+__host__ __device__ __forceinline__ size_t ch_lds_bytes_fi(int band, int nblk) {
+    return sizeof(ChainLds) + 8 + (size_t)(band + 1 > nblk ? band + 1 : nblk) * CH_TS * sizeof(double);
+}
+#define CH_FI_MAX_NB 13    // block rows up to which the forward-inverse form is used: 13 tiles beside ChainLds fill a CU's LDS, and 2 x 13 working workgroups fit one XCD (32 CUs)
 #define CH_BW_MAXT 9       // in-band tiles left of the diagonal up to which the right-hand-side workgroup substitutes backwards itself: two register sets of so many tiles (dense: 10 block rows = the 50-keyframe headline; beyond, ldlt_backward_kernel follows the launch)
 // Looks a waiting workgroup takes before it gives up (BaDev::spin_limit; PTAM_CH_SPIN_LIMIT overrides): ~0.25 s.  A legitimate
 // wait is microseconds; what a wait can run into is a partner that was never dispatched — two persistent solves on one device
@@ -115,8 +128,11 @@ __device__ __forceinline__ void ch_wait_lanes(const unsigned* f, bool active, un
 }
 // working workgroups of a launch: the chain, the row workers of rows 2 .. nblk-1, the right-hand side
 __host__ __device__ __forceinline__ int ch_roles(int nblk) { return nblk > 2 ? nblk : 2; }
-// flag words: [0] error, then F[nblk], RF[nblk], XCC[nblk + 1], XF[nblk][band + 1]
-__host__ __device__ __forceinline__ size_t ch_flag_words(int nblk, int band) { return 2 + 3 * (size_t)nblk + (size_t)nblk * (band + 1); }
+// ... and, behind them, the column workers of the forward-inverse form: one per block column
+__host__ __device__ __forceinline__ int ch_roles_fi(int nblk) { return ch_roles(nblk) + nblk; }
+// flag words: [0] error, then F[nblk], RF[nblk], XCC[nblk + 1], XF[nblk][band + 1], and for the forward-inverse form WF[nblk]
+// (w_m = D_m^-1 z_m is published), XD[nblk] (column worker j has stored x_j), XCC2[nblk] (the column workers' XCC ids)
+__host__ __device__ __forceinline__ size_t ch_flag_words(int nblk, int band) { return 2 + 6 * (size_t)nblk + (size_t)nblk * (band + 1); }
 
 // What one chain of a launch works on.  [k0, k1): the block columns it eliminates; kr: one past the last block row that receives
 // their updates (k1 when nothing below takes part: the whole system, or the middle part of a two-ended elimination, whose
@@ -129,8 +145,17 @@ struct ChainArgs {
     unsigned* flags;
     int k0, k1, kr, n;
 };
-// do_bw (one chain over the WHOLE system only): the right-hand-side workgroup goes on with D^-1 and the backward substitution,
-// writes da, the trial poses pose[cur ^ 1] and |da|^2 — no ldlt_backward_kernel behind this launch.
+// do_bw (one chain over the WHOLE system only): no ldlt_backward_kernel behind this launch, da, the trial poses pose[cur ^ 1] and
+// |da|^2 are written here.  1: the right-hand-side workgroup goes on with D^-1 and the backward substitution.  2, the
+// FORWARD-INVERSE form: there is no backward pass.  x = L^-T w, w = D^-1 z, is x_j = sum_{m >= j} Y(m,j)^T w_m with Y = L^-1,
+// and Y is the forward substitution of the identity — what the right-hand-side workgroup does for one column, done for the 32
+// columns of block j by COLUMN WORKER j (role n_roles + j), behind the factorisation like the right-hand side and with its flags:
+//   R(j) = I, R(jb) = 0 below (LDS);  for m = j, j+1, ...:  F[m] up -> Y(m,j) = (Lmm^-T)^T R(m);  XF[jb][m] up -> R(jb) -=
+//   L(jb,m) Y(m,j) for the in-band rows below;  WF[m] up (the right-hand side has published w_m: d.bw_scratch) -> x_j += Y(m,j)^T w_m,
+//   eight partial sums per column in registers, block rows in ascending order, added in a fixed tree at the end: the same bits
+//   on every rank.  After the last block: x_j -> d.da, flag XD[j].
+// The right-hand-side workgroup waits for the XD flags, takes da back into LDS and finishes as form 1 does.  What follows the
+// chain's last flag is z_last, one hop, a 32x32 product and mat-vec in every column worker at once, one hop, the poses.
 __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a0, ChainArgs a1, int clubs, int cur, int do_bw) {
     const int club = ((int)(blockIdx.x & 7) - d.chain_xcd) & 7;   // (the bundle's XCD takes chain 0, the next one chain 1)
     if (club >= clubs) return;   // (only one or two of every eight blocks work: one XCD per chain, see above)
@@ -142,13 +167,17 @@ __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a
     ChainLds& s = *(ChainLds*)ch_lds;
     const int band = se_band(d), nblk = d.npad / NB;
     const int n_roles = ch_roles(kr - k0);
-    if (role >= n_roles) return;
+    const int n_col = do_bw == 2 ? kr - k0 : 0;   // column workers (forward-inverse form: k0 = 0, kr = nblk)
+    if (role >= n_roles + n_col) return;
     const unsigned seq = d.solve_seq;
     unsigned* const err = d.sflags;   // (one error word for the launch: the first chain's)
     unsigned* const F = a.flags + 1;
     unsigned* const RF = F + nblk;
     unsigned* const XCC = RF + nblk;
     unsigned* const XFb = XCC + nblk + 1;
+    unsigned* const WF = XFb + (size_t)nblk * (band + 1);
+    unsigned* const XD = WF + nblk;
+    unsigned* const XCC2 = XD + nblk;
     auto XF = [&](int r, int m) { return XFb + (size_t)r * (band + 1) + (m - max(0, r - band)); };
     double* __restrict__ S = a.S;
     double* __restrict__ E = a.E;
@@ -160,7 +189,7 @@ __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a
     const int colq = 16 * qj + i16;   // my column of an accumulator quadrant (its rows: 16 qi + m4 + 4 v)
     // where am I: HW_REG_XCC_ID (hwreg 20, bits 3:0), recorded with the solve's sequence number
     const unsigned my_xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 0xf;
-    if (tid == 0) __hip_atomic_store(XCC + role, (seq << 4) | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) __hip_atomic_store(role < n_roles ? XCC + role : XCC2 + (role - n_roles), (seq << 4) | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // a 32x32x32 product on the matrix cores, quadrant (qi, qj):  sum_k A[16 qi + i][k] * Bt[16 qj + j][k]
     //   A operand lane (i, m) = A[16 qi + i][4 kk + m], B operand lane (j, m) = Bt[16 qj + j][4 kk + m]
     auto mma_t = [&](const double* A, const double (&bt)[NB / 4]) {
@@ -250,7 +279,7 @@ __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a
                 // microsecond, this is 4 us later); one that has not counts as "elsewhere".  ONE wave looks, all follow.
                 if (w == 0) {   // (lane i looks at role i's word: one round trip, not one per role)
                     bool same = true;
-                    for (int i = lane; i < n_roles; i += 64) same = same && ch_flag(XCC + i) == ((seq << 4) | my_xcc);
+                    for (int i = lane; i < n_roles + n_col; i += 64) same = same && ch_flag(i < n_roles ? XCC + i : XCC2 + (i - n_roles)) == ((seq << 4) | my_xcc);
                     const bool all_same = __builtin_amdgcn_ballot_w64(!same) == 0;
                     if (lane == 0) s.one_xcd = all_same;
                 }
@@ -273,7 +302,10 @@ __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a
                 store_diag();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
-                if (tid == 0) ch_raise(F + k, seq, one_xcd);
+                if (tid == 0) {
+                    ch_raise(F + k, seq, one_xcd);
+                    CH_RT(200)
+                }
                 break;
             }
             // ---- block row k+1: its last step is mine ----
@@ -375,7 +407,10 @@ __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a
         const int q = tid & (NB - 1), part = tid >> 5;   // z: column q of Lmm^-T, its rows part + 8 j
         const int row = tid >> 3, g = tid & 7;           // updates: row of a tile, its columns g + 8 jj
         for (int m = k0; m < k1; m++) {
-            if (lane == 0) (void)ch_wait(F + m, seq, err, d.spin_limit);
+            unsigned fv = 0;
+            if (lane == 0) fv = ch_wait(F + m, seq, err, d.spin_limit);
+            const bool one_xcd = (__builtin_amdgcn_readfirstlane(fv) & 1u) != 0;
+            if (tid == 0 && m == k1 - 1) { CH_RT(201) }
             const size_t o_mm = se_blk(m, m, band);
             double t4[NB / 8];
 #pragma unroll
@@ -389,8 +424,16 @@ __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a
                 const double z = ((s.zp[0][tid] + s.zp[1][tid]) + (s.zp[2][tid] + s.zp[3][tid])) +
                                  ((s.zp[4][tid] + s.zp[5][tid]) + (s.zp[6][tid] + s.zp[7][tid]));
                 s.z[tid] = z;
-                a.y[m * NB + tid] = z;   // (read by the next kernel)
-                if (do_bw) bb[m * NB - b0 + tid] = z / ch_ld(a.Dg + m * NB + tid);   // (b_m was consumed above: its place takes w_m = D^-1 z_m)
+                if (do_bw != 2) a.y[m * NB + tid] = z;   // (read by the next kernel; the forward-inverse form has none that reads it)
+                if (do_bw == 1) bb[m * NB - b0 + tid] = z / ch_ld(a.Dg + m * NB + tid);   // (b_m was consumed above: its place takes w_m = D^-1 z_m)
+                if (do_bw == 2) ch_st(d.bw_scratch + m * NB + tid, z / ch_ld(a.Dg + m * NB + tid), one_xcd);   // (w_m for the column workers)
+            }
+            if (do_bw == 2 && w == 0) {   // (wave 0 stored w_m: its own wait orders the flag behind it)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0) {
+                    ch_raise(WF + m, seq, one_xcd);
+                    if (m == k1 - 1) { CH_RT(202) }
+                }
             }
             __syncthreads();
             double zr[NB / 8];
@@ -427,6 +470,59 @@ __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a
         }
         for (int i = k1 * NB + tid; i < kr * NB; i += TPB) E[i] = bb[i - b0];   // (the rows below my columns: their right-hand side as it stands)
         if (!do_bw) return;
+        // the trial poses exp(da_j) * se3CfW (src/Bundle.cc:496-501), |da|^2 — as ldlt_backward_kernel leaves them (xs: da in LDS)
+        auto finish = [&](const double* xs, int nrow) {
+            for (int c2 = tid; c2 < d.C; c2 += TPB) {
+                const int f = d.cam_free[c2];
+                const double* T = d.pose[cur] + 12 * c2;
+                double* Tn = d.pose[cur ^ 1] + 12 * c2;
+                double Tl[12], o[12];
+#pragma unroll
+                for (int i = 0; i < 12; i++) Tl[i] = T[i];
+                if (f < 0) {
+#pragma unroll
+                    for (int i = 0; i < 12; i++) Tn[i] = Tl[i];
+                } else {
+                    double mu[6];
+#pragma unroll
+                    for (int i = 0; i < 6; i++) mu[i] = xs[6 * f + i];
+                    se3_exp_mul(mu, Tl, o);
+#pragma unroll
+                    for (int i = 0; i < 12; i++) Tn[i] = o[i];
+                }
+            }
+#ifdef K7_TIMING
+            if (tid == 0) d.dbg[1398] = (long long)__builtin_readcyclecounter();
+#endif
+            if (tid < 64) {
+                double sq = 0;
+                for (int i = tid; i < min(nrow, d.n); i += 64) sq += xs[i] * xs[i];
+                sq = wave_sum_f64(sq);
+                if (tid == 0) {
+                    d.sumsq2[0] = sq;
+                    d.sumsq2[1] = 0.0;
+                    // a wait of THIS solve gave up somewhere (every wait that could still give up has been passed by now): the solve is
+                    // void, the host repeats the trial with the launch-per-block-column form; the word is taken down again
+                    if (ch_flag(err) != 0) {
+                        d.sc->solve_fault = 1;
+                        __hip_atomic_store(err, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+            }
+        };
+        if (do_bw == 2) {
+            // ================================ ... forward-inverse form: the column workers have x ================================
+            // one look at all their flags per round trip, then da comes back through the L2 they stored to
+            const int nrow = kr * NB;
+            double* const xs = bb + nrow;
+            ch_wait_lanes(XD + min(lane, kr - 1), lane < kr, seq, err, d.spin_limit);
+            if (tid == 0) { CH_RT(207) }
+            for (int i = tid; i < nrow; i += TPB) xs[i] = ch_ld(d.da + i);
+            __syncthreads();
+            finish(xs, nrow);
+            if (tid == 0) { CH_RT(208) }
+            return;
+        }
         // ================================ ... and backwards ================================
         // L^T x = w, block by block from the last, right-looking (solve.hip: ldlt_backward_kernel is the stand-alone form): per
         // block k  x_k = Lkk^-T (w_k - pending_k), then pending_m += L(k, m)^T x_k for the in-band blocks m < k.  Everything this
@@ -550,44 +646,115 @@ __global__ void __launch_bounds__(TPB, 2) ldlt_chain_kernel(BaDev d, ChainArgs a
                 __syncthreads();   // the pending sums of block k - 1 are complete
             }
             __syncthreads();
-            // da, the trial poses exp(da_j) * se3CfW (src/Bundle.cc:496-501), |da|^2 — as ldlt_backward_kernel leaves them
             for (int i = tid; i < nrow; i += TPB) d.da[i] = xs[i];
-            for (int c2 = tid; c2 < d.C; c2 += TPB) {
-                const int f = d.cam_free[c2];
-                const double* T = d.pose[cur] + 12 * c2;
-                double* Tn = d.pose[cur ^ 1] + 12 * c2;
-                double Tl[12], o[12];
+            finish(xs, nrow);
+        }
+        return;
+    }
+    if (role >= n_roles) {
+        // ================================ column worker (forward-inverse form) ================================
+        const int j = role - n_roles;   // my block column: the 32 columns of L^-1 below and including block j
+        double* const Rt = ch_lds + (sizeof(ChainLds) + 7) / 8;   // R(jb), jb = j .. kr-1: tile jb - j
+        for (int e = tid; e < (kr - j) * CH_TS; e += TPB) Rt[e] = 0.0;
+        __syncthreads();
+        if (tid < NB) Rt[tid * LDP + tid] = 1.0;
+        __syncthreads();
+        const int c32 = tid & (NB - 1), part = tid >> 5;   // x_j: column c32 of Y(m,j), its rows part + 8 jj
+        double xp = 0;
+        bool one_xcd = false;
+        for (int m = j; m < kr; m++) {
+            unsigned fv = 0;
+            if (lane == 0) fv = ch_wait(F + m, seq, err, d.spin_limit);
+            one_xcd = (__builtin_amdgcn_readfirstlane(fv) & 1u) != 0;
+            if (tid == 0 && j == 0 && m == kr - 1) { CH_RT(203) }
+            // Y(m,j) = Lmm^-1 R(m): the stored Lmm^-T transposed as the A operand, straight from memory (16 doubles of 4 rows per request)
+            {
+                const double* Tm = Lf + se_blk(m, m, band) + m4 * NB + 16 * qi + i16;
+                const double* Rm = Rt + (m - j) * CH_TS + m4 * LDP + colq;
+                double a8[NB / 4], b8[NB / 4];
 #pragma unroll
-                for (int i = 0; i < 12; i++) Tl[i] = T[i];
-                if (f < 0) {
+                for (int kk = 0; kk < NB / 4; kk++) a8[kk] = ch_ld(Tm + 4 * kk * NB);
 #pragma unroll
-                    for (int i = 0; i < 12; i++) Tn[i] = Tl[i];
-                } else {
-                    double mu[6];
+                for (int kk = 0; kk < NB / 4; kk++) b8[kk] = Rm[4 * kk * LDP];
+                v4f64 y = {0, 0, 0, 0};
 #pragma unroll
-                    for (int i = 0; i < 6; i++) mu[i] = xs[6 * f + i];
-                    se3_exp_mul(mu, Tl, o);
+                for (int kk = 0; kk < NB / 4; kk++) y = __builtin_amdgcn_mfma_f64_16x16x4f64(a8[kk], b8[kk], y, 0, 0, 0);
 #pragma unroll
-                    for (int i = 0; i < 12; i++) Tn[i] = o[i];
+                for (int v = 0; v < 4; v++) s.T2[(16 * qi + m4 + 4 * v) * LDP + colq] = y[v];
+            }
+            __syncthreads();   // (Y(m,j) is in T2)
+            if (tid == 0 && j == 0 && m == kr - 1) { CH_RT(204) }
+            // R(jb) -= L(jb,m) Y(m,j) for the in-band rows below: all their flags in one look per round trip, the tiles COALESCED and
+            // through LDS, three per round, the next round's loads in flight under this round's products (as a row worker does)
+            const int jhi = min(kr - 1, m + band);
+            if (jhi > m) {
+                {
+                    const int jw = m + 1 + lane;   // lane u looks at row m+1+u's flag
+                    ch_wait_lanes(XF(min(jw, jhi), m), jw <= jhi, seq, err, d.spin_limit);
+                }
+                double bt[NB / 4];   // B operand: Bt[c][k] = Y[k][c]
+#pragma unroll
+                for (int kk = 0; kk < NB / 4; kk++) bt[kk] = s.T2[(4 * kk + m4) * LDP + colq];
+                constexpr int RT = 3;
+                double* const stage[RT] = {s.T0, s.T3, s.T4};
+                auto issue = [&](int jb, double (&pr)[RT][NB * NB / TPB]) {
+#pragma unroll
+                    for (int u = 0; u < RT; u++)
+                        if (jb + u <= jhi) {
+                            const double* src = Lf + se_blk(jb + u, m, band) + tid;
+#pragma unroll
+                            for (int i = 0; i < NB * NB / TPB; i++) pr[u][i] = ch_ld(src + TPB * i);
+                        }
+                };
+                auto round = [&](int jb, const double (&now)[RT][NB * NB / TPB], double (&nxt)[RT][NB * NB / TPB]) {
+                    if (jb + RT <= jhi) issue(jb + RT, nxt);
+#pragma unroll
+                    for (int u = 0; u < RT; u++)
+                        if (jb + u <= jhi) {
+#pragma unroll
+                            for (int i = 0; i < NB * NB / TPB; i++) {
+                                const int e = tid + TPB * i;
+                                stage[u][(e / NB) * LDP + e % NB] = now[u][i];
+                            }
+                        }
+                    __syncthreads();
+#pragma unroll
+                    for (int u = 0; u < RT; u++)
+                        if (jb + u <= jhi) {
+                            const v4f64 upd = mma_t(stage[u], bt);
+                            double* rj = Rt + (jb + u - j) * CH_TS + (16 * qi + m4) * LDP + colq;
+#pragma unroll
+                            for (int v = 0; v < 4; v++) rj[4 * v * LDP] -= upd[v];
+                        }
+                    __syncthreads();   // (the stage is rewritten by the next round; R(m+1) is complete for the next step)
+                };
+                double pa[RT][NB * NB / TPB], pb[RT][NB * NB / TPB];   // (ping-pong)
+                issue(m + 1, pa);
+                for (int jb = m + 1; jb <= jhi; jb += 2 * RT) {
+                    round(jb, pa, pb);
+                    if (jb + RT <= jhi) round(jb + RT, pb, pa);
                 }
             }
-#ifdef K7_TIMING
-            if (tid == 0) d.dbg[1398] = (long long)__builtin_readcyclecounter();
-#endif
-            if (tid < 64) {
-                double sq = 0;
-                for (int i = tid; i < min(nrow, d.n); i += 64) sq += xs[i] * xs[i];
-                sq = wave_sum_f64(sq);
-                if (tid == 0) {
-                    d.sumsq2[0] = sq;
-                    d.sumsq2[1] = 0.0;
-                    // a wait of THIS solve gave up somewhere (every wait that could still give up has been passed by now): the solve is
-                    // void, the host repeats the trial with the launch-per-block-column form; the word is taken down again
-                    if (ch_flag(err) != 0) {
-                        d.sc->solve_fault = 1;
-                        __hip_atomic_store(err, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
+            // x_j += Y(m,j)^T w_m
+            if (lane == 0) (void)ch_wait(WF + m, seq, err, d.spin_limit);
+            if (tid == 0 && j == 0 && m == kr - 1) { CH_RT(205) }
+            double wv[NB / 8];
+#pragma unroll
+            for (int jj = 0; jj < NB / 8; jj++) wv[jj] = ch_ld(d.bw_scratch + m * NB + part + 8 * jj);
+#pragma unroll
+            for (int jj = 0; jj < NB / 8; jj++) xp += s.T2[(part + 8 * jj) * LDP + c32] * wv[jj];
+            __syncthreads();   // (T2 is rewritten by the next step)
+        }
+        s.zp[part][c32] = xp;
+        __syncthreads();
+        if (w == 0) {
+            if (tid < NB)
+                ch_st(d.da + j * NB + tid,
+                      ((s.zp[0][tid] + s.zp[1][tid]) + (s.zp[2][tid] + s.zp[3][tid])) + ((s.zp[4][tid] + s.zp[5][tid]) + (s.zp[6][tid] + s.zp[7][tid])), one_xcd);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (wave 0 stored x_j: its own wait orders the flag behind it)
+            if (lane == 0) {
+                ch_raise(XD + j, seq, one_xcd);
+                if (j == 0) { CH_RT(206) }
             }
         }
         return;

@@ -4,12 +4,16 @@
 // Blocked LDL^T, block size 32, in the block band of S.  Which form runs (ba_solve, bottom of this file):
 //   1 - 2 block rows                 ldlt_small_kernel: everything in one workgroup (ldlt_small.inc);
 //   3 .. 13 dense, <= 28 banded      ONE persistent launch: a chain workgroup through the pivot blocks, a workgroup per block
-//                                    row, one for the right-hand side, hand-offs by flags on one XCD (ldlt_chain.inc);
+//                                    row, one for the right-hand side, hand-offs by flags on one XCD (ldlt_chain.inc); up to
+//                                    13 block rows also a workgroup per block COLUMN that carries its columns of L^-1 down
+//                                    the factorisation, so that x = L^-T D^-1 z is a sum of products and no backward pass
+//                                    follows (the forward-inverse form; PTAM_LDLT_BACKWARD_IN_LAUNCH=1: the backward
+//                                    substitution in the right-hand-side workgroup instead, up to 10 block rows);
 //   banded, nblk >= 2 band + 8       eliminated from BOTH ends: two such chains in one launch (the upward one on a mirrored
 //                                    copy of the bottom end, on a second XCD), then the middle part as a third;
 //   anything else (and A/B runs)     one launch per block column — the form described next (ldlt_step_body.inc; for a
 //                                    two-ended elimination one launch per step of both chains, ldlt_step_twin_kernel);
-// then ldlt_backward_kernel: D^-1 and the backward substitution, trial poses, |da|^2.
+// then — where the launch has not done it itself — ldlt_backward_kernel: D^-1 and the backward substitution, trial poses, |da|^2.
 //
 // The launch-per-block-column form: right-looking, ONE launch per block column k.  Every workgroup of
 // step k re-factors the 32x32 diagonal block (cheap; avoids an extra launch + hand-off) and, in the
@@ -318,6 +322,16 @@ static int ldlt_twist_len(int nblk, int band) {
     return (nblk - 2 * band) / 2;
 }
 
+// does a system of nblk block rows and this band take the forward-inverse form (ldlt_chain.inc, column workers)?  ONE chain over
+// the whole system, a column worker's tiles fit its LDS, twice the workgroups fit one XCD.  PTAM_LDLT_BACKWARD_IN_LAUNCH=1: the
+// backward pass in the right-hand-side workgroup as before; PTAM_LDLT_SEPARATE_BACKWARD=1: ldlt_backward_kernel behind the launch
+// (A/B runs and tests/test_gpu_solve_forward_inverse.py, which compares the forms on the product library: hence getenv)
+static bool ldlt_forward_inverse(int nblk, int band) {
+    static const bool off = getenv("PTAM_LDLT_BACKWARD_IN_LAUNCH") != nullptr || getenv("PTAM_LDLT_SEPARATE_BACKWARD") != nullptr ||
+                            getenv("PTAM_LDLT_NO_CHAIN") != nullptr;
+    return !off && ldlt_twist_len(nblk, band) == 0 && nblk > SM_USE_NB && nblk <= CH_FI_MAX_NB && ch_lds_bytes_fi(band, nblk) <= CH_LDS_MAX;
+}
+
 size_t ba_solve_flag_bytes(int nblk) { return ch_flag_words(nblk, nblk) * sizeof(unsigned); }
 
 static ChainArgs chain_args_natural(const BaDev& d, int k0, int k1, int kr) {
@@ -351,15 +365,17 @@ int ba_solve(ptam_ctx* ctx, BaDev& d, int cur) {
         // (measured, tools/ldlt, us per solve inside / behind the launch: 28.8 / 29.7 at 4 block rows, 47.4 / 47.9 at 7, 69.0 / 68.4 at 10 — one
         //  compute unit fetches a tile from the L2 in ~200 cycles, 34 B per cycle, whoever asks; so only where the rows are short)
         const bool bw_in = !sep_bw && band <= CH_BW_MAXT && ch_lds_bytes_bw(band, nblk) <= CH_LDS_MAX;
-        const size_t lds = bw_in ? ch_lds_bytes_bw(band, nblk) : ch_lds_bytes(band);
+        const bool fwd_inv = ldlt_forward_inverse(nblk, band);
+        const int do_bw = fwd_inv ? 2 : bw_in ? 1 : 0;
+        const size_t lds = fwd_inv ? ch_lds_bytes_fi(band, nblk) : bw_in ? ch_lds_bytes_bw(band, nblk) : ch_lds_bytes(band);
         if (t_end == 0 && !no_chain && !d.chain_off && d.sflags && nblk <= CH_MAX_NB && lds <= CH_LDS_MAX) {
             d.solve_seq++;
             if (d.solve_seq >= (1u << 27)) d.solve_seq = 1;   // (flags carry it shifted by up to 4 bits; flags of 2^27 solves ago are no concern)
             {
                 const ChainArgs a = chain_args_natural(d, 0, nblk, nblk);
-                hipLaunchKernelGGL(ldlt_chain_kernel, dim3(8 * ch_roles(nblk)), dim3(TPB), lds, ctx->stream, d, a, a, 1, cur, bw_in ? 1 : 0);
+                hipLaunchKernelGGL(ldlt_chain_kernel, dim3(8 * (fwd_inv ? ch_roles_fi(nblk) : ch_roles(nblk))), dim3(TPB), lds, ctx->stream, d, a, a, 1, cur, do_bw);
             }
-            if (!bw_in) {
+            if (!do_bw) {
                 const size_t bw = (size_t)6 * d.npad * sizeof(double);
                 hipLaunchKernelGGL(ldlt_backward_kernel<false>, dim3(1), dim3(1024), bw, ctx->stream, d, cur, nblk);
             }

@@ -1,5 +1,7 @@
 // tools/ldlt/ldlt_bench.hip — the camera solve (csrc/solve.hip) alone, on a synthetic banded SPD system:
 //   ldlt_bench [free cameras = 49] [band (blocks) = all] [repetitions = 200]
+// (the forms are chosen by ba_solve and its switches: up to 13 block rows the forward-inverse form, PTAM_LDLT_BACKWARD_IN_LAUNCH=1
+//  the backward pass inside the launch, PTAM_LDLT_SEPARATE_BACKWARD=1 ldlt_backward_kernel behind it)
 // Builds S = G G^T + n I inside the block band (lower triangle, block-banded storage of csrc/bundle.h), a right-hand
 // side, runs ba_solve() `repetitions` times (S | E restored from a master copy before each), checks da against a host
 // LDL^T of the same system and prints the average wall time per solve (events around the whole loop, copies included — use
@@ -129,8 +131,11 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(&sc, d.sc, sizeof sc, hipMemcpyDeviceToHost));
         if (sc.solve_fault) printf("SOLVE FAULT: a wait of the persistent form gave up\n");
     }
-    printf("F %d n %d nblk %d band %d: %.2f us per solve (copy included), max |da - ref| = %.3e (|ref| max %.3e) %s\n", F, n, nblk, band,
-           1e3 * best / reps, err, nrm, err <= 1e-11 * nrm + 1e-300 ? "OK" : "MISMATCH");
+    // (what ba_solve chose, by its own predicate; the other labels only name the switch that was set)
+    const char* const form = ldlt_forward_inverse(nblk, band) ? " [forward inverse]" : nblk <= SM_USE_NB || getenv("PTAM_LDLT_NO_CHAIN") ? "" :
+                             getenv("PTAM_LDLT_SEPARATE_BACKWARD") ? " [separate backward]" : getenv("PTAM_LDLT_BACKWARD_IN_LAUNCH") ? " [backward in launch]" : "";
+    printf("F %d n %d nblk %d band %d%s: %.2f us per solve (copy included), max |da - ref| = %.3e (|ref| max %.3e) %s\n", F, n, nblk, band,
+           form, 1e3 * best / reps, err, nrm, err <= 1e-11 * nrm + 1e-300 ? "OK" : "MISMATCH");
 #ifdef K7_TIMING
     if (!getenv("PTAM_LDLT_NO_CHAIN") && nblk > SM_USE_NB) {
         std::vector<long long> st(512);
@@ -179,6 +184,18 @@ int main(int argc, char** argv) {
         printf("stamps (cycles between consecutive ones):");
         for (int i = 1; i < 400 && st[32 + i]; i++) printf(" %lld", st[32 + i] - st[31 + i]);
         printf("\n");
+    }
+#endif
+#ifdef K7_TIMING
+    if (ldlt_forward_inverse(nblk, band)) {
+        // the forward-inverse form's tail: what follows the chain's last flag (10 ns units since F[last] went up)
+        std::vector<long long> rt(9);
+        CK(hipMemcpy(rt.data(), dbg + 800, rt.size() * 8, hipMemcpyDeviceToHost));
+        static const char* const what[9] = {"chain: F[last] raised", "right-hand side: saw F[last]", "right-hand side: w_last published", "column worker 0: saw F[last]",
+                                            "column worker 0: Y(last, 0) in LDS", "column worker 0: saw w_last", "column worker 0: x_0 stored, flag up",
+                                            "right-hand side: every x_j flag seen", "right-hand side: poses, |da|^2 written"};
+        printf("forward-inverse form, tail (10 ns units since the chain's last flag):\n");
+        for (int i = 0; i < 9; i++) printf("  %-45s %6lld\n", what[i], rt[i] - rt[0]);
     }
 #endif
 #ifdef K7_TIMING
