@@ -102,7 +102,7 @@ int ptam_kf_level_info(ptam_ctx* ctx, const ptam_kf* kf, int level, int* w, int*
 int ptam_kf_read_level(ptam_ctx* ctx, const ptam_kf* kf, int level,
                        uint8_t* px, ptam_int2* corners, int32_t* rowlut);
 
-/* ---- KeyFrame::MakeKeyFrame_Rest (src/KeyFrame.cc:61-82) minus the SmallBlurryImage: libCVD fast_nonmax
+/* ---- KeyFrame::MakeKeyFrame_Rest (src/KeyFrame.cc:61-79; its SmallBlurryImage, :80-81, is ptam_sbi_bank_add): libCVD fast_nonmax
  *      (score = largest threshold >= 10 at which the corner survives; kept iff no 8-neighbour corner
  *      scores strictly higher) and ImageProcess::ShiTomasiScoreAtPoint (src/ImageProcess.cc:20-47) on
  *      the maximal corners that lie >= 10 pixels inside the level.   */
@@ -626,9 +626,9 @@ int ptam_track_map_frame(ptam_tracker* t, ptam_kf* current, const uint8_t* d_fra
                          const ptam_trackmap_opts* opts, ptam_trackmap_result* out);
 /* ---- the tracker's motion model and Tracker::TrackFrame's tracking branch (src/Tracker.cc:134-137) ----------------------
  *      Host scalar code (no device work of its own): the decaying constant-velocity model of :1008-1056 and the bTryCoarse
- *      heuristics of :505-516, kept in a plain struct the caller owns.  The SmallBlurryImage rotation estimator
- *      (Tracker.UseRotationEstimator, :1017-1028) is outside this path (SmallBlurryImage is out of scope);
- *      this is the model with it switched off — the velocity comes from the last two tracked poses alone. */
+ *      heuristics of :505-516, kept in a plain struct the caller owns.  ptam_motion_predict / ptam_track_frame are the model with
+ *      the SmallBlurryImage rotation estimator (Tracker.UseRotationEstimator, :1017-1028) switched off — the velocity comes from
+ *      the last two tracked poses alone; ptam_motion_predict_sbi / ptam_track_frame_sbi below are the model with it on. */
 typedef struct {
     double pose[12];               /* mse3CamFromWorld */
     double start_pose[12];         /* mse3StartPos: the pose before the prediction, :1015 */
@@ -659,6 +659,102 @@ void ptam_se3_ln(const double pose[12], double mu_out[6]);
  * model is advanced on a copy and committed on success): the frame can be retried. */
 int ptam_track_frame(ptam_tracker* t, ptam_kf* current, const uint8_t* d_frame, ptam_motion_model* m,
                      const ptam_trackmap_opts* opts, ptam_trackmap_result* out);
+
+/* ---- SmallBlurryImage (src/ImageProcess.cc:255-495), Relocaliser (src/Relocaliser.cc:12-38) and the tracker's rotation
+ *      estimator (src/Tracker.cc:94-108, :1016-1028) ----------------------------------------------------------------------
+ *      An SBI is halfSample(aLevels[3].im) — (level-3 size) / 2 by integer division, 40x30 for a 640x480 frame —, its mean
+ *      (exact unsigned sum, float division), the float template `small - mean` blurred by convolveGaussian, and the central
+ *      differences (r - l, d - u) of the template without the 0.5, zero on the one-pixel border.  The Jacobians are always made:
+ *      there is no mbMadeJacs to forget.  Limits: at most 4096 pixels and 256 a side (PTAM_E_LIMIT), at least 3x3.
+ *      Three libCVD rules are restated here as the project's own and are UNPINNED (libCVD is not vendored by the reference and
+ *      no build of it has confirmed them):
+ *        halfSample        the context's variant (ptam_ctx_set_halfsample), the pyramid's routine;
+ *        transform/sample  as in ptam_make_templates_batch: p0 = inOrig - M * outOrig, then `across` added per pixel and the carriage
+ *                          return per row by repeated fp64 addition; a sample is inside iff 0 <= p.x, 0 <= p.y, p.x < w - 1,
+ *                          p.y < h - 1 (or the whole image's bounding box is); the bilinear blend in fp64, rounded once to float32
+ *                          (not truncated to a byte); outside: the default value -9e20f;
+ *        convolveGaussian  k = ceil(3 sigma) taps each side, weights exp(-i^2 / 2 sigma^2) normalised to sum 1 in fp64 on the host;
+ *                          a row pass then a column pass, fp64 between them, taps in ascending order; pixels outside the image
+ *                          count as 0, nothing is renormalised at the border; rounded once to float32.  0 < sigma <= 5, else
+ *                          PTAM_E_ARG.
+ *      Sums over pixels are reduced in a fixed order: two calls on the same input give the same bits. */
+typedef struct ptam_sbi ptam_sbi;   /* one SmallBlurryImage, device-resident */
+int ptam_sbi_create(ptam_ctx* ctx, int frame_w, int frame_h, ptam_sbi** out);
+int ptam_sbi_destroy(ptam_sbi* s);
+/* SmallBlurryImage::MakeFromKF (:279-304) + MakeJacs (:170-191) from kf's level 3; one launch, asynchronous.  blur: 2.5 for
+ * keyframes and the relocaliser (include/ImageProcess.h:57-58), Tracker.RotationEstimatorBlur = 0.75 for the per-frame pair.
+ * PTAM_E_ARG: a keyframe of another device or frame size.  The kernel reads the keyframe's level 3 on THIS object's context's queue: a
+ * keyframe made on another context's queue must be synchronised by the caller first (ptam_ctx_sync of that context); the same holds
+ * for ptam_sbi_bank_add, ptam_sbi_bank_add_batch and ptam_relocalise. */
+int ptam_sbi_make(ptam_sbi* s, const ptam_kf* kf, double blur);
+int ptam_sbi_size(const ptam_sbi* s, int* w, int* h);   /* mirSize */
+/* mimSmall (w*h bytes), mimTemplate (w*h floats), mimImageJacs (w*h x 2 floats: x, y per pixel); NULL pointers are skipped.
+ * PTAM_E_STATE before the first make. */
+int ptam_sbi_read(ptam_sbi* s, uint8_t* small, float* tmpl, float* jacs);
+
+typedef struct {
+    double se2_rot[4], se2_trans[2];   /* se2CtoC: rotation matrix row-major, translation */
+    double score, mean_offset;         /* dFinalScore: the LAST formed sums' sum of dDiff^2 (taken before that iteration's update); dMeanOffset */
+    double rotation[9];                /* SE3fromSE2(se2CtoC): the rotation, row-major (its translation is zero) */
+    int32_t iterations_done;           /* iterations whose update was applied */
+    int32_t n_used;                    /* pixels that entered the last formed sums */
+    int32_t degenerate, pad_;
+} ptam_sbi_alignment;
+/* SmallBlurryImage::CalcSBIRotation (:485-495) = IteratePosRelToTarget (:313-417; the reference passes 6 iterations) + SE3fromSE2
+ * (:427-476) with the context's camera at the SBI's size; one launch (all iterations, fp64 sums, the 4x4 Cholesky, the SE2 update),
+ * one wait for the result block in host-mapped memory.  1 <= iterations <= 64.
+ * Degenerate systems, which the reference divides by: when a pivot of the Cholesky is not strictly positive (a blank frame: all
+ * gradients zero; a warp that leaves no pixel inside) the iteration stops, the SE2 of the previous iteration stands and
+ * degenerate = 1; score and rotation are finite.  An SE2 that is exactly the identity gives exactly the identity rotation (the
+ * reference's three Gauss-Newton steps would leave the ~1e-17 of Project(UnProject(p)) - p in it).  A step that is not finite (the
+ * update, or the SE2 and mean offset it would give: a tiny positive pivot) ends the iteration in the same way, degenerate = 1. */
+int ptam_sbi_calc_rotation(ptam_sbi* current, const ptam_sbi* target, int iterations, ptam_sbi_alignment* out);
+
+/* The map's keyframe SBIs (KeyFrame::MakeKeyFrame_Rest, src/KeyFrame.cc:80-81: pSBI = new SmallBlurryImage(*this); pSBI->MakeJacs)
+ * side by side in device memory, in the order they were added = the order of Map::vpKeyFrames. */
+typedef struct ptam_sbi_bank ptam_sbi_bank;
+int ptam_sbi_bank_create(ptam_ctx* ctx, int frame_w, int frame_h, int capacity, ptam_sbi_bank** out);
+int ptam_sbi_bank_destroy(ptam_sbi_bank* b);
+/* one make launch into the next entry, asynchronous; *index (nullable): the entry.  PTAM_E_LIMIT: the bank is full. */
+int ptam_sbi_bank_add(ptam_sbi_bank* b, const ptam_kf* kf, double blur, int* index);
+/* n keyframes into the next n entries with ONE make launch (grid x = n), asynchronous; *first_index (nullable): the first entry.
+ * PTAM_E_LIMIT: fewer than n entries are free; nothing is added. */
+int ptam_sbi_bank_add_batch(ptam_sbi_bank* b, int n, const ptam_kf* const* kfs, double blur, int* first_index);
+int ptam_sbi_bank_count(const ptam_sbi_bank* b, int* n);
+typedef struct {
+    int32_t best, good;     /* mnBest; AttemptRecovery's return value: align.score < max_score */
+    double best_ssd;        /* mdBestScore */
+    double pose[12];        /* mse3Best = rotation * se3CfromW(best) */
+    ptam_sbi_alignment align;
+} ptam_reloc_result;
+/* Relocaliser::AttemptRecovery (src/Relocaliser.cc:12-38, called at src/Tracker.cc:171): the current keyframe's SBI into `scratch`
+ * (blur 2.5), SSDofImgs (src/ImageProcess.cc:88-105: difference in float, sum in double) against every entry — one workgroup each —,
+ * the first entry with the strictly lowest SSD, CalcSBIRotation against it, pose = rotation * kf_poses12[best].  The arg-min is taken
+ * at the start of the align launch: make, SSD and align launches, one wait.  kf_poses12: host, count x 12.  max_score:
+ * Reloc2.MaxScore, 9e6.  ssd_out (nullable): count doubles.  PTAM_E_STATE: an empty bank. */
+int ptam_relocalise(ptam_sbi_bank* b, ptam_sbi* scratch, const ptam_kf* current, const double* kf_poses12, double blur, double max_score,
+                    ptam_reloc_result* out, double* ssd_out);
+
+/* mpSBILastFrame / mpSBIThisFrame (src/Tracker.cc:94-108): two SBIs and which of them is last frame's */
+typedef struct ptam_rotation_estimator ptam_rotation_estimator;
+int ptam_rotation_estimator_create(ptam_ctx* ctx, int frame_w, int frame_h, double blur /* Tracker.RotationEstimatorBlur 0.75 */,
+                                   ptam_rotation_estimator** out);
+int ptam_rotation_estimator_destroy(ptam_rotation_estimator* e);
+/* the next frame is both "this" and "last" (:98-102): its rotation is the identity */
+int ptam_rotation_estimator_reset(ptam_rotation_estimator* e);
+/* Tracker::PredictPoseWithMotionModel (:1013-1029) with mbUseSBIInit: start_pose = pose; v = velocity with v[3..5] = ln(rotation),
+ * v[0] = v[1] = 0 (v[2] stays); pose = exp(v) * start_pose */
+void ptam_motion_predict_sbi(ptam_motion_model* m, const double rotation[9]);
+/* Tracker::AttemptRecovery (:196-207) after a good ptam_relocalise: pose = start_pose = the given pose, zero velocity, just_recovered */
+void ptam_motion_recover(ptam_motion_model* m, const double pose[12]);
+/* ptam_track_frame with the rotation estimator switched on, the reference's default (Tracker.UseRotationEstimator = 1, :96):
+ * ptam_make_keyframe_lite_dev of d_frame into `current`; this frame's SBI and its alignment against last frame's (two launches), one
+ * mapped wait for the rotation; ptam_motion_predict_sbi and the bTryCoarse heuristics on the host, as ptam_track_frame has them;
+ * ptam_track_map on the made keyframe; ptam_motion_update.  Two waits per frame instead of ptam_track_frame's one.  The model and the
+ * estimator's last / this pair are advanced on copies and committed only when the frame was tracked: a call that fails leaves both
+ * untouched.  align_out (nullable): the frame's alignment.  The estimator must belong to the tracker's context. */
+int ptam_track_frame_sbi(ptam_tracker* t, ptam_kf* current, const uint8_t* d_frame, ptam_motion_model* m, ptam_rotation_estimator* e,
+                         const ptam_trackmap_opts* opts, ptam_trackmap_result* out, ptam_sbi_alignment* align_out);
 
 /* nb frames of nb independent trackers (own context, map, keyframe, prediction each) as ONE chain of launches on the first
  * tracker's queue: every kernel of the chain gets a second grid dimension, row i works on frame i.  Not part of the

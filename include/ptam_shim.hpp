@@ -111,7 +111,7 @@ public:
         check(ptam_make_keyframe_lite(ctx_->handle(), h_, im, stride), "ptam_make_keyframe_lite");
         fetched_ = 0;
     }
-    // void MakeKeyFrame_Rest()   include/KeyFrame.h:142, src/KeyFrame.cc:61-82 (without the SmallBlurryImage)
+    // void MakeKeyFrame_Rest()   include/KeyFrame.h:142, src/KeyFrame.cc:61-79; the keyframe's SmallBlurryImage (:80-81) is Relocaliser::AddKeyFrame
     void MakeKeyFrame_Rest() { check(ptam_make_keyframe_rest(ctx_->handle(), h_), "ptam_make_keyframe_rest"); }
     // aLevels[l] host view (pixels, vCorners, vCornerRowLUT)
     const Level& aLevels(int l) {
@@ -629,6 +629,102 @@ private:
     void *res_ = nullptr, *meas_ = nullptr, *src_ = nullptr, *flags_ = nullptr, *count_ = nullptr, *pose_ = nullptr;
 };
 
+// class SmallBlurryImage (include/ImageProcess.h, src/ImageProcess.cc:255-495), device-resident.  The Jacobians are made with the
+// image (there is no MakeJacs to call); the camera is the Context's.
+class SmallBlurryImage {
+public:
+    explicit SmallBlurryImage(Context& c) { check(ptam_sbi_create(c.handle(), c.size().x, c.size().y, &h_), "ptam_sbi_create"); }
+    // SmallBlurryImage(KeyFrame &kf, double dBlur = 2.5)
+    SmallBlurryImage(Context& c, KeyFrame& kf, double dBlur = 2.5) : SmallBlurryImage(c) { MakeFromKF(kf, dBlur); }
+    ~SmallBlurryImage() { ptam_sbi_destroy(h_); }
+    SmallBlurryImage(const SmallBlurryImage&) = delete;
+    SmallBlurryImage& operator=(const SmallBlurryImage&) = delete;
+    // void MakeFromKF(KeyFrame &kf, double dBlur = 2.5)   src/ImageProcess.cc:279
+    void MakeFromKF(KeyFrame& kf, double dBlur = 2.5) { check(ptam_sbi_make(h_, kf.handle(), dBlur), "ptam_sbi_make"); }
+    // std::pair<SE3<>, double> CalcSBIRotation(SmallBlurryImage *pSBIRef, ATANCamera camera, int nIterations = 6)   :485
+    std::pair<SE3, double> CalcSBIRotation(SmallBlurryImage* pSBIRef, int nIterations = 6, ptam_sbi_alignment* pAlignment = nullptr) {
+        ptam_sbi_alignment a;
+        check(ptam_sbi_calc_rotation(h_, pSBIRef->h_, nIterations, &a), "ptam_sbi_calc_rotation");
+        if (pAlignment) *pAlignment = a;
+        SE3 r = SE3::Identity();
+        std::memcpy(r.R, a.rotation, sizeof r.R);
+        return {r, a.score};
+    }
+    ImageRef GetSize() const {   // mirSize
+        ImageRef s{0, 0};
+        check(ptam_sbi_size(h_, &s.x, &s.y), "ptam_sbi_size");
+        return s;
+    }
+    ptam_sbi* handle() const { return h_; }
+
+private:
+    ptam_sbi* h_ = nullptr;
+};
+
+// class Relocaliser (include/Relocaliser.h, src/Relocaliser.cc:12-38).  The reference walks Map::vpKeyFrames and their pSBI; here
+// the map's keyframes are handed over as they are made (AddKeyFrame = the pSBI lines of MakeKeyFrame_Rest, src/KeyFrame.cc:80-81).
+class Relocaliser {
+public:
+    Relocaliser(Context& c, int nMaxKeyFrames) : scratch_(c) {
+        check(ptam_sbi_bank_create(c.handle(), c.size().x, c.size().y, nMaxKeyFrames, &h_), "ptam_sbi_bank_create");
+    }
+    ~Relocaliser() { ptam_sbi_bank_destroy(h_); }
+    Relocaliser(const Relocaliser&) = delete;
+    Relocaliser& operator=(const Relocaliser&) = delete;
+    int AddKeyFrame(KeyFrame& k, double dBlur = 2.5) {   // k.se3CfromW is copied
+        int i = -1;
+        check(ptam_sbi_bank_add(h_, k.handle(), dBlur, &i), "ptam_sbi_bank_add");
+        double p[12];
+        k.se3CfromW.to12(p);
+        poses_.insert(poses_.end(), p, p + 12);
+        return i;
+    }
+    int AddKeyFrames(const std::vector<KeyFrame*>& vKeyFrames, double dBlur = 2.5) {   // a map handed over at once: one launch
+        std::vector<const ptam_kf*> h;
+        for (KeyFrame* k : vKeyFrames) h.push_back(k->handle());
+        int i = -1;
+        check(ptam_sbi_bank_add_batch(h_, (int)h.size(), h.data(), dBlur, &i), "ptam_sbi_bank_add_batch");
+        for (KeyFrame* k : vKeyFrames) {
+            double p[12];
+            k->se3CfromW.to12(p);
+            poses_.insert(poses_.end(), p, p + 12);
+        }
+        return i;
+    }
+    void SetKeyFramePose(int i, const SE3& se3CfromW) { se3CfromW.to12(&poses_[12 * (size_t)i]); }   // after a bundle adjustment
+    // bool AttemptRecovery(KeyFrame &k)   src/Relocaliser.cc:12; Reloc2.MaxScore = 9e6
+    bool AttemptRecovery(KeyFrame& kCurrent, double dMaxScore = 9e6, double dBlur = 2.5) {
+        check(ptam_relocalise(h_, scratch_.handle(), kCurrent.handle(), poses_.data(), dBlur, dMaxScore, &last_, nullptr), "ptam_relocalise");
+        return last_.good != 0;
+    }
+    SE3 BestPose() const { return SE3::from12(last_.pose); }   // mse3Best
+    int mnBest() const { return last_.best; }
+    double mdBestScore() const { return last_.best_ssd; }
+    const ptam_reloc_result& Last() const { return last_; }
+
+private:
+    SmallBlurryImage scratch_;
+    ptam_sbi_bank* h_ = nullptr;
+    std::vector<double> poses_;
+    ptam_reloc_result last_{};
+};
+
+// mpSBILastFrame / mpSBIThisFrame of the Tracker (src/Tracker.cc:94-108), for MapTracker::TrackFrame with the estimator
+class RotationEstimator {
+public:
+    explicit RotationEstimator(Context& c, double dBlur = 0.75) {   // Tracker.RotationEstimatorBlur
+        check(ptam_rotation_estimator_create(c.handle(), c.size().x, c.size().y, dBlur, &h_), "ptam_rotation_estimator_create");
+    }
+    ~RotationEstimator() { ptam_rotation_estimator_destroy(h_); }
+    RotationEstimator(const RotationEstimator&) = delete;
+    RotationEstimator& operator=(const RotationEstimator&) = delete;
+    void Reset() { check(ptam_rotation_estimator_reset(h_), "ptam_rotation_estimator_reset"); }   // Tracker::Reset
+    ptam_rotation_estimator* handle() const { return h_; }
+
+private:
+    ptam_rotation_estimator* h_ = nullptr;
+};
+
 // Tracker::TrackMap (src/Tracker.cc:442-696) as one device-resident chain: the map (world positions, pixel vectors, patch
 // sources) lives on the device between frames; a frame is one call that returns the refined pose, mbDidCoarse, the
 // per-level manMeasAttempted / manMeasFound counters and the scene-depth sums.  The caller keeps what is host logic in the
@@ -676,6 +772,15 @@ public:
     ptam_trackmap_result TrackFrame(KeyFrame& kfCurrent, const uint8_t* dFrame, ptam_motion_model& motion, const ptam_trackmap_opts* pOpts = nullptr) {
         ptam_trackmap_result r;
         check(ptam_track_frame(h_, kfCurrent.handle(), dFrame, &motion, pOpts, &r), "ptam_track_frame");
+        return r;
+    }
+    // The same with Tracker.UseRotationEstimator = 1, the reference's default (:94-108, :1016-1028): the prediction's rotation comes
+    // from the SmallBlurryImages of this frame and the last (ptam_track_frame_sbi).  After Relocaliser::AttemptRecovery succeeded:
+    // ptam_motion_recover(&motion, pose) (:196-207), then this.
+    ptam_trackmap_result TrackFrame(KeyFrame& kfCurrent, const uint8_t* dFrame, ptam_motion_model& motion, RotationEstimator& estimator,
+                                    const ptam_trackmap_opts* pOpts = nullptr, ptam_sbi_alignment* pAlignment = nullptr) {
+        ptam_trackmap_result r;
+        check(ptam_track_frame_sbi(h_, kfCurrent.handle(), dFrame, &motion, estimator.handle(), pOpts, &r, pAlignment), "ptam_track_frame_sbi");
         return r;
     }
     // Several cameras (or agents) on one device: ONE chain of launches for all their frames, results as the single calls give

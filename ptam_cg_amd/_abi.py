@@ -182,6 +182,18 @@ class SceneDepth(C.Structure):
     _fields_ = [("depth_mean", C.c_double), ("depth_sigma", C.c_double), ("n_meas", C.c_int32), ("pad_", C.c_int32)]
 
 
+class SbiAlignment(C.Structure):
+    """ptam_sbi_alignment (SmallBlurryImage::CalcSBIRotation, src/ImageProcess.cc:313-495)"""
+    _fields_ = [("se2_rot", C.c_double * 4), ("se2_trans", C.c_double * 2), ("score", C.c_double), ("mean_offset", C.c_double),
+                ("rotation", C.c_double * 9), ("iterations_done", C.c_int32), ("n_used", C.c_int32), ("degenerate", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class RelocResult(C.Structure):
+    """ptam_reloc_result (Relocaliser::AttemptRecovery, src/Relocaliser.cc:12-38)"""
+    _fields_ = [("best", C.c_int32), ("good", C.c_int32), ("best_ssd", C.c_double), ("pose", C.c_double * 12), ("align", SbiAlignment)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p)
 
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
@@ -286,6 +298,24 @@ PROTOTYPES = {
     "se3_exp": (None, [_vp, _vp]),
     "se3_ln": (None, [_vp, _vp]),
     "track_frame": (_i, [_vp, _vp, _vp, C.POINTER(MotionModel), _vp, _vp]),
+    "sbi_create": (_i, [_vp, _i, _i, _ppv]),
+    "sbi_destroy": (_i, [_vp]),
+    "sbi_make": (_i, [_vp, _vp, _d]),
+    "sbi_size": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "sbi_read": (_i, [_vp, _vp, _vp, _vp]),
+    "sbi_calc_rotation": (_i, [_vp, _vp, _i, C.POINTER(SbiAlignment)]),
+    "sbi_bank_create": (_i, [_vp, _i, _i, _i, _ppv]),
+    "sbi_bank_destroy": (_i, [_vp]),
+    "sbi_bank_add": (_i, [_vp, _vp, _d, C.POINTER(_i)]),
+    "sbi_bank_add_batch": (_i, [_vp, _i, _vp, _d, C.POINTER(_i)]),
+    "sbi_bank_count": (_i, [_vp, C.POINTER(_i)]),
+    "relocalise": (_i, [_vp, _vp, _vp, _vp, _d, _d, C.POINTER(RelocResult), _vp]),
+    "rotation_estimator_create": (_i, [_vp, _i, _i, _d, _ppv]),
+    "rotation_estimator_destroy": (_i, [_vp]),
+    "rotation_estimator_reset": (_i, [_vp]),
+    "motion_predict_sbi": (None, [C.POINTER(MotionModel), _pd]),
+    "motion_recover": (None, [C.POINTER(MotionModel), _pd]),
+    "track_frame_sbi": (_i, [_vp, _vp, _vp, C.POINTER(MotionModel), _vp, _vp, _vp, C.POINTER(SbiAlignment)]),
     "bench_track_sequence": (_i, [_vp, _vp, _i, _vp, C.POINTER(MotionModel), _vp, _vp, _vp, _i, _vp, _pd, _pd]),
     "tracker_set_profiling": (_i, [_vp, _i]),
     "tracker_stage_time": (_i, [_vp, _i, _pd, C.POINTER(_i)]),

@@ -264,6 +264,7 @@ int ptam_ctx_create(const ptam_cam_params* cam, int device, ptam_ctx** out) {
     mapalign_preload_kernels();
     kf_preload_kernels();
     pvs_preload_kernels();
+    sbi_preload_kernels();
     *out = c;
     return PTAM_OK;
 }

@@ -6,6 +6,8 @@
 #include <cstring>
 
 #include "common.h"
+#include "sbi.h"
+#include "track_internal.h"
 #include "../../include/ptam_hip_bench.h"
 
 namespace {
@@ -108,6 +110,26 @@ void ptam_motion_predict(ptam_motion_model* m) {
     se3_exp_mul<false>(m->velocity, m->start_pose, m->pose);
 }
 
+// src/Tracker.cc:1013-1029 with mbUseSBIInit
+void ptam_motion_predict_sbi(ptam_motion_model* m, const double rotation[9]) {
+    if (!m || !rotation) return;
+    std::memcpy(m->start_pose, m->pose, 96);
+    double v[6];
+    std::memcpy(v, m->velocity, sizeof v);
+    so3_ln(rotation, v + 3);   // SE3<>::ln of a pose without translation: (0, 0, 0, rotation vector)
+    v[0] = v[1] = 0.0;
+    se3_exp_mul<false>(v, m->start_pose, m->pose);
+}
+
+// src/Tracker.cc:196-207
+void ptam_motion_recover(ptam_motion_model* m, const double pose[12]) {
+    if (!m || !pose) return;
+    std::memcpy(m->pose, pose, 96);
+    std::memcpy(m->start_pose, pose, 96);
+    std::memset(m->velocity, 0, sizeof m->velocity);
+    m->just_recovered = 1;
+}
+
 void ptam_motion_update(ptam_motion_model* m, const ptam_trackmap_result* r) {
     if (!m || !r) return;
     std::memcpy(m->pose, r->pose, 96);
@@ -168,6 +190,38 @@ int ptam_track_frame(ptam_tracker* t, ptam_kf* current, const uint8_t* d_frame, 
     if (rc) return rc;
     ptam_motion_update(&tmp, out);
     *m = tmp;
+    return PTAM_OK;
+}
+
+int ptam_track_frame_sbi(ptam_tracker* t, ptam_kf* current, const uint8_t* d_frame, ptam_motion_model* m, ptam_rotation_estimator* e,
+                         const ptam_trackmap_opts* opts, ptam_trackmap_result* out, ptam_sbi_alignment* align_out) {
+    ARG_TRY(t && current && d_frame && m && e && out);
+    ARG_TRY(sbi_estimator_ctx(e) == tracker_ctx(t));
+    ptam_trackmap_opts o;
+    if (opts) o = *opts;
+    else ptam_trackmap_opts_default(&o);
+    // the heuristics and the copy of the model: as in ptam_track_frame
+    o.try_coarse = 1;
+    if (m->disable_coarse || m->msd_scaled_velocity < m->coarse_min_velocity || o.coarse_max == 0) o.try_coarse = 0;
+    ptam_motion_model tmp = *m;
+    if (tmp.just_recovered) {
+        o.try_coarse = 1;
+        o.coarse_max *= 2;
+        o.coarse_range *= 2;
+        tmp.just_recovered = 0;
+    }
+    int rc = ptam_make_keyframe_lite_dev(tracker_ctx(t), current, d_frame);
+    if (rc) return rc;
+    ptam_sbi_alignment al;
+    rc = sbi_estimator_step(e, current, &al);   // (the estimator's last / this pair moves at the commit below)
+    if (rc) return rc;
+    ptam_motion_predict_sbi(&tmp, al.rotation);
+    rc = ptam_track_map(t, current, tmp.pose, &o, out);
+    if (rc) return rc;
+    ptam_motion_update(&tmp, out);
+    *m = tmp;
+    sbi_estimator_commit(e);
+    if (align_out) *align_out = al;
     return PTAM_OK;
 }
 

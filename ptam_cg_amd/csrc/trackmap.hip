@@ -949,6 +949,8 @@ static void tm_read_result(const ptam_tracker* t, ptam_trackmap_result* out) {
     out->depth_n = (int)t->mbox->depth3[2];
 }
 
+ptam_ctx* tracker_ctx(const ptam_tracker* t) { return t->ctx; }
+
 extern "C" {
 
 void ptam_trackmap_opts_default(ptam_trackmap_opts* o) {

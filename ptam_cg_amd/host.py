@@ -783,6 +783,16 @@ class Tracker:
                         "track_frame")
         return res[0]
 
+    def track_frame_sbi(self, kf, d_frame, motion, estimator, opts=None):
+        """ptam_track_frame_sbi: TrackFrameMoving with the SmallBlurryImage rotation estimator on (the reference's default,
+        src/Tracker.cc:94-108, :1016-1028) -> (result, alignment dict).  `motion` and `estimator` advance only on success."""
+        res = np.zeros(1, dtype=TRACKMAP_RESULT_DT)
+        a = _abi.SbiAlignment()
+        dp = d_frame.p if isinstance(d_frame, DevBuf) else d_frame
+        self.ctx._check(self.lib.track_frame_sbi(self.h, kf.h, dp, C.byref(motion), estimator.h, _ptr(opts) if opts is not None else None,
+                                                 _ptr(res), C.byref(a)), "track_frame_sbi")
+        return res[0], _alignment(a)
+
     def set_profiling(self, on=True):
         self.ctx._check(self.lib.tracker_set_profiling(self.h, 1 if on else 0), "tracker_set_profiling")
 
@@ -838,6 +848,111 @@ class Tracker:
     def close(self):
         if getattr(self, "h", None):
             self.lib.tracker_destroy(self.h)
+            self.h = None
+
+
+def _alignment(a):
+    """ptam_sbi_alignment -> dict (R, t: se2CtoC; rotation (3, 3))"""
+    return dict(R=np.array(a.se2_rot).reshape(2, 2), t=np.array(a.se2_trans), score=a.score, mean_offset=a.mean_offset,
+                rotation=np.array(a.rotation).reshape(3, 3), iterations_done=a.iterations_done, n_used=a.n_used, degenerate=a.degenerate)
+
+
+class SmallBlurryImage:
+    """SmallBlurryImage (src/ImageProcess.cc:255-495) on the device: ptam_sbi_*"""
+
+    def __init__(self, ctx, size=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        fw, fh = size or ctx.size
+        self.h = C.c_void_p()
+        ctx._check(self.lib.sbi_create(ctx.h, int(fw), int(fh), C.byref(self.h)), "sbi_create")
+        w, h = C.c_int(), C.c_int()
+        ctx._check(self.lib.sbi_size(self.h, C.byref(w), C.byref(h)), "sbi_size")
+        self.size = (w.value, h.value)
+
+    def MakeFromKF(self, kf, blur=2.5):
+        """MakeFromKF + MakeJacs; asynchronous"""
+        self.ctx._check(self.lib.sbi_make(self.h, kf.h, float(blur)), "sbi_make")
+        return self
+
+    def read(self):
+        """-> dict(small (h, w) u8, tmpl (h, w) f32, jacs (h, w, 2) f32)"""
+        w, h = self.size
+        small, tmpl, jacs = np.zeros((h, w), np.uint8), np.zeros((h, w), np.float32), np.zeros((h, w, 2), np.float32)
+        self.ctx._check(self.lib.sbi_read(self.h, _ptr(small), _ptr(tmpl), _ptr(jacs)), "sbi_read")
+        return dict(small=small, tmpl=tmpl, jacs=jacs)
+
+    def CalcSBIRotation(self, target, iterations=6):
+        a = _abi.SbiAlignment()
+        self.ctx._check(self.lib.sbi_calc_rotation(self.h, target.h, int(iterations), C.byref(a)), "sbi_calc_rotation")
+        return _alignment(a)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.sbi_destroy(self.h)
+            self.h = None
+
+
+class Relocaliser:
+    """The map's keyframe SBIs (ptam_sbi_bank_*) and Relocaliser::AttemptRecovery (src/Relocaliser.cc:12-38) on them: ptam_relocalise"""
+
+    def __init__(self, ctx, capacity, size=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        fw, fh = size or ctx.size
+        self.h = C.c_void_p()
+        ctx._check(self.lib.sbi_bank_create(ctx.h, int(fw), int(fh), int(capacity), C.byref(self.h)), "sbi_bank_create")
+        self.scratch = SmallBlurryImage(ctx, (fw, fh))
+        self.poses = []
+
+    def add(self, kf, pose, blur=2.5):
+        """a keyframe of the map and its se3CfromW -> its index"""
+        i = C.c_int()
+        self.ctx._check(self.lib.sbi_bank_add(self.h, kf.h, float(blur), C.byref(i)), "sbi_bank_add")
+        self.poses.append(np.array(pose, np.float64).reshape(12))
+        return i.value
+
+    def add_batch(self, kfs, poses, blur=2.5):
+        """several keyframes with one make launch (ptam_sbi_bank_add_batch) -> the first one's index"""
+        i = C.c_int()
+        hs = (C.c_void_p * len(kfs))(*[k.h.value if hasattr(k.h, "value") else int(k.h) for k in kfs])
+        self.ctx._check(self.lib.sbi_bank_add_batch(self.h, len(kfs), hs, float(blur), C.byref(i)), "sbi_bank_add_batch")
+        self.poses += [np.array(p, np.float64).reshape(12) for p in poses]
+        return i.value
+
+    def count(self):
+        n = C.c_int()
+        self.ctx._check(self.lib.sbi_bank_count(self.h, C.byref(n)), "sbi_bank_count")
+        return n.value
+
+    def AttemptRecovery(self, kf, blur=2.5, max_score=9e6):
+        """-> dict(best, good, best_ssd, pose (12,), ssd (count,), align)"""
+        poses = np.ascontiguousarray(np.stack(self.poses))
+        r, ssd = _abi.RelocResult(), np.zeros(len(self.poses))
+        self.ctx._check(self.lib.relocalise(self.h, self.scratch.h, kf.h, _ptr(poses), float(blur), float(max_score), C.byref(r),
+                                            _ptr(ssd)), "relocalise")
+        return dict(best=r.best, good=bool(r.good), best_ssd=r.best_ssd, pose=np.array(r.pose), ssd=ssd, align=_alignment(r.align))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.sbi_bank_destroy(self.h)
+            self.h = None
+            self.scratch.close()
+
+
+class RotationEstimator:
+    """mpSBILastFrame / mpSBIThisFrame of the tracker (src/Tracker.cc:94-108): ptam_rotation_estimator_*, used by Tracker.track_frame_sbi"""
+
+    def __init__(self, ctx, blur=0.75, size=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        fw, fh = size or ctx.size
+        self.h = C.c_void_p()
+        ctx._check(self.lib.rotation_estimator_create(ctx.h, int(fw), int(fh), float(blur), C.byref(self.h)), "rotation_estimator_create")
+
+    def reset(self):
+        self.ctx._check(self.lib.rotation_estimator_reset(self.h), "rotation_estimator_reset")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.rotation_estimator_destroy(self.h)
             self.h = None
 
 
