@@ -91,6 +91,38 @@ enum {
     PTAM_BL_CAM_MEAS = 17    /* deterministic mode: int32[measurements by free cameras] */
 };
 int ptam_ba_debug_lists(ptam_ba* ba, int which, void* out, size_t cap_bytes);
+/* Test hook (host only, no device needed): what the camera solve (csrc/solve.hip: ba_solve) launches for a system of nblk block
+ * rows of 32 and block bandwidth `band` (clamped to nblk - 1, as the solve does), as a mask of the bits below.  ba_solve takes its
+ * decisions from this function, so a table checked against it is the dispatch.  flags bit 0 (PTAM_SOLVE_PER_COLUMN): the
+ * launch-per-block-column forms only — what a bundle does after a persistent solve gave up a wait, or while another bundle of
+ * the process is adjusting.  The environment switches of the solve (PTAM_LDLT_*) apply as they do to ba_solve: read once per
+ * process.  Returns a negative error for nblk < 1 or band < 0. */
+enum {
+    PTAM_SP_SMALL = 1 << 0,              /* everything in one workgroup, one launch (ldlt_small.inc) */
+    PTAM_SP_CHAIN_FWD_INV = 1 << 1,      /* one persistent chain, L^-1 built beside it: no backward pass */
+    PTAM_SP_CHAIN_BW_IN_LAUNCH = 1 << 2, /* one persistent chain, the backward pass in its right-hand-side workgroup */
+    PTAM_SP_CHAIN_SEPARATE_BW = 1 << 3,  /* one persistent chain, ldlt_backward_kernel behind it */
+    PTAM_SP_STEPS = 1 << 4,              /* one-ended, one launch per block column */
+    PTAM_SP_TWO_CHAINS = 1 << 5,         /* two-ended: both ends as persistent chains of one launch (mirrored bottom end) */
+    PTAM_SP_TWIN_STEPS = 1 << 6,         /* two-ended: one launch per step of both ends */
+    PTAM_SP_MID_CHAIN = 1 << 7,          /* two-ended: the middle part as a persistent chain */
+    PTAM_SP_MID_STEPS = 1 << 8,          /* two-ended: the middle part as one launch per block column */
+    PTAM_SP_BW_TWO_WG = 1 << 9,          /* ldlt_backward_kernel with a workgroup per end */
+    PTAM_SP_BW_GLOBAL = 1 << 10          /* ldlt_backward_kernel with its vectors in global memory instead of LDS */
+};
+#define PTAM_SOLVE_PER_COLUMN 1          /* flags bit 0 of ptam_ba_solve_plan and ptam_ba_debug_solve */
+#define PTAM_SOLVE_POISON_UPPER 2        /* flags bit 1 of ptam_ba_debug_solve */
+int ptam_ba_solve_plan(int nblk, int band, int flags);
+/* Test hook: ONE camera solve on a prepared bundle's own buffers and queue, for a system the caller supplies.  S: the dense lower
+ * triangle, n x n row-major with n = 6 F (the strictly upper part is not read); E: n.  The in-band 32x32 blocks of S go to the
+ * bundle's packed storage, the identity padding as the Schur reduce writes it; flags bit 1 fills the strictly upper triangle of
+ * the diagonal blocks with NaN (the solve reads the lower triangle only).  The factor, the substituted vectors, da, |da|^2 and
+ * the trial poses are filled with NaN before the solve, so that whatever it leaves unwritten shows.  Out (each nullable): da[n],
+ * *sumsq = |da|^2 as the trial reads it, trial_poses[C][12] = exp(da) * pose for the free cameras and the pose itself for the
+ * fixed ones, *plan = ptam_ba_solve_plan of what ran.  A persistent form that gives up a wait is reported as PTAM_E_HIP, not
+ * repeated.  The bundle stays usable: ptam_ba_compute behind this call gives what it gives without it. */
+int ptam_ba_debug_solve(ptam_ba* ba, const double* S, const double* E, int flags, double* da, double* sumsq, double* trial_poses,
+                        int* plan);
 
 #ifdef __cplusplus
 }

@@ -326,6 +326,8 @@ PROTOTYPES = {
     "ba_bench_jacobian_rotating": (_i, [_vp, _i, _i, _pd]),
     "ba_schur_index_map": (_i, [_i, _vp, _i]),
     "ba_debug_lists": (_i, [_vp, _i, _vp, C.c_size_t]),
+    "ba_solve_plan": (_i, [_i, _i, _i]),
+    "ba_debug_solve": (_i, [_vp, _vp, _vp, _i, _vp, _pd, _vp, C.POINTER(_i)]),
     "ba_set_comm": (_i, [_vp, _i, _i, ALLREDUCE_FN, _vp]),
     "map_bundle_adjust": (_i, [_vp, C.POINTER(BaOpts), _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(MapBaResult), _vp, _i, _vp, _vp]),
     "plane_opts_default": (None, [C.POINTER(PlaneOpts)]),

@@ -22,6 +22,7 @@
 #include <array>
 #include <chrono>
 #include <climits>
+#include <limits>
 #include <atomic>
 #include <numeric>
 #include <utility>
@@ -2016,6 +2017,82 @@ int ptam_ba_debug_lists(ptam_ba* ba, int which, void* out, size_t cap_bytes) {  
     }
     if (bytes > (size_t)INT_MAX) return PTAM_E_LIMIT;
     return (int)bytes;
+}
+
+// One camera solve on the bundle's own buffers, for a system the caller supplies (test hook: include/ptam_hip_bench.h;
+// tests/test_gpu_solve_direct.py).
+int ptam_ba_debug_solve(ptam_ba* ba, const double* S, const double* E, int flags, double* da, double* sumsq, double* trial_poses, int* plan) {
+    ARG_TRY(ba && S && E);
+    if (!ba->prepared || ba->d.F <= 0 || (ba->comm && ba->world > 1)) {
+        ptam_set_error("ptam_ba_debug_solve: needs a prepared single-device bundle with a free camera");
+        return PTAM_E_STATE;
+    }
+    ptam_ctx* ctx = ba->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    BaDev& d = ba->d;
+    const int n = d.n, npad = d.npad, nblk = npad / SOLVE_NB, band = se_band(d), cur = ba->cur;
+    const size_t ssz = se_size(nblk, band);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const bool poison = (flags & PTAM_SOLVE_POISON_UPPER) != 0;
+    // S | E in the packed layout (bundle.h: se_blk), as schur_reduce_kernel (ba_schur.inc) leaves it:
+    //   - every element of the in-band blocks on or below the diagonal is written; of a diagonal block's strictly upper triangle
+    //     only what lies inside a camera's own 6x6 block (the mirror image of its lower part) — the rest of it is never written
+    //     and never read (here: zero, as in a fresh bundle, or NaN with PTAM_SOLVE_POISON_UPPER — then the whole strictly upper
+    //     triangle, the cameras' own blocks included);
+    //   - padding rows n .. npad-1 (all in the last block row): zero in every in-band column c <= r, ONE on the diagonal;
+    //     the columns >= n of the rows above are upper triangle: not written;
+    //   - E[n .. npad) = 0.
+    std::vector<double> se(ssz + (size_t)npad, 0.0);
+    for (int r = 0; r < npad; r++) {
+        const int Rb = r / SOLVE_NB;
+        for (int Cb = std::max(0, Rb - band); Cb <= Rb; Cb++) {
+            const size_t off = se_blk(Rb, Cb, band) + (size_t)(r % SOLVE_NB) * SOLVE_NB;
+            ARG_TRY(off + SOLVE_NB <= ssz);   // (the layout's own arithmetic: a slip there must not become a stray write)
+            double* row = se.data() + off;
+            for (int q = 0; q < SOLVE_NB; q++) {
+                const int c = Cb * SOLVE_NB + q;
+                if (c <= r)
+                    row[q] = r < n ? S[(size_t)r * n + c] : (r == c ? 1.0 : 0.0);
+                else
+                    row[q] = poison ? nan : (c < n && c / 6 == r / 6) ? S[(size_t)c * n + r] : 0.0;
+            }
+        }
+    }
+    for (int i = 0; i < n; i++) se[ssz + i] = E[i];
+    ChainTurn chain_turn(d, ctx->device);
+    const int chain_was = d.chain_off;
+    if (flags & PTAM_SOLVE_PER_COLUMN) d.chain_off = 1;
+    const int plan_now = ptam_ba_solve_plan(nblk, band, d.chain_off ? PTAM_SOLVE_PER_COLUMN : 0);
+    int rc = PTAM_OK, fault = 0;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d.SE, se.data(), se.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        // whatever the solve leaves unwritten shows: all-ones bytes are a NaN
+        HIP_TRY(hipMemsetAsync(d.L, 0xff, ssz * sizeof(double), ctx->stream));
+        for (double* v : {d.Dg, d.y, d.da}) HIP_TRY(hipMemsetAsync(v, 0xff, (size_t)npad * sizeof(double), ctx->stream));
+        HIP_TRY(hipMemsetAsync(d.sumsq2, 0xff, 2 * sizeof(double), ctx->stream));
+        HIP_TRY(hipMemsetAsync(d.pose[cur ^ 1], 0xff, (size_t)d.C * 12 * sizeof(double), ctx->stream));
+        if (int r = ba_solve(ctx, d, cur)) return r;
+        double sq[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(&fault, &d.sc->solve_fault, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(sq, d.sumsq2, sizeof sq, hipMemcpyDeviceToHost, ctx->stream));
+        if (da) HIP_TRY(hipMemcpyAsync(da, d.da, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (trial_poses) HIP_TRY(hipMemcpyAsync(trial_poses, d.pose[cur ^ 1], (size_t)d.C * 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ptam_stream_wait(ctx->stream));
+        if (sumsq) *sumsq = sq[0] + sq[1];   // (finalize_new_kernel adds the two)
+        return PTAM_OK;
+    };
+    rc = run();
+    d.chain_off = chain_was;
+    if (rc) return rc;
+    if (plan) *plan = plan_now;
+    if (fault) {   // (not repeated with the other form, as Compute() would: the caller asked for THIS form's answer)
+        HIP_TRY(hipMemsetAsync(&d.sc->solve_fault, 0, sizeof(int), ctx->stream));
+        if (d.sflags) HIP_TRY(hipMemsetAsync(d.sflags, 0, sizeof(unsigned), ctx->stream));
+        HIP_TRY(ptam_stream_wait(ctx->stream));
+        ptam_set_error("ptam_ba_debug_solve: a wait of the persistent camera solve gave up (plan 0x%x)", plan_now);
+        return PTAM_E_HIP;
+    }
+    return PTAM_OK;
 }
 
 int ptam_ba_bench_jacobian_rotating(ptam_ba** bas, int n, int reps, double* avg_ms) {

@@ -36,6 +36,7 @@
 // A final single-workgroup kernel does D^-1 and the backward substitution with L^T, right-looking:
 // per block a 32x32 mat-vec with Lkk^-T, then every pending block below is updated in parallel.
 #include "bundle.h"
+#include "../../include/ptam_hip_bench.h"
 
 #define NB SOLVE_NB
 #define LDP (NB + 1)    // LDS pitch in doubles (odd -> conflict-free column access)
@@ -322,14 +323,59 @@ static int ldlt_twist_len(int nblk, int band) {
     return (nblk - 2 * band) / 2;
 }
 
-// does a system of nblk block rows and this band take the forward-inverse form (ldlt_chain.inc, column workers)?  ONE chain over
-// the whole system, a column worker's tiles fit its LDS, twice the workgroups fit one XCD.  PTAM_LDLT_BACKWARD_IN_LAUNCH=1: the
-// backward pass in the right-hand-side workgroup as before; PTAM_LDLT_SEPARATE_BACKWARD=1: ldlt_backward_kernel behind the launch
-// (A/B runs and tests/test_gpu_solve_forward_inverse.py, which compares the forms on the product library: hence getenv)
-static bool ldlt_forward_inverse(int nblk, int band) {
-    static const bool off = getenv("PTAM_LDLT_BACKWARD_IN_LAUNCH") != nullptr || getenv("PTAM_LDLT_SEPARATE_BACKWARD") != nullptr ||
-                            getenv("PTAM_LDLT_NO_CHAIN") != nullptr;
-    return !off && ldlt_twist_len(nblk, band) == 0 && nblk > SM_USE_NB && nblk <= CH_FI_MAX_NB && ch_lds_bytes_fi(band, nblk) <= CH_LDS_MAX;
+// WHICH FORM RUNS: every decision of ba_solve, in one host-only function (include/ptam_hip_bench.h: the PTAM_SP_* bits;
+// tests/test_solve_plan.py holds the table).  ba_solve below launches what this mask says and decides nothing itself.
+extern "C" int ptam_ba_solve_plan(int nblk, int band, int flags) {
+    if (nblk < 1 || band < 0) return PTAM_E_ARG;
+    band = std::min(band, nblk - 1);   // (se_band)
+    const bool per_column = (flags & PTAM_SOLVE_PER_COLUMN) != 0;
+    // the switches, read once per process.  getenv where tests/test_gpu_solve_forward_inverse.py compares the forms on the
+    // product library, ptam_ab_env (the measurement build only) for the rest
+    static const bool no_small = ptam_ab_env("PTAM_LDLT_NO_SMALL") != nullptr;   // (A/B runs: launch-per-block-column form only)
+    static const bool no_chain = getenv("PTAM_LDLT_NO_CHAIN") != nullptr;        // (A/B runs)
+    // PTAM_LDLT_BACKWARD_IN_LAUNCH=1: the backward pass in the right-hand-side workgroup as before the forward-inverse form;
+    // PTAM_LDLT_SEPARATE_BACKWARD=1: ldlt_backward_kernel behind the launch
+    static const bool sep_bw = getenv("PTAM_LDLT_SEPARATE_BACKWARD") != nullptr;
+    static const bool no_fwd_inv = getenv("PTAM_LDLT_BACKWARD_IN_LAUNCH") != nullptr || sep_bw || no_chain;
+    static const bool twin_launches = ptam_ab_env("PTAM_LDLT_TWIN_LAUNCHES") != nullptr;   // (A/B runs)
+    // one or two block rows in one workgroup and one launch: ldlt_small.inc.  (It holds up to SM_NB = 5 block rows and was the
+    // form of every system up to that size until the persistent launch's row workers learnt to keep up with the chain; now,
+    // us per solve, small / persistent: 10.3 / 10.7 at 1 block row, 16.8 / 16.5 at 2, 25.7 / 23.8 at 3, 36.1 / 30.6 at 4,
+    // 48.7 / 37.7 at 5 — the single workgroup does the row updates one after the other.)
+    if (!no_small && nblk <= SM_USE_NB) return PTAM_SP_SMALL;
+    const size_t bw_bytes = (size_t)6 * nblk * NB * sizeof(double);
+    const int bw_global = bw_bytes > BW_LDS_MAX ? PTAM_SP_BW_GLOBAL : 0;   // (the vectors in d.bw_scratch instead)
+    const bool persistent = !no_chain && !per_column;
+    const int t_end = ldlt_twist_len(nblk, band), b_start = nblk - t_end;
+    if (t_end == 0) {
+        // not banded enough for two chains: one persistent launch (ldlt_chain.inc) when a row worker's in-band tiles fit its
+        // LDS and the block rows — a workgroup each — fit one XCD: measured against the
+        // launch-per-block-column form (tools/ldlt, us per solve) 49 / 67 at 7 block rows, 71 / 98 at 10, 86 / 119 at 12,
+        // 96 / 133 at 13 (dense: from 14 block rows on a worker's tiles no longer fit), 105 / 149 at 15 rows of band 5,
+        // 202 / 287 at 28 of band 9.  (Where two chains apply they win: 137 against 152 at 23 rows of band 2.)
+        // The forward-inverse form (column workers): a column worker's tiles fit its LDS, twice the workgroups fit one XCD.
+        const bool fwd_inv = !no_fwd_inv && nblk > SM_USE_NB && nblk <= CH_FI_MAX_NB && ch_lds_bytes_fi(band, nblk) <= CH_LDS_MAX;
+        // (the right-hand-side workgroup of that launch also substitutes backwards — ldlt_chain.inc, "and backwards" — when
+        //  its vectors fit beside a row worker's tiles.  Measured, tools/ldlt, us per solve inside / behind the launch: 28.8 /
+        //  29.7 at 4 block rows, 47.4 / 47.9 at 7, 69.0 / 68.4 at 10 — one compute unit fetches a tile from the L2 in ~200
+        //  cycles, 34 B per cycle, whoever asks; so only where the rows are short)
+        const bool bw_in = !sep_bw && band <= CH_BW_MAXT && ch_lds_bytes_bw(band, nblk) <= CH_LDS_MAX;
+        const size_t lds = fwd_inv ? ch_lds_bytes_fi(band, nblk) : bw_in ? ch_lds_bytes_bw(band, nblk) : ch_lds_bytes(band);
+        if (persistent && nblk <= CH_MAX_NB && lds <= CH_LDS_MAX)
+            return fwd_inv ? PTAM_SP_CHAIN_FWD_INV : bw_in ? PTAM_SP_CHAIN_BW_IN_LAUNCH : PTAM_SP_CHAIN_SEPARATE_BW;
+        return PTAM_SP_STEPS | bw_global;
+    }
+    // Two chains: as TWO persistent chains of one launch — the downward one on S itself (blocks 0, 8, 16 ... of the launch: XCD
+    // 0), the upward one on a mirrored copy of the system's bottom end (blocks 1, 9, 17 ...: XCD 1; ldlt_chain.inc, "the bottom
+    // end") — where each chain's block rows fit one XCD; as one launch per step of both chains otherwise.
+    const int kr2 = std::min(b_start, t_end + band);   // (each chain's rows: its columns and the `band` block rows they reach)
+    const bool tiles_fit = ch_lds_bytes(band) <= CH_LDS_MAX;
+    const bool two_persistent = t_end >= 2 && persistent && !twin_launches && kr2 <= CH_MAX_NB && tiles_fit;
+    // the middle: one persistent launch over its block rows where that form applies (ldlt_chain.inc: 5.6 us per block row
+    // against 8.3 per launch), one launch per block column otherwise
+    const int n_mid = b_start - t_end;
+    const bool mid_chain = persistent && n_mid >= 3 && n_mid <= CH_MAX_NB && tiles_fit;
+    return (two_persistent ? PTAM_SP_TWO_CHAINS : PTAM_SP_TWIN_STEPS) | (mid_chain ? PTAM_SP_MID_CHAIN : PTAM_SP_MID_STEPS) | PTAM_SP_BW_TWO_WG | bw_global;
 }
 
 size_t ba_solve_flag_bytes(int nblk) { return ch_flag_words(nblk, nblk) * sizeof(unsigned); }
@@ -340,94 +386,67 @@ static ChainArgs chain_args_natural(const BaDev& d, int k0, int k1, int kr) {
 
 int ba_solve(ptam_ctx* ctx, BaDev& d, int cur) {
     const int nblk = d.npad / NB, band = se_band(d);
-    static const bool no_small = ptam_ab_env("PTAM_LDLT_NO_SMALL") != nullptr;   // (A/B runs: launch-per-block-column form only)
-    // one or two block rows in one workgroup and one launch: ldlt_small.inc.  (It holds up to SM_NB = 5 block rows and was the
-    // form of every system up to that size until the persistent launch's row workers learnt to keep up with the chain; now,
-    // us per solve, small / persistent: 10.3 / 10.7 at 1 block row, 16.8 / 16.5 at 2, 25.7 / 23.8 at 3, 36.1 / 30.6 at 4,
-    // 48.7 / 37.7 at 5 — the single workgroup does the row updates one after the other.)
-    if (!no_small && nblk <= SM_USE_NB) {
+    // (a bundle without the persistent forms' flag words or second-chain buffers — tools/ — has the per-column forms only)
+    const int plan = ptam_ba_solve_plan(nblk, band, (d.chain_off || !d.sflags || !d.SE2) ? PTAM_SOLVE_PER_COLUMN : 0);
+    if (plan < 0) return plan;
+    if (plan & PTAM_SP_SMALL) {
         hipLaunchKernelGGL(ldlt_small_kernel, dim3(1), dim3(TPB), sizeof(SmallLds), ctx->stream, d, cur);
         HIP_TRY(hipGetLastError());
         return PTAM_OK;
     }
     auto nwg_of = [](int rem) { return 1 + rem + rem * (rem + 1) / 2; };
-    const int t_end = ldlt_twist_len(nblk, band), b_start = nblk - t_end;
-    {
-        // not banded enough for two chains (below): one persistent launch (ldlt_chain.inc) when a row worker's in-band tiles fit its
-        // LDS and the block rows — a workgroup each — fit one XCD: measured against the
-        // launch-per-block-column form below (tools/ldlt, us per solve) 49 / 67 at 7 block rows, 71 / 98 at 10, 86 / 119 at 12,
-        // 96 / 133 at 13 (dense: from 14 block rows on a worker's tiles no longer fit), 105 / 149 at 15 rows of band 5,
-        // 202 / 287 at 28 of band 9.  (Where two chains apply they win: 137 against 152 at 23 rows of band 2.)
-        static const bool no_chain = getenv("PTAM_LDLT_NO_CHAIN") != nullptr;   // (A/B runs)
-        // (the right-hand-side workgroup of that launch also substitutes backwards — ldlt_chain.inc, "and backwards" — when
-        //  its vectors fit beside a row worker's tiles; PTAM_LDLT_SEPARATE_BACKWARD=1: ldlt_backward_kernel behind it, A/B runs)
-        static const bool sep_bw = getenv("PTAM_LDLT_SEPARATE_BACKWARD") != nullptr;
-        // (measured, tools/ldlt, us per solve inside / behind the launch: 28.8 / 29.7 at 4 block rows, 47.4 / 47.9 at 7, 69.0 / 68.4 at 10 — one
-        //  compute unit fetches a tile from the L2 in ~200 cycles, 34 B per cycle, whoever asks; so only where the rows are short)
-        const bool bw_in = !sep_bw && band <= CH_BW_MAXT && ch_lds_bytes_bw(band, nblk) <= CH_LDS_MAX;
-        const bool fwd_inv = ldlt_forward_inverse(nblk, band);
-        const int do_bw = fwd_inv ? 2 : bw_in ? 1 : 0;
-        const size_t lds = fwd_inv ? ch_lds_bytes_fi(band, nblk) : bw_in ? ch_lds_bytes_bw(band, nblk) : ch_lds_bytes(band);
-        if (t_end == 0 && !no_chain && !d.chain_off && d.sflags && nblk <= CH_MAX_NB && lds <= CH_LDS_MAX) {
-            d.solve_seq++;
-            if (d.solve_seq >= (1u << 27)) d.solve_seq = 1;   // (flags carry it shifted by up to 4 bits; flags of 2^27 solves ago are no concern)
-            {
-                const ChainArgs a = chain_args_natural(d, 0, nblk, nblk);
-                hipLaunchKernelGGL(ldlt_chain_kernel, dim3(8 * (fwd_inv ? ch_roles_fi(nblk) : ch_roles(nblk))), dim3(TPB), lds, ctx->stream, d, a, a, 1, cur, do_bw);
-            }
-            if (!do_bw) {
-                const size_t bw = (size_t)6 * d.npad * sizeof(double);
-                hipLaunchKernelGGL(ldlt_backward_kernel<false>, dim3(1), dim3(1024), bw, ctx->stream, d, cur, nblk);
-            }
-            HIP_TRY(hipGetLastError());
-            return PTAM_OK;
-        }
-    }
-    // Two chains: as TWO persistent chains of one launch — the downward one on S itself (blocks 0, 8, 16 ... of the launch: XCD
-    // 0), the upward one on a mirrored copy of the system's bottom end (blocks 1, 9, 17 ...: XCD 1; ldlt_chain.inc, "the bottom
-    // end") — where each chain's block rows fit one XCD; as one launch per step of both chains otherwise.
-    static const bool no_chain2 = getenv("PTAM_LDLT_NO_CHAIN") != nullptr || ptam_ab_env("PTAM_LDLT_TWIN_LAUNCHES") != nullptr;   // (A/B runs)
-    const int kr2 = std::min(b_start, t_end + band);   // (each chain's rows: its columns and the `band` block rows they reach)
-    const bool two_persistent = t_end >= 2 && !no_chain2 && !d.chain_off && d.sflags && d.SE2 && kr2 <= CH_MAX_NB && ch_lds_bytes(band) <= CH_LDS_MAX;
-    if (two_persistent) {
+    auto next_seq = [&d] {
         d.solve_seq++;
-        if (d.solve_seq >= (1u << 27)) d.solve_seq = 1;
+        if (d.solve_seq >= (1u << 27)) d.solve_seq = 1;   // (flags carry it shifted by up to 4 bits; flags of 2^27 solves ago are no concern)
+    };
+    const int t_end = ldlt_twist_len(nblk, band), b_start = nblk - t_end;
+    if (plan & (PTAM_SP_CHAIN_FWD_INV | PTAM_SP_CHAIN_BW_IN_LAUNCH | PTAM_SP_CHAIN_SEPARATE_BW)) {
+        const bool fwd_inv = (plan & PTAM_SP_CHAIN_FWD_INV) != 0;
+        const int do_bw = fwd_inv ? 2 : (plan & PTAM_SP_CHAIN_BW_IN_LAUNCH) ? 1 : 0;
+        const size_t lds = fwd_inv ? ch_lds_bytes_fi(band, nblk) : do_bw ? ch_lds_bytes_bw(band, nblk) : ch_lds_bytes(band);
+        next_seq();
+        {
+            const ChainArgs a = chain_args_natural(d, 0, nblk, nblk);
+            hipLaunchKernelGGL(ldlt_chain_kernel, dim3(8 * (fwd_inv ? ch_roles_fi(nblk) : ch_roles(nblk))), dim3(TPB), lds, ctx->stream, d, a, a, 1, cur, do_bw);
+        }
+        if (!do_bw) {
+            const size_t bw = (size_t)6 * d.npad * sizeof(double);
+            hipLaunchKernelGGL(ldlt_backward_kernel<false>, dim3(1), dim3(1024), bw, ctx->stream, d, cur, nblk);
+        }
+        HIP_TRY(hipGetLastError());
+        return PTAM_OK;
+    }
+    if (plan & PTAM_SP_TWO_CHAINS) {
+        const int kr2 = std::min(b_start, t_end + band);   // (each chain's rows: its columns and the `band` block rows they reach)
+        next_seq();
         hipLaunchKernelGGL(ldlt_mirror_in_kernel, dim3(kr2 * (band + 1)), dim3(TPB), 0, ctx->stream, d, kr2);
         const ChainArgs a0 = chain_args_natural(d, 0, t_end, kr2);
         const ChainArgs a1{d.SE2, d.SE2 + se_size(nblk, band), d.L2, d.Dg2, d.y2, d.sflags2, 0, t_end, kr2, d.npad};   // (mirrored: the padding comes first, nothing to skip)
         hipLaunchKernelGGL(ldlt_chain_kernel, dim3(8 * ch_roles(kr2)), dim3(TPB), ch_lds_bytes(band), ctx->stream, d, a0, a1, 2, cur, 0);
         hipLaunchKernelGGL(ldlt_mirror_out_kernel, dim3(kr2 * (band + 1)), dim3(TPB), 0, ctx->stream, d, t_end, kr2);
     }
-    for (int st = 0; st < (two_persistent ? 0 : t_end); st++) {   // one step of each chain per launch
-        const int kt = st, kb = nblk - 1 - st;
-        const int nt = nwg_of(std::min(nblk - kt - 1, band)), nb = nwg_of(std::min(kb, band));
-        hipLaunchKernelGGL(ldlt_step_twin_kernel, dim3(nt + nb), dim3(TPB), 0, ctx->stream, d, kt, kb, nt);
-    }
-    {
-        // the middle (everything, without a second chain): one persistent launch over its block rows where that form applies
-        // (ldlt_chain.inc: 5.6 us per block row against 8.3 per launch), one launch per block column otherwise
-        static const bool no_chain = getenv("PTAM_LDLT_NO_CHAIN") != nullptr;
-        const int n_mid = b_start - t_end;
-        const size_t lds = ch_lds_bytes(band);
-        if (t_end > 0 && !no_chain && !d.chain_off && d.sflags && n_mid >= 3 && n_mid <= CH_MAX_NB && lds <= CH_LDS_MAX) {
-            d.solve_seq++;
-            if (d.solve_seq >= (1u << 27)) d.solve_seq = 1;
-            {
-                const ChainArgs a = chain_args_natural(d, t_end, b_start, b_start);
-                hipLaunchKernelGGL(ldlt_chain_kernel, dim3(8 * ch_roles(n_mid)), dim3(TPB), lds, ctx->stream, d, a, a, 1, cur, 0);
-            }
-        } else {
-            for (int k = t_end; k < b_start; k++) {
-                const int nwg = nwg_of(std::min(b_start - k - 1, band));
-                hipLaunchKernelGGL(ldlt_step_kernel, dim3(nwg), dim3(TPB), 0, ctx->stream, d, k, b_start);
-            }
+    if (plan & PTAM_SP_TWIN_STEPS)
+        for (int st = 0; st < t_end; st++) {   // one step of each chain per launch
+            const int kt = st, kb = nblk - 1 - st;
+            const int nt = nwg_of(std::min(nblk - kt - 1, band)), nb = nwg_of(std::min(kb, band));
+            hipLaunchKernelGGL(ldlt_step_twin_kernel, dim3(nt + nb), dim3(TPB), 0, ctx->stream, d, kt, kb, nt);
+        }
+    // the middle (everything, without a second chain)
+    if (plan & PTAM_SP_MID_CHAIN) {
+        next_seq();
+        const ChainArgs a = chain_args_natural(d, t_end, b_start, b_start);
+        hipLaunchKernelGGL(ldlt_chain_kernel, dim3(8 * ch_roles(b_start - t_end)), dim3(TPB), ch_lds_bytes(band), ctx->stream, d, a, a, 1, cur, 0);
+    } else {
+        for (int k = t_end; k < b_start; k++) {
+            const int nwg = nwg_of(std::min(b_start - k - 1, band));
+            hipLaunchKernelGGL(ldlt_step_kernel, dim3(nwg), dim3(TPB), 0, ctx->stream, d, k, b_start);
         }
     }
-    const size_t bw_bytes = (size_t)6 * d.npad * sizeof(double);
-    if (bw_bytes > BW_LDS_MAX)   // (the vectors in d.bw_scratch instead)
-        hipLaunchKernelGGL(ldlt_backward_kernel<true>, dim3(t_end > 0 ? 2 : 1), dim3(1024), 0, ctx->stream, d, cur, b_start);
+    const int n_bw = (plan & PTAM_SP_BW_TWO_WG) ? 2 : 1;
+    if (plan & PTAM_SP_BW_GLOBAL)
+        hipLaunchKernelGGL(ldlt_backward_kernel<true>, dim3(n_bw), dim3(1024), 0, ctx->stream, d, cur, b_start);
     else
-        hipLaunchKernelGGL(ldlt_backward_kernel<false>, dim3(t_end > 0 ? 2 : 1), dim3(1024), bw_bytes, ctx->stream, d, cur, b_start);
+        hipLaunchKernelGGL(ldlt_backward_kernel<false>, dim3(n_bw), dim3(1024), (size_t)6 * d.npad * sizeof(double), ctx->stream, d, cur, b_start);
     HIP_TRY(hipGetLastError());
     return PTAM_OK;
 }

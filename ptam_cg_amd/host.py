@@ -1119,6 +1119,21 @@ class Bundle:
         self.ctx._check(self.lib.ba_debug_lists(self.h, which, _ptr(out), n), "ba_debug_lists")
         return out[:n].view(dtype)
 
+    def debug_solve(self, S, E, flags=0):
+        """ONE camera solve of S da = E on the prepared bundle's own buffers (include/ptam_hip_bench.h: ptam_ba_debug_solve).
+        S: dense n x n, lower triangle read, n = 6 x free cameras.  flags bit 0: launch-per-block-column forms only; bit 1: NaN in
+        the strictly upper triangle of the diagonal blocks.  -> da[n], |da|^2, trial poses [C][12], plan mask"""
+        nc, nf, _, _ = self.counts()
+        n = 6 * nf
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        assert S.shape == (n, n) and E.shape == (n,)
+        da, poses = np.full(n, np.nan), np.full((nc, 12), np.nan)
+        sumsq, plan = C.c_double(float("nan")), C.c_int(-1)
+        self.ctx._check(self.lib.ba_debug_solve(self.h, _ptr(S), _ptr(E), int(flags), _ptr(da), C.byref(sumsq), _ptr(poses),
+                                                C.byref(plan)), "ba_debug_solve")
+        return da, sumsq.value, poses, plan.value
+
     def bench_jacobian(self, reps):
         ms, by = C.c_double(), C.c_double()
         self.ctx._check(self.lib.ba_bench_jacobian(self.h, reps, C.byref(ms), C.byref(by)), "ba_bench_jacobian")

@@ -21,6 +21,7 @@ SHAPES = {
     "17_cams_4_blocks_last_6_rows": dict(n_cams=18, n_pts=200, seed=171),      # 102 rows: niter = 2 in the last block, a camera straddles every block boundary
     "49_cams_10_blocks": dict(n_cams=50, n_pts=300, seed=491),                 # 294 rows: the headline's role count without its run time
     "19_cams_4_blocks": dict(n_cams=20, n_pts=300, seed=191),                  # 114 rows: the local bundle's shape
+    "69_cams_13_blocks": dict(n_cams=70, n_pts=300, seed=691),                 # 414 rows: the form's last size, 13 tiles fill a column worker's LDS
 }
 
 

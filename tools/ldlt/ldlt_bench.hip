@@ -7,6 +7,9 @@
 // LDL^T of the same system and prints the average wall time per solve (events around the whole loop, copies included — use
 // rocprofv3 --kernel-trace --stats on this binary for per-kernel durations; -DK7_TIMING builds print the kernels' stamps).
 // Not part of the product: it includes solve.hip textually so that instrumented variants need no library rebuild.
+// A timing tool: the gated check of the solve's result — every form of ba_solve against an exact answer and an extended-precision
+// reference, on the product's own buffers — lives in tests/test_gpu_solve_direct.py (ptam_ba_debug_solve); the OK / MISMATCH
+// printed here only guards a measurement against a broken variant.
 #include <cstdarg>
 #include <cstdlib>
 #include <random>
@@ -131,9 +134,10 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(&sc, d.sc, sizeof sc, hipMemcpyDeviceToHost));
         if (sc.solve_fault) printf("SOLVE FAULT: a wait of the persistent form gave up\n");
     }
-    // (what ba_solve chose, by its own predicate; the other labels only name the switch that was set)
-    const char* const form = ldlt_forward_inverse(nblk, band) ? " [forward inverse]" : nblk <= SM_USE_NB || getenv("PTAM_LDLT_NO_CHAIN") ? "" :
-                             getenv("PTAM_LDLT_SEPARATE_BACKWARD") ? " [separate backward]" : getenv("PTAM_LDLT_BACKWARD_IN_LAUNCH") ? " [backward in launch]" : "";
+    // (what ba_solve chose, by its own plan)
+    const int plan = ptam_ba_solve_plan(nblk, band, 0);
+    const char* const form = (plan & PTAM_SP_CHAIN_FWD_INV) ? " [forward inverse]" : (plan & PTAM_SP_CHAIN_SEPARATE_BW) ? " [separate backward]" :
+                             (plan & PTAM_SP_CHAIN_BW_IN_LAUNCH) ? " [backward in launch]" : "";
     printf("F %d n %d nblk %d band %d%s: %.2f us per solve (copy included), max |da - ref| = %.3e (|ref| max %.3e) %s\n", F, n, nblk, band,
            form, 1e3 * best / reps, err, nrm, err <= 1e-11 * nrm + 1e-300 ? "OK" : "MISMATCH");
 #ifdef K7_TIMING
@@ -187,7 +191,7 @@ int main(int argc, char** argv) {
     }
 #endif
 #ifdef K7_TIMING
-    if (ldlt_forward_inverse(nblk, band)) {
+    if (plan & PTAM_SP_CHAIN_FWD_INV) {
         // the forward-inverse form's tail: what follows the chain's last flag (10 ns units since F[last] went up)
         std::vector<long long> rt(9);
         CK(hipMemcpy(rt.data(), dbg + 800, rt.size() * 8, hipMemcpyDeviceToHost));
