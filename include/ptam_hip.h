@@ -1003,6 +1003,55 @@ typedef struct {
 int  ptam_map_scene_depth(ptam_ctx*, int n_kf, const double* kf_poses12, int n_points, const double* points3, int n_meas,
                           const ptam_map_meas* meas, ptam_scene_depth* out /* n_kf */);
 
+/* ---- MapMaker::ReFindInSingleKeyFrame / ReFindNewlyMade / ReFindFromFailureQueue (src/MapMaker.cc:1028-1081) as ONE call on the
+ *      map tables.  The caller keeps its map and hands over: the keyframe handles and their se3CfromW (vpKeyFrames order), the
+ *      point table (vpPoints order: pixel vectors, patch source as a keyframe INDEX, bBad), the table of all mMeasurements as
+ *      ptam_map_bundle_adjust takes it, and the table of all sNeverRetryKFs entries, both sorted by (kf, point) with no repeated
+ *      pair.  Index order stands in for pointer order.  The pairs, in visiting order:
+ *        KEYFRAME (:1028-1040): work = one int32 keyframe index k (n_work == 1); the pairs (k, p), p = 0 .. n_points-1.  bBad is
+ *          not looked at (:1031-1037).
+ *        NEW_POINTS (:1046-1065): work = n_work point indices in mqNewQueue order, none repeated; a point with `bad` set adds one
+ *          to n_bad_points and makes no pair (:1056-1059), every other one is paired with keyframes 0 .. n_kf-1 in turn.
+ *        FAILURE_QUEUE (:1070-1081): work = n_work ptam_map_pair in any order; the call sorts them by (kf, point) (:1074, on the
+ *          host: the list comes from there) and skips a pair equal to its predecessor (the reference's first visit has put it into
+ *          one of the two sets).
+ *      On the device, per pair: skip = (kf, point) is in meas or in never (:947-948, a binary search in each table); the pair
+ *      record ptam_refind_pairs would have been given (pose, point, template source, point_id = point index); then the finder
+ *      chain of ptam_refind_pairs itself, with `finder`'s state, which carries over to the next call of either entry.  No per-pair
+ *      data is built on or copied from the host: the tables go up once per call.
+ *      Passes: at most opts->max_pairs_per_pass pairs are in flight (0 or opts == NULL: 4096), in NEW_POINTS whole points (at
+ *      least one): the per-pair work memory is bounded by the pass, the finder state carries from pass to pass.  *stop_flag
+ *      (nullable) is read on the host before each pass is enqueued — mvpKeyFrameQueue.empty() per point (:1053); once it is set
+ *      the call finishes what is enqueued and reports stopped = 1, the pairs visited (n_pairs) and, in NEW_POINTS, the work
+ *      entries consumed (points_consumed, bad ones included).  No host wait between passes; two waits per call.
+ *      Outputs, in visiting order: found_out = {kf, point, level, PTAM_MAP_SRC_REFIND, root_pos} with found_subpix (Measurement::
+ *      bSubPix) beside it (:996-1011), never_out = every visited, non-skipped pair that failed (each failure path of :951-993).
+ *      meas_merged / never_merged (nullable, each on its own; room for n_meas / n_never + the call's pair count): meas + the found
+ *      rows, never + the new never pairs, each sorted by (kf, point) on the device — what the next ptam_map_bundle_adjust /
+ *      ptam_map_scene_depth / ptam_map_refind takes as it is.  The same input gives the same bits.
+ *      out_cap: at least the call's pair count (n_points | n_kf * n_work | n_work).  n_work == 0: PTAM_OK, zero counts, the
+ *      merged tables are copies.
+ *      PTAM_E_ARG, with nothing written and the finder state untouched: a table out of order or repeated, an index, level or
+ *      source out of range, a null or foreign-device keyframe, a keyframe of another frame size than the context's, a repeated
+ *      point in NEW_POINTS, n_work > 1 in KEYFRAME, a capacity that is too small, a null output with a non-zero pair count. */
+enum { PTAM_MAP_REFIND_KEYFRAME = 0, PTAM_MAP_REFIND_NEW_POINTS = 1, PTAM_MAP_REFIND_FAILURE_QUEUE = 2 };
+typedef struct {
+    ptam_pvs_point pv;                                  /* v3WorldPos, v3PixelRight_W, v3PixelDown_W */
+    int32_t src_kf, src_level, center_x, center_y;      /* pPatchSourceKF (index), nSourceLevel, irCenter */
+    int32_t bad, pad_;                                  /* bBad */
+} ptam_map_refind_point;
+typedef struct { int32_t kf, point; } ptam_map_pair;
+typedef struct { int32_t max_pairs_per_pass; /* 0: the library's default */ int32_t pad_; } ptam_map_refind_opts;
+typedef struct {
+    int32_t n_pairs, n_skipped, n_found, n_never;       /* visited = skipped + found + never */
+    int32_t n_bad_points, n_template_kept, points_consumed, stopped;
+} ptam_map_refind_result;
+int ptam_map_refind(ptam_ctx*, ptam_refinder*, const ptam_map_refind_opts*, int mode, int n_kf, const ptam_kf* const* kfs,
+                    const double* kf_poses12, int n_points, const ptam_map_refind_point* points, int n_meas, const ptam_map_meas* meas,
+                    int n_never, const ptam_map_pair* never, int n_work, const void* work, const volatile unsigned char* stop_flag,
+                    ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix, ptam_map_pair* never_out, int out_cap,
+                    ptam_map_meas* meas_merged, ptam_map_pair* never_merged);
+
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,
  * ordered on `stream` (hipStream_t).  Return 0 on success. */

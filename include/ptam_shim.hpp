@@ -851,11 +851,58 @@ public:
               "ptam_refind_pairs");
         return out;
     }
+    ptam_refinder* handle() const { return h_; }
 
 private:
     Context& c_;
     ptam_refinder* h_ = nullptr;
 };
+
+// int MapMaker::ReFindInSingleKeyFrame(KeyFrame&) / void ReFindNewlyMade() / void ReFindFromFailureQueue()   src/MapMaker.cc:1028-1081
+// in ONE device call (ptam_map_refind) for a host that keeps its map as tables: vpKeyFrames in map order with their se3CfromW,
+// vPoints in vpPoints order (patch source as a keyframe index), vMeas as MapBundleAdjust takes it, vNever = every sNeverRetryKFs
+// entry, both sorted by (kf, point).  pWork / nWork per mode (ptam_hip.h): the keyframe index | the new points in queue order |
+// the failure queue as it stands.  The set tests of :947-948, the pair records and the search run on the device through
+// `finder`.  The caller applies vFound[i] (k.mMeasurements[&p] = {level, root_pos, bSubPix = vFoundSubPix[i], SRC_REFIND};
+// p.sMeasurementKFs.insert(&k)) and vNeverNew[i] (p.sNeverRetryKFs.insert(&k)) — or simply takes vMeas / vNever, which come back
+// merged and sorted when bMerge is set.  pbStop: mvpKeyFrameQueue.empty() turned false (:1053), looked at between passes.
+struct MapReFindResult {
+    ptam_map_refind_result result;
+    std::vector<ptam_map_meas> vFound;       // visiting order
+    std::vector<int32_t> vFoundSubPix;
+    std::vector<ptam_map_pair> vNeverNew;    // visiting order
+};
+inline MapReFindResult MapReFind(Context& c, ReFinder& finder, int mode, const std::vector<const KeyFrame*>& vpKeyFrames,
+                                 const std::vector<SE3>& vKFPoses, const std::vector<ptam_map_refind_point>& vPoints,
+                                 std::vector<ptam_map_meas>& vMeas, std::vector<ptam_map_pair>& vNever, const void* pWork, int nWork,
+                                 bool bMerge = true, const bool* pbStop = nullptr, const ptam_map_refind_opts* opts = nullptr) {
+    if (vpKeyFrames.size() != vKFPoses.size()) throw std::runtime_error("MapReFind: one pose per keyframe");
+    std::vector<const ptam_kf*> kfs;
+    for (const KeyFrame* k : vpKeyFrames) kfs.push_back(k ? k->handle() : nullptr);
+    const size_t cap = mode == PTAM_MAP_REFIND_KEYFRAME ? (nWork > 0 ? vPoints.size() : 0)
+                       : mode == PTAM_MAP_REFIND_NEW_POINTS ? kfs.size() * (size_t)(nWork > 0 ? nWork : 0) : (size_t)(nWork > 0 ? nWork : 0);
+    MapReFindResult r{};
+    r.vFound.resize(cap);
+    r.vFoundSubPix.resize(cap);
+    r.vNeverNew.resize(cap);
+    std::vector<ptam_map_meas> mm(bMerge ? vMeas.size() + cap : 0);
+    std::vector<ptam_map_pair> nm(bMerge ? vNever.size() + cap : 0);
+    check(ptam_map_refind(c.handle(), finder.handle(), opts, mode, (int)kfs.size(), kfs.data(), reinterpret_cast<const double*>(vKFPoses.data()),
+                          (int)vPoints.size(), vPoints.data(), (int)vMeas.size(), vMeas.data(), (int)vNever.size(), vNever.data(), nWork, pWork,
+                          reinterpret_cast<const volatile unsigned char*>(pbStop), &r.result, r.vFound.data(), r.vFoundSubPix.data(),
+                          r.vNeverNew.data(), (int)cap, bMerge ? mm.data() : nullptr, bMerge ? nm.data() : nullptr),
+          "ptam_map_refind");
+    r.vFound.resize((size_t)r.result.n_found);
+    r.vFoundSubPix.resize((size_t)r.result.n_found);
+    r.vNeverNew.resize((size_t)r.result.n_never);
+    if (bMerge) {
+        mm.resize(vMeas.size() + r.vFound.size());
+        nm.resize(vNever.size() + r.vNeverNew.size());
+        vMeas.swap(mm);
+        vNever.swap(nm);
+    }
+    return r;
+}
 
 // class Bundle (include/Bundle.h:106-152)
 class Bundle {

@@ -182,6 +182,30 @@ class SceneDepth(C.Structure):
     _fields_ = [("depth_mean", C.c_double), ("depth_sigma", C.c_double), ("n_meas", C.c_int32), ("pad_", C.c_int32)]
 
 
+MAP_REFIND_KEYFRAME, MAP_REFIND_NEW_POINTS, MAP_REFIND_FAILURE_QUEUE = range(3)
+
+
+class MapRefindPoint(C.Structure):
+    """ptam_map_refind_point (MapPoint: the pixel vectors, pPatchSourceKF as an index, nSourceLevel, irCenter, bBad)"""
+    _fields_ = [("pv", PvsPoint), ("src_kf", C.c_int32), ("src_level", C.c_int32), ("center_x", C.c_int32), ("center_y", C.c_int32),
+                ("bad", C.c_int32), ("pad_", C.c_int32)]
+
+
+class MapPair(C.Structure):
+    """ptam_map_pair: one entry of sNeverRetryKFs / mvFailureQueue as table indices"""
+    _fields_ = [("kf", C.c_int32), ("point", C.c_int32)]
+
+
+class MapRefindOpts(C.Structure):
+    _fields_ = [("max_pairs_per_pass", C.c_int32), ("pad_", C.c_int32)]
+
+
+class MapRefindResult(C.Structure):
+    """ptam_map_refind_result (MapMaker::ReFind*, src/MapMaker.cc:1028-1081)"""
+    _fields_ = [(f, C.c_int32) for f in ("n_pairs", "n_skipped", "n_found", "n_never", "n_bad_points", "n_template_kept",
+                                         "points_consumed", "stopped")]
+
+
 class SbiAlignment(C.Structure):
     """ptam_sbi_alignment (SmallBlurryImage::CalcSBIRotation, src/ImageProcess.cc:313-495)"""
     _fields_ = [("se2_rot", C.c_double * 4), ("se2_trans", C.c_double * 2), ("score", C.c_double), ("mean_offset", C.c_double),
@@ -336,6 +360,8 @@ PROTOTYPES = {
     "map_apply_global_transform": (_i, [_vp, _pd, _i, _vp, _i, _vp, _vp, _vp]),
     "map_align_to_plane": (_i, [_vp, C.POINTER(PlaneOpts), _i, _vp, _i, _vp, _vp, _vp, _pd, C.POINTER(PlaneInfo), _vp]),
     "map_scene_depth": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "map_refind": (_i, [_vp, _vp, C.POINTER(MapRefindOpts), _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp,
+                        C.POINTER(MapRefindResult), _vp, _vp, _vp, _i, _vp, _vp]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

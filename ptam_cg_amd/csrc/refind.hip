@@ -1,6 +1,6 @@
 // refind.hip — the mapmaker's data association: MapMaker::ReFind_Common (src/MapMaker.cc:943-1020) over the map points of one
 // keyframe (ptam_refind_batch) and over a list of (keyframe, point) pairs through one PatchFinder (ptam_refinder_*, ptam_refind_pairs).
-#include "track_internal.h"
+#include "refind_internal.h"
 #include "patch_device.h"
 #include "keyframe_device.h"
 #include "pvs_device.h"
@@ -98,40 +98,6 @@ __global__ void __launch_bounds__(256) refind_finish_kernel(int n, const ptam_pa
 // compacts the reaching pairs and walks each run with one thread — which pair re-makes, which template a kept one uses,
 // whether a rejected warp has raised mbTemplateBad since; (3) the re-made templates; (4) one wave per pair searches with its
 // template; (5) the finder's state after the last pair.
-struct RpPair {
-    ptam_pvs_point pt;
-    TmSrc src;
-    double pose[12];
-    long long id;
-    int skip, kf;
-};
-struct RpFinder {   // the state of the reference's static PatchFinder that outlives a call
-    long long pt;          // mpLastTemplateMapPoint
-    double m2[4];          // mm2LastWarpMatrix {m00, m01, m10, m11}
-    int valid, bad;        // mpLastTemplateMapPoint != NULL, mbTemplateBad
-    uint8_t tpl[64];       // mimTemplate
-};
-struct RpDev {
-    int n;
-    const RpPair* pairs;
-    const KfLevels* Ls;
-    TemplateJob* jobs;
-    ptam_patch_query* q;
-    double* m2;            // [n][4]
-    int* reach;            // the pair gets as far as the finder
-    int* detbad;           // CalcSearchLevelAndWarpMatrix rejects the warp
-    int* R;                // reaching pairs, in order
-    int* nr;
-    int* refresh;          // the finder re-makes its template for this pair
-    int* srcp;             // pair whose template this pair searches with (-1: the template the finder brought along)
-    int* dacc;             // a warp was rejected since that template was made (this pair's included)
-    int* bad;              // Finder.TemplateBad() for this pair
-    uint8_t* tm;           // [n][64]
-    ptam_template_result* tres;
-    RpFinder* st;
-    ptam_refind_result* out;
-    int* kept;
-};
 __global__ void __launch_bounds__(256) rp_prep_kernel(DevCam cam, RpDev d) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= d.n) return;
@@ -316,6 +282,40 @@ __global__ void __launch_bounds__(64) rp_state_kernel(RpDev d) {
     if (lane == 0) d.st->bad = d.bad[last];
 }
 
+static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+size_t rp_carve(RpDev& d, char* b, size_t off, int n) {
+    const size_t N = (size_t)n;
+    auto take = [&](size_t bytes) {
+        char* p = b ? b + off : nullptr;
+        off += up256(bytes);
+        return p;
+    };
+    d.jobs = (TemplateJob*)take(N * sizeof(TemplateJob));
+    d.q = (ptam_patch_query*)take(N * sizeof(ptam_patch_query));
+    d.m2 = (double*)take(N * 32);
+    d.reach = (int*)take(N * 4);
+    d.detbad = (int*)take(N * 4);
+    d.R = (int*)take(N * 4);
+    d.nr = (int*)take(4);
+    d.refresh = (int*)take(N * 4);
+    d.srcp = (int*)take(N * 4);
+    d.dacc = (int*)take(N * 4);
+    d.bad = (int*)take(N * 4);
+    d.tm = (uint8_t*)take(N * 64);
+    d.tres = (ptam_template_result*)take(N * sizeof(ptam_template_result));
+    d.out = (ptam_refind_result*)take(N * sizeof(ptam_refind_result));
+    d.kept = (int*)take(N * 4);
+    return off;
+}
+void rp_launch_chain(hipStream_t st, const DevCam& cam, const RpDev& d) {
+    const int n = d.n;
+    hipLaunchKernelGGL(rp_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, cam, d);
+    hipLaunchKernelGGL(rp_scan_kernel, dim3(1), dim3(1024), 0, st, d);
+    hipLaunchKernelGGL(rp_template_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d);
+    hipLaunchKernelGGL(rp_search_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d);
+    hipLaunchKernelGGL(rp_state_kernel, dim3(1), dim3(64), 0, st, d);
+}
+
 extern "C" {
 
 int ptam_refind_batch(ptam_ctx* ctx, const ptam_kf* kf, const double kf_pose[12], int n, const ptam_pvs_point* points,
@@ -378,10 +378,6 @@ int ptam_refind_batch(ptam_ctx* ctx, const ptam_kf* kf, const double kf_pose[12]
     return PTAM_OK;
 }
 
-struct ptam_refinder {
-    ptam_ctx* ctx;
-    RpFinder* st;   // device
-};
 int ptam_refinder_create(ptam_ctx* ctx, ptam_refinder** out) {
     ARG_TRY(ctx && out);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -441,49 +437,22 @@ int ptam_refind_pairs(ptam_ctx* ctx, ptam_refinder* finder, int n, const ptam_re
         }
         r.kf = k;
     }
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
     const size_t N = (size_t)n;
-    const size_t o_pairs = take(N * sizeof(RpPair)), o_ls = take(hl.size() * sizeof(KfLevels)), o_jobs = take(N * sizeof(TemplateJob)),
-                 o_q = take(N * sizeof(ptam_patch_query)), o_m2 = take(N * 32), o_reach = take(N * 4), o_det = take(N * 4), o_R = take(N * 4),
-                 o_nr = take(4), o_ref = take(N * 4), o_src = take(N * 4), o_dacc = take(N * 4), o_bad = take(N * 4), o_tm = take(N * 64),
-                 o_tr = take(N * sizeof(ptam_template_result)), o_out = take(N * sizeof(ptam_refind_result)), o_kept = take(N * 4);
+    const size_t o_pairs = 0, o_ls = up256(N * sizeof(RpPair)), o_work = o_ls + up256(hl.size() * sizeof(KfLevels));
+    RpDev d;
     void* sc;
-    int rc = ctx_scratch(ctx, off, &sc);
+    int rc = ctx_scratch(ctx, rp_carve(d, nullptr, o_work, n), &sc);
     if (rc) return rc;
     char* b = (char*)sc;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(b + o_pairs, hp.data(), N * sizeof(RpPair), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b + o_ls, hl.data(), hl.size() * sizeof(KfLevels), hipMemcpyHostToDevice, st));
-    RpDev d;
+    rp_carve(d, b, o_work, n);
     d.n = n;
     d.pairs = (const RpPair*)(b + o_pairs);
     d.Ls = (const KfLevels*)(b + o_ls);
-    d.jobs = (TemplateJob*)(b + o_jobs);
-    d.q = (ptam_patch_query*)(b + o_q);
-    d.m2 = (double*)(b + o_m2);
-    d.reach = (int*)(b + o_reach);
-    d.detbad = (int*)(b + o_det);
-    d.R = (int*)(b + o_R);
-    d.nr = (int*)(b + o_nr);
-    d.refresh = (int*)(b + o_ref);
-    d.srcp = (int*)(b + o_src);
-    d.dacc = (int*)(b + o_dacc);
-    d.bad = (int*)(b + o_bad);
-    d.tm = (uint8_t*)(b + o_tm);
-    d.tres = (ptam_template_result*)(b + o_tr);
     d.st = finder->st;
-    d.out = (ptam_refind_result*)(b + o_out);
-    d.kept = (int*)(b + o_kept);
-    hipLaunchKernelGGL(rp_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->cam, d);
-    hipLaunchKernelGGL(rp_scan_kernel, dim3(1), dim3(1024), 0, st, d);
-    hipLaunchKernelGGL(rp_template_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d);
-    hipLaunchKernelGGL(rp_search_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d);
-    hipLaunchKernelGGL(rp_state_kernel, dim3(1), dim3(64), 0, st, d);
+    rp_launch_chain(st, ctx->cam, d);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, d.out, N * sizeof(ptam_refind_result), hipMemcpyDeviceToHost, st));
     if (template_kept) HIP_TRY(hipMemcpyAsync(template_kept, d.kept, N * 4, hipMemcpyDeviceToHost, st));

@@ -705,6 +705,64 @@ class ReFinder:
             self.h = None
 
 
+MAP_PAIR_DT = np.dtype([("kf", "<i4"), ("point", "<i4")])
+MAP_REFIND_POINT_DT = np.dtype([("pv", PVS_POINT_DT), ("src_kf", "<i4"), ("src_level", "<i4"), ("center_x", "<i4"), ("center_y", "<i4"),
+                                ("bad", "<i4"), ("pad_", "<i4")])
+assert MAP_PAIR_DT.itemsize == C.sizeof(_abi.MapPair) == 8 and MAP_REFIND_POINT_DT.itemsize == C.sizeof(_abi.MapRefindPoint) == 96
+
+
+def map_refind_points(world, pixel_right_w, pixel_down_w, src_kf, src_level, centers, bad=None):
+    """the point table of map_refind (MAP_REFIND_POINT_DT): src_kf is an index into the keyframe table"""
+    n = len(world)
+    p = np.zeros(n, MAP_REFIND_POINT_DT)
+    p["pv"]["world"], p["pv"]["pixel_right_w"], p["pv"]["pixel_down_w"] = world, pixel_right_w, pixel_down_w
+    p["src_kf"], p["src_level"] = src_kf, src_level
+    c = np.asarray(centers, dtype=np.int32).reshape(n, 2)
+    p["center_x"], p["center_y"] = c[:, 0], c[:, 1]
+    if bad is not None:
+        p["bad"] = bad
+    return p
+
+
+def map_refind_pair_count(mode, n_kf, n_points, n_work):
+    """the pair count a call's output capacities are held against"""
+    return {_abi.MAP_REFIND_KEYFRAME: n_points if n_work else 0, _abi.MAP_REFIND_NEW_POINTS: n_kf * n_work,
+            _abi.MAP_REFIND_FAILURE_QUEUE: n_work}[mode]
+
+
+def map_refind(ctx, finder, mode, kfs, poses, points, meas, never, work, stop=None, max_pairs_per_pass=0, merged=True):
+    """MapMaker::ReFindInSingleKeyFrame (mode _abi.MAP_REFIND_KEYFRAME, work = the keyframe index) / ReFindNewlyMade
+    (MAP_REFIND_NEW_POINTS, work = point indices in queue order) / ReFindFromFailureQueue (MAP_REFIND_FAILURE_QUEUE, work =
+    MAP_PAIR_DT in any order) in ONE device call on the map tables (ptam_map_refind, src/MapMaker.cc:1028-1081) through
+    `finder` (a ReFinder): kfs a list of KeyFrame, poses (K, 12), points MAP_REFIND_POINT_DT, meas MAP_MEAS_DT and never
+    MAP_PAIR_DT sorted by (kf, point).  The inputs are not modified; -> dict with the result counts, "found" (MAP_MEAS_DT) and
+    "found_subpix", "never" (MAP_PAIR_DT), all in visiting order, and (merged) "meas_merged" / "never_merged", sorted."""
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+    points = np.ascontiguousarray(points, dtype=MAP_REFIND_POINT_DT)
+    meas = np.ascontiguousarray(meas, dtype=MAP_MEAS_DT)
+    never = np.ascontiguousarray(never, dtype=MAP_PAIR_DT)
+    if mode == _abi.MAP_REFIND_FAILURE_QUEUE:
+        work = np.ascontiguousarray(work, dtype=MAP_PAIR_DT)
+    else:
+        work = np.ascontiguousarray(work, dtype=np.int32).reshape(-1)
+    handles = np.array([k.h.value if hasattr(k.h, "value") else int(k.h) for k in kfs], dtype=np.uint64)
+    K, N, M, V, W = len(handles), len(points), len(meas), len(never), len(work)
+    cap = map_refind_pair_count(mode, K, N, W)
+    found, subpix, nev = np.zeros(max(cap, 1), MAP_MEAS_DT), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), MAP_PAIR_DT)
+    mm = np.zeros(max(M + cap, 1), MAP_MEAS_DT) if merged else None
+    nm = np.zeros(max(V + cap, 1), MAP_PAIR_DT) if merged else None
+    o = _abi.MapRefindOpts(int(max_pairs_per_pass), 0)
+    res = _abi.MapRefindResult()
+    ctx._check(ctx.lib.map_refind(ctx.h, finder.h, C.byref(o), int(mode), K, _ptr(handles), _ptr(poses), N, _ptr(points), M, _ptr(meas), V,
+                                  _ptr(never), W, _ptr(work), _ptr(stop), C.byref(res), _ptr(found), _ptr(subpix), _ptr(nev), cap,
+                                  _ptr(mm), _ptr(nm)), "map_refind")
+    d = {f: getattr(res, f) for f, _ in _abi.MapRefindResult._fields_}
+    d.update(found=found[:res.n_found].copy(), found_subpix=subpix[:res.n_found].copy(), never=nev[:res.n_never].copy())
+    if merged:
+        d.update(meas_merged=mm[:M + res.n_found].copy(), never_merged=nm[:V + res.n_never].copy())
+    return d
+
+
 class Tracker:
     """Tracker::TrackMap (src/Tracker.cc:442-696) as one device-resident chain (ptam_tracker_* / ptam_track_map): the map
     stays on the device, a frame is one call."""
