@@ -1052,6 +1052,97 @@ int ptam_map_refind(ptam_ctx*, ptam_refinder*, const ptam_map_refind_opts*, int 
                     ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix, ptam_map_pair* never_out, int out_cap,
                     ptam_map_meas* meas_merged, ptam_map_pair* never_merged);
 
+/* ---- The edits of the map tables between the ptam_map_* calls, each as ONE device call: the bundle's outliers
+ *      (src/MapMaker.cc:916-932), MapMaker::HandleBadPoints with Map::MoveBadPointsToTrash (:131-153, src/Map.cc:20-30) and a
+ *      call's new points (:679-688, :352-362).  With them one MapMaker::run() iteration (:57-114) is a sequence of table calls:
+ *      every table one call returns is valid input for the next.
+ *      Common to the three: the tables are host arrays that go up once; flags are set per row, the rows are compacted or merged
+ *      in order on the device (an ordered multi-workgroup compaction: per-tile counts, a scan of the tile counts, a scatter) and
+ *      the point column is remapped; one host wait at the end, and one before it where a count decides how much comes down.
+ *      Every order is fixed: the same input gives the same bits.  All outputs are integer and bit-copy work.  Output buffers must
+ *      not overlap input buffers.  The inputs are not modified (`bad` of ptam_map_apply_outliers and the columns of
+ *      ptam_map_handle_bad_points excepted, which are in and out).  Rows behind the counts a call reports are not written. */
+
+/* ---- the outlier loop of MapMaker::BundleAdjust (src/MapMaker.cc:916-932) applied to the tables.  meas / never: sorted by
+ *      (kf, point), no repeated pair; failure: mvFailureQueue as it stands (any order, duplicates allowed); outliers: exactly
+ *      what ptam_map_bundle_adjust returned for this meas; bad: n_points bytes, bBad, in and out.  Per outlier, in list order:
+ *        PTAM_MAP_OUT_POINT_BAD      bad[point] = 1, the row stays (:921-922)
+ *        PTAM_MAP_OUT_FAILURE_QUEUE  (kf, point) is appended to the failure queue, the row is erased (:925-926, :929-930)
+ *        PTAM_MAP_OUT_NEVER_RETRY    (kf, point) enters the never table, the row is erased (:928-930)
+ *      meas_out (room for n_meas): the surviving rows, in order.  never_out (room for n_never + n_outliers): the old and the new
+ *      pairs, merged and sorted.  failure_out (room for n_failure + n_outliers): the old queue, then the new pairs in outlier order.
+ *      On the device: one thread per outlier writes its row's flag and sets bad; the rows without a flag are compacted into
+ *      meas_out; the rows flagged NEVER_RETRY are compacted into the new never pairs, which are sorted because the table is;
+ *      the two sorted never lists are merged by the rule of ptam_map_refind's merge; the outliers with FAILURE_QUEUE are
+ *      compacted in list order.
+ *      PTAM_E_ARG, with nothing written: a table out of order or with a repeated pair, an index out of range, a level outside
+ *      0..3, a source outside 0..4, an action outside 1..3, an outlier whose meas is outside the table or whose (kf, point) is not
+ *      that row's, the same row named twice, a NEVER_RETRY pair that is already in never (a consistent map holds no pair in both
+ *      sets, :947-948), a null pointer with a non-zero count (bad: with n_points > 0), a negative count. */
+typedef struct {
+    int32_t n_point_bad, n_failure_added, n_never_added;   /* outliers per action */
+    int32_t n_meas_out, n_never_out, n_failure_out;        /* rows written */
+} ptam_map_outliers_result;
+int ptam_map_apply_outliers(ptam_ctx*, int n_kf, int n_points, int n_meas, const ptam_map_meas* meas, int n_never,
+                            const ptam_map_pair* never, int n_failure, const ptam_map_pair* failure, int n_outliers,
+                            const ptam_map_outlier* outliers, uint8_t* bad, ptam_map_outliers_result* res, ptam_map_meas* meas_out,
+                            ptam_map_pair* never_out, ptam_map_pair* failure_out);
+
+/* ---- MapMaker::HandleBadPoints (src/MapMaker.cc:131-153) with Map::MoveBadPointsToTrash (src/Map.cc:20-30) on the tables.
+ *      bad (n_points bytes, nullable = all zero): bBad.  outlier_count / inlier_count (int32 per point, nullable together):
+ *      nMEstimatorOutlierCount / nMEstimatorInlierCount, which the caller keeps from the tracker's iteration-set flags.
+ *      A point is removed iff bad[i], or outlier_count[i] > 20 && outlier_count[i] > inlier_count[i] (:136).  The survivors keep
+ *      their order (src/Map.cc:23-29 erases from the back).  Removing a point renumbers every later one:
+ *        new_index (n_points int32)  the point's new index, -1 for a removed point
+ *        kept (room for n_points)    survivor j's old index: the prevIndex of ptam_tracker_update_map for a tracker that last
+ *                                    saw the whole old table
+ *        meas_out (room for n_meas)  the rows of surviving points with `point` rewritten (:142-151); still sorted by (kf, point)
+ *                                    because the remap is monotone
+ *        never_out (room for n_never)  the same: a removed point's sNeverRetryKFs go with its pMMData
+ *        new_queue (n_new point indices in mqNewQueue order, none repeated, nullable) -> new_queue_out (room for n_new): the
+ *                                    surviving entries, rewritten, in order.  The reference leaves a removed point in the queue
+ *                                    and skips it when it is popped (:1056-1059): n_new_dropped is what ptam_map_refind would
+ *                                    have reported as n_bad_points
+ *        failure (any order, duplicates allowed, nullable) -> failure_out (room for n_failure): the surviving pairs, rewritten, in
+ *                                    order.  A DEFINED DEVIATION: the reference keeps the MapPoint pointer in mvFailureQueue and
+ *                                    would re-find a trashed point; no later stage reads such a measurement (:876-877)
+ *        columns (at most 8)         point-side tables with one row of row_bytes (a positive multiple of 4) per point — points3,
+ *                                    the ptam_map_refind_point table, the ptam_map_point_source table, the two counts, whatever
+ *                                    the caller keeps — each compacted IN PLACE: rows 0 .. n_kept-1 of data become the
+ *                                    survivors' rows, the bytes behind them are not touched
+ *      On the device: one thread per point marks; an ordered exclusive scan over the points gives new_index and kept; one ordered
+ *      compaction with the remap per table and per queue; one gather per column, threads over (surviving row, dword).
+ *      PTAM_E_ARG, with nothing written: the table refusals of ptam_map_apply_outliers, a repeated or out-of-range new_queue entry,
+ *      one of the two count arrays without the other, more than 8 columns, a row_bytes that is not a positive multiple of 4, a
+ *      null column.  (The compaction takes any table of fewer than 2^31 rows: there is no size refusal.) */
+enum { PTAM_MAP_MAX_COLUMNS = 8 };
+typedef struct { void* data; int32_t row_bytes; int32_t pad_; } ptam_map_column;
+typedef struct {
+    int32_t n_marked;                  /* points the counts marked that bad had not (:136-137) */
+    int32_t n_removed, n_kept;
+    int32_t n_meas_out, n_never_out, n_new_out, n_new_dropped, n_failure_out;
+} ptam_map_bad_points_result;
+int ptam_map_handle_bad_points(ptam_ctx*, int n_kf, int n_points, const uint8_t* bad, const int32_t* outlier_count,
+                               const int32_t* inlier_count, int n_meas, const ptam_map_meas* meas, int n_never,
+                               const ptam_map_pair* never, int n_new, const int32_t* new_queue, int n_failure,
+                               const ptam_map_pair* failure, int n_columns, const ptam_map_column* columns,
+                               ptam_map_bad_points_result* res, int32_t* new_index, int32_t* kept, ptam_map_meas* meas_out,
+                               ptam_map_pair* never_out, int32_t* new_queue_out, ptam_map_pair* failure_out);
+
+/* ---- the new points of ptam_add_map_points_epipolar (MapMaker::AddPointEpipolar, src/MapMaker.cc:670-685; target_source =
+ *      PTAM_MAP_SRC_EPIPOLAR) or ptam_init_points_from_trails (InitFromStereo, :352-362; PTAM_MAP_SRC_TRAIL) into the tables.
+ *      New point i gets index n_points + i; the new queue (mqNewQueue.push, :671) is that index range itself, in order.
+ *      meas_out (room for n_meas + 2 n_made): meas with {src_kf, n_points + i, level, PTAM_MAP_SRC_ROOT, src_root_pos} and
+ *      {target_kf, n_points + i, level, target_source, target_pos} inserted, each at the end of its keyframe's run because the new
+ *      indices exceed all old ones: two upper-bound searches and one shifted copy, one thread per output row.
+ *      points_out (nullable, n_made ptam_map_refind_point): pv = the record's point, src_kf, src_level = level, center_x / y,
+ *      bad = 0.  sources_out (nullable, n_made ptam_map_point_source): src_kf and the record's three _nc vectors.
+ *      PTAM_E_ARG, with nothing written: a table out of order or repeated, src_kf == target_kf, an index, level or source out of
+ *      range, n_points + n_made >= 2^31 or n_meas + 2 n_made >= 2^31, a null pointer with a non-zero count, a negative count. */
+int ptam_map_add_points(ptam_ctx*, int n_kf, int n_points, int n_meas, const ptam_map_meas* meas, int src_kf, int target_kf,
+                        int target_source, int n_made, const ptam_new_map_point* made, ptam_map_meas* meas_out,
+                        ptam_map_refind_point* points_out, ptam_map_point_source* sources_out);
+
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,
  * ordered on `stream` (hipStream_t).  Return 0 on success. */

@@ -904,6 +904,88 @@ inline MapReFindResult MapReFind(Context& c, ReFinder& finder, int mode, const s
     return r;
 }
 
+// The edits of the tables between the calls above, each in ONE device call, for a host that keeps its map as tables (ptam_hip.h).
+//
+// The outlier loop of MapMaker::BundleAdjust   src/MapMaker.cc:916-932 (ptam_map_apply_outliers): vOutliers as MapBundleAdjust
+// returned them for this vMeas.  vBad (bBad per point), vMeas, vNever and vFailureQueue (mvFailureQueue) are updated in place:
+// POINT_BAD sets vBad, FAILURE_QUEUE appends the pair to the queue and erases the row, NEVER_RETRY moves the pair into vNever.
+inline ptam_map_outliers_result ApplyBundleOutliers(Context& c, int nKeyFrames, std::vector<uint8_t>& vBad, std::vector<ptam_map_meas>& vMeas,
+                                                    std::vector<ptam_map_pair>& vNever, std::vector<ptam_map_pair>& vFailureQueue,
+                                                    const std::vector<ptam_map_outlier>& vOutliers) {
+    ptam_map_outliers_result r{};
+    std::vector<ptam_map_meas> mo(vMeas.size());
+    std::vector<ptam_map_pair> no(vNever.size() + vOutliers.size()), fo(vFailureQueue.size() + vOutliers.size());
+    check(ptam_map_apply_outliers(c.handle(), nKeyFrames, (int)vBad.size(), (int)vMeas.size(), vMeas.data(), (int)vNever.size(), vNever.data(),
+                                  (int)vFailureQueue.size(), vFailureQueue.data(), (int)vOutliers.size(), vOutliers.data(), vBad.data(), &r,
+                                  mo.data(), no.data(), fo.data()),
+          "ptam_map_apply_outliers");
+    mo.resize((size_t)r.n_meas_out);
+    no.resize((size_t)r.n_never_out);
+    fo.resize((size_t)r.n_failure_out);
+    vMeas.swap(mo);
+    vNever.swap(no);
+    vFailureQueue.swap(fo);
+    return r;
+}
+
+// void MapMaker::HandleBadPoints()   src/MapMaker.cc:131-153 with Map::MoveBadPointsToTrash (src/Map.cc:20-30)
+// (ptam_map_handle_bad_points).  vBad: bBad per point; pOutlierCount / pInlierCount (nullable together): nMEstimatorOutlierCount /
+// nMEstimatorInlierCount per point.  vMeas, vNever, vNewQueue (mqNewQueue as point indices) and vFailureQueue are rewritten in
+// place with the removed points gone and the later ones renumbered; every column (a point-side table: data, bytes per row) is
+// compacted in place, and the caller shrinks it to result.n_kept rows — vBad included if it is handed over as a column.
+// vKept[j] = survivor j's old index = the prevIndex of MapTracker::UpdateMap; vNewIndex[i] = -1 for a removed point.
+struct HandleBadPointsResult {
+    ptam_map_bad_points_result result;
+    std::vector<int32_t> vNewIndex, vKept;
+};
+inline HandleBadPointsResult HandleBadPoints(Context& c, int nKeyFrames, const std::vector<uint8_t>& vBad, const int32_t* pOutlierCount,
+                                             const int32_t* pInlierCount, std::vector<ptam_map_meas>& vMeas, std::vector<ptam_map_pair>& vNever,
+                                             std::vector<int32_t>& vNewQueue, std::vector<ptam_map_pair>& vFailureQueue,
+                                             const std::vector<ptam_map_column>& vColumns = {}) {
+    HandleBadPointsResult r{};
+    r.vNewIndex.resize(vBad.size());
+    r.vKept.resize(vBad.size());
+    std::vector<ptam_map_meas> mo(vMeas.size());
+    std::vector<ptam_map_pair> no(vNever.size()), fo(vFailureQueue.size());
+    std::vector<int32_t> qo(vNewQueue.size());
+    check(ptam_map_handle_bad_points(c.handle(), nKeyFrames, (int)vBad.size(), vBad.data(), pOutlierCount, pInlierCount, (int)vMeas.size(),
+                                     vMeas.data(), (int)vNever.size(), vNever.data(), (int)vNewQueue.size(), vNewQueue.data(),
+                                     (int)vFailureQueue.size(), vFailureQueue.data(), (int)vColumns.size(), vColumns.data(), &r.result,
+                                     r.vNewIndex.data(), r.vKept.data(), mo.data(), no.data(), qo.data(), fo.data()),
+          "ptam_map_handle_bad_points");
+    r.vKept.resize((size_t)r.result.n_kept);
+    mo.resize((size_t)r.result.n_meas_out);
+    no.resize((size_t)r.result.n_never_out);
+    qo.resize((size_t)r.result.n_new_out);
+    fo.resize((size_t)r.result.n_failure_out);
+    vMeas.swap(mo);
+    vNever.swap(no);
+    vNewQueue.swap(qo);
+    vFailureQueue.swap(fo);
+    return r;
+}
+
+// The table side of MapMaker::AddPointEpipolar   src/MapMaker.cc:670-685 (nTargetSource PTAM_MAP_SRC_EPIPOLAR, vMade from
+// AddMapPointsEpipolar) and of InitFromStereo's point loop :352-362 (PTAM_MAP_SRC_TRAIL, vMade from InitPointsFromTrails)
+// (ptam_map_add_points): new point i gets index nPoints + i, vMeas gets its two rows in place, the point-side rows of the new
+// points come back for the caller to append to its tables; their indices are mqNewQueue's new entries, in order.
+struct AddPointsResult {
+    std::vector<ptam_map_refind_point> vPoints;
+    std::vector<ptam_map_point_source> vSources;
+};
+inline AddPointsResult AddPointsToTables(Context& c, int nKeyFrames, int nPoints, std::vector<ptam_map_meas>& vMeas, int nSrcKF, int nTargetKF,
+                                         const std::vector<ptam_new_map_point>& vMade, int nTargetSource = PTAM_MAP_SRC_EPIPOLAR) {
+    AddPointsResult r{};
+    r.vPoints.resize(vMade.size());
+    r.vSources.resize(vMade.size());
+    std::vector<ptam_map_meas> mo(vMeas.size() + 2 * vMade.size());
+    check(ptam_map_add_points(c.handle(), nKeyFrames, nPoints, (int)vMeas.size(), vMeas.data(), nSrcKF, nTargetKF, nTargetSource, (int)vMade.size(),
+                              vMade.data(), mo.data(), r.vPoints.data(), r.vSources.data()),
+          "ptam_map_add_points");
+    vMeas.swap(mo);
+    return r;
+}
+
 // class Bundle (include/Bundle.h:106-152)
 class Bundle {
 public:

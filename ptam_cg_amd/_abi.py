@@ -206,6 +206,25 @@ class MapRefindResult(C.Structure):
                                          "points_consumed", "stopped")]
 
 
+class MapOutliersResult(C.Structure):
+    """ptam_map_outliers_result (the outlier loop of MapMaker::BundleAdjust, src/MapMaker.cc:916-932)"""
+    _fields_ = [(f, C.c_int32) for f in ("n_point_bad", "n_failure_added", "n_never_added", "n_meas_out", "n_never_out", "n_failure_out")]
+
+
+MAP_MAX_COLUMNS = 8
+
+
+class MapColumn(C.Structure):
+    """ptam_map_column: one point-side table of ptam_map_handle_bad_points, one row of row_bytes per point"""
+    _fields_ = [("data", C.c_void_p), ("row_bytes", C.c_int32), ("pad_", C.c_int32)]
+
+
+class MapBadPointsResult(C.Structure):
+    """ptam_map_bad_points_result (MapMaker::HandleBadPoints, src/MapMaker.cc:131-153)"""
+    _fields_ = [(f, C.c_int32) for f in ("n_marked", "n_removed", "n_kept", "n_meas_out", "n_never_out", "n_new_out", "n_new_dropped",
+                                         "n_failure_out")]
+
+
 class SbiAlignment(C.Structure):
     """ptam_sbi_alignment (SmallBlurryImage::CalcSBIRotation, src/ImageProcess.cc:313-495)"""
     _fields_ = [("se2_rot", C.c_double * 4), ("se2_trans", C.c_double * 2), ("score", C.c_double), ("mean_offset", C.c_double),
@@ -362,6 +381,10 @@ PROTOTYPES = {
     "map_scene_depth": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "map_refind": (_i, [_vp, _vp, C.POINTER(MapRefindOpts), _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp,
                         C.POINTER(MapRefindResult), _vp, _vp, _vp, _i, _vp, _vp]),
+    "map_apply_outliers": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(MapOutliersResult), _vp, _vp, _vp]),
+    "map_handle_bad_points": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, C.POINTER(MapBadPointsResult),
+                                   _vp, _vp, _vp, _vp, _vp, _vp]),
+    "map_add_points": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

@@ -100,6 +100,7 @@ void pvs_preload_kernels();
 void trackmap_preload_kernels();
 void refind_preload_kernels();
 void maprefind_preload_kernels();
+void maptables_preload_kernels();
 void sbi_preload_kernels();
 int pose_hazards_read_pose(hipStream_t st, unsigned long long* out);
 int pose_hazards_read_trackmap(hipStream_t st, unsigned long long* out);

@@ -1,0 +1,596 @@
+// maptables.hip — the edits of the map tables between the ptam_map_* calls, each as one call on the tables (ptam_hip.h):
+//   ptam_map_apply_outliers     the outlier loop of MapMaker::BundleAdjust (src/MapMaker.cc:916-932)
+//   ptam_map_handle_bad_points  MapMaker::HandleBadPoints (:131-153) with Map::MoveBadPointsToTrash (src/Map.cc:20-30)
+//   ptam_map_add_points         the table side of AddPointEpipolar (:670-685) and of InitFromStereo's point loop (:352-362)
+// All three set a flag per row, compact or merge the rows in order and remap the point column.  The one primitive is the ordered
+// compaction mt_compact over a row source (keep / put / drop), three launches:
+//   mt_count_kernel    one workgroup per tile of MT_TILE = 1024 rows, one row per thread: __ballot / __popcll per 64-lane wave,
+//                      the 16 wave counts summed through LDS -> the tile's count
+//   mt_scan_kernel     one workgroup: the tile counts -> exclusive offsets and the total, MT_SCAN_CHUNK = 1024 tile counts per
+//                      round with the running sum carried from round to round (it walks the tile counts, not the table)
+//   mt_scatter_kernel  the tiling of mt_count_kernel again: row -> tile offset + offset inside the tile
+// No atomic decides where a row lands; the only atomic of the file adds up a count (n_marked).
+// Sizes at which the compaction changes path (tests/test_gpu_map_edit.py runs n - 1, n, n + 1 of each):
+//   64          rows: a second wave inside the tile
+//   1024        rows (MT_TILE): a second workgroup
+//   1024 * 1024 rows (MT_TILE * MT_SCAN_CHUNK): a second round of the tile-count scan
+// The scan has no capacity of its own: any table of fewer than 2^31 rows is taken.
+#include <algorithm>
+
+#include "common.h"
+
+enum { MT_TILE = 1024, MT_SCAN_CHUNK = 1024 };
+
+__device__ __forceinline__ unsigned long long mt_key(int kf, int point) {   // (indices are >= 0: one unsigned compare orders (kf, point))
+    return ((unsigned long long)(unsigned)kf << 32) | (unsigned)point;
+}
+
+// ---- the ordered compaction ----------------------------------------------------------------------------------------------------
+// the thread's place among the tile's kept rows, in thread order, and the tile's count
+__device__ __forceinline__ int mt_tile_offset(bool keep, int tid, int* ws, int& total) {
+    const unsigned long long m = __ballot(keep);
+    const int lane = tid & 63, wid = tid >> 6;
+    if (lane == 0) ws[wid] = __popcll(m);
+    __syncthreads();
+    int off = __popcll(m & ((1ull << lane) - 1ull));
+    total = 0;
+    for (int w = 0; w < MT_TILE / 64; w++) {
+        const int c = ws[w];
+        if (w < wid) off += c;
+        total += c;
+    }
+    return off;
+}
+
+template <class Src>
+__global__ void __launch_bounds__(MT_TILE) mt_count_kernel(Src s, int n, int* __restrict__ tile_cnt) {
+    __shared__ int ws[MT_TILE / 64];
+    const long long i = (long long)blockIdx.x * MT_TILE + threadIdx.x;
+    const bool keep = i < n && s.keep((int)i);
+    int total;
+    mt_tile_offset(keep, threadIdx.x, ws, total);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(MT_SCAN_CHUNK) mt_scan_kernel(int n_tiles, int* __restrict__ tile_cnt, int* __restrict__ total_out) {
+    __shared__ int ws[MT_SCAN_CHUNK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int run = 0;
+    for (int b0 = 0; b0 < n_tiles; b0 += MT_SCAN_CHUNK) {
+        const int t = b0 + tid;
+        const int c = t < n_tiles ? tile_cnt[t] : 0;
+        const int inc = wave_incl_scan_i32(c);
+        __syncthreads();   // (the previous round's sums have been read)
+        if (lane == 63) ws[wid] = inc;
+        __syncthreads();
+        int off = inc - c, tot = 0;
+        for (int w = 0; w < MT_SCAN_CHUNK / 64; w++) {
+            if (w < wid) off += ws[w];
+            tot += ws[w];
+        }
+        if (t < n_tiles) tile_cnt[t] = run + off;
+        run += tot;
+    }
+    if (tid == 0) *total_out = run;
+}
+
+template <class Src>
+__global__ void __launch_bounds__(MT_TILE) mt_scatter_kernel(Src s, int n, const int* __restrict__ tile_off) {
+    __shared__ int ws[MT_TILE / 64];
+    const long long i = (long long)blockIdx.x * MT_TILE + threadIdx.x;
+    const bool keep = i < n && s.keep((int)i);
+    int total;
+    const int off = mt_tile_offset(keep, threadIdx.x, ws, total);
+    if (i >= n) return;
+    if (keep) s.put((int)i, tile_off[blockIdx.x] + off);
+    else s.drop((int)i);
+}
+
+static inline int mt_tiles(int n) { return (int)(((long long)n + MT_TILE - 1) / MT_TILE); }
+// rows [0, n) of s, kept ones in order; *total (zeroed by the caller) = how many.  tile_cnt: room for mt_tiles(n)
+template <class Src>
+static void mt_compact(hipStream_t st, const Src& s, int n, int* tile_cnt, int* total) {
+    if (n == 0) return;
+    const int tiles = mt_tiles(n);
+    hipLaunchKernelGGL(mt_count_kernel<Src>, dim3(tiles), dim3(MT_TILE), 0, st, s, n, tile_cnt);
+    hipLaunchKernelGGL(mt_scan_kernel, dim3(1), dim3(MT_SCAN_CHUNK), 0, st, tiles, tile_cnt, total);
+    hipLaunchKernelGGL(mt_scatter_kernel<Src>, dim3(tiles), dim3(MT_TILE), 0, st, s, n, (const int*)tile_cnt);
+}
+
+// ---- the row sources -----------------------------------------------------------------------------------------------------------
+struct MtUnflaggedRows {   // the measurement rows no outlier erases
+    const uint8_t* flag;
+    const ptam_map_meas* in;
+    ptam_map_meas* out;
+    __device__ bool keep(int i) const { return flag[i] == 0; }
+    __device__ void put(int i, int at) const { out[at] = in[i]; }
+    __device__ void drop(int) const {}
+};
+struct MtNeverRows {   // the rows flagged NEVER_RETRY, as pairs: sorted, because they are rows of a sorted table
+    const uint8_t* flag;
+    const ptam_map_meas* in;
+    ptam_map_pair* out;
+    __device__ bool keep(int i) const { return flag[i] == PTAM_MAP_OUT_NEVER_RETRY; }
+    __device__ void put(int i, int at) const {
+        ptam_map_pair q;
+        q.kf = in[i].kf;
+        q.point = in[i].point;
+        out[at] = q;
+    }
+    __device__ void drop(int) const {}
+};
+struct MtFailureOutliers {   // the outliers that go to the failure queue, in list order
+    const ptam_map_outlier* in;
+    ptam_map_pair* out;
+    __device__ bool keep(int i) const { return in[i].action == PTAM_MAP_OUT_FAILURE_QUEUE; }
+    __device__ void put(int i, int at) const {
+        ptam_map_pair q;
+        q.kf = in[i].kf;
+        q.point = in[i].point;
+        out[at] = q;
+    }
+    __device__ void drop(int) const {}
+};
+struct MtPoints {   // the exclusive scan over the points: new_index and kept
+    const uint8_t* removed;
+    int32_t* new_index;
+    int32_t* kept;
+    __device__ bool keep(int i) const { return removed[i] == 0; }
+    __device__ void put(int i, int at) const {
+        new_index[i] = at;
+        kept[at] = i;
+    }
+    __device__ void drop(int i) const { new_index[i] = -1; }
+};
+template <class Row>
+struct MtRemapRows {   // the rows of surviving points, `point` rewritten (ptam_map_meas, ptam_map_pair)
+    const int32_t* new_index;
+    const Row* in;
+    Row* out;
+    __device__ bool keep(int i) const { return new_index[in[i].point] >= 0; }
+    __device__ void put(int i, int at) const {
+        Row r = in[i];
+        r.point = new_index[r.point];
+        out[at] = r;
+    }
+    __device__ void drop(int) const {}
+};
+struct MtRemapQueue {   // mqNewQueue
+    const int32_t* new_index;
+    const int32_t* in;
+    int32_t* out;
+    __device__ bool keep(int i) const { return new_index[in[i]] >= 0; }
+    __device__ void put(int i, int at) const { out[at] = new_index[in[i]]; }
+    __device__ void drop(int) const {}
+};
+
+// ---- the kernels around it -----------------------------------------------------------------------------------------------------
+// :916-932, one thread per outlier: the row's flag (no row is named twice) and bBad (the same byte may be set more than once)
+__global__ void __launch_bounds__(256) mt_outliers_kernel(int n, const ptam_map_outlier* __restrict__ o, uint8_t* __restrict__ flag,
+                                                           uint8_t* __restrict__ bad) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const ptam_map_outlier r = o[i];
+    if (r.action == PTAM_MAP_OUT_POINT_BAD) bad[r.point] = 1;
+    else flag[r.meas] = (uint8_t)r.action;
+}
+
+// out = A (sorted) merged with B (sorted, *nB_ptr rows); no key is in both: each row placed by a binary search in the other list
+// (the rule of maprefind.hip's mr_merge_kernel)
+__global__ void __launch_bounds__(256) mt_merge_kernel(int nA, const ptam_map_pair* __restrict__ A, const int* __restrict__ nB_ptr,
+                                                        const ptam_map_pair* __restrict__ B, ptam_map_pair* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int nB = *nB_ptr;
+    if (t >= (long long)nA + nB) return;
+    const bool fromA = t < nA;
+    const int j = fromA ? (int)t : (int)(t - nA);
+    const ptam_map_pair r = fromA ? A[j] : B[j];
+    const ptam_map_pair* other = fromA ? B : A;
+    const unsigned long long key = mt_key(r.kf, r.point);
+    int lo = 0, hi = fromA ? nB : nA;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (mt_key(other[mid].kf, other[mid].point) < key) lo = mid + 1;
+        else hi = mid;
+    }
+    out[(size_t)j + (size_t)lo] = r;
+}
+
+// :136, one thread per point
+__global__ void __launch_bounds__(256) mt_mark_kernel(int n, const uint8_t* __restrict__ bad, const int32_t* __restrict__ n_out,
+                                                       const int32_t* __restrict__ n_in, uint8_t* __restrict__ removed, int* __restrict__ n_marked) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool b = false, m = false;
+    if (i < n) {
+        b = bad && bad[i] != 0;
+        m = n_out && n_out[i] > 20 && n_out[i] > n_in[i];
+        removed[i] = b || m;
+    }
+    const unsigned long long newly = __ballot(m && !b);
+    if ((threadIdx.x & 63) == 0 && newly) atomicAdd(n_marked, __popcll(newly));
+}
+
+// a point-side column, survivors to the front: threads over (surviving row, dword)
+__global__ void __launch_bounds__(256) mt_gather_kernel(const int* __restrict__ n_kept_ptr, const int32_t* __restrict__ kept, int dwords,
+                                                         const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+    const long long total = (long long)*n_kept_ptr * dwords, step = (long long)gridDim.x * 256;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += step) {
+        const long long j = t / dwords;
+        out[t] = in[(long long)kept[j] * dwords + (t - j * dwords)];
+    }
+}
+
+struct MtAdd {
+    int n_meas, n_made, n_points;
+    int a, b;                 // rows of meas before the two insertions: the ends of the lower / the higher keyframe's run
+    int kf_lo, kf_hi;         // the two keyframes, ascending
+    int src_is_lo, target_source;
+    const ptam_map_meas* meas;
+    const ptam_new_map_point* made;
+    ptam_map_meas* out;
+    int src_kf;
+    ptam_map_refind_point* points;
+    ptam_map_point_source* sources;
+};
+// :673-682 / :352-362, one thread per output row: meas[0, a) | the lower keyframe's new rows | meas[a, b) | the higher one's | meas[b, n)
+__global__ void __launch_bounds__(256) mt_add_rows_kernel(MtAdd p) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)p.n_meas + 2ll * p.n_made) return;
+    int old_row = -1, made_row = 0, lo = 0;
+    if (t < p.a) old_row = (int)t;
+    else if (t < (long long)p.a + p.n_made) made_row = (int)(t - p.a), lo = 1;
+    else if (t < (long long)p.b + p.n_made) old_row = (int)(t - p.n_made);
+    else if (t < (long long)p.b + 2ll * p.n_made) made_row = (int)(t - p.b - p.n_made);
+    else old_row = (int)(t - 2ll * p.n_made);
+    ptam_map_meas m;
+    if (old_row >= 0) m = p.meas[old_row];
+    else {
+        const ptam_new_map_point& q = p.made[made_row];
+        const bool src = lo == p.src_is_lo;
+        m.kf = lo ? p.kf_lo : p.kf_hi;
+        m.point = p.n_points + made_row;
+        m.level = q.level;
+        m.source = src ? (int)PTAM_MAP_SRC_ROOT : p.target_source;
+        m.root_pos[0] = src ? q.src_root_pos[0] : q.target_pos[0];
+        m.root_pos[1] = src ? q.src_root_pos[1] : q.target_pos[1];
+    }
+    p.out[t] = m;
+}
+// :651-666, one thread per new point: the point-side rows
+__global__ void __launch_bounds__(256) mt_add_points_kernel(MtAdd p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.n_made) return;
+    const ptam_new_map_point& q = p.made[i];
+    if (p.points) {
+        ptam_map_refind_point r;
+        r.pv = q.point;
+        r.src_kf = p.src_kf;
+        r.src_level = q.level;
+        r.center_x = q.center_x;
+        r.center_y = q.center_y;
+        r.bad = 0;
+        r.pad_ = 0;
+        p.points[i] = r;
+    }
+    if (p.sources) {
+        ptam_map_point_source s;
+        s.src_kf = p.src_kf;
+        s.pad_ = 0;
+        for (int j = 0; j < 3; j++) {
+            s.center_nc[j] = q.center_nc[j];
+            s.one_right_nc[j] = q.one_right_nc[j];
+            s.one_down_nc[j] = q.one_down_nc[j];
+        }
+        p.sources[i] = s;
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+static inline size_t mt_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct MtCarve {   // offsets into the context's scratch
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t at = off;
+        off += mt_up256(bytes > 0 ? bytes : 1);
+        return at;
+    }
+};
+template <class Row>
+static bool mt_sorted_in_range(int n, const Row* t, int n_kf, int n_points) {
+    for (int i = 0; i < n; i++) {
+        if (t[i].kf < 0 || t[i].kf >= n_kf || t[i].point < 0 || t[i].point >= n_points) return false;
+        if (i > 0 && !(t[i - 1].kf < t[i].kf || (t[i - 1].kf == t[i].kf && t[i - 1].point < t[i].point))) return false;
+    }
+    return true;
+}
+static bool mt_meas_valid(int n, const ptam_map_meas* m, int n_kf, int n_points) {
+    if (!mt_sorted_in_range(n, m, n_kf, n_points)) return false;
+    for (int i = 0; i < n; i++)
+        if (m[i].level < 0 || m[i].level >= PTAM_LEVELS || m[i].source < PTAM_MAP_SRC_TRACKER || m[i].source > PTAM_MAP_SRC_EPIPOLAR) return false;
+    return true;
+}
+static bool mt_pairs_in_range(int n, const ptam_map_pair* q, int n_kf, int n_points) {
+    for (int i = 0; i < n; i++)
+        if (q[i].kf < 0 || q[i].kf >= n_kf || q[i].point < 0 || q[i].point >= n_points) return false;
+    return true;
+}
+static inline bool mt_pair_less(const ptam_map_pair& x, const ptam_map_pair& y) { return x.kf < y.kf || (x.kf == y.kf && x.point < y.point); }
+#define MT_UP(dst, src, bytes)                                                                   \
+    do {                                                                                         \
+        if ((bytes) > 0) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, st)); \
+    } while (0)
+#define MT_DOWN(dst, src, bytes)                                                                 \
+    do {                                                                                         \
+        if ((bytes) > 0) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, st)); \
+    } while (0)
+
+extern "C" int ptam_map_apply_outliers(ptam_ctx* ctx, int n_kf, int n_points, int n_meas, const ptam_map_meas* meas, int n_never,
+                                       const ptam_map_pair* never, int n_failure, const ptam_map_pair* failure, int n_outliers,
+                                       const ptam_map_outlier* outliers, uint8_t* bad, ptam_map_outliers_result* res,
+                                       ptam_map_meas* meas_out, ptam_map_pair* never_out, ptam_map_pair* failure_out) {
+    // ---- refusals: nothing is written and nothing enqueued before all of them have passed
+    ARG_TRY(ctx && res);
+    ARG_TRY(n_kf >= 0 && n_points >= 0 && n_meas >= 0 && n_never >= 0 && n_failure >= 0 && n_outliers >= 0);
+    ARG_TRY((long long)n_never + n_outliers < (1ll << 31) && (long long)n_failure + n_outliers < (1ll << 31));
+    ARG_TRY((n_meas == 0 || (meas && meas_out)) && (n_never == 0 || never) && (n_failure == 0 || failure) && (n_outliers == 0 || outliers) &&
+            (n_points == 0 || bad));
+    ARG_TRY((n_never + n_outliers == 0 || never_out) && (n_failure + n_outliers == 0 || failure_out));
+    ARG_TRY(mt_meas_valid(n_meas, meas, n_kf, n_points));
+    ARG_TRY(mt_sorted_in_range(n_never, never, n_kf, n_points));
+    ARG_TRY(mt_pairs_in_range(n_failure, failure, n_kf, n_points));
+    ptam_map_outliers_result r = {};
+    {
+        std::vector<uint8_t> named((size_t)n_meas, 0);
+        for (int i = 0; i < n_outliers; i++) {
+            const ptam_map_outlier& o = outliers[i];
+            ARG_TRY(o.action >= PTAM_MAP_OUT_POINT_BAD && o.action <= PTAM_MAP_OUT_NEVER_RETRY);
+            ARG_TRY(o.meas >= 0 && o.meas < n_meas && meas[o.meas].kf == o.kf && meas[o.meas].point == o.point);
+            ARG_TRY(!named[(size_t)o.meas]);
+            named[(size_t)o.meas] = 1;
+            if (o.action == PTAM_MAP_OUT_NEVER_RETRY) {
+                ptam_map_pair q;
+                q.kf = o.kf;
+                q.point = o.point;
+                ARG_TRY(!std::binary_search(never, never + n_never, q, mt_pair_less));   // :947-948: no pair is in both sets
+                r.n_never_added++;
+            } else if (o.action == PTAM_MAP_OUT_FAILURE_QUEUE)
+                r.n_failure_added++;
+            else
+                r.n_point_bad++;
+        }
+    }
+    r.n_meas_out = n_meas - r.n_failure_added - r.n_never_added;
+    r.n_never_out = n_never + r.n_never_added;
+    r.n_failure_out = n_failure + r.n_failure_added;
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    // ---- device memory
+    const size_t Mz = (size_t)n_meas, Vz = (size_t)n_never, Oz = (size_t)n_outliers, Nz = (size_t)n_points;
+    MtCarve c;
+    const size_t o_meas = c.take(Mz * sizeof(ptam_map_meas)), o_never = c.take(Vz * sizeof(ptam_map_pair)),
+                 o_outl = c.take(Oz * sizeof(ptam_map_outlier)), o_bad = c.take(Nz), o_flag = c.take(Mz), o_tot = c.take(3 * sizeof(int)),
+                 o_tiles = c.take((size_t)mt_tiles(std::max(n_meas, n_outliers)) * sizeof(int)), o_mo = c.take(Mz * sizeof(ptam_map_meas)),
+                 o_nn = c.take(Oz * sizeof(ptam_map_pair)), o_no = c.take((Vz + Oz) * sizeof(ptam_map_pair)), o_fo = c.take(Oz * sizeof(ptam_map_pair));
+    void* sc;
+    if (int rc = ctx_scratch(ctx, c.off, &sc)) return rc;
+    char* b = (char*)sc;
+    hipStream_t st = ctx->stream;
+    MT_UP(b + o_meas, meas, Mz * sizeof(ptam_map_meas));
+    MT_UP(b + o_never, never, Vz * sizeof(ptam_map_pair));
+    MT_UP(b + o_outl, outliers, Oz * sizeof(ptam_map_outlier));
+    MT_UP(b + o_bad, bad, Nz);
+    HIP_TRY(hipMemsetAsync(b + o_flag, 0, Mz > 0 ? Mz : 1, st));
+    HIP_TRY(hipMemsetAsync(b + o_tot, 0, 3 * sizeof(int), st));
+    int* tot = (int*)(b + o_tot);
+    int* tiles = (int*)(b + o_tiles);
+    const ptam_map_meas* d_meas = (const ptam_map_meas*)(b + o_meas);
+    const uint8_t* d_flag = (const uint8_t*)(b + o_flag);
+
+    // ---- the flags, the three compactions, the merge
+    if (n_outliers > 0)
+        hipLaunchKernelGGL(mt_outliers_kernel, dim3((n_outliers + 255) / 256), dim3(256), 0, st, n_outliers, (const ptam_map_outlier*)(b + o_outl),
+                           (uint8_t*)(b + o_flag), (uint8_t*)(b + o_bad));
+    mt_compact(st, MtUnflaggedRows{d_flag, d_meas, (ptam_map_meas*)(b + o_mo)}, n_meas, tiles, tot + 0);
+    mt_compact(st, MtNeverRows{d_flag, d_meas, (ptam_map_pair*)(b + o_nn)}, n_meas, tiles, tot + 1);
+    mt_compact(st, MtFailureOutliers{(const ptam_map_outlier*)(b + o_outl), (ptam_map_pair*)(b + o_fo)}, n_outliers, tiles, tot + 2);
+    if (r.n_never_out > 0)
+        hipLaunchKernelGGL(mt_merge_kernel, dim3((unsigned)(((long long)r.n_never_out + 255) / 256)), dim3(256), 0, st, n_never,
+                           (const ptam_map_pair*)(b + o_never), (const int*)(tot + 1), (const ptam_map_pair*)(b + o_nn), (ptam_map_pair*)(b + o_no));
+    HIP_TRY(hipGetLastError());
+
+    // ---- down: every size is known from the outlier list
+    MT_DOWN(meas_out, b + o_mo, (size_t)r.n_meas_out * sizeof(ptam_map_meas));
+    MT_DOWN(never_out, b + o_no, (size_t)r.n_never_out * sizeof(ptam_map_pair));
+    MT_DOWN(failure_out + n_failure, b + o_fo, (size_t)r.n_failure_added * sizeof(ptam_map_pair));
+    MT_DOWN(bad, b + o_bad, Nz);
+    HIP_TRY(ptam_stream_wait(st));
+    if (n_failure > 0) std::memcpy(failure_out, failure, (size_t)n_failure * sizeof(ptam_map_pair));   // the old queue never left the host
+    *res = r;
+    return PTAM_OK;
+}
+
+extern "C" int ptam_map_handle_bad_points(ptam_ctx* ctx, int n_kf, int n_points, const uint8_t* bad, const int32_t* outlier_count,
+                                          const int32_t* inlier_count, int n_meas, const ptam_map_meas* meas, int n_never,
+                                          const ptam_map_pair* never, int n_new, const int32_t* new_queue, int n_failure,
+                                          const ptam_map_pair* failure, int n_columns, const ptam_map_column* columns,
+                                          ptam_map_bad_points_result* res, int32_t* new_index, int32_t* kept, ptam_map_meas* meas_out,
+                                          ptam_map_pair* never_out, int32_t* new_queue_out, ptam_map_pair* failure_out) {
+    // ---- refusals
+    ARG_TRY(ctx && res);
+    ARG_TRY(n_kf >= 0 && n_points >= 0 && n_meas >= 0 && n_never >= 0 && n_new >= 0 && n_failure >= 0);
+    ARG_TRY(n_columns >= 0 && n_columns <= PTAM_MAP_MAX_COLUMNS && (n_columns == 0 || columns));
+    ARG_TRY((outlier_count != nullptr) == (inlier_count != nullptr));
+    ARG_TRY((n_points == 0 || (new_index && kept)) && (n_meas == 0 || (meas && meas_out)) && (n_never == 0 || (never && never_out)) &&
+            (n_new == 0 || (new_queue && new_queue_out)) && (n_failure == 0 || (failure && failure_out)));
+    for (int k = 0; k < n_columns; k++)
+        ARG_TRY(columns[k].row_bytes > 0 && columns[k].row_bytes % 4 == 0 && (n_points == 0 || columns[k].data));
+    ARG_TRY(mt_meas_valid(n_meas, meas, n_kf, n_points));
+    ARG_TRY(mt_sorted_in_range(n_never, never, n_kf, n_points));
+    ARG_TRY(mt_pairs_in_range(n_failure, failure, n_kf, n_points));
+    {
+        std::vector<uint8_t> seen((size_t)n_points, 0);
+        for (int e = 0; e < n_new; e++) {
+            ARG_TRY(new_queue[e] >= 0 && new_queue[e] < n_points && !seen[(size_t)new_queue[e]]);
+            seen[(size_t)new_queue[e]] = 1;
+        }
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    // ---- device memory
+    enum { T_KEPT = 0, T_MEAS, T_NEVER, T_NEW, T_FAIL, T_MARKED, T_COUNT };
+    const size_t Nz = (size_t)n_points, Mz = (size_t)n_meas, Vz = (size_t)n_never, Qz = (size_t)n_new, Fz = (size_t)n_failure;
+    const int longest = std::max(std::max(n_points, n_meas), std::max(std::max(n_never, n_new), n_failure));
+    MtCarve c;
+    const size_t o_bad = c.take(bad ? Nz : 0), o_cnt_o = c.take(outlier_count ? Nz * 4 : 0), o_cnt_i = c.take(outlier_count ? Nz * 4 : 0),
+                 o_meas = c.take(Mz * sizeof(ptam_map_meas)), o_never = c.take(Vz * sizeof(ptam_map_pair)), o_new = c.take(Qz * 4),
+                 o_fail = c.take(Fz * sizeof(ptam_map_pair)), o_rem = c.take(Nz), o_tot = c.take(T_COUNT * sizeof(int)),
+                 o_tiles = c.take((size_t)mt_tiles(longest) * sizeof(int)), o_ni = c.take(Nz * 4), o_kept = c.take(Nz * 4),
+                 o_mo = c.take(Mz * sizeof(ptam_map_meas)), o_no = c.take(Vz * sizeof(ptam_map_pair)), o_qo = c.take(Qz * 4),
+                 o_fo = c.take(Fz * sizeof(ptam_map_pair));
+    size_t o_cin[PTAM_MAP_MAX_COLUMNS], o_cout[PTAM_MAP_MAX_COLUMNS];
+    for (int k = 0; k < n_columns; k++) {
+        o_cin[k] = c.take(Nz * (size_t)columns[k].row_bytes);
+        o_cout[k] = c.take(Nz * (size_t)columns[k].row_bytes);
+    }
+    void *sc, *hp;
+    if (int rc = ctx_scratch(ctx, c.off, &sc)) return rc;
+    if (int rc = ctx_pinned(ctx, 256, &hp)) return rc;
+    char* b = (char*)sc;
+    hipStream_t st = ctx->stream;
+    if (bad) MT_UP(b + o_bad, bad, Nz);
+    if (outlier_count) {
+        MT_UP(b + o_cnt_o, outlier_count, Nz * 4);
+        MT_UP(b + o_cnt_i, inlier_count, Nz * 4);
+    }
+    MT_UP(b + o_meas, meas, Mz * sizeof(ptam_map_meas));
+    MT_UP(b + o_never, never, Vz * sizeof(ptam_map_pair));
+    MT_UP(b + o_new, new_queue, Qz * 4);
+    MT_UP(b + o_fail, failure, Fz * sizeof(ptam_map_pair));
+    for (int k = 0; k < n_columns; k++) MT_UP(b + o_cin[k], columns[k].data, Nz * (size_t)columns[k].row_bytes);
+    HIP_TRY(hipMemsetAsync(b + o_tot, 0, T_COUNT * sizeof(int), st));
+    int* tot = (int*)(b + o_tot);
+    int* tiles = (int*)(b + o_tiles);
+    const int32_t* d_ni = (const int32_t*)(b + o_ni);
+
+    // ---- mark, scan the points, compact every table and queue through the remap, gather the columns
+    if (n_points > 0)
+        hipLaunchKernelGGL(mt_mark_kernel, dim3((unsigned)(((long long)n_points + 255) / 256)), dim3(256), 0, st, n_points,
+                           bad ? (const uint8_t*)(b + o_bad) : nullptr, outlier_count ? (const int32_t*)(b + o_cnt_o) : nullptr,
+                           outlier_count ? (const int32_t*)(b + o_cnt_i) : nullptr, (uint8_t*)(b + o_rem), tot + T_MARKED);
+    mt_compact(st, MtPoints{(const uint8_t*)(b + o_rem), (int32_t*)(b + o_ni), (int32_t*)(b + o_kept)}, n_points, tiles, tot + T_KEPT);
+    mt_compact(st, MtRemapRows<ptam_map_meas>{d_ni, (const ptam_map_meas*)(b + o_meas), (ptam_map_meas*)(b + o_mo)}, n_meas, tiles, tot + T_MEAS);
+    mt_compact(st, MtRemapRows<ptam_map_pair>{d_ni, (const ptam_map_pair*)(b + o_never), (ptam_map_pair*)(b + o_no)}, n_never, tiles, tot + T_NEVER);
+    mt_compact(st, MtRemapQueue{d_ni, (const int32_t*)(b + o_new), (int32_t*)(b + o_qo)}, n_new, tiles, tot + T_NEW);
+    mt_compact(st, MtRemapRows<ptam_map_pair>{d_ni, (const ptam_map_pair*)(b + o_fail), (ptam_map_pair*)(b + o_fo)}, n_failure, tiles, tot + T_FAIL);
+    for (int k = 0; k < n_columns && n_points > 0; k++) {
+        const int dwords = columns[k].row_bytes / 4;
+        const long long blocks = ((long long)n_points * dwords + 255) / 256;
+        hipLaunchKernelGGL(mt_gather_kernel, dim3((unsigned)std::min(blocks, 1ll << 20)), dim3(256), 0, st, (const int*)(tot + T_KEPT),
+                           (const int32_t*)(b + o_kept), dwords, (const uint32_t*)(b + o_cin[k]), (uint32_t*)(b + o_cout[k]));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hp, tot, T_COUNT * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ptam_stream_wait(st));   // the counts say how much of each table to fetch
+    const int* hc = (const int*)hp;
+    ptam_map_bad_points_result r = {};
+    r.n_marked = hc[T_MARKED];
+    r.n_kept = hc[T_KEPT];
+    r.n_removed = n_points - r.n_kept;
+    r.n_meas_out = hc[T_MEAS];
+    r.n_never_out = hc[T_NEVER];
+    r.n_new_out = hc[T_NEW];
+    r.n_new_dropped = n_new - r.n_new_out;
+    r.n_failure_out = hc[T_FAIL];
+    MT_DOWN(new_index, b + o_ni, Nz * 4);
+    MT_DOWN(kept, b + o_kept, (size_t)r.n_kept * 4);
+    MT_DOWN(meas_out, b + o_mo, (size_t)r.n_meas_out * sizeof(ptam_map_meas));
+    MT_DOWN(never_out, b + o_no, (size_t)r.n_never_out * sizeof(ptam_map_pair));
+    MT_DOWN(new_queue_out, b + o_qo, (size_t)r.n_new_out * 4);
+    MT_DOWN(failure_out, b + o_fo, (size_t)r.n_failure_out * sizeof(ptam_map_pair));
+    for (int k = 0; k < n_columns; k++) MT_DOWN(columns[k].data, b + o_cout[k], (size_t)r.n_kept * (size_t)columns[k].row_bytes);
+    HIP_TRY(ptam_stream_wait(st));
+    *res = r;
+    return PTAM_OK;
+}
+
+extern "C" int ptam_map_add_points(ptam_ctx* ctx, int n_kf, int n_points, int n_meas, const ptam_map_meas* meas, int src_kf, int target_kf,
+                                   int target_source, int n_made, const ptam_new_map_point* made, ptam_map_meas* meas_out,
+                                   ptam_map_refind_point* points_out, ptam_map_point_source* sources_out) {
+    // ---- refusals
+    ARG_TRY(ctx);
+    ARG_TRY(n_kf >= 0 && n_points >= 0 && n_meas >= 0 && n_made >= 0);
+    ARG_TRY((long long)n_points + n_made < (1ll << 31) && (long long)n_meas + 2ll * n_made < (1ll << 31));
+    ARG_TRY((n_meas == 0 || meas) && (n_made == 0 || made) && (n_meas + n_made == 0 || meas_out));
+    ARG_TRY(src_kf >= 0 && src_kf < n_kf && target_kf >= 0 && target_kf < n_kf && src_kf != target_kf);
+    ARG_TRY(target_source >= PTAM_MAP_SRC_TRACKER && target_source <= PTAM_MAP_SRC_EPIPOLAR);
+    ARG_TRY(mt_meas_valid(n_meas, meas, n_kf, n_points));
+    for (int i = 0; i < n_made; i++) ARG_TRY(made[i].level >= 0 && made[i].level < PTAM_LEVELS);
+    if (n_made == 0) {   // nothing to insert: the table is a copy
+        if (n_meas > 0) std::memcpy(meas_out, meas, (size_t)n_meas * sizeof(ptam_map_meas));
+        return PTAM_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    MtAdd p;
+    p.n_meas = n_meas;
+    p.n_made = n_made;
+    p.n_points = n_points;
+    p.kf_lo = std::min(src_kf, target_kf);
+    p.kf_hi = std::max(src_kf, target_kf);
+    p.src_is_lo = src_kf < target_kf;
+    p.src_kf = src_kf;
+    p.target_source = target_source;
+    const auto run_end = [&](int kf) {   // the new indices exceed all old ones: the end of the keyframe's run
+        return (int)(std::upper_bound(meas, meas + n_meas, kf, [](int k, const ptam_map_meas& m) { return k < m.kf; }) - meas);
+    };
+    p.a = run_end(p.kf_lo);
+    p.b = run_end(p.kf_hi);
+
+    const size_t Mz = (size_t)n_meas, Az = (size_t)n_made;
+    MtCarve c;
+    const size_t o_meas = c.take(Mz * sizeof(ptam_map_meas)), o_made = c.take(Az * sizeof(ptam_new_map_point)),
+                 o_mo = c.take((Mz + 2 * Az) * sizeof(ptam_map_meas)), o_pts = c.take(points_out ? Az * sizeof(ptam_map_refind_point) : 0),
+                 o_src = c.take(sources_out ? Az * sizeof(ptam_map_point_source) : 0);
+    void* sc;
+    if (int rc = ctx_scratch(ctx, c.off, &sc)) return rc;
+    char* b = (char*)sc;
+    hipStream_t st = ctx->stream;
+    MT_UP(b + o_meas, meas, Mz * sizeof(ptam_map_meas));
+    MT_UP(b + o_made, made, Az * sizeof(ptam_new_map_point));
+    p.meas = (const ptam_map_meas*)(b + o_meas);
+    p.made = (const ptam_new_map_point*)(b + o_made);
+    p.out = (ptam_map_meas*)(b + o_mo);
+    p.points = points_out ? (ptam_map_refind_point*)(b + o_pts) : nullptr;
+    p.sources = sources_out ? (ptam_map_point_source*)(b + o_src) : nullptr;
+    hipLaunchKernelGGL(mt_add_rows_kernel, dim3((unsigned)(((long long)n_meas + 2ll * n_made + 255) / 256)), dim3(256), 0, st, p);
+    if (points_out || sources_out) hipLaunchKernelGGL(mt_add_points_kernel, dim3((n_made + 255) / 256), dim3(256), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    MT_DOWN(meas_out, b + o_mo, (Mz + 2 * Az) * sizeof(ptam_map_meas));
+    if (points_out) MT_DOWN(points_out, b + o_pts, Az * sizeof(ptam_map_refind_point));
+    if (sources_out) MT_DOWN(sources_out, b + o_src, Az * sizeof(ptam_map_point_source));
+    HIP_TRY(ptam_stream_wait(st));
+    return PTAM_OK;
+}
+
+void maptables_preload_kernels() {
+    ptam_preload((const void*)mt_scan_kernel);
+    ptam_preload((const void*)mt_count_kernel<MtUnflaggedRows>);
+    ptam_preload((const void*)mt_scatter_kernel<MtUnflaggedRows>);
+    ptam_preload((const void*)mt_count_kernel<MtNeverRows>);
+    ptam_preload((const void*)mt_scatter_kernel<MtNeverRows>);
+    ptam_preload((const void*)mt_count_kernel<MtFailureOutliers>);
+    ptam_preload((const void*)mt_scatter_kernel<MtFailureOutliers>);
+    ptam_preload((const void*)mt_count_kernel<MtPoints>);
+    ptam_preload((const void*)mt_scatter_kernel<MtPoints>);
+    ptam_preload((const void*)mt_count_kernel<MtRemapRows<ptam_map_meas>>);
+    ptam_preload((const void*)mt_scatter_kernel<MtRemapRows<ptam_map_meas>>);
+    ptam_preload((const void*)mt_count_kernel<MtRemapRows<ptam_map_pair>>);
+    ptam_preload((const void*)mt_scatter_kernel<MtRemapRows<ptam_map_pair>>);
+    ptam_preload((const void*)mt_count_kernel<MtRemapQueue>);
+    ptam_preload((const void*)mt_scatter_kernel<MtRemapQueue>);
+    ptam_preload((const void*)mt_outliers_kernel);
+    ptam_preload((const void*)mt_merge_kernel);
+    ptam_preload((const void*)mt_mark_kernel);
+    ptam_preload((const void*)mt_gather_kernel);
+    ptam_preload((const void*)mt_add_rows_kernel);
+    ptam_preload((const void*)mt_add_points_kernel);
+}

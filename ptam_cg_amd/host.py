@@ -763,6 +763,98 @@ def map_refind(ctx, finder, mode, kfs, poses, points, meas, never, work, stop=No
     return d
 
 
+assert C.sizeof(_abi.MapColumn) == 16 and C.sizeof(_abi.MapOutliersResult) == 24 and C.sizeof(_abi.MapBadPointsResult) == 32
+
+
+def _counts(res):
+    return {f: getattr(res, f) for f, _ in type(res)._fields_}
+
+
+def map_apply_outliers(ctx, n_kf, bad, meas, never, failure, outliers):
+    """the outlier loop of MapMaker::BundleAdjust (src/MapMaker.cc:916-932) on the map tables in ONE device call
+    (ptam_map_apply_outliers): bad (N,) uint8 bBad, meas MAP_MEAS_DT and never MAP_PAIR_DT sorted by (kf, point), failure
+    MAP_PAIR_DT (mvFailureQueue as it stands), outliers MAP_OUTLIER_DT as map_bundle_adjust returned them for this meas.  The
+    inputs are not modified; -> dict with the result counts and the tables after the call: "bad", "meas", "never" (sorted),
+    "failure" (the old queue, then the new pairs in outlier order)."""
+    bad = np.array(bad, dtype=np.uint8).reshape(-1)
+    meas = np.ascontiguousarray(meas, dtype=MAP_MEAS_DT)
+    never = np.ascontiguousarray(never, dtype=MAP_PAIR_DT)
+    failure = np.ascontiguousarray(failure, dtype=MAP_PAIR_DT)
+    outliers = np.ascontiguousarray(outliers, dtype=MAP_OUTLIER_DT)
+    N, M, V, F, O = len(bad), len(meas), len(never), len(failure), len(outliers)
+    mo, no, fo = np.zeros(max(M, 1), MAP_MEAS_DT), np.zeros(max(V + O, 1), MAP_PAIR_DT), np.zeros(max(F + O, 1), MAP_PAIR_DT)
+    res = _abi.MapOutliersResult()
+    ctx._check(ctx.lib.map_apply_outliers(ctx.h, int(n_kf), N, M, _ptr(meas), V, _ptr(never), F, _ptr(failure), O, _ptr(outliers),
+                                          _ptr(bad), C.byref(res), _ptr(mo), _ptr(no), _ptr(fo)), "map_apply_outliers")
+    d = _counts(res)
+    d.update(bad=bad, meas=mo[:res.n_meas_out].copy(), never=no[:res.n_never_out].copy(), failure=fo[:res.n_failure_out].copy())
+    return d
+
+
+def map_columns(arrays):
+    """the ptam_map_column table of map_handle_bad_points for C-contiguous arrays with one row per point along axis 0 ->
+    (ctypes array, row_bytes list)"""
+    cols = (_abi.MapColumn * max(len(arrays), 1))()
+    for i, a in enumerate(arrays):
+        cols[i].data = a.ctypes.data
+        cols[i].row_bytes = a.itemsize * int(np.prod(a.shape[1:], dtype=np.int64))
+    return cols, [cols[i].row_bytes for i in range(len(arrays))]
+
+
+def map_handle_bad_points(ctx, n_kf, n_points, meas, never, bad=None, outlier_count=None, inlier_count=None, new_queue=None,
+                          failure=None, columns=()):
+    """MapMaker::HandleBadPoints with Map::MoveBadPointsToTrash (src/MapMaker.cc:131-153, src/Map.cc:20-30) on the map tables in
+    ONE device call (ptam_map_handle_bad_points): bad (N,) uint8 or None, outlier_count / inlier_count (N,) int32 or both None,
+    new_queue point indices in mqNewQueue order, failure MAP_PAIR_DT, columns a sequence of arrays with one row per point.  The
+    inputs are not modified; -> dict with the result counts, "new_index" (N,) (-1: removed), "kept" (n_kept,) (the prevIndex of
+    Tracker.update_map), the tables after the call "meas", "never", "new_queue", "failure", and "columns": copies of the columns
+    compacted in place (rows [:n_kept] are the survivors', the rows behind them are as they were)."""
+    N = int(n_points)
+    meas = np.ascontiguousarray(meas, dtype=MAP_MEAS_DT)
+    never = np.ascontiguousarray(never, dtype=MAP_PAIR_DT)
+    bad = None if bad is None else np.ascontiguousarray(bad, dtype=np.uint8).reshape(-1)
+    oc = None if outlier_count is None else np.ascontiguousarray(outlier_count, dtype=np.int32).reshape(-1)
+    ic = None if inlier_count is None else np.ascontiguousarray(inlier_count, dtype=np.int32).reshape(-1)
+    nq = np.zeros(0, np.int32) if new_queue is None else np.ascontiguousarray(new_queue, dtype=np.int32).reshape(-1)
+    fq = np.zeros(0, MAP_PAIR_DT) if failure is None else np.ascontiguousarray(failure, dtype=MAP_PAIR_DT)
+    for a in (bad, oc, ic):
+        if a is not None and len(a) != N:
+            raise ValueError("map_handle_bad_points: one entry per point")
+    cols = [np.array(c, order="C") for c in columns]
+    if any(len(c) != N for c in cols):
+        raise ValueError("map_handle_bad_points: one column row per point")
+    ctab, _ = map_columns(cols)
+    M, V, Q, F = len(meas), len(never), len(nq), len(fq)
+    ni, kept = np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.int32)
+    mo, no = np.zeros(max(M, 1), MAP_MEAS_DT), np.zeros(max(V, 1), MAP_PAIR_DT)
+    qo, fo = np.zeros(max(Q, 1), np.int32), np.zeros(max(F, 1), MAP_PAIR_DT)
+    res = _abi.MapBadPointsResult()
+    ctx._check(ctx.lib.map_handle_bad_points(ctx.h, int(n_kf), N, _ptr(bad), _ptr(oc), _ptr(ic), M, _ptr(meas), V, _ptr(never), Q, _ptr(nq),
+                                             F, _ptr(fq), len(cols), C.cast(ctab, C.c_void_p), C.byref(res), _ptr(ni), _ptr(kept), _ptr(mo),
+                                             _ptr(no), _ptr(qo), _ptr(fo)), "map_handle_bad_points")
+    d = _counts(res)
+    d.update(new_index=ni[:N].copy(), kept=kept[:res.n_kept].copy(), meas=mo[:res.n_meas_out].copy(), never=no[:res.n_never_out].copy(),
+             new_queue=qo[:res.n_new_out].copy(), failure=fo[:res.n_failure_out].copy(), columns=cols)
+    return d
+
+
+def map_add_points(ctx, n_kf, n_points, meas, src_kf, target_kf, made, target_source=_abi.SRC_EPIPOLAR):
+    """a call's new points (MapMaker.AddSomeMapPoints, target_source _abi.SRC_EPIPOLAR; init_points_from_trails, _abi.SRC_TRAIL;
+    src/MapMaker.cc:670-685, :352-362) into the map tables in ONE device call (ptam_map_add_points): made NEW_MAP_POINT_DT; new
+    point i gets index n_points + i.  The inputs are not modified; -> dict: "meas" (the table with the two rows per point
+    inserted, sorted), "points" (MAP_REFIND_POINT_DT rows of the new points), "sources" (MAP_POINT_SOURCE_DT rows) and
+    "new_queue" (their indices: mqNewQueue's new entries, in order)."""
+    meas = np.ascontiguousarray(meas, dtype=MAP_MEAS_DT)
+    made = np.ascontiguousarray(made, dtype=NEW_MAP_POINT_DT)
+    M, A = len(meas), len(made)
+    mo = np.zeros(max(M + 2 * A, 1), MAP_MEAS_DT)
+    pts, src = np.zeros(max(A, 1), MAP_REFIND_POINT_DT), np.zeros(max(A, 1), MAP_POINT_SOURCE_DT)
+    ctx._check(ctx.lib.map_add_points(ctx.h, int(n_kf), int(n_points), M, _ptr(meas), int(src_kf), int(target_kf), int(target_source), A,
+                                      _ptr(made), _ptr(mo), _ptr(pts), _ptr(src)), "map_add_points")
+    return dict(meas=mo[:M + 2 * A].copy(), points=pts[:A].copy(), sources=src[:A].copy(),
+                new_queue=np.arange(int(n_points), int(n_points) + A, dtype=np.int32))
+
+
 class Tracker:
     """Tracker::TrackMap (src/Tracker.cc:442-696) as one device-resident chain (ptam_tracker_* / ptam_track_map): the map
     stays on the device, a frame is one call."""
