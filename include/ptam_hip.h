@@ -1143,6 +1143,131 @@ int ptam_map_add_points(ptam_ctx*, int n_kf, int n_points, int n_meas, const pta
                         int target_source, int n_made, const ptam_new_map_point* made, ptam_map_meas* meas_out,
                         ptam_map_refind_point* points_out, ptam_map_point_source* sources_out);
 
+/* ---- The resident map: the tables of the ptam_map_* calls kept in device memory from call to call ------------------------------
+ *      A ptam_rmap owns, on its context's device, the keyframe side (se3CfromW, bFixed; the ptam_kf handles and a mirror of the
+ *      poses and flags stay on the host), the point side (points3, the ptam_map_refind_point rows, the ptam_map_point_source
+ *      rows, the bBad bytes, the two M-estimator counts), the measurement table and the never table, both sorted by (kf, point),
+ *      mqNewQueue as point indices and mvFailureQueue as pairs.  A resident form ptam_rmap_X does what ptam_map_X does, through the
+ *      same device kernels, on these tables: nothing proportional to a table crosses the host link, and the order and range rules
+ *      the host-table forms walk on every call are checked once, on the device, by ptam_rmap_upload.  Every resident call keeps
+ *      them, so every call finds valid tables.
+ *      Redundant columns: points3 and refind_point.pv.world, bad and refind_point.bad, source.src_kf and refind_point.src_kf
+ *      hold the same values.  ptam_rmap_upload refuses tables in which they differ; every call that writes one writes the other.
+ *      Transactions: a call that can be refused by what the device finds writes each new table into the table's second buffer
+ *      and, after its one wait has shown that no refusal was published, swaps the buffers on the host; rows appended behind a
+ *      table's count are no part of the table until the count moves, after the same wait; the bytes of bad are set in place by a
+ *      kernel that first reads the refusal word of the kernels launched before it; the accepted bundle's scatter and the count
+ *      increments are in place, in calls nothing can refuse once they run.  A refused call (PTAM_E_ARG) leaves every table and
+ *      count as it was; ptam_rmap_last_refusal names the row.
+ *      Memory: ptam_rmap_reserve sets capacities in rows; a call that needs more doubles the table (device-to-device copy) —
+ *      the only place a resident call allocates.  Work memory is the context's scratch.
+ *      All calls are synchronous and belong to the context's thread.  The same input gives the same bits.
+ *      One exception to the memory rule: ptam_rmap_bundle_adjust builds its bundle per call, as ptam_map_bundle_adjust does, from
+ *      the context's cache of released bundle blocks (no allocation once a bundle of that size has run).
+ *      The context must outlive the handle: ptam_rmap_destroy before ptam_ctx_destroy. */
+typedef struct ptam_rmap ptam_rmap;
+enum {   /* the tables, as ptam_rmap_download and ptam_rmap_last_refusal name them; one row is ... */
+    PTAM_RMAP_KF_POSES = 0,      /* 12 doubles */
+    PTAM_RMAP_KF_FIXED = 1,      /* 1 byte */
+    PTAM_RMAP_POINTS3 = 2,       /* 3 doubles */
+    PTAM_RMAP_REFIND_POINTS = 3, /* ptam_map_refind_point */
+    PTAM_RMAP_SOURCES = 4,       /* ptam_map_point_source */
+    PTAM_RMAP_BAD = 5,           /* 1 byte */
+    PTAM_RMAP_OUTLIER_COUNT = 6, /* int32 */
+    PTAM_RMAP_INLIER_COUNT = 7,  /* int32 */
+    PTAM_RMAP_MEAS = 8,          /* ptam_map_meas */
+    PTAM_RMAP_NEVER = 9,         /* ptam_map_pair */
+    PTAM_RMAP_NEW_QUEUE = 10,    /* int32 */
+    PTAM_RMAP_FAILURE = 11,      /* ptam_map_pair */
+    PTAM_RMAP_TABLES = 12,
+    PTAM_RMAP_OUTLIERS = 12      /* ptam_rmap_last_refusal only: the outlier list of ptam_rmap_apply_outliers */
+};
+typedef struct { int32_t n_kf, n_points, n_meas, n_never, n_new, n_failure; } ptam_rmap_counts_t;
+typedef struct { int32_t point, level; double root_pos[2]; } ptam_map_kf_row;   /* one measurement of a new keyframe */
+/* the bytes every resident call moves besides its arguments: the refusal and count words, down */
+enum { PTAM_RMAP_WORD_BYTES = 64 };
+/* an upper bound on the level record (image and corner-table addresses of the four levels) that ptam_rmap_refind sends per keyframe */
+enum { PTAM_RMAP_KF_RECORD_BYTES = 512 };
+
+int ptam_rmap_create(ptam_ctx*, ptam_rmap** out);   /* an empty map */
+int ptam_rmap_destroy(ptam_rmap*);
+/* capacities in rows, each at least the table's count; never shrinks.  PTAM_E_ARG: a negative capacity. */
+int ptam_rmap_reserve(ptam_rmap*, int n_kf, int n_points, int n_meas, int n_never, int n_new, int n_failure);
+int ptam_rmap_counts(const ptam_rmap*, ptam_rmap_counts_t* out);
+/* Replaces the whole map.  kfs (nullable: no handles are kept), outlier_count / inlier_count (nullable together: zeros).  The
+ * tables go up into the second buffers and are checked there by kernels, one thread per row against its predecessor and the
+ * ranges: meas and never sorted by (kf, point) with no repeated pair, kf in [0, n_kf), point in [0, n_points), level 0..3,
+ * source 0..4; failure in range; new_queue in range and without a repeated entry (a per-point owner word: atomicMin of the
+ * entry's index, then a compare — the later entry of a repeated point offends); the redundant columns equal and src_kf in
+ * range.  The lowest offending row of each table is published with atomicMin and read in the call's one wait: PTAM_E_ARG,
+ * ptam_rmap_last_refusal = the first offending table in the order meas, never, new_queue, failure, refind_points and that
+ * row, and the previous map stays as it was.  PTAM_E_ARG also for a negative count or a null table with a non-zero count. */
+int ptam_rmap_upload(ptam_rmap*, int n_kf, const ptam_kf* const* kfs, const double* kf_poses12, const uint8_t* kf_fixed, int n_points,
+                     const double* points3, const ptam_map_refind_point* points, const ptam_map_point_source* sources,
+                     const uint8_t* bad, const int32_t* outlier_count, const int32_t* inlier_count, int n_meas,
+                     const ptam_map_meas* meas, int n_never, const ptam_map_pair* never, int n_new, const int32_t* new_queue,
+                     int n_failure, const ptam_map_pair* failure);
+/* rows [first, first + count) of one table into dst.  PTAM_E_ARG: a range outside the table. */
+int ptam_rmap_download(ptam_rmap*, int which, int first, int count, void* dst);
+/* the device-decided refusal of the handle's last refused call: the table (or PTAM_RMAP_OUTLIERS) and the offending row */
+int ptam_rmap_last_refusal(const ptam_rmap*, int* table, int* row);
+/* running sums of every byte the handle's calls have copied over the host link, in either direction */
+int ptam_rmap_traffic(const ptam_rmap*, unsigned long long* h2d_bytes, unsigned long long* d2h_bytes);
+
+/* ptam_map_bundle_adjust on the resident tables: the selection, the id maps and the bundle's measurement chunks are built from
+ * the handle's buffers; the O(K) camera list is marshalled from the host mirror.  accepted > 0: the scatter kernels write the
+ * poses and points in place (nothing can refuse the call once they run), a kernel copies points3 into refind_point.pv.world,
+ * and the K poses come down into the mirror; the caller fetches them with ptam_rmap_download.  Otherwise no table is touched.
+ * The reference does not refresh the pixel vectors after a bundle (src/MapMaker.cc:895-904), and neither does this call.
+ * outliers (nullable; outlier_cap >= n_meas), cam_kf, point_ids: as ptam_map_bundle_adjust.  ptam_rmap_traffic counts what this
+ * layer copies: 32 + 4 n_kf bytes, the accepted poses, 16 bytes per outlier and point_ids down.  Up it adds a NOMINAL 97 bytes per
+ * bundle camera (pose and flag, marshalled from the mirror): the bundle object's own transfers — its camera upload, Compute()'s
+ * result words — happen inside ptam_ba_* and are not measured by the handle. */
+int ptam_rmap_bundle_adjust(ptam_rmap*, const ptam_ba_opts* opts, int mode, const volatile unsigned char* abort_flag,
+                            ptam_map_ba_result* res, ptam_map_outlier* outliers, int outlier_cap, int32_t* cam_kf, int32_t* point_ids);
+/* ptam_map_refind on the resident tables, through `finder` (its state carries from call to call as with ptam_map_refind); the
+ * keyframe handles are those given to ptam_rmap_upload / ptam_rmap_add_keyframe (PTAM_E_ARG if one is missing).  work: as
+ * ptam_map_refind, or NULL for NEW_POINTS / FAILURE_QUEUE: the resident queue is the work, and afterwards points_consumed entries
+ * are popped from the front of new_queue, or failure is cleared (src/MapMaker.cc:1080; not when the call was stopped).  The merged
+ * tables are written into the second buffers and become the map's after the call's wait.  found_out / found_subpix / never_out
+ * (nullable together; out_cap as ptam_map_refind when given) come down only when asked for.  The visiting order is the host's:
+ * the resident queue comes down (4 bytes per new_queue entry plus its point's bBad byte, 8 bytes per failure pair; for a caller's
+ * NEW_POINTS list its indices go up and a byte each comes down) and the pairs' work lists go up (8 bytes per good new point, 8
+ * per failure pair), with one level record per keyframe (at most PTAM_RMAP_KF_RECORD_BYTES); 16 bytes of counts and the lists asked for come down.  Nothing
+ * proportional to the measurement table moves. */
+int ptam_rmap_refind(ptam_rmap*, ptam_refinder*, const ptam_map_refind_opts*, int mode, int n_work, const void* work,
+                     const volatile unsigned char* stop_flag, ptam_map_refind_result* res, ptam_map_meas* found_out,
+                     int32_t* found_subpix, ptam_map_pair* never_out, int out_cap);
+/* ptam_map_apply_global_transform on the resident tables (the re-anchoring call): the poses are written into the second buffer
+ * and come down into the mirror, the points move in place, and every point's RefreshPixelVectors runs against its source
+ * keyframe's new pose straight into the point rows' pv (pv.world included).  out_rows (nullable, n_points ptam_pvs_point): the
+ * rows for ptam_tracker_set_map.  Moves 256 bytes up; 96 n_kf bytes and out_rows down. */
+int ptam_rmap_apply_global_transform(ptam_rmap*, const double se3_new_from_old[12], ptam_pvs_point* out_rows);
+/* ptam_map_apply_outliers on the resident tables; outliers: host.  The action and the row index of every outlier are checked on
+ * the host (the list is there).  What needs the table is checked by a kernel launched before the flag kernel, one thread per
+ * outlier: the row's (kf, point) is the outlier's; no row is named twice (owner word per row); a NEVER_RETRY pair is not in
+ * never (binary search).  PTAM_E_ARG with ptam_rmap_last_refusal = (PTAM_RMAP_OUTLIERS, the lowest offending list index).
+ * Moves n_outliers * 16 bytes up and PTAM_RMAP_WORD_BYTES down. */
+int ptam_rmap_apply_outliers(ptam_rmap*, int n_outliers, const ptam_map_outlier* outliers, ptam_map_outliers_result* res);
+/* ptam_map_handle_bad_points on the resident tables: the columns are the handle's six point-side tables (the surviving points'
+ * bad bytes are zero by construction).  kept_out (nullable, room for n_points; the tracker's prevIndex) and new_index_out
+ * (nullable, n_points) come down only when asked for.  Moves PTAM_RMAP_WORD_BYTES down, and what was asked for. */
+int ptam_rmap_handle_bad_points(ptam_rmap*, ptam_map_bad_points_result* res, int32_t* kept_out, int32_t* new_index_out);
+/* ptam_map_add_points on the resident tables; made: host.  The two run ends are found by a binary search in the resident table
+ * in each thread of the row kernel.  The new points' rows go to the ends of the six point-side tables (points3 from the record's
+ * point, zeros to bad and the counts), their indices to the end of new_queue.  Moves n_made * sizeof(ptam_new_map_point) up. */
+int ptam_rmap_add_points(ptam_rmap*, int src_kf, int target_kf, int target_source, int n_made, const ptam_new_map_point* made);
+/* The table side of MapMaker::AddKeyFrameFromTopOfQueue (src/MapMaker.cc:501-506): the keyframe gets index n_kf, and its
+ * measurements (rows: host, sorted by point, none repeated; checked on the host) are appended at the table's end as
+ * {n_kf, point, level, PTAM_MAP_SRC_TRACKER, root_pos}.  kf (nullable): the handle kept for it.  Moves 97 + n_rows * 24 bytes up. */
+int ptam_rmap_add_keyframe(ptam_rmap*, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows, const ptam_map_kf_row* rows);
+/* The tracker's per-frame iteration set (src/Tracker.cc:987-998) into the counts: per entry outlier_count[point]++ where the
+ * flag is set, else inlier_count[point]++ (integer atomic adds: exact in any order; a point may be named more than once).
+ * points, outlier_flags: host, checked there.  Moves n * 5 bytes up. */
+int ptam_rmap_note_tracked(ptam_rmap*, int n, const int32_t* points, const uint8_t* outlier_flags);
+/* ptam_map_scene_depth on the resident tables.  out: n_kf rows, host.  Moves n_kf * sizeof(ptam_scene_depth) down. */
+int ptam_rmap_scene_depth(ptam_rmap*, ptam_scene_depth* out);
+
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,
  * ordered on `stream` (hipStream_t).  Return 0 on success. */

@@ -986,6 +986,150 @@ inline AddPointsResult AddPointsToTables(Context& c, int nKeyFrames, int nPoints
     return r;
 }
 
+// The map of the calls above kept in device memory from call to call (ptam_rmap, ptam_hip.h): Upload once, then one method per
+// step of MapMaker::run()  src/MapMaker.cc:57-114 — each does what the function of the same name above does, on the resident
+// tables, and moves only its small arguments and results over the host link.  Download fetches a table or a row range of it
+// (table: PTAM_RMAP_*; T: the row type, e.g. ptam_map_meas, Vec<3>, SE3).  Move-only.
+class ResidentMap {
+public:
+    explicit ResidentMap(Context& c) { check(ptam_rmap_create(c.handle(), &h_), "ptam_rmap_create"); }
+    ~ResidentMap() { ptam_rmap_destroy(h_); }
+    ResidentMap(const ResidentMap&) = delete;
+    ResidentMap& operator=(const ResidentMap&) = delete;
+    ResidentMap(ResidentMap&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    ResidentMap& operator=(ResidentMap&& o) noexcept {
+        if (this != &o) {
+            ptam_rmap_destroy(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    void Reserve(int nKeyFrames, int nPoints, int nMeas, int nNever, int nNewQueue, int nFailureQueue) {
+        check(ptam_rmap_reserve(h_, nKeyFrames, nPoints, nMeas, nNever, nNewQueue, nFailureQueue), "ptam_rmap_reserve");
+    }
+    ptam_rmap_counts_t Counts() const {
+        ptam_rmap_counts_t n{};
+        check(ptam_rmap_counts(h_, &n), "ptam_rmap_counts");
+        return n;
+    }
+    // every table of the map; vpKeyFrames may be empty (no handles are kept), pOutlierCount / pInlierCount null together (zeros)
+    void Upload(const std::vector<const KeyFrame*>& vpKeyFrames, const std::vector<SE3>& vKFPoses, const std::vector<uint8_t>& vFixed,
+                const std::vector<Vec<3>>& vPoints, const std::vector<ptam_map_refind_point>& vRefindPoints,
+                const std::vector<ptam_map_point_source>& vSources, const std::vector<uint8_t>& vBad, const int32_t* pOutlierCount,
+                const int32_t* pInlierCount, const std::vector<ptam_map_meas>& vMeas, const std::vector<ptam_map_pair>& vNever,
+                const std::vector<int32_t>& vNewQueue, const std::vector<ptam_map_pair>& vFailureQueue) {
+        if (vFixed.size() != vKFPoses.size() || (!vpKeyFrames.empty() && vpKeyFrames.size() != vKFPoses.size()))
+            throw std::runtime_error("ResidentMap::Upload: one bFixed (and one handle, if any) per keyframe");
+        if (vRefindPoints.size() != vPoints.size() || vSources.size() != vPoints.size() || vBad.size() != vPoints.size())
+            throw std::runtime_error("ResidentMap::Upload: one row per point in every point-side table");
+        std::vector<const ptam_kf*> kfs;
+        for (const KeyFrame* k : vpKeyFrames) kfs.push_back(k->handle());
+        check(ptam_rmap_upload(h_, (int)vKFPoses.size(), kfs.empty() ? nullptr : kfs.data(), reinterpret_cast<const double*>(vKFPoses.data()),
+                               vFixed.data(), (int)vPoints.size(), reinterpret_cast<const double*>(vPoints.data()), vRefindPoints.data(),
+                               vSources.data(), vBad.data(), pOutlierCount, pInlierCount, (int)vMeas.size(), vMeas.data(), (int)vNever.size(),
+                               vNever.data(), (int)vNewQueue.size(), vNewQueue.data(), (int)vFailureQueue.size(), vFailureQueue.data()),
+              "ptam_rmap_upload");
+    }
+    template <class T>
+    std::vector<T> Download(int table, int first = 0, int count = -1) const {
+        static const size_t row[PTAM_RMAP_TABLES] = {96, 1, 24, sizeof(ptam_map_refind_point), sizeof(ptam_map_point_source), 1, 4, 4,
+                                                     sizeof(ptam_map_meas), sizeof(ptam_map_pair), 4, sizeof(ptam_map_pair)};
+        if (table < 0 || table >= PTAM_RMAP_TABLES || sizeof(T) != row[table]) throw std::runtime_error("ResidentMap::Download: row type");
+        const ptam_rmap_counts_t n = Counts();
+        const int rows[PTAM_RMAP_TABLES] = {n.n_kf, n.n_kf, n.n_points, n.n_points, n.n_points, n.n_points, n.n_points, n.n_points,
+                                            n.n_meas, n.n_never, n.n_new, n.n_failure};
+        if (count < 0) count = rows[table] - first;
+        std::vector<T> v((size_t)(count > 0 ? count : 0));
+        check(ptam_rmap_download(h_, table, first, count, v.data()), "ptam_rmap_download");
+        return v;
+    }
+    void Traffic(unsigned long long& nBytesUp, unsigned long long& nBytesDown) const {
+        check(ptam_rmap_traffic(h_, &nBytesUp, &nBytesDown), "ptam_rmap_traffic");
+    }
+    // MapBundleAdjust on the resident tables: the adjusted poses and points stay on the device
+    MapBundleAdjustResult BundleAdjust(int mode, const ptam_ba_opts* opts = nullptr, const volatile unsigned char* abort_flag = nullptr) {
+        MapBundleAdjustResult r{};
+        const ptam_rmap_counts_t n = Counts();
+        r.outliers.resize((size_t)n.n_meas);
+        r.cam_kf.resize((size_t)n.n_kf);
+        r.point_ids.resize((size_t)n.n_points);
+        check(ptam_rmap_bundle_adjust(h_, opts, mode, abort_flag, &r.result, r.outliers.data(), n.n_meas, r.cam_kf.data(), r.point_ids.data()),
+              "ptam_rmap_bundle_adjust");
+        r.outliers.resize((size_t)r.result.n_outliers);
+        r.cam_kf.resize((size_t)(r.result.n_adjust + r.result.n_fixed));
+        r.point_ids.resize((size_t)r.result.n_points);
+        return r;
+    }
+    // MapReFind on the resident tables (the keyframe handles are those of Upload / AddKeyFrame).  pWork == nullptr with
+    // PTAM_MAP_REFIND_NEW_POINTS / _FAILURE_QUEUE: the resident queue is the work and is popped / cleared.  The merged tables stay
+    // on the device; the found rows and new never pairs come down only when bLists is set.
+    MapReFindResult ReFind(ReFinder& finder, int mode, const void* pWork = nullptr, int nWork = 0, bool bLists = false,
+                           const bool* pbStop = nullptr, const ptam_map_refind_opts* opts = nullptr) {
+        const ptam_rmap_counts_t n = Counts();
+        const size_t w = pWork ? (size_t)(nWork > 0 ? nWork : 0) : (size_t)(mode == PTAM_MAP_REFIND_NEW_POINTS ? n.n_new : n.n_failure);
+        const size_t cap = !bLists ? 0 : mode == PTAM_MAP_REFIND_KEYFRAME ? (w > 0 ? (size_t)n.n_points : 0)
+                           : mode == PTAM_MAP_REFIND_NEW_POINTS ? (size_t)n.n_kf * w : w;
+        MapReFindResult r{};
+        r.vFound.resize(cap);
+        r.vFoundSubPix.resize(cap);
+        r.vNeverNew.resize(cap);
+        check(ptam_rmap_refind(h_, finder.handle(), opts, mode, pWork ? nWork : 0, pWork, reinterpret_cast<const volatile unsigned char*>(pbStop),
+                               &r.result, bLists ? r.vFound.data() : nullptr, bLists ? r.vFoundSubPix.data() : nullptr,
+                               bLists ? r.vNeverNew.data() : nullptr, (int)cap),
+              "ptam_rmap_refind");
+        if (bLists) {
+            r.vFound.resize((size_t)r.result.n_found);
+            r.vFoundSubPix.resize((size_t)r.result.n_found);
+            r.vNeverNew.resize((size_t)r.result.n_never);
+        }
+        return r;
+    }
+    // ApplyGlobalTransformationToMap on the resident poses, points and point rows; the ptam_pvs_point rows when bRows is set
+    std::vector<ptam_pvs_point> ApplyGlobalTransformationToMap(const SE3& se3NewFromOld, bool bRows = true) {
+        std::vector<ptam_pvs_point> rows(bRows ? (size_t)Counts().n_points : 0);
+        check(ptam_rmap_apply_global_transform(h_, reinterpret_cast<const double*>(&se3NewFromOld), bRows && !rows.empty() ? rows.data() : nullptr),
+              "ptam_rmap_apply_global_transform");
+        return rows;
+    }
+    ptam_map_outliers_result ApplyBundleOutliers(const std::vector<ptam_map_outlier>& vOutliers) {
+        ptam_map_outliers_result r{};
+        check(ptam_rmap_apply_outliers(h_, (int)vOutliers.size(), vOutliers.data(), &r), "ptam_rmap_apply_outliers");
+        return r;
+    }
+    // vKept (the prevIndex of MapTracker::UpdateMap) comes down when bKept is set; vNewIndex stays empty
+    HandleBadPointsResult HandleBadPoints(bool bKept = true) {
+        HandleBadPointsResult r{};
+        if (bKept) r.vKept.resize((size_t)Counts().n_points);
+        check(ptam_rmap_handle_bad_points(h_, &r.result, bKept ? r.vKept.data() : nullptr, nullptr), "ptam_rmap_handle_bad_points");
+        if (bKept) r.vKept.resize((size_t)r.result.n_kept);
+        return r;
+    }
+    void AddPointsToTables(int nSrcKF, int nTargetKF, const std::vector<ptam_new_map_point>& vMade, int nTargetSource = PTAM_MAP_SRC_EPIPOLAR) {
+        check(ptam_rmap_add_points(h_, nSrcKF, nTargetKF, nTargetSource, (int)vMade.size(), vMade.data()), "ptam_rmap_add_points");
+    }
+    // the table side of MapMaker::AddKeyFrameFromTopOfQueue   src/MapMaker.cc:501-506: vRows sorted by point
+    void AddKeyFrame(const KeyFrame* pK, const SE3& se3CfromW, bool bFixed, const std::vector<ptam_map_kf_row>& vRows) {
+        check(ptam_rmap_add_keyframe(h_, pK ? pK->handle() : nullptr, reinterpret_cast<const double*>(&se3CfromW), bFixed, (int)vRows.size(),
+                                     vRows.data()),
+              "ptam_rmap_add_keyframe");
+    }
+    // the tracker's iteration set: nMEstimatorOutlierCount++ / nMEstimatorInlierCount++   src/Tracker.cc:987-998
+    void NoteTracked(const std::vector<int32_t>& vPoints, const std::vector<uint8_t>& vOutlier) {
+        if (vPoints.size() != vOutlier.size()) throw std::runtime_error("ResidentMap::NoteTracked: one flag per point");
+        check(ptam_rmap_note_tracked(h_, (int)vPoints.size(), vPoints.data(), vOutlier.data()), "ptam_rmap_note_tracked");
+    }
+    std::vector<ptam_scene_depth> RefreshSceneDepth() {
+        std::vector<ptam_scene_depth> v((size_t)Counts().n_kf);
+        check(ptam_rmap_scene_depth(h_, v.data()), "ptam_rmap_scene_depth");
+        return v;
+    }
+    ptam_rmap* handle() const { return h_; }
+
+private:
+    ptam_rmap* h_ = nullptr;
+};
+
 // class Bundle (include/Bundle.h:106-152)
 class Bundle {
 public:

@@ -225,6 +225,24 @@ class MapBadPointsResult(C.Structure):
                                          "n_failure_out")]
 
 
+# the tables of a ptam_rmap, as ptam_rmap_download and ptam_rmap_last_refusal name them
+(RMAP_KF_POSES, RMAP_KF_FIXED, RMAP_POINTS3, RMAP_REFIND_POINTS, RMAP_SOURCES, RMAP_BAD, RMAP_OUTLIER_COUNT, RMAP_INLIER_COUNT, RMAP_MEAS,
+ RMAP_NEVER, RMAP_NEW_QUEUE, RMAP_FAILURE) = range(12)
+RMAP_TABLES = RMAP_OUTLIERS = 12
+RMAP_WORD_BYTES = 64
+RMAP_KF_RECORD_BYTES = 512
+
+
+class RmapCounts(C.Structure):
+    """ptam_rmap_counts_t"""
+    _fields_ = [(f, C.c_int32) for f in ("n_kf", "n_points", "n_meas", "n_never", "n_new", "n_failure")]
+
+
+class MapKfRow(C.Structure):
+    """ptam_map_kf_row: one measurement of a keyframe that ptam_rmap_add_keyframe appends"""
+    _fields_ = [("point", C.c_int32), ("level", C.c_int32), ("root_pos", C.c_double * 2)]
+
+
 class SbiAlignment(C.Structure):
     """ptam_sbi_alignment (SmallBlurryImage::CalcSBIRotation, src/ImageProcess.cc:313-495)"""
     _fields_ = [("se2_rot", C.c_double * 4), ("se2_trans", C.c_double * 2), ("score", C.c_double), ("mean_offset", C.c_double),
@@ -385,6 +403,23 @@ PROTOTYPES = {
     "map_handle_bad_points": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, C.POINTER(MapBadPointsResult),
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "map_add_points": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "rmap_create": (_i, [_vp, _ppv]),
+    "rmap_destroy": (_i, [_vp]),
+    "rmap_reserve": (_i, [_vp, _i, _i, _i, _i, _i, _i]),
+    "rmap_counts": (_i, [_vp, C.POINTER(RmapCounts)]),
+    "rmap_upload": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    "rmap_download": (_i, [_vp, _i, _i, _i, _vp]),
+    "rmap_last_refusal": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "rmap_traffic": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "rmap_bundle_adjust": (_i, [_vp, C.POINTER(BaOpts), _i, _vp, C.POINTER(MapBaResult), _vp, _i, _vp, _vp]),
+    "rmap_refind": (_i, [_vp, _vp, C.POINTER(MapRefindOpts), _i, _i, _vp, _vp, C.POINTER(MapRefindResult), _vp, _vp, _vp, _i]),
+    "rmap_apply_global_transform": (_i, [_vp, _pd, _vp]),
+    "rmap_apply_outliers": (_i, [_vp, _i, _vp, C.POINTER(MapOutliersResult)]),
+    "rmap_handle_bad_points": (_i, [_vp, C.POINTER(MapBadPointsResult), _vp, _vp]),
+    "rmap_add_points": (_i, [_vp, _i, _i, _i, _i, _vp]),
+    "rmap_add_keyframe": (_i, [_vp, _vp, _pd, _i, _i, _vp]),
+    "rmap_note_tracked": (_i, [_vp, _i, _vp, _vp]),
+    "rmap_scene_depth": (_i, [_vp, _vp]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

@@ -51,6 +51,7 @@ struct ApplyArgs {
     double* pts;              // N x 3, in place
     const ptam_map_point_source* src;   // N or null
     ptam_pvs_point* pvs;                // N or null
+    int pvs_stride;                     // bytes from one output row to the next (sizeof(ptam_pvs_point), or the row of a wider table)
 };
 
 struct DepthArgs {
@@ -360,7 +361,7 @@ __global__ void __launch_bounds__(ALIGN_THREADS) map_apply_kernel(ApplyArgs a) {
         o.pixel_right_w[k] = (P[k] * right[0] + P[3 + k] * right[1]) + P[6 + k] * right[2];
         o.pixel_down_w[k] = (P[k] * down[0] + P[3 + k] * down[1]) + P[6 + k] * down[2];
     }
-    a.pvs[i] = o;
+    *(ptam_pvs_point*)((char*)a.pvs + (size_t)i * a.pvs_stride) = o;
 }
 
 // ---- RefreshSceneDepth (:1202-1219) for keyframe blockIdx.x ------------------------------------------------------------------------
@@ -502,6 +503,7 @@ static int align_run(ptam_ctx* ctx, const ptam_plane_opts* o, const double* se3_
         a.pts = (double*)(d + o_pts);
         a.src = src ? (const ptam_map_point_source*)(d + o_src) : nullptr;
         a.pvs = src ? (ptam_pvs_point*)(d + o_pvs) : nullptr;
+        a.pvs_stride = (int)sizeof(ptam_pvs_point);
         if (K > 0) HIP_TRY(hipMemcpyAsync(d + o_pose, poses, (size_t)K * 96, hipMemcpyHostToDevice, st));
         if (src && N > 0) HIP_TRY(hipMemcpyAsync(d + o_src, src, (size_t)N * sizeof(ptam_map_point_source), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(map_apply_kernel, dim3((K + N + ALIGN_THREADS - 1) / ALIGN_THREADS), dim3(ALIGN_THREADS), 0, st, a);
@@ -588,27 +590,63 @@ int ptam_map_scene_depth(ptam_ctx* ctx, int n_kf, const double* kf_poses12, int 
                  total = o_meas + up256(Mz * sizeof(ptam_map_meas));
     void *s, *hp;
     if (int rc = ctx_scratch(ctx, total, &s)) return rc;
-    if (int rc = ctx_pinned(ctx, (size_t)n_kf * sizeof(ptam_scene_depth), &hp)) return rc;
+    if (int rc = ctx_pinned(ctx, (size_t)n_kf * sizeof(ptam_scene_depth), &hp)) return rc;   // (before the copies are queued: growing it waits)
+    (void)hp;
     char* d = (char*)s;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(d + o_pose, kf_poses12, (size_t)n_kf * 96, hipMemcpyHostToDevice, st));
     if (n_points > 0) HIP_TRY(hipMemcpyAsync(d + o_pts, points3, (size_t)n_points * 24, hipMemcpyHostToDevice, st));
     if (n_meas > 0) HIP_TRY(hipMemcpyAsync(d + o_meas, meas, (size_t)n_meas * sizeof(ptam_map_meas), hipMemcpyHostToDevice, st));
-    DepthArgs a;
-    a.K = n_kf;
-    a.M = n_meas;
-    a.poses = (const double*)(d + o_pose);
-    a.pts = (const double*)(d + o_pts);
-    a.meas = (const ptam_map_meas*)(d + o_meas);
-    a.out = (ptam_scene_depth*)ctx->d_pinned;
-    hipLaunchKernelGGL(scene_depth_kernel, dim3(n_kf), dim3(ALIGN_THREADS), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(ptam_stream_wait(st));
-    std::memcpy(out, hp, (size_t)n_kf * sizeof(ptam_scene_depth));
-    return PTAM_OK;
+    return map_scene_depth_core(ctx, n_kf, (const double*)(d + o_pose), (const double*)(d + o_pts), n_meas, (const ptam_map_meas*)(d + o_meas), out);
 }
 
 }   // extern "C"
+
+// ptam_map_apply_global_transform's launch on tables that are in device memory: poses -> poses_new, the points in place, the pixel
+// vectors (d_src / d_pvs nullable together) into rows pvs_stride bytes apart.  Enqueues only; K + N > 0.
+int map_transform_core(ptam_ctx* ctx, const double se3_new_from_old[12], int K, const double* d_poses, double* d_poses_new, int N,
+                       double* d_points3, const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride) {
+    void *s, *hp;
+    if (int rc = ctx_scratch(ctx, 256, &s)) return rc;
+    if (int rc = ctx_pinned(ctx, 256, &hp)) return rc;
+    PlaneOut* h_out = (PlaneOut*)hp;
+    *h_out = PlaneOut{};
+    h_out->info.status = PTAM_PLANE_OK;
+    std::memcpy(h_out->se3, se3_new_from_old, sizeof h_out->se3);
+    HIP_TRY(hipMemcpyAsync(s, h_out, sizeof(PlaneOut), hipMemcpyHostToDevice, ctx->stream));
+    ApplyArgs a;
+    a.K = K;
+    a.N = N;
+    a.plane = (const PlaneOut*)s;
+    a.poses = d_poses;
+    a.poses_new = d_poses_new;
+    a.pts = d_points3;
+    a.src = d_src;
+    a.pvs = d_pvs;
+    a.pvs_stride = pvs_stride;
+    hipLaunchKernelGGL(map_apply_kernel, dim3((K + N + ALIGN_THREADS - 1) / ALIGN_THREADS), dim3(ALIGN_THREADS), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
+// the launch and the wait of ptam_map_scene_depth on tables that are in device memory (n_kf > 0); out: host
+int map_scene_depth_core(ptam_ctx* ctx, int n_kf, const double* d_poses, const double* d_points3, int n_meas, const ptam_map_meas* d_meas,
+                         ptam_scene_depth* out) {
+    void* hp;
+    if (int rc = ctx_pinned(ctx, (size_t)n_kf * sizeof(ptam_scene_depth), &hp)) return rc;
+    DepthArgs a;
+    a.K = n_kf;
+    a.M = n_meas;
+    a.poses = d_poses;
+    a.pts = d_points3;
+    a.meas = d_meas;
+    a.out = (ptam_scene_depth*)ctx->d_pinned;
+    hipLaunchKernelGGL(scene_depth_kernel, dim3(n_kf), dim3(ALIGN_THREADS), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(ptam_stream_wait(ctx->stream));
+    std::memcpy(out, hp, (size_t)n_kf * sizeof(ptam_scene_depth));
+    return PTAM_OK;
+}
 
 void mapalign_preload_kernels() {
     ptam_preload((const void*)plane_score_kernel);

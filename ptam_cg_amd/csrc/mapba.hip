@@ -18,11 +18,15 @@
 //   mba_scatter_*       accepted > 0: the bundle's points and poses back into the tables through the id maps
 //   mba_order_kernel    the purged measurements per LM step in insertion order (GetOutlierMeasurements, src/Bundle.cc:540, :623)
 //   mba_route_kernel    one lane per point with outliers walks them in list order: GoodMeasCount / SRC_ROOT rules (:916-932)
+// mba_run is all of the above on tables that are either the caller's host arrays (ptam_map_bundle_adjust: up into the scratch, the
+// adjusted poses and points down) or a resident map's device buffers (ptam_rmap_bundle_adjust, maprmap.hip: adjusted in place,
+// mba_sync_world_kernel copies the points into the point rows' pv.world, the poses come down into the host mirror).
 #include "common.h"
 #include <climits>
 #include <vector>
 
 #include "bundle.h"
+#include "maptables_internal.h"   // MbaTables, mba_run
 #include "patch_device.h"   // nc_mul / nc_add / nc_sub
 
 namespace {
@@ -341,22 +345,25 @@ struct BaGuard {   // the call's own bundle, destroyed on every return path
 };
 }   // namespace
 
-extern "C" {
+// the resident map's second copy of the world positions (ptam_map_refind_point::pv) follows points3 after an accepted bundle
+__global__ void __launch_bounds__(256) mba_sync_world_kernel(int n, const double* __restrict__ pts, ptam_map_refind_point* __restrict__ rows) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    for (int c = 0; c < 3; c++) rows[i].pv.world[c] = pts[(size_t)3 * i + c];
+}
 
-int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, int n_kf, double* kf_poses12, const uint8_t* kf_fixed,
-                           int n_points, double* points3, int n_meas, const ptam_map_meas* meas, const volatile unsigned char* abort_flag,
-                           ptam_map_ba_result* res, ptam_map_outlier* outliers, int outlier_cap, int32_t* cam_kf, int32_t* point_ids) {
-    ARG_TRY(ctx && res);
-    ARG_TRY(mode == PTAM_MAP_BA_ALL || mode == PTAM_MAP_BA_RECENT);
-    ARG_TRY(n_kf >= 0 && n_points >= 0 && n_meas >= 0);
-    ARG_TRY(n_kf == 0 || (kf_poses12 && kf_fixed));
-    ARG_TRY(n_points == 0 || points3);
-    ARG_TRY(n_meas == 0 || meas);
-    ARG_TRY(!outliers || outlier_cap >= n_meas);
+// ptam_map_bundle_adjust behind its argument checks, on host tables (they go up into the scratch; the adjusted poses and points come
+// down) or on resident ones (written in place; the poses come down into the mirror): maptables_internal.h
+int mba_run(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, const MbaTables& t, const volatile unsigned char* abort_flag,
+            ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids, unsigned long long traffic[2]) {
+    const int n_kf = t.K;
+    const double* kf_poses12 = t.h_poses;
+    const uint8_t* kf_fixed = t.h_fixed;
+    const bool resident = t.d_meas != nullptr || t.d_poses != nullptr;
     std::memset(res, 0, sizeof *res);
     if (mode == PTAM_MAP_BA_RECENT && n_kf < 8) return PTAM_OK;   // :790-793
     HIP_TRY(hipSetDevice(ctx->device));
-    const int K = n_kf, N = n_points, M = n_meas, nb = (M + MBA_BLOCK - 1) / MBA_BLOCK;
+    const int K = t.K, N = t.N, M = t.M, nb = (M + MBA_BLOCK - 1) / MBA_BLOCK;
     BaGuard g;
     if (int rc = ptam_ba_create(ctx, opts, &g.ba)) return rc;
     char* d_ms = nullptr;
@@ -366,8 +373,8 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
     Carver cv;
     const size_t o_hdr = cv.take(sizeof(MbaHdr)), o_role = cv.take(Kz * 4), o_mark = cv.take(Nz * 4), o_rows = cv.take(Nz * 4);
     const size_t clear = cv.off;
-    const size_t o_pose = cv.take(Kz * 96), o_fixed = cv.take(Kz), o_pts = cv.take(Nz * 24), o_meas = cv.take(Mz * sizeof(ptam_map_meas)),
-                 o_camid = cv.take(Kz * 4), o_camkf = cv.take(Kz * 4), o_ptid = cv.take(Nz * 4), o_ptof = cv.take(Nz * 4), o_ptsel = cv.take(Nz * 24),
+    const size_t o_pose = cv.take(resident ? 0 : Kz * 96), o_fixed = cv.take(resident ? 0 : Kz), o_pts = cv.take(resident ? 0 : Nz * 24),
+                 o_meas = cv.take(resident ? 0 : Mz * sizeof(ptam_map_meas)), o_camid = cv.take(Kz * 4), o_camkf = cv.take(Kz * 4), o_ptid = cv.take(Nz * 4), o_ptof = cv.take(Nz * 4), o_ptsel = cv.take(Nz * 24),
                  o_blk = cv.take(((size_t)nb + 1) * 4), o_selrow = cv.take(Mz * 4);
     // outlier routing (outliers <= bundle measurements <= M)
     const size_t o_ord = cv.take(Mz * 4), o_orow = cv.take(Mz * 4), o_opt = cv.take(Mz * 4), o_first = cv.take(Nz * 4),
@@ -377,10 +384,10 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
     char* b = (char*)s;
     MbaDev a;
     a.mode = mode, a.K = K, a.N = N, a.M = M, a.nb = nb;
-    a.pose = (const double*)(b + o_pose);
-    a.fixed = (const uint8_t*)(b + o_fixed);
-    a.pts = (double*)(b + o_pts);
-    a.meas = (const ptam_map_meas*)(b + o_meas);
+    a.pose = resident ? t.d_poses : (const double*)(b + o_pose);
+    a.fixed = resident ? t.d_fixed : (const uint8_t*)(b + o_fixed);
+    a.pts = resident ? t.d_points3 : (double*)(b + o_pts);
+    a.meas = resident ? t.d_meas : (const ptam_map_meas*)(b + o_meas);
     a.role = (int*)(b + o_role);
     a.cam_id = (int*)(b + o_camid);
     a.cam_kf = (int*)(b + o_camkf);
@@ -395,12 +402,14 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
     a.hdr = (MbaHdr*)(b + o_hdr);
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemsetAsync(b, 0, clear, st));
-    if (K > 0) {
-        HIP_TRY(hipMemcpyAsync(b + o_pose, kf_poses12, (size_t)K * 96, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_fixed, kf_fixed, (size_t)K, hipMemcpyHostToDevice, st));
+    if (!resident) {
+        if (K > 0) {
+            HIP_TRY(hipMemcpyAsync(b + o_pose, kf_poses12, (size_t)K * 96, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(b + o_fixed, kf_fixed, (size_t)K, hipMemcpyHostToDevice, st));
+        }
+        if (N > 0) HIP_TRY(hipMemcpyAsync(b + o_pts, t.h_points3, (size_t)N * 24, hipMemcpyHostToDevice, st));
+        if (M > 0) HIP_TRY(hipMemcpyAsync(b + o_meas, t.h_meas, (size_t)M * sizeof(ptam_map_meas), hipMemcpyHostToDevice, st));
     }
-    if (N > 0) HIP_TRY(hipMemcpyAsync(b + o_pts, points3, (size_t)N * 24, hipMemcpyHostToDevice, st));
-    if (M > 0) HIP_TRY(hipMemcpyAsync(b + o_meas, meas, (size_t)M * sizeof(ptam_map_meas), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(mba_select_kernel, dim3(1), dim3(1024), 0, st, a);
     if (M > 0) {
         hipLaunchKernelGGL(mba_mark_kernel, dim3(nb), dim3(MBA_BLOCK), 0, st, a);
@@ -415,6 +424,8 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
     if (K > 0) HIP_TRY(hipMemcpyAsync((char*)hp + sizeof(MbaHdr), a.cam_kf, (size_t)K * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ptam_stream_wait(st));   // the one wait of the selection
     const MbaHdr h = *(const MbaHdr*)hp;
+    unsigned long long down = sizeof(MbaHdr) + (size_t)K * 4;   // what this layer copies over the host link (the bundle's own words apart)
+    if (traffic) traffic[1] = down;                             // (it stands if the call ends early)
     if (h.err) {
         ptam_set_error("map_bundle_adjust: table row %d is out of range or out of (kf, point) order", h.err_row);
         return PTAM_E_ARG;
@@ -444,9 +455,11 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
         if (h.n_points > 0) hipLaunchKernelGGL(mba_scatter_points_kernel, dim3((h.n_points + 255) / 256), dim3(256), 0, st, a, h.n_points);
         const int nl = std::max(r.P_live, r.C);
         if (nl > 0) hipLaunchKernelGGL(mba_scatter_live_kernel, dim3((nl + 255) / 256), dim3(256), 0, st, a, r, (double*)a.pose);
+        if (t.d_points && N > 0) hipLaunchKernelGGL(mba_sync_world_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, (const double*)a.pts, t.d_points);
         HIP_TRY(hipGetLastError());
-        if (N > 0) HIP_TRY(hipMemcpyAsync(points3, a.pts, (size_t)N * 24, hipMemcpyDeviceToHost, st));
-        if (K > 0) HIP_TRY(hipMemcpyAsync(kf_poses12, a.pose, (size_t)K * 96, hipMemcpyDeviceToHost, st));
+        if (N > 0 && t.points3_out) HIP_TRY(hipMemcpyAsync(t.points3_out, a.pts, (size_t)N * 24, hipMemcpyDeviceToHost, st));
+        if (K > 0) HIP_TRY(hipMemcpyAsync(t.poses_out, a.pose, (size_t)K * 96, hipMemcpyDeviceToHost, st));
+        down += (size_t)K * 96 + (t.points3_out ? (size_t)N * 24 : 0);
     }
     const int n_out = std::min(r.n_out, h.n_meas);
     if (outliers && n_out > 0) {   // :916-932
@@ -465,9 +478,17 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
                            (const int*)first, d_out);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(outliers, d_out, (size_t)n_out * sizeof(ptam_map_outlier), hipMemcpyDeviceToHost, st));
+        down += (size_t)n_out * sizeof(ptam_map_outlier);
     }
-    if (point_ids && h.n_points > 0) HIP_TRY(hipMemcpyAsync(point_ids, a.pt_of, (size_t)h.n_points * 4, hipMemcpyDeviceToHost, st));
+    if (point_ids && h.n_points > 0) {
+        HIP_TRY(hipMemcpyAsync(point_ids, a.pt_of, (size_t)h.n_points * 4, hipMemcpyDeviceToHost, st));
+        down += (size_t)h.n_points * 4;
+    }
     HIP_TRY(ptam_stream_wait(st));
+    if (traffic) {
+        traffic[0] = (unsigned long long)C * 97;   // the bundle's cameras: pose and flag
+        traffic[1] = down;
+    }
     if (cam_kf && C > 0) std::memcpy(cam_kf, ckf.data(), (size_t)C * 4);
     res->ran = 1;
     res->accepted = accepted;
@@ -478,6 +499,31 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
     res->n_meas = h.n_meas;
     res->n_outliers = r.n_out;
     return PTAM_OK;
+}
+
+extern "C" {
+
+int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, int n_kf, double* kf_poses12, const uint8_t* kf_fixed,
+                           int n_points, double* points3, int n_meas, const ptam_map_meas* meas, const volatile unsigned char* abort_flag,
+                           ptam_map_ba_result* res, ptam_map_outlier* outliers, int outlier_cap, int32_t* cam_kf, int32_t* point_ids) {
+    ARG_TRY(ctx && res);
+    ARG_TRY(mode == PTAM_MAP_BA_ALL || mode == PTAM_MAP_BA_RECENT);
+    ARG_TRY(n_kf >= 0 && n_points >= 0 && n_meas >= 0);
+    ARG_TRY(n_kf == 0 || (kf_poses12 && kf_fixed));
+    ARG_TRY(n_points == 0 || points3);
+    ARG_TRY(n_meas == 0 || meas);
+    ARG_TRY(!outliers || outlier_cap >= n_meas);
+    MbaTables t = {};
+    t.K = n_kf;
+    t.N = n_points;
+    t.M = n_meas;
+    t.h_poses = kf_poses12;
+    t.h_fixed = kf_fixed;
+    t.h_points3 = points3;
+    t.h_meas = meas;
+    t.poses_out = kf_poses12;
+    t.points3_out = points3;
+    return mba_run(ctx, opts, mode, t, abort_flag, res, outliers, cam_kf, point_ids, nullptr);
 }
 
 }   // extern "C"
@@ -493,4 +539,5 @@ void mapba_preload_kernels() {
     ptam_preload((const void*)mba_order_kernel);
     ptam_preload((const void*)mba_route_prep_kernel);
     ptam_preload((const void*)mba_route_kernel);
+    ptam_preload((const void*)mba_sync_world_kernel);
 }

@@ -10,10 +10,12 @@
 // into one, each row placed by a binary search in the other list).  Every order is fixed: the same input gives the same bits.
 #include <algorithm>
 
+#include "maptables_internal.h"
 #include "refind_internal.h"
 
 enum { MR_FOUND = 0, MR_NEVER = 1, MR_SKIPPED = 2, MR_KEPT = 3, MR_COUNTS = 4 };
 enum { MR_DEFAULT_PASS = 4096 };
+static_assert(sizeof(KfLevels) <= PTAM_RMAP_KF_RECORD_BYTES, "the per-keyframe record ptam_hip.h promises ptam_rmap_refind's callers");
 
 struct MrArgs {
     int mode, n_kf;
@@ -226,29 +228,39 @@ static bool table_sorted_in_range(int n, const Row* t, int n_kf, int n_points) {
     return true;
 }
 
-extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, int n_kf,
-                               const ptam_kf* const* kfs, const double* kf_poses12, int n_points, const ptam_map_refind_point* points, int n_meas,
-                               const ptam_map_meas* meas, int n_never, const ptam_map_pair* never, int n_work, const void* work,
-                               const volatile unsigned char* stop_flag, ptam_map_refind_result* res, ptam_map_meas* found_out,
-                               int32_t* found_subpix, ptam_map_pair* never_out, int out_cap, ptam_map_meas* meas_merged,
-                               ptam_map_pair* never_merged) {
+// ptam_map_refind on host tables or on a resident map's (maptables_internal.h)
+int mr_run(ptam_ctx* ctx, ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, const MrTables& t, int n_work, const void* work,
+           const volatile unsigned char* stop_flag, ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix,
+           ptam_map_pair* never_out, int out_cap, ptam_map_meas* meas_merged, ptam_map_pair* never_merged, int* merged_written,
+           unsigned long long traffic[2]) {
+    const int n_kf = t.n_kf, n_points = t.n_points, n_meas = t.n_meas, n_never = t.n_never;
+    const ptam_kf* const* kfs = t.kfs;
+    const double* kf_poses12 = t.h_poses;
+    const ptam_map_refind_point* points = t.h_points;
+    const ptam_map_meas* meas = t.h_meas;
+    const ptam_map_pair* never = t.h_never;
+    const bool resident = t.d_poses != nullptr;
+    unsigned long long up = 0, down = 0;
+    if (merged_written) *merged_written = 0;
     // ---- refusals: nothing is written and nothing enqueued before all of them have passed
     ARG_TRY(ctx && finder && finder->ctx->device == ctx->device && res);
     ARG_TRY(mode == PTAM_MAP_REFIND_KEYFRAME || mode == PTAM_MAP_REFIND_NEW_POINTS || mode == PTAM_MAP_REFIND_FAILURE_QUEUE);
     ARG_TRY(n_kf >= 0 && n_points >= 0 && n_meas >= 0 && n_never >= 0 && n_work >= 0 && out_cap >= 0);
-    ARG_TRY((n_kf == 0 || (kfs && kf_poses12)) && (n_points == 0 || points) && (n_meas == 0 || meas) && (n_never == 0 || never) &&
-            (n_work == 0 || work));
+    ARG_TRY((n_kf == 0 || kfs) && (n_work == 0 || work));
+    ARG_TRY(resident || ((n_kf == 0 || kf_poses12) && (n_points == 0 || points) && (n_meas == 0 || meas) && (n_never == 0 || never)));
     ARG_TRY(!opts || opts->max_pairs_per_pass >= 0);
     for (int k = 0; k < n_kf; k++) {
         ARG_TRY(kfs[k] && kfs[k]->device == ctx->device);
         ARG_TRY(kfs[k]->L.w[0] == ctx->params.width && kfs[k]->L.h[0] == ctx->params.height);
     }
-    for (int p = 0; p < n_points; p++)
-        ARG_TRY(points[p].src_kf >= 0 && points[p].src_kf < n_kf && points[p].src_level >= 0 && points[p].src_level < PTAM_LEVELS);
-    ARG_TRY(table_sorted_in_range(n_meas, meas, n_kf, n_points));
-    for (int i = 0; i < n_meas; i++)
-        ARG_TRY(meas[i].level >= 0 && meas[i].level < PTAM_LEVELS && meas[i].source >= PTAM_MAP_SRC_TRACKER && meas[i].source <= PTAM_MAP_SRC_EPIPOLAR);
-    ARG_TRY(table_sorted_in_range(n_never, never, n_kf, n_points));
+    if (!resident) {   // (a resident map's tables have been checked on the device when they went up, and every call keeps the rules)
+        for (int p = 0; p < n_points; p++)
+            ARG_TRY(points[p].src_kf >= 0 && points[p].src_kf < n_kf && points[p].src_level >= 0 && points[p].src_level < PTAM_LEVELS);
+        ARG_TRY(table_sorted_in_range(n_meas, meas, n_kf, n_points));
+        for (int i = 0; i < n_meas; i++)
+            ARG_TRY(meas[i].level >= 0 && meas[i].level < PTAM_LEVELS && meas[i].source >= PTAM_MAP_SRC_TRACKER && meas[i].source <= PTAM_MAP_SRC_EPIPOLAR);
+        ARG_TRY(table_sorted_in_range(n_never, never, n_kf, n_points));
+    }
     std::vector<int> wpts, wrank, wentry;   // NEW_POINTS: the points that make pairs, their index-order places, their queue entries
     std::vector<ptam_map_pair> wq;          // FAILURE_QUEUE: sorted (:1074)
     int kf0 = 0;
@@ -266,7 +278,7 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
         for (int e = 0; e < n_work; e++) {
             ARG_TRY(w[e] >= 0 && w[e] < n_points && !seen[(size_t)w[e]]);
             seen[(size_t)w[e]] = 1;
-            if (points[w[e]].bad) continue;   // :1056-1059
+            if (t.work_bad ? t.work_bad[e] != 0 : points[w[e]].bad != 0) continue;   // :1056-1059
             wpts.push_back(w[e]);
             wentry.push_back(e);
         }
@@ -276,8 +288,11 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
         for (int e = 0; e < n_work; e++) ARG_TRY(w[e].kf >= 0 && w[e].kf < n_kf && w[e].point >= 0 && w[e].point < n_points);
         total = n_work;
     }
-    ARG_TRY(total <= (long long)out_cap && total + n_meas < (1ll << 31) && total + n_never < (1ll << 31));
-    ARG_TRY(total == 0 || (found_out && found_subpix && never_out));
+    ARG_TRY(total + n_meas < (1ll << 31) && total + n_never < (1ll << 31));
+    if (!resident || found_out || found_subpix || never_out) {
+        ARG_TRY(total <= (long long)out_cap);
+        ARG_TRY(total == 0 || (found_out && found_subpix && never_out));
+    }
     if (mode == PTAM_MAP_REFIND_NEW_POINTS) {
         total = (long long)n_kf * (long long)wpts.size();
         std::vector<int> by_index(wpts.size());
@@ -298,8 +313,8 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
             r.n_bad_points = n_work - (int)wpts.size();
         } else if (mode == PTAM_MAP_REFIND_NEW_POINTS)
             r.stopped = n_work > 0;
-        if (meas_merged && n_meas > 0) std::memcpy(meas_merged, meas, (size_t)n_meas * sizeof(ptam_map_meas));
-        if (never_merged && n_never > 0) std::memcpy(never_merged, never, (size_t)n_never * sizeof(ptam_map_pair));
+        if (!resident && meas_merged && n_meas > 0) std::memcpy(meas_merged, meas, (size_t)n_meas * sizeof(ptam_map_meas));
+        if (!resident && never_merged && n_never > 0) std::memcpy(never_merged, never, (size_t)n_never * sizeof(ptam_map_pair));
         *res = r;
         return PTAM_OK;
     }
@@ -309,7 +324,10 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
     int per_pass = opts && opts->max_pairs_per_pass > 0 ? opts->max_pairs_per_pass : MR_DEFAULT_PASS;
     if (mode == PTAM_MAP_REFIND_NEW_POINTS) per_pass = n_kf * (per_pass / n_kf > 0 ? per_pass / n_kf : 1);   // whole points, at least one
     if (per_pass > P) per_pass = P;
-    const bool merged = meas_merged || never_merged, ordered = merged && mode == PTAM_MAP_REFIND_NEW_POINTS;
+    ptam_map_meas* const d_mm_res = resident ? t.d_meas_merged : nullptr;
+    ptam_map_pair* const d_nm_res = resident ? t.d_never_merged : nullptr;
+    const bool want_mm = resident ? d_mm_res != nullptr : meas_merged != nullptr, want_nm = resident ? d_nm_res != nullptr : never_merged != nullptr;
+    const bool merged = want_mm || want_nm, ordered = merged && mode == PTAM_MAP_REFIND_NEW_POINTS;
     const size_t Pz = (size_t)P, Kz = (size_t)n_kf, Wz = wpts.size() > wq.size() * 2 ? wpts.size() : wq.size() * 2;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -317,13 +335,15 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
         off += up256(bytes > 0 ? bytes : 1);
         return at;
     };
-    const size_t o_pose = take(Kz * 96), o_ls = take(Kz * sizeof(KfLevels)), o_pts = take((size_t)n_points * sizeof(ptam_map_refind_point)),
-                 o_meas = take((size_t)n_meas * sizeof(ptam_map_meas)), o_never = take((size_t)n_never * sizeof(ptam_map_pair)),
+    const size_t o_pose = take(resident ? 0 : Kz * 96), o_ls = take(Kz * sizeof(KfLevels)),
+                 o_pts = take(resident ? 0 : (size_t)n_points * sizeof(ptam_map_refind_point)),
+                 o_meas = take(resident ? 0 : (size_t)n_meas * sizeof(ptam_map_meas)),
+                 o_never = take(resident ? 0 : (size_t)n_never * sizeof(ptam_map_pair)),
                  o_w0 = take(Wz * 4), o_w1 = take(Wz * 4), o_cnt = take(MR_COUNTS * 4), o_found = take(Pz * sizeof(ptam_map_meas)),
                  o_sub = take(Pz * 4), o_nev = take(Pz * sizeof(ptam_map_pair)), o_slot = take(ordered ? Pz * 4 : 0),
                  o_ordf = take(ordered ? Pz * 4 : 0), o_ordn = take(ordered ? Pz * 4 : 0),
-                 o_mm = take(meas_merged ? (Pz + (size_t)n_meas) * sizeof(ptam_map_meas) : 0),
-                 o_nm = take(never_merged ? (Pz + (size_t)n_never) * sizeof(ptam_map_pair) : 0), o_pairs = take((size_t)per_pass * sizeof(RpPair));
+                 o_mm = take(want_mm && !resident ? (Pz + (size_t)n_meas) * sizeof(ptam_map_meas) : 0),
+                 o_nm = take(want_nm && !resident ? (Pz + (size_t)n_never) * sizeof(ptam_map_pair) : 0), o_pairs = take((size_t)per_pass * sizeof(RpPair));
     RpDev d;
     void *sc, *hp;
     if (int rc = ctx_scratch(ctx, rp_carve(d, nullptr, off, per_pass), &sc)) return rc;
@@ -333,11 +353,14 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
     hipStream_t st = ctx->stream;
     std::vector<KfLevels> hl(Kz);
     for (int k = 0; k < n_kf; k++) hl[(size_t)k] = kfs[k]->L;
-    HIP_TRY(hipMemcpyAsync(b + o_pose, kf_poses12, Kz * 96, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b + o_ls, hl.data(), Kz * sizeof(KfLevels), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b + o_pts, points, (size_t)n_points * sizeof(ptam_map_refind_point), hipMemcpyHostToDevice, st));
-    if (n_meas > 0) HIP_TRY(hipMemcpyAsync(b + o_meas, meas, (size_t)n_meas * sizeof(ptam_map_meas), hipMemcpyHostToDevice, st));
-    if (n_never > 0) HIP_TRY(hipMemcpyAsync(b + o_never, never, (size_t)n_never * sizeof(ptam_map_pair), hipMemcpyHostToDevice, st));
+    up += Kz * sizeof(KfLevels) + wpts.size() * 8 + wq.size() * sizeof(ptam_map_pair);
+    if (!resident) {
+        HIP_TRY(hipMemcpyAsync(b + o_pose, kf_poses12, Kz * 96, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + o_pts, points, (size_t)n_points * sizeof(ptam_map_refind_point), hipMemcpyHostToDevice, st));
+        if (n_meas > 0) HIP_TRY(hipMemcpyAsync(b + o_meas, meas, (size_t)n_meas * sizeof(ptam_map_meas), hipMemcpyHostToDevice, st));
+        if (n_never > 0) HIP_TRY(hipMemcpyAsync(b + o_never, never, (size_t)n_never * sizeof(ptam_map_pair), hipMemcpyHostToDevice, st));
+    }
     if (!wpts.empty()) {
         HIP_TRY(hipMemcpyAsync(b + o_w0, wpts.data(), wpts.size() * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(b + o_w1, wrank.data(), wrank.size() * 4, hipMemcpyHostToDevice, st));
@@ -353,13 +376,13 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
     a.wpts = (const int*)(b + o_w0);
     a.wrank = (const int*)(b + o_w1);
     a.wq = (const ptam_map_pair*)(b + o_w0);
-    a.poses = (const double*)(b + o_pose);
+    a.poses = resident ? t.d_poses : (const double*)(b + o_pose);
     a.Ls = (const KfLevels*)(b + o_ls);
-    a.pts = (const ptam_map_refind_point*)(b + o_pts);
+    a.pts = resident ? t.d_points : (const ptam_map_refind_point*)(b + o_pts);
     a.n_meas = n_meas;
     a.n_never = n_never;
-    a.meas = (const ptam_map_meas*)(b + o_meas);
-    a.never = (const ptam_map_pair*)(b + o_never);
+    a.meas = resident ? t.d_meas : (const ptam_map_meas*)(b + o_meas);
+    a.never = resident ? t.d_never : (const ptam_map_pair*)(b + o_never);
     a.pairs = (RpPair*)(b + o_pairs);
     a.out = d.out;
     a.kept = d.kept;
@@ -399,12 +422,12 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
         order_n = (const int*)(b + o_ordn);
         hipLaunchKernelGGL(mr_order_kernel, dim3(1), dim3(1024), 0, st, P, (const int*)a.slot, (int*)(b + o_ordf), (int*)(b + o_ordn));
     }
-    if (meas_merged)
+    if (want_mm)
         hipLaunchKernelGGL(mr_merge_kernel<ptam_map_meas>, dim3((n_meas + visited + 255) / 256 + 1), dim3(256), 0, st, n_meas, a.meas,
-                           (const int*)(a.cnt + MR_FOUND), (const ptam_map_meas*)a.found, order_f, (ptam_map_meas*)(b + o_mm));
-    if (never_merged)
+                           (const int*)(a.cnt + MR_FOUND), (const ptam_map_meas*)a.found, order_f, resident ? d_mm_res : (ptam_map_meas*)(b + o_mm));
+    if (want_nm)
         hipLaunchKernelGGL(mr_merge_kernel<ptam_map_pair>, dim3((n_never + visited + 255) / 256 + 1), dim3(256), 0, st, n_never, a.never,
-                           (const int*)(a.cnt + MR_NEVER), (const ptam_map_pair*)a.nev, order_n, (ptam_map_pair*)(b + o_nm));
+                           (const int*)(a.cnt + MR_NEVER), (const ptam_map_pair*)a.nev, order_n, resident ? d_nm_res : (ptam_map_pair*)(b + o_nm));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hp, a.cnt, MR_COUNTS * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ptam_stream_wait(st));   // the counts say how much of the lists to fetch
@@ -414,18 +437,45 @@ extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_
     r.n_skipped = hc[MR_SKIPPED];
     r.n_template_kept = hc[MR_KEPT];
     const size_t nf = (size_t)r.n_found, nn = (size_t)r.n_never;
-    if (nf > 0) {
+    down += MR_COUNTS * 4;
+    if (merged_written) *merged_written = 1;
+    if (found_out) down += nf * (sizeof(ptam_map_meas) + 4) + nn * sizeof(ptam_map_pair);
+    if (nf > 0 && found_out) {
         HIP_TRY(hipMemcpyAsync(found_out, a.found, nf * sizeof(ptam_map_meas), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(found_subpix, a.subpix, nf * 4, hipMemcpyDeviceToHost, st));
     }
-    if (nn > 0) HIP_TRY(hipMemcpyAsync(never_out, a.nev, nn * sizeof(ptam_map_pair), hipMemcpyDeviceToHost, st));
-    if (meas_merged && nf + (size_t)n_meas > 0)
+    if (nn > 0 && never_out) HIP_TRY(hipMemcpyAsync(never_out, a.nev, nn * sizeof(ptam_map_pair), hipMemcpyDeviceToHost, st));
+    if (!resident && meas_merged && nf + (size_t)n_meas > 0)
         HIP_TRY(hipMemcpyAsync(meas_merged, b + o_mm, (nf + (size_t)n_meas) * sizeof(ptam_map_meas), hipMemcpyDeviceToHost, st));
-    if (never_merged && nn + (size_t)n_never > 0)
+    if (!resident && never_merged && nn + (size_t)n_never > 0)
         HIP_TRY(hipMemcpyAsync(never_merged, b + o_nm, (nn + (size_t)n_never) * sizeof(ptam_map_pair), hipMemcpyDeviceToHost, st));
     HIP_TRY(ptam_stream_wait(st));   // (also keeps the staging vectors alive until their pageable copies have been staged)
+    if (traffic) {
+        traffic[0] = up;
+        traffic[1] = down;
+    }
     *res = r;
     return PTAM_OK;
+}
+
+extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, int n_kf,
+                               const ptam_kf* const* kfs, const double* kf_poses12, int n_points, const ptam_map_refind_point* points, int n_meas,
+                               const ptam_map_meas* meas, int n_never, const ptam_map_pair* never, int n_work, const void* work,
+                               const volatile unsigned char* stop_flag, ptam_map_refind_result* res, ptam_map_meas* found_out,
+                               int32_t* found_subpix, ptam_map_pair* never_out, int out_cap, ptam_map_meas* meas_merged,
+                               ptam_map_pair* never_merged) {
+    MrTables t = {};
+    t.n_kf = n_kf;
+    t.n_points = n_points;
+    t.n_meas = n_meas;
+    t.n_never = n_never;
+    t.kfs = kfs;
+    t.h_poses = kf_poses12;
+    t.h_points = points;
+    t.h_meas = meas;
+    t.h_never = never;
+    return mr_run(ctx, finder, opts, mode, t, n_work, work, stop_flag, res, found_out, found_subpix, never_out, out_cap, meas_merged,
+                  never_merged, nullptr, nullptr);
 }
 
 void maprefind_preload_kernels() {

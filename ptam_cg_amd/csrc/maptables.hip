@@ -15,11 +15,12 @@
 //   1024        rows (MT_TILE): a second workgroup
 //   1024 * 1024 rows (MT_TILE * MT_SCAN_CHUNK): a second round of the tile-count scan
 // The scan has no capacity of its own: any table of fewer than 2^31 rows is taken.
+// Each entry is a host front that checks the tables and uploads them into the context's scratch, a core that takes device pointers
+// and only enqueues (mt_*_core, maptables_internal.h) and a host back that downloads; the resident forms ptam_rmap_* (maprmap.hip)
+// hand the same cores the tables a ptam_rmap keeps on the device.
 #include <algorithm>
 
-#include "common.h"
-
-enum { MT_TILE = 1024, MT_SCAN_CHUNK = 1024 };
+#include "maptables_internal.h"
 
 __device__ __forceinline__ unsigned long long mt_key(int kf, int point) {   // (indices are >= 0: one unsigned compare orders (kf, point))
     return ((unsigned long long)(unsigned)kf << 32) | (unsigned)point;
@@ -86,7 +87,6 @@ __global__ void __launch_bounds__(MT_TILE) mt_scatter_kernel(Src s, int n, const
     else s.drop((int)i);
 }
 
-static inline int mt_tiles(int n) { return (int)(((long long)n + MT_TILE - 1) / MT_TILE); }
 // rows [0, n) of s, kept ones in order; *total (zeroed by the caller) = how many.  tile_cnt: room for mt_tiles(n)
 template <class Src>
 static void mt_compact(hipStream_t st, const Src& s, int n, int* tile_cnt, int* total) {
@@ -165,14 +165,19 @@ struct MtRemapQueue {   // mqNewQueue
 };
 
 // ---- the kernels around it -----------------------------------------------------------------------------------------------------
-// :916-932, one thread per outlier: the row's flag (no row is named twice) and bBad (the same byte may be set more than once)
+// :916-932, one thread per outlier: the row's flag (no row is named twice) and bBad (the same byte may be set more than once).
+// gate (nullable): the word in which the kernels launched before this one have published a refusal; then nothing is written
 __global__ void __launch_bounds__(256) mt_outliers_kernel(int n, const ptam_map_outlier* __restrict__ o, uint8_t* __restrict__ flag,
-                                                           uint8_t* __restrict__ bad) {
+                                                           uint8_t* __restrict__ bad, ptam_map_refind_point* __restrict__ points,
+                                                           const int* __restrict__ gate) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || (gate && *gate != MT_GATE_OPEN)) return;
     const ptam_map_outlier r = o[i];
-    if (r.action == PTAM_MAP_OUT_POINT_BAD) bad[r.point] = 1;
-    else flag[r.meas] = (uint8_t)r.action;
+    if (r.action == PTAM_MAP_OUT_POINT_BAD) {
+        bad[r.point] = 1;
+        if (points) points[r.point].bad = 1;
+    } else
+        flag[r.meas] = (uint8_t)r.action;
 }
 
 // out = A (sorted) merged with B (sorted, *nB_ptr rows); no key is in both: each row placed by a binary search in the other list
@@ -220,22 +225,24 @@ __global__ void __launch_bounds__(256) mt_gather_kernel(const int* __restrict__ 
     }
 }
 
-struct MtAdd {
-    int n_meas, n_made, n_points;
-    int a, b;                 // rows of meas before the two insertions: the ends of the lower / the higher keyframe's run
-    int kf_lo, kf_hi;         // the two keyframes, ascending
-    int src_is_lo, target_source;
-    const ptam_map_meas* meas;
-    const ptam_new_map_point* made;
-    ptam_map_meas* out;
-    int src_kf;
-    ptam_map_refind_point* points;
-    ptam_map_point_source* sources;
-};
+// the end of keyframe kf's run in the sorted table (an upper bound on kf alone)
+__device__ __forceinline__ int mt_run_end(const ptam_map_meas* __restrict__ m, int n, int kf) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (m[mid].kf <= kf) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
 // :673-682 / :352-362, one thread per output row: meas[0, a) | the lower keyframe's new rows | meas[a, b) | the higher one's | meas[b, n)
 __global__ void __launch_bounds__(256) mt_add_rows_kernel(MtAdd p) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long long)p.n_meas + 2ll * p.n_made) return;
+    if (p.a < 0) {   // (the same for every thread: the two searches read ~20 cached rows each)
+        p.a = mt_run_end(p.meas, p.n_meas, p.kf_lo);
+        p.b = mt_run_end(p.meas, p.n_meas, p.kf_hi);
+    }
     int old_row = -1, made_row = 0, lo = 0;
     if (t < p.a) old_row = (int)t;
     else if (t < (long long)p.a + p.n_made) made_row = (int)(t - p.a), lo = 1;
@@ -283,6 +290,12 @@ __global__ void __launch_bounds__(256) mt_add_points_kernel(MtAdd p) {
         }
         p.sources[i] = s;
     }
+    if (p.points3)
+        for (int j = 0; j < 3; j++) p.points3[(size_t)3 * i + j] = q.point.world[j];
+    if (p.bad) p.bad[i] = 0;
+    if (p.outlier_count) p.outlier_count[i] = 0;
+    if (p.inlier_count) p.inlier_count[i] = 0;
+    if (p.new_queue) p.new_queue[i] = p.n_points + i;
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
@@ -323,6 +336,53 @@ static inline bool mt_pair_less(const ptam_map_pair& x, const ptam_map_pair& y) 
     do {                                                                                         \
         if ((bytes) > 0) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, st)); \
     } while (0)
+
+// ---- the cores: device pointers in, launches on the stream, no wait (maptables_internal.h) ---------------------------------------
+// the flags, the three compactions, the merge
+int mt_apply_outliers_core(hipStream_t st, const MtOutliersDev& d) {
+    HIP_TRY(hipMemsetAsync(d.flag, 0, d.n_meas > 0 ? (size_t)d.n_meas : 1, st));
+    HIP_TRY(hipMemsetAsync(d.tot, 0, 3 * sizeof(int), st));
+    if (d.n_outliers > 0)
+        hipLaunchKernelGGL(mt_outliers_kernel, dim3((d.n_outliers + 255) / 256), dim3(256), 0, st, d.n_outliers, d.outliers, d.flag, d.bad,
+                           d.points, d.gate);
+    mt_compact(st, MtUnflaggedRows{d.flag, d.meas, d.meas_out}, d.n_meas, d.tiles, d.tot + 0);
+    mt_compact(st, MtNeverRows{d.flag, d.meas, d.new_never}, d.n_meas, d.tiles, d.tot + 1);
+    mt_compact(st, MtFailureOutliers{d.outliers, d.failure_new}, d.n_outliers, d.tiles, d.tot + 2);
+    if (d.n_never_out > 0)
+        hipLaunchKernelGGL(mt_merge_kernel, dim3((unsigned)(((long long)d.n_never_out + 255) / 256)), dim3(256), 0, st, d.n_never, d.never,
+                           (const int*)(d.tot + 1), (const ptam_map_pair*)d.new_never, d.never_out);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
+// mark, scan the points, compact every table and queue through the remap, gather the columns
+int mt_handle_bad_points_core(hipStream_t st, const MtBadDev& d) {
+    HIP_TRY(hipMemsetAsync(d.tot, 0, MT_T_COUNT * sizeof(int), st));
+    if (d.n_points > 0)
+        hipLaunchKernelGGL(mt_mark_kernel, dim3((unsigned)(((long long)d.n_points + 255) / 256)), dim3(256), 0, st, d.n_points, d.bad,
+                           d.outlier_count, d.inlier_count, d.removed, d.tot + MT_T_MARKED);
+    const int32_t* ni = d.new_index;
+    mt_compact(st, MtPoints{d.removed, d.new_index, d.kept}, d.n_points, d.tiles, d.tot + MT_T_KEPT);
+    mt_compact(st, MtRemapRows<ptam_map_meas>{ni, d.meas, d.meas_out}, d.n_meas, d.tiles, d.tot + MT_T_MEAS);
+    mt_compact(st, MtRemapRows<ptam_map_pair>{ni, d.never, d.never_out}, d.n_never, d.tiles, d.tot + MT_T_NEVER);
+    mt_compact(st, MtRemapQueue{ni, d.new_queue, d.new_out}, d.n_new, d.tiles, d.tot + MT_T_NEW);
+    mt_compact(st, MtRemapRows<ptam_map_pair>{ni, d.failure, d.failure_out}, d.n_failure, d.tiles, d.tot + MT_T_FAIL);
+    for (int k = 0; k < d.n_columns && d.n_points > 0; k++) {
+        const long long blocks = ((long long)d.n_points * d.col_dwords[k] + 255) / 256;
+        hipLaunchKernelGGL(mt_gather_kernel, dim3((unsigned)std::min(blocks, 1ll << 20)), dim3(256), 0, st, (const int*)(d.tot + MT_T_KEPT),
+                           (const int32_t*)d.kept, d.col_dwords[k], (const uint32_t*)d.col_in[k], (uint32_t*)d.col_out[k]);
+    }
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
+int mt_add_points_core(hipStream_t st, const MtAdd& p) {
+    hipLaunchKernelGGL(mt_add_rows_kernel, dim3((unsigned)(((long long)p.n_meas + 2ll * p.n_made + 255) / 256)), dim3(256), 0, st, p);
+    if (p.points || p.sources || p.points3 || p.bad || p.outlier_count || p.inlier_count || p.new_queue)
+        hipLaunchKernelGGL(mt_add_points_kernel, dim3((p.n_made + 255) / 256), dim3(256), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
 
 extern "C" int ptam_map_apply_outliers(ptam_ctx* ctx, int n_kf, int n_points, int n_meas, const ptam_map_meas* meas, int n_never,
                                        const ptam_map_pair* never, int n_failure, const ptam_map_pair* failure, int n_outliers,
@@ -379,24 +439,23 @@ extern "C" int ptam_map_apply_outliers(ptam_ctx* ctx, int n_kf, int n_points, in
     MT_UP(b + o_never, never, Vz * sizeof(ptam_map_pair));
     MT_UP(b + o_outl, outliers, Oz * sizeof(ptam_map_outlier));
     MT_UP(b + o_bad, bad, Nz);
-    HIP_TRY(hipMemsetAsync(b + o_flag, 0, Mz > 0 ? Mz : 1, st));
-    HIP_TRY(hipMemsetAsync(b + o_tot, 0, 3 * sizeof(int), st));
-    int* tot = (int*)(b + o_tot);
-    int* tiles = (int*)(b + o_tiles);
-    const ptam_map_meas* d_meas = (const ptam_map_meas*)(b + o_meas);
-    const uint8_t* d_flag = (const uint8_t*)(b + o_flag);
-
-    // ---- the flags, the three compactions, the merge
-    if (n_outliers > 0)
-        hipLaunchKernelGGL(mt_outliers_kernel, dim3((n_outliers + 255) / 256), dim3(256), 0, st, n_outliers, (const ptam_map_outlier*)(b + o_outl),
-                           (uint8_t*)(b + o_flag), (uint8_t*)(b + o_bad));
-    mt_compact(st, MtUnflaggedRows{d_flag, d_meas, (ptam_map_meas*)(b + o_mo)}, n_meas, tiles, tot + 0);
-    mt_compact(st, MtNeverRows{d_flag, d_meas, (ptam_map_pair*)(b + o_nn)}, n_meas, tiles, tot + 1);
-    mt_compact(st, MtFailureOutliers{(const ptam_map_outlier*)(b + o_outl), (ptam_map_pair*)(b + o_fo)}, n_outliers, tiles, tot + 2);
-    if (r.n_never_out > 0)
-        hipLaunchKernelGGL(mt_merge_kernel, dim3((unsigned)(((long long)r.n_never_out + 255) / 256)), dim3(256), 0, st, n_never,
-                           (const ptam_map_pair*)(b + o_never), (const int*)(tot + 1), (const ptam_map_pair*)(b + o_nn), (ptam_map_pair*)(b + o_no));
-    HIP_TRY(hipGetLastError());
+    MtOutliersDev d = {};
+    d.n_meas = n_meas;
+    d.n_never = n_never;
+    d.n_outliers = n_outliers;
+    d.n_never_out = r.n_never_out;
+    d.meas = (const ptam_map_meas*)(b + o_meas);
+    d.never = (const ptam_map_pair*)(b + o_never);
+    d.outliers = (const ptam_map_outlier*)(b + o_outl);
+    d.bad = (uint8_t*)(b + o_bad);
+    d.flag = (uint8_t*)(b + o_flag);
+    d.tot = (int*)(b + o_tot);
+    d.tiles = (int*)(b + o_tiles);
+    d.new_never = (ptam_map_pair*)(b + o_nn);
+    d.meas_out = (ptam_map_meas*)(b + o_mo);
+    d.never_out = (ptam_map_pair*)(b + o_no);
+    d.failure_new = (ptam_map_pair*)(b + o_fo);
+    if (int rc = mt_apply_outliers_core(st, d)) return rc;
 
     // ---- down: every size is known from the outlier list
     MT_DOWN(meas_out, b + o_mo, (size_t)r.n_meas_out * sizeof(ptam_map_meas));
@@ -437,7 +496,8 @@ extern "C" int ptam_map_handle_bad_points(ptam_ctx* ctx, int n_kf, int n_points,
     HIP_TRY(hipSetDevice(ctx->device));
 
     // ---- device memory
-    enum { T_KEPT = 0, T_MEAS, T_NEVER, T_NEW, T_FAIL, T_MARKED, T_COUNT };
+    enum { T_KEPT = MT_T_KEPT, T_MEAS = MT_T_MEAS, T_NEVER = MT_T_NEVER, T_NEW = MT_T_NEW, T_FAIL = MT_T_FAIL, T_MARKED = MT_T_MARKED,
+           T_COUNT = MT_T_COUNT };
     const size_t Nz = (size_t)n_points, Mz = (size_t)n_meas, Vz = (size_t)n_never, Qz = (size_t)n_new, Fz = (size_t)n_failure;
     const int longest = std::max(std::max(n_points, n_meas), std::max(std::max(n_never, n_new), n_failure));
     MtCarve c;
@@ -467,29 +527,36 @@ extern "C" int ptam_map_handle_bad_points(ptam_ctx* ctx, int n_kf, int n_points,
     MT_UP(b + o_new, new_queue, Qz * 4);
     MT_UP(b + o_fail, failure, Fz * sizeof(ptam_map_pair));
     for (int k = 0; k < n_columns; k++) MT_UP(b + o_cin[k], columns[k].data, Nz * (size_t)columns[k].row_bytes);
-    HIP_TRY(hipMemsetAsync(b + o_tot, 0, T_COUNT * sizeof(int), st));
-    int* tot = (int*)(b + o_tot);
-    int* tiles = (int*)(b + o_tiles);
-    const int32_t* d_ni = (const int32_t*)(b + o_ni);
-
-    // ---- mark, scan the points, compact every table and queue through the remap, gather the columns
-    if (n_points > 0)
-        hipLaunchKernelGGL(mt_mark_kernel, dim3((unsigned)(((long long)n_points + 255) / 256)), dim3(256), 0, st, n_points,
-                           bad ? (const uint8_t*)(b + o_bad) : nullptr, outlier_count ? (const int32_t*)(b + o_cnt_o) : nullptr,
-                           outlier_count ? (const int32_t*)(b + o_cnt_i) : nullptr, (uint8_t*)(b + o_rem), tot + T_MARKED);
-    mt_compact(st, MtPoints{(const uint8_t*)(b + o_rem), (int32_t*)(b + o_ni), (int32_t*)(b + o_kept)}, n_points, tiles, tot + T_KEPT);
-    mt_compact(st, MtRemapRows<ptam_map_meas>{d_ni, (const ptam_map_meas*)(b + o_meas), (ptam_map_meas*)(b + o_mo)}, n_meas, tiles, tot + T_MEAS);
-    mt_compact(st, MtRemapRows<ptam_map_pair>{d_ni, (const ptam_map_pair*)(b + o_never), (ptam_map_pair*)(b + o_no)}, n_never, tiles, tot + T_NEVER);
-    mt_compact(st, MtRemapQueue{d_ni, (const int32_t*)(b + o_new), (int32_t*)(b + o_qo)}, n_new, tiles, tot + T_NEW);
-    mt_compact(st, MtRemapRows<ptam_map_pair>{d_ni, (const ptam_map_pair*)(b + o_fail), (ptam_map_pair*)(b + o_fo)}, n_failure, tiles, tot + T_FAIL);
-    for (int k = 0; k < n_columns && n_points > 0; k++) {
-        const int dwords = columns[k].row_bytes / 4;
-        const long long blocks = ((long long)n_points * dwords + 255) / 256;
-        hipLaunchKernelGGL(mt_gather_kernel, dim3((unsigned)std::min(blocks, 1ll << 20)), dim3(256), 0, st, (const int*)(tot + T_KEPT),
-                           (const int32_t*)(b + o_kept), dwords, (const uint32_t*)(b + o_cin[k]), (uint32_t*)(b + o_cout[k]));
+    MtBadDev d = {};
+    d.n_points = n_points;
+    d.n_meas = n_meas;
+    d.n_never = n_never;
+    d.n_new = n_new;
+    d.n_failure = n_failure;
+    d.n_columns = n_columns;
+    d.bad = bad ? (const uint8_t*)(b + o_bad) : nullptr;
+    d.outlier_count = outlier_count ? (const int32_t*)(b + o_cnt_o) : nullptr;
+    d.inlier_count = outlier_count ? (const int32_t*)(b + o_cnt_i) : nullptr;
+    d.meas = (const ptam_map_meas*)(b + o_meas);
+    d.never = (const ptam_map_pair*)(b + o_never);
+    d.new_queue = (const int32_t*)(b + o_new);
+    d.failure = (const ptam_map_pair*)(b + o_fail);
+    d.removed = (uint8_t*)(b + o_rem);
+    d.tot = (int*)(b + o_tot);
+    d.tiles = (int*)(b + o_tiles);
+    d.new_index = (int32_t*)(b + o_ni);
+    d.kept = (int32_t*)(b + o_kept);
+    d.meas_out = (ptam_map_meas*)(b + o_mo);
+    d.never_out = (ptam_map_pair*)(b + o_no);
+    d.new_out = (int32_t*)(b + o_qo);
+    d.failure_out = (ptam_map_pair*)(b + o_fo);
+    for (int k = 0; k < n_columns; k++) {
+        d.col_in[k] = b + o_cin[k];
+        d.col_out[k] = b + o_cout[k];
+        d.col_dwords[k] = columns[k].row_bytes / 4;
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hp, tot, T_COUNT * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (int rc = mt_handle_bad_points_core(st, d)) return rc;
+    HIP_TRY(hipMemcpyAsync(hp, d.tot, T_COUNT * sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(ptam_stream_wait(st));   // the counts say how much of each table to fetch
     const int* hc = (const int*)hp;
     ptam_map_bad_points_result r = {};
@@ -530,7 +597,7 @@ extern "C" int ptam_map_add_points(ptam_ctx* ctx, int n_kf, int n_points, int n_
         return PTAM_OK;
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    MtAdd p;
+    MtAdd p = {};
     p.n_meas = n_meas;
     p.n_made = n_made;
     p.n_points = n_points;
@@ -561,9 +628,7 @@ extern "C" int ptam_map_add_points(ptam_ctx* ctx, int n_kf, int n_points, int n_
     p.out = (ptam_map_meas*)(b + o_mo);
     p.points = points_out ? (ptam_map_refind_point*)(b + o_pts) : nullptr;
     p.sources = sources_out ? (ptam_map_point_source*)(b + o_src) : nullptr;
-    hipLaunchKernelGGL(mt_add_rows_kernel, dim3((unsigned)(((long long)n_meas + 2ll * n_made + 255) / 256)), dim3(256), 0, st, p);
-    if (points_out || sources_out) hipLaunchKernelGGL(mt_add_points_kernel, dim3((n_made + 255) / 256), dim3(256), 0, st, p);
-    HIP_TRY(hipGetLastError());
+    if (int rc = mt_add_points_core(st, p)) return rc;
     MT_DOWN(meas_out, b + o_mo, (Mz + 2 * Az) * sizeof(ptam_map_meas));
     if (points_out) MT_DOWN(points_out, b + o_pts, Az * sizeof(ptam_map_refind_point));
     if (sources_out) MT_DOWN(sources_out, b + o_src, Az * sizeof(ptam_map_point_source));

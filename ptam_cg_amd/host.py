@@ -855,6 +855,207 @@ def map_add_points(ctx, n_kf, n_points, meas, src_kf, target_kf, made, target_so
                 new_queue=np.arange(int(n_points), int(n_points) + A, dtype=np.int32))
 
 
+MAP_KF_ROW_DT = np.dtype([("point", "<i4"), ("level", "<i4"), ("root_pos", "<f8", (2,))])
+assert MAP_KF_ROW_DT.itemsize == C.sizeof(_abi.MapKfRow) == 24 and C.sizeof(_abi.RmapCounts) == 24
+
+
+class ResidentMap:
+    """ptam_rmap: the tables of the map_* calls kept in device memory from call to call, and the resident form of each edit of one
+    MapMaker::run() iteration (src/MapMaker.cc:57-114).  A method returns the dict of counts of the host.map_* wrapper it stands
+    for; the tables stay on the device and come down through download() / tables()."""
+    TABLES = {"poses": (_abi.RMAP_KF_POSES, np.dtype(("<f8", (12,)))), "fixed": (_abi.RMAP_KF_FIXED, np.dtype(np.uint8)),
+              "points3": (_abi.RMAP_POINTS3, np.dtype(("<f8", (3,)))), "points": (_abi.RMAP_REFIND_POINTS, MAP_REFIND_POINT_DT),
+              "sources": (_abi.RMAP_SOURCES, MAP_POINT_SOURCE_DT), "bad": (_abi.RMAP_BAD, np.dtype(np.uint8)),
+              "outlier_count": (_abi.RMAP_OUTLIER_COUNT, np.dtype(np.int32)), "inlier_count": (_abi.RMAP_INLIER_COUNT, np.dtype(np.int32)),
+              "meas": (_abi.RMAP_MEAS, MAP_MEAS_DT), "never": (_abi.RMAP_NEVER, MAP_PAIR_DT),
+              "new_queue": (_abi.RMAP_NEW_QUEUE, np.dtype(np.int32)), "failure": (_abi.RMAP_FAILURE, MAP_PAIR_DT)}
+    COUNT_OF = {"poses": "n_kf", "fixed": "n_kf", "meas": "n_meas", "never": "n_never", "new_queue": "n_new", "failure": "n_failure"}
+
+    def __init__(self, ctx):
+        self.ctx, self.lib = ctx, ctx.lib   # (holds the Context: close the map before the context, ptam_rmap_destroy reads it)
+        self.h = C.c_void_p()
+        self._kfs = []                      # the KeyFrame objects whose handles the map holds stay alive with it
+        ctx._check(self.lib.rmap_create(ctx.h, C.byref(self.h)), "rmap_create")
+
+    def reserve(self, n_kf=0, n_points=0, n_meas=0, n_never=0, n_new=0, n_failure=0):
+        self.ctx._check(self.lib.rmap_reserve(self.h, int(n_kf), int(n_points), int(n_meas), int(n_never), int(n_new), int(n_failure)),
+                        "rmap_reserve")
+
+    def counts(self):
+        c = _abi.RmapCounts()
+        self.ctx._check(self.lib.rmap_counts(self.h, C.byref(c)), "rmap_counts")
+        return _counts(c)
+
+    def traffic(self):
+        """-> (bytes host to device, bytes device to host) of all the handle's calls so far"""
+        up, down = C.c_ulonglong(), C.c_ulonglong()
+        self.ctx._check(self.lib.rmap_traffic(self.h, C.byref(up), C.byref(down)), "rmap_traffic")
+        return up.value, down.value
+
+    def last_refusal(self):
+        """-> (table, row) of the last call the device refused"""
+        t, r = C.c_int(), C.c_int()
+        self.ctx._check(self.lib.rmap_last_refusal(self.h, C.byref(t), C.byref(r)), "rmap_last_refusal")
+        return t.value, r.value
+
+    @staticmethod
+    def _host_tables(poses, fixed, points3, points, sources, bad, meas, never, new_queue, failure, outlier_count, inlier_count):
+        t = dict(poses=np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12), fixed=np.ascontiguousarray(fixed, dtype=np.uint8).reshape(-1),
+                 points3=np.ascontiguousarray(points3, dtype=np.float64).reshape(-1, 3), points=np.ascontiguousarray(points, dtype=MAP_REFIND_POINT_DT),
+                 sources=np.ascontiguousarray(sources, dtype=MAP_POINT_SOURCE_DT), bad=np.ascontiguousarray(bad, dtype=np.uint8).reshape(-1),
+                 meas=np.ascontiguousarray(meas, dtype=MAP_MEAS_DT),
+                 never=np.ascontiguousarray(never if never is not None else np.zeros(0, MAP_PAIR_DT), dtype=MAP_PAIR_DT),
+                 new_queue=np.ascontiguousarray(new_queue if new_queue is not None else np.zeros(0, np.int32), dtype=np.int32).reshape(-1),
+                 failure=np.ascontiguousarray(failure if failure is not None else np.zeros(0, MAP_PAIR_DT), dtype=MAP_PAIR_DT),
+                 outlier_count=None if outlier_count is None else np.ascontiguousarray(outlier_count, dtype=np.int32).reshape(-1),
+                 inlier_count=None if inlier_count is None else np.ascontiguousarray(inlier_count, dtype=np.int32).reshape(-1))
+        if len(t["fixed"]) != len(t["poses"]):
+            raise ValueError("ResidentMap.upload: one fixed flag per keyframe")
+        for k in ("points", "sources", "bad", "outlier_count", "inlier_count"):
+            if t[k] is not None and len(t[k]) != len(t["points3"]):
+                raise ValueError("ResidentMap.upload: one row per point in " + k)
+        return t
+
+    def upload(self, poses, fixed, points3, points, sources, bad, meas, never=None, new_queue=None, failure=None, outlier_count=None,
+               inlier_count=None, kfs=None, check=True):
+        """Replaces the whole map (ptam_rmap_upload): poses (K, 12), fixed (K,), points3 (N, 3), points MAP_REFIND_POINT_DT, sources
+        MAP_POINT_SOURCE_DT, bad (N,) uint8, meas MAP_MEAS_DT and never MAP_PAIR_DT sorted by (kf, point), new_queue point indices,
+        failure MAP_PAIR_DT, the two counts (N,) int32 or both None (zeros), kfs a list of KeyFrame or None.  The order and range
+        check runs on the device.  check=False: -> the status instead of raising (last_refusal() names the row)."""
+        t = self._host_tables(poses, fixed, points3, points, sources, bad, meas, never, new_queue, failure, outlier_count, inlier_count)
+        handles = None
+        if kfs is not None:
+            handles = np.array([k.h.value if hasattr(k.h, "value") else int(k.h) for k in kfs], dtype=np.uint64)
+            if len(handles) != len(t["poses"]):
+                raise ValueError("ResidentMap.upload: one keyframe handle per pose")
+        rc = self.lib.rmap_upload(self.h, len(t["poses"]), _ptr(handles), _ptr(t["poses"]), _ptr(t["fixed"]), len(t["points3"]), _ptr(t["points3"]),
+                                  _ptr(t["points"]), _ptr(t["sources"]), _ptr(t["bad"]), _ptr(t["outlier_count"]), _ptr(t["inlier_count"]),
+                                  len(t["meas"]), _ptr(t["meas"]), len(t["never"]), _ptr(t["never"]), len(t["new_queue"]), _ptr(t["new_queue"]),
+                                  len(t["failure"]), _ptr(t["failure"]))
+        if rc == 0:
+            self._kfs = list(kfs) if kfs is not None else []
+        return self.ctx._check(rc, "rmap_upload") if check else rc
+
+    def download(self, which, first=0, count=None):
+        """rows [first, first + count) of one table (a key of TABLES; count None: to the table's end)"""
+        idx, dt = self.TABLES[which]
+        n = self.counts()[self.COUNT_OF.get(which, "n_points")]
+        count = n - first if count is None else int(count)
+        out = np.zeros(max(count, 0), dt)
+        self.ctx._check(self.lib.rmap_download(self.h, idx, int(first), count, _ptr(out) if count > 0 else None), "rmap_download")
+        return out
+
+    def tables(self):
+        """every table, downloaded: dict by the keys of TABLES"""
+        return {k: self.download(k) for k in self.TABLES}
+
+    def bundle_adjust(self, mode, abort=None, **ba_opts):
+        """map_bundle_adjust on the resident tables -> its counts with "outliers", "cam_kf" and "point_ids"; the adjusted poses
+        and points stay on the device (download("poses") / download("points3"))"""
+        o = BaOpts()
+        self.lib.ba_opts_default(C.byref(o))
+        for k, v in ba_opts.items():
+            setattr(o, k, v)
+        c = self.counts()
+        K, N, M = c["n_kf"], c["n_points"], c["n_meas"]
+        res = _abi.MapBaResult()
+        out, cam_kf, point_ids = np.zeros(max(M, 1), MAP_OUTLIER_DT), np.zeros(max(K, 1), np.int32), np.zeros(max(N, 1), np.int32)
+        self.ctx._check(self.lib.rmap_bundle_adjust(self.h, C.byref(o), int(mode), _ptr(abort), C.byref(res), _ptr(out), M, _ptr(cam_kf),
+                                                    _ptr(point_ids)), "rmap_bundle_adjust")
+        d = _counts(res)
+        d.update(outliers=out[:res.n_outliers].copy(), cam_kf=cam_kf[:res.n_adjust + res.n_fixed].copy(), point_ids=point_ids[:res.n_points].copy())
+        return d
+
+    def refind(self, finder, mode, work=None, stop=None, max_pairs_per_pass=0, lists=True):
+        """map_refind on the resident tables through `finder` (a ReFinder): work None = the resident queue (NEW_POINTS: popped by
+        points_consumed; FAILURE_QUEUE: cleared).  -> the result counts, with "found", "found_subpix", "never" when lists is set; the
+        merged tables stay on the device"""
+        c = self.counts()
+        if work is None:
+            W, wp = {_abi.MAP_REFIND_NEW_POINTS: c["n_new"], _abi.MAP_REFIND_FAILURE_QUEUE: c["n_failure"]}[mode], None
+        else:
+            work = np.ascontiguousarray(work, dtype=MAP_PAIR_DT if mode == _abi.MAP_REFIND_FAILURE_QUEUE else np.int32).reshape(-1)
+            W, wp = len(work), _ptr(work)
+        cap = map_refind_pair_count(mode, c["n_kf"], c["n_points"], W)
+        found = subpix = nev = None
+        if lists:
+            found, subpix, nev = np.zeros(max(cap, 1), MAP_MEAS_DT), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), MAP_PAIR_DT)
+        o, res = _abi.MapRefindOpts(int(max_pairs_per_pass), 0), _abi.MapRefindResult()
+        self.ctx._check(self.lib.rmap_refind(self.h, finder.h, C.byref(o), int(mode), 0 if work is None else W, wp, _ptr(stop), C.byref(res),
+                                             _ptr(found), _ptr(subpix), _ptr(nev), cap), "rmap_refind")
+        d = _counts(res)
+        if lists:
+            d.update(found=found[:res.n_found].copy(), found_subpix=subpix[:res.n_found].copy(), never=nev[:res.n_never].copy())
+        return d
+
+    def apply_global_transform(self, se3_new_from_old, rows=True):
+        """map_apply_global_transform on the resident tables -> the pvs rows (PVS_POINT_DT) when asked for, else None"""
+        se3 = np.ascontiguousarray(se3_new_from_old, dtype=np.float64).reshape(12)
+        n = self.counts()["n_points"]
+        out = np.zeros(max(n, 1), PVS_POINT_DT) if rows else None
+        self.ctx._check(self.lib.rmap_apply_global_transform(self.h, _pd(se3), _ptr(out)), "rmap_apply_global_transform")
+        return out[:n] if rows else None
+
+    def apply_outliers(self, outliers, check=True):
+        """map_apply_outliers on the resident tables -> its counts"""
+        outliers = np.ascontiguousarray(outliers, dtype=MAP_OUTLIER_DT)
+        res = _abi.MapOutliersResult()
+        rc = self.lib.rmap_apply_outliers(self.h, len(outliers), _ptr(outliers), C.byref(res))
+        if not check and rc < 0:
+            return rc
+        self.ctx._check(rc, "rmap_apply_outliers")
+        return _counts(res)
+
+    def handle_bad_points(self, kept=False, new_index=False):
+        """map_handle_bad_points on the resident tables -> its counts, with "kept" / "new_index" when asked for"""
+        n = self.counts()["n_points"]
+        k = np.zeros(max(n, 1), np.int32) if kept else None
+        ni = np.zeros(max(n, 1), np.int32) if new_index else None
+        res = _abi.MapBadPointsResult()
+        self.ctx._check(self.lib.rmap_handle_bad_points(self.h, C.byref(res), _ptr(k), _ptr(ni)), "rmap_handle_bad_points")
+        d = _counts(res)
+        if kept:
+            d["kept"] = k[:res.n_kept].copy()
+        if new_index:
+            d["new_index"] = ni[:n].copy()
+        return d
+
+    def add_points(self, src_kf, target_kf, made, target_source=_abi.SRC_EPIPOLAR, check=True):
+        """map_add_points on the resident tables -> the status"""
+        made = np.ascontiguousarray(made, dtype=NEW_MAP_POINT_DT)
+        rc = self.lib.rmap_add_points(self.h, int(src_kf), int(target_kf), int(target_source), len(made), _ptr(made))
+        return self.ctx._check(rc, "rmap_add_points") if check else rc
+
+    def add_keyframe(self, pose, fixed, rows, kf=None, check=True):
+        """the table side of AddKeyFrameFromTopOfQueue: rows MAP_KF_ROW_DT sorted by point -> the status"""
+        rows = np.ascontiguousarray(rows, dtype=MAP_KF_ROW_DT)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        rc = self.lib.rmap_add_keyframe(self.h, kf.h if kf is not None else None, _pd(pose), int(bool(fixed)), len(rows), _ptr(rows))
+        if rc == 0:
+            self._kfs.append(kf)
+        return self.ctx._check(rc, "rmap_add_keyframe") if check else rc
+
+    def note_tracked(self, points, outlier_flags):
+        """the tracker's iteration set (Tracker.iteration_set) into the two counts"""
+        points = np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
+        flags = np.ascontiguousarray(outlier_flags, dtype=np.uint8).reshape(-1)
+        if len(points) != len(flags):
+            raise ValueError("ResidentMap.note_tracked: one flag per point")
+        self.ctx._check(self.lib.rmap_note_tracked(self.h, len(points), _ptr(points), _ptr(flags)), "rmap_note_tracked")
+
+    def scene_depth(self):
+        """map_scene_depth on the resident tables -> SCENE_DEPTH_DT, one row per keyframe"""
+        k = self.counts()["n_kf"]
+        out = np.zeros(max(k, 1), SCENE_DEPTH_DT)
+        self.ctx._check(self.lib.rmap_scene_depth(self.h, _ptr(out)), "rmap_scene_depth")
+        return out[:k]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.rmap_destroy(self.h)
+            self.h = None
+
+
 class Tracker:
     """Tracker::TrackMap (src/Tracker.cc:442-696) as one device-resident chain (ptam_tracker_* / ptam_track_map): the map
     stays on the device, a frame is one call."""
