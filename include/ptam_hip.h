@@ -1267,6 +1267,52 @@ int ptam_rmap_add_keyframe(ptam_rmap*, const ptam_kf* kf, const double pose12[12
 int ptam_rmap_note_tracked(ptam_rmap*, int n, const int32_t* points, const uint8_t* outlier_flags);
 /* ptam_map_scene_depth on the resident tables.  out: n_kf rows, host.  Moves n_kf * sizeof(ptam_scene_depth) down. */
 int ptam_rmap_scene_depth(ptam_rmap*, ptam_scene_depth* out);
+/* MapMaker::ClosestKeyFrame / NClosestKeyFrames (src/MapMaker.cc:711-752) on the resident pose table: the n_out = min(n, n_kf - 1)
+ * keyframes other than `kf` that come first by (KeyFrameLinearDist(kf, k), k), ascending — a strictly lower distance wins, equal
+ * distances go to the lower index.  One one-workgroup kernel, in the arithmetic ptam_rmap_bundle_adjust(RECENT) chooses its four
+ * nearest with (camera centres of se3CfromW^-1 in uncontracted fp64, sqrt).  out_kf, out_dist: room for min(n, n_kf - 1) entries.
+ * PTAM_E_ARG: kf outside [0, n_kf), n < 1.  Moves 8 + 12 n_out bytes down and nothing else. */
+int ptam_rmap_closest_keyframes(ptam_rmap*, int kf, int n, int32_t* out_kf, double* out_dist, int32_t* n_out);
+
+/* MapMaker::AddKeyFrameFromTopOfQueue (src/MapMaker.cc:493-518) after MakeKeyFrame_Rest, as ONE call on the resident map. */
+typedef struct {
+    ptam_epipolar_opts epipolar;        /* levels {3,0,1,2}, the new keyframe's depth_mean/sigma, wiggle, threshold */
+    ptam_map_refind_opts refind;        /* as ptam_rmap_refind */
+    int32_t target_kf;                  /* -1: ClosestKeyFrame of the new keyframe */
+    int32_t skip_refind, skip_points;   /* 0 / 0 is the reference */
+} ptam_rmap_insert_opts;
+typedef struct {
+    int32_t kf;                         /* the new keyframe's index */
+    int32_t target_kf;                  /* -1 with skip_points */
+    double target_dist;                 /* KeyFrameLinearDist(kf, target_kf) */
+    ptam_map_refind_result refind;
+    int32_t first_point, n_made;        /* the new points are [first_point, first_point + n_made) */
+    ptam_epipolar_level_stats levels[4];
+} ptam_rmap_insert_result;
+/* The steps, each enqueued behind the one it depends on:
+ *   (a) ptam_rmap_add_keyframe's table step (:501-506);
+ *   (b) ptam_rmap_refind(KEYFRAME) of the new keyframe through `finder` (:508): the merged tables become the map's;
+ *   (c) target_kf < 0: the closest keyframe (AddSomeMapPoints' ClosestKeyFrame, :451), by ptam_rmap_closest_keyframes' kernel
+ *       (it reads the poses alone and is enqueued with (a)); target_kf >= 0: the same kernel measures that keyframe's distance;
+ *   (d) a kernel writes the busy list of ThinCandidates (:415-441) from the new keyframe's run in the resident measurement
+ *       table as (b) left it — the run of the highest keyframe index is the table's tail;
+ *   (e) the launch chain of ptam_add_map_points_epipolar (:511-514), the target's pose taken from the handle's mirror and its
+ *       implane tables built on its handle (as ptam_add_map_points_epipolar does on the target it is given);
+ *   (f) the made count and the level stats come down in one wait;
+ *   (g) ptam_rmap_add_points' kernels on the chain's device output, target_source = PTAM_MAP_SRC_EPIPOLAR, the new points'
+ *       indices to the end of new_queue.
+ * The ptam_new_map_point records never leave the device: the tracker's rows are
+ * ptam_rmap_download(PTAM_RMAP_REFIND_POINTS, first_point, n_made).  skip_refind / skip_points leave out (b) / (c)-(g).
+ * Everything that can refuse the call is decided on the host before anything is enqueued, and a refused call leaves every table
+ * and count as it was.  PTAM_E_ARG: rows unsorted, repeated or out of range; kf null, or (unless both steps are skipped) a
+ * keyframe of the map without a handle; target_kf outside [-1, n_kf) (the new keyframe's own index n_kf included); the level list
+ * as ptam_add_map_points_epipolar.  PTAM_E_STATE, unless skip_points: kf has no MakeKeyFrame_Rest; the map has no keyframe
+ * (where the reference's assert(nClosest != -1) stands).
+ * Moves 97 + 24 n_rows bytes, the re-find's level records (at most PTAM_RMAP_KF_RECORD_BYTES per keyframe) up; 20 bytes for (c),
+ * the re-find's 16 bytes of counts and 16 + 4 sizeof(ptam_epipolar_level_stats) bytes for (f) down.  Nothing proportional to the
+ * candidates, the made points or the measurement table moves. */
+int ptam_rmap_insert_keyframe(ptam_rmap*, ptam_refinder*, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows,
+                              const ptam_map_kf_row* rows, const ptam_rmap_insert_opts*, ptam_rmap_insert_result*);
 
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,

@@ -1124,6 +1124,38 @@ public:
         check(ptam_rmap_scene_depth(h_, v.data()), "ptam_rmap_scene_depth");
         return v;
     }
+    // MapMaker::ClosestKeyFrame / NClosestKeyFrames   src/MapMaker.cc:711-752 on the resident poses: the min(n, keyframes - 1) others
+    // nearest to keyframe nKF by (KeyFrameLinearDist, index); pvDist: their distances
+    std::vector<int32_t> ClosestKeyFrames(int nKF, int n = 1, std::vector<double>* pvDist = nullptr) {
+        const int cap = std::max(std::min(n, Counts().n_kf - 1), 1);
+        std::vector<int32_t> v((size_t)cap);
+        std::vector<double> d((size_t)cap);
+        int32_t got = 0;
+        check(ptam_rmap_closest_keyframes(h_, nKF, n, v.data(), d.data(), &got), "ptam_rmap_closest_keyframes");
+        v.resize((size_t)got);
+        d.resize((size_t)got);
+        if (pvDist) *pvDist = d;
+        return v;
+    }
+    // MapMaker::AddKeyFrameFromTopOfQueue   src/MapMaker.cc:493-518 after pK's MakeKeyFrame_Rest, as one call: the keyframe's rows
+    // (vRows sorted by point), ReFindInSingleKeyFrame, ClosestKeyFrame, AddSomeMapPoints at opts.epipolar.levels; the new points
+    // stay on the device: Download<ptam_map_refind_point>(PTAM_RMAP_REFIND_POINTS, first_point, n_made) are the tracker's rows
+    static ptam_rmap_insert_opts InsertOpts(double dDepthMean, double dDepthSigma) {
+        ptam_rmap_insert_opts o{};
+        ptam_epipolar_opts_default(&o.epipolar);
+        o.epipolar.depth_mean = dDepthMean;
+        o.epipolar.depth_sigma = dDepthSigma;
+        o.target_kf = -1;
+        return o;
+    }
+    ptam_rmap_insert_result InsertKeyFrame(ReFinder& finder, const KeyFrame& k, const SE3& se3CfromW, bool bFixed,
+                                           const std::vector<ptam_map_kf_row>& vRows, const ptam_rmap_insert_opts& opts) {
+        ptam_rmap_insert_result r{};
+        check(ptam_rmap_insert_keyframe(h_, finder.handle(), k.handle(), reinterpret_cast<const double*>(&se3CfromW), bFixed, (int)vRows.size(),
+                                        vRows.data(), &opts, &r),
+              "ptam_rmap_insert_keyframe");
+        return r;
+    }
     ptam_rmap* handle() const { return h_; }
 
 private:

@@ -243,6 +243,18 @@ class MapKfRow(C.Structure):
     _fields_ = [("point", C.c_int32), ("level", C.c_int32), ("root_pos", C.c_double * 2)]
 
 
+class RmapInsertOpts(C.Structure):
+    """ptam_rmap_insert_opts"""
+    _fields_ = [("epipolar", EpipolarOpts), ("refind", MapRefindOpts), ("target_kf", C.c_int32), ("skip_refind", C.c_int32),
+                ("skip_points", C.c_int32)]
+
+
+class RmapInsertResult(C.Structure):
+    """ptam_rmap_insert_result (MapMaker::AddKeyFrameFromTopOfQueue, src/MapMaker.cc:493-518)"""
+    _fields_ = [("kf", C.c_int32), ("target_kf", C.c_int32), ("target_dist", C.c_double), ("refind", MapRefindResult),
+                ("first_point", C.c_int32), ("n_made", C.c_int32), ("levels", EpipolarLevelStats * 4)]
+
+
 class SbiAlignment(C.Structure):
     """ptam_sbi_alignment (SmallBlurryImage::CalcSBIRotation, src/ImageProcess.cc:313-495)"""
     _fields_ = [("se2_rot", C.c_double * 4), ("se2_trans", C.c_double * 2), ("score", C.c_double), ("mean_offset", C.c_double),
@@ -420,6 +432,8 @@ PROTOTYPES = {
     "rmap_add_keyframe": (_i, [_vp, _vp, _pd, _i, _i, _vp]),
     "rmap_note_tracked": (_i, [_vp, _i, _vp, _vp]),
     "rmap_scene_depth": (_i, [_vp, _vp]),
+    "rmap_closest_keyframes": (_i, [_vp, _i, _i, _vp, _pd, C.POINTER(C.c_int32)]),
+    "rmap_insert_keyframe": (_i, [_vp, _vp, _vp, _pd, _i, _i, _vp, C.POINTER(RmapInsertOpts), C.POINTER(RmapInsertResult)]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

@@ -27,7 +27,7 @@
 
 #include "bundle.h"
 #include "maptables_internal.h"   // MbaTables, mba_run
-#include "patch_device.h"   // nc_mul / nc_add / nc_sub
+#include "kf_dist_device.h"   // mba_centre, mba_linear_dist, mba_pair_less, mba_block_least
 
 namespace {
 
@@ -67,18 +67,9 @@ __device__ __forceinline__ bool mba_row_ok(const MbaDev& a, const ptam_map_meas&
     return (unsigned)m.kf < (unsigned)a.K && (unsigned)m.point < (unsigned)a.N && (unsigned)m.level < 4u && (unsigned)m.source < 5u;
 }
 
-// se3CfromW.inverse().get_translation() = -(R^T t), TooN's row dot products left to right, no contraction
-__device__ __forceinline__ void mba_centre(const double* P, double c[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) c[i] = -nc_add(nc_add(nc_mul(P[i], P[9]), nc_mul(P[3 + i], P[10])), nc_mul(P[6 + i], P[11]));
-}
-
-// std::pair<double, KeyFrame*>::operator< with the keyframe index in place of the pointer
-__device__ __forceinline__ bool mba_pair_less(double d1, int k1, double d2, int k2) { return d1 < d2 || (!(d2 < d1) && k1 < k2); }
-
 // ---- set choice: BundleAdjustRecent's adjust set (:797-803) / BundleAdjustAll's roles (:770-776) ----------------------------------
 __global__ void __launch_bounds__(1024) mba_select_kernel(MbaDev a) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) a.hdr->err_row = INT_MAX;
     if (a.mode == PTAM_MAP_BA_ALL) {
         for (int k = tid; k < a.K; k += 1024) a.role[k] = a.fixed[k] ? ROLE_FIXED : ROLE_ADJUST;
@@ -98,24 +89,11 @@ __global__ void __launch_bounds__(1024) mba_select_kernel(MbaDev a) {
             bool taken = false;
             for (int q = 0; q < r; q++) taken |= chosen[q] == k;
             if (taken) continue;
-            double c[3];
-            mba_centre(a.pose + (size_t)12 * k, c);   // KeyFrameLinearDist(k1 = newest, k2 = k): v3Diff = c2 - c1 (:700-701)
-            const double dx = nc_sub(c[0], c0[0]), dy = nc_sub(c[1], c0[1]), dz = nc_sub(c[2], c0[2]);
-            const double d = sqrt(nc_add(nc_add(nc_mul(dx, dx), nc_mul(dy, dy)), nc_mul(dz, dz)));
+            const double d = mba_linear_dist(c0, a.pose + (size_t)12 * k);   // KeyFrameLinearDist(k1 = newest, k2 = k) (:700-701)
             if (bk < 0 || mba_pair_less(d, k, bd, bk)) bd = d, bk = k;
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            const double od = __shfl_xor(bd, o, 64);
-            const int ok = __shfl_xor(bk, o, 64);
-            if (ok >= 0 && (bk < 0 || mba_pair_less(od, ok, bd, bk))) bd = od, bk = ok;
-        }
-        if (lane == 0) s_d[wid] = bd, s_k[wid] = bk;
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 16; w++)
-                if (s_k[w] >= 0 && (bk < 0 || mba_pair_less(s_d[w], s_k[w], bd, bk))) bd = s_d[w], bk = s_k[w];
-            chosen[r] = bk;
-        }
+        mba_block_least(bd, bk, s_d, s_k);
+        if (tid == 0) chosen[r] = bk;
         __syncthreads();
     }
     if (tid == 0) {

@@ -20,13 +20,10 @@
 #include "track_internal.h"
 #include "patch_device.h"
 #include "mapmaker_device.h"
+#include "mapmaker_internal.h"   // EpiBusy, EpiRun, the chain's launch sequence
 
 namespace {
 
-struct EpiBusy {        // a busy measurement of kSrc: nLevel, v2RootPos
-    double x, y;
-    int level, pad_;
-};
 struct EpiCand {        // a kept candidate: index before thinning, irLevelPos
     int cand, x, y, pad_;
 };
@@ -344,50 +341,17 @@ int ptam_add_map_points_epipolar(ptam_ctx* ctx, const ptam_kf* src, const double
     ARG_TRY(n_busy == 0 || (busy_level && busy_root_xy));
     ARG_TRY(out || cap == 0);
     ARG_TRY(src->device == ctx->device && target->device == ctx->device);
-    const int nl = opts->n_levels;
-    ARG_TRY(nl >= 1 && nl <= PTAM_LEVELS);
-    for (int i = 0; i < nl; i++) {
-        ARG_TRY(opts->levels[i] >= 0 && opts->levels[i] < PTAM_LEVELS);
-        for (int j = 0; j < i; j++) ARG_TRY(opts->levels[i] != opts->levels[j]);
-    }
     for (int i = 0; i < n_busy; i++) ARG_TRY(busy_level[i] >= 0 && busy_level[i] < PTAM_LEVELS);
-    if (!src->rest_made) {
-        ptam_set_error("add_map_points_epipolar: the source keyframe has no MakeKeyFrame_Rest since its MakeKeyFrame_Lite");
-        return PTAM_E_STATE;
-    }
+    if (int rc = epi_check(src, opts)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    int n_max[PTAM_LEVELS], sum = 0, most = 0;
-    for (int i = 0; i < nl; i++) {
-        int rc = ptam_kf_rest_info(ctx, src, opts->levels[i], &n_max[i]);
-        if (rc) return rc;
-        sum += n_max[i];
-        most = max(most, n_max[i]);
-    }
+    EpiRun run;
+    if (int rc = epi_sizes(ctx, src, opts, run)) return rc;
+    const int sum = run.sum, nl = run.nl;
     ARG_TRY(cap >= sum);
-    for (int i = 0; i < nl; i++) {
-        int rc = kf_build_implane(ctx, target, opts->levels[i]);   // (bImplaneCornersCached :609-614)
-        if (rc) return rc;
-    }
-    // device scratch: busy list (caller's + one per made point), kept list, per-candidate status and point, output, counters
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_busy = up(sizeof(EpiBusy) * (size_t)(n_busy + sum + 1)), b_kept = up(sizeof(EpiCand) * (size_t)(most + 1)),
-                 b_stat = up(sizeof(int) * (size_t)(most + 1)), b_pts = up(sizeof(ptam_new_map_point) * (size_t)(most + 1)),
-                 b_out = up(sizeof(ptam_new_map_point) * (size_t)(sum + 1)), b_hdr = up(16 + sizeof(ptam_epipolar_level_stats) * PTAM_LEVELS);
-    void* s;
-    int rc = ctx_scratch(ctx, b_busy + b_kept + b_stat + b_pts + b_out + b_hdr, &s);
-    if (rc) return rc;
-    char* p = (char*)s;
-    EpiBusy* d_busy = (EpiBusy*)p;
-    EpiCand* d_kept = (EpiCand*)(p += b_busy);
-    int* d_status = (int*)(p += b_kept);
-    ptam_new_map_point* d_pts = (ptam_new_map_point*)(p += b_stat);
-    ptam_new_map_point* d_out = (ptam_new_map_point*)(p += b_pts);
-    int* d_hdr = (int*)(p += b_out);   // {n_busy, n_out, n_kept, pad} then the per-level stats
-    ptam_epipolar_level_stats* d_stats = (ptam_epipolar_level_stats*)(d_hdr + 4);
-    const size_t b_res = 16 + sizeof(ptam_epipolar_level_stats) * PTAM_LEVELS;
+    if (int rc = epi_carve(ctx, target, opts, n_busy, run)) return rc;
+    const size_t b_res = EPI_HDR_BYTES;
     void* hp;
-    rc = ctx_pinned(ctx, b_res + sizeof(ptam_new_map_point) * (size_t)sum, &hp);
-    if (rc) return rc;
+    if (int rc = ctx_pinned(ctx, b_res + sizeof(ptam_new_map_point) * (size_t)sum, &hp)) return rc;
     int* h_hdr = (int*)hp;
     ptam_new_map_point* h_out = (ptam_new_map_point*)((char*)hp + b_res);
     // the caller's busy measurements (pageable: staged before the call returns, which is after the final wait)
@@ -398,30 +362,12 @@ int ptam_add_map_points_epipolar(ptam_ctx* ctx, const ptam_kf* src, const double
         hb[(size_t)i].level = busy_level[i];
         hb[(size_t)i].pad_ = 0;
     }
-    if (n_busy > 0) HIP_TRY(hipMemcpyAsync(d_busy, hb.data(), sizeof(EpiBusy) * (size_t)n_busy, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(d_hdr, 0, b_res, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_hdr, &n_busy, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    EpiArgs a;
-    a.cam = ctx->cam;
-    for (int i = 0; i < 9; i++) a.Rs[i] = src_pose[i], a.Rt[i] = target_pose[i];
-    for (int i = 0; i < 3; i++) a.ts[i] = src_pose[9 + i], a.tt[i] = target_pose[9 + i];
-    a.depth_mean = opts->depth_mean;
-    a.depth_sigma = opts->depth_sigma;
-    a.wiggle = opts->wiggle_scale;
-    a.its = opts->subpix_max_its;
-    for (int i = 0; i < nl; i++) {
-        const int lev = opts->levels[i];
-        hipLaunchKernelGGL(epi_select_kernel, dim3(1), dim3(1024), 0, ctx->stream, src->L, lev, opts->min_shi_tomasi, (const EpiBusy*)d_busy,
-                           (const int*)d_hdr, d_kept, d_hdr + 2, d_stats + i);
-        if (n_max[i] > 0)
-            hipLaunchKernelGGL(epi_point_kernel, dim3((n_max[i] + 3) / 4), dim3(256), 0, ctx->stream, a, src->L, target->L, lev,
-                               (const double2*)target->implane[lev], (const EpiCand*)d_kept, (const int*)(d_hdr + 2), d_status, d_pts);
-        hipLaunchKernelGGL(epi_emit_kernel, dim3(1), dim3(1024), 0, ctx->stream, lev, (const int*)(d_hdr + 2), (const int*)d_status,
-                           (const ptam_new_map_point*)d_pts, d_out, d_hdr + 1, d_busy, d_hdr, d_stats + i);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(h_hdr, d_hdr, b_res, hipMemcpyDeviceToHost, ctx->stream));
-    if (sum > 0) HIP_TRY(hipMemcpyAsync(h_out, d_out, sizeof(ptam_new_map_point) * (size_t)sum, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_busy > 0) HIP_TRY(hipMemcpyAsync(run.d_busy, hb.data(), sizeof(EpiBusy) * (size_t)n_busy, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(run.d_hdr, 0, b_res, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(run.d_hdr, &n_busy, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = epi_launch_chain(ctx, src, src_pose, target, target_pose, opts, run)) return rc;
+    HIP_TRY(hipMemcpyAsync(h_hdr, run.d_hdr, b_res, hipMemcpyDeviceToHost, ctx->stream));
+    if (sum > 0) HIP_TRY(hipMemcpyAsync(h_out, run.d_out, sizeof(ptam_new_map_point) * (size_t)sum, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ptam_stream_wait(ctx->stream));
     const int made = h_hdr[1];
     if (made > sum) {
@@ -435,6 +381,85 @@ int ptam_add_map_points_epipolar(ptam_ctx* ctx, const ptam_kf* src, const double
 }
 
 }   // extern "C"
+
+int epi_check(const ptam_kf* src, const ptam_epipolar_opts* opts) {
+    ARG_TRY(src && opts);
+    const int nl = opts->n_levels;
+    ARG_TRY(nl >= 1 && nl <= PTAM_LEVELS);
+    for (int i = 0; i < nl; i++) {
+        ARG_TRY(opts->levels[i] >= 0 && opts->levels[i] < PTAM_LEVELS);
+        for (int j = 0; j < i; j++) ARG_TRY(opts->levels[i] != opts->levels[j]);
+    }
+    if (!src->rest_made) {
+        ptam_set_error("add_map_points_epipolar: the source keyframe has no MakeKeyFrame_Rest since its MakeKeyFrame_Lite");
+        return PTAM_E_STATE;
+    }
+    return PTAM_OK;
+}
+
+int epi_sizes(ptam_ctx* ctx, const ptam_kf* src, const ptam_epipolar_opts* opts, EpiRun& run) {
+    run.nl = opts->n_levels;
+    run.sum = run.most = 0;
+    for (int i = 0; i < run.nl; i++) {
+        int rc = ptam_kf_rest_info(ctx, src, opts->levels[i], &run.n_max[i]);
+        if (rc) return rc;
+        run.sum += run.n_max[i];
+        run.most = max(run.most, run.n_max[i]);
+    }
+    return PTAM_OK;
+}
+
+int epi_carve(ptam_ctx* ctx, ptam_kf* target, const ptam_epipolar_opts* opts, int n_busy, EpiRun& run) {
+    for (int i = 0; i < run.nl; i++) {
+        int rc = kf_build_implane(ctx, target, opts->levels[i]);   // (bImplaneCornersCached :609-614)
+        if (rc) return rc;
+    }
+    // device scratch: busy list (caller's + one per made point), kept list, per-candidate status and point, output, counters
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const int sum = run.sum, most = run.most;
+    const size_t b_busy = up(sizeof(EpiBusy) * (size_t)(n_busy + sum + 1)), b_kept = up(sizeof(EpiCand) * (size_t)(most + 1)),
+                 b_stat = up(sizeof(int) * (size_t)(most + 1)), b_pts = up(sizeof(ptam_new_map_point) * (size_t)(most + 1)),
+                 b_out = up(sizeof(ptam_new_map_point) * (size_t)(sum + 1)), b_hdr = up(EPI_HDR_BYTES);
+    void* s;
+    int rc = ctx_scratch(ctx, b_busy + b_kept + b_stat + b_pts + b_out + b_hdr, &s);
+    if (rc) return rc;
+    char* p = (char*)s;
+    run.d_busy = (EpiBusy*)p;
+    run.d_kept = (void*)(p += b_busy);
+    run.d_status = (int*)(p += b_kept);
+    run.d_pts = (ptam_new_map_point*)(p += b_stat);
+    run.d_out = (ptam_new_map_point*)(p += b_pts);
+    run.d_hdr = (int*)(p += b_out);   // {n_busy, n_out, n_kept, pad} then the per-level stats
+    return PTAM_OK;
+}
+
+int epi_launch_chain(ptam_ctx* ctx, const ptam_kf* src, const double src_pose[12], const ptam_kf* target, const double target_pose[12],
+                     const ptam_epipolar_opts* opts, const EpiRun& run) {
+    EpiBusy* d_busy = run.d_busy;
+    EpiCand* d_kept = (EpiCand*)run.d_kept;
+    int* d_hdr = run.d_hdr;
+    ptam_epipolar_level_stats* d_stats = (ptam_epipolar_level_stats*)(d_hdr + 4);
+    EpiArgs a;
+    a.cam = ctx->cam;
+    for (int i = 0; i < 9; i++) a.Rs[i] = src_pose[i], a.Rt[i] = target_pose[i];
+    for (int i = 0; i < 3; i++) a.ts[i] = src_pose[9 + i], a.tt[i] = target_pose[9 + i];
+    a.depth_mean = opts->depth_mean;
+    a.depth_sigma = opts->depth_sigma;
+    a.wiggle = opts->wiggle_scale;
+    a.its = opts->subpix_max_its;
+    for (int i = 0; i < run.nl; i++) {
+        const int lev = opts->levels[i];
+        hipLaunchKernelGGL(epi_select_kernel, dim3(1), dim3(1024), 0, ctx->stream, src->L, lev, opts->min_shi_tomasi, (const EpiBusy*)d_busy,
+                           (const int*)d_hdr, d_kept, d_hdr + 2, d_stats + i);
+        if (run.n_max[i] > 0)
+            hipLaunchKernelGGL(epi_point_kernel, dim3((run.n_max[i] + 3) / 4), dim3(256), 0, ctx->stream, a, src->L, target->L, lev,
+                               (const double2*)target->implane[lev], (const EpiCand*)d_kept, (const int*)(d_hdr + 2), run.d_status, run.d_pts);
+        hipLaunchKernelGGL(epi_emit_kernel, dim3(1), dim3(1024), 0, ctx->stream, lev, (const int*)(d_hdr + 2), (const int*)run.d_status,
+                           (const ptam_new_map_point*)run.d_pts, run.d_out, d_hdr + 1, d_busy, d_hdr, d_stats + i);
+        HIP_TRY(hipGetLastError());
+    }
+    return PTAM_OK;
+}
 
 void mapmaker_preload_kernels() {
     ptam_preload((const void*)epi_select_kernel);

@@ -10,6 +10,10 @@
 //   ptam_rmap_bundle_adjust         mba_run (mapba.hip) on the handle's buffers: adjusted in place, the poses into the mirror
 //   ptam_rmap_refind                mr_run (maprefind.hip): the merged tables into the second buffers, the resident queue popped
 //   ptam_rmap_apply_global_transform  map_apply_kernel (mapalign.hip): the pixel vectors straight into the point rows
+//   ptam_rmap_closest_keyframes     ClosestKeyFrame / NClosestKeyFrames (:711-752): rm_closest_kernel on the resident pose table
+//   ptam_rmap_insert_keyframe       AddKeyFrameFromTopOfQueue (:493-518) after MakeKeyFrame_Rest as one call: the keyframe's rows, its
+//                                   re-find (mr_run), the closest keyframe, the busy list from the resident measurement table
+//                                   (rm_busy_kernel), the epipolar chain of mapmaker.hip, and mt_add_points_core on the chain's output
 // Every table has two buffers of one capacity.  A kernel that rebuilds a table reads buf[cur] and writes buf[cur ^ 1]; the host
 // flips cur after the call's wait has read the refusal word.  Rows appended behind a table's count change nothing until the count
 // moves, which it does after the same wait.
@@ -20,6 +24,9 @@
 #include <algorithm>
 
 #include "maptables_internal.h"
+#include "kf_dist_device.h"       // mba_centre, mba_linear_dist, mba_pair_less, mba_block_least
+#include "mapmaker_internal.h"    // EpiBusy, EpiRun, the epipolar chain
+#include "refind_internal.h"      // ptam_refinder
 
 namespace {
 
@@ -176,6 +183,57 @@ __global__ void __launch_bounds__(256) rm_note_tracked_kernel(int n, const int32
     atomicAdd((outlier[i] ? outlier_count : inlier_count) + points[i], 1);
 }
 
+// ClosestKeyFrame / NClosestKeyFrames (:711-752), ONE WORKGROUP: the n_pick keyframes other than `self` that come first by
+// (KeyFrameLinearDist(self, k), k) — a strictly lower distance wins, equal distances go to the lower index (the `<` of :745,
+// partial_sort on the pairs of :716-722).  The order is total, so pass r takes the least pair above pass r - 1's: no list of the
+// taken ones.  only >= 0: keyframe `only` is the one candidate (its distance is what is asked for).
+// out: {count, pad}, n_pick distances, n_pick indices
+__global__ void __launch_bounds__(1024) rm_closest_kernel(int K, const double* __restrict__ pose, int self, int only, int n_pick, int* __restrict__ hdr,
+                                                          double* __restrict__ out_d, int32_t* __restrict__ out_k) {
+    __shared__ double s_d[16], s_pd;
+    __shared__ int s_k[16], s_pk;
+    const int tid = threadIdx.x;
+    double c0[3];
+    mba_centre(pose + (size_t)12 * self, c0);
+    double pd = 0.0;
+    int pk = -1, r = 0;
+    for (; r < n_pick; r++) {
+        double bd = 0.0;
+        int bk = -1;
+        for (int k = tid; k < K; k += 1024) {
+            if (k == self || (only >= 0 && k != only)) continue;
+            const double d = mba_linear_dist(c0, pose + (size_t)12 * k);
+            if (pk >= 0 && !mba_pair_less(pd, pk, d, k)) continue;   // taken by an earlier pass
+            if (bk < 0 || mba_pair_less(d, k, bd, bk)) bd = d, bk = k;
+        }
+        mba_block_least(bd, bk, s_d, s_k);
+        if (tid == 0) {
+            s_pd = bd, s_pk = bk;
+            if (bk >= 0) out_d[r] = bd, out_k[r] = bk;
+        }
+        __syncthreads();
+        pd = s_pd, pk = s_pk;
+        __syncthreads();   // (s_pd / s_pk are rewritten by the next pass)
+        if (pk < 0) break;   // (uniform: nothing left, which only distances that are not numbers bring about)
+    }
+    if (tid == 0) hdr[0] = r, hdr[1] = 0;
+}
+
+// kSrc.mMeasurements as ThinCandidates sees them (:415-441), one thread per row of the new keyframe's run in the resident
+// measurement table: the busy list of the epipolar chain (mapmaker.hip) and its count
+__global__ void __launch_bounds__(256) rm_busy_kernel(int n, const ptam_map_meas* __restrict__ run, EpiBusy* __restrict__ busy, int* __restrict__ hdr) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) hdr[0] = n;
+    if (i >= n) return;
+    const ptam_map_meas m = run[i];
+    EpiBusy b;
+    b.x = m.root_pos[0];
+    b.y = m.root_pos[1];
+    b.level = m.level;
+    b.pad_ = 0;
+    busy[i] = b;
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 inline size_t rm_up256(size_t b) { return (b + 255) & ~(size_t)255; }
 struct RmCarve {   // offsets into the context's scratch
@@ -263,6 +321,97 @@ template <class T>
 T* rm_now(ptam_rmap* m, int w) { return (T*)m->t[w].now(); }
 template <class T>
 T* rm_alt(ptam_rmap* m, int w) { return (T*)m->t[w].alt(); }
+
+// a new keyframe's measurement list, checked where it is: sorted by point, none repeated, in range
+int rm_check_kf_rows(int n_points, int n_rows, const ptam_map_kf_row* rows) {
+    for (int i = 0; i < n_rows; i++) {
+        ARG_TRY(rows[i].point >= 0 && rows[i].point < n_points && rows[i].level >= 0 && rows[i].level < PTAM_LEVELS);
+        ARG_TRY(i == 0 || rows[i - 1].point < rows[i].point);
+    }
+    return PTAM_OK;
+}
+// :501-506 enqueued: the pose and the flag behind the keyframe tables' counts, the rows behind the measurement table's
+int rm_add_keyframe_enqueue(ptam_rmap* m, const double pose12[12], const uint8_t* fx, int n_rows, const ptam_map_kf_row* rows) {
+    const int K = m->n[RM_N_KF], M = m->n[RM_N_MEAS];
+    if (int rc = rm_room(m, PTAM_RMAP_KF_POSES, (long long)K + 1)) return rc;
+    if (int rc = rm_room(m, PTAM_RMAP_KF_FIXED, (long long)K + 1)) return rc;
+    if (int rc = rm_room(m, PTAM_RMAP_MEAS, (long long)M + n_rows)) return rc;
+    void* sc;
+    if (int rc = ctx_scratch(m->ctx, rm_up256((size_t)n_rows * sizeof(ptam_map_kf_row)) + 256, &sc)) return rc;
+    if (int rc = rm_up(m, rm_now<double>(m, PTAM_RMAP_KF_POSES) + (size_t)12 * K, pose12, 96)) return rc;
+    if (int rc = rm_up(m, rm_now<uint8_t>(m, PTAM_RMAP_KF_FIXED) + K, fx, 1)) return rc;
+    if (n_rows > 0) {
+        if (int rc = rm_up(m, sc, rows, (size_t)n_rows * sizeof(ptam_map_kf_row))) return rc;
+        hipLaunchKernelGGL(rm_add_keyframe_kernel, dim3(rm_blocks(n_rows)), dim3(256), 0, m->ctx->stream, n_rows, (const ptam_map_kf_row*)sc, K,
+                           rm_now<ptam_map_meas>(m, PTAM_RMAP_MEAS) + M);
+        HIP_TRY(hipGetLastError());
+    }
+    return PTAM_OK;
+}
+// ... and the counts moved: the keyframe is the map's
+void rm_add_keyframe_commit(ptam_rmap* m, const ptam_kf* kf, const double pose12[12], uint8_t fx, int n_rows) {
+    m->kfs.push_back(kf);
+    m->h_poses.insert(m->h_poses.end(), pose12, pose12 + 12);
+    m->h_fixed.push_back(fx);
+    m->n[RM_N_KF] += 1;
+    m->n[RM_N_MEAS] += n_rows;
+}
+
+// rm_closest_kernel on the first K rows of the pose table and its result down: 8 + 12 n_pick bytes, one wait.  -> the pinned words
+// {count, pad}, n_pick distances, n_pick indices
+int rm_closest(ptam_rmap* m, int K, int self, int only, int n_pick, const int** hdr, const double** dist, const int32_t** idx) {
+    const size_t bytes = 8 + (size_t)12 * n_pick;
+    void *sc, *hp;
+    if (int rc = ctx_scratch(m->ctx, bytes, &sc)) return rc;
+    if (int rc = ctx_pinned(m->ctx, bytes, &hp)) return rc;
+    char* b = (char*)sc;
+    hipLaunchKernelGGL(rm_closest_kernel, dim3(1), dim3(1024), 0, m->ctx->stream, K, (const double*)rm_now<double>(m, PTAM_RMAP_KF_POSES), self, only,
+                       n_pick, (int*)b, (double*)(b + 8), (int32_t*)(b + 8 + (size_t)8 * n_pick));
+    HIP_TRY(hipGetLastError());
+    if (int rc = rm_down(m, hp, sc, bytes)) return rc;
+    HIP_TRY(ptam_stream_wait(m->ctx->stream));
+    *hdr = (const int*)hp;
+    *dist = (const double*)((const char*)hp + 8);
+    *idx = (const int32_t*)((const char*)hp + 8 + (size_t)8 * n_pick);
+    return PTAM_OK;
+}
+
+
+// mt_add_points_core on the handle's buffers; d_made: the records in device memory.  One wait, then the counts move.
+int rm_add_points_device(ptam_rmap* m, int src_kf, int target_kf, int target_source, int n_made, const ptam_new_map_point* d_made) {
+    const int N = m->n[RM_N_POINTS], M = m->n[RM_N_MEAS], Q = m->n[RM_N_NEW];
+    if (int rc = rm_room(m, PTAM_RMAP_MEAS, (long long)M + 2ll * n_made)) return rc;
+    if (int rc = rm_room_points(m, (long long)N + n_made)) return rc;
+    if (int rc = rm_room(m, PTAM_RMAP_NEW_QUEUE, (long long)Q + n_made)) return rc;
+    MtAdd p = {};
+    p.n_meas = M;
+    p.n_made = n_made;
+    p.n_points = N;
+    p.a = p.b = -1;   // found in the resident table by the kernel
+    p.kf_lo = std::min(src_kf, target_kf);
+    p.kf_hi = std::max(src_kf, target_kf);
+    p.src_is_lo = src_kf < target_kf;
+    p.src_kf = src_kf;
+    p.target_source = target_source;
+    p.meas = rm_now<ptam_map_meas>(m, PTAM_RMAP_MEAS);
+    p.made = d_made;
+    p.out = rm_alt<ptam_map_meas>(m, PTAM_RMAP_MEAS);
+    // the point side: behind the counts
+    p.points = rm_now<ptam_map_refind_point>(m, PTAM_RMAP_REFIND_POINTS) + N;
+    p.sources = rm_now<ptam_map_point_source>(m, PTAM_RMAP_SOURCES) + N;
+    p.points3 = rm_now<double>(m, PTAM_RMAP_POINTS3) + (size_t)3 * N;
+    p.bad = rm_now<uint8_t>(m, PTAM_RMAP_BAD) + N;
+    p.outlier_count = rm_now<int32_t>(m, PTAM_RMAP_OUTLIER_COUNT) + N;
+    p.inlier_count = rm_now<int32_t>(m, PTAM_RMAP_INLIER_COUNT) + N;
+    p.new_queue = rm_now<int32_t>(m, PTAM_RMAP_NEW_QUEUE) + Q;
+    if (int rc = mt_add_points_core(m->ctx->stream, p)) return rc;
+    HIP_TRY(ptam_stream_wait(m->ctx->stream));
+    m->t[PTAM_RMAP_MEAS].cur ^= 1;
+    m->n[RM_N_MEAS] = M + 2 * n_made;
+    m->n[RM_N_POINTS] = N + n_made;
+    m->n[RM_N_NEW] = Q + n_made;
+    return PTAM_OK;
+}
 
 }   // namespace
 
@@ -725,71 +874,26 @@ int ptam_rmap_add_points(ptam_rmap* m, int src_kf, int target_kf, int target_sou
     for (int i = 0; i < n_made; i++) ARG_TRY(made[i].level >= 0 && made[i].level < PTAM_LEVELS);
     if (n_made == 0) return PTAM_OK;
     HIP_TRY(hipSetDevice(m->ctx->device));
+    // (the tables' room first: growing one waits for the stream, and the records are read from the scratch after it)
     if (int rc = rm_room(m, PTAM_RMAP_MEAS, (long long)M + 2ll * n_made)) return rc;
     if (int rc = rm_room_points(m, (long long)N + n_made)) return rc;
     if (int rc = rm_room(m, PTAM_RMAP_NEW_QUEUE, (long long)Q + n_made)) return rc;
     void* sc;
     if (int rc = ctx_scratch(m->ctx, rm_up256((size_t)n_made * sizeof(ptam_new_map_point)), &sc)) return rc;
     if (int rc = rm_up(m, sc, made, (size_t)n_made * sizeof(ptam_new_map_point))) return rc;
-    MtAdd p = {};
-    p.n_meas = M;
-    p.n_made = n_made;
-    p.n_points = N;
-    p.a = p.b = -1;   // found in the resident table by the kernel
-    p.kf_lo = std::min(src_kf, target_kf);
-    p.kf_hi = std::max(src_kf, target_kf);
-    p.src_is_lo = src_kf < target_kf;
-    p.src_kf = src_kf;
-    p.target_source = target_source;
-    p.meas = rm_now<ptam_map_meas>(m, PTAM_RMAP_MEAS);
-    p.made = (const ptam_new_map_point*)sc;
-    p.out = rm_alt<ptam_map_meas>(m, PTAM_RMAP_MEAS);
-    // the point side: behind the counts
-    p.points = rm_now<ptam_map_refind_point>(m, PTAM_RMAP_REFIND_POINTS) + N;
-    p.sources = rm_now<ptam_map_point_source>(m, PTAM_RMAP_SOURCES) + N;
-    p.points3 = rm_now<double>(m, PTAM_RMAP_POINTS3) + (size_t)3 * N;
-    p.bad = rm_now<uint8_t>(m, PTAM_RMAP_BAD) + N;
-    p.outlier_count = rm_now<int32_t>(m, PTAM_RMAP_OUTLIER_COUNT) + N;
-    p.inlier_count = rm_now<int32_t>(m, PTAM_RMAP_INLIER_COUNT) + N;
-    p.new_queue = rm_now<int32_t>(m, PTAM_RMAP_NEW_QUEUE) + Q;
-    if (int rc = mt_add_points_core(m->ctx->stream, p)) return rc;
-    HIP_TRY(ptam_stream_wait(m->ctx->stream));
-    m->t[PTAM_RMAP_MEAS].cur ^= 1;
-    m->n[RM_N_MEAS] = M + 2 * n_made;
-    m->n[RM_N_POINTS] = N + n_made;
-    m->n[RM_N_NEW] = Q + n_made;
-    return PTAM_OK;
+    return rm_add_points_device(m, src_kf, target_kf, target_source, n_made, (const ptam_new_map_point*)sc);
 }
 
 int ptam_rmap_add_keyframe(ptam_rmap* m, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows, const ptam_map_kf_row* rows) {
     ARG_TRY(m && pose12 && n_rows >= 0 && (n_rows == 0 || rows));
     const int K = m->n[RM_N_KF], N = m->n[RM_N_POINTS], M = m->n[RM_N_MEAS];
     ARG_TRY((long long)K + 1 < (1ll << 31) && (long long)M + n_rows < (1ll << 31));
-    for (int i = 0; i < n_rows; i++) {   // the small list is checked where it is
-        ARG_TRY(rows[i].point >= 0 && rows[i].point < N && rows[i].level >= 0 && rows[i].level < PTAM_LEVELS);
-        ARG_TRY(i == 0 || rows[i - 1].point < rows[i].point);
-    }
+    if (int rc = rm_check_kf_rows(N, n_rows, rows)) return rc;   // the small list is checked where it is
     HIP_TRY(hipSetDevice(m->ctx->device));
-    if (int rc = rm_room(m, PTAM_RMAP_KF_POSES, (long long)K + 1)) return rc;
-    if (int rc = rm_room(m, PTAM_RMAP_KF_FIXED, (long long)K + 1)) return rc;
-    if (int rc = rm_room(m, PTAM_RMAP_MEAS, (long long)M + n_rows)) return rc;
-    void* sc;
-    if (int rc = ctx_scratch(m->ctx, rm_up256((size_t)n_rows * sizeof(ptam_map_kf_row)) + 256, &sc)) return rc;
     const uint8_t fx = fixed ? 1 : 0;
-    if (int rc = rm_up(m, rm_now<double>(m, PTAM_RMAP_KF_POSES) + (size_t)12 * K, pose12, 96)) return rc;
-    if (int rc = rm_up(m, rm_now<uint8_t>(m, PTAM_RMAP_KF_FIXED) + K, &fx, 1)) return rc;
-    if (n_rows > 0) {
-        if (int rc = rm_up(m, sc, rows, (size_t)n_rows * sizeof(ptam_map_kf_row))) return rc;
-        hipLaunchKernelGGL(rm_add_keyframe_kernel, dim3(rm_blocks(n_rows)), dim3(256), 0, m->ctx->stream, n_rows, (const ptam_map_kf_row*)sc, K,
-                           rm_now<ptam_map_meas>(m, PTAM_RMAP_MEAS) + M);
-        HIP_TRY(hipGetLastError());
-    }
+    if (int rc = rm_add_keyframe_enqueue(m, pose12, &fx, n_rows, rows)) return rc;
     HIP_TRY(ptam_stream_wait(m->ctx->stream));
-    m->kfs.push_back(kf);
-    m->h_poses.insert(m->h_poses.end(), pose12, pose12 + 12);
-    m->h_fixed.push_back(fx);
-    m->n[RM_N_KF] = K + 1;
-    m->n[RM_N_MEAS] = M + n_rows;
+    rm_add_keyframe_commit(m, kf, pose12, fx, n_rows);
     return PTAM_OK;
 }
 
@@ -825,9 +929,117 @@ int ptam_rmap_scene_depth(ptam_rmap* m, ptam_scene_depth* out) {
     return PTAM_OK;
 }
 
+int ptam_rmap_closest_keyframes(ptam_rmap* m, int kf, int n, int32_t* out_kf, double* out_dist, int32_t* n_out) {
+    ARG_TRY(m && out_kf && out_dist && n_out);
+    const int K = m->n[RM_N_KF];
+    ARG_TRY(kf >= 0 && kf < K && n >= 1);
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    const int n_pick = std::min(n, K - 1);
+    const int* hdr;
+    const double* dist;
+    const int32_t* idx;
+    if (int rc = rm_closest(m, K, kf, -1, n_pick, &hdr, &dist, &idx)) return rc;
+    const int got = std::min(std::max(hdr[0], 0), n_pick);
+    std::copy(idx, idx + got, out_kf);
+    std::copy(dist, dist + got, out_dist);
+    *n_out = got;
+    return PTAM_OK;
+}
+
+int ptam_rmap_insert_keyframe(ptam_rmap* m, ptam_refinder* finder, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows,
+                              const ptam_map_kf_row* rows, const ptam_rmap_insert_opts* opts, ptam_rmap_insert_result* res) {
+    // ---- refusals: nothing is enqueued before all of them have passed
+    ARG_TRY(m && finder && kf && pose12 && opts && res && n_rows >= 0 && (n_rows == 0 || rows));
+    ptam_ctx* ctx = m->ctx;
+    const int K = m->n[RM_N_KF], N = m->n[RM_N_POINTS], M = m->n[RM_N_MEAS], V = m->n[RM_N_NEVER];
+    const bool refind = !opts->skip_refind, points = !opts->skip_points;
+    ARG_TRY(finder->ctx->device == ctx->device && opts->refind.max_pairs_per_pass >= 0);
+    ARG_TRY((long long)K + 1 < (1ll << 31) && (long long)M + n_rows + N < (1ll << 31) && (long long)V + N < (1ll << 31));
+    if (int rc = rm_check_kf_rows(N, n_rows, rows)) return rc;
+    ARG_TRY(opts->target_kf >= -1 && opts->target_kf < K);
+    auto usable = [&](const ptam_kf* k) { return k && k->device == ctx->device && k->L.w[0] == ctx->params.width && k->L.h[0] == ctx->params.height; };
+    ARG_TRY(usable(kf));
+    if (refind || points)
+        for (int k = 0; k < K; k++) ARG_TRY(usable(m->kfs[(size_t)k]));   // the re-find visits every source keyframe; any may be the target
+    if (points) {
+        if (int rc = epi_check(kf, &opts->epipolar)) return rc;
+        if (K == 0) {
+            ptam_set_error("ptam_rmap_insert_keyframe: the map has no keyframe to be the closest one");
+            return PTAM_E_STATE;
+        }
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    EpiRun run = {};
+    if (points) {   // (the corner counts of the new keyframe's levels, read from its handle: every made point is one of them)
+        if (int rc = epi_sizes(ctx, kf, &opts->epipolar, run)) return rc;
+        ARG_TRY((long long)N + run.sum < (1ll << 31) && (long long)M + n_rows + N + 2ll * run.sum < (1ll << 31) &&
+                (long long)m->n[RM_N_NEW] + run.sum < (1ll << 31));
+    }
+    hipStream_t st = ctx->stream;
+    ptam_rmap_insert_result r = {};
+    r.kf = K;
+    r.target_kf = -1;
+    r.first_point = N;
+    // ---- (a) the keyframe's rows; the counts move at once: nothing below can refuse the call
+    const uint8_t fx = fixed ? 1 : 0;
+    if (int rc = rm_add_keyframe_enqueue(m, pose12, &fx, n_rows, rows)) return rc;
+    rm_add_keyframe_commit(m, kf, pose12, fx, n_rows);
+    // ---- (c) the target: it needs the poses alone, and its wait is (a)'s
+    if (points) {
+        const int* hdr;
+        const double* dist;
+        const int32_t* idx;
+        if (int rc = rm_closest(m, K + 1, K, opts->target_kf, 1, &hdr, &dist, &idx)) return rc;
+        if (hdr[0] != 1 || idx[0] < 0 || idx[0] >= K) {
+            ptam_set_error("ptam_rmap_insert_keyframe: no closest keyframe among %d", K);
+            return PTAM_E_STATE;
+        }
+        r.target_kf = idx[0];
+        r.target_dist = dist[0];
+    }
+    // ---- (b) the re-find of the new keyframe; the merged tables become the map's
+    if (refind) {
+        const int32_t work = K;
+        if (int rc = ptam_rmap_refind(m, finder, &opts->refind, PTAM_MAP_REFIND_KEYFRAME, 1, &work, nullptr, &r.refind, nullptr, nullptr, nullptr, 0)) return rc;
+    }
+    if (!points) {
+        HIP_TRY(ptam_stream_wait(st));
+        *res = r;
+        return PTAM_OK;
+    }
+    // ---- (d) the busy list: the new keyframe's run is the tail of the table as (b) left it
+    const int n_busy = m->n[RM_N_MEAS] - M;
+    ptam_kf* target = const_cast<ptam_kf*>(m->kfs[(size_t)r.target_kf]);   // (its implane tables are cached on the handle)
+    if (int rc = epi_carve(ctx, target, &opts->epipolar, n_busy, run)) return rc;
+    HIP_TRY(hipMemsetAsync(run.d_hdr, 0, EPI_HDR_BYTES, st));
+    hipLaunchKernelGGL(rm_busy_kernel, dim3(std::max(rm_blocks(n_busy), 1u)), dim3(256), 0, st, n_busy,
+                       (const ptam_map_meas*)rm_now<ptam_map_meas>(m, PTAM_RMAP_MEAS) + M, run.d_busy, run.d_hdr);
+    HIP_TRY(hipGetLastError());
+    // ---- (e) the epipolar chain, (f) its count and stats
+    if (int rc = epi_launch_chain(ctx, kf, pose12, target, m->h_poses.data() + (size_t)12 * r.target_kf, &opts->epipolar, run)) return rc;
+    void* hp;
+    if (int rc = ctx_pinned(ctx, EPI_HDR_BYTES, &hp)) return rc;
+    if (int rc = rm_down(m, hp, run.d_hdr, EPI_HDR_BYTES)) return rc;
+    HIP_TRY(ptam_stream_wait(st));
+    const int made = ((const int*)hp)[1];
+    if (made < 0 || made > run.sum) {
+        ptam_set_error("ptam_rmap_insert_keyframe: %d points made, room for %d", made, run.sum);
+        return PTAM_E_STATE;
+    }
+    std::memcpy(r.levels, (const char*)hp + 16, sizeof(ptam_epipolar_level_stats) * (size_t)run.nl);
+    r.n_made = made;
+    // ---- (g) the made points into the tables, straight from the chain's output
+    if (made > 0)
+        if (int rc = rm_add_points_device(m, K, r.target_kf, PTAM_MAP_SRC_EPIPOLAR, made, run.d_out)) return rc;
+    *res = r;
+    return PTAM_OK;
+}
+
 }   // extern "C"
 
 void maprmap_preload_kernels() {
+    ptam_preload((const void*)rm_closest_kernel);
+    ptam_preload((const void*)rm_busy_kernel);
     ptam_preload((const void*)rm_check_sorted_kernel<ptam_map_meas, true>);
     ptam_preload((const void*)rm_check_sorted_kernel<ptam_map_pair, false>);
     ptam_preload((const void*)rm_check_pairs_kernel);

@@ -1050,6 +1050,45 @@ class ResidentMap:
         self.ctx._check(self.lib.rmap_scene_depth(self.h, _ptr(out)), "rmap_scene_depth")
         return out[:k]
 
+    def ClosestKeyFrames(self, kf, n=1, check=True):
+        """MapMaker::ClosestKeyFrame / NClosestKeyFrames on the resident poses -> (keyframe indices int32, distances float64), the
+        min(n, n_kf - 1) nearest other keyframes by (distance, index)"""
+        cap = max(min(int(n), self.counts()["n_kf"] - 1), 1)
+        idx, dist, got = np.zeros(cap, np.int32), np.zeros(cap, np.float64), C.c_int32()
+        rc = self.lib.rmap_closest_keyframes(self.h, int(kf), int(n), _ptr(idx), _pd(dist), C.byref(got))
+        if not check and rc < 0:
+            return rc
+        self.ctx._check(rc, "rmap_closest_keyframes")
+        return idx[:got.value].copy(), dist[:got.value].copy()
+
+    def insert_opts(self, target_kf=-1, skip_refind=False, skip_points=False, max_pairs_per_pass=0, **epipolar):
+        """ptam_rmap_insert_opts: the epipolar options as MapMaker.opts takes them, the target (-1: the closest keyframe)"""
+        o = _abi.RmapInsertOpts()
+        o.epipolar = MapMaker(self.ctx).opts(**epipolar)
+        o.refind = _abi.MapRefindOpts(int(max_pairs_per_pass), 0)
+        o.target_kf, o.skip_refind, o.skip_points = int(target_kf), int(bool(skip_refind)), int(bool(skip_points))
+        return o
+
+    def InsertKeyFrame(self, finder, kf, pose, fixed, rows, opts=None, check=True):
+        """MapMaker::AddKeyFrameFromTopOfQueue after MakeKeyFrame_Rest as one call (ptam_rmap_insert_keyframe): kf a KeyFrame, rows
+        MAP_KF_ROW_DT sorted by point, opts from insert_opts() -> dict(kf, target_kf, target_dist, refind (the re-find's counts),
+        first_point, n_made, levels EPIPOLAR_STATS_DT per visited level); the new points stay on the device
+        (download("points", first_point, n_made)).  check=False: -> the status of a refused call instead of raising."""
+        opts = opts if opts is not None else self.insert_opts()
+        rows = np.ascontiguousarray(rows, dtype=MAP_KF_ROW_DT)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        res = _abi.RmapInsertResult()
+        rc = self.lib.rmap_insert_keyframe(self.h, finder.h, kf.h if kf is not None else None, _pd(pose), int(bool(fixed)), len(rows), _ptr(rows),
+                                           C.byref(opts), C.byref(res))
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "rmap_insert_keyframe")
+        self._kfs.append(kf)
+        nl = min(max(opts.epipolar.n_levels, 0), _abi.LEVELS)
+        levels = np.frombuffer(bytes(res.levels), dtype=EPIPOLAR_STATS_DT)[:nl].copy()
+        return dict(kf=res.kf, target_kf=res.target_kf, target_dist=res.target_dist, refind=_counts(res.refind), first_point=res.first_point,
+                    n_made=res.n_made, levels=levels)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.rmap_destroy(self.h)
