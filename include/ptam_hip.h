@@ -611,7 +611,10 @@ int ptam_tracker_set_map(ptam_tracker* t, int n, const ptam_pvs_point* points, c
  * adjustment): like ptam_tracker_set_map, but a point that was in the previous map keeps its TrackerData — prev_index[i] is the
  * index new point i had in the map of the last set_map / update_map call, -1 for a new point.  Its PatchFinder's template, warp
  * matrix and mbTemplateBad carry over as they do in the reference, where TrackerData lives as long as its MapPoint
- * (include/Tracker.h:42-67, src/Tracker.cc:453-464); new points start with a fresh finder.  No old index may appear twice. */
+ * (include/Tracker.h:42-67, src/Tracker.cc:453-464); new points start with a fresh finder.  No old index may appear twice.
+ * Both calls clear the tracker's serial list (ptam_tracker_take_map, below): the points handed over here have no identity the
+ * resident map knows, and the next take treats every point as new.  With the map in a ptam_rmap on the same device,
+ * ptam_rmap_publish / ptam_tracker_take_map do this hand-over without the host tables and without a composed prev_index. */
 int ptam_tracker_update_map(ptam_tracker* t, int n, const ptam_pvs_point* points, const ptam_template_query* sources,
                             const int32_t* prev_index);
 /* The frame's random orders, each a permutation of 0..n-1 (asynchronous upload): level l's PVS list is taken in the order
@@ -1250,7 +1253,7 @@ int ptam_rmap_apply_global_transform(ptam_rmap*, const double se3_new_from_old[1
  * Moves n_outliers * 16 bytes up and PTAM_RMAP_WORD_BYTES down. */
 int ptam_rmap_apply_outliers(ptam_rmap*, int n_outliers, const ptam_map_outlier* outliers, ptam_map_outliers_result* res);
 /* ptam_map_handle_bad_points on the resident tables: the columns are the handle's six point-side tables (the surviving points'
- * bad bytes are zero by construction).  kept_out (nullable, room for n_points; the tracker's prevIndex) and new_index_out
+ * bad bytes are zero by construction) and the serial column.  kept_out (nullable, room for n_points; the tracker's prevIndex) and new_index_out
  * (nullable, n_points) come down only when asked for.  Moves PTAM_RMAP_WORD_BYTES down, and what was asked for. */
 int ptam_rmap_handle_bad_points(ptam_rmap*, ptam_map_bad_points_result* res, int32_t* kept_out, int32_t* new_index_out);
 /* ptam_map_add_points on the resident tables; made: host.  The two run ends are found by a binary search in the resident table
@@ -1313,6 +1316,92 @@ typedef struct {
  * candidates, the made points or the measurement table moves. */
 int ptam_rmap_insert_keyframe(ptam_rmap*, ptam_refinder*, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows,
                               const ptam_map_kf_row* rows, const ptam_rmap_insert_opts*, ptam_rmap_insert_result*);
+
+/* ---- The resident map published to the tracker on the device --------------------------------------------------------------------
+ *      Replaces the one table-sized trip left between the two threads: ptam_rmap_download of the point rows and `kept`, the host
+ *      loop that composes prev_index, ptam_tracker_update_map's upload.
+ *      POINT SERIALS.  A ptam_rmap keeps a seventh point-side column: one 64-bit serial per point, given by the library from the
+ *      handle's running counter (starting at 1) and never reused within the handle.  ptam_rmap_upload gives every point a fresh
+ *      one (a re-uploaded map is a new map to every tracker), ptam_rmap_add_points and ptam_rmap_insert_keyframe append the next
+ *      ones behind the count, ptam_rmap_handle_bad_points compacts the column with the others, growth copies it.  Points are only
+ *      appended at the end and removed by an order-preserving compaction, so the column is strictly increasing with the point index
+ *      without any sort.  It follows the two-buffer rules of its neighbours: a refused call leaves it as it was.  It is no table
+ *      of ptam_rmap_download and costs no existing call a byte over the host link.  Every handle also has a process-wide map_id,
+ *      given at ptam_rmap_create: (map_id, serial) names a point for as long as the handle lives.
+ *      SNAPSHOT.  A ptam_map_snapshot holds, in device memory, what the tracker needs of one state of the map: n, the map_id, a
+ *      generation number, the ptam_pvs_point rows, the patch sources resolved to level images, and the serials.  It has three
+ *      slots: the current generation, the one a publish is writing, one a take may still be copying.  The hand-over is host-side:
+ *      a publish completes on the mapmaker's queue (its one wait) before the generation becomes current under the snapshot's
+ *      mutex; a take picks the current slot under the same mutex and enqueues on the tracker's queue afterwards.  No kernel waits
+ *      for another queue and no flag is spun on in device memory; a take never sees a half-written generation, a publish never
+ *      overwrites one a take is copying, and neither thread waits for the other's device work (with more than one tracker taking
+ *      from one snapshot, a publish may wait for one take's copy).  One thread publishes into a snapshot; any number take.
+ *      The keyframes of the map must outlive every snapshot generation and tracker that names their images. */
+typedef struct ptam_map_snapshot ptam_map_snapshot;
+typedef struct {
+    int64_t generation;                 /* of this publish: 1, 2, ... per snapshot */
+    int64_t map_id;
+    int32_t n_points, n_kf;
+    int32_t grew, pad_;                 /* the slot was too small and was reallocated (the call's only allocation) */
+} ptam_map_publish_result;
+typedef struct {
+    int32_t changed;                    /* 0: the tracker holds this generation already; nothing else was done */
+    int32_t n_points;
+    int32_t n_carried, n_new, n_dropped;   /* points that kept their PatchFinder | new to the tracker | old points without successor */
+    int32_t link_bytes;                 /* what crossed the host link in this call */
+    int64_t generation, map_id;
+} ptam_map_take_result;
+typedef struct { int64_t generation, map_id; int32_t n_points, pad_; } ptam_map_snapshot_info_t;
+/* max_points: the capacity of all three slots.  The snapshot remembers the context's device and frame size, not the context. */
+int ptam_map_snapshot_create(ptam_ctx*, int max_points, ptam_map_snapshot** out);
+int ptam_map_snapshot_destroy(ptam_map_snapshot*);
+/* at least max_points in every slot that is neither current nor being copied (those grow when they are next written); the
+ * publisher's thread.  Never shrinks. */
+int ptam_map_snapshot_reserve(ptam_map_snapshot*, int max_points);
+/* the current generation (0: never published into), its map and point count; any thread */
+int ptam_map_snapshot_info(ptam_map_snapshot*, ptam_map_snapshot_info_t* out);
+
+/* The map as it stands into the snapshot's free slot; the mapmaker's thread, synchronous.  One gather kernel, one thread per point,
+ * reads refind_points[i].pv, src_kf, src_level, center_x / y and the serial, and resolves src_kf through a per-keyframe record of
+ * the four level image addresses and sizes, which goes up with the call (64 bytes a keyframe, well under
+ * PTAM_RMAP_KF_RECORD_BYTES, counted in ptam_rmap_traffic).  Every point of the table is published, bad ones included (the
+ * reference's tracker walks vpPoints until HandleBadPoints has trashed a point).  After the call's one wait the slot becomes the
+ * current generation.  A slot that is too small is reallocated at double its size: the call's only allocation, which
+ * ptam_map_snapshot_reserve avoids.
+ * PTAM_E_ARG, decided before anything is enqueued, the snapshot keeping its generation: a keyframe of the map without a handle (or
+ * with one of another device), a snapshot on another device than the map's.  PTAM_E_STATE: a publish into this snapshot is under way.
+ * Moves 64 n_kf bytes up and nothing down: nothing proportional to the points. */
+int ptam_rmap_publish(ptam_rmap*, ptam_map_snapshot*, ptam_map_publish_result* res);
+/* rows [first, first + count) of the serial column.  PTAM_E_ARG: a range outside the points.  Moves 8 count bytes down. */
+int ptam_rmap_point_serials(ptam_rmap*, int first, int count, int64_t* out);
+/* The current point index of each serial, by a binary-search kernel in the resident serial column, one thread per entry: -1 for
+ * a point that has been removed (or a value never given out); *n_gone (nullable) counts those.  No order rule on the input.
+ * Serial order is index order: a host that sorts a keyframe's found entries by serial has the rows of ptam_rmap_insert_keyframe
+ * sorted by point.  This is how the tracker's iteration set (ptam_tracker_read_iteration_serials) reaches ptam_rmap_note_tracked
+ * and ptam_rmap_insert_keyframe after ptam_rmap_handle_bad_points has renumbered the map.
+ * Moves 8 n bytes up, 4 n + PTAM_RMAP_WORD_BYTES down. */
+int ptam_rmap_resolve_serials(ptam_rmap*, int n, const int64_t* serials, int32_t* index_out, int32_t* n_gone);
+
+/* ptam_tracker_update_map from the snapshot's current generation, everything table-sized staying on the device; the tracker's
+ * thread, synchronous.  If the snapshot's generation is the one this tracker took last: changed = 0, no launch, no copy, one mutex
+ * hold — the per-frame poll.  Otherwise the point rows and the sources are copied device to device; a kernel computes prev[i],
+ * one thread per new point, by a binary search of the new serial in the tracker's serial list of its current map (-1 when it is
+ * not there, or when the map_id differs: both lists are strictly increasing, so no old index is hit twice); the finder-carry
+ * kernel of ptam_tracker_update_map runs on that prev; a kernel writes the identity shuffles when n changed; the tracker's
+ * serial list becomes the snapshot's.  The same input gives the same bits, and the tracker's next frame is the one
+ * ptam_tracker_update_map with the composed prev_index gives.
+ * PTAM_E_ARG, with the tracker's map untouched: n above the tracker's max_points, a snapshot on another device, a snapshot of
+ * another frame size than the tracker's context's, a snapshot never published into.
+ * Moves 8 bytes down (the carried count) and nothing up: at most 64 bytes cross the host link. */
+int ptam_tracker_take_map(ptam_tracker*, ptam_map_snapshot*, ptam_map_take_result* res);
+/* rows [first, first + count) of the tracker's serial list: the serials of its map's points after a take, empty after
+ * ptam_tracker_set_map / ptam_tracker_update_map (which clear it: the next take treats every point as new).
+ * PTAM_E_ARG: a range outside the list. */
+int ptam_tracker_point_serials(ptam_tracker*, int first, int count, int64_t* out);
+/* the serial of every entry of the iteration set, in the order of ptam_tracker_read_iteration_set (a gather kernel): what
+ * ptam_rmap_resolve_serials turns into the map's numbering of the moment.  out (nullable: *n alone), cap as there.
+ * PTAM_E_STATE: the tracker's map did not come from a snapshot. */
+int ptam_tracker_read_iteration_serials(ptam_tracker*, int64_t* out, int cap, int* n);
 
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,

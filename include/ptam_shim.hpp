@@ -725,6 +725,28 @@ private:
     ptam_rotation_estimator* h_ = nullptr;
 };
 
+// The map as the tracker wants it, in device memory (ptam_map_snapshot, ptam_hip.h): ResidentMap::Publish fills it on the mapmaker's
+// thread, MapTracker::TakeMap copies from it on the tracker's.  Three slots and a mutex on the host: neither thread waits for the
+// other's device work, and nothing table-sized crosses the host link.  Create it before the threads start; it must outlive both.
+class MapSnapshot {
+public:
+    MapSnapshot(Context& c, int nMaxPoints) { check(ptam_map_snapshot_create(c.handle(), nMaxPoints, &h_), "ptam_map_snapshot_create"); }
+    ~MapSnapshot() { ptam_map_snapshot_destroy(h_); }
+    MapSnapshot(const MapSnapshot&) = delete;
+    MapSnapshot& operator=(const MapSnapshot&) = delete;
+    void Reserve(int nMaxPoints) { check(ptam_map_snapshot_reserve(h_, nMaxPoints), "ptam_map_snapshot_reserve"); }
+    // the current generation (0: never published into), its map and its point count
+    ptam_map_snapshot_info_t Info() const {
+        ptam_map_snapshot_info_t r{};
+        check(ptam_map_snapshot_info(h_, &r), "ptam_map_snapshot_info");
+        return r;
+    }
+    ptam_map_snapshot* handle() const { return h_; }
+
+private:
+    ptam_map_snapshot* h_ = nullptr;
+};
+
 // Tracker::TrackMap (src/Tracker.cc:442-696) as one device-resident chain: the map (world positions, pixel vectors, patch
 // sources) lives on the device between frames; a frame is one call that returns the refined pose, mbDidCoarse, the
 // per-level manMeasAttempted / manMeasFound counters and the scene-depth sums.  The caller keeps what is host logic in the
@@ -746,6 +768,22 @@ public:
                    const std::vector<int32_t>& vPrevIndex) {
         if (vSources.size() != vMapPoints.size() || vPrevIndex.size() != vMapPoints.size()) throw std::runtime_error("UpdateMap: sizes differ");
         check(ptam_tracker_update_map(h_, (int)vMapPoints.size(), vMapPoints.data(), vSources.data(), vPrevIndex.data()), "ptam_tracker_update_map");
+    }
+    // The map after the mapmaker published it (ResidentMap::Publish), device to device: points the tracker knows by their serial
+    // keep their TrackerData, whatever was removed or appended in between and however many publishes the tracker skipped.
+    // changed == 0: the tracker holds this generation already and nothing was done — call it every frame.  When the point count
+    // changed the shuffles are the identity again: SetShuffle before the next frame.
+    ptam_map_take_result TakeMap(MapSnapshot& snapshot) {
+        ptam_map_take_result r{};
+        check(ptam_tracker_take_map(h_, snapshot.handle(), &r), "ptam_tracker_take_map");
+        return r;
+    }
+    // the serials of the map's points after TakeMap (none after SetMap / UpdateMap); nCount < 0: nTotal points from nFirst on
+    std::vector<int64_t> PointSerials(int nTotal, int nFirst = 0, int nCount = -1) {
+        if (nCount < 0) nCount = nTotal - nFirst;
+        std::vector<int64_t> v((size_t)(nCount > 0 ? nCount : 0));
+        check(ptam_tracker_point_serials(h_, nFirst, nCount, v.data()), "ptam_tracker_point_serials");
+        return v;
     }
     void SetShuffle(const std::vector<int32_t>& vLevels, const std::vector<int32_t>& vFine) {
         check(ptam_tracker_set_shuffle(h_, vLevels.data(), vFine.data()), "ptam_tracker_set_shuffle");
@@ -810,6 +848,15 @@ public:
         check(ptam_tracker_read_iteration_set(h_, nullptr, 0, &n), "ptam_tracker_read_iteration_set");
         std::vector<ptam_trackmap_meas> v((size_t)n);
         if (n > 0) check(ptam_tracker_read_iteration_set(h_, v.data(), n, &n), "ptam_tracker_read_iteration_set");
+        return v;
+    }
+    // the serial of every entry of IterationSet(), in its order: ResidentMap::ResolveSerials turns them into the map's numbering
+    // of the moment, for NoteTracked and the rows of InsertKeyFrame (the map came from TakeMap)
+    std::vector<int64_t> IterationSerials() {
+        int n = 0;
+        check(ptam_tracker_read_iteration_serials(h_, nullptr, 0, &n), "ptam_tracker_read_iteration_serials");
+        std::vector<int64_t> v((size_t)n);
+        if (n > 0) check(ptam_tracker_read_iteration_serials(h_, v.data(), n, &n), "ptam_tracker_read_iteration_serials");
         return v;
     }
 
@@ -1155,6 +1202,26 @@ public:
                                         vRows.data(), &opts, &r),
               "ptam_rmap_insert_keyframe");
         return r;
+    }
+    // The map as it stands into the snapshot, as its next generation (the mapmaker's thread): after HandleBadPoints, InsertKeyFrame and
+    // every accepted bundle.  vKept no longer has to come down for the tracker.  The keyframes need handles (Upload / AddKeyFrame).
+    ptam_map_publish_result Publish(MapSnapshot& snapshot) {
+        ptam_map_publish_result r{};
+        check(ptam_rmap_publish(h_, snapshot.handle(), &r), "ptam_rmap_publish");
+        return r;
+    }
+    // the serial column: one int64 per point, strictly increasing with the index, never reused by this map
+    std::vector<int64_t> PointSerials(int nFirst = 0, int nCount = -1) const {
+        if (nCount < 0) nCount = Counts().n_points - nFirst;
+        std::vector<int64_t> v((size_t)(nCount > 0 ? nCount : 0));
+        check(ptam_rmap_point_serials(h_, nFirst, nCount, v.data()), "ptam_rmap_point_serials");
+        return v;
+    }
+    // serials (any order) -> the points' current indices, -1 for a removed point; pnGone: how many of those
+    std::vector<int32_t> ResolveSerials(const std::vector<int64_t>& vSerials, int32_t* pnGone = nullptr) {
+        std::vector<int32_t> v(vSerials.size());
+        check(ptam_rmap_resolve_serials(h_, (int)vSerials.size(), vSerials.data(), v.data(), pnGone), "ptam_rmap_resolve_serials");
+        return v;
     }
     ptam_rmap* handle() const { return h_; }
 

@@ -255,6 +255,23 @@ class RmapInsertResult(C.Structure):
                 ("first_point", C.c_int32), ("n_made", C.c_int32), ("levels", EpipolarLevelStats * 4)]
 
 
+class MapPublishResult(C.Structure):
+    """ptam_map_publish_result"""
+    _fields_ = [("generation", C.c_int64), ("map_id", C.c_int64), ("n_points", C.c_int32), ("n_kf", C.c_int32), ("grew", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class MapTakeResult(C.Structure):
+    """ptam_map_take_result"""
+    _fields_ = [("changed", C.c_int32), ("n_points", C.c_int32), ("n_carried", C.c_int32), ("n_new", C.c_int32), ("n_dropped", C.c_int32),
+                ("link_bytes", C.c_int32), ("generation", C.c_int64), ("map_id", C.c_int64)]
+
+
+class MapSnapshotInfo(C.Structure):
+    """ptam_map_snapshot_info_t"""
+    _fields_ = [("generation", C.c_int64), ("map_id", C.c_int64), ("n_points", C.c_int32), ("pad_", C.c_int32)]
+
+
 class SbiAlignment(C.Structure):
     """ptam_sbi_alignment (SmallBlurryImage::CalcSBIRotation, src/ImageProcess.cc:313-495)"""
     _fields_ = [("se2_rot", C.c_double * 4), ("se2_trans", C.c_double * 2), ("score", C.c_double), ("mean_offset", C.c_double),
@@ -434,6 +451,16 @@ PROTOTYPES = {
     "rmap_scene_depth": (_i, [_vp, _vp]),
     "rmap_closest_keyframes": (_i, [_vp, _i, _i, _vp, _pd, C.POINTER(C.c_int32)]),
     "rmap_insert_keyframe": (_i, [_vp, _vp, _vp, _pd, _i, _i, _vp, C.POINTER(RmapInsertOpts), C.POINTER(RmapInsertResult)]),
+    "rmap_publish": (_i, [_vp, _vp, C.POINTER(MapPublishResult)]),
+    "rmap_point_serials": (_i, [_vp, _i, _i, _vp]),
+    "rmap_resolve_serials": (_i, [_vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
+    "map_snapshot_create": (_i, [_vp, _i, _ppv]),
+    "map_snapshot_destroy": (_i, [_vp]),
+    "map_snapshot_reserve": (_i, [_vp, _i]),
+    "map_snapshot_info": (_i, [_vp, C.POINTER(MapSnapshotInfo)]),
+    "tracker_take_map": (_i, [_vp, _vp, C.POINTER(MapTakeResult)]),
+    "tracker_point_serials": (_i, [_vp, _i, _i, _vp]),
+    "tracker_read_iteration_serials": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

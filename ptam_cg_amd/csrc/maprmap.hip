@@ -14,6 +14,10 @@
 //   ptam_rmap_insert_keyframe       AddKeyFrameFromTopOfQueue (:493-518) after MakeKeyFrame_Rest as one call: the keyframe's rows, its
 //                                   re-find (mr_run), the closest keyframe, the busy list from the resident measurement table
 //                                   (rm_busy_kernel), the epipolar chain of mapmaker.hip, and mt_add_points_core on the chain's output
+//   ptam_rmap_publish               the map as the tracker wants it into a ptam_map_snapshot's free slot (rm_publish_kernel): rows, patch
+//                                   sources resolved through a per-keyframe level record, serials; the hand-over is snapshot_slots.h
+//   ptam_rmap_point_serials / resolve_serials   the serial column (one int64 per point, strictly increasing, given by rm_serials_kernel)
+//                                   and a binary search in it (rm_resolve_kernel)
 // Every table has two buffers of one capacity.  A kernel that rebuilds a table reads buf[cur] and writes buf[cur ^ 1]; the host
 // flips cur after the call's wait has read the refusal word.  Rows appended behind a table's count change nothing until the count
 // moves, which it does after the same wait.
@@ -22,11 +26,13 @@
 // atomicAdd on the counts.  Nothing is handed between workgroups inside a launch: an owner word is written by one launch and
 // compared by the next.
 #include <algorithm>
+#include <atomic>
 
 #include "maptables_internal.h"
 #include "kf_dist_device.h"       // mba_centre, mba_linear_dist, mba_pair_less, mba_block_least
 #include "mapmaker_internal.h"    // EpiBusy, EpiRun, the epipolar chain
 #include "refind_internal.h"      // ptam_refinder
+#include "snapshot_internal.h"    // ptam_map_snapshot: ptam_rmap_publish fills its free slot
 
 namespace {
 
@@ -56,6 +62,8 @@ struct ptam_rmap {
     ptam_ctx* ctx;
     int n[RM_N_COUNTS];
     RmTable t[PTAM_RMAP_TABLES];
+    RmTable serial;                    // the seventh point-side column: one int64 per point, strictly increasing; no table of download
+    long long map_id, next_serial;     // process-wide | the next serial this handle gives out (never reused)
     std::vector<const ptam_kf*> kfs;   // host only
     std::vector<double> h_poses;       // the mirror: K x 12
     std::vector<uint8_t> h_fixed;
@@ -234,6 +242,56 @@ __global__ void __launch_bounds__(256) rm_busy_kernel(int n, const ptam_map_meas
     busy[i] = b;
 }
 
+// the next serials of the handle, one thread per new point
+__global__ void __launch_bounds__(256) rm_serials_kernel(int n, long long first, long long* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = first + i;
+}
+// the index of `key` in the strictly increasing list s[0..n), or -1
+__device__ __forceinline__ int rm_find_serial(const long long* __restrict__ s, int n, long long key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (s[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && s[lo] == key ? lo : -1;
+}
+// ptam_rmap_resolve_serials, one thread per entry: the serial's current point index, -1 and a count for one that is gone
+__global__ void __launch_bounds__(256) rm_resolve_kernel(int n, const long long* __restrict__ keys, int n_points, const long long* __restrict__ serials,
+                                                          int32_t* __restrict__ index_out, int* __restrict__ n_gone) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int at = rm_find_serial(serials, n_points, keys[i]);
+    index_out[i] = at;
+    if (at < 0) atomicAdd(n_gone, 1);
+}
+// a keyframe as ptam_rmap_publish sends it up: the four level images
+struct RmKfRecord {
+    const uint8_t* im[PTAM_LEVELS];
+    int w[PTAM_LEVELS], h[PTAM_LEVELS];
+};
+static_assert(sizeof(RmKfRecord) == 64 && sizeof(RmKfRecord) <= PTAM_RMAP_KF_RECORD_BYTES, "the record ptam_hip.h describes");
+// ptam_rmap_publish, one thread per point: the tracker's row, its patch source resolved to the level image, its serial
+// (src_kf and src_level are in range by the handle's invariant: rm_check_points_kernel, mt_add_points_core)
+__global__ void __launch_bounds__(256) rm_publish_kernel(int n, const ptam_map_refind_point* __restrict__ rows, const long long* __restrict__ serials,
+                                                          const RmKfRecord* __restrict__ kfs, ptam_pvs_point* __restrict__ pts, TmSrc* __restrict__ src,
+                                                          long long* __restrict__ serials_out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const ptam_map_refind_point r = rows[i];
+    const RmKfRecord& k = kfs[r.src_kf];
+    TmSrc s;
+    s.im = k.im[r.src_level];
+    s.w = k.w[r.src_level];
+    s.h = k.h[r.src_level];
+    s.cx = r.center_x;
+    s.cy = r.center_y;
+    pts[i] = r.pv;
+    src[i] = s;
+    serials_out[i] = serials[i];
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 inline size_t rm_up256(size_t b) { return (b + 255) & ~(size_t)255; }
 struct RmCarve {   // offsets into the context's scratch
@@ -260,20 +318,19 @@ int rm_down(ptam_rmap* m, void* dst, const void* src, size_t bytes) {
 }
 
 // table w holds at least `rows` rows in both buffers; growth doubles, keeps the live rows and is the only allocation of a call
-int rm_room(ptam_rmap* m, int w, long long rows) {
-    RmTable& t = m->t[w];
+int rm_room_of(ptam_rmap* m, RmTable& t, int w, size_t row_bytes, int live_rows, long long rows) {
     if ((size_t)rows <= t.cap) return PTAM_OK;
     ARG_TRY(rows < (1ll << 31));
     const size_t cap = std::max(std::max((size_t)rows, 2 * t.cap), (size_t)64);
     char* nb[2] = {nullptr, nullptr};
     for (int k = 0; k < 2; k++)
-        if (hipMalloc((void**)&nb[k], cap * RM_ROW_BYTES[w]) != hipSuccess) {
+        if (hipMalloc((void**)&nb[k], cap * row_bytes) != hipSuccess) {
             if (nb[0]) (void)hipFree(nb[0]);
             ptam_set_error("ptam_rmap: no device memory for %zu rows of table %d", cap, w);
             return PTAM_E_HIP;
         }
     hipStream_t st = m->ctx->stream;
-    const size_t live = (size_t)m->n[RM_COUNT_OF[w]] * RM_ROW_BYTES[w];
+    const size_t live = (size_t)live_rows * row_bytes;
     hipError_t e = live > 0 ? hipMemcpyAsync(nb[t.cur], t.now(), live, hipMemcpyDeviceToDevice, st) : hipSuccess;
     if (e == hipSuccess) e = ptam_stream_wait(st);   // (nothing queued reads the old buffers any more)
     if (e != hipSuccess) {
@@ -289,10 +346,18 @@ int rm_room(ptam_rmap* m, int w, long long rows) {
     t.cap = cap;
     return PTAM_OK;
 }
+int rm_room(ptam_rmap* m, int w, long long rows) { return rm_room_of(m, m->t[w], w, RM_ROW_BYTES[w], m->n[RM_COUNT_OF[w]], rows); }
+enum { RM_SERIAL_COLUMN = PTAM_RMAP_TABLES + 1 };   // (what a failed growth of the serial column calls it)
+int rm_room_serials(ptam_rmap* m, long long rows) { return rm_room_of(m, m->serial, RM_SERIAL_COLUMN, sizeof(long long), m->n[RM_N_POINTS], rows); }
 int rm_room_points(ptam_rmap* m, long long rows) {
     for (int w = PTAM_RMAP_POINTS3; w <= PTAM_RMAP_INLIER_COUNT; w++)
         if (int rc = rm_room(m, w, rows)) return rc;
-    return PTAM_OK;
+    return rm_room_serials(m, rows);
+}
+
+// out[i] = first + i: the serials of points that a call appends (or, at an upload, of all of them)
+void rm_give_serials(hipStream_t st, int n, long long first, long long* out) {
+    if (n > 0) hipLaunchKernelGGL(rm_serials_kernel, dim3(rm_blocks(n)), dim3(256), 0, st, n, first, out);
 }
 
 // the refusal words open, the counts zero
@@ -405,7 +470,10 @@ int rm_add_points_device(ptam_rmap* m, int src_kf, int target_kf, int target_sou
     p.inlier_count = rm_now<int32_t>(m, PTAM_RMAP_INLIER_COUNT) + N;
     p.new_queue = rm_now<int32_t>(m, PTAM_RMAP_NEW_QUEUE) + Q;
     if (int rc = mt_add_points_core(m->ctx->stream, p)) return rc;
+    rm_give_serials(m->ctx->stream, n_made, m->next_serial, (long long*)m->serial.now() + N);   // behind the count, like the other rows
+    HIP_TRY(hipGetLastError());
     HIP_TRY(ptam_stream_wait(m->ctx->stream));
+    m->next_serial += n_made;
     m->t[PTAM_RMAP_MEAS].cur ^= 1;
     m->n[RM_N_MEAS] = M + 2 * n_made;
     m->n[RM_N_POINTS] = N + n_made;
@@ -426,6 +494,9 @@ int ptam_rmap_create(ptam_ctx* ctx, ptam_rmap** out) {
     m->d_words = nullptr;
     m->h2d = m->d2h = 0;
     m->refusal_table = m->refusal_row = -1;
+    static std::atomic<long long> map_ids{0};
+    m->map_id = ++map_ids;
+    m->next_serial = 1;
     if (hipMalloc((void**)&m->d_words, RM_WORDS * sizeof(int)) != hipSuccess) {
         delete m;
         ptam_set_error("ptam_rmap_create: no device memory");
@@ -442,6 +513,8 @@ int ptam_rmap_destroy(ptam_rmap* m) {
     for (int w = 0; w < PTAM_RMAP_TABLES; w++)
         for (int k = 0; k < 2; k++)
             if (m->t[w].buf[k]) (void)hipFree(m->t[w].buf[k]);
+    for (int k = 0; k < 2; k++)
+        if (m->serial.buf[k]) (void)hipFree(m->serial.buf[k]);
     if (m->d_words) (void)hipFree(m->d_words);
     delete m;
     return PTAM_OK;
@@ -454,7 +527,7 @@ int ptam_rmap_reserve(ptam_rmap* m, int n_kf, int n_points, int n_meas, int n_ne
     const int rows[RM_N_COUNTS] = {n_kf, n_points, n_meas, n_never, n_new, n_failure};
     for (int w = 0; w < PTAM_RMAP_TABLES; w++)
         if (int rc = rm_room(m, w, rows[RM_COUNT_OF[w]])) return rc;
-    return PTAM_OK;
+    return rm_room_serials(m, n_points);
 }
 
 int ptam_rmap_counts(const ptam_rmap* m, ptam_rmap_counts_t* out) {
@@ -495,6 +568,7 @@ int ptam_rmap_upload(ptam_rmap* m, int n_kf, const ptam_kf* const* kfs, const do
     const int rows[RM_N_COUNTS] = {n_kf, n_points, n_meas, n_never, n_new, n_failure};
     for (int w = 0; w < PTAM_RMAP_TABLES; w++)
         if (int rc = rm_room(m, w, rows[RM_COUNT_OF[w]])) return rc;
+    if (int rc = rm_room_serials(m, n_points)) return rc;
     const size_t Nz = (size_t)n_points;
     void* sc;
     if (int rc = ctx_scratch(m->ctx, rm_up256(Nz * sizeof(unsigned)) + 256, &sc)) return rc;
@@ -510,6 +584,7 @@ int ptam_rmap_upload(ptam_rmap* m, int n_kf, const ptam_kf* const* kfs, const do
         } else if (bytes > 0)
             HIP_TRY(hipMemsetAsync(m->t[w].alt(), 0, bytes, st));   // (the counts, when none are given)
     }
+    rm_give_serials(st, n_points, m->next_serial, (long long*)m->serial.alt());   // every point a fresh serial: a new map to every tracker
     // ---- the checks, one thread per row
     if (int rc = rm_words_reset(m)) return rc;
     int* err = m->d_words;
@@ -543,6 +618,8 @@ int ptam_rmap_upload(ptam_rmap* m, int n_kf, const ptam_kf* const* kfs, const do
         if (hw[o[0]] != RM_NO_ROW) return rm_refuse(m, o[1], hw[o[0]]);
     // ---- commit
     for (int w = 0; w < PTAM_RMAP_TABLES; w++) m->t[w].cur ^= 1;
+    m->serial.cur ^= 1;
+    m->next_serial += n_points;
     for (int i = 0; i < RM_N_COUNTS; i++) m->n[i] = rows[i];
     m->kfs.assign((size_t)n_kf, nullptr);
     if (kfs) std::copy(kfs, kfs + n_kf, m->kfs.begin());
@@ -828,12 +905,15 @@ int ptam_rmap_handle_bad_points(ptam_rmap* m, ptam_map_bad_points_result* res, i
     d.failure_out = rm_alt<ptam_map_pair>(m, PTAM_RMAP_FAILURE);
     // the point-side tables, all compacted; a survivor's bad byte is 0 (it would not have survived)
     const int cols[5] = {PTAM_RMAP_POINTS3, PTAM_RMAP_REFIND_POINTS, PTAM_RMAP_SOURCES, PTAM_RMAP_OUTLIER_COUNT, PTAM_RMAP_INLIER_COUNT};
-    d.n_columns = 5;
+    d.n_columns = 6;
     for (int k = 0; k < 5; k++) {
         d.col_in[k] = m->t[cols[k]].now();
         d.col_out[k] = m->t[cols[k]].alt();
         d.col_dwords[k] = (int)(RM_ROW_BYTES[cols[k]] / 4);
     }
+    d.col_in[5] = m->serial.now();   // the serials: compacted in order, so still strictly increasing
+    d.col_out[5] = m->serial.alt();
+    d.col_dwords[5] = (int)(sizeof(long long) / 4);
     if (N > 0) HIP_TRY(hipMemsetAsync(m->t[PTAM_RMAP_BAD].alt(), 0, Nz, st));
     if (int rc = mt_handle_bad_points_core(st, d)) return rc;
     const int* hw;
@@ -849,6 +929,7 @@ int ptam_rmap_handle_bad_points(ptam_rmap* m, ptam_map_bad_points_result* res, i
     r.n_new_dropped = Q - r.n_new_out;
     r.n_failure_out = hc[MT_T_FAIL];
     for (int w = PTAM_RMAP_POINTS3; w < PTAM_RMAP_TABLES; w++) m->t[w].cur ^= 1;
+    m->serial.cur ^= 1;
     m->n[RM_N_POINTS] = r.n_kept;
     m->n[RM_N_MEAS] = r.n_meas_out;
     m->n[RM_N_NEVER] = r.n_never_out;
@@ -1035,6 +1116,89 @@ int ptam_rmap_insert_keyframe(ptam_rmap* m, ptam_refinder* finder, const ptam_kf
     return PTAM_OK;
 }
 
+int ptam_rmap_point_serials(ptam_rmap* m, int first, int count, int64_t* out) {
+    ARG_TRY(m && first >= 0 && count >= 0 && (long long)first + count <= m->n[RM_N_POINTS]);
+    ARG_TRY(count == 0 || out);
+    if (count == 0) return PTAM_OK;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (int rc = rm_down(m, out, (const long long*)m->serial.now() + first, (size_t)count * sizeof(long long))) return rc;
+    HIP_TRY(ptam_stream_wait(m->ctx->stream));
+    return PTAM_OK;
+}
+
+int ptam_rmap_resolve_serials(ptam_rmap* m, int n, const int64_t* serials, int32_t* index_out, int32_t* n_gone) {
+    ARG_TRY(m && n >= 0 && (n == 0 || (serials && index_out)));
+    if (n_gone) *n_gone = 0;
+    if (n == 0) return PTAM_OK;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    const size_t o_idx = rm_up256((size_t)n * sizeof(long long));
+    void* sc;
+    if (int rc = ctx_scratch(m->ctx, o_idx + rm_up256((size_t)n * 4), &sc)) return rc;
+    char* b = (char*)sc;
+    if (int rc = rm_up(m, b, serials, (size_t)n * sizeof(long long))) return rc;
+    if (int rc = rm_words_reset(m)) return rc;
+    hipLaunchKernelGGL(rm_resolve_kernel, dim3(rm_blocks(n)), dim3(256), 0, m->ctx->stream, n, (const long long*)b, m->n[RM_N_POINTS],
+                       (const long long*)m->serial.now(), (int32_t*)(b + o_idx), m->d_words + RM_W_TOT);
+    HIP_TRY(hipGetLastError());
+    if (int rc = rm_down(m, index_out, b + o_idx, (size_t)n * 4)) return rc;
+    const int* hw;
+    if (int rc = rm_words_wait(m, &hw)) return rc;
+    if (n_gone) *n_gone = hw[RM_W_TOT];
+    return PTAM_OK;
+}
+
+int ptam_rmap_publish(ptam_rmap* m, ptam_map_snapshot* snap, ptam_map_publish_result* res) {
+    // ---- refusals: nothing is enqueued, and no slot is taken, before all of them have passed
+    ARG_TRY(m && snap && res);
+    ARG_TRY(snap->device == m->ctx->device);
+    const int K = m->n[RM_N_KF], N = m->n[RM_N_POINTS];
+    for (int k = 0; k < K; k++) ARG_TRY(m->kfs[(size_t)k] && m->kfs[(size_t)k]->device == m->ctx->device);
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    std::vector<RmKfRecord> recs((size_t)K);
+    for (int k = 0; k < K; k++)
+        for (int l = 0; l < PTAM_LEVELS; l++) {
+            recs[(size_t)k].im[l] = m->kfs[(size_t)k]->L.im[l];
+            recs[(size_t)k].w[l] = m->kfs[(size_t)k]->L.w[l];
+            recs[(size_t)k].h[l] = m->kfs[(size_t)k]->L.h[l];
+        }
+    void* sc;
+    if (int rc = ctx_scratch(m->ctx, rm_up256((size_t)K * sizeof(RmKfRecord)), &sc)) return rc;
+    const int s = snap->slots.begin_write();
+    if (s < 0) {
+        ptam_set_error("ptam_rmap_publish: a publish into this snapshot is under way");
+        return PTAM_E_STATE;
+    }
+    // ---- the free slot is this call's until the commit
+    ptam_map_publish_result r = {};
+    int grew = 0;
+    int rc = snap_slot_room(snap, s, (size_t)std::max(N, 1), &grew);
+    if (!rc) rc = rm_up(m, sc, recs.data(), (size_t)K * sizeof(RmKfRecord));
+    if (!rc && N > 0) {
+        SnapSlot& sl = snap->slot[s];
+        hipLaunchKernelGGL(rm_publish_kernel, dim3(rm_blocks(N)), dim3(256), 0, m->ctx->stream, N,
+                           (const ptam_map_refind_point*)rm_now<ptam_map_refind_point>(m, PTAM_RMAP_REFIND_POINTS), (const long long*)m->serial.now(),
+                           (const RmKfRecord*)sc, sl.pts, sl.src, sl.serials);
+        if (hipGetLastError() != hipSuccess) rc = PTAM_E_HIP;
+    }
+    if (!rc && ptam_stream_wait(m->ctx->stream) != hipSuccess) rc = PTAM_E_HIP;   // the call's one wait: the slot is whole
+    if (rc) {
+        if (rc == PTAM_E_HIP) ptam_set_error("ptam_rmap_publish: the gather failed: %s", hipGetErrorString(hipGetLastError()));
+        snap->slots.abort_write();
+        return rc;
+    }
+    SnapSlot& sl = snap->slot[s];
+    sl.n = N;
+    sl.map_id = m->map_id;
+    sl.generation = snap->slots.next_generation();
+    r.generation = snap->slots.commit_write();
+    r.map_id = m->map_id;
+    r.n_points = N;
+    r.n_kf = K;
+    r.grew = grew;
+    *res = r;
+    return PTAM_OK;
+}
+
 }   // extern "C"
 
 void maprmap_preload_kernels() {
@@ -1052,4 +1216,7 @@ void maprmap_preload_kernels() {
     ptam_preload((const void*)rm_note_tracked_kernel);
     ptam_preload((const void*)rm_queue_bad_kernel);
     ptam_preload((const void*)rm_pack_pvs_kernel);
+    ptam_preload((const void*)rm_serials_kernel);
+    ptam_preload((const void*)rm_resolve_kernel);
+    ptam_preload((const void*)rm_publish_kernel);
 }

@@ -20,6 +20,7 @@
 #include <climits>
 
 #include "track_internal.h"
+#include "snapshot_internal.h"    // ptam_map_snapshot: ptam_tracker_take_map copies its current slot
 #include "wait_mapped.h"
 #include "../../include/ptam_hip_bench.h"
 #include "patch_device.h"
@@ -878,6 +879,11 @@ struct ptam_tracker {
     void* batch_dev;
     size_t batch_cap;
     hipStream_t last_stream;   // the queue that last ran this tracker (its own context's, or a batch's lead tracker's)
+    // ptam_tracker_take_map: the serials of the map's points (device, [cap]; valid iff has_serials), the map they belong to and
+    // the (snapshot, generation) they were taken from.  ptam_tracker_set_map / update_map clear all of it.
+    long long* serials;
+    int has_serials;
+    long long map_id, snap_uid, snap_generation;
     // stage timing of ptam_track_map_frame (ptam_tracker_set_profiling): an event after every launch of the frame
     bool prof;
     hipEvent_t ev[PTAM_TS_COUNT + 1];
@@ -985,7 +991,7 @@ int ptam_tracker_create(ptam_ctx* ctx, int max_points, ptam_tracker** out) {
                  o_sr = take(cap * sizeof(ptam_subpix_result)), o_sf = take(cap * 4), o_st = take(cap * 4), o_ss = take(cap * 4), o_sv = take(cap * 16), o_rec = take(cap * TM_REC_F * 8), o_rect = take(cap * 8),
                  o_me = take(cap * sizeof(ptam_pose_meas)), o_en = take(cap * sizeof(ptam_projection)), o_mi = take(cap * 4),
                  o_ms = take(cap * 4), o_ou = take(cap * 4), o_ctl = take(sizeof(TmCtl)), o_pose = take(96),
-                 o_fs = take(cap * sizeof(TmFinder));
+                 o_fs = take(cap * sizeof(TmFinder)), o_ser = take(cap * sizeof(long long));
     // every failure past this point leaves through ONE path that releases what exists so far
     auto fail = [&](const char* what) {
         ptam_set_error("ptam_tracker_create: %s failed", what);
@@ -1027,6 +1033,7 @@ int ptam_tracker_create(ptam_ctx* ctx, int max_points, ptam_tracker** out) {
     d.ctl = (TmCtl*)(b + o_ctl);
     d.pose = (double*)(b + o_pose);
     d.finder = (TmFinder*)(b + o_fs);   // (cleared with the block: no finder has made a template yet)
+    t->serials = (long long*)(b + o_ser);
     void* h = nullptr;
     if (hipHostMalloc(&h, sizeof(TmMailbox), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail("hipHostMalloc");
     t->mbox = (TmMailbox*)h;
@@ -1141,6 +1148,167 @@ static int tracker_set_map_impl(ptam_tracker* t, int n, const ptam_pvs_point* pt
         }
     }
     t->d.n = n;
+    t->has_serials = 0;   // the points have no identity any more: the next take treats every one as new
+    t->map_id = t->snap_uid = t->snap_generation = 0;
+    return PTAM_OK;
+}
+
+// ---- ptam_tracker_take_map: the map from a snapshot, device to device ----
+// prev[i] = where new point i was in the tracker's map: its serial, searched in the old list (both strictly increasing, so no old
+// index is found twice); n_old = 0 when the tracker has no list or the map is another one.  *n_carried counts the hits.
+__global__ void __launch_bounds__(256) tm_take_prev_kernel(int n, const long long* __restrict__ fresh, int n_old, const long long* __restrict__ old,
+                                                           int* __restrict__ prev, int* __restrict__ n_carried) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long key = fresh[i];
+    int lo = 0, hi = n_old;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (old[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    const int at = lo < n_old && old[lo] == key ? lo : -1;
+    prev[i] = at;
+    if (at >= 0) atomicAdd(n_carried, 1);
+}
+// the shuffles back to the identity (the map's size changed: they are permutations of 0..n-1)
+__global__ void __launch_bounds__(256) tm_identity_kernel(int n, int* __restrict__ a, int* __restrict__ b) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) a[i] = i, b[i] = i;
+}
+// the serial of every entry of the iteration set (list: search slot -> map point)
+__global__ void __launch_bounds__(256) tm_iteration_serials_kernel(int ns, const int* __restrict__ list, int n, const long long* __restrict__ serials,
+                                                                   long long* __restrict__ out) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= ns) return;
+    const int p = list[s];
+    out[s] = p >= 0 && p < n ? serials[p] : -1;
+}
+
+// the device side of a take, from slot `sl` (held by the caller): everything enqueued on the context's queue, one wait
+static int tracker_take_enqueue(ptam_tracker* t, const SnapSlot& sl, int* n_carried) {
+    ptam_ctx* ctx = t->ctx;
+    hipStream_t st = ctx->stream;
+    const int n = sl.n, cap = t->d.cap;
+    HIP_TRY(ptam_stream_wait(st));   // (as ptam_tracker_update_map: no frame of this tracker is in flight, the scratch is nobody's)
+    if (t->last_stream && t->last_stream != st) HIP_TRY(ptam_stream_wait(t->last_stream));
+    const size_t bf = (size_t)cap * sizeof(TmFinder), bfa = (bf + 255) & ~(size_t)255, bpa = ((size_t)n * 4 + 255) & ~(size_t)255;
+    void *sc, *hp;
+    if (int rc = ctx_scratch(ctx, bfa + bpa + 256, &sc)) return rc;
+    if (int rc = ctx_pinned(ctx, 256, &hp)) return rc;
+    int* d_prev = (int*)((char*)sc + bfa);
+    int* d_count = (int*)((char*)sc + bfa + bpa);
+    HIP_TRY(hipMemsetAsync(d_count, 0, 8, st));
+    HIP_TRY(hipMemcpyAsync(sc, t->d.finder, bf, hipMemcpyDeviceToDevice, st));
+    const int n_old = t->has_serials && t->map_id == sl.map_id ? t->d.n : 0;
+    if (n > 0)
+        hipLaunchKernelGGL(tm_take_prev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const long long*)sl.serials, n_old,
+                           (const long long*)t->serials, d_prev, d_count);
+    const long long words = (long long)cap * (long long)(sizeof(TmFinder) / 4);
+    hipLaunchKernelGGL(tm_finder_carry_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, t->d.finder, (const TmFinder*)sc,
+                       (const int*)d_prev, n, cap);
+    HIP_TRY(hipGetLastError());
+    if (n > 0) {   // (behind the search: the old serial list has been read)
+        HIP_TRY(hipMemcpyAsync(t->d.pts, sl.pts, (size_t)n * sizeof(ptam_pvs_point), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t->d.src, sl.src, (size_t)n * sizeof(TmSrc), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t->serials, sl.serials, (size_t)n * sizeof(long long), hipMemcpyDeviceToDevice, st));
+    }
+    if (n != t->d.n) {   // the ≤ 8192-point path keeps the frame's shuffles in host-mapped memory: back to the device arrays
+        t->d.perm_a = t->perm_dev_a;
+        t->d.perm_b = t->perm_dev_b;
+        if (n > 0) {
+            hipLaunchKernelGGL(tm_identity_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, t->d.perm_a, t->d.perm_b);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(hp, d_count, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ptam_stream_wait(st));
+    *n_carried = *(const int*)hp;
+    return PTAM_OK;
+}
+
+int ptam_tracker_take_map(ptam_tracker* t, ptam_map_snapshot* snap, ptam_map_take_result* res) {
+    ARG_TRY(t && snap && res);
+    ptam_ctx* ctx = t->ctx;
+    ARG_TRY(snap->device == ctx->device);
+    ARG_TRY(snap->width == ctx->params.width && snap->height == ctx->params.height);
+    ptam_map_take_result r = {};
+    long long gen = 0;
+    const int k = snap->slots.begin_read(t->snap_uid == snap->uid ? t->snap_generation : -1, &gen);
+    if (k == SnapSlots::NEVER) {
+        ptam_set_error("bad argument: ptam_tracker_take_map: nothing has been published into the snapshot");
+        return PTAM_E_ARG;
+    }
+    if (k == SnapSlots::UNCHANGED) {   // the per-frame poll
+        r.generation = gen;
+        r.map_id = t->map_id;
+        r.n_points = t->d.n;
+        *res = r;
+        return PTAM_OK;
+    }
+    const SnapSlot& sl = snap->slot[k];   // ours until end_read: the publisher leaves it alone
+    if (sl.n > t->d.cap) {
+        const int n = sl.n;
+        snap->slots.end_read(k);
+        ptam_set_error("bad argument: ptam_tracker_take_map: the snapshot holds %d points, the tracker %d at most", n, t->d.cap);
+        return PTAM_E_ARG;
+    }
+    int rc = hipSetDevice(ctx->device) == hipSuccess ? PTAM_OK : PTAM_E_HIP;
+    int carried = 0;
+    if (!rc) rc = tracker_take_enqueue(t, sl, &carried);
+    const int n = sl.n, n_old = t->d.n;
+    const long long map_id = sl.map_id, generation = sl.generation;
+    snap->slots.end_read(k);
+    if (rc) return rc;
+    t->d.n = n;
+    t->has_serials = 1;
+    t->map_id = map_id;
+    t->snap_uid = snap->uid;
+    t->snap_generation = generation;
+    r.changed = 1;
+    r.n_points = n;
+    r.n_carried = carried;
+    r.n_new = n - carried;
+    r.n_dropped = n_old - carried;
+    r.link_bytes = 8;
+    r.generation = generation;
+    r.map_id = map_id;
+    *res = r;
+    return PTAM_OK;
+}
+
+int ptam_tracker_point_serials(ptam_tracker* t, int first, int count, int64_t* out) {
+    ARG_TRY(t && first >= 0 && count >= 0 && (long long)first + count <= (t->has_serials ? t->d.n : 0));
+    ARG_TRY(count == 0 || out);
+    if (count == 0) return PTAM_OK;
+    HIP_TRY(hipSetDevice(t->ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, t->serials + first, (size_t)count * sizeof(long long), hipMemcpyDeviceToHost, t->ctx->stream));
+    HIP_TRY(ptam_stream_wait(t->ctx->stream));
+    return PTAM_OK;
+}
+
+int ptam_tracker_read_iteration_serials(ptam_tracker* t, int64_t* out, int cap, int* n_out) {
+    ARG_TRY(t && n_out && cap >= 0);
+    if (!t->has_serials) {
+        ptam_set_error("ptam_tracker_read_iteration_serials: the tracker's map did not come from a snapshot");
+        return PTAM_E_STATE;
+    }
+    ptam_ctx* ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ptam_stream_wait(ctx->stream));
+    TmCtl c;
+    HIP_TRY(hipMemcpy(&c, t->d.ctl, sizeof c, hipMemcpyDeviceToHost));
+    const int ns = std::min(std::max(c.n_slots, 0), t->d.cap);
+    *n_out = ns;
+    const int take = std::min(ns, cap);
+    if (!out || take == 0) return PTAM_OK;
+    void* sc;
+    if (int rc = ctx_scratch(ctx, (size_t)take * sizeof(long long), &sc)) return rc;
+    hipLaunchKernelGGL(tm_iteration_serials_kernel, dim3((unsigned)((take + 255) / 256)), dim3(256), 0, ctx->stream, take, (const int*)t->d.list, t->d.n,
+                       (const long long*)t->serials, (long long*)sc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, sc, (size_t)take * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ptam_stream_wait(ctx->stream));
     return PTAM_OK;
 }
 
@@ -1559,6 +1727,9 @@ void trackmap_preload_kernels() {
     ptam_preload((const void*)tm_search_kernel);
     ptam_preload((const void*)tm_gather_kernel);
     ptam_preload((const void*)tm_finder_carry_kernel);
+    ptam_preload((const void*)tm_take_prev_kernel);
+    ptam_preload((const void*)tm_identity_kernel);
+    ptam_preload((const void*)tm_iteration_serials_kernel);
     ptam_preload((const void*)tm_pose_kernel<1, GS_WAVE_LIMIT>);
     ptam_preload((const void*)tm_pose_kernel<1, GS_THREADS>);
     ptam_preload((const void*)tm_pose_kernel<GS_MPT, GS_THREADS>);

@@ -1089,9 +1089,61 @@ class ResidentMap:
         return dict(kf=res.kf, target_kf=res.target_kf, target_dist=res.target_dist, refind=_counts(res.refind), first_point=res.first_point,
                     n_made=res.n_made, levels=levels)
 
+    def publish(self, snapshot, check=True):
+        """ptam_rmap_publish: the map as it stands into `snapshot` (a MapSnapshot) as its next generation -> dict(generation, map_id,
+        n_points, n_kf, grew); nothing table-sized crosses the host link.  check=False: -> the status of a refused call."""
+        res = _abi.MapPublishResult()
+        rc = self.lib.rmap_publish(self.h, snapshot.h, C.byref(res))
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "rmap_publish")
+        snapshot._kfs = list(self._kfs)     # the level images a generation names stay alive with the snapshot
+        return _counts(res)
+
+    def point_serials(self, first=0, count=None):
+        """ptam_rmap_point_serials: the serial column (int64, strictly increasing), rows [first, first + count)"""
+        n = self.counts()["n_points"]
+        count = n - first if count is None else int(count)
+        out = np.zeros(max(count, 0), np.int64)
+        self.ctx._check(self.lib.rmap_point_serials(self.h, int(first), count, _ptr(out) if count > 0 else None), "rmap_point_serials")
+        return out
+
+    def resolve_serials(self, serials):
+        """ptam_rmap_resolve_serials: serials (any order) -> (current point index int32, -1 for a removed point; how many are gone)"""
+        serials = np.ascontiguousarray(serials, dtype=np.int64).reshape(-1)
+        out, gone = np.zeros(max(len(serials), 1), np.int32), C.c_int32()
+        self.ctx._check(self.lib.rmap_resolve_serials(self.h, len(serials), _ptr(serials) if len(serials) else None, _ptr(out), C.byref(gone)),
+                        "rmap_resolve_serials")
+        return out[:len(serials)].copy(), gone.value
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.rmap_destroy(self.h)
+            self.h = None
+
+
+class MapSnapshot:
+    """ptam_map_snapshot: the map as the tracker wants it, in device memory — ResidentMap.publish fills it on the mapmaker's thread,
+    Tracker.take_map copies from it on the tracker's.  Three slots; the hand-over is a mutex on the host."""
+
+    def __init__(self, ctx, max_points):
+        self.lib, self._check = ctx.lib, ctx._check
+        self.h = C.c_void_p()
+        self._kfs = []
+        ctx._check(self.lib.map_snapshot_create(ctx.h, int(max_points), C.byref(self.h)), "map_snapshot_create")
+
+    def reserve(self, max_points):
+        self._check(self.lib.map_snapshot_reserve(self.h, int(max_points)), "map_snapshot_reserve")
+
+    def info(self):
+        """-> dict(generation (0: never published into), map_id, n_points) of the current generation"""
+        r = _abi.MapSnapshotInfo()
+        self._check(self.lib.map_snapshot_info(self.h, C.byref(r)), "map_snapshot_info")
+        return dict(generation=r.generation, map_id=r.map_id, n_points=r.n_points)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.map_snapshot_destroy(self.h)
             self.h = None
 
 
@@ -1104,6 +1156,7 @@ class Tracker:
         self.h = C.c_void_p()
         ctx._check(self.lib.tracker_create(ctx.h, int(max_points), C.byref(self.h)), "tracker_create")
         self._keep = []
+        self.n, self._serials = 0, False    # points of the map | they have serials (the map came from take_map)
 
     def set_map(self, world, pixel_right_w, pixel_down_w, src_kfs, src_levels, centers, prev_index=None):
         """prev_index (update_map): for every point its index in the previous map, -1 for a new one — those points keep their
@@ -1124,7 +1177,7 @@ class Tracker:
             pi = np.ascontiguousarray(prev_index, dtype=np.int32)
             assert len(pi) == n
             self.ctx._check(self.lib.tracker_update_map(self.h, n, _ptr(pts), _ptr(q), _ptr(pi)), "tracker_update_map")
-        self.n = n
+        self.n, self._serials = n, False
 
     def update_map(self, world, pixel_right_w, pixel_down_w, src_kfs, src_levels, centers, prev_index):
         self.set_map(world, pixel_right_w, pixel_down_w, src_kfs, src_levels, centers, prev_index=prev_index)
@@ -1234,6 +1287,38 @@ class Tracker:
         if n.value:
             self.ctx._check(self.lib.tracker_read_iteration_set(self.h, _ptr(out), n.value, C.byref(n)), "tracker_read_iteration_set")
         return out
+
+    def take_map(self, snapshot, check=True):
+        """ptam_tracker_take_map: the snapshot's current generation becomes the tracker's map, device to device; points the tracker
+        knows by their serial keep their PatchFinder -> dict(changed, n_points, n_carried, n_new, n_dropped, link_bytes,
+        generation, map_id); changed == 0 is the per-frame poll.  check=False: -> the status of a refused call."""
+        res = _abi.MapTakeResult()
+        rc = self.lib.tracker_take_map(self.h, snapshot.h, C.byref(res))
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "tracker_take_map")
+        if res.changed:
+            self._keep = [snapshot]
+            self.n, self._serials = res.n_points, True
+        return _counts(res)
+
+    def point_serials(self, first=0, count=None):
+        """ptam_tracker_point_serials: the serials of the map's points after take_map (count None: all of them; none after set_map)"""
+        if count is None:
+            count = (self.n if self._serials else 0) - first
+        out = np.zeros(max(int(count), 0), np.int64)
+        self.ctx._check(self.lib.tracker_point_serials(self.h, int(first), int(count), _ptr(out) if count > 0 else None),
+                        "tracker_point_serials")
+        return out
+
+    def iteration_serials(self):
+        """ptam_tracker_read_iteration_serials: the serial of every entry of iteration_set(), in its order"""
+        n = C.c_int()
+        self.ctx._check(self.lib.tracker_read_iteration_serials(self.h, None, 0, C.byref(n)), "tracker_read_iteration_serials")
+        out = np.zeros(max(n.value, 1), dtype=np.int64)
+        if n.value:
+            self.ctx._check(self.lib.tracker_read_iteration_serials(self.h, _ptr(out), n.value, C.byref(n)), "tracker_read_iteration_serials")
+        return out[:n.value]
 
     def close(self):
         if getattr(self, "h", None):
