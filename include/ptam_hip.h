@@ -769,6 +769,34 @@ int ptam_track_frame_sbi(ptam_tracker* t, ptam_kf* current, const uint8_t* d_fra
  * variant; set the frames' permutations beforehand (ptam_tracker_set_shuffle). */
 int ptam_track_map_frames_batch(int nb, ptam_tracker* const* trackers, ptam_kf* const* current, const uint8_t* const* d_frames,
                                 const double* poses_in, const ptam_trackmap_opts* opts, ptam_trackmap_result* out);
+/* Tracker::TrackFrame's tracking branch for nb cameras as ONE chain of launches with one wait per camera: ptam_track_map_frames_batch
+ * with the motion model, the bTryCoarse heuristics (:503-514) PER CAMERA, and the rotation estimator.  Frame i is
+ *   with estimators[i]:     what ptam_track_frame_sbi(trackers[i], current[i], d_frames[i], &models[i], estimators[i], opts, ..) does —
+ *                           this frame's SmallBlurryImage, its alignment and the prediction from the rotation are made on the device
+ *                           (the device's asin / acos / sin / cos are not the host's: pose_in agrees with ptam_motion_predict_sbi to a
+ *                           few ulps, and everything behind it is ptam_track_map_frame from info[i].pose_in, bit for bit);
+ *   without (estimators == NULL or a NULL entry): what ptam_track_frame(trackers[i], ..) does, bit for bit.
+ * opts: the tunables, shared by all frames; its try_coarse is ignored (every frame's is decided from its model).  The conditions of
+ * ptam_track_map_frames_batch hold (one device, different contexts, the same camera model, image size and halfSample variant, nb in
+ * 1..4096); estimators[i] must belong to trackers[i]'s context, no estimator may appear twice, and all share image size and blur.
+ * All or nothing: the models and the estimators' last / this pairs are advanced on copies and committed when every frame of the batch
+ * has arrived; a call that returns an error leaves every models[i] byte for byte as it was and every estimator where it was.  (As in
+ * ptam_track_map_frames_batch the trackers' per-point PatchFinder state may already have moved.)  info (nullable): per frame the pose
+ * TrackMap started from, the alignment and the heuristics as applied. */
+typedef struct {
+    double pose_in[12];          /* the predicted pose TrackMap started from (device-computed when an estimator is given) */
+    ptam_sbi_alignment align;    /* this frame's alignment; all zero without an estimator */
+    int32_t try_coarse;          /* the frame's heuristics as applied (:503-514) */
+    uint32_t coarse_max, coarse_range;
+    int32_t pad_;
+} ptam_track_frame_info;
+int ptam_track_frames_batch(int nb, ptam_tracker* const* trackers, ptam_kf* const* current, const uint8_t* const* d_frames,
+                            ptam_motion_model* models /* nb, in/out */, ptam_rotation_estimator* const* estimators /* nullable; entries nullable */,
+                            const ptam_trackmap_opts* opts, ptam_trackmap_result* out, ptam_track_frame_info* info /* nullable, nb */);
+/* Test hook: the device's form of ptam_motion_predict_sbi (the one ptam_track_frames_batch runs in the align workgroup) on a table —
+ * one launch, one thread per row: poses_out12 + 12 i = the pose ptam_motion_predict_sbi(models + i, rotations9 + 9 i) leaves in the
+ * model.  The models are not changed.  The ranges of SO3::ln near pi, which no tracked sequence reaches, are run through this. */
+int ptam_motion_predict_sbi_dev(ptam_ctx* ctx, int n, const ptam_motion_model* models, const double* rotations9, double* poses_out12);
 /* vIterationSet of the last frame (what :667-676 turns into mCurrentKF.mMeasurements): *n = its length; out (nullable)
  * receives up to cap entries. */
 int ptam_tracker_read_iteration_set(ptam_tracker* t, ptam_trackmap_meas* out, int cap, int* n);

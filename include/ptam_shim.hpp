@@ -841,6 +841,33 @@ public:
         check(ptam_track_map_frames_batch((int)n, t.data(), k.data(), vdFrames.data(), poses.data(), pOpts, r.data()), "ptam_track_map_frames_batch");
         return r;
     }
+    // The same for cameras that move: per camera the motion model (vMotion[i], advanced in place), the bTryCoarse heuristics and —
+    // where vEstimators[i] is not null — the rotation estimator, i.e. TrackFrame(kf, dFrame, motion[, estimator]) for every camera,
+    // in one chain of launches with one wait per camera (ptam_track_frames_batch).  vEstimators may be empty (no camera has one).
+    // pvInfo (nullable): per camera the pose TrackMap started from, the alignment and the heuristics as applied.  A call that
+    // throws leaves every model and every estimator as it was.
+    static std::vector<ptam_trackmap_result> TrackFramesBatch(const std::vector<MapTracker*>& vTrackers, const std::vector<KeyFrame*>& vCurrent,
+                                                              const std::vector<const uint8_t*>& vdFrames, std::vector<ptam_motion_model>& vMotion,
+                                                              const std::vector<RotationEstimator*>& vEstimators, const ptam_trackmap_opts* pOpts = nullptr,
+                                                              std::vector<ptam_track_frame_info>* pvInfo = nullptr) {
+        const size_t n = vTrackers.size();
+        if (n == 0 || vCurrent.size() != n || vdFrames.size() != n || vMotion.size() != n || (!vEstimators.empty() && vEstimators.size() != n))
+            throw std::runtime_error("TrackFramesBatch: sizes differ");
+        std::vector<ptam_tracker*> t(n);
+        std::vector<ptam_kf*> k(n);
+        std::vector<ptam_rotation_estimator*> e(n, nullptr);
+        for (size_t i = 0; i < n; i++) {
+            t[i] = vTrackers[i]->h_;
+            k[i] = vCurrent[i]->handle();
+            if (!vEstimators.empty() && vEstimators[i]) e[i] = vEstimators[i]->handle();
+        }
+        std::vector<ptam_trackmap_result> r(n);
+        if (pvInfo) pvInfo->assign(n, ptam_track_frame_info{});
+        check(ptam_track_frames_batch((int)n, t.data(), k.data(), vdFrames.data(), vMotion.data(), vEstimators.empty() ? nullptr : e.data(), pOpts,
+                                      r.data(), pvInfo ? pvInfo->data() : nullptr),
+              "ptam_track_frames_batch");
+        return r;
+    }
     // vIterationSet of the last frame: what :667-676 turns into mCurrentKF.mMeasurements and what routes the outlier flags
     // back to MapPoint::nMEstimatorOutlierCount
     std::vector<ptam_trackmap_meas> IterationSet() {

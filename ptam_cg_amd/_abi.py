@@ -279,6 +279,12 @@ class SbiAlignment(C.Structure):
                 ("pad_", C.c_int32)]
 
 
+class TrackFrameInfo(C.Structure):
+    """ptam_track_frame_info (ptam_track_frames_batch): the pose TrackMap started from, the alignment, the heuristics as applied"""
+    _fields_ = [("pose_in", C.c_double * 12), ("align", SbiAlignment), ("try_coarse", C.c_int32), ("coarse_max", C.c_uint32),
+                ("coarse_range", C.c_uint32), ("pad_", C.c_int32)]
+
+
 class RelocResult(C.Structure):
     """ptam_reloc_result (Relocaliser::AttemptRecovery, src/Relocaliser.cc:12-38)"""
     _fields_ = [("best", C.c_int32), ("good", C.c_int32), ("best_ssd", C.c_double), ("pose", C.c_double * 12), ("align", SbiAlignment)]
@@ -411,6 +417,8 @@ PROTOTYPES = {
     "tracker_stage_time": (_i, [_vp, _i, _pd, C.POINTER(_i)]),
     "bench_track_frames": (_i, [_i, _vp, _vp, _vp, _pd, _vp, _vp, _vp, _i, _pd]),
     "track_map_frames_batch": (_i, [_i, _vp, _vp, _vp, _pd, _vp, _vp]),
+    "track_frames_batch": (_i, [_i, _vp, _vp, _vp, C.POINTER(MotionModel), _vp, _vp, _vp, C.POINTER(TrackFrameInfo)]),
+    "motion_predict_sbi_dev": (_i, [_vp, _i, C.POINTER(MotionModel), _pd, _pd]),
     "bench_track_batch": (_i, [_i, _vp, _vp, _vp, _pd, _vp, _vp, _vp, _i, _i, _pd]),
     "tracker_read_iteration_set": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "ba_bench_jacobian_rotating": (_i, [_vp, _i, _i, _pd]),

@@ -9,6 +9,7 @@
 #include "keyframe_device.h"   // half4: the pyramid's halfSample
 #include "patch_device.h"      // nc_*: products and sums that are never contracted; cam_unproject
 #include "wait_mapped.h"
+#include "motion_device.h"     // the prediction behind SE3fromSE2 (a batch's frames)
 
 #define SBI_THREADS 256
 #define SBI_MAX_PIXELS 4096    // LDS: make 48 KB (f32 template + f64 row pass), align 32 KB (template + warped image)
@@ -20,6 +21,7 @@
 struct SbiMakeArgs {
     const uint8_t* l3;   // aLevels[3].im; or, for a grid of several images:
     const uint8_t* const* l3_list;   // image b's level 3 (device array, nullable); its outputs follow b images further on
+    const SbiBatchRec* recs;         // or (nullable) a record per image: its level 3 and its own three output arrays
     int w3, w, h, k;     // level-3 row pitch; the SBI's size; taps each side
     uint8_t* small;      // mimSmall
     float* tmpl;         // mimTemplate
@@ -33,10 +35,11 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_make_kernel(SbiMakeArgs a) {
     __shared__ double s_h[SBI_MAX_PIXELS];
     __shared__ unsigned s_sum[SBI_THREADS / 64];
     const int tid = threadIdx.x, n = a.w * a.h;
-    const uint8_t* __restrict__ l3 = a.l3_list ? a.l3_list[blockIdx.x] : a.l3;
-    uint8_t* __restrict__ o_small = a.small + (size_t)blockIdx.x * n;
-    float* __restrict__ o_tmpl = a.tmpl + (size_t)blockIdx.x * n;
-    float* __restrict__ o_jacs = a.jacs + (size_t)blockIdx.x * 2 * n;
+    const SbiBatchRec* rec = a.recs ? a.recs + blockIdx.x : nullptr;
+    const uint8_t* __restrict__ l3 = rec ? rec->l3 : a.l3_list ? a.l3_list[blockIdx.x] : a.l3;
+    uint8_t* __restrict__ o_small = rec ? rec->small : a.small + (size_t)blockIdx.x * n;
+    float* __restrict__ o_tmpl = rec ? rec->tmpl : a.tmpl + (size_t)blockIdx.x * n;
+    float* __restrict__ o_jacs = rec ? rec->jacs : a.jacs + (size_t)blockIdx.x * 2 * n;
     unsigned sum = 0;   // (exact: at most 4096 * 255)
     for (int i = tid; i < n; i += SBI_THREADS) {
         const int x = i % a.w, y = i / a.w;
@@ -123,6 +126,15 @@ struct SbiAlignArgs {
     DevCam cam;               // the camera at the SBI's size (camera.SetImageSize(mirSize), :429)
     SbiOut* out;
     unsigned long long seq;
+    // a batch's frames (nullable): workgroup b aligns record b's image against record b's target, then predicts the frame's pose;
+    // cur, tgt_*, ssd, out and seq are not used
+    const SbiBatchRec* recs;
+    // ... with, in the same launch, the FAST detection of the batch's keyframes (det_items nullable): it needs the pyramid only, as the
+    // images do, so its workgroups — behind the n_align align workgroups, det_blocks per keyframe, keyframe f's KfLevels at
+    // det_items + f * det_stride + det_off — fill the chip while the align workgroups walk their ~100 us of serial chain
+    const char* det_items;
+    size_t det_stride, det_off;
+    int det_blocks, n_align;
 };
 
 // TooN Cholesky<N> (L D L^T, the scaled column cached in the upper half) + backsub.  false: a pivot that is not strictly positive.
@@ -239,6 +251,11 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_align_kernel(SbiAlignArgs g) 
     __shared__ SbiWalk s_walk;
     __shared__ double s_bv[SBI_THREADS];
     __shared__ int s_bi[SBI_THREADS];
+    if (g.det_items && (int)blockIdx.x >= g.n_align) {
+        const int d = (int)blockIdx.x - g.n_align;
+        fast_detect_tall_body<FAST_BATCH_TH>(*(const KfLevels*)(g.det_items + (size_t)(d / g.det_blocks) * g.det_stride + g.det_off), d % g.det_blocks);
+        return;
+    }
     const int tid = threadIdx.x, w = g.w, h = g.h, n = w * h;
     // the relocaliser's nearest keyframe: the first strictly smallest SSD (src/Relocaliser.cc:21-31) = the smallest value, and among
     // equal values the lowest index.  Each thread scans every 256th entry in ascending order, then a tree over the workgroup.
@@ -265,9 +282,11 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_align_kernel(SbiAlignArgs g) 
         best = s_bi[0];
         best_ssd = s_bv[0];
     }
-    const float* __restrict__ tgt = g.tgt_tmpl + (size_t)(best > 0 ? best : 0) * n;
-    const float* __restrict__ tjac = g.tgt_jacs + (size_t)(best > 0 ? best : 0) * 2 * n;
-    for (int i = tid; i < n; i += SBI_THREADS) s_cur[i] = g.cur[i];
+    const SbiBatchRec* rec = g.recs ? g.recs + blockIdx.x : nullptr;
+    const float* __restrict__ tgt = rec ? rec->tgt_tmpl : g.tgt_tmpl + (size_t)(best > 0 ? best : 0) * n;
+    const float* __restrict__ tjac = rec ? rec->tgt_jacs : g.tgt_jacs + (size_t)(best > 0 ? best : 0) * 2 * n;
+    const float* __restrict__ cur = rec ? rec->tmpl : g.cur;
+    for (int i = tid; i < n; i += SBI_THREADS) s_cur[i] = cur[i];
     // thread 0's state
     double R2[4] = {1.0, 0.0, 0.0, 1.0}, t2[2] = {0.0, 0.0}, mean_offset = 0.0, score = 0.0;
     int done = 0, n_used = 0, degenerate = 0;
@@ -419,6 +438,18 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_align_kernel(SbiAlignArgs g) 
         o.n_used = n_used;
         o.degenerate = degenerate;
         o.pad_ = 0;
+        if (rec) {
+            // the frame's prediction (src/Tracker.cc:1013-1029 with mbUseSBIInit) where the rotation is: into the frame's pose for
+            // the PVS pass, and with the alignment into the frame's host-mapped block.  No sequence word of its own: the frame's
+            // last kernel, later on this queue, publishes one, and the fence below is passed before this kernel ends.
+            double pose[12];
+            motion_predict_sbi_hd(rec->velocity, rec->start_pose, o.rotation, pose);
+            for (int i = 0; i < 12; i++) rec->pose_out[i] = pose[i];
+            *rec->h_align = o;
+            for (int i = 0; i < 12; i++) rec->h_pose_in[i] = pose[i];
+            __threadfence_system();
+            return;
+        }
         g.out->a = o;
         g.out->best = best;
         g.out->pad_ = 0;
@@ -494,6 +525,25 @@ static int sbi_check_kf(const ptam_ctx* ctx, const SbiGeom& g, const ptam_kf* kf
     return PTAM_OK;
 }
 
+// exp(-i^2 / 2 sigma^2), normalised to sum 1
+static void sbi_make_weights(double blur, SbiMakeArgs* a) {
+    a->k = (int)std::ceil(3.0 * blur);
+    double sum = 0.0;
+    for (int i = -a->k; i <= a->k; i++) sum += (a->wt[i + a->k] = std::exp(-(double)(i * i) / (2.0 * blur * blur)));
+    for (int i = 0; i <= 2 * a->k; i++) a->wt[i] /= sum;
+    for (int i = 2 * a->k + 1; i <= 2 * SBI_MAX_TAPS; i++) a->wt[i] = 0.0;
+}
+// camera.SetImageSize(mirSize) + RefreshParams (src/ATANCamera.cc:21-40): focal and centre scale with the size
+static DevCam sbi_camera(const ptam_ctx* ctx, const SbiGeom& g) {
+    const ptam_cam_params& p = ctx->params;
+    DevCam c = ctx->cam;
+    c.width = g.w, c.height = g.h;
+    c.fx = g.w * p.fx, c.fy = g.h * p.fy;
+    c.cx = g.w * p.cx - 0.5, c.cy = g.h * p.cy - 0.5;
+    c.inv_fx = 1.0 / c.fx, c.inv_fy = 1.0 / c.fy;
+    return c;
+}
+
 // one launch for n images: image b from kf (n == 1) or from d_list[b], into im's arrays b images further on
 static int sbi_launch_make(ptam_ctx* ctx, const SbiGeom& g, const ptam_kf* kf, double blur, const SbiImage& im, int n = 1,
                            const uint8_t* const* d_list = nullptr) {
@@ -503,14 +553,10 @@ static int sbi_launch_make(ptam_ctx* ctx, const SbiGeom& g, const ptam_kf* kf, d
     SbiMakeArgs a;
     a.l3 = kf ? kf->L.im[3] : nullptr;
     a.l3_list = d_list;
+    a.recs = nullptr;
     a.w3 = g.w3, a.w = g.w, a.h = g.h;
-    a.k = (int)std::ceil(3.0 * blur);
     a.small = im.small, a.tmpl = im.tmpl, a.jacs = im.jacs;
-    // exp(-i^2 / 2 sigma^2), normalised to sum 1
-    double sum = 0.0;
-    for (int i = -a.k; i <= a.k; i++) sum += (a.wt[i + a.k] = std::exp(-(double)(i * i) / (2.0 * blur * blur)));
-    for (int i = 0; i <= 2 * a.k; i++) a.wt[i] /= sum;
-    for (int i = 2 * a.k + 1; i <= 2 * SBI_MAX_TAPS; i++) a.wt[i] = 0.0;
+    sbi_make_weights(blur, &a);
     if (ctx->halfsample == PTAM_HALFSAMPLE_T)
         hipLaunchKernelGGL(sbi_make_kernel<PTAM_HALFSAMPLE_T>, dim3(n), dim3(SBI_THREADS), 0, ctx->stream, a);
     else
@@ -531,14 +577,10 @@ static int sbi_align(ptam_ctx* ctx, const SbiGeom& g, const float* cur, const Sb
     a.ssd = bank ? bank->ssd : nullptr;
     a.count = bank ? bank->count : 0;
     a.w = g.w, a.h = g.h, a.iterations = iterations;
-    // camera.SetImageSize(mirSize) + RefreshParams (src/ATANCamera.cc:21-40): focal and centre scale with the size
-    const ptam_cam_params& p = ctx->params;
-    a.cam = ctx->cam;
-    a.cam.width = g.w, a.cam.height = g.h;
-    a.cam.fx = g.w * p.fx, a.cam.fy = g.h * p.fy;
-    a.cam.cx = g.w * p.cx - 0.5, a.cam.cy = g.h * p.cy - 0.5;
-    a.cam.inv_fx = 1.0 / a.cam.fx, a.cam.inv_fy = 1.0 / a.cam.fy;
+    a.cam = sbi_camera(ctx, g);
     a.out = (SbiOut*)((char*)ctx->d_pinned + pin_offset);
+    a.recs = nullptr;
+    a.det_items = nullptr, a.det_stride = a.det_off = 0, a.det_blocks = a.n_align = 0;
     a.seq = ++ctx->pose_seq;
     volatile SbiOut* h_out = (volatile SbiOut*)((char*)hp + pin_offset);
     h_out->seq = 0;   // (the staging buffer is shared: no stale sequence numbers)
@@ -573,6 +615,56 @@ void sbi_estimator_commit(ptam_rotation_estimator* e) {
     e->pending = -1;
 }
 ptam_ctx* sbi_estimator_ctx(const ptam_rotation_estimator* e) { return e->ctx; }
+
+// ---- the estimators' steps of a batch of frames: sbi_estimator_step's two launches, once for all frames ----
+int sbi_batch_rec(ptam_rotation_estimator* e, const ptam_kf* kf, SbiBatchRec* rec) {
+    const int cur = e->last < 0 ? 0 : 1 - e->last;
+    const ptam_sbi *c = e->slot[cur], *tgt = e->slot[e->last < 0 ? cur : e->last];
+    if (int rc = sbi_check_kf(e->ctx, c->g, kf)) return rc;
+    rec->l3 = kf->L.im[3];
+    rec->small = c->im.small, rec->tmpl = c->im.tmpl, rec->jacs = c->im.jacs;
+    rec->tgt_tmpl = tgt->im.tmpl, rec->tgt_jacs = tgt->im.jacs;
+    e->pending = cur;
+    return PTAM_OK;
+}
+void sbi_estimator_rollback(ptam_rotation_estimator* e) { e->pending = -1; }
+bool sbi_estimators_alike(const ptam_rotation_estimator* a, const ptam_rotation_estimator* b) {
+    return a->blur == b->blur && a->slot[0]->g.fw == b->slot[0]->g.fw && a->slot[0]->g.fh == b->slot[0]->g.fh;
+}
+int sbi_batch_launch_make(const ptam_rotation_estimator* lead, int n, const SbiBatchRec* d_recs, hipStream_t st) {
+    const SbiGeom& g = lead->slot[0]->g;
+    SbiMakeArgs a;
+    a.l3 = nullptr, a.l3_list = nullptr, a.recs = d_recs;
+    a.w3 = g.w3, a.w = g.w, a.h = g.h;
+    a.small = nullptr, a.tmpl = nullptr, a.jacs = nullptr;
+    sbi_make_weights(lead->blur, &a);
+    if (lead->ctx->halfsample == PTAM_HALFSAMPLE_T)
+        hipLaunchKernelGGL(sbi_make_kernel<PTAM_HALFSAMPLE_T>, dim3(n), dim3(SBI_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL(sbi_make_kernel<PTAM_HALFSAMPLE_R>, dim3(n), dim3(SBI_THREADS), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+int sbi_batch_launch_align(const ptam_rotation_estimator* lead, int n, const SbiBatchRec* d_recs, hipStream_t st, int nb_detect, const KfLevels* L,
+                           const void* det_items, size_t det_stride, size_t det_off) {
+    const SbiGeom& g = lead->slot[0]->g;
+    SbiAlignArgs a;
+    a.cur = a.tgt_tmpl = a.tgt_jacs = nullptr;
+    a.ssd = nullptr;
+    a.count = 0;
+    a.w = g.w, a.h = g.h, a.iterations = 6;   // (sbi_estimator_step's)
+    a.cam = sbi_camera(lead->ctx, g);
+    a.out = nullptr;
+    a.seq = 0;
+    a.recs = d_recs;
+    a.det_items = nb_detect > 0 ? (const char*)det_items : nullptr;
+    a.det_stride = det_stride, a.det_off = det_off;
+    a.det_blocks = nb_detect > 0 ? fast_detect_tall_blocks(*L) : 0;
+    a.n_align = n;
+    hipLaunchKernelGGL(sbi_align_kernel, dim3(n + nb_detect * a.det_blocks), dim3(SBI_THREADS), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
 
 extern "C" {
 
@@ -746,6 +838,34 @@ int ptam_relocalise(ptam_sbi_bank* b, ptam_sbi* scratch, const ptam_kf* current,
         out->pose[9 + i] = R[3 * i] * K[9] + R[3 * i + 1] * K[10] + R[3 * i + 2] * K[11];
     }
     out->good = r.a.score < max_score ? 1 : 0;
+    return PTAM_OK;
+}
+
+__global__ __launch_bounds__(256) void motion_predict_sbi_kernel(int n, const ptam_motion_model* __restrict__ models, const double* __restrict__ rot,
+                                                                 double* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double R[9], pose[12];
+    for (int k = 0; k < 9; k++) R[k] = rot[(size_t)i * 9 + k];
+    motion_predict_sbi_hd(models[i].velocity, models[i].pose, R, pose);
+    for (int k = 0; k < 12; k++) out[(size_t)i * 12 + k] = pose[k];
+}
+
+int ptam_motion_predict_sbi_dev(ptam_ctx* ctx, int n, const ptam_motion_model* models, const double* rotations9, double* poses_out12) {
+    ARG_TRY(ctx && n >= 1 && n <= (1 << 20) && models && rotations9 && poses_out12);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t b_m = sbi_up256((size_t)n * sizeof(ptam_motion_model)), b_r = sbi_up256((size_t)n * 72), b_o = (size_t)n * 96;
+    HIP_TRY(ptam_stream_wait(ctx->stream));   // (the scratch is nobody's)
+    void* sc;
+    if (int rc = ctx_scratch(ctx, b_m + b_r + b_o, &sc)) return rc;
+    char* b = (char*)sc;
+    HIP_TRY(hipMemcpy(b, models, (size_t)n * sizeof(ptam_motion_model), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b + b_m, rotations9, (size_t)n * 72, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(motion_predict_sbi_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, (const ptam_motion_model*)b,
+                       (const double*)(b + b_m), (double*)(b + b_m + b_r));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(poses_out12, b + b_m + b_r, b_o, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ptam_stream_wait(ctx->stream));
     return PTAM_OK;
 }
 

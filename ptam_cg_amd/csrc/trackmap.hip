@@ -20,6 +20,7 @@
 #include <climits>
 
 #include "track_internal.h"
+#include "sbi.h"                  // ptam_track_frames_batch: the estimators' steps of a batch
 #include "snapshot_internal.h"    // ptam_map_snapshot: ptam_tracker_take_map copies its current slot
 #include "wait_mapped.h"
 #include "../../include/ptam_hip_bench.h"
@@ -473,6 +474,10 @@ struct TmMailbox {
     ptam_trackmap_result res;
     double depth3[3];
     unsigned long long seq;
+    // ptam_track_frames_batch, a frame with a rotation estimator: the alignment and the pose predicted from it, written by the
+    // frame's align workgroup (sbi.hip) — covered by the sequence word, which a later kernel of the same queue publishes
+    ptam_sbi_alignment align;
+    double pose_in[12];
 };
 // the last act of a gather pass: thread 0 books the per-level counts and the stage's outcome (coarse: mbDidCoarse and the
 // fine range; fine: everything of the frame's result but the pose and the depth sums)
@@ -820,8 +825,12 @@ struct TmBatchItem {
     int n_pyr, n;          // pyramid workgroups (gx * gy), map points
     KfLevels L;
     TmDev d;
-    PoseArg pv;
+    PoseArg pv;            // use = 0: the pose is made on the device (ptam_track_frames_batch, a frame with a rotation estimator) —
+                           // the PVS pass then runs behind the align workgroup, in tm_pvs_batch_kernel
     TmMailbox* mbox;
+    // the frame's own bTryCoarse heuristics (src/Tracker.cc:503-514); ptam_track_map_frames_batch fills every frame with its one opts
+    int try_coarse;
+    unsigned coarse_max, coarse_range;
 };
 template <int VARIANT>
 __global__ void __launch_bounds__(256) tm_pyr_pvs_batch_kernel(const TmBatchItem* __restrict__ items, int gx, DevCam cam) {
@@ -829,20 +838,28 @@ __global__ void __launch_bounds__(256) tm_pyr_pvs_batch_kernel(const TmBatchItem
     const int b = blockIdx.x;
     if (b < it.n_pyr)
         pyramid_body<VARIANT>(it.pa, (b % gx) * 64 + (threadIdx.x & 63), (b / gx) * 4 + (threadIdx.x >> 6));
-    else if ((b - it.n_pyr) * 256 < max(it.n, 1))
+    else if (it.pv.use && (b - it.n_pyr) * 256 < max(it.n, 1))
         track_pvs_body(cam, it.n, it.d.pts, it.d.pose, it.d.pvs, nullptr, it.pv, it.d.pose, b - it.n_pyr, &it.d.finder->bad, (int)sizeof(TmFinder));
+}
+// the PVS pass of the frames whose pose was made on the device: row y works on frame idx[y], the pose is read from the frame's d.pose
+__global__ void __launch_bounds__(256) tm_pvs_batch_kernel(const TmBatchItem* __restrict__ items, const int* __restrict__ idx, DevCam cam) {
+    const TmBatchItem& it = items[idx[blockIdx.y]];
+    if ((int)blockIdx.x * 256 < max(it.n, 1))
+        track_pvs_body(cam, it.n, it.d.pts, it.d.pose, it.d.pvs, nullptr, it.pv, it.d.pose, blockIdx.x, &it.d.finder->bad, (int)sizeof(TmFinder));
 }
 __global__ void __launch_bounds__(1024) tm_compact_select_batch_kernel(const TmBatchItem* __restrict__ items, ptam_trackmap_opts o) {
     const TmBatchItem& it = items[blockIdx.y];
-    if (blockIdx.x == 0)
+    if (blockIdx.x == 0) {
+        o.try_coarse = it.try_coarse;
+        o.coarse_max = it.coarse_max;
+        o.coarse_range = it.coarse_range;
         tm_select_body(it.d, o);
-    else
+    } else
         fast_compact_body(it.L, blockIdx.x - 1, 0);
 }
-__global__ void __launch_bounds__(256) tm_search_batch_kernel(DevCam cam, const TmBatchItem* __restrict__ items, int stage, unsigned coarse_range,
-                                                              int coarse_its) {
+__global__ void __launch_bounds__(256) tm_search_batch_kernel(DevCam cam, const TmBatchItem* __restrict__ items, int stage, int coarse_its) {
     const TmBatchItem& it = items[blockIdx.y];
-    tm_search_body(cam, it.L, it.d, stage, coarse_range, coarse_its, blockIdx.x);
+    tm_search_body(cam, it.L, it.d, stage, it.coarse_range, coarse_its, blockIdx.x);
 }
 __global__ void __launch_bounds__(TM_GATHER_THREADS) tm_gather_batch_kernel(const TmBatchItem* __restrict__ items, int stage, int coarse_its,
                                                                             unsigned coarse_min) {
@@ -850,15 +867,17 @@ __global__ void __launch_bounds__(TM_GATHER_THREADS) tm_gather_batch_kernel(cons
     tm_gather_body(it.d, stage, coarse_its, coarse_min, it.mbox, blockIdx.x);
 }
 // the fused bookkeeping + pose loop (tm_pose_body) for the frames of a batch: one workgroup per frame; io and scratch of the frame's
-// stage come from the pose items the unfused path uses
+// stage come from the pose items the unfused path uses.  idx (nullable): workgroup x works on frame idx[x] — the frames whose lists
+// select this instantiation (ptam_track_frames_batch).  A fine list that outgrows the kernel is told to the host, as in the single frame.
 template <int MPT, int THREADS>
 __global__ void __launch_bounds__(THREADS) tm_pose_batch_kernel(DevCam cam, const TmBatchItem* __restrict__ items, const PoseBatchItem* __restrict__ pitems,
-                                                                int stage, unsigned coarse_min, ptam_gn_opts opts) {
-    const TmBatchItem& it = items[blockIdx.x];
-    const PoseBatchItem& pi = pitems[blockIdx.x];
-    tm_pose_body<MPT, THREADS>(cam, it.d, stage, coarse_min, it.mbox, opts, pi.io, pi.updates, 0ull);
+                                                                const int* __restrict__ idx, int stage, unsigned coarse_min, ptam_gn_opts opts) {
+    const int f = idx ? idx[blockIdx.x] : (int)blockIdx.x;
+    const TmBatchItem& it = items[f];
+    const PoseBatchItem& pi = pitems[f];
+    tm_pose_body<MPT, THREADS>(cam, it.d, stage, coarse_min, it.mbox, opts, pi.io, pi.updates, stage == 1 && it.n > GS_LIMIT ? pi.io.seq : 0ull);
 }
-typedef void (*tm_pose_batch_fn)(DevCam, const TmBatchItem*, const PoseBatchItem*, int, unsigned, ptam_gn_opts);
+typedef void (*tm_pose_batch_fn)(DevCam, const TmBatchItem*, const PoseBatchItem*, const int*, int, unsigned, ptam_gn_opts);
 static const tm_pose_batch_fn tm_pose_batch_fns[3] = {tm_pose_batch_kernel<1, GS_WAVE_LIMIT>, tm_pose_batch_kernel<1, GS_THREADS>,
                                                       tm_pose_batch_kernel<GS_MPT, GS_THREADS>};
 
@@ -896,6 +915,8 @@ struct ptam_tracker {
 // (A/B builds, `make ab`: the pyramid | FAST as two launches; the gather pass + pose kernel of rounds 2-3 instead of the fused one)
 static const bool tm_kf_two = ptam_ab_env("PTAM_TM_KF_TWO_LAUNCHES") != nullptr;
 static const bool tm_no_fuse = ptam_ab_env("PTAM_TM_NO_FUSE") != nullptr;
+// (ptam_track_frames_batch: the FAST detection as a launch of its own in front of the images' make instead of inside the align launch)
+static const bool tfb_plain = ptam_ab_env("PTAM_TFB_PLAIN") != nullptr;
 
 // the instantiation of a kernel template for the context's halfSample variant
 #define TM_HS_KERNEL(ctx, kernel) ((ctx)->halfsample == PTAM_HALFSAMPLE_T ? kernel<PTAM_HALFSAMPLE_T> : kernel<PTAM_HALFSAMPLE_R>)
@@ -953,6 +974,43 @@ static void tm_read_result(const ptam_tracker* t, ptam_trackmap_result* out) {
     out->depth_sum = t->mbox->depth3[0];
     out->depth_sum_sq = t->mbox->depth3[1];
     out->depth_n = (int)t->mbox->depth3[2];
+}
+
+// Wait for frame `seq` of t, whose chain was enqueued on `st` (the tracker's own queue, or a batch's): the frame's last kernel
+// publishes the sequence number — or, for a list of more than 1024 entries, asks for the general path, which the tracker's own queue
+// then runs and which publishes it.  fused: the fine stage went out as the fused bookkeeping + pose kernel.
+static int tm_wait_frame(ptam_tracker* t, hipStream_t st, const ptam_trackmap_opts& o, unsigned long long seq, bool fused) {
+    ptam_ctx* ctx = t->ctx;
+    const TmDev& d = t->d;
+    const int n = d.n, n_fine = std::max(n, 1);
+    const ptam_gn_opts g = tm_gn_opts(1, o.estimator);
+    const PoseChainIo io = tm_chain_io(t, 1, seq);
+    auto fine_chain = [&](int mode) { return pose_launch_chain(ctx, n_fine, &d.ctl->n_meas, d.meas, d.entry, d.pose, &g, d.outlier, io, mode); };
+    for (int pass = 0; pass < 3; pass++) {
+        unsigned long long v;
+        int rc = tm_wait_seq(t, st, seq, "the frame's result", &v);
+        if (rc) return rc;
+        if (!(v & POSE_CHAIN_LONG)) break;
+        if (pass == 2) return PTAM_E_STATE;
+        if (st != ctx->stream) {   // (a batch: the other frames' kernels still run there, and this frame goes on on its own queue)
+            HIP_TRY(ptam_stream_wait(st));
+            st = ctx->stream;
+        }
+        t->mbox->seq = 0;   // (the stream is idle: nobody else writes the word until the next kernel does)
+        if (fused) {
+            // more slots than the fused kernel holds: compact them, then the register-resident kernel if the FOUND ones fit
+            // (it says so otherwise: next pass)
+            fused = false;
+            hipLaunchKernelGGL(tm_gather_kernel, dim3(std::max(1, (n + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS)), dim3(TM_GATHER_THREADS), 0, st, d, 1,
+                               o.coarse_subpix_its, o.coarse_min, t->mbox_dev);
+            rc = fine_chain(1);
+        } else {
+            rc = fine_chain(2);
+        }
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+    }
+    return PTAM_OK;
 }
 
 ptam_ctx* tracker_ctx(const ptam_tracker* t) { return t->ctx; }
@@ -1446,7 +1504,7 @@ static int track_map_impl(ptam_tracker* t, ptam_kf* cur, const uint8_t* d_new_fr
     g = tm_gn_opts(1, o.estimator);
     io = tm_chain_io(t, 1, seq);
     auto fine_chain = [&](int mode) { return pose_launch_chain(ctx, n_fine, &d.ctl->n_meas, d.meas, d.entry, d.pose, &g, d.outlier, io, mode); };
-    bool fused = !tm_no_fuse;
+    const bool fused = !tm_no_fuse;
     if (fused) {
         // bookkeeping + the ten fine iterations in one launch.  The iteration set holds at most max(MaxPatchesPerFrame, coarse
         // + top-level set) slots: with more than the kernel's 1024 it says so instead (POSE_CHAIN_LONG) and the gather pass
@@ -1462,27 +1520,8 @@ static int track_map_impl(ptam_tracker* t, ptam_kf* cur, const uint8_t* d_new_fr
     }
     mark(PTAM_TS_COUNT);
     HIP_TRY(hipGetLastError());
-    // ---- wait: the frame's last kernel publishes the sequence number — or, for a list of more than 1024 entries, asks for the
-    // general path, which then publishes it ----
-    for (int pass = 0; pass < 3; pass++) {
-        unsigned long long v;
-        rc = tm_wait_seq(t, st, seq, "the frame's result", &v);
-        if (rc) return rc;
-        if (!(v & POSE_CHAIN_LONG)) break;
-        if (pass == 2) return PTAM_E_STATE;
-        t->mbox->seq = 0;   // (the stream is idle: nobody else writes the word until the next kernel does)
-        if (fused) {
-            // more slots than the fused kernel holds: compact them, then the register-resident kernel if the FOUND ones fit
-            // (it says so otherwise: next pass)
-            fused = false;
-            gather(n, 1);
-            rc = fine_chain(1);
-        } else {
-            rc = fine_chain(2);
-        }
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
-    }
+    rc = tm_wait_frame(t, st, o, seq, fused);
+    if (rc) return rc;
     // ---- result ----
     tm_read_result(t, out);
     if (prof) {
@@ -1603,6 +1642,7 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
         std::memcpy(it.pv.v, poses_in + 12 * (size_t)i, 96);
         it.pv.use = 1;
         it.mbox = t->mbox_dev;
+        it.try_coarse = o.try_coarse, it.coarse_max = o.coarse_max, it.coarse_range = o.coarse_range;
         const int n = t->d.n, ncc = std::max(1, std::min(n, (int)o.coarse_max));
         n_max = std::max(n_max, n);
         ncc_max = std::max(ncc_max, ncc);
@@ -1630,22 +1670,22 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
     const bool fuse = !tm_no_fuse && n_max <= GS_LIMIT && ncc_max <= GS_LIMIT;
     int thr;
     // ---- coarse stage :519-569 ----
-    hipLaunchKernelGGL(tm_search_batch_kernel, dim3((ncc_max + 3) / 4, nb), dim3(256), 0, st, ctx->cam, d_it, 0, o.coarse_range, o.coarse_subpix_its);
+    hipLaunchKernelGGL(tm_search_batch_kernel, dim3((ncc_max + 3) / 4, nb), dim3(256), 0, st, ctx->cam, d_it, 0, o.coarse_subpix_its);
     ptam_gn_opts g = tm_gn_opts(0, o.estimator);
     if (fuse) {
         const tm_pose_batch_fn fn = tm_pose_batch_fns[tm_pose_shape(ncc_max, &thr)];
-        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_pc, 0, o.coarse_min, g);
+        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_pc, (const int*)nullptr, 0, o.coarse_min, g);
     } else {
         gather(ncc_max, 0);
         rc = pose_launch_chain_batch(ctx, nb, ncc_max, d_pc, &g);
         if (rc) return rc;
     }
     // ---- fine stage :571-643 ----
-    hipLaunchKernelGGL(tm_search_batch_kernel, dim3(std::max(1, (n_max + 3) / 4), nb), dim3(256), 0, st, ctx->cam, d_it, 1, 0u, 0);
+    hipLaunchKernelGGL(tm_search_batch_kernel, dim3(std::max(1, (n_max + 3) / 4), nb), dim3(256), 0, st, ctx->cam, d_it, 1, 0);
     g = tm_gn_opts(1, o.estimator);
     if (fuse) {
         const tm_pose_batch_fn fn = tm_pose_batch_fns[tm_pose_shape(n_fine, &thr)];
-        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_pf, 1, o.coarse_min, g);
+        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_pf, (const int*)nullptr, 1, o.coarse_min, g);
     } else {
         gather(n_max, 1);
         rc = pose_launch_chain_batch(ctx, nb, n_fine, d_pf, &g);
@@ -1661,6 +1701,247 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
             return rc;
         }
         tm_read_result(ts[i], outs + i);
+    }
+    return PTAM_OK;
+}
+
+
+// ---- Tracker::TrackFrame's tracking branch (src/Tracker.cc:94-108, :134-137, :1013-1056) for nb cameras in ONE chain ----
+// ptam_track_map_frames_batch with what ptam_track_frame / ptam_track_frame_sbi put around TrackMap: the bTryCoarse heuristics per
+// camera (each frame's TmBatchItem carries its own), the motion model, and — for a frame with a rotation estimator — this frame's
+// SmallBlurryImage, its alignment against last frame's and the prediction from the rotation, all on the device: the align workgroup's
+// thread 0 writes the pose the PVS pass then reads.  The chain (docs/LOG_sbi.md has the arrangements that were measured):
+//   pyramid | PVS of the frames the host predicted  ->  SBI make  ->  align + predict | FAST detect  ->  PVS of the aligned frames
+//   ->  set choice | corner compaction  ->  search, pose (coarse)  ->  search, pose (fine)
+// Every frame's pose loops run in the kernel instantiation its OWN list lengths select (the frames of one instantiation share a
+// launch), so a frame's result is the single call's bit for bit; a fine list that outgrows the fused kernel is finished on the
+// frame's own queue after the wait, as in the single call.
+int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_motion_model* models,
+                            ptam_rotation_estimator* const* ests, const ptam_trackmap_opts* opts, ptam_trackmap_result* outs,
+                            ptam_track_frame_info* info) {
+    // ---- everything that needs no device ----
+    ARG_TRY(nb >= 1 && nb <= 4096 && ts && curs && d_frames && models && outs);
+    for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i] && d_frames[i]);
+    ptam_trackmap_opts o;
+    int rc = tm_opts(opts, &o);
+    if (rc) return rc;
+    ptam_tracker* lead = ts[0];
+    ptam_ctx* ctx = lead->ctx;
+    const KfLevels& L0 = curs[0]->L;
+    for (int i = 0; i < nb; i++) {
+        ARG_TRY(ts[i]->ctx->device == ctx->device && curs[i]->device == ctx->device);
+        ARG_TRY(ts[i]->ctx->halfsample == ctx->halfsample && std::memcmp(&ts[i]->ctx->cam, &ctx->cam, sizeof(DevCam)) == 0);
+        ARG_TRY(curs[i]->n_blocks == curs[0]->n_blocks);
+        for (int l = 0; l < PTAM_LEVELS; l++) ARG_TRY(curs[i]->L.w[l] == L0.w[l] && curs[i]->L.h[l] == L0.h[l]);
+        for (int j = 0; j < i; j++) ARG_TRY(ts[j] != ts[i] && curs[j] != curs[i] && ts[j]->ctx != ts[i]->ctx);   // (a context's scratch serves ONE frame)
+    }
+    // the estimators: each its tracker's context's, none twice, all of one image size and blur (their images are made in one launch)
+    std::vector<int> est_of;   // the frames that have one
+    for (int i = 0; ests && i < nb; i++) {
+        if (!ests[i]) continue;
+        ARG_TRY(sbi_estimator_ctx(ests[i]) == ts[i]->ctx);
+        for (int j : est_of) ARG_TRY(ests[j] != ests[i]);
+        if (!est_of.empty()) ARG_TRY(sbi_estimators_alike(ests[est_of[0]], ests[i]));
+        est_of.push_back(i);
+    }
+    const int n_est = (int)est_of.size();
+    // the heuristics, per frame, as ptam_track_frame has them (src/Tracker.cc:503-514); the models advance on copies
+    std::vector<ptam_motion_model> tmp(models, models + nb);
+    std::vector<ptam_trackmap_opts> fo((size_t)nb, o);
+    for (int i = 0; i < nb; i++) {
+        ptam_motion_model& m = tmp[(size_t)i];
+        ptam_trackmap_opts& f = fo[(size_t)i];
+        f.try_coarse = 1;
+        if (m.disable_coarse || m.msd_scaled_velocity < m.coarse_min_velocity || f.coarse_max == 0) f.try_coarse = 0;
+        if (m.just_recovered) {
+            f.try_coarse = 1;
+            f.coarse_max *= 2;
+            f.coarse_range *= 2;
+            m.just_recovered = 0;
+            ptam_trackmap_opts checked;
+            rc = tm_opts(&f, &checked);   // (the doubled values, as TrackMap checks them in the single call)
+            if (rc) return rc;
+        }
+        if (ests && ests[i]) std::memcpy(m.start_pose, m.pose, 96);   // (the device makes the pose: ptam_motion_predict_sbi's first line)
+        else ptam_motion_predict(&m);
+    }
+    // ---- from here on an error leaves through fail(): the estimators are where they were ----
+    auto fail = [&](int code) {
+        for (int i : est_of) sbi_estimator_rollback(ests[i]);
+        return code;
+    };
+#define TFB_HIP_TRY(expr)                                                          \
+    do {                                                                           \
+        const hipError_t e_ = (expr);                                              \
+        if (e_ != hipSuccess) {                                                    \
+            ptam_set_error("HIP error: %s (%s)", hipGetErrorString(e_), #expr);    \
+            return fail(PTAM_E_HIP);                                               \
+        }                                                                          \
+    } while (0)
+    TFB_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    for (int i = 1; i < nb; i++)
+        if (ts[i]->ctx != ctx) TFB_HIP_TRY(ptam_stream_wait(ts[i]->ctx->stream));
+    // ---- the argument arrays: [nb TmBatchItem | nb PoseBatchItem (coarse) | nb (fine) | n_est SbiBatchRec | 3 nb frame indices] ----
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_items = up((size_t)nb * sizeof(TmBatchItem)), b_pose = up((size_t)nb * sizeof(PoseBatchItem)),
+                 b_rec = up((size_t)std::max(n_est, 1) * sizeof(SbiBatchRec)), b_idx = up((size_t)nb * 4);
+    const size_t b_all = b_items + 2 * b_pose + b_rec + 3 * b_idx;
+    void* pin;
+    rc = ctx_pinned(ctx, b_all + 64, &pin);
+    if (rc) return fail(rc);
+    if (lead->batch_cap < b_all) {
+        TFB_HIP_TRY(ptam_stream_wait(st));
+        if (lead->batch_dev) TFB_HIP_TRY(hipFree(lead->batch_dev));
+        lead->batch_dev = nullptr;
+        lead->batch_cap = 0;
+        TFB_HIP_TRY(hipMalloc(&lead->batch_dev, b_all * 2));
+        lead->batch_cap = b_all * 2;
+    }
+    char* hb = (char*)pin;
+    const char* db = (const char*)lead->batch_dev;
+    TmBatchItem* h_it = (TmBatchItem*)hb;
+    PoseBatchItem* h_pc = (PoseBatchItem*)(hb + b_items);
+    PoseBatchItem* h_pf = (PoseBatchItem*)(hb + b_items + b_pose);
+    SbiBatchRec* h_rec = (SbiBatchRec*)(hb + b_items + 2 * b_pose);
+    int* h_idx = (int*)(hb + b_items + 2 * b_pose + b_rec);   // [est frames | coarse stage by instantiation | fine stage by instantiation]
+    const size_t idx_stride = b_idx / 4;
+    const TmBatchItem* d_it = (const TmBatchItem*)db;
+    const PoseBatchItem* d_pc = (const PoseBatchItem*)(db + b_items);
+    const PoseBatchItem* d_pf = (const PoseBatchItem*)(db + b_items + b_pose);
+    const SbiBatchRec* d_rec = (const SbiBatchRec*)(db + b_items + 2 * b_pose);
+    const int* d_idx = (const int*)(db + b_items + 2 * b_pose + b_rec);
+    int gx = 0, gy = 0, n_max = 0, ncc_max = 1;
+    std::vector<int> shape_c((size_t)nb), shape_f((size_t)nb);
+    std::vector<unsigned long long> seqs((size_t)nb);
+    int thr;
+    for (int i = 0; i < nb; i++) {
+        ptam_tracker* t = ts[i];
+        const ptam_trackmap_opts& f = fo[(size_t)i];
+        TmBatchItem& it = h_it[i];
+        std::memset(&it, 0, sizeof it);
+        kf_lite_begin(curs[i], d_frames[i], &it.pa, &gx, &gy);
+        it.n_pyr = gx * gy;
+        it.n = t->d.n;
+        it.L = curs[i]->L;
+        it.d = t->d;
+        it.mbox = t->mbox_dev;
+        it.try_coarse = f.try_coarse, it.coarse_max = f.coarse_max, it.coarse_range = f.coarse_range;
+        if (!(ests && ests[i])) {
+            std::memcpy(it.pv.v, tmp[(size_t)i].pose, 96);
+            it.pv.use = 1;
+        }
+        const int n = t->d.n, ncc = std::max(1, std::min(n, (int)f.coarse_max));
+        n_max = std::max(n_max, n);
+        ncc_max = std::max(ncc_max, ncc);
+        shape_c[(size_t)i] = tm_pose_shape(std::min(ncc, GS_LIMIT), &thr);
+        shape_f[(size_t)i] = tm_pose_shape(std::min(std::max(n, 1), GS_LIMIT), &thr);
+        void* sst;
+        double* su;
+        rc = pose_chain_scratch(t->ctx, std::max(n, 1), &sst, &su);
+        if (rc) return fail(rc);
+        seqs[(size_t)i] = t->seq + 1;
+        h_pc[i] = tm_pose_item(t, 0, ncc, su, sst, 0);
+        h_pf[i] = tm_pose_item(t, 1, std::max(n, 1), su, sst, seqs[(size_t)i]);
+    }
+    for (int k = 0; k < n_est; k++) {
+        const int i = est_of[(size_t)k];
+        SbiBatchRec& r = h_rec[k];
+        std::memset(&r, 0, sizeof r);
+        rc = sbi_batch_rec(ests[i], curs[i], &r);
+        if (rc) return fail(rc);
+        std::memcpy(r.velocity, tmp[(size_t)i].velocity, sizeof r.velocity);
+        std::memcpy(r.start_pose, tmp[(size_t)i].start_pose, sizeof r.start_pose);
+        r.pose_out = ts[i]->d.pose;
+        r.h_align = &ts[i]->mbox_dev->align;
+        r.h_pose_in = ts[i]->mbox_dev->pose_in;
+        h_idx[k] = i;
+    }
+    // the frames of every pose-kernel instantiation, stage by stage: n_shape[stage][k] frames from first[stage][k] on
+    int n_shape[2][3] = {{0, 0, 0}, {0, 0, 0}}, first[2][3];
+    for (int sg = 0; sg < 2; sg++) {
+        const std::vector<int>& sh = sg ? shape_f : shape_c;
+        int at = 0;
+        for (int k = 0; k < 3; k++) {
+            first[sg][k] = at;
+            for (int i = 0; i < nb; i++)
+                if (sh[(size_t)i] == k) h_idx[(size_t)(1 + sg) * idx_stride + (size_t)at++] = i;
+            n_shape[sg][k] = at - first[sg][k];
+        }
+    }
+    for (int i = 0; i < nb; i++) {
+        ts[i]->seq = seqs[(size_t)i];
+        ts[i]->last_stream = st;
+    }
+    TFB_HIP_TRY(hipMemcpyAsync(lead->batch_dev, pin, b_all, hipMemcpyHostToDevice, st));
+    // ---- keyframe, the estimators' steps, PVS, set choice ----
+    const int n_pyr = gx * gy, n_pvs = std::max(1, (n_max + 255) / 256);
+    hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_pyr_pvs_batch_kernel), dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, gx, ctx->cam);
+    // (the detection shares the align launch: its workgroups fill the chip under the align workgroups' ~100 us of serial chain, and
+    //  a launch boundary goes — 6-9 % per frame up to 64 cameras, 2-4 % slower at 128; docs/LOG_sbi.md)
+    const bool share = !tfb_plain && n_est > 0;
+    if (!share) kf_launch_detect_batch(nb, L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L), st);
+    if (n_est > 0) {
+        rc = sbi_batch_launch_make(ests[est_of[0]], n_est, d_rec, st);
+        if (!rc && share) rc = sbi_batch_launch_align(ests[est_of[0]], n_est, d_rec, st, nb, &L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L));
+        else if (!rc) rc = sbi_batch_launch_align(ests[est_of[0]], n_est, d_rec, st);
+        if (rc) return fail(rc);
+        hipLaunchKernelGGL(tm_pvs_batch_kernel, dim3(n_pvs, n_est), dim3(256), 0, st, d_it, d_idx, ctx->cam);
+    }
+    hipLaunchKernelGGL(tm_compact_select_batch_kernel, dim3(1 + fast_compact_blocks(L0), nb), dim3(1024), 0, st, d_it, o);
+    // ---- the two stages ----
+    // (per-frame instantiations when every coarse list fits the fused kernels; otherwise — a CoarseMax above 1024 — the gather pass
+    //  and the small / general kernel pair for everybody, as ptam_track_map_frames_batch does it: results then equal the single
+    //  calls' to rounding)
+    const bool grouped = !tm_no_fuse && ncc_max <= GS_LIMIT;
+    static const int shape_threads[3] = {GS_WAVE_LIMIT, GS_THREADS, GS_THREADS};
+    auto gather = [&](int cap, int stage) {
+        hipLaunchKernelGGL(tm_gather_batch_kernel, dim3(std::max(1, (cap + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS), nb), dim3(TM_GATHER_THREADS), 0, st,
+                           d_it, stage, (int)o.coarse_subpix_its, o.coarse_min);
+    };
+    for (int sg = 0; sg < 2; sg++) {
+        const int cap = sg ? std::max(n_max, 1) : ncc_max;
+        hipLaunchKernelGGL(tm_search_batch_kernel, dim3(std::max(1, (cap + 3) / 4), nb), dim3(256), 0, st, ctx->cam, d_it, sg, sg ? 0 : (int)o.coarse_subpix_its);
+        const ptam_gn_opts g = tm_gn_opts(sg, o.estimator);
+        if (grouped) {
+            for (int k = 0; k < 3; k++)
+                if (n_shape[sg][k] > 0)
+                    hipLaunchKernelGGL(tm_pose_batch_fns[k], dim3(n_shape[sg][k]), dim3(shape_threads[k]), 0, st, ctx->cam, d_it, sg ? d_pf : d_pc,
+                                       d_idx + (size_t)(1 + sg) * idx_stride + first[sg][k], sg, o.coarse_min, g);
+        } else {
+            gather(sg ? n_max : ncc_max, sg);
+            rc = pose_launch_chain_batch(ctx, nb, cap, sg ? d_pf : d_pc, &g);
+            if (rc) return fail(rc);
+        }
+    }
+    TFB_HIP_TRY(hipGetLastError());
+#undef TFB_HIP_TRY
+    // ---- wait + result, frame by frame; then, every frame having arrived, the models and the estimators move ----
+    for (int i = 0; i < nb; i++) {
+        rc = tm_wait_frame(ts[i], st, o, seqs[(size_t)i], grouped);
+        if (rc) {
+            const std::string e = ptam_last_error();
+            ptam_set_error("frame %d of the batch: %s", i, e.c_str());
+            return fail(rc);
+        }
+        tm_read_result(ts[i], outs + i);
+    }
+    for (int i = 0; i < nb; i++) {
+        ptam_motion_model& m = tmp[(size_t)i];
+        const bool est = ests && ests[i];
+        if (est) std::memcpy(m.pose, (const void*)ts[i]->mbox->pose_in, 96);
+        if (info) {
+            ptam_track_frame_info& fi = info[i];
+            std::memset(&fi, 0, sizeof fi);
+            std::memcpy(fi.pose_in, m.pose, 96);
+            if (est) std::memcpy(&fi.align, (const void*)&ts[i]->mbox->align, sizeof fi.align);
+            fi.try_coarse = fo[(size_t)i].try_coarse;
+            fi.coarse_max = fo[(size_t)i].coarse_max;
+            fi.coarse_range = fo[(size_t)i].coarse_range;
+        }
+        ptam_motion_update(&m, outs + i);
+        models[i] = m;
+        if (est) sbi_estimator_commit(ests[i]);
     }
     return PTAM_OK;
 }
@@ -1741,4 +2022,5 @@ void trackmap_preload_kernels() {
     ptam_preload((const void*)tm_compact_select_batch_kernel);
     ptam_preload((const void*)tm_search_batch_kernel);
     ptam_preload((const void*)tm_gather_batch_kernel);
+    ptam_preload((const void*)tm_pvs_batch_kernel);
 }

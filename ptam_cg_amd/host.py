@@ -1280,6 +1280,30 @@ class Tracker:
                       "track_map_frames_batch")
         return res
 
+    @staticmethod
+    def track_frames_batch(trackers, kfs, d_frames, models, estimators=None, opts=None):
+        """ptam_track_frames_batch: Tracker::TrackFrame's tracking branch for len(trackers) cameras in one chain of launches — per
+        camera the motion model (`models`, updated in place), the bTryCoarse heuristics and, where estimators[i] is not None, the
+        SmallBlurryImage rotation estimator -> (array of TRACKMAP_RESULT_DT, list of dict(pose_in, align, try_coarse, coarse_max,
+        coarse_range)).  An error leaves models and estimators as they were."""
+        k = len(trackers)
+        raw = lambda h: h.value if hasattr(h, "value") else int(h)
+        trs = (C.c_void_p * k)(*[raw(t.h) for t in trackers])
+        kf_ = (C.c_void_p * k)(*[raw(f.h) for f in kfs])
+        dis = (C.c_void_p * k)(*[raw(d.p if isinstance(d, DevBuf) else d) for d in d_frames])
+        es = None if estimators is None else (C.c_void_p * k)(*[None if e is None else raw(e.h) for e in estimators])
+        mm = (MotionModel * k)(*models)      # (a contiguous copy: written back on success only)
+        res = np.zeros(k, dtype=TRACKMAP_RESULT_DT)
+        inf = (_abi.TrackFrameInfo * k)()
+        t0 = trackers[0]
+        t0.ctx._check(t0.lib.track_frames_batch(k, trs, kf_, dis, mm, es, _ptr(opts) if opts is not None else None, _ptr(res), inf),
+                      "track_frames_batch")
+        for m, new in zip(models, mm):
+            C.memmove(C.byref(m), C.byref(new), C.sizeof(MotionModel))
+        infos = [dict(pose_in=np.array(f.pose_in), align=_alignment(f.align), try_coarse=f.try_coarse, coarse_max=f.coarse_max,
+                      coarse_range=f.coarse_range) for f in inf]
+        return res, infos
+
     def iteration_set(self):
         n = C.c_int()
         self.ctx._check(self.lib.tracker_read_iteration_set(self.h, None, 0, C.byref(n)), "tracker_read_iteration_set")
