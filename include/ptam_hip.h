@@ -883,7 +883,10 @@ int ptam_ba_solve_fallbacks(const ptam_ba* ba);
 int ptam_ba_duplicates_refused(const ptam_ba* ba);
 /* Operating switches of the camera solve, read from the environment once per process: PTAM_LDLT_NO_CHAIN=1 uses the
  * launch-per-block-column form everywhere (a device shared between processes that all adjust bundles); PTAM_CH_SPIN_LIMIT=<n> is
- * the number of looks (~1 us each, default 2^18) a workgroup of the persistent form takes before it gives up a wait. */
+ * the number of looks (~1 us each, default 2^18) a workgroup of the persistent form takes before it gives up a wait.
+ * A comparison switch of the bundle's trial, read once per process as well (the GPU tests compare the two forms on this library):
+ * PTAM_UPDATE_LOADS_W=1 — the point update reads W back from the Jacobian pass' planes instead of rebuilding it in registers
+ * (the form before docs/LOG_point_update.md; the same adjustment to the last few bits). */
 
 /* profiling hooks used by bench.py: HIP-event timing of individual kernels on the ctx stream. */
 enum {

@@ -135,6 +135,40 @@ __device__ __forceinline__ double ba_sqrt_weight(int est, double e2, double s2, 
     if (est == PTAM_EST_TUKEY) return e2 > s2 ? 0.0 : 1.0 - e2 * is2;
     return est_sqrt_weight(est, e2, s2);
 }
+// W_ij = A^T B (6x3, row-major) of one measurement K7 found alive with a free camera, from what K7 formed it from: the CURRENT
+// pose and point, the measurement's record and sigma^2 — K7's expressions in K7's order (ba_jacobian.inc, the `full` branch and
+// the W stores).  The point update rebuilds W with this instead of reading 144 bytes per measurement back; K7 keeps its own
+// text (its register budget is tuned by hand).  A measurement K7 gave weight 0 is MS_BAD by now and never gets here.
+__device__ __forceinline__ void ba_rebuild_w(const DevCam& cam, int est, const double* __restrict__ T, const double* __restrict__ Xp,
+                                             double2 fo, double sn, double sigma_sq, double w18[18]) {
+    BaProj pr;
+    ba_project(cam, T, Xp, pr);
+    const double ex = sn * (fo.x - pr.u), ey = sn * (fo.y - pr.v);
+    const double w = ba_sqrt_weight(est, ex * ex + ey * ey, sigma_sq, 1.0 / sigma_sq);
+    double D[4];
+    ba_derivs(cam, pr, D);
+    const double sw = sn * w;
+    const double D0 = sw * D[0], D1 = sw * D[1], D2 = sw * D[2], D3 = sw * D[3];
+    const double X = pr.X, Y = pr.Y, Z = pr.Z;
+    const double iz = rcp_nr(Z);
+    double B0[3], B1[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double g0 = T[k], g1 = T[3 + k], g2 = T[6 + k];
+        const double mx = (g0 - X * g2 * iz) * iz, my = (g1 - Y * g2 * iz) * iz;
+        B0[k] = D0 * mx + D1 * my;
+        B1[k] = D2 * mx + D3 * my;
+    }
+    const double zx = -X * iz * iz, zy = -Y * iz * iz;
+    const double mxs[6] = {iz, 0, zx, zx * Y, iz * Z - zx * X, -iz * Y};
+    const double mys[6] = {0, iz, zy, -iz * Z + zy * Y, -zy * X, iz * X};
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const double A0 = D0 * mxs[k] + D1 * mys[k], A1 = D2 * mxs[k] + D3 * mys[k];
+#pragma unroll
+        for (int c = 0; c < 3; c++) w18[k * 3 + c] = A0 * B0[c] + A1 * B1[c];
+    }
+}
 __device__ __forceinline__ double ba_objective(int est, double e2, double s2, double is2) {
     if (est == PTAM_EST_TUKEY) {
         if (e2 > s2) return 1.0;

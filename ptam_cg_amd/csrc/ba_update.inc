@@ -34,22 +34,39 @@ __global__ void __launch_bounds__(64) pose_update_kernel(BaDev d, int cur) {
 // A chunk that is ONE point with more than BA_CHUNK measurements (a point seen by more than 256 keyframes): the same
 // arithmetic, BA_CHUNK measurements at a time — W^T da summed per thread over its strided measurements, the threads' sums
 // added in thread order by one wave (fixed order), then the new-error pass over the same strides.
+template <bool LOADW>
 __device__ void point_update_long(const DevCam& cam, const BaDev& d, int cur, int est, const BaChunk& ch, double (*Ts)[3], double (*wred)[2]) {
     const int tid = threadIdx.x, pp = ch.pt_begin;
     const size_t wp = w_plane(d);
+    const double sig2 = d.sc->sigma_sq;
+    const double Xc[3] = {d.pt[cur][(size_t)pp * 3], d.pt[cur][(size_t)pp * 3 + 1], d.pt[cur][(size_t)pp * 3 + 2]};
     double t0 = 0, t1 = 0, t2 = 0;
     for (int m = ch.m_begin + tid; m < ch.m_end; m += BA_CHUNK) {
-        const int f = d.cam_free[d.m_cam[m]];
+        const int c = d.m_cam[m], f = d.cam_free[c];
         if (d.m_state[m] != MS_ALIVE || f < 0) continue;   // non-fixed, non-bad  (:469-474)
         const double* da = d.da + 6 * f;
+        if (LOADW) {
 #pragma unroll
-        for (int h = 0; h < 3; h++) {
-            const double a0 = da[2 * h], a1 = da[2 * h + 1];
-            const double2 w0 = *(const double2*)(d.W + 0 * wp + (size_t)m * 6 + 2 * h), w1 = *(const double2*)(d.W + 1 * wp + (size_t)m * 6 + 2 * h),
-                          w2 = *(const double2*)(d.W + 2 * wp + (size_t)m * 6 + 2 * h);
-            t0 += w0.x * a0 + w0.y * a1;
-            t1 += w1.x * a0 + w1.y * a1;
-            t2 += w2.x * a0 + w2.y * a1;
+            for (int h = 0; h < 3; h++) {
+                const double a0 = da[2 * h], a1 = da[2 * h + 1];
+                const double2 w0 = *(const double2*)(d.W + 0 * wp + (size_t)m * 6 + 2 * h), w1 = *(const double2*)(d.W + 1 * wp + (size_t)m * 6 + 2 * h),
+                              w2 = *(const double2*)(d.W + 2 * wp + (size_t)m * 6 + 2 * h);
+                t0 += w0.x * a0 + w0.y * a1;
+                t1 += w1.x * a0 + w1.y * a1;
+                t2 += w2.x * a0 + w2.y * a1;
+            }
+        } else {   // W rebuilt from the current state (ba_rebuild_w), added in the same order
+            double Tc[12], w[18];
+#pragma unroll
+            for (int i = 0; i < 12; i++) Tc[i] = d.pose[cur][12 * (size_t)c + i];
+            ba_rebuild_w(cam, est, Tc, Xc, d.m_found[m], d.m_s[m], sig2, w);
+#pragma unroll
+            for (int h = 0; h < 3; h++) {
+                const double a0 = da[2 * h], a1 = da[2 * h + 1];
+                t0 += w[(2 * h) * 3] * a0 + w[(2 * h + 1) * 3] * a1;
+                t1 += w[(2 * h) * 3 + 1] * a0 + w[(2 * h + 1) * 3 + 1] * a1;
+                t2 += w[(2 * h) * 3 + 2] * a0 + w[(2 * h + 1) * 3 + 2] * a1;
+            }
         }
     }
     Ts[tid][0] = t0, Ts[tid][1] = t1, Ts[tid][2] = t2;
@@ -72,7 +89,7 @@ __device__ void point_update_long(const DevCam& cam, const BaDev& d, int cur, in
     __syncthreads();
     const double Xn[3] = {wred[0][0], wred[0][1], wred[1][0]};
     const double sq = wred[1][1];
-    const double s2 = d.sc->sigma_sq;
+    const double s2 = sig2;
     double err = 0;
     for (int m = ch.m_begin + tid; m < ch.m_end; m += BA_CHUNK) {   // FindNewError over every listed measurement (:188-207)
         if (d.m_state[m] == MS_DEAD) continue;
@@ -101,7 +118,11 @@ __device__ void point_update_long(const DevCam& cam, const BaDev& d, int cur, in
     }
 }
 
-// delta b, trial points, new robust error; block owns whole points
+// delta b, trial points, new robust error; block owns whole points.  W_ij, which this kernel needs for sum_j W_ij^T da_j alone, is
+// not read back from K7's planes (144 of the 176 bytes a measurement moved here) but rebuilt in registers from the current pose
+// and point (ba_rebuild_w: ~200 fp64 instructions).  LOADW = true is the loading form, kept for comparison
+// (PTAM_UPDATE_LOADS_W=1, bundle.hip).
+template <bool LOADW>
 __global__ void __launch_bounds__(BA_CHUNK) point_update_kernel(DevCam cam, BaDev d, int cur, int est) {
     TL_MARK(d, 11)
     __shared__ double Ts[BA_CHUNK][3];
@@ -110,16 +131,17 @@ __global__ void __launch_bounds__(BA_CHUNK) point_update_kernel(DevCam cam, BaDe
     const int tid = threadIdx.x;
     const BaChunk ch = d.chunks[blockIdx.x];
     if (ch.m_end - ch.m_begin > BA_CHUNK) {   // (uniform: a long point, alone in its chunk)
-        point_update_long(cam, d, cur, est, ch, Ts, wred);
+        point_update_long<LOADW>(cam, d, cur, est, ch, Ts, wred);
         return;
     }
     const int m = ch.m_begin + tid;
     const bool active = m < ch.m_end;
     // Every load of the workgroup leaves in ONE go, the small ones first: the measurement's record, the first round's per-point
-    // data (V*^-1, epsB, the point — they depend on the chunk alone), then W (144 of the ~190 bytes per measurement), and behind
-    // it what hangs on the record: the camera's update and its trial pose (cache hits).  Issued phase by phase (record -> free
-    // index -> update; the per-point data after the first barrier; the pose after the second) each phase was a round trip
-    // queued behind the W stream of the ~1 000 co-resident workgroups: 13 us for 47 MB.
+    // data (V*^-1, epsB, the point — they depend on the chunk alone), then (LOADW) W, 144 of the ~190 bytes per measurement, and
+    // behind it what hangs on the record: the camera's update and — for the rebuilt W — its current pose and the measurement's
+    // own point, or (LOADW) its trial pose (cache hits).  Issued phase by phase (record -> free index -> update; the per-point
+    // data after the first barrier; the pose after the second) each phase was a round trip queued behind the W stream of the
+    // ~1 000 co-resident workgroups: 13 us for 47 MB.
     const int mc = min(m, d.M - 1);
     const int st = active ? (int)d.m_state[mc] : (int)MS_DEAD;
     const int c = d.m_cam[mc], p = d.m_pt[mc];
@@ -143,7 +165,7 @@ __global__ void __launch_bounds__(BA_CHUNK) point_update_kernel(DevCam cam, BaDe
         for (int i = 0; i < 3; i++) x[i] = X[i], eb[i] = E[i];
     }
     double w[18];   // row-major 6x3 again, from the three coordinate planes (bundle.h)
-    {
+    if (LOADW) {
         const size_t wp = w_plane(d);
 #pragma unroll
         for (int c3 = 0; c3 < 3; c3++)
@@ -154,29 +176,53 @@ __global__ void __launch_bounds__(BA_CHUNK) point_update_kernel(DevCam cam, BaDe
                 w[(2 * h + 1) * 3 + c3] = t.y;
             }
     }
-    double da[6], T[12];
+    double da[6], T[12], Tc[12], xm[3];
     {
         const double2* dq = (const double2*)(d.da + 6 * (size_t)max(f, 0));   // (48-byte pitch: 16-byte aligned)
         const double2* Tq = (const double2*)(d.pose[cur ^ 1] + 12 * (size_t)c);
+        if (!LOADW) {
+            const double2* Cq = (const double2*)(d.pose[cur] + 12 * (size_t)c);
+            const double* Xm = d.pt[cur] + (size_t)p * 3;
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                const double2 t = Cq[i];
+                Tc[2 * i] = t.x, Tc[2 * i + 1] = t.y;
+            }
+#pragma unroll
+            for (int i = 0; i < 3; i++) xm[i] = Xm[i];
+        }
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             const double2 t = dq[i];
             da[2 * i] = t.x, da[2 * i + 1] = t.y;
         }
+        if (LOADW) {
 #pragma unroll
-        for (int i = 0; i < 6; i++) {
-            const double2 t = Tq[i];
-            T[2 * i] = t.x, T[2 * i + 1] = t.y;
+            for (int i = 0; i < 6; i++) {
+                const double2 t = Tq[i];
+                T[2 * i] = t.x, T[2 * i + 1] = t.y;
+            }
         }
     }
     double t0 = 0, t1 = 0, t2 = 0;
     if (st == MS_ALIVE && f >= 0) {   // non-fixed, non-bad  (:469-474)
+        if (!LOADW) ba_rebuild_w(cam, est, Tc, xm, fo, sn, s2, w);
 #pragma unroll
         for (int r = 0; r < 6; r++) {
             const double a = da[r];
             t0 += w[r * 3] * a;
             t1 += w[r * 3 + 1] * a;
             t2 += w[r * 3 + 2] * a;
+        }
+    }
+    if (!LOADW) {
+        // (the trial pose is needed behind the second barrier only: asked for here, where the current pose's registers are
+        //  free again, the kernel keeps its 128 VGPRs and four workgroups a CU; the two barriers and the per-point sums cover it)
+        const double2* Tq = (const double2*)(d.pose[cur ^ 1] + 12 * (size_t)c);
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            const double2 t = Tq[i];
+            T[2 * i] = t.x, T[2 * i + 1] = t.y;
         }
     }
     Ts[tid][0] = t0;

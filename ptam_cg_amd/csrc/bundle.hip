@@ -1199,9 +1199,13 @@ static int ba_trial(ptam_ba* ba, double lambda, bool skip_vinv, int last_allowed
     prof_begin(ba, PTAM_K_UPDATE);
     if (d.F == 0)   // no free camera: nothing was solved, the trial poses are copies
         hipLaunchKernelGGL(pose_update_kernel, dim3(std::max(1, (d.C + 63) / 64)), dim3(64), 0, ctx->stream, d, ba->cur);
-    if (d.n_chunks > 0)
-        hipLaunchKernelGGL(point_update_kernel, dim3(d.n_chunks), dim3(BA_CHUNK), 0, ctx->stream, ctx->cam, d, ba->cur,
-                           ba->opts.estimator);
+    if (d.n_chunks > 0) {
+        // PTAM_UPDATE_LOADS_W=1: W read back from K7's planes as before (read once per process; getenv, not ptam_ab_env:
+        // tests/test_gpu_update_recompute.py compares the two forms on the product library)
+        static const bool loads_w = getenv("PTAM_UPDATE_LOADS_W") != nullptr;
+        hipLaunchKernelGGL(loads_w ? point_update_kernel<true> : point_update_kernel<false>, dim3(d.n_chunks), dim3(BA_CHUNK), 0,
+                           ctx->stream, ctx->cam, d, ba->cur, ba->opts.estimator);
+    }
     {
         // single device, no per-kernel events: finalize publishes the scalars itself
         const bool fuse = !(ba->comm && ba->world > 1) && !ba->prof;
@@ -2155,7 +2159,8 @@ int ba_preload_kernels() {
     ptam_preload((const void*)schur_tile_mfma_kernel);
     ptam_preload((const void*)schur_reduce_kernel);
     ptam_preload((const void*)pose_update_kernel);
-    ptam_preload((const void*)point_update_kernel);
+    ptam_preload((const void*)point_update_kernel<false>);
+    ptam_preload((const void*)point_update_kernel<true>);
     ptam_preload((const void*)finalize_new_kernel);
     ptam_preload((const void*)purge_kernel);
     ptam_preload((const void*)readback_kernel);

@@ -119,7 +119,8 @@ int ctx_pinned(ptam_ctx* ctx, size_t bytes, void** out);      // pinned host sta
 // What the product does read: PTAM_LDLT_NO_CHAIN (launch-per-block-column camera solve only), PTAM_CH_SPIN_LIMIT (how long a
 // workgroup of the persistent solve waits for another one) — operating switches, documented in ptam_hip.h —, the solve's
 // PTAM_LDLT_SEPARATE_BACKWARD and PTAM_LDLT_BACKWARD_IN_LAUNCH (the forms of its backward part: the GPU tests compare them on
-// the product build, solve.hip) and the PTAM_DEBUG_* diagnostics, which only print.
+// the product build, solve.hip), the point update's PTAM_UPDATE_LOADS_W (likewise: bundle.hip) and the PTAM_DEBUG_*
+// diagnostics, which only print.
 #ifdef PTAM_AB_SWITCHES
 #define ptam_ab_env(name) getenv(name)
 #else
