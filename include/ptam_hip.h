@@ -797,6 +797,93 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* trackers, ptam_kf* cons
  * one launch, one thread per row: poses_out12 + 12 i = the pose ptam_motion_predict_sbi(models + i, rotations9 + 9 i) leaves in the
  * model.  The models are not changed.  The ranges of SO3::ln near pi, which no tracked sequence reaches, are run through this. */
 int ptam_motion_predict_sbi_dev(ptam_ctx* ctx, int n, const ptam_motion_model* models, const double* rotations9, double* poses_out12);
+
+/* ---- Tracker::TrackFrame for a good map (src/Tracker.cc:91-111, :127-176): tracking, loss and recovery per camera ----------------
+ *      The tracker's state next to the motion model, and AssessTrackingQuality (:1062-1107); plain host code like ptam_motion_*. */
+#define PTAM_TRACK_BAD 0
+#define PTAM_TRACK_GOOD 1
+typedef struct {
+    ptam_motion_model model;
+    int32_t lost_frames;            /* mnLostFrames */
+    int32_t quality;                /* mTrackingQuality: PTAM_TRACK_BAD 0, PTAM_TRACK_GOOD 1 */
+    int32_t frame;                  /* mnFrame */
+    int32_t last_keyframe_dropped;  /* mnLastKeyFrameDropped; -20 after a reset (:62) */
+} ptam_track_state;
+/* Tracker::Reset :52-62: ptam_motion_reset, quality GOOD, no lost frames, frame 0, last_keyframe_dropped -20 */
+void ptam_track_state_reset(ptam_track_state* s, const double pose[12]);
+typedef struct {
+    double quality_good;                   /* Tracker.TrackingQualityGood 0.3 */
+    double quality_lost;                   /* Tracker.TrackingQualityLost 0.13 */
+    double wiggle_scale;                   /* MapMaker::GetWiggleScale(), 0.1 */
+    double wiggle_scale_depth_normalized;  /* mdWiggleScaleDepthNormalized (the map maker's; 0.1 here: the wiggle scale at unit depth) */
+    double max_kf_dist_wiggle_mult;        /* MapMaker.MaxKFDistWiggleMult 0.05 (IsNeedNewKeyFrame, src/MapMaker.cc:754-763) */
+    double reloc_blur;                     /* the relocaliser's SmallBlurryImage blur, 2.5 */
+    double reloc_max_score;                /* Reloc2.MaxScore 9e6 */
+} ptam_track_state_opts;
+void ptam_track_state_opts_default(ptam_track_state_opts* o);
+/* AssessTrackingQuality :1062-1107 on a frame's counts (ptam_trackmap_result.attempted / .found): quality and lost_frames move, nothing
+ * else does, and lost_frames moves nowhere else.  closest_kf_dist (KeyFrameLinearDist to the closest keyframe) is read in the third
+ * branch only (:1095-1100), where a camera within 10 wiggle scales of a keyframe KEEPS its previous quality.  opts nullable. */
+void ptam_assess_tracking_quality(ptam_track_state* s, const int32_t attempted[4], const int32_t found[4], double closest_kf_dist,
+                                  const ptam_track_state_opts* opts);
+
+/* se3CfromW of the bank's entries first .. first + n - 1 (which must exist), kept in device memory (mse3Best is formed there by
+ * ptam_track_frames_recover_batch) and in a host mirror (the closest-keyframe distance); the upload is asynchronous on the bank's
+ * context's queue.  ptam_relocalise keeps taking its own host table.  ptam_sbi_bank_poses reads the mirror; PTAM_E_STATE where an
+ * entry's pose was never set. */
+int ptam_sbi_bank_set_poses(ptam_sbi_bank* b, int first, int n, const double* poses12);
+int ptam_sbi_bank_poses(const ptam_sbi_bank* b, int first, int n, double* poses_out12);
+
+#define PTAM_FRAME_TRACKED 0
+#define PTAM_FRAME_RECOVERED 1
+#define PTAM_FRAME_RECOVERY_FAILED 2
+typedef struct {
+    int32_t branch;                /* PTAM_FRAME_* */
+    int32_t closest_kf;            /* ClosestKeyFrame (src/MapMaker.cc:736-752) of the tracked pose among banks[i]'s poses; -1 without them */
+    double closest_kf_dist;        /* KeyFrameLinearDist (:696-703) to it; 0 without */
+    int32_t need_new_keyframe;     /* IsNeedNewKeyFrame :754-763 — information only, as the reference has it commented out */
+    int32_t want_keyframe;         /* quality == GOOD && frame - last_keyframe_dropped > 20 (:146-161 without the queue size) */
+    ptam_track_frame_info frame;   /* PTAM_FRAME_RECOVERED: pose_in is the relocaliser's pose, align is zero (no alignment is run) */
+    ptam_reloc_result reloc;       /* the recovery branches; zero for PTAM_FRAME_TRACKED */
+} ptam_track_frame_state_info;
+/* Tracker::TrackFrame for a good map, for nb cameras as ONE chain of launches with one wait per camera; each camera takes the branch its
+ * own state selects, decided on the host before the launch.
+ *   states[i].lost_frames < 3   the frame is what ptam_track_frames_batch does for it (out, info.frame and the model bit for bit), then
+ *                               ptam_assess_tracking_quality on its counts and the keyframe decision (:146-166): the caller ANDs
+ *                               want_keyframe with its queue size and sets last_keyframe_dropped = frame when it adds the keyframe.
+ *   otherwise                   recovery (:168-176, :196-207, src/Relocaliser.cc:12-38) inside the same chain: MakeKeyFrame_Lite; the
+ *                               estimator's pair advances (this frame's image is made, nothing is aligned); this frame's relocaliser
+ *                               image goes into scratch[i] (opts' reloc_blur; a second make launch, enqueued only when a camera
+ *                               recovers); its SSD against every entry of banks[i] (one launch for all recovering cameras); an align
+ *                               workgroup in the estimators' align launch takes the first strictly lowest SSD, aligns against that
+ *                               entry, forms pose = rotation * bank pose[best] exactly as ptam_relocalise does and decides
+ *                               good = score < reloc_max_score.
+ *       good    PTAM_FRAME_RECOVERED: TrackMap from that pose with try_coarse = 1 and doubled coarse_max / coarse_range (:508-513);
+ *               the model is pose = the tracked pose, start_pose = the relocaliser's, zero velocity, just_recovered = 0, the scene
+ *               depth of :692-696 (msd_scaled_velocity stays: no UpdateMotionModel, :171-175); AssessTrackingQuality follows.  The
+ *               reference takes no keyframe decision on this branch: need_new_keyframe and want_keyframe are 0.
+ *       else    PTAM_FRAME_RECOVERY_FAILED: the device skips the frame's TrackMap kernels (they read the workgroup's verdict from device
+ *               memory; nothing is waited for or spun on): the tracker's per-point PatchFinder state, its iteration set and states[i]
+ *               stay byte for byte but for states[i].frame, the estimator's pair still advances, out[i] is zero.
+ * states[i].frame moves by one in every branch.  A batch without a recovering camera enqueues exactly ptam_track_frames_batch's launches.
+ * banks[i]: needed (with every entry's pose set, ptam_sbi_bank_set_poses) for a recovering camera; for a tracking camera it is
+ * optional and feeds closest_kf (walked on the host after the wait).  One bank may serve several cameras.  A recovering camera's bank
+ * is read on the LEAD tracker's queue: the call waits for the bank's own context's queue first, so whatever was enqueued there (adds,
+ * pose uploads) is seen; nothing else may use that queue during the call.  scratch[i]: the recovering camera's current image, none
+ * twice.  Banks, scratches and estimators must sit on the trackers' device and have the frames' size.
+ * PTAM_E_ARG / PTAM_E_STATE, decided before the first enqueue with everything where it was: a recovering camera without bank or
+ * scratch, an empty bank (STATE), entries whose pose was never set (STATE), another device or image size, a scratch named twice, a
+ * recovering camera in a batch whose coarse_max exceeds the fused pose kernels' 1024 entries.  As in ptam_track_frames_batch states and
+ * estimators advance on copies and commit when every frame has arrived; an error leaves every states[i] byte for byte.
+ * estimators, banks, scratch and info are nullable, as are their entries (banks / scratch: of cameras that are not lost). */
+int ptam_track_frames_recover_batch(int nb, ptam_tracker* const* trackers, ptam_kf* const* current, const uint8_t* const* d_frames,
+                                    ptam_track_state* states /* nb, in/out */, ptam_rotation_estimator* const* estimators,
+                                    ptam_sbi_bank* const* banks, ptam_sbi* const* scratch, const ptam_trackmap_opts* opts,
+                                    const ptam_track_state_opts* state_opts, ptam_trackmap_result* out, ptam_track_frame_state_info* info);
+/* Test hook: the SSD table (mdBestScore's candidates, src/Relocaliser.cc:21-31) of the row-th recovering camera, in camera order, of the
+ * last ptam_track_frames_recover_batch that `lead` (its trackers[0]) led: the first count entries of its bank.  PTAM_E_ARG: no such row,
+ * or more entries than the row's bank held. */
+int ptam_tracker_read_reloc_ssd(ptam_tracker* lead, int row, int count, double* ssd_out);
 /* vIterationSet of the last frame (what :667-676 turns into mCurrentKF.mMeasurements): *n = its length; out (nullable)
  * receives up to cap entries. */
 int ptam_tracker_read_iteration_set(ptam_tracker* t, ptam_trackmap_meas* out, int cap, int* n);

@@ -677,6 +677,7 @@ public:
         double p[12];
         k.se3CfromW.to12(p);
         poses_.insert(poses_.end(), p, p + 12);
+        check(ptam_sbi_bank_set_poses(h_, i, 1, p), "ptam_sbi_bank_set_poses");
         return i;
     }
     int AddKeyFrames(const std::vector<KeyFrame*>& vKeyFrames, double dBlur = 2.5) {   // a map handed over at once: one launch
@@ -689,9 +690,22 @@ public:
             k->se3CfromW.to12(p);
             poses_.insert(poses_.end(), p, p + 12);
         }
+        check(ptam_sbi_bank_set_poses(h_, i, (int)h.size(), &poses_[12 * (size_t)i]), "ptam_sbi_bank_set_poses");
         return i;
     }
-    void SetKeyFramePose(int i, const SE3& se3CfromW) { se3CfromW.to12(&poses_[12 * (size_t)i]); }   // after a bundle adjustment
+    // after a bundle adjustment: the bank keeps the pose on the device and in its mirror (MapTracker::TrackFramesRecoverBatch forms
+    // mse3Best there and walks the mirror for the closest keyframe); AttemptRecovery's own table follows
+    void SetKeyFramePose(int i, const SE3& se3CfromW) {
+        se3CfromW.to12(&poses_[12 * (size_t)i]);
+        check(ptam_sbi_bank_set_poses(h_, i, 1, &poses_[12 * (size_t)i]), "ptam_sbi_bank_set_poses");
+    }
+    SE3 KeyFramePose(int i) const {
+        double p[12];
+        check(ptam_sbi_bank_poses(h_, i, 1, p), "ptam_sbi_bank_poses");
+        return SE3::from12(p);
+    }
+    ptam_sbi_bank* handle() const { return h_; }
+    ptam_sbi* scratch() const { return scratch_.handle(); }
     // bool AttemptRecovery(KeyFrame &k)   src/Relocaliser.cc:12; Reloc2.MaxScore = 9e6
     bool AttemptRecovery(KeyFrame& kCurrent, double dMaxScore = 9e6, double dBlur = 2.5) {
         check(ptam_relocalise(h_, scratch_.handle(), kCurrent.handle(), poses_.data(), dBlur, dMaxScore, &last_, nullptr), "ptam_relocalise");
@@ -723,6 +737,24 @@ public:
 
 private:
     ptam_rotation_estimator* h_ = nullptr;
+};
+
+// The tracker's state around TrackMap (src/Tracker.cc:52-62): the motion model, mnLostFrames, mTrackingQuality, mnFrame and
+// mnLastKeyFrameDropped, for MapTracker::TrackFramesRecoverBatch
+struct TrackState : ptam_track_state {
+    explicit TrackState(const SE3& se3CfromW = SE3::Identity()) { Reset(se3CfromW); }
+    void Reset(const SE3& se3CfromW) {   // Tracker::Reset
+        double p[12];
+        se3CfromW.to12(p);
+        ptam_track_state_reset(this, p);
+    }
+    bool IsLost() const { return lost_frames >= 3; }                      // :129 / :168
+    bool IsGood() const { return quality == PTAM_TRACK_GOOD; }
+    void KeyFrameAdded() { last_keyframe_dropped = frame; }               // :165
+    // AssessTrackingQuality :1062-1107 on a frame's counts
+    void Assess(const ptam_trackmap_result& r, double dClosestKeyFrameDist, const ptam_track_state_opts* pOpts = nullptr) {
+        ptam_assess_tracking_quality(this, r.attempted, r.found, dClosestKeyFrameDist, pOpts);
+    }
 };
 
 // The map as the tracker wants it, in device memory (ptam_map_snapshot, ptam_hip.h): ResidentMap::Publish fills it on the mapmaker's
@@ -866,6 +898,41 @@ public:
         check(ptam_track_frames_batch((int)n, t.data(), k.data(), vdFrames.data(), vMotion.data(), vEstimators.empty() ? nullptr : e.data(), pOpts,
                                       r.data(), pvInfo ? pvInfo->data() : nullptr),
               "ptam_track_frames_batch");
+        return r;
+    }
+    // Tracker::TrackFrame for a good map (src/Tracker.cc:127-176) for every camera, in one chain of launches with one wait per camera
+    // (ptam_track_frames_recover_batch): a camera whose state says lost runs vRelocalisers[i]'s AttemptRecovery inside the chain and is
+    // tracked from mse3Best in the same call when it is good; AssessTrackingQuality and the keyframe decision follow per camera.
+    // vStates advance in place.  vEstimators and vRelocalisers may be empty, their entries null (a relocaliser: of a camera that is
+    // not lost — with one, vInfo carries the closest keyframe).  A call that throws leaves every state, estimator and bank as it was.
+    static std::vector<ptam_trackmap_result> TrackFramesRecoverBatch(const std::vector<MapTracker*>& vTrackers, const std::vector<KeyFrame*>& vCurrent,
+                                                                     const std::vector<const uint8_t*>& vdFrames, std::vector<TrackState>& vStates,
+                                                                     const std::vector<RotationEstimator*>& vEstimators,
+                                                                     const std::vector<Relocaliser*>& vRelocalisers,
+                                                                     std::vector<ptam_track_frame_state_info>& vInfo, const ptam_trackmap_opts* pOpts = nullptr,
+                                                                     const ptam_track_state_opts* pStateOpts = nullptr) {
+        const size_t n = vTrackers.size();
+        if (n == 0 || vCurrent.size() != n || vdFrames.size() != n || vStates.size() != n || (!vEstimators.empty() && vEstimators.size() != n) ||
+            (!vRelocalisers.empty() && vRelocalisers.size() != n))
+            throw std::runtime_error("TrackFramesRecoverBatch: sizes differ");
+        std::vector<ptam_tracker*> t(n);
+        std::vector<ptam_kf*> k(n);
+        std::vector<ptam_rotation_estimator*> e(n, nullptr);
+        std::vector<ptam_sbi_bank*> b(n, nullptr);
+        std::vector<ptam_sbi*> s(n, nullptr);
+        std::vector<ptam_track_state> st(vStates.begin(), vStates.end());
+        for (size_t i = 0; i < n; i++) {
+            t[i] = vTrackers[i]->h_;
+            k[i] = vCurrent[i]->handle();
+            if (!vEstimators.empty() && vEstimators[i]) e[i] = vEstimators[i]->handle();
+            if (!vRelocalisers.empty() && vRelocalisers[i]) b[i] = vRelocalisers[i]->handle(), s[i] = vRelocalisers[i]->scratch();
+        }
+        std::vector<ptam_trackmap_result> r(n);
+        vInfo.assign(n, ptam_track_frame_state_info{});
+        check(ptam_track_frames_recover_batch((int)n, t.data(), k.data(), vdFrames.data(), st.data(), e.data(), b.data(), s.data(), pOpts, pStateOpts,
+                                              r.data(), vInfo.data()),
+              "ptam_track_frames_recover_batch");
+        for (size_t i = 0; i < n; i++) static_cast<ptam_track_state&>(vStates[i]) = st[i];
         return r;
     }
     // vIterationSet of the last frame: what :667-676 turns into mCurrentKF.mMeasurements and what routes the outlier flags

@@ -290,6 +290,29 @@ class RelocResult(C.Structure):
     _fields_ = [("best", C.c_int32), ("good", C.c_int32), ("best_ssd", C.c_double), ("pose", C.c_double * 12), ("align", SbiAlignment)]
 
 
+TRACK_BAD, TRACK_GOOD = 0, 1
+FRAME_TRACKED, FRAME_RECOVERED, FRAME_RECOVERY_FAILED = 0, 1, 2
+
+
+class TrackState(C.Structure):
+    """ptam_track_state: the motion model with mnLostFrames, mTrackingQuality, mnFrame, mnLastKeyFrameDropped"""
+    _fields_ = [("model", MotionModel), ("lost_frames", C.c_int32), ("quality", C.c_int32), ("frame", C.c_int32),
+                ("last_keyframe_dropped", C.c_int32)]
+
+
+class TrackStateOpts(C.Structure):
+    """ptam_track_state_opts (AssessTrackingQuality, IsNeedNewKeyFrame, the relocaliser's tunables)"""
+    _fields_ = [("quality_good", C.c_double), ("quality_lost", C.c_double), ("wiggle_scale", C.c_double),
+                ("wiggle_scale_depth_normalized", C.c_double), ("max_kf_dist_wiggle_mult", C.c_double), ("reloc_blur", C.c_double),
+                ("reloc_max_score", C.c_double)]
+
+
+class TrackFrameStateInfo(C.Structure):
+    """ptam_track_frame_state_info (ptam_track_frames_recover_batch)"""
+    _fields_ = [("branch", C.c_int32), ("closest_kf", C.c_int32), ("closest_kf_dist", C.c_double), ("need_new_keyframe", C.c_int32),
+                ("want_keyframe", C.c_int32), ("frame", TrackFrameInfo), ("reloc", RelocResult)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p)
 
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
@@ -419,6 +442,14 @@ PROTOTYPES = {
     "track_map_frames_batch": (_i, [_i, _vp, _vp, _vp, _pd, _vp, _vp]),
     "track_frames_batch": (_i, [_i, _vp, _vp, _vp, C.POINTER(MotionModel), _vp, _vp, _vp, C.POINTER(TrackFrameInfo)]),
     "motion_predict_sbi_dev": (_i, [_vp, _i, C.POINTER(MotionModel), _pd, _pd]),
+    "track_state_reset": (None, [C.POINTER(TrackState), _pd]),
+    "track_state_opts_default": (None, [C.POINTER(TrackStateOpts)]),
+    "assess_tracking_quality": (None, [C.POINTER(TrackState), _vp, _vp, _d, C.POINTER(TrackStateOpts)]),
+    "sbi_bank_set_poses": (_i, [_vp, _i, _i, _vp]),
+    "sbi_bank_poses": (_i, [_vp, _i, _i, _vp]),
+    "tracker_read_reloc_ssd": (_i, [_vp, _i, _i, _pd]),
+    "track_frames_recover_batch": (_i, [_i, _vp, _vp, _vp, C.POINTER(TrackState), _vp, _vp, _vp, _vp, C.POINTER(TrackStateOpts), _vp,
+                                        C.POINTER(TrackFrameStateInfo)]),
     "bench_track_batch": (_i, [_i, _vp, _vp, _vp, _pd, _vp, _vp, _vp, _i, _i, _pd]),
     "tracker_read_iteration_set": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "ba_bench_jacobian_rotating": (_i, [_vp, _i, _i, _pd]),

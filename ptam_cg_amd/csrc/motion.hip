@@ -130,6 +130,59 @@ void ptam_motion_recover(ptam_motion_model* m, const double pose[12]) {
     m->just_recovered = 1;
 }
 
+// src/Tracker.cc:52-62
+void ptam_track_state_reset(ptam_track_state* s, const double pose[12]) {
+    if (!s) return;
+    ptam_motion_reset(&s->model, pose);
+    s->lost_frames = 0;
+    s->quality = PTAM_TRACK_GOOD;
+    s->frame = 0;
+    s->last_keyframe_dropped = -20;
+}
+
+void ptam_track_state_opts_default(ptam_track_state_opts* o) {
+    if (!o) return;
+    o->quality_good = 0.3;                    // Tracker.TrackingQualityGood, :1088
+    o->quality_lost = 0.13;                   // Tracker.TrackingQualityLost, :1089
+    o->wiggle_scale = 0.1;                    // MapMaker.WiggleScale
+    o->wiggle_scale_depth_normalized = 0.1;
+    o->max_kf_dist_wiggle_mult = 0.05;        // src/MapMaker.cc:760
+    o->reloc_blur = 2.5;
+    o->reloc_max_score = 9e6;                 // Reloc2.MaxScore
+}
+
+// src/Tracker.cc:1062-1107
+void ptam_assess_tracking_quality(ptam_track_state* s, const int32_t attempted[4], const int32_t found[4], double closest_kf_dist,
+                                  const ptam_track_state_opts* opts) {
+    if (!s || !attempted || !found) return;
+    ptam_track_state_opts o;
+    ptam_track_state_opts_default(&o);
+    if (opts) o = *opts;
+    int total_attempted = 0, total_found = 0, large_attempted = 0, large_found = 0;
+    for (int i = 0; i < 4; i++) {
+        total_attempted += attempted[i];
+        total_found += found[i];
+        if (i >= 2) {
+            large_attempted += attempted[i];
+            large_found += found[i];
+        }
+    }
+    if (total_found == 0 || total_attempted == 0)
+        s->quality = PTAM_TRACK_BAD;
+    else {
+        const double total_frac = (double)total_found / total_attempted;
+        const double large_frac = large_attempted > 10 ? (double)large_found / large_attempted : total_frac;
+        if (total_frac > o.quality_good)
+            s->quality = PTAM_TRACK_GOOD;
+        else if (large_frac < o.quality_lost)
+            s->quality = PTAM_TRACK_BAD;
+        else if (closest_kf_dist > o.wiggle_scale * 10.0)   // far from the nearest keyframe; otherwise the quality stays (:1095-1100)
+            s->quality = PTAM_TRACK_BAD;
+    }
+    if (s->quality == PTAM_TRACK_BAD) s->lost_frames++;
+    else s->lost_frames = 0;
+}
+
 void ptam_motion_update(ptam_motion_model* m, const ptam_trackmap_result* r) {
     if (!m || !r) return;
     std::memcpy(m->pose, r->pose, 96);

@@ -35,4 +35,35 @@ int sbi_batch_launch_make(const ptam_rotation_estimator* lead, int n, const SbiB
 struct KfLevels;
 int sbi_batch_launch_align(const ptam_rotation_estimator* lead, int n, const SbiBatchRec* d_recs, hipStream_t st, int nb_detect = 0,
                            const KfLevels* L = nullptr, const void* det_items = nullptr, size_t det_stride = 0, size_t det_off = 0);
+// ---- a batch's recovering cameras (ptam_track_frames_recover_batch): Relocaliser::AttemptRecovery inside the frames' chain ----
+// One recovering camera, in device memory.  Its relocaliser image is made by a make launch of its own (the blur differs from the
+// estimators') from an SbiBatchRec whose l3 / small / tmpl / jacs are filled; row y of the SSD launch takes record y's image against
+// every entry of its bank into the camera's OWN table (a bank may serve several cameras); an align workgroup behind the estimators'
+// takes the arg-min, aligns, and thread 0 forms mse3Best, decides `good` and writes pose, result and gate.
+struct SbiRelocRec {
+    const float* cur;               // the scratch image's mimTemplate
+    const float* bank_tmpl;         // entry 0's mimTemplate / mimImageJacs
+    const float* bank_jacs;
+    const double* bank_poses;       // se3CfromW of the entries, 12 doubles each
+    double* ssd;                    // [count]
+    int count, pad_;
+    double max_score;
+    double* pose_out;               // the frame's pose on the device, written when good
+    ptam_reloc_result* h_reloc;     // host-mapped
+    int* gate;                      // 1: good, the frame's TrackMap kernels run; 0: they return at once
+};
+// refusals, host only: PTAM_E_ARG / PTAM_E_STATE as ptam_track_frames_recover_batch lists them
+int sbi_reloc_check(const ptam_sbi_bank* b, const ptam_sbi* scratch, int device, const ptam_kf* kf);
+void sbi_reloc_rec(const ptam_sbi_bank* b, const ptam_sbi* scratch, const ptam_kf* kf, SbiBatchRec* make_rec, SbiRelocRec* rec);
+void sbi_reloc_commit(ptam_sbi* scratch);   // the scratch holds an image
+ptam_ctx* sbi_bank_ctx(const ptam_sbi_bank* b);
+// the camera positions (-R^T t, 3 doubles each) of the bank's host mirror of its poses: *count entries; nullptr while a pose was never set
+const double* sbi_bank_camera_positions(const ptam_sbi_bank* b, int* count);
+// the launches on `st`; ctx: the lead tracker's (halfSample variant, camera), b: a bank of the batch (image size)
+int sbi_reloc_launch_make(ptam_ctx* ctx, const ptam_sbi_bank* b, double blur, int n, const SbiBatchRec* d_recs, hipStream_t st);
+int sbi_reloc_launch_ssd(const ptam_sbi_bank* b, int n, int max_count, const SbiRelocRec* d_rrecs, hipStream_t st);
+// sbi_batch_launch_align with n_reloc relocaliser workgroups between the n_est estimator ones (n_est may be 0) and the detection's
+int sbi_recover_launch_align(ptam_ctx* ctx, const ptam_sbi_bank* b, int n_est, const SbiBatchRec* d_recs, int n_reloc, const SbiRelocRec* d_rrecs,
+                             hipStream_t st, int nb_detect, const KfLevels* L, const void* det_items, size_t det_stride, size_t det_off);
+bool sbi_estimator_fits_bank(const ptam_rotation_estimator* e, const ptam_sbi_bank* b);   // same frame size
 bool sbi_estimators_alike(const ptam_rotation_estimator* a, const ptam_rotation_estimator* b);   // same image size and blur

@@ -108,6 +108,27 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_ssd_kernel(const float* __res
         if (h_ssd) h_ssd[blockIdx.x] = s;   // (host-mapped; the align kernel's sequence word, later on the same queue, covers it)
     }
 }
+// ... for a batch's recovering cameras: row y is camera y's image against its own bank, into its own table; the sums are sbi_ssd_kernel's
+__global__ __launch_bounds__(SBI_THREADS) void sbi_ssd_batch_kernel(const SbiRelocRec* __restrict__ recs, int n) {
+    __shared__ double s_part[SBI_THREADS / 64];
+    const SbiRelocRec& r = recs[blockIdx.y];
+    if ((int)blockIdx.x >= r.count) return;
+    const float* __restrict__ cur = r.cur;
+    const float* __restrict__ b = r.bank_tmpl + (size_t)blockIdx.x * n;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += SBI_THREADS) {
+        const double d = (double)(cur[i] - b[i]);
+        acc = nc_add(acc, nc_mul(d, d));
+    }
+    acc = wave_sum_f64(acc);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = s_part[0];
+        for (int i = 1; i < SBI_THREADS / 64; i++) s += s_part[i];
+        r.ssd[blockIdx.x] = s;
+    }
+}
 
 // ---- align: IteratePosRelToTarget (:313-417) + SE3fromSE2 (:427-476) --------------------------------------------------------
 struct SbiOut {   // host-mapped
@@ -135,6 +156,10 @@ struct SbiAlignArgs {
     const char* det_items;
     size_t det_stride, det_off;
     int det_blocks, n_align;
+    // ... and (rrecs nullable) the relocaliser of the batch's recovering cameras: workgroups n_est .. n_align - 1, one per record — the
+    // arg-min over the camera's SSD table, the alignment against that entry, then mse3Best, `good` and the frame's gate
+    const SbiRelocRec* rrecs;
+    int n_est;
 };
 
 // TooN Cholesky<N> (L D L^T, the scaled column cached in the upper half) + backsub.  false: a pivot that is not strictly positive.
@@ -261,11 +286,15 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_align_kernel(SbiAlignArgs g) 
     // equal values the lowest index.  Each thread scans every 256th entry in ascending order, then a tree over the workgroup.
     int best = -1;
     double best_ssd = 0.0;
-    if (g.ssd) {
+    const SbiRelocRec* rr = g.rrecs && (int)blockIdx.x >= g.n_est ? g.rrecs + ((int)blockIdx.x - g.n_est) : nullptr;
+    const double* __restrict__ ssd_tab = g.ssd;
+    int count = g.count;
+    if (rr) ssd_tab = rr->ssd, count = rr->count;
+    if (ssd_tab) {
         double bv = INFINITY;
         int bi = INT_MAX;
-        for (int i = tid; i < g.count; i += SBI_THREADS) {
-            const double v = g.ssd[i];
+        for (int i = tid; i < count; i += SBI_THREADS) {
+            const double v = ssd_tab[i];
             if (v < bv) bv = v, bi = i;
         }
         s_bv[tid] = bv;
@@ -281,11 +310,17 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_align_kernel(SbiAlignArgs g) 
         }
         best = s_bi[0];
         best_ssd = s_bv[0];
+        if (rr && best >= count) best = 0;   // (no SSD compared below infinity: cannot happen with images made from bytes)
     }
-    const SbiBatchRec* rec = g.recs ? g.recs + blockIdx.x : nullptr;
-    const float* __restrict__ tgt = rec ? rec->tgt_tmpl : g.tgt_tmpl + (size_t)(best > 0 ? best : 0) * n;
-    const float* __restrict__ tjac = rec ? rec->tgt_jacs : g.tgt_jacs + (size_t)(best > 0 ? best : 0) * 2 * n;
+    const SbiBatchRec* rec = g.recs && !rr ? g.recs + blockIdx.x : nullptr;
+    const float *tgt_base = g.tgt_tmpl, *tjac_base = g.tgt_jacs;
+    if (rr) tgt_base = rr->bank_tmpl, tjac_base = rr->bank_jacs;
+    const float* __restrict__ tgt = rec ? rec->tgt_tmpl : tgt_base + (size_t)(best > 0 ? best : 0) * n;
+    const float* __restrict__ tjac = rec ? rec->tgt_jacs : tjac_base + (size_t)(best > 0 ? best : 0) * 2 * n;
     const float* __restrict__ cur = rec ? rec->tmpl : g.cur;
+    // (volatile: otherwise the compiler selects among the three ADDRESSES the pointer is read from, which needs a copy of g.cur in scratch
+    //  memory, and a kernel that needs scratch is dispatched later)
+    if (rr) cur = *(const float* const volatile*)&rr->cur;
     for (int i = tid; i < n; i += SBI_THREADS) s_cur[i] = cur[i];
     // thread 0's state
     double R2[4] = {1.0, 0.0, 0.0, 1.0}, t2[2] = {0.0, 0.0}, mean_offset = 0.0, score = 0.0;
@@ -450,6 +485,36 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_align_kernel(SbiAlignArgs g) 
             __threadfence_system();
             return;
         }
+        if (rr) {
+            // mse3Best = rotation * se3CfromW(best) in ptam_relocalise's operation order, never contracted: the host's bits.  The pose
+            // goes where the frame's PVS pass reads it, the verdict into the frame's gate (the TrackMap kernels behind this launch
+            // read it at their start) and everything into the frame's host-mapped block, which the frame's last kernel publishes.
+            const double* K = rr->bank_poses + (size_t)best * 12;
+            const double* R = o.rotation;
+            double pose[12];   // (unrolled: a dynamically indexed local array is scratch memory)
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+#pragma unroll
+                for (int j = 0; j < 3; j++)
+                    pose[3 * i + j] = nc_add(nc_add(nc_mul(R[3 * i], K[j]), nc_mul(R[3 * i + 1], K[3 + j])), nc_mul(R[3 * i + 2], K[6 + j]));
+                pose[9 + i] = nc_add(nc_add(nc_mul(R[3 * i], K[9]), nc_mul(R[3 * i + 1], K[10])), nc_mul(R[3 * i + 2], K[11]));
+            }
+            const int good = o.score < rr->max_score ? 1 : 0;
+            ptam_reloc_result* out = rr->h_reloc;
+            out->best = best;
+            out->good = good;
+            out->best_ssd = best_ssd;
+            out->align = o;
+#pragma unroll
+            for (int i = 0; i < 12; i++) out->pose[i] = pose[i];
+            if (good) {
+#pragma unroll
+                for (int i = 0; i < 12; i++) rr->pose_out[i] = pose[i];
+            }
+            *rr->gate = good;
+            __threadfence_system();
+            return;
+        }
         g.out->a = o;
         g.out->best = best;
         g.out->pad_ = 0;
@@ -484,6 +549,11 @@ struct ptam_sbi_bank {
     double* ssd;   // [capacity]
     const uint8_t** l3_list;   // [capacity]: the level-3 images of a batch that is being added
     int capacity, count;
+    // se3CfromW of the entries (ptam_sbi_bank_set_poses): on the device for mse3Best, and the host's mirror of it
+    double* d_poses;                // [capacity][12]
+    std::vector<double> h_poses;    // [capacity][12]
+    std::vector<double> h_campos;   // [capacity][3]: the camera positions -R^T t of the mirror (the closest-keyframe walk reads these)
+    std::vector<char> pose_set;     // [capacity]
 };
 struct ptam_rotation_estimator {
     ptam_ctx* ctx;
@@ -581,6 +651,7 @@ static int sbi_align(ptam_ctx* ctx, const SbiGeom& g, const float* cur, const Sb
     a.out = (SbiOut*)((char*)ctx->d_pinned + pin_offset);
     a.recs = nullptr;
     a.det_items = nullptr, a.det_stride = a.det_off = 0, a.det_blocks = a.n_align = 0;
+    a.rrecs = nullptr, a.n_est = 0;
     a.seq = ++ctx->pose_seq;
     volatile SbiOut* h_out = (volatile SbiOut*)((char*)hp + pin_offset);
     h_out->seq = 0;   // (the staging buffer is shared: no stale sequence numbers)
@@ -595,6 +666,7 @@ void sbi_preload_kernels() {
     ptam_preload((const void*)sbi_make_kernel<PTAM_HALFSAMPLE_R>);
     ptam_preload((const void*)sbi_make_kernel<PTAM_HALFSAMPLE_T>);
     ptam_preload((const void*)sbi_ssd_kernel);
+    ptam_preload((const void*)sbi_ssd_batch_kernel);
     ptam_preload((const void*)sbi_align_kernel);
 }
 
@@ -631,39 +703,97 @@ void sbi_estimator_rollback(ptam_rotation_estimator* e) { e->pending = -1; }
 bool sbi_estimators_alike(const ptam_rotation_estimator* a, const ptam_rotation_estimator* b) {
     return a->blur == b->blur && a->slot[0]->g.fw == b->slot[0]->g.fw && a->slot[0]->g.fh == b->slot[0]->g.fh;
 }
-int sbi_batch_launch_make(const ptam_rotation_estimator* lead, int n, const SbiBatchRec* d_recs, hipStream_t st) {
-    const SbiGeom& g = lead->slot[0]->g;
+// the make launch for n records: image b from record b's level 3 into record b's three arrays
+static int sbi_make_recs(const ptam_ctx* ctx, const SbiGeom& g, double blur, int n, const SbiBatchRec* d_recs, hipStream_t st) {
     SbiMakeArgs a;
     a.l3 = nullptr, a.l3_list = nullptr, a.recs = d_recs;
     a.w3 = g.w3, a.w = g.w, a.h = g.h;
     a.small = nullptr, a.tmpl = nullptr, a.jacs = nullptr;
-    sbi_make_weights(lead->blur, &a);
-    if (lead->ctx->halfsample == PTAM_HALFSAMPLE_T)
+    sbi_make_weights(blur, &a);
+    if (ctx->halfsample == PTAM_HALFSAMPLE_T)
         hipLaunchKernelGGL(sbi_make_kernel<PTAM_HALFSAMPLE_T>, dim3(n), dim3(SBI_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL(sbi_make_kernel<PTAM_HALFSAMPLE_R>, dim3(n), dim3(SBI_THREADS), 0, st, a);
     HIP_TRY(hipGetLastError());
     return PTAM_OK;
 }
-int sbi_batch_launch_align(const ptam_rotation_estimator* lead, int n, const SbiBatchRec* d_recs, hipStream_t st, int nb_detect, const KfLevels* L,
-                           const void* det_items, size_t det_stride, size_t det_off) {
-    const SbiGeom& g = lead->slot[0]->g;
+// the align launch: n_est estimator workgroups, n_reloc relocaliser workgroups, then the detection's
+static int sbi_align_recs(const ptam_ctx* ctx, const SbiGeom& g, int n_est, const SbiBatchRec* d_recs, int n_reloc, const SbiRelocRec* d_rrecs,
+                          hipStream_t st, int nb_detect, const KfLevels* L, const void* det_items, size_t det_stride, size_t det_off) {
     SbiAlignArgs a;
     a.cur = a.tgt_tmpl = a.tgt_jacs = nullptr;
     a.ssd = nullptr;
     a.count = 0;
-    a.w = g.w, a.h = g.h, a.iterations = 6;   // (sbi_estimator_step's)
-    a.cam = sbi_camera(lead->ctx, g);
+    a.w = g.w, a.h = g.h, a.iterations = 6;   // (sbi_estimator_step's and ptam_relocalise's)
+    a.cam = sbi_camera(ctx, g);
     a.out = nullptr;
     a.seq = 0;
     a.recs = d_recs;
     a.det_items = nb_detect > 0 ? (const char*)det_items : nullptr;
     a.det_stride = det_stride, a.det_off = det_off;
     a.det_blocks = nb_detect > 0 ? fast_detect_tall_blocks(*L) : 0;
-    a.n_align = n;
-    hipLaunchKernelGGL(sbi_align_kernel, dim3(n + nb_detect * a.det_blocks), dim3(SBI_THREADS), 0, st, a);
+    a.n_align = n_est + n_reloc;
+    a.rrecs = n_reloc > 0 ? d_rrecs : nullptr, a.n_est = n_est;
+    hipLaunchKernelGGL(sbi_align_kernel, dim3(a.n_align + nb_detect * a.det_blocks), dim3(SBI_THREADS), 0, st, a);
     HIP_TRY(hipGetLastError());
     return PTAM_OK;
+}
+int sbi_batch_launch_make(const ptam_rotation_estimator* lead, int n, const SbiBatchRec* d_recs, hipStream_t st) {
+    return sbi_make_recs(lead->ctx, lead->slot[0]->g, lead->blur, n, d_recs, st);
+}
+int sbi_batch_launch_align(const ptam_rotation_estimator* lead, int n, const SbiBatchRec* d_recs, hipStream_t st, int nb_detect, const KfLevels* L,
+                           const void* det_items, size_t det_stride, size_t det_off) {
+    return sbi_align_recs(lead->ctx, lead->slot[0]->g, n, d_recs, 0, nullptr, st, nb_detect, L, det_items, det_stride, det_off);
+}
+
+// ---- the recovering cameras of a batch (ptam_track_frames_recover_batch) ----
+int sbi_reloc_check(const ptam_sbi_bank* b, const ptam_sbi* scratch, int device, const ptam_kf* kf) {
+    ARG_TRY(b && scratch);
+    ARG_TRY(b->ctx->device == device && scratch->ctx->device == device);
+    ARG_TRY(scratch->g.fw == b->g.fw && scratch->g.fh == b->g.fh);
+    if (int rc = sbi_check_kf(b->ctx, b->g, kf)) return rc;
+    if (b->count < 1) {
+        ptam_set_error("a recovering camera's bank is empty");
+        return PTAM_E_STATE;
+    }
+    for (int i = 0; i < b->count; i++)
+        if (!b->pose_set[(size_t)i]) {
+            ptam_set_error("the pose of bank entry %d was never set (ptam_sbi_bank_set_poses)", i);
+            return PTAM_E_STATE;
+        }
+    return PTAM_OK;
+}
+void sbi_reloc_rec(const ptam_sbi_bank* b, const ptam_sbi* scratch, const ptam_kf* kf, SbiBatchRec* mk, SbiRelocRec* rec) {
+    mk->l3 = kf->L.im[3];
+    mk->small = scratch->im.small, mk->tmpl = scratch->im.tmpl, mk->jacs = scratch->im.jacs;
+    rec->cur = scratch->im.tmpl;
+    rec->bank_tmpl = b->im.tmpl, rec->bank_jacs = b->im.jacs;
+    rec->bank_poses = b->d_poses;
+    rec->count = b->count;
+}
+void sbi_reloc_commit(ptam_sbi* scratch) { scratch->made = 1; }
+ptam_ctx* sbi_bank_ctx(const ptam_sbi_bank* b) { return b->ctx; }
+const double* sbi_bank_camera_positions(const ptam_sbi_bank* b, int* count) {
+    *count = b->count;
+    for (int i = 0; i < b->count; i++)
+        if (!b->pose_set[(size_t)i]) return nullptr;
+    return b->h_campos.data();
+}
+int sbi_reloc_launch_make(ptam_ctx* ctx, const ptam_sbi_bank* b, double blur, int n, const SbiBatchRec* d_recs, hipStream_t st) {
+    ARG_TRY(blur > 0.0 && blur <= 5.0);
+    return sbi_make_recs(ctx, b->g, blur, n, d_recs, st);
+}
+int sbi_reloc_launch_ssd(const ptam_sbi_bank* b, int n, int max_count, const SbiRelocRec* d_rrecs, hipStream_t st) {
+    hipLaunchKernelGGL(sbi_ssd_batch_kernel, dim3(max_count, n), dim3(SBI_THREADS), 0, st, d_rrecs, b->g.w * b->g.h);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+int sbi_recover_launch_align(ptam_ctx* ctx, const ptam_sbi_bank* b, int n_est, const SbiBatchRec* d_recs, int n_reloc, const SbiRelocRec* d_rrecs,
+                             hipStream_t st, int nb_detect, const KfLevels* L, const void* det_items, size_t det_stride, size_t det_off) {
+    return sbi_align_recs(ctx, b->g, n_est, d_recs, n_reloc, d_rrecs, st, nb_detect, L, det_items, det_stride, det_off);
+}
+bool sbi_estimator_fits_bank(const ptam_rotation_estimator* e, const ptam_sbi_bank* b) {
+    return e->slot[0]->g.fw == b->g.fw && e->slot[0]->g.fh == b->g.fh;
 }
 
 extern "C" {
@@ -744,12 +874,16 @@ int ptam_sbi_bank_create(ptam_ctx* ctx, int frame_w, int frame_h, int capacity, 
     ptam_sbi_bank* b = new ptam_sbi_bank();
     b->ctx = ctx, b->g = g, b->capacity = capacity, b->count = 0;
     void* x;
-    if (int rc = sbi_alloc(g, capacity, (size_t)capacity * 16, &b->block, &b->im, &x)) {
+    if (int rc = sbi_alloc(g, capacity, (size_t)capacity * (16 + 96), &b->block, &b->im, &x)) {
         delete b;
         return rc;
     }
     b->ssd = (double*)x;
     b->l3_list = (const uint8_t**)(b->ssd + capacity);
+    b->d_poses = (double*)((char*)x + (size_t)capacity * 16);
+    b->h_poses.assign((size_t)capacity * 12, 0.0);
+    b->h_campos.assign((size_t)capacity * 3, 0.0);
+    b->pose_set.assign((size_t)capacity, 0);
     *out = b;
     return PTAM_OK;
 }
@@ -803,6 +937,37 @@ int ptam_sbi_bank_add_batch(ptam_sbi_bank* b, int n, const ptam_kf* const* kfs, 
 int ptam_sbi_bank_count(const ptam_sbi_bank* b, int* n) {
     ARG_TRY(b && n);
     *n = b->count;
+    return PTAM_OK;
+}
+
+int ptam_sbi_bank_set_poses(ptam_sbi_bank* b, int first, int n, const double* poses12) {
+    ARG_TRY(b && poses12 && first >= 0 && n >= 1 && n <= b->count && first <= b->count - n);
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    double* h = b->h_poses.data() + (size_t)first * 12;
+    // (the mirror is the copy's source and lives as long as the bank; a second set of the same entries waits for the first copy)
+    for (int i = first; i < first + n; i++)
+        if (b->pose_set[(size_t)i]) {
+            HIP_TRY(ptam_stream_wait(b->ctx->stream));
+            break;
+        }
+    std::memcpy(h, poses12, (size_t)n * 96);
+    HIP_TRY(hipMemcpyAsync(b->d_poses + (size_t)first * 12, h, (size_t)n * 96, hipMemcpyHostToDevice, b->ctx->stream));
+    for (int i = first; i < first + n; i++) {
+        b->pose_set[(size_t)i] = 1;
+        const double* p = b->h_poses.data() + (size_t)i * 12;   // se3CfromW.inverse().get_translation(), src/MapMaker.cc:698
+        for (int k = 0; k < 3; k++) b->h_campos[(size_t)i * 3 + k] = -(p[k] * p[9] + p[3 + k] * p[10] + p[6 + k] * p[11]);
+    }
+    return PTAM_OK;
+}
+
+int ptam_sbi_bank_poses(const ptam_sbi_bank* b, int first, int n, double* poses_out12) {
+    ARG_TRY(b && poses_out12 && first >= 0 && n >= 1 && n <= b->count && first <= b->count - n);
+    for (int i = first; i < first + n; i++)
+        if (!b->pose_set[(size_t)i]) {
+            ptam_set_error("the pose of bank entry %d was never set", i);
+            return PTAM_E_STATE;
+        }
+    std::memcpy(poses_out12, b->h_poses.data() + (size_t)first * 12, (size_t)n * 96);
     return PTAM_OK;
 }
 

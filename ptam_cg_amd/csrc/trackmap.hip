@@ -478,6 +478,8 @@ struct TmMailbox {
     // frame's align workgroup (sbi.hip) — covered by the sequence word, which a later kernel of the same queue publishes
     ptam_sbi_alignment align;
     double pose_in[12];
+    // ptam_track_frames_recover_batch, a recovering frame: the relocaliser's result, written by the frame's align workgroup likewise
+    ptam_reloc_result reloc;
 };
 // the last act of a gather pass: thread 0 books the per-level counts and the stage's outcome (coarse: mbDidCoarse and the
 // fine range; fine: everything of the frame's result but the pose and the depth sums)
@@ -831,7 +833,12 @@ struct TmBatchItem {
     // the frame's own bTryCoarse heuristics (src/Tracker.cc:503-514); ptam_track_map_frames_batch fills every frame with its one opts
     int try_coarse;
     unsigned coarse_max, coarse_range;
+    // a recovering frame (ptam_track_frames_recover_batch; null otherwise): the relocaliser's verdict, written by the frame's align
+    // workgroup in a launch in front of every kernel that reads it.  0: nothing of TrackMap happens — the kernels of the frame return
+    // at their start, and the fine pose kernel only publishes the frame's sequence word
+    const int* gate;
 };
+__device__ __forceinline__ bool tm_gated_off(const TmBatchItem& it) { return it.gate && !*it.gate; }
 template <int VARIANT>
 __global__ void __launch_bounds__(256) tm_pyr_pvs_batch_kernel(const TmBatchItem* __restrict__ items, int gx, DevCam cam) {
     const TmBatchItem& it = items[blockIdx.y];
@@ -844,12 +851,14 @@ __global__ void __launch_bounds__(256) tm_pyr_pvs_batch_kernel(const TmBatchItem
 // the PVS pass of the frames whose pose was made on the device: row y works on frame idx[y], the pose is read from the frame's d.pose
 __global__ void __launch_bounds__(256) tm_pvs_batch_kernel(const TmBatchItem* __restrict__ items, const int* __restrict__ idx, DevCam cam) {
     const TmBatchItem& it = items[idx[blockIdx.y]];
+    if (tm_gated_off(it)) return;
     if ((int)blockIdx.x * 256 < max(it.n, 1))
         track_pvs_body(cam, it.n, it.d.pts, it.d.pose, it.d.pvs, nullptr, it.pv, it.d.pose, blockIdx.x, &it.d.finder->bad, (int)sizeof(TmFinder));
 }
 __global__ void __launch_bounds__(1024) tm_compact_select_batch_kernel(const TmBatchItem* __restrict__ items, ptam_trackmap_opts o) {
     const TmBatchItem& it = items[blockIdx.y];
     if (blockIdx.x == 0) {
+        if (tm_gated_off(it)) return;
         o.try_coarse = it.try_coarse;
         o.coarse_max = it.coarse_max;
         o.coarse_range = it.coarse_range;
@@ -859,6 +868,7 @@ __global__ void __launch_bounds__(1024) tm_compact_select_batch_kernel(const TmB
 }
 __global__ void __launch_bounds__(256) tm_search_batch_kernel(DevCam cam, const TmBatchItem* __restrict__ items, int stage, int coarse_its) {
     const TmBatchItem& it = items[blockIdx.y];
+    if (tm_gated_off(it)) return;
     tm_search_body(cam, it.L, it.d, stage, it.coarse_range, coarse_its, blockIdx.x);
 }
 __global__ void __launch_bounds__(TM_GATHER_THREADS) tm_gather_batch_kernel(const TmBatchItem* __restrict__ items, int stage, int coarse_its,
@@ -875,6 +885,14 @@ __global__ void __launch_bounds__(THREADS) tm_pose_batch_kernel(DevCam cam, cons
     const int f = idx ? idx[blockIdx.x] : (int)blockIdx.x;
     const TmBatchItem& it = items[f];
     const PoseBatchItem& pi = pitems[f];
+    if (tm_gated_off(it)) {
+        // (the relocaliser's result is in the frame's host-mapped block since the align launch, behind a system fence)
+        if (stage == 1 && threadIdx.x == 0) {
+            __threadfence_system();
+            *(volatile unsigned long long*)pi.io.result_seq = pi.io.seq;
+        }
+        return;
+    }
     tm_pose_body<MPT, THREADS>(cam, it.d, stage, coarse_min, it.mbox, opts, pi.io, pi.updates, stage == 1 && it.n > GS_LIMIT ? pi.io.seq : 0ull);
 }
 typedef void (*tm_pose_batch_fn)(DevCam, const TmBatchItem*, const PoseBatchItem*, const int*, int, unsigned, ptam_gn_opts);
@@ -897,6 +915,10 @@ struct ptam_tracker {
     // argument arrays of the batches this tracker leads (ptam_track_map_frames_batch): grown on demand
     void* batch_dev;
     size_t batch_cap;
+    // the recovering cameras' SSD tables of the last batch this tracker led (inside batch_dev): rows x stride, row r holds reloc_count[r]
+    const double* reloc_ssd;
+    int reloc_stride;
+    std::vector<int>* reloc_count;
     hipStream_t last_stream;   // the queue that last ran this tracker (its own context's, or a batch's lead tracker's)
     // ptam_tracker_take_map: the serials of the map's points (device, [cap]; valid iff has_serials), the map they belong to and
     // the (snapshot, generation) they were taken from.  ptam_tracker_set_map / update_map clear all of it.
@@ -1127,6 +1149,7 @@ int ptam_tracker_destroy(ptam_tracker* t) {
     if (t->mbox) hipHostFree(t->mbox);
     if (t->perm_host) hipHostFree(t->perm_host);
     if (t->batch_dev) hipFree(t->batch_dev);
+    delete t->reloc_count;
     if (t->ev[0])
         for (int i = 0; i <= PTAM_TS_COUNT; i++) hipEventDestroy(t->ev[i]);
     delete t;
@@ -1594,6 +1617,7 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
     for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i] && d_frames[i]);
     ptam_tracker* lead = ts[0];
     ptam_ctx* ctx = lead->ctx;
+    if (lead->reloc_count) lead->reloc_count->clear();   // (the argument block is rewritten: ptam_tracker_read_reloc_ssd has no rows)
     ptam_trackmap_opts o;
     int rc = tm_opts(opts, &o);
     if (rc) return rc;
@@ -1716,9 +1740,22 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
 // Every frame's pose loops run in the kernel instantiation its OWN list lengths select (the frames of one instantiation share a
 // launch), so a frame's result is the single call's bit for bit; a fine list that outgrows the fused kernel is finished on the
 // frame's own queue after the wait, as in the single call.
-int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_motion_model* models,
-                            ptam_rotation_estimator* const* ests, const ptam_trackmap_opts* opts, ptam_trackmap_result* outs,
-                            ptam_track_frame_info* info) {
+// rv (nullable): ptam_track_frames_recover_batch's recovering cameras — rv->recovering[i] != 0: frame i runs the relocaliser in the
+// chain instead of a prediction, and TrackMap behind it only where the relocaliser's verdict is good (TmBatchItem::gate).  The caller
+// has checked their banks and scratches.  Without rv, or with no camera recovering, nothing below differs from the plain batch.
+struct TfbRecover {
+    const char* recovering;           // [nb]
+    ptam_sbi_bank* const* banks;      // [nb]
+    ptam_sbi* const* scratch;         // [nb]
+    double blur, max_score;
+    ptam_reloc_result* reloc;         // out: the recovering frames' results, frame i's reloc_stride bytes behind frame i - 1's
+    size_t reloc_stride;
+};
+static int tfb_impl(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_motion_model* models,
+                    ptam_rotation_estimator* const* ests, const ptam_trackmap_opts* opts, ptam_trackmap_result* outs, ptam_track_frame_info* info,
+                    size_t info_stride, const TfbRecover* rv) {
+    // (info_stride: frame i's info lies that many bytes behind frame i - 1's — inside the caller's own per-frame struct, or an array)
+    auto info_at = [&](int i) -> ptam_track_frame_info& { return *(ptam_track_frame_info*)((char*)info + (size_t)i * info_stride); };
     // ---- everything that needs no device ----
     ARG_TRY(nb >= 1 && nb <= 4096 && ts && curs && d_frames && models && outs);
     for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i] && d_frames[i]);
@@ -1736,15 +1773,32 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
         for (int j = 0; j < i; j++) ARG_TRY(ts[j] != ts[i] && curs[j] != curs[i] && ts[j]->ctx != ts[i]->ctx);   // (a context's scratch serves ONE frame)
     }
     // the estimators: each its tracker's context's, none twice, all of one image size and blur (their images are made in one launch)
+    // (those of recovering frames last: their images are made with the others', but nothing is aligned, src/Tracker.cc:94-108 + :168-176)
+    auto recovering = [&](int i) { return rv && rv->recovering[i]; };
     std::vector<int> est_of;   // the frames that have one
-    for (int i = 0; ests && i < nb; i++) {
-        if (!ests[i]) continue;
-        ARG_TRY(sbi_estimator_ctx(ests[i]) == ts[i]->ctx);
-        for (int j : est_of) ARG_TRY(ests[j] != ests[i]);
-        if (!est_of.empty()) ARG_TRY(sbi_estimators_alike(ests[est_of[0]], ests[i]));
-        est_of.push_back(i);
-    }
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; ests && i < nb; i++) {
+            if (!ests[i] || (int)recovering(i) != pass) continue;
+            ARG_TRY(sbi_estimator_ctx(ests[i]) == ts[i]->ctx);
+            for (int j : est_of) ARG_TRY(ests[j] != ests[i]);
+            if (!est_of.empty()) ARG_TRY(sbi_estimators_alike(ests[est_of[0]], ests[i]));
+            est_of.push_back(i);
+        }
     const int n_est = (int)est_of.size();
+    std::vector<int> rr_of;    // the recovering frames
+    for (int i = 0; i < nb; i++)
+        if (recovering(i)) rr_of.push_back(i);
+    const int n_rr = (int)rr_of.size();
+    int n_est_align = 0, rr_max_count = 0;
+    for (int i : est_of) n_est_align += !recovering(i);
+    const ptam_sbi_bank* bank0 = n_rr ? rv->banks[rr_of[0]] : nullptr;
+    if (lead->reloc_count) lead->reloc_count->clear();
+    for (int i : rr_of) {
+        int c;
+        sbi_bank_camera_positions(rv->banks[i], &c);
+        rr_max_count = std::max(rr_max_count, c);
+        if (ests && ests[i]) ARG_TRY(sbi_estimator_fits_bank(ests[i], rv->banks[i]));
+    }
     // the heuristics, per frame, as ptam_track_frame has them (src/Tracker.cc:503-514); the models advance on copies
     std::vector<ptam_motion_model> tmp(models, models + nb);
     std::vector<ptam_trackmap_opts> fo((size_t)nb, o);
@@ -1753,6 +1807,15 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
         ptam_trackmap_opts& f = fo[(size_t)i];
         f.try_coarse = 1;
         if (m.disable_coarse || m.msd_scaled_velocity < m.coarse_min_velocity || f.coarse_max == 0) f.try_coarse = 0;
+        if (recovering(i)) {   // AttemptRecovery sets mbJustRecoveredSoUseCoarse and TrackMap follows at once (:171-173, :205, :508-513)
+            f.try_coarse = 1;
+            f.coarse_max *= 2;
+            f.coarse_range *= 2;
+            ptam_trackmap_opts checked;
+            rc = tm_opts(&f, &checked);
+            if (rc) return rc;
+            continue;          // (no prediction: the relocaliser's pose is the start; the model moves after the wait, if at all)
+        }
         if (m.just_recovered) {
             f.try_coarse = 1;
             f.coarse_max *= 2;
@@ -1782,21 +1845,26 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
     hipStream_t st = ctx->stream;
     for (int i = 1; i < nb; i++)
         if (ts[i]->ctx != ctx) TFB_HIP_TRY(ptam_stream_wait(ts[i]->ctx->stream));
+    for (int i : rr_of)   // (the recovering cameras' banks are read on this queue: their adds and pose uploads must be done)
+        if (sbi_bank_ctx(rv->banks[i]) != ctx) TFB_HIP_TRY(ptam_stream_wait(sbi_bank_ctx(rv->banks[i])->stream));
     // ---- the argument arrays: [nb TmBatchItem | nb PoseBatchItem (coarse) | nb (fine) | n_est SbiBatchRec | 3 nb frame indices] ----
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_items = up((size_t)nb * sizeof(TmBatchItem)), b_pose = up((size_t)nb * sizeof(PoseBatchItem)),
-                 b_rec = up((size_t)std::max(n_est, 1) * sizeof(SbiBatchRec)), b_idx = up((size_t)nb * 4);
-    const size_t b_all = b_items + 2 * b_pose + b_rec + 3 * b_idx;
+                 b_rec = up((size_t)std::max(n_est + n_rr, 1) * sizeof(SbiBatchRec)), b_idx = up((size_t)nb * 4),
+                 b_rrec = up((size_t)n_rr * sizeof(SbiRelocRec));
+    const size_t b_all = b_items + 2 * b_pose + b_rec + 3 * b_idx + b_rrec;
+    // (device only, behind the uploaded arrays: the recovering cameras' SSD tables and gates)
+    const size_t b_ssd = up((size_t)n_rr * (size_t)rr_max_count * 8), b_dev = b_all + b_ssd + up((size_t)n_rr * 4);
     void* pin;
     rc = ctx_pinned(ctx, b_all + 64, &pin);
     if (rc) return fail(rc);
-    if (lead->batch_cap < b_all) {
+    if (lead->batch_cap < b_dev) {
         TFB_HIP_TRY(ptam_stream_wait(st));
         if (lead->batch_dev) TFB_HIP_TRY(hipFree(lead->batch_dev));
         lead->batch_dev = nullptr;
         lead->batch_cap = 0;
-        TFB_HIP_TRY(hipMalloc(&lead->batch_dev, b_all * 2));
-        lead->batch_cap = b_all * 2;
+        TFB_HIP_TRY(hipMalloc(&lead->batch_dev, b_dev * 2));
+        lead->batch_cap = b_dev * 2;
     }
     char* hb = (char*)pin;
     const char* db = (const char*)lead->batch_dev;
@@ -1811,6 +1879,15 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
     const PoseBatchItem* d_pf = (const PoseBatchItem*)(db + b_items + b_pose);
     const SbiBatchRec* d_rec = (const SbiBatchRec*)(db + b_items + 2 * b_pose);
     const int* d_idx = (const int*)(db + b_items + 2 * b_pose + b_rec);
+    SbiRelocRec* h_rrec = (SbiRelocRec*)(hb + b_items + 2 * b_pose + b_rec + 3 * b_idx);
+    const SbiRelocRec* d_rrec = (const SbiRelocRec*)(db + b_items + 2 * b_pose + b_rec + 3 * b_idx);
+    double* d_ssd = (double*)((char*)lead->batch_dev + b_all);
+    int* d_gate = (int*)((char*)lead->batch_dev + b_all + b_ssd);
+    if (n_rr > 0) {
+        if (!lead->reloc_count) lead->reloc_count = new std::vector<int>();
+        lead->reloc_ssd = d_ssd;
+        lead->reloc_stride = rr_max_count;
+    }
     int gx = 0, gy = 0, n_max = 0, ncc_max = 1;
     std::vector<int> shape_c((size_t)nb), shape_f((size_t)nb);
     std::vector<unsigned long long> seqs((size_t)nb);
@@ -1827,7 +1904,7 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
         it.d = t->d;
         it.mbox = t->mbox_dev;
         it.try_coarse = f.try_coarse, it.coarse_max = f.coarse_max, it.coarse_range = f.coarse_range;
-        if (!(ests && ests[i])) {
+        if (!(ests && ests[i]) && !recovering(i)) {
             std::memcpy(it.pv.v, tmp[(size_t)i].pose, 96);
             it.pv.use = 1;
         }
@@ -1844,6 +1921,10 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
         h_pc[i] = tm_pose_item(t, 0, ncc, su, sst, 0);
         h_pf[i] = tm_pose_item(t, 1, std::max(n, 1), su, sst, seqs[(size_t)i]);
     }
+    if (n_rr > 0 && (tm_no_fuse || ncc_max > GS_LIMIT)) {
+        ptam_set_error("a recovering camera in a batch whose coarse lists exceed the fused pose kernels' %d entries", GS_LIMIT);
+        return fail(PTAM_E_ARG);
+    }
     for (int k = 0; k < n_est; k++) {
         const int i = est_of[(size_t)k];
         SbiBatchRec& r = h_rec[k];
@@ -1855,8 +1936,27 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
         r.pose_out = ts[i]->d.pose;
         r.h_align = &ts[i]->mbox_dev->align;
         r.h_pose_in = ts[i]->mbox_dev->pose_in;
-        h_idx[k] = i;
     }
+    // the recovering frames: a make record behind the estimators', and the relocaliser's record
+    for (int k = 0; k < n_rr; k++) {
+        const int i = rr_of[(size_t)k];
+        SbiBatchRec& mk = h_rec[n_est + k];
+        SbiRelocRec& r = h_rrec[k];
+        std::memset(&mk, 0, sizeof mk);
+        std::memset(&r, 0, sizeof r);
+        sbi_reloc_rec(rv->banks[i], rv->scratch[i], curs[i], &mk, &r);
+        r.ssd = d_ssd + (size_t)k * (size_t)rr_max_count;
+        r.max_score = rv->max_score;
+        r.pose_out = ts[i]->d.pose;
+        r.h_reloc = &ts[i]->mbox_dev->reloc;
+        r.gate = d_gate + k;
+        h_it[i].gate = d_gate + k;
+        lead->reloc_count->push_back(r.count);
+    }
+    // the frames whose pose is made on the device (their PVS pass runs behind the align launch): the aligned ones, then the recovering
+    int n_dev_pose = 0;
+    for (int k = 0; k < n_est_align; k++) h_idx[n_dev_pose++] = est_of[(size_t)k];
+    for (int i : rr_of) h_idx[n_dev_pose++] = i;
     // the frames of every pose-kernel instantiation, stage by stage: n_shape[stage][k] frames from first[stage][k] on
     int n_shape[2][3] = {{0, 0, 0}, {0, 0, 0}}, first[2][3];
     for (int sg = 0; sg < 2; sg++) {
@@ -1879,9 +1979,21 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
     hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_pyr_pvs_batch_kernel), dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, gx, ctx->cam);
     // (the detection shares the align launch: its workgroups fill the chip under the align workgroups' ~100 us of serial chain, and
     //  a launch boundary goes — 6-9 % per frame up to 64 cameras, 2-4 % slower at 128; docs/LOG_sbi.md)
-    const bool share = !tfb_plain && n_est > 0;
+    const bool share = !tfb_plain && n_est + n_rr > 0;
     if (!share) kf_launch_detect_batch(nb, L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L), st);
-    if (n_est > 0) {
+    if (n_rr > 0) {
+        // a recovering camera in the batch: the relocaliser's images (a make launch of their own: the weights are a launch argument and
+        // the blur is not the estimators'), every recovering camera's SSDs in one launch, and their align workgroups between the
+        // estimators' and the detection's
+        if (n_est > 0) rc = sbi_batch_launch_make(ests[est_of[0]], n_est, d_rec, st);
+        if (!rc) rc = sbi_reloc_launch_make(ctx, bank0, rv->blur, n_rr, d_rec + n_est, st);
+        if (!rc) rc = sbi_reloc_launch_ssd(bank0, n_rr, rr_max_count, d_rrec, st);
+        if (!rc)
+            rc = sbi_recover_launch_align(ctx, bank0, n_est_align, d_rec, n_rr, d_rrec, st, share ? nb : 0, &L0, d_it, sizeof(TmBatchItem),
+                                          offsetof(TmBatchItem, L));
+        if (rc) return fail(rc);
+        hipLaunchKernelGGL(tm_pvs_batch_kernel, dim3(n_pvs, n_dev_pose), dim3(256), 0, st, d_it, d_idx, ctx->cam);
+    } else if (n_est > 0) {
         rc = sbi_batch_launch_make(ests[est_of[0]], n_est, d_rec, st);
         if (!rc && share) rc = sbi_batch_launch_align(ests[est_of[0]], n_est, d_rec, st, nb, &L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L));
         else if (!rc) rc = sbi_batch_launch_align(ests[est_of[0]], n_est, d_rec, st);
@@ -1929,9 +2041,39 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
     for (int i = 0; i < nb; i++) {
         ptam_motion_model& m = tmp[(size_t)i];
         const bool est = ests && ests[i];
+        if (recovering(i)) {
+            ptam_reloc_result& rr = *(ptam_reloc_result*)((char*)rv->reloc + (size_t)i * rv->reloc_stride);
+            std::memcpy(&rr, (const void*)&ts[i]->mbox->reloc, sizeof rr);
+            if (info) {
+                ptam_track_frame_info& fi = info_at(i);
+                std::memset(&fi, 0, sizeof fi);
+                if (rr.good) std::memcpy(fi.pose_in, rr.pose, 96);
+                fi.try_coarse = fo[(size_t)i].try_coarse;
+                fi.coarse_max = fo[(size_t)i].coarse_max;
+                fi.coarse_range = fo[(size_t)i].coarse_range;
+            }
+            if (rr.good) {
+                // Tracker::AttemptRecovery :203-205, then TrackMap and no UpdateMotionModel (:171-175): the scene depth of :692-696 is
+                // all that ptam_motion_update would do here
+                std::memcpy(m.pose, outs[i].pose, 96);
+                std::memcpy(m.start_pose, rr.pose, 96);
+                std::memset(m.velocity, 0, sizeof m.velocity);
+                m.just_recovered = 0;
+                if (outs[i].depth_n > 20) {
+                    m.scene_depth_mean = outs[i].depth_sum / outs[i].depth_n;
+                    m.scene_depth_sigma = std::sqrt(outs[i].depth_sum_sq / outs[i].depth_n - m.scene_depth_mean * m.scene_depth_mean);
+                }
+                models[i] = m;
+            } else {
+                std::memset(outs + i, 0, sizeof outs[i]);   // (the mailbox still holds the frame before: nothing of TrackMap ran)
+            }
+            sbi_reloc_commit(rv->scratch[i]);
+            if (est) sbi_estimator_commit(ests[i]);
+            continue;
+        }
         if (est) std::memcpy(m.pose, (const void*)ts[i]->mbox->pose_in, 96);
         if (info) {
-            ptam_track_frame_info& fi = info[i];
+            ptam_track_frame_info& fi = info_at(i);
             std::memset(&fi, 0, sizeof fi);
             std::memcpy(fi.pose_in, m.pose, 96);
             if (est) std::memcpy(&fi.align, (const void*)&ts[i]->mbox->align, sizeof fi.align);
@@ -1943,6 +2085,101 @@ int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* cur
         models[i] = m;
         if (est) sbi_estimator_commit(ests[i]);
     }
+    return PTAM_OK;
+}
+
+int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_motion_model* models,
+                            ptam_rotation_estimator* const* ests, const ptam_trackmap_opts* opts, ptam_trackmap_result* outs,
+                            ptam_track_frame_info* info) {
+    return tfb_impl(nb, ts, curs, d_frames, models, ests, opts, outs, info, sizeof(ptam_track_frame_info), nullptr);
+}
+
+// the camera position of an se3CfromW: se3CfromW.inverse().get_translation() = -R^T t (KeyFrameLinearDist, src/MapMaker.cc:696-703)
+static void tfr_camera_position(const double p[12], double out[3]) {
+    for (int k = 0; k < 3; k++) out[k] = -(p[k] * p[9] + p[3 + k] * p[10] + p[6 + k] * p[11]);
+}
+
+// ---- Tracker::TrackFrame for a good map (src/Tracker.cc:127-176) for nb cameras: ptam_track_frames_batch's chain, in which a camera
+// that is lost runs the relocaliser instead of the prediction (tfb_impl with a TfbRecover); the state machine around it is host code ----
+int ptam_track_frames_recover_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_track_state* states,
+                                    ptam_rotation_estimator* const* ests, ptam_sbi_bank* const* banks, ptam_sbi* const* scratch,
+                                    const ptam_trackmap_opts* opts, const ptam_track_state_opts* state_opts, ptam_trackmap_result* outs,
+                                    ptam_track_frame_state_info* info) {
+    ARG_TRY(nb >= 1 && nb <= 4096 && ts && curs && d_frames && states && outs);
+    for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i] && d_frames[i]);
+    ptam_track_state_opts so;
+    ptam_track_state_opts_default(&so);
+    if (state_opts) so = *state_opts;
+    ARG_TRY(so.reloc_blur > 0.0 && so.reloc_blur <= 5.0);
+    // the branches (:129, :168), and the recovering cameras' refusals — before anything is enqueued or moved
+    std::vector<char> rec((size_t)nb, 0);
+    int n_rr = 0;
+    for (int i = 0; i < nb; i++) {
+        if (states[i].lost_frames < 3) continue;
+        rec[(size_t)i] = 1;
+        n_rr++;
+        if (!banks || !banks[i] || !scratch || !scratch[i]) {
+            ptam_set_error("camera %d is lost and has no %s", i, banks && banks[i] ? "scratch image" : "bank");
+            return PTAM_E_ARG;
+        }
+        if (int rc = sbi_reloc_check(banks[i], scratch[i], ts[0]->ctx->device, curs[i])) return rc;
+        ARG_TRY(std::memcmp(&sbi_bank_ctx(banks[i])->cam, &ts[0]->ctx->cam, sizeof(DevCam)) == 0);
+        for (int j = 0; j < i; j++) ARG_TRY(!rec[(size_t)j] || scratch[j] != scratch[i]);
+    }
+    std::vector<ptam_motion_model> models((size_t)nb);
+    for (int i = 0; i < nb; i++) models[(size_t)i] = states[i].model;
+    // (the frame's info and the relocaliser's result are written where they stay: info[i].frame and info[i].reloc, after every wait)
+    std::vector<ptam_track_frame_state_info> own;
+    if (!info) {
+        own.resize((size_t)nb);
+        info = own.data();
+    }
+    const size_t stride = sizeof(ptam_track_frame_state_info);
+    const TfbRecover rv = {rec.data(), banks, scratch, so.reloc_blur, so.reloc_max_score, &info[0].reloc, stride};
+    if (int rc = tfb_impl(nb, ts, curs, d_frames, models.data(), ests, opts, outs, &info[0].frame, stride, n_rr ? &rv : nullptr)) return rc;
+    // ---- every frame has arrived: the states move ----
+    for (int i = 0; i < nb; i++) {
+        ptam_track_state& s = states[i];
+        ptam_track_frame_state_info& fi = info[i];
+        if (!rec[(size_t)i]) std::memset(&fi.reloc, 0, sizeof fi.reloc);
+        fi.closest_kf = -1;
+        fi.closest_kf_dist = 0.0;
+        fi.need_new_keyframe = fi.want_keyframe = 0;
+        fi.branch = !rec[(size_t)i] ? PTAM_FRAME_TRACKED : fi.reloc.good ? PTAM_FRAME_RECOVERED : PTAM_FRAME_RECOVERY_FAILED;
+        s.frame++;                                         // :111
+        if (fi.branch != PTAM_FRAME_RECOVERY_FAILED) {
+            s.model = models[(size_t)i];
+            // ClosestKeyFrame (src/MapMaker.cc:736-752) of the tracked pose: the first strictly lowest distance
+            int count = 0;
+            const double* kp = banks && banks[i] ? sbi_bank_camera_positions(banks[i], &count) : nullptr;
+            if (kp && count > 0) {
+                double best = 9999999999.9, here[3];
+                tfr_camera_position(outs[i].pose, here);
+                for (int k = 0; k < count; k++) {
+                    const double* there = kp + 3 * (size_t)k;
+                    const double dx = there[0] - here[0], dy = there[1] - here[1], dz = there[2] - here[2];
+                    const double d = std::sqrt(dx * dx + dy * dy + dz * dz);   // KeyFrameLinearDist
+                    if (d < best) best = d, fi.closest_kf = k;
+                }
+                if (fi.closest_kf >= 0) fi.closest_kf_dist = best;
+            }
+            ptam_assess_tracking_quality(&s, outs[i].attempted, outs[i].found, fi.closest_kf_dist, &so);
+            if (fi.branch == PTAM_FRAME_TRACKED) {         // :146-161; the recovery branch decides nothing about keyframes
+                if (fi.closest_kf >= 0)                    // IsNeedNewKeyFrame, src/MapMaker.cc:754-763
+                    fi.need_new_keyframe = fi.closest_kf_dist * (1.0 / s.model.scene_depth_mean) > so.max_kf_dist_wiggle_mult * so.wiggle_scale_depth_normalized;
+                fi.want_keyframe = s.quality == PTAM_TRACK_GOOD && s.frame - s.last_keyframe_dropped > 20;
+            }
+        }
+    }
+    return PTAM_OK;
+}
+
+int ptam_tracker_read_reloc_ssd(ptam_tracker* lead, int row, int count, double* ssd_out) {
+    ARG_TRY(lead && ssd_out && lead->reloc_count && row >= 0 && row < (int)lead->reloc_count->size());
+    ARG_TRY(count >= 1 && count <= (*lead->reloc_count)[(size_t)row]);
+    HIP_TRY(hipSetDevice(lead->ctx->device));
+    HIP_TRY(ptam_stream_wait(lead->ctx->stream));
+    HIP_TRY(hipMemcpy(ssd_out, lead->reloc_ssd + (size_t)row * (size_t)lead->reloc_stride, (size_t)count * 8, hipMemcpyDeviceToHost));
     return PTAM_OK;
 }
 

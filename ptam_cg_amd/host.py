@@ -1304,6 +1304,64 @@ class Tracker:
                       coarse_range=f.coarse_range) for f in inf]
         return res, infos
 
+    def track_state(self, pose):
+        """a ptam_track_state at `pose` (Tracker::Reset, src/Tracker.cc:52-62)"""
+        s = _abi.TrackState()
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        self.lib.track_state_reset(C.byref(s), _pd(pose))
+        return s
+
+    def state_opts(self, **kw):
+        """ptam_track_state_opts with the reference's defaults, fields overridden by keyword"""
+        o = _abi.TrackStateOpts()
+        self.lib.track_state_opts_default(C.byref(o))
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        return o
+
+    @staticmethod
+    def track_frames_recover_batch(trackers, kfs, d_frames, states, estimators=None, relocalisers=None, opts=None, state_opts=None,
+                                   check=True):
+        """ptam_track_frames_recover_batch: Tracker::TrackFrame for a good map (src/Tracker.cc:127-176) for len(trackers) cameras in
+        one chain — a camera whose state says lost (lost_frames >= 3) runs the relocaliser of relocalisers[i] (a Relocaliser: its bank,
+        its poses, its scratch image) inside the chain and is tracked from its pose when that is good.  `states` (ptam_track_state
+        each) are updated in place -> (array of TRACKMAP_RESULT_DT, list of dict(branch, closest_kf, closest_kf_dist,
+        need_new_keyframe, want_keyframe, pose_in, align, try_coarse, coarse_max, coarse_range, reloc)).  An error leaves states,
+        estimators and banks as they were; check=False: -> the status of a refused call."""
+        k = len(trackers)
+        raw = lambda h: h.value if hasattr(h, "value") else int(h)
+        arr = lambda xs, f: None if xs is None else (C.c_void_p * k)(*[None if x is None or f(x) is None else raw(f(x)) for x in xs])
+        trs = (C.c_void_p * k)(*[raw(t.h) for t in trackers])
+        kf_ = (C.c_void_p * k)(*[raw(f.h) for f in kfs])
+        dis = (C.c_void_p * k)(*[raw(d.p if isinstance(d, DevBuf) else d) for d in d_frames])
+        es = arr(estimators, lambda e: e.h)
+        bs = arr(relocalisers, lambda r: r.h)
+        sc = arr(relocalisers, lambda r: None if r.scratch is None else r.scratch.h)
+        ss = (_abi.TrackState * k)(*states)      # (a contiguous copy: written back on success only)
+        res = np.zeros(k, dtype=TRACKMAP_RESULT_DT)
+        inf = (_abi.TrackFrameStateInfo * k)()
+        t0 = trackers[0]
+        rc = t0.lib.track_frames_recover_batch(k, trs, kf_, dis, ss, es, bs, sc, _ptr(opts) if opts is not None else None,
+                                               C.byref(state_opts) if state_opts is not None else None, _ptr(res), inf)
+        if rc < 0 and not check:
+            return rc
+        t0.ctx._check(rc, "track_frames_recover_batch")
+        for s_, new in zip(states, ss):
+            C.memmove(C.byref(s_), C.byref(new), C.sizeof(_abi.TrackState))
+        infos = [dict(branch=f.branch, closest_kf=f.closest_kf, closest_kf_dist=f.closest_kf_dist, need_new_keyframe=f.need_new_keyframe,
+                      want_keyframe=f.want_keyframe, pose_in=np.array(f.frame.pose_in), align=_alignment(f.frame.align),
+                      try_coarse=f.frame.try_coarse, coarse_max=f.frame.coarse_max, coarse_range=f.frame.coarse_range,
+                      reloc=dict(best=f.reloc.best, good=bool(f.reloc.good), best_ssd=f.reloc.best_ssd, pose=np.array(f.reloc.pose),
+                                 align=_alignment(f.reloc.align))) for f in inf]
+        return res, infos
+
+    def reloc_ssd(self, row, count):
+        """ptam_tracker_read_reloc_ssd: the SSD table of the row-th recovering camera of the last recover batch this tracker led"""
+        out = np.zeros(int(count))
+        self.ctx._check(self.lib.tracker_read_reloc_ssd(self.h, int(row), int(count), _pd(out)), "tracker_read_reloc_ssd")
+        return out
+
     def iteration_set(self):
         n = C.c_int()
         self.ctx._check(self.lib.tracker_read_iteration_set(self.h, None, 0, C.byref(n)), "tracker_read_iteration_set")
@@ -1407,7 +1465,23 @@ class Relocaliser:
         i = C.c_int()
         self.ctx._check(self.lib.sbi_bank_add(self.h, kf.h, float(blur), C.byref(i)), "sbi_bank_add")
         self.poses.append(np.array(pose, np.float64).reshape(12))
+        self.set_poses(i.value, [pose])
         return i.value
+
+    def set_poses(self, first, poses):
+        """ptam_sbi_bank_set_poses: se3CfromW of entries first .. first + len(poses) - 1, kept on the device and in the bank's host mirror
+        (Relocaliser::SetKeyFramePose); AttemptRecovery's host table follows"""
+        p = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12))
+        self.ctx._check(self.lib.sbi_bank_set_poses(self.h, int(first), len(p), _ptr(p)), "sbi_bank_set_poses")
+        for k, row in enumerate(p):
+            self.poses[first + k] = row.copy()
+
+    def bank_poses(self, first=0, n=None):
+        """ptam_sbi_bank_poses: the bank's mirror of the poses"""
+        n = self.count() - first if n is None else n
+        out = np.zeros((n, 12))
+        self.ctx._check(self.lib.sbi_bank_poses(self.h, int(first), int(n), _ptr(out)), "sbi_bank_poses")
+        return out
 
     def add_batch(self, kfs, poses, blur=2.5):
         """several keyframes with one make launch (ptam_sbi_bank_add_batch) -> the first one's index"""
@@ -1415,6 +1489,7 @@ class Relocaliser:
         hs = (C.c_void_p * len(kfs))(*[k.h.value if hasattr(k.h, "value") else int(k.h) for k in kfs])
         self.ctx._check(self.lib.sbi_bank_add_batch(self.h, len(kfs), hs, float(blur), C.byref(i)), "sbi_bank_add_batch")
         self.poses += [np.array(p, np.float64).reshape(12) for p in poses]
+        self.set_poses(i.value, poses)
         return i.value
 
     def count(self):
