@@ -1521,6 +1521,84 @@ int ptam_tracker_point_serials(ptam_tracker*, int first, int count, int64_t* out
  * PTAM_E_STATE: the tracker's map did not come from a snapshot. */
 int ptam_tracker_read_iteration_serials(ptam_tracker*, int64_t* out, int cap, int* n);
 
+/* ---- A tracked frame handed to the resident map on the device ----------------------------------------------------------------------
+ *      The opposite direction of the snapshot.  The reference's tracker writes into the map on every frame: CalcPoseUpdate bumps
+ *      nMEstimatorOutlierCount / nMEstimatorInlierCount of every found point (src/Tracker.cc:989-997), TrackMap turns vIterationSet
+ *      into mCurrentKF.mMeasurements (:667-676), AddKeyFrameFromTopOfQueue stamps those into the map (src/MapMaker.cc:501-506).
+ *      A ptam_frame_report holds, in device memory, the FOUND entries of one iteration set as 32-byte records sorted by point serial
+ *      (strictly increasing: a point makes at most one record; if the set named a point twice, the later entry would stand, as
+ *      mMeasurements[&p] = m does).  Serial order is the tracker's point-index order and the map's, because both serial columns
+ *      increase strictly with the index: nothing is sorted, and no atomic decides where a record lands — the same frame gives the
+ *      same bytes.  The host keeps the report's info: the map_id the serials belong to, the caller's tag, the counts.
+ *      THREADING.  A report is complete on the device when the call that fills it returns; whoever holds it then may read it, on any
+ *      queue of its device.  The library keeps no lock on a report and no kernel waits for another queue: handing a report from the
+ *      tracker's thread to the mapmaker's (a queue, a pool) is the caller's, as mvpKeyFrameQueue is the reference's.  Refilling or
+ *      destroying a report that another thread is consuming is the caller's error. */
+typedef struct ptam_frame_report ptam_frame_report;
+typedef struct {
+    int64_t serial;             /* of the point, in the map `map_id` */
+    int32_t level;              /* nSearchLevel */
+    uint8_t outlier, did_subpix, pad_[2];   /* 0 / 1, as ptam_trackmap_meas::outlier and ::did_subpix */
+    double root_pos[2];         /* v2_found */
+} ptam_frame_record;
+typedef struct {
+    int64_t map_id;             /* 0: an empty report (never filled, or too small for its frame) */
+    int64_t tag;                /* the caller's, e.g. the frame number */
+    int32_t n_records;          /* found points */
+    int32_t n_entries;          /* the iteration set's length */
+    int32_t n_outliers;         /* records with outlier != 0 */
+    int32_t pad_;
+} ptam_frame_report_info_t;
+/* max_records >= 1: the report's capacity, device memory of 32 max_records bytes; a fill also keeps one word per point of the
+ * frame's map on the report (grown on demand: the one allocation a fill may make). */
+int ptam_frame_report_create(ptam_ctx*, int max_records, ptam_frame_report** out);
+int ptam_frame_report_destroy(ptam_frame_report*);
+/* host only: moves nothing */
+int ptam_frame_report_info(const ptam_frame_report*, ptam_frame_report_info_t* out);
+/* records [first, first + count) down, for tests, drawing and hosts that keep MapPoint objects.  PTAM_E_ARG: a range outside
+ * [0, n_records).  Moves 32 count bytes down. */
+int ptam_frame_report_read(ptam_frame_report*, int first, int count, ptam_frame_record* out);
+/* The frames the trackers tracked last into the reports, nb >= 1 cameras in ONE launch (a workgroup per camera) and one wait, on
+ * the queue that last ran trackers[0] (a tracker that last ran on another queue is waited for on the host first: its frame has
+ * been delivered, so that wait finds the queue idle).  The kernel reads the tracker's own buffers — search slots, found flags,
+ * levels, positions, the outlier flags in whichever of the two layouts the frame's pose loop left them (at the slots, or at the
+ * compacted measurements) — and the tracker's serial list; the set's length is read on the device.  tags (nullable): nb values.
+ * PTAM_E_STATE: a tracker whose map did not come from a snapshot (ptam_tracker_take_map).  PTAM_E_ARG: a null handle, a report on
+ * another device than its tracker, a report or a tracker named twice.  All of these are decided before anything is enqueued and
+ * leave every report as it was.  A report too small for its frame's found points is known only after the wait: that report comes
+ * back empty (n_records = 0, map_id = 0), the others are filled, and the call returns PTAM_E_ARG.
+ * Moves 144 bytes per camera up (where its buffers lie) and 16 bytes per camera down; no record crosses the host link. */
+int ptam_tracker_report_frames(int nb, ptam_tracker* const* trackers, ptam_frame_report* const* reports, const int64_t* tags);
+/* The same device core on arrays the host supplies, for a host whose tracker is not a ptam_tracker: point_serials (n_points,
+ * strictly increasing) is the serial list of the tracker's map, entries (n_entries) an iteration set in that tracker's point
+ * numbering.  tag becomes 0.  PTAM_E_ARG, the report as it was: map_id == 0, serials not strictly increasing, a found entry whose
+ * point is outside [0, n_points) or whose level is outside 0..3; after the wait, the report empty: more found points than
+ * max_records.  Moves 8 n_points + 40 n_entries + 144 bytes up, 16 down. */
+int ptam_frame_report_from_host(ptam_frame_report*, int64_t map_id, int n_points, const int64_t* point_serials, int n_entries,
+                                const ptam_trackmap_meas* entries);
+
+/* The consumers, on the mapmaker's thread.  Both refuse, on the host with every table as it was (PTAM_E_ARG): a null or empty
+ * report (n_records == 0), a report whose map_id is not this handle's, a report on another device. */
+typedef struct { int32_t n_records, n_gone; } ptam_rmap_note_result;
+/* ptam_rmap_note_tracked for n >= 1 reports in one launch (a row of workgroups per report): every record's serial is looked up in
+ * the resident serial column (the binary search of ptam_rmap_resolve_serials); a live point gets outlier_count++ or inlier_count++
+ * (integer atomic adds: exact in any order), a point that ptam_rmap_handle_bad_points has removed since the frame is counted in
+ * n_gone.  The same report may be named more than once (it then counts more than once).  res->n_records: the records of all reports.
+ * Moves 16 bytes per report up (where its records lie, how many) and PTAM_RMAP_WORD_BYTES down. */
+int ptam_rmap_note_reports(ptam_rmap*, int n, ptam_frame_report* const* reports, ptam_rmap_note_result* res);
+/* ptam_rmap_insert_keyframe with step (a) fed from the report: one one-workgroup kernel resolves every record's serial and
+ * appends the live ones, in order, behind the measurement table's count as {n_kf, point, level, PTAM_MAP_SRC_TRACKER, root_pos}
+ * — sorted by point and unique by construction, so there is nothing to check.  Room is made for report.n_records rows, the
+ * host-known upper bound; the live count comes down in a wait of its own (PTAM_RMAP_WORD_BYTES) before the counts move and steps
+ * (b)-(g) run, which are ptam_rmap_insert_keyframe's own code.  *n_rows (nullable): the rows appended; *n_gone (nullable):
+ * n_records - *n_rows.  Refusals as ptam_rmap_insert_keyframe (the row checks apart) and as above.  A record's level is inside
+ * 0..3: a found slot has been searched at a level, and ptam_frame_report_from_host refuses any other.
+ * Moves 97 bytes and the re-find's level records up, PTAM_RMAP_WORD_BYTES more than ptam_rmap_insert_keyframe down: nothing
+ * proportional to the rows. */
+int ptam_rmap_insert_keyframe_report(ptam_rmap*, ptam_refinder*, const ptam_kf* kf, const double pose12[12], int fixed,
+                                     ptam_frame_report* report, const ptam_rmap_insert_opts*, ptam_rmap_insert_result*, int32_t* n_rows,
+                                     int32_t* n_gone);
+
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,
  * ordered on `stream` (hipStream_t).  Return 0 on success. */

@@ -779,6 +779,41 @@ private:
     ptam_map_snapshot* h_ = nullptr;
 };
 
+// One tracked frame for the mapmaker, in device memory (ptam_frame_report, ptam_hip.h): the found entries of the frame's iteration
+// set as records sorted by point serial.  MapTracker::ReportFrame fills it on the tracker's thread (one launch, one wait); the host
+// hands it over — a queue and a pool of reports are the caller's, as mvpKeyFrameQueue is the reference's — and ResidentMap::NoteTracked /
+// InsertKeyFrame consume it on the mapmaker's thread without a record crossing the host link.  No lock is kept: do not refill or
+// destroy a report that the other thread is still consuming.
+class FrameReport {
+public:
+    FrameReport(Context& c, int nMaxRecords) { check(ptam_frame_report_create(c.handle(), nMaxRecords, &h_), "ptam_frame_report_create"); }
+    ~FrameReport() { ptam_frame_report_destroy(h_); }
+    FrameReport(const FrameReport&) = delete;
+    FrameReport& operator=(const FrameReport&) = delete;
+    // map_id (0: empty), the caller's tag, n_records, n_entries, n_outliers
+    ptam_frame_report_info_t Info() const {
+        ptam_frame_report_info_t r{};
+        check(ptam_frame_report_info(h_, &r), "ptam_frame_report_info");
+        return r;
+    }
+    // the records, for drawing and for hosts that keep MapPoint objects; nCount < 0: from nFirst to the end
+    std::vector<ptam_frame_record> Read(int nFirst = 0, int nCount = -1) const {
+        if (nCount < 0) nCount = Info().n_records - nFirst;
+        std::vector<ptam_frame_record> v((size_t)(nCount > 0 ? nCount : 0));
+        check(ptam_frame_report_read(h_, nFirst, nCount, v.data()), "ptam_frame_report_read");
+        return v;
+    }
+    // the same device core for a host whose tracker is not a MapTracker: its map's serial list, its iteration set in its numbering
+    void FromHost(int64_t nMapId, const std::vector<int64_t>& vPointSerials, const std::vector<ptam_trackmap_meas>& vEntries) {
+        check(ptam_frame_report_from_host(h_, nMapId, (int)vPointSerials.size(), vPointSerials.data(), (int)vEntries.size(), vEntries.data()),
+              "ptam_frame_report_from_host");
+    }
+    ptam_frame_report* handle() const { return h_; }
+
+private:
+    ptam_frame_report* h_ = nullptr;
+};
+
 // Tracker::TrackMap (src/Tracker.cc:442-696) as one device-resident chain: the map (world positions, pixel vectors, patch
 // sources) lives on the device between frames; a frame is one call that returns the refined pose, mbDidCoarse, the
 // per-level manMeasAttempted / manMeasFound counters and the scene-depth sums.  The caller keeps what is host logic in the
@@ -952,6 +987,26 @@ public:
         std::vector<int64_t> v((size_t)n);
         if (n > 0) check(ptam_tracker_read_iteration_serials(h_, v.data(), n, &n), "ptam_tracker_read_iteration_serials");
         return v;
+    }
+    // The frame tracked last into `report`, on the device (the map came from TakeMap): what CalcPoseUpdate's counts (:989-997) and
+    // mCurrentKF.mMeasurements (:667-676) are made from.  One launch and one wait; nTag: e.g. the frame number.
+    ptam_frame_report_info_t ReportFrame(FrameReport& report, int64_t nTag = 0) {
+        ptam_frame_report* r = report.handle();
+        check(ptam_tracker_report_frames(1, &h_, &r, &nTag), "ptam_tracker_report_frames");
+        return report.Info();
+    }
+    // ... for the cameras of a batch: still one launch and one wait
+    static void ReportFramesBatch(const std::vector<MapTracker*>& vTrackers, const std::vector<FrameReport*>& vReports,
+                                  const std::vector<int64_t>& vTags = {}) {
+        const size_t n = vTrackers.size();
+        if (n == 0 || vReports.size() != n || (!vTags.empty() && vTags.size() != n)) throw std::runtime_error("ReportFramesBatch: sizes differ");
+        std::vector<ptam_tracker*> t(n);
+        std::vector<ptam_frame_report*> r(n);
+        for (size_t i = 0; i < n; i++) {
+            t[i] = vTrackers[i]->h_;
+            r[i] = vReports[i]->handle();
+        }
+        check(ptam_tracker_report_frames((int)n, t.data(), r.data(), vTags.empty() ? nullptr : vTags.data()), "ptam_tracker_report_frames");
     }
 
 private:
@@ -1260,6 +1315,16 @@ public:
         if (vPoints.size() != vOutlier.size()) throw std::runtime_error("ResidentMap::NoteTracked: one flag per point");
         check(ptam_rmap_note_tracked(h_, (int)vPoints.size(), vPoints.data(), vOutlier.data()), "ptam_rmap_note_tracked");
     }
+    // ... from frame reports: every record resolved by its serial on the device, so the reports may be older than the last
+    // HandleBadPoints (n_gone counts the records of removed points)
+    ptam_rmap_note_result NoteTracked(const std::vector<FrameReport*>& vReports) {
+        std::vector<ptam_frame_report*> r;
+        for (FrameReport* p : vReports) r.push_back(p->handle());
+        ptam_rmap_note_result res{};
+        check(ptam_rmap_note_reports(h_, (int)r.size(), r.data(), &res), "ptam_rmap_note_reports");
+        return res;
+    }
+    ptam_rmap_note_result NoteTracked(FrameReport& report) { return NoteTracked(std::vector<FrameReport*>{&report}); }
     std::vector<ptam_scene_depth> RefreshSceneDepth() {
         std::vector<ptam_scene_depth> v((size_t)Counts().n_kf);
         check(ptam_rmap_scene_depth(h_, v.data()), "ptam_rmap_scene_depth");
@@ -1295,6 +1360,16 @@ public:
         check(ptam_rmap_insert_keyframe(h_, finder.handle(), k.handle(), reinterpret_cast<const double*>(&se3CfromW), bFixed, (int)vRows.size(),
                                         vRows.data(), &opts, &r),
               "ptam_rmap_insert_keyframe");
+        return r;
+    }
+    // ... with the keyframe's rows taken from the frame report of the frame that became the keyframe: resolved, filtered and appended
+    // on the device.  pnRows / pnGone: the rows appended, the records whose points are gone.
+    ptam_rmap_insert_result InsertKeyFrame(ReFinder& finder, const KeyFrame& k, const SE3& se3CfromW, bool bFixed, FrameReport& report,
+                                           const ptam_rmap_insert_opts& opts, int32_t* pnRows = nullptr, int32_t* pnGone = nullptr) {
+        ptam_rmap_insert_result r{};
+        check(ptam_rmap_insert_keyframe_report(h_, finder.handle(), k.handle(), reinterpret_cast<const double*>(&se3CfromW), bFixed, report.handle(),
+                                               &opts, &r, pnRows, pnGone),
+              "ptam_rmap_insert_keyframe_report");
         return r;
     }
     // The map as it stands into the snapshot, as its next generation (the mapmaker's thread): after HandleBadPoints, InsertKeyFrame and

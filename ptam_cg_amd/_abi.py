@@ -272,6 +272,23 @@ class MapSnapshotInfo(C.Structure):
     _fields_ = [("generation", C.c_int64), ("map_id", C.c_int64), ("n_points", C.c_int32), ("pad_", C.c_int32)]
 
 
+class FrameRecord(C.Structure):
+    """ptam_frame_record: one found entry of a tracked frame's iteration set, named by its point's serial"""
+    _fields_ = [("serial", C.c_int64), ("level", C.c_int32), ("outlier", C.c_uint8), ("did_subpix", C.c_uint8), ("pad_", C.c_uint8 * 2),
+                ("root_pos", C.c_double * 2)]
+
+
+class FrameReportInfo(C.Structure):
+    """ptam_frame_report_info_t"""
+    _fields_ = [("map_id", C.c_int64), ("tag", C.c_int64), ("n_records", C.c_int32), ("n_entries", C.c_int32), ("n_outliers", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class RmapNoteResult(C.Structure):
+    """ptam_rmap_note_result"""
+    _fields_ = [("n_records", C.c_int32), ("n_gone", C.c_int32)]
+
+
 class SbiAlignment(C.Structure):
     """ptam_sbi_alignment (SmallBlurryImage::CalcSBIRotation, src/ImageProcess.cc:313-495)"""
     _fields_ = [("se2_rot", C.c_double * 4), ("se2_trans", C.c_double * 2), ("score", C.c_double), ("mean_offset", C.c_double),
@@ -500,6 +517,15 @@ PROTOTYPES = {
     "tracker_take_map": (_i, [_vp, _vp, C.POINTER(MapTakeResult)]),
     "tracker_point_serials": (_i, [_vp, _i, _i, _vp]),
     "tracker_read_iteration_serials": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
+    "frame_report_create": (_i, [_vp, _i, _ppv]),
+    "frame_report_destroy": (_i, [_vp]),
+    "frame_report_info": (_i, [_vp, C.POINTER(FrameReportInfo)]),
+    "frame_report_read": (_i, [_vp, _i, _i, _vp]),
+    "frame_report_from_host": (_i, [_vp, C.c_int64, _i, _vp, _i, _vp]),
+    "tracker_report_frames": (_i, [_i, _vp, _vp, _vp]),
+    "rmap_note_reports": (_i, [_vp, _i, _vp, C.POINTER(RmapNoteResult)]),
+    "rmap_insert_keyframe_report": (_i, [_vp, _vp, _vp, _pd, _i, _vp, C.POINTER(RmapInsertOpts), C.POINTER(RmapInsertResult),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

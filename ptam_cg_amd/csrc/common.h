@@ -103,6 +103,7 @@ void maprefind_preload_kernels();
 void maptables_preload_kernels();
 void sbi_preload_kernels();
 void maprmap_preload_kernels();
+void framereport_preload_kernels();
 // ptam_map_scene_depth behind its upload (mapalign.hip): tables in device memory, n_kf > 0, out on the host; one launch, one wait
 int map_scene_depth_core(ptam_ctx* ctx, int n_kf, const double* d_poses, const double* d_points3, int n_meas, const ptam_map_meas* d_meas,
                          ptam_scene_depth* out);

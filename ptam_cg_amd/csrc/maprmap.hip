@@ -18,6 +18,8 @@
 //                                   sources resolved through a per-keyframe level record, serials; the hand-over is snapshot_slots.h
 //   ptam_rmap_point_serials / resolve_serials   the serial column (one int64 per point, strictly increasing, given by rm_serials_kernel)
 //                                   and a binary search in it (rm_resolve_kernel)
+//   ptam_rmap_note_reports / insert_keyframe_report   the tracker's frame reports (framereport.hip) into the counts (rm_note_reports_kernel)
+//                                   and into a new keyframe's rows (rm_report_rows_kernel): records resolved by serial where they lie
 // Every table has two buffers of one capacity.  A kernel that rebuilds a table reads buf[cur] and writes buf[cur ^ 1]; the host
 // flips cur after the call's wait has read the refusal word.  Rows appended behind a table's count change nothing until the count
 // moves, which it does after the same wait.
@@ -33,6 +35,7 @@
 #include "mapmaker_internal.h"    // EpiBusy, EpiRun, the epipolar chain
 #include "refind_internal.h"      // ptam_refinder
 #include "snapshot_internal.h"    // ptam_map_snapshot: ptam_rmap_publish fills its free slot
+#include "framereport_internal.h" // ptam_frame_report: ptam_rmap_note_reports, ptam_rmap_insert_keyframe_report
 
 namespace {
 
@@ -266,6 +269,66 @@ __global__ void __launch_bounds__(256) rm_resolve_kernel(int n, const long long*
     index_out[i] = at;
     if (at < 0) atomicAdd(n_gone, 1);
 }
+// where a report's records lie, as ptam_rmap_note_reports sends it up
+struct RmReportRef {
+    const ptam_frame_record* rec;
+    int n, pad_;
+};
+static_assert(sizeof(RmReportRef) == 16, "what ptam_hip.h says a report costs the call");
+// src/Tracker.cc:987-998 from frame reports, one thread per record, a row of workgroups per report (blockIdx.y): the record's serial
+// resolved as rm_resolve_kernel does, a live point's count bumped as rm_note_tracked_kernel does
+__global__ void __launch_bounds__(256) rm_note_reports_kernel(const RmReportRef* __restrict__ reports, int n_points, const long long* __restrict__ serials,
+                                                               int32_t* __restrict__ outlier_count, int32_t* __restrict__ inlier_count,
+                                                               int* __restrict__ n_gone) {
+    const RmReportRef r = reports[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= r.n) return;
+    const ptam_frame_record rec = r.rec[i];
+    const int at = rm_find_serial(serials, n_points, rec.serial);
+    if (at < 0) atomicAdd(n_gone, 1);
+    else atomicAdd((rec.outlier ? outlier_count : inlier_count) + at, 1);
+}
+// :501-506 from a frame report, ONE WORKGROUP: every record's serial resolved, the live ones appended in order behind the table's
+// last row (tiles of 1024 records, the count of live records carried from tile to tile: no atomic decides where a row lands).
+// The records ascend by serial and so do the points: the run is sorted and unique.  tot: {rows written, records gone}
+__global__ void __launch_bounds__(1024) rm_report_rows_kernel(int n, const ptam_frame_record* __restrict__ rec, int n_points,
+                                                               const long long* __restrict__ serials, int kf, ptam_map_meas* __restrict__ out,
+                                                               int* __restrict__ tot) {
+    __shared__ int ws[16];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int run = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + tid;
+        ptam_frame_record r;
+        int at = -1;
+        if (i < n) {
+            r = rec[i];
+            at = rm_find_serial(serials, n_points, r.serial);
+        }
+        const bool keep = at >= 0;
+        const unsigned long long mk = __ballot(keep);
+        if (lane == 0) ws[wid] = __popcll(mk);
+        __syncthreads();
+        int off = __popcll(mk & ((1ull << lane) - 1ull)), total = 0;
+        for (int w = 0; w < 16; w++) {
+            if (w < wid) off += ws[w];
+            total += ws[w];
+        }
+        if (keep) {
+            ptam_map_meas m;
+            m.kf = kf;
+            m.point = at;
+            m.level = r.level;
+            m.source = PTAM_MAP_SRC_TRACKER;
+            m.root_pos[0] = r.root_pos[0];
+            m.root_pos[1] = r.root_pos[1];
+            out[run + off] = m;
+        }
+        run += total;
+        __syncthreads();   // (the wave counts are rewritten by the next tile)
+    }
+    if (tid == 0) tot[0] = run, tot[1] = n - run;
+}
 // a keyframe as ptam_rmap_publish sends it up: the four level images
 struct RmKfRecord {
     const uint8_t* im[PTAM_LEVELS];
@@ -411,6 +474,28 @@ int rm_add_keyframe_enqueue(ptam_rmap* m, const double pose12[12], const uint8_t
                            rm_now<ptam_map_meas>(m, PTAM_RMAP_MEAS) + M);
         HIP_TRY(hipGetLastError());
     }
+    return PTAM_OK;
+}
+// the same from a frame report: room for every record, the live ones appended by the device; their count comes down in a wait
+int rm_add_keyframe_enqueue_report(ptam_rmap* m, const double pose12[12], const uint8_t* fx, const ptam_frame_report* rep, int* n_rows) {
+    const int K = m->n[RM_N_KF], M = m->n[RM_N_MEAS], R = rep->info.n_records;
+    if (int rc = rm_room(m, PTAM_RMAP_KF_POSES, (long long)K + 1)) return rc;
+    if (int rc = rm_room(m, PTAM_RMAP_KF_FIXED, (long long)K + 1)) return rc;
+    if (int rc = rm_room(m, PTAM_RMAP_MEAS, (long long)M + R)) return rc;
+    if (int rc = rm_up(m, rm_now<double>(m, PTAM_RMAP_KF_POSES) + (size_t)12 * K, pose12, 96)) return rc;
+    if (int rc = rm_up(m, rm_now<uint8_t>(m, PTAM_RMAP_KF_FIXED) + K, fx, 1)) return rc;
+    if (int rc = rm_words_reset(m)) return rc;
+    hipLaunchKernelGGL(rm_report_rows_kernel, dim3(1), dim3(1024), 0, m->ctx->stream, R, (const ptam_frame_record*)rep->rec, m->n[RM_N_POINTS],
+                       (const long long*)m->serial.now(), K, rm_now<ptam_map_meas>(m, PTAM_RMAP_MEAS) + M, m->d_words + RM_W_TOT);
+    HIP_TRY(hipGetLastError());
+    const int* hw;
+    if (int rc = rm_words_wait(m, &hw)) return rc;
+    const int live = hw[RM_W_TOT];
+    if (live < 0 || live > R) {
+        ptam_set_error("ptam_rmap_insert_keyframe_report: %d rows from %d records", live, R);
+        return PTAM_E_STATE;
+    }
+    *n_rows = live;
     return PTAM_OK;
 }
 // ... and the counts moved: the keyframe is the map's
@@ -1027,16 +1112,55 @@ int ptam_rmap_closest_keyframes(ptam_rmap* m, int kf, int n, int32_t* out_kf, do
     return PTAM_OK;
 }
 
-int ptam_rmap_insert_keyframe(ptam_rmap* m, ptam_refinder* finder, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows,
-                              const ptam_map_kf_row* rows, const ptam_rmap_insert_opts* opts, ptam_rmap_insert_result* res) {
+// what both consumers ask of a report, on the host
+static int rm_report_usable(const ptam_rmap* m, const ptam_frame_report* rep) {
+    ARG_TRY(rep && rep->ctx->device == m->ctx->device);
+    ARG_TRY(rep->info.n_records > 0 && rep->info.n_records <= rep->max_records);
+    ARG_TRY(rep->info.map_id == m->map_id);
+    return PTAM_OK;
+}
+
+int ptam_rmap_note_reports(ptam_rmap* m, int n, ptam_frame_report* const* reports, ptam_rmap_note_result* res) {
+    ARG_TRY(m && res && n >= 1 && n <= 65535 && reports);
+    std::vector<RmReportRef> refs((size_t)n);
+    int most = 0;
+    long long all = 0;
+    for (int i = 0; i < n; i++) {
+        if (int rc = rm_report_usable(m, reports[i])) return rc;
+        refs[(size_t)i] = RmReportRef{reports[i]->rec, reports[i]->info.n_records, 0};
+        most = std::max(most, reports[i]->info.n_records);
+        all += reports[i]->info.n_records;
+    }
+    ARG_TRY(all < (1ll << 31));
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    void* sc;
+    if (int rc = ctx_scratch(m->ctx, rm_up256((size_t)n * sizeof(RmReportRef)), &sc)) return rc;
+    if (int rc = rm_up(m, sc, refs.data(), (size_t)n * sizeof(RmReportRef))) return rc;
+    if (int rc = rm_words_reset(m)) return rc;
+    hipLaunchKernelGGL(rm_note_reports_kernel, dim3(rm_blocks(most), (unsigned)n), dim3(256), 0, m->ctx->stream, (const RmReportRef*)sc,
+                       m->n[RM_N_POINTS], (const long long*)m->serial.now(), rm_now<int32_t>(m, PTAM_RMAP_OUTLIER_COUNT),
+                       rm_now<int32_t>(m, PTAM_RMAP_INLIER_COUNT), m->d_words + RM_W_TOT);
+    HIP_TRY(hipGetLastError());
+    const int* hw;
+    if (int rc = rm_words_wait(m, &hw)) return rc;
+    res->n_records = (int32_t)all;
+    res->n_gone = hw[RM_W_TOT];
+    return PTAM_OK;
+}
+
+// ptam_rmap_insert_keyframe and ptam_rmap_insert_keyframe_report: the rows of step (a) from the host (rows) or from a report (rep)
+static int rm_insert_keyframe(ptam_rmap* m, ptam_refinder* finder, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows,
+                              const ptam_map_kf_row* rows, const ptam_frame_report* rep, const ptam_rmap_insert_opts* opts,
+                              ptam_rmap_insert_result* res, int* n_rows_out) {
     // ---- refusals: nothing is enqueued before all of them have passed
-    ARG_TRY(m && finder && kf && pose12 && opts && res && n_rows >= 0 && (n_rows == 0 || rows));
+    ARG_TRY(m && finder && kf && pose12 && opts && res && n_rows >= 0 && (n_rows == 0 || rows || rep));
     ptam_ctx* ctx = m->ctx;
     const int K = m->n[RM_N_KF], N = m->n[RM_N_POINTS], M = m->n[RM_N_MEAS], V = m->n[RM_N_NEVER];
     const bool refind = !opts->skip_refind, points = !opts->skip_points;
     ARG_TRY(finder->ctx->device == ctx->device && opts->refind.max_pairs_per_pass >= 0);
     ARG_TRY((long long)K + 1 < (1ll << 31) && (long long)M + n_rows + N < (1ll << 31) && (long long)V + N < (1ll << 31));
-    if (int rc = rm_check_kf_rows(N, n_rows, rows)) return rc;
+    if (!rep)
+        if (int rc = rm_check_kf_rows(N, n_rows, rows)) return rc;
     ARG_TRY(opts->target_kf >= -1 && opts->target_kf < K);
     auto usable = [&](const ptam_kf* k) { return k && k->device == ctx->device && k->L.w[0] == ctx->params.width && k->L.h[0] == ctx->params.height; };
     ARG_TRY(usable(kf));
@@ -1063,8 +1187,12 @@ int ptam_rmap_insert_keyframe(ptam_rmap* m, ptam_refinder* finder, const ptam_kf
     r.first_point = N;
     // ---- (a) the keyframe's rows; the counts move at once: nothing below can refuse the call
     const uint8_t fx = fixed ? 1 : 0;
-    if (int rc = rm_add_keyframe_enqueue(m, pose12, &fx, n_rows, rows)) return rc;
+    if (rep) {   // (n_rows was the bound: the records; now the live ones)
+        if (int rc = rm_add_keyframe_enqueue_report(m, pose12, &fx, rep, &n_rows)) return rc;
+    } else if (int rc = rm_add_keyframe_enqueue(m, pose12, &fx, n_rows, rows))
+        return rc;
     rm_add_keyframe_commit(m, kf, pose12, fx, n_rows);
+    if (n_rows_out) *n_rows_out = n_rows;
     // ---- (c) the target: it needs the poses alone, and its wait is (a)'s
     if (points) {
         const int* hdr;
@@ -1113,6 +1241,24 @@ int ptam_rmap_insert_keyframe(ptam_rmap* m, ptam_refinder* finder, const ptam_kf
     if (made > 0)
         if (int rc = rm_add_points_device(m, K, r.target_kf, PTAM_MAP_SRC_EPIPOLAR, made, run.d_out)) return rc;
     *res = r;
+    return PTAM_OK;
+}
+
+int ptam_rmap_insert_keyframe(ptam_rmap* m, ptam_refinder* finder, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows,
+                              const ptam_map_kf_row* rows, const ptam_rmap_insert_opts* opts, ptam_rmap_insert_result* res) {
+    ARG_TRY(n_rows == 0 || rows);
+    return rm_insert_keyframe(m, finder, kf, pose12, fixed, n_rows, rows, nullptr, opts, res, nullptr);
+}
+
+int ptam_rmap_insert_keyframe_report(ptam_rmap* m, ptam_refinder* finder, const ptam_kf* kf, const double pose12[12], int fixed,
+                                     ptam_frame_report* report, const ptam_rmap_insert_opts* opts, ptam_rmap_insert_result* res, int32_t* n_rows,
+                                     int32_t* n_gone) {
+    ARG_TRY(m);
+    if (int rc = rm_report_usable(m, report)) return rc;
+    int live = 0;
+    if (int rc = rm_insert_keyframe(m, finder, kf, pose12, fixed, report->info.n_records, nullptr, report, opts, res, &live)) return rc;
+    if (n_rows) *n_rows = live;
+    if (n_gone) *n_gone = report->info.n_records - live;
     return PTAM_OK;
 }
 
@@ -1219,4 +1365,6 @@ void maprmap_preload_kernels() {
     ptam_preload((const void*)rm_serials_kernel);
     ptam_preload((const void*)rm_resolve_kernel);
     ptam_preload((const void*)rm_publish_kernel);
+    ptam_preload((const void*)rm_note_reports_kernel);
+    ptam_preload((const void*)rm_report_rows_kernel);
 }

@@ -28,6 +28,7 @@
 #include "keyframe_device.h"
 #include "pvs_device.h"
 #include "pose_device.h"
+#include "framereport_internal.h"   // ptam_tracker_report_frames: FrJob, fr_fill_core
 
 struct TmCtl {
     int n_lvl[4];           // avPVS[l].size() after the PVS loop
@@ -1391,6 +1392,87 @@ int ptam_tracker_read_iteration_serials(ptam_tracker* t, int64_t* out, int cap, 
     HIP_TRY(hipMemcpyAsync(out, sc, (size_t)take * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ptam_stream_wait(ctx->stream));
     return PTAM_OK;
+}
+
+// The frames the trackers tracked last into the reports: where each tracker's iteration set lies goes up as a job table, one launch
+// of the report core fills all of them, one wait brings the counts down (framereport.hip)
+int ptam_tracker_report_frames(int nb, ptam_tracker* const* trackers, ptam_frame_report* const* reports, const int64_t* tags) {
+    // ---- refusals: nothing is enqueued, and no report is touched, before all of them have passed
+    ARG_TRY(nb >= 1 && nb <= 4096 && trackers && reports);
+    for (int i = 0; i < nb; i++) {
+        ARG_TRY(trackers[i] && reports[i]);
+        ARG_TRY(reports[i]->ctx->device == trackers[i]->ctx->device && trackers[i]->ctx->device == trackers[0]->ctx->device);
+        for (int j = 0; j < i; j++) ARG_TRY(reports[j] != reports[i] && trackers[j] != trackers[i]);
+    }
+    for (int i = 0; i < nb; i++)
+        if (!trackers[i]->has_serials) {
+            ptam_set_error("ptam_tracker_report_frames: the map of tracker %d did not come from a snapshot", i);
+            return PTAM_E_STATE;
+        }
+    ptam_tracker* lead = trackers[0];
+    ptam_ctx* ctx = lead->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = lead->last_stream ? lead->last_stream : ctx->stream;
+    // (every frame has been delivered: these find their queues idle)
+    if (st != ctx->stream) HIP_TRY(ptam_stream_wait(ctx->stream));
+    for (int i = 1; i < nb; i++) {
+        hipStream_t si = trackers[i]->last_stream ? trackers[i]->last_stream : trackers[i]->ctx->stream;
+        if (si != st) HIP_TRY(ptam_stream_wait(si));
+    }
+    for (int i = 0; i < nb; i++)
+        if (int rc = fr_mark_room(reports[i], trackers[i]->d.n)) return rc;
+    const size_t b_jobs = ((size_t)nb * sizeof(FrJob) + 255) & ~(size_t)255, b_heads = (size_t)nb * FR_HEAD_WORDS * sizeof(int);
+    void *sc, *hp;
+    if (int rc = ctx_scratch(ctx, b_jobs + b_heads, &sc)) return rc;
+    if (int rc = ctx_pinned(ctx, b_heads, &hp)) return rc;
+    std::vector<FrJob> jobs((size_t)nb);
+    for (int i = 0; i < nb; i++) {
+        const TmDev& d = trackers[i]->d;
+        FrJob& j = jobs[(size_t)i];
+        j = FrJob{};
+        j.n_points = d.n;
+        j.serials = trackers[i]->serials;
+        j.cap = d.cap;
+        j.n_slots = &d.ctl->n_slots;
+        j.n_meas = &d.ctl->n_meas;
+        j.outlier_by_slot = &d.ctl->outlier_by_slot;
+        j.list = d.list;
+        j.slot_found = d.slot_found;
+        j.slot_subpix = d.slot_subpix;
+        j.q = d.q;
+        j.tres = d.tres;
+        j.slot_v2 = d.slot_v2;
+        j.outlier = d.outlier;
+        j.mslot = d.mslot;
+        j.mark = reports[i]->mark;
+        j.rec = reports[i]->rec;
+        j.max_records = reports[i]->max_records;
+    }
+    int* d_heads = (int*)((char*)sc + b_jobs);
+    HIP_TRY(hipMemcpyAsync(sc, jobs.data(), (size_t)nb * sizeof(FrJob), hipMemcpyHostToDevice, st));
+    if (int rc = fr_fill_core(st, nb, (const FrJob*)sc, d_heads)) return rc;
+    HIP_TRY(hipMemcpyAsync(hp, d_heads, b_heads, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ptam_stream_wait(st));   // the call's one wait: every report is whole
+    const int* h = (const int*)hp;
+    int too_small = -1;
+    for (int i = 0; i < nb; i++, h += FR_HEAD_WORDS) {
+        ptam_frame_report_info_t& info = reports[i]->info;
+        info = ptam_frame_report_info_t{};
+        if (h[FR_H_RECORDS] > reports[i]->max_records) {
+            if (too_small < 0) {
+                too_small = i;
+                ptam_set_error("bad argument: ptam_tracker_report_frames: frame %d found %d points, its report holds %d records", i, h[FR_H_RECORDS],
+                               reports[i]->max_records);
+            }
+            continue;
+        }
+        info.map_id = trackers[i]->map_id;
+        info.tag = tags ? tags[i] : 0;
+        info.n_records = h[FR_H_RECORDS];
+        info.n_entries = h[FR_H_ENTRIES];
+        info.n_outliers = h[FR_H_OUTLIERS];
+    }
+    return too_small < 0 ? PTAM_OK : PTAM_E_ARG;
 }
 
 int ptam_tracker_set_map(ptam_tracker* t, int n, const ptam_pvs_point* pts, const ptam_template_query* src) {

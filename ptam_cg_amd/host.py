@@ -856,6 +856,9 @@ def map_add_points(ctx, n_kf, n_points, meas, src_kf, target_kf, made, target_so
 
 
 MAP_KF_ROW_DT = np.dtype([("point", "<i4"), ("level", "<i4"), ("root_pos", "<f8", (2,))])
+FRAME_RECORD_DT = np.dtype([("serial", "<i8"), ("level", "<i4"), ("outlier", "u1"), ("did_subpix", "u1"), ("pad_", "u1", (2,)),
+                            ("root_pos", "<f8", (2,))])
+assert FRAME_RECORD_DT.itemsize == 32
 assert MAP_KF_ROW_DT.itemsize == C.sizeof(_abi.MapKfRow) == 24 and C.sizeof(_abi.RmapCounts) == 24
 
 
@@ -1069,25 +1072,51 @@ class ResidentMap:
         o.target_kf, o.skip_refind, o.skip_points = int(target_kf), int(bool(skip_refind)), int(bool(skip_points))
         return o
 
-    def InsertKeyFrame(self, finder, kf, pose, fixed, rows, opts=None, check=True):
+    def InsertKeyFrame(self, finder, kf, pose, fixed, rows=None, opts=None, check=True, report=None):
         """MapMaker::AddKeyFrameFromTopOfQueue after MakeKeyFrame_Rest as one call (ptam_rmap_insert_keyframe): kf a KeyFrame, rows
         MAP_KF_ROW_DT sorted by point, opts from insert_opts() -> dict(kf, target_kf, target_dist, refind (the re-find's counts),
         first_point, n_made, levels EPIPOLAR_STATS_DT per visited level); the new points stay on the device
-        (download("points", first_point, n_made)).  check=False: -> the status of a refused call instead of raising."""
+        (download("points", first_point, n_made)).  check=False: -> the status of a refused call instead of raising.
+        report (a FrameReport, instead of rows): ptam_rmap_insert_keyframe_report — the keyframe's rows are the report's live records,
+        resolved and appended on the device; the dict also holds n_rows and n_gone."""
         opts = opts if opts is not None else self.insert_opts()
-        rows = np.ascontiguousarray(rows, dtype=MAP_KF_ROW_DT)
         pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
         res = _abi.RmapInsertResult()
-        rc = self.lib.rmap_insert_keyframe(self.h, finder.h, kf.h if kf is not None else None, _pd(pose), int(bool(fixed)), len(rows), _ptr(rows),
-                                           C.byref(opts), C.byref(res))
+        if report is not None:
+            if rows is not None:
+                raise ValueError("ResidentMap.InsertKeyFrame: rows or report, not both")
+            n_rows, n_gone = C.c_int32(), C.c_int32()
+            what = "rmap_insert_keyframe_report"
+            rc = self.lib.rmap_insert_keyframe_report(self.h, finder.h, kf.h if kf is not None else None, _pd(pose), int(bool(fixed)), report.h,
+                                                      C.byref(opts), C.byref(res), C.byref(n_rows), C.byref(n_gone))
+        else:
+            rows = np.ascontiguousarray(rows, dtype=MAP_KF_ROW_DT)
+            what = "rmap_insert_keyframe"
+            rc = self.lib.rmap_insert_keyframe(self.h, finder.h, kf.h if kf is not None else None, _pd(pose), int(bool(fixed)), len(rows),
+                                               _ptr(rows), C.byref(opts), C.byref(res))
         if rc < 0 and not check:
             return rc
-        self.ctx._check(rc, "rmap_insert_keyframe")
+        self.ctx._check(rc, what)
         self._kfs.append(kf)
         nl = min(max(opts.epipolar.n_levels, 0), _abi.LEVELS)
         levels = np.frombuffer(bytes(res.levels), dtype=EPIPOLAR_STATS_DT)[:nl].copy()
-        return dict(kf=res.kf, target_kf=res.target_kf, target_dist=res.target_dist, refind=_counts(res.refind), first_point=res.first_point,
-                    n_made=res.n_made, levels=levels)
+        out = dict(kf=res.kf, target_kf=res.target_kf, target_dist=res.target_dist, refind=_counts(res.refind), first_point=res.first_point,
+                   n_made=res.n_made, levels=levels)
+        if report is not None:
+            out.update(n_rows=n_rows.value, n_gone=n_gone.value)
+        return out
+
+    def note_reports(self, reports, check=True):
+        """ptam_rmap_note_reports: the records of the FrameReports into the two counts, resolved by serial on the device ->
+        dict(n_records, n_gone).  check=False: -> the status of a refused call."""
+        reports = list(reports)
+        hs = (C.c_void_p * max(len(reports), 1))(*[r.h for r in reports])
+        res = _abi.RmapNoteResult()
+        rc = self.lib.rmap_note_reports(self.h, len(reports), hs, C.byref(res))
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "rmap_note_reports")
+        return _counts(res)
 
     def publish(self, snapshot, check=True):
         """ptam_rmap_publish: the map as it stands into `snapshot` (a MapSnapshot) as its next generation -> dict(generation, map_id,
@@ -1119,6 +1148,47 @@ class ResidentMap:
     def close(self):
         if getattr(self, "h", None):
             self.lib.rmap_destroy(self.h)
+            self.h = None
+
+
+class FrameReport:
+    """ptam_frame_report: the found entries of one tracked frame as records in device memory, sorted by point serial —
+    Tracker.report_frame fills it on the tracker's thread, ResidentMap.note_reports / InsertKeyFrame(report=) consume it on the
+    mapmaker's.  The library keeps no lock: whoever refills a report makes sure nobody is still consuming it."""
+
+    def __init__(self, ctx, max_records):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = C.c_void_p()
+        ctx._check(self.lib.frame_report_create(ctx.h, int(max_records), C.byref(self.h)), "frame_report_create")
+
+    def info(self):
+        """-> dict(map_id (0: empty), tag, n_records, n_entries, n_outliers)"""
+        r = _abi.FrameReportInfo()
+        self.ctx._check(self.lib.frame_report_info(self.h, C.byref(r)), "frame_report_info")
+        return dict(map_id=r.map_id, tag=r.tag, n_records=r.n_records, n_entries=r.n_entries, n_outliers=r.n_outliers)
+
+    def read(self, first=0, count=None):
+        """records [first, first + count) -> FRAME_RECORD_DT (count None: to the end)"""
+        count = self.info()["n_records"] - first if count is None else int(count)
+        out = np.zeros(max(count, 0), FRAME_RECORD_DT)
+        self.ctx._check(self.lib.frame_report_read(self.h, int(first), count, _ptr(out) if count > 0 else None), "frame_report_read")
+        return out
+
+    def from_host(self, map_id, point_serials, entries, check=True):
+        """ptam_frame_report_from_host: the device core on the host's arrays (the serial list of the tracker's map, an iteration set
+        TRACKMAP_MEAS_DT in that tracker's numbering) -> info().  check=False: -> the status of a refused call."""
+        ser = np.ascontiguousarray(point_serials, dtype=np.int64).reshape(-1)
+        ent = np.ascontiguousarray(entries, dtype=TRACKMAP_MEAS_DT).reshape(-1)
+        rc = self.lib.frame_report_from_host(self.h, int(map_id), len(ser), _ptr(ser) if len(ser) else None, len(ent),
+                                             _ptr(ent) if len(ent) else None)
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "frame_report_from_host")
+        return self.info()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.frame_report_destroy(self.h)
             self.h = None
 
 
@@ -1401,6 +1471,24 @@ class Tracker:
         if n.value:
             self.ctx._check(self.lib.tracker_read_iteration_serials(self.h, _ptr(out), n.value, C.byref(n)), "tracker_read_iteration_serials")
         return out[:n.value]
+
+    def report_frame(self, report, tag=0, check=True):
+        """ptam_tracker_report_frames for this tracker: the frame tracked last into `report` (a FrameReport) -> report.info()"""
+        rc = Tracker.report_frames([self], [report], [tag], check=False)
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "tracker_report_frames")
+        return report.info()
+
+    @staticmethod
+    def report_frames(trackers, reports, tags=None, check=True):
+        """ptam_tracker_report_frames: one launch and one wait for every camera of a batch -> the status"""
+        nb = len(trackers)
+        ts = (C.c_void_p * max(nb, 1))(*[t.h for t in trackers])
+        rs = (C.c_void_p * max(nb, 1))(*[r.h for r in reports])
+        tg = (C.c_int64 * max(nb, 1))(*[int(x) for x in tags]) if tags is not None else None
+        rc = trackers[0].lib.tracker_report_frames(nb, ts, rs, tg)
+        return trackers[0].ctx._check(rc, "tracker_report_frames") if check else rc
 
     def close(self):
         if getattr(self, "h", None):
