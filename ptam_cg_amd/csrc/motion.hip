@@ -56,6 +56,24 @@ const double kIdentity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
 
 }   // namespace
 
+bool track_coarse_heuristics(ptam_trackmap_opts* o, ptam_motion_model* m, bool recovering) {
+    o->try_coarse = 1;
+    if (m->disable_coarse || m->msd_scaled_velocity < m->coarse_min_velocity || o->coarse_max == 0) o->try_coarse = 0;
+    if (!recovering && !m->just_recovered) return false;
+    o->try_coarse = 1;
+    o->coarse_max *= 2;
+    o->coarse_range *= 2;
+    m->just_recovered = 0;
+    return true;
+}
+
+void motion_update_scene_depth(ptam_motion_model* m, const ptam_trackmap_result* r) {
+    if (r->depth_n > 20) {
+        m->scene_depth_mean = r->depth_sum / r->depth_n;
+        m->scene_depth_sigma = std::sqrt(r->depth_sum_sq / r->depth_n - m->scene_depth_mean * m->scene_depth_mean);
+    }
+}
+
 extern "C" {
 
 void ptam_se3_exp(const double mu[6], double pose_out[12]) {
@@ -186,10 +204,7 @@ void ptam_assess_tracking_quality(ptam_track_state* s, const int32_t attempted[4
 void ptam_motion_update(ptam_motion_model* m, const ptam_trackmap_result* r) {
     if (!m || !r) return;
     std::memcpy(m->pose, r->pose, 96);
-    if (r->depth_n > 20) {                // :692-696
-        m->scene_depth_mean = r->depth_sum / r->depth_n;
-        m->scene_depth_sigma = std::sqrt(r->depth_sum_sq / r->depth_n - m->scene_depth_mean * m->scene_depth_mean);
-    }
+    motion_update_scene_depth(m, r);      // :692-696
     // :1038-1039  se3NewFromOld = mse3CamFromWorld * mse3StartPos.inverse()
     const double* S = m->start_pose;
     double inv[12];
@@ -225,19 +240,11 @@ int ptam_track_frame(ptam_tracker* t, ptam_kf* current, const uint8_t* d_frame, 
     ptam_trackmap_opts o;
     if (opts) o = *opts;
     else ptam_trackmap_opts_default(&o);
-    // src/Tracker.cc:503-514
-    o.try_coarse = 1;
-    if (m->disable_coarse || m->msd_scaled_velocity < m->coarse_min_velocity || o.coarse_max == 0) o.try_coarse = 0;
     // (the model is advanced on a COPY and committed only when the frame was tracked: a call that fails — time-out, HIP error,
     //  PTAM_E_STATE — leaves the caller's model as it was, so that a retry neither predicts twice nor has lost the doubled
     //  coarse range of a recovery; the reference has no such partial state)
     ptam_motion_model tmp = *m;
-    if (tmp.just_recovered) {
-        o.try_coarse = 1;
-        o.coarse_max *= 2;
-        o.coarse_range *= 2;
-        tmp.just_recovered = 0;
-    }
+    track_coarse_heuristics(&o, &tmp, false);   // src/Tracker.cc:503-514
     ptam_motion_predict(&tmp);
     const int rc = ptam_track_map_frame(t, current, d_frame, tmp.pose, &o, out);
     if (rc) return rc;
@@ -253,16 +260,9 @@ int ptam_track_frame_sbi(ptam_tracker* t, ptam_kf* current, const uint8_t* d_fra
     ptam_trackmap_opts o;
     if (opts) o = *opts;
     else ptam_trackmap_opts_default(&o);
-    // the heuristics and the copy of the model: as in ptam_track_frame
-    o.try_coarse = 1;
-    if (m->disable_coarse || m->msd_scaled_velocity < m->coarse_min_velocity || o.coarse_max == 0) o.try_coarse = 0;
+    // the copy of the model and the heuristics: as in ptam_track_frame
     ptam_motion_model tmp = *m;
-    if (tmp.just_recovered) {
-        o.try_coarse = 1;
-        o.coarse_max *= 2;
-        o.coarse_range *= 2;
-        tmp.just_recovered = 0;
-    }
+    track_coarse_heuristics(&o, &tmp, false);
     int rc = ptam_make_keyframe_lite_dev(tracker_ctx(t), current, d_frame);
     if (rc) return rc;
     ptam_sbi_alignment al;
@@ -301,13 +301,11 @@ int ptam_bench_track_sequence(ptam_tracker* t, ptam_kf* current, int n_frames, c
             st[5] += tried ? 1 : 0;
             if (poses_true) {
                 const double* q = poses_true + (size_t)f * 12;
-                // camera centres: -R^T t of the tracked and of the true pose
-                double d2 = 0;
-                for (int c = 0; c < 3; c++) {
-                    const double a = -(res.pose[0 * 3 + c] * res.pose[9] + res.pose[1 * 3 + c] * res.pose[10] + res.pose[2 * 3 + c] * res.pose[11]);
-                    const double b = -(q[0 * 3 + c] * q[9] + q[1 * 3 + c] * q[10] + q[2 * 3 + c] * q[11]);
-                    d2 += (a - b) * (a - b);
-                }
+                // camera centres of the tracked and of the true pose
+                double a[3], b[3], d2 = 0;
+                se3_camera_position(res.pose, a);
+                se3_camera_position(q, b);
+                for (int c = 0; c < 3; c++) d2 += (a[c] - b[c]) * (a[c] - b[c]);
                 st[6] = std::fmax(st[6], std::sqrt(d2));
             }
             st[7] += res.n_meas < 50 ? 1 : 0;

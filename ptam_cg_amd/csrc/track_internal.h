@@ -41,6 +41,17 @@ void kf_launch_detect(ptam_kf* kf, hipStream_t stream);
 void kf_launch_detect_batch(int nb, const KfLevels& L, const void* d_items, size_t stride, size_t off_levels, hipStream_t stream);   // (L: the common geometry)
 // trackmap.hip: the context a tracker was created with
 ptam_ctx* tracker_ctx(const ptam_tracker* t);
+// motion.hip
+// The bTryCoarse heuristics (src/Tracker.cc:503-514) on a copy of the caller's options and a copy of the model: coarse when the camera
+// moves fast enough and CoarseMax allows it; after a recovery — the model's just_recovered, which is cleared, or `recovering`: the
+// relocaliser runs in front of this very TrackMap — coarse in any case, with CoarseMax and CoarseRange doubled.  -> doubled or not
+bool track_coarse_heuristics(ptam_trackmap_opts* o, ptam_motion_model* m, bool recovering);
+// the scene depth of src/Tracker.cc:692-696, the part of ptam_motion_update a recovered frame keeps
+void motion_update_scene_depth(ptam_motion_model* m, const ptam_trackmap_result* r);
+// the camera position of an se3CfromW: se3CfromW.inverse().get_translation() = -R^T t (KeyFrameLinearDist, src/MapMaker.cc:696-703)
+static inline void se3_camera_position(const double p[12], double out[3]) {
+    for (int k = 0; k < 3; k++) out[k] = -(p[k] * p[9] + p[3 + k] * p[10] + p[6 + k] * p[11]);
+}
 // pvs.hip
 struct PoseArg {   // a pose handed over by value
     double v[12];

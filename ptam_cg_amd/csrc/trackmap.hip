@@ -1672,6 +1672,95 @@ int ptam_track_map_frame(ptam_tracker* t, ptam_kf* cur, const uint8_t* d_frame, 
     return track_map_impl(t, cur, d_frame, pose_in, opts, out);
 }
 
+// =================================================================================================
+// ---- the batch chain's host side: what ptam_track_map_frames_batch, ptam_track_frames_batch and ptam_track_frames_recover_batch
+//      are made of.  Each of them reads check -> argument block -> fill -> upload -> keyframe / PVS / set choice -> two stages -> collect ----
+
+// What every batch call refuses before it looks further (no HIP call).  All trackers must live on one device and share camera model,
+// image geometry and halfSample variant; no tracker, keyframe or context comes twice.
+static int tm_batch_check(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames) {
+    ARG_TRY(nb >= 1 && nb <= 4096 && ts && curs && d_frames);
+    for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i] && d_frames[i]);
+    const ptam_ctx* ctx = ts[0]->ctx;
+    const KfLevels& L0 = curs[0]->L;
+    for (int i = 0; i < nb; i++) {
+        ARG_TRY(ts[i]->ctx->device == ctx->device && curs[i]->device == ctx->device);
+        ARG_TRY(ts[i]->ctx->halfsample == ctx->halfsample && std::memcmp(&ts[i]->ctx->cam, &ctx->cam, sizeof(DevCam)) == 0);
+        ARG_TRY(curs[i]->n_blocks == curs[0]->n_blocks);
+        for (int l = 0; l < PTAM_LEVELS; l++) ARG_TRY(curs[i]->L.w[l] == L0.w[l] && curs[i]->L.h[l] == L0.h[l]);
+        for (int j = 0; j < i; j++) ARG_TRY(ts[j] != ts[i] && curs[j] != curs[i] && ts[j]->ctx != ts[i]->ctx);   // (a context's scratch serves ONE frame)
+    }
+    return PTAM_OK;
+}
+
+// The chain runs on the first tracker's queue: whatever the other trackers' own queues still hold (a map upload, the tail of their
+// last frame) must be done.
+static int tm_batch_join(int nb, ptam_tracker* const* ts) {
+    ptam_ctx* ctx = ts[0]->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    for (int i = 1; i < nb; i++)
+        if (ts[i]->ctx != ctx) HIP_TRY(ptam_stream_wait(ts[i]->ctx->stream));
+    return PTAM_OK;
+}
+
+// The argument block of a batch: a pinned copy the host fills and the device copy in the lead tracker's batch_dev, section by
+// section at the same offsets, every section 256-byte aligned:
+//   nb TmBatchItem | nb PoseBatchItem (coarse) | nb (fine) | n_est + n_rr SbiBatchRec | 3 x nb frame indices | n_rr SbiRelocRec
+// and behind what is uploaded, on the device only, the recovering cameras' SSD tables (n_rr x rr_max_count) and gates.
+// The frame indices: [frames whose pose is made on the device | coarse stage by instantiation | fine stage by instantiation],
+// idx_stride ints apart.  ptam_track_map_frames_batch has n_est = n_rr = 0 and uploads the first three sections.
+extern "C++" {   // (member templates, inside this file's extern "C")
+struct TmBatchArgs {
+    enum Section { ITEMS, POSE_COARSE, POSE_FINE, SBI_REC, FRAME_IDX, RELOC_REC, RELOC_SSD, RELOC_GATE, N_SECTIONS };
+    size_t off[N_SECTIONS + 1];
+    size_t idx_stride;
+    char* hb = nullptr;
+    char* db = nullptr;
+
+    TmBatchArgs(int nb, int n_est, int n_rr, int rr_max_count) {
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t b_idx = up((size_t)nb * 4);
+        const size_t n = (size_t)nb, rr = (size_t)n_rr;
+        const size_t bytes[N_SECTIONS] = {n * sizeof(TmBatchItem), n * sizeof(PoseBatchItem), n * sizeof(PoseBatchItem),
+                                          (size_t)std::max(n_est + n_rr, 1) * sizeof(SbiBatchRec), 3 * b_idx, rr * sizeof(SbiRelocRec),
+                                          rr * (size_t)rr_max_count * 8, rr * 4};
+        idx_stride = b_idx / 4;
+        off[0] = 0;
+        for (int s = 0; s < N_SECTIONS; s++) off[s + 1] = off[s] + up(bytes[s]);
+    }
+    size_t end(Section s) const { return off[s + 1]; }   // bytes up to and including section s
+    template <class T> T* host(Section s) const { return (T*)(hb + off[s]); }
+    template <class T> T* dev(Section s) const { return (T*)(db + off[s]); }
+    int* host_idx(int list) const { return host<int>(FRAME_IDX) + (size_t)list * idx_stride; }
+    const int* dev_idx(int list) const { return dev<int>(FRAME_IDX) + (size_t)list * idx_stride; }
+
+    // the pinned copy from the lead tracker's context, and its batch_dev grown on demand
+    int reserve(ptam_tracker* lead) {
+        void* pin;
+        const int rc = ctx_pinned(lead->ctx, end(RELOC_REC) + 64, &pin);
+        if (rc) return rc;
+        if (lead->batch_cap < end(RELOC_GATE)) {
+            HIP_TRY(ptam_stream_wait(lead->ctx->stream));
+            if (lead->batch_dev) HIP_TRY(hipFree(lead->batch_dev));
+            lead->batch_dev = nullptr;
+            lead->batch_cap = 0;
+            HIP_TRY(hipMalloc(&lead->batch_dev, end(RELOC_GATE) * 2));
+            lead->batch_cap = end(RELOC_GATE) * 2;
+        }
+        hb = (char*)pin;
+        db = (char*)lead->batch_dev;
+        return PTAM_OK;
+    }
+};
+}
+
+// what the launches of a batch are shaped by
+struct TmBatchDims {
+    int gx = 0, gy = 0;              // a frame's pyramid workgroups (one geometry: tm_batch_check)
+    int n_max = 0, ncc_max = 1;      // the longest fine and the longest coarse list
+    int n_shape[2][3], first[2][3];  // tm_group_by_shape
+};
+
 // one frame's pose loop of a batch: what pose_launch_chain takes as arguments (updates, st: the frame's own context's scratch)
 static PoseBatchItem tm_pose_item(const ptam_tracker* t, int stage, int n_cap, double* updates, void* st, unsigned long long seq) {
     const TmDev& d = t->d;
@@ -1689,118 +1778,112 @@ static PoseBatchItem tm_pose_item(const ptam_tracker* t, int stage, int n_cap, d
     return p;
 }
 
-// nb frames of nb independent trackers — each with its own map, keyframe and motion-model prediction — as ONE chain of
-// launches on the first tracker's queue (see TmBatchItem).  Per frame the result is what ptam_track_map_frame gives (the same
-// kernel bodies on the same data).  All trackers must live on one device and share camera model, image geometry and
-// halfSample variant; opts apply to every frame.
-int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, const double* poses_in,
-                                const ptam_trackmap_opts* opts, ptam_trackmap_result* outs) {
-    ARG_TRY(nb >= 1 && nb <= 4096 && ts && curs && d_frames && poses_in && outs);
-    for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i] && d_frames[i]);
-    ptam_tracker* lead = ts[0];
-    ptam_ctx* ctx = lead->ctx;
-    if (lead->reloc_count) lead->reloc_count->clear();   // (the argument block is rewritten: ptam_tracker_read_reloc_ssd has no rows)
-    ptam_trackmap_opts o;
-    int rc = tm_opts(opts, &o);
-    if (rc) return rc;
-    const KfLevels& L0 = curs[0]->L;
-    for (int i = 0; i < nb; i++) {
-        ARG_TRY(ts[i]->ctx->device == ctx->device && curs[i]->device == ctx->device);
-        ARG_TRY(ts[i]->ctx->halfsample == ctx->halfsample && std::memcmp(&ts[i]->ctx->cam, &ctx->cam, sizeof(DevCam)) == 0);
-        ARG_TRY(curs[i]->n_blocks == curs[0]->n_blocks);
-        for (int l = 0; l < PTAM_LEVELS; l++) ARG_TRY(curs[i]->L.w[l] == L0.w[l] && curs[i]->L.h[l] == L0.h[l]);
-        for (int j = 0; j < i; j++) ARG_TRY(ts[j] != ts[i] && curs[j] != curs[i] && ts[j]->ctx != ts[i]->ctx);   // (a context's scratch serves ONE frame)
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // the other trackers' own queues: whatever they still hold (a map upload, the tail of their last frame) must be done
-    for (int i = 1; i < nb; i++)
-        if (ts[i]->ctx != ctx) HIP_TRY(ptam_stream_wait(ts[i]->ctx->stream));
-    // ---- the argument arrays: [nb TmBatchItem | nb PoseBatchItem (coarse) | nb PoseBatchItem (fine)] ----
-    const size_t b_items = (size_t)nb * sizeof(TmBatchItem), b_pose = (size_t)nb * sizeof(PoseBatchItem), b_all = b_items + 2 * b_pose;
-    void* pin;
-    rc = ctx_pinned(ctx, b_all + 64, &pin);
-    if (rc) return rc;
-    if (lead->batch_cap < b_all) {
-        HIP_TRY(ptam_stream_wait(st));
-        if (lead->batch_dev) HIP_TRY(hipFree(lead->batch_dev));
-        lead->batch_dev = nullptr;
-        lead->batch_cap = 0;
-        HIP_TRY(hipMalloc(&lead->batch_dev, b_all * 2));
-        lead->batch_cap = b_all * 2;
-    }
-    TmBatchItem* h_it = (TmBatchItem*)pin;
-    PoseBatchItem* h_pc = (PoseBatchItem*)((char*)pin + b_items);
-    PoseBatchItem* h_pf = h_pc + nb;
-    const TmBatchItem* d_it = (const TmBatchItem*)lead->batch_dev;
-    const PoseBatchItem* d_pc = (const PoseBatchItem*)((const char*)lead->batch_dev + b_items);
-    const PoseBatchItem* d_pf = d_pc + nb;
-    int gx = 0, gy = 0, n_max = 0, ncc_max = 1;
-    for (int i = 0; i < nb; i++) {
-        ptam_tracker* t = ts[i];
-        TmBatchItem& it = h_it[i];
-        std::memset(&it, 0, sizeof it);
-        kf_lite_begin(curs[i], d_frames[i], &it.pa, &gx, &gy);
-        it.n_pyr = gx * gy;
-        it.n = t->d.n;
-        it.L = curs[i]->L;
-        it.d = t->d;
-        std::memcpy(it.pv.v, poses_in + 12 * (size_t)i, 96);
+// Frame i of the block: the tracker's TmBatchItem and its two PoseBatchItem.  pose (nullable): the pose the host predicted; without
+// it the device makes the pose and the frame's PVS pass runs in tm_pvs_batch_kernel.  f: the frame's own options (the bTryCoarse
+// heuristics applied).  The fine loop publishes the tracker's NEXT sequence number; tm_commit_seqs makes it the tracker's own.
+static int tm_fill_frame(const TmBatchArgs& a, int i, ptam_tracker* t, ptam_kf* cur, const uint8_t* d_frame, const double* pose,
+                         const ptam_trackmap_opts& f, TmBatchDims* dm) {
+    TmBatchItem& it = a.host<TmBatchItem>(TmBatchArgs::ITEMS)[i];
+    std::memset(&it, 0, sizeof it);
+    kf_lite_begin(cur, d_frame, &it.pa, &dm->gx, &dm->gy);
+    it.n_pyr = dm->gx * dm->gy;
+    it.n = t->d.n;
+    it.L = cur->L;
+    it.d = t->d;
+    it.mbox = t->mbox_dev;
+    it.try_coarse = f.try_coarse, it.coarse_max = f.coarse_max, it.coarse_range = f.coarse_range;
+    if (pose) {
+        std::memcpy(it.pv.v, pose, 96);
         it.pv.use = 1;
-        it.mbox = t->mbox_dev;
-        it.try_coarse = o.try_coarse, it.coarse_max = o.coarse_max, it.coarse_range = o.coarse_range;
-        const int n = t->d.n, ncc = std::max(1, std::min(n, (int)o.coarse_max));
-        n_max = std::max(n_max, n);
-        ncc_max = std::max(ncc_max, ncc);
-        void* sst;
-        double* su;
-        rc = pose_chain_scratch(t->ctx, std::max(n, 1), &sst, &su);   // (sized for the fine loop; the coarse one uses its start)
-        if (rc) return rc;
-        h_pc[i] = tm_pose_item(t, 0, ncc, su, sst, 0);
-        h_pf[i] = tm_pose_item(t, 1, std::max(n, 1), su, sst, ++t->seq);
-        t->last_stream = st;
     }
-    HIP_TRY(hipMemcpyAsync(lead->batch_dev, pin, b_all, hipMemcpyHostToDevice, st));
-    const int n_fine = std::max(n_max, 1);
-    auto gather = [&](int cap, int stage) {
-        hipLaunchKernelGGL(tm_gather_batch_kernel, dim3(std::max(1, (cap + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS), nb), dim3(TM_GATHER_THREADS), 0, st,
-                           d_it, stage, (int)o.coarse_subpix_its, o.coarse_min);
-    };
-    // ---- keyframe + PVS + set choice ----
-    const int n_pyr = gx * gy, n_pvs = std::max(1, (n_max + 255) / 256);
-    hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_pyr_pvs_batch_kernel), dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, gx, ctx->cam);
-    kf_launch_detect_batch(nb, L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L), st);
-    hipLaunchKernelGGL(tm_compact_select_batch_kernel, dim3(1 + fast_compact_blocks(L0), nb), dim3(1024), 0, st, d_it, o);
-    // (fused bookkeeping + pose loop per stage when no frame's list can outgrow the register-resident kernel: maps of at most
-    //  1024 points; larger maps keep the gather pass and the small / general kernel pair)
-    const bool fuse = !tm_no_fuse && n_max <= GS_LIMIT && ncc_max <= GS_LIMIT;
-    int thr;
-    // ---- coarse stage :519-569 ----
-    hipLaunchKernelGGL(tm_search_batch_kernel, dim3((ncc_max + 3) / 4, nb), dim3(256), 0, st, ctx->cam, d_it, 0, o.coarse_subpix_its);
-    ptam_gn_opts g = tm_gn_opts(0, o.estimator);
-    if (fuse) {
-        const tm_pose_batch_fn fn = tm_pose_batch_fns[tm_pose_shape(ncc_max, &thr)];
-        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_pc, (const int*)nullptr, 0, o.coarse_min, g);
-    } else {
-        gather(ncc_max, 0);
-        rc = pose_launch_chain_batch(ctx, nb, ncc_max, d_pc, &g);
-        if (rc) return rc;
-    }
-    // ---- fine stage :571-643 ----
-    hipLaunchKernelGGL(tm_search_batch_kernel, dim3(std::max(1, (n_max + 3) / 4), nb), dim3(256), 0, st, ctx->cam, d_it, 1, 0);
-    g = tm_gn_opts(1, o.estimator);
-    if (fuse) {
-        const tm_pose_batch_fn fn = tm_pose_batch_fns[tm_pose_shape(n_fine, &thr)];
-        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_pf, (const int*)nullptr, 1, o.coarse_min, g);
-    } else {
-        gather(n_max, 1);
-        rc = pose_launch_chain_batch(ctx, nb, n_fine, d_pf, &g);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipGetLastError());
-    // ---- wait + result, frame by frame (no frame of a batch asks for the general path: POSE_CHAIN_LONG is never set) ----
+    const int n = t->d.n, n_fine = std::max(n, 1), ncc = std::max(1, std::min(n, (int)f.coarse_max));
+    dm->n_max = std::max(dm->n_max, n);
+    dm->ncc_max = std::max(dm->ncc_max, ncc);
+    void* sst;
+    double* su;
+    const int rc = pose_chain_scratch(t->ctx, n_fine, &sst, &su);   // (sized for the fine loop; the coarse one uses its start)
+    if (rc) return rc;
+    a.host<PoseBatchItem>(TmBatchArgs::POSE_COARSE)[i] = tm_pose_item(t, 0, ncc, su, sst, 0);
+    a.host<PoseBatchItem>(TmBatchArgs::POSE_FINE)[i] = tm_pose_item(t, 1, n_fine, su, sst, t->seq + 1);
+    return PTAM_OK;
+}
+// behind the last point where the call can refuse: the frames' sequence numbers become the trackers'
+static void tm_commit_seqs(int nb, ptam_tracker* const* ts, hipStream_t st) {
     for (int i = 0; i < nb; i++) {
-        rc = tm_wait_seq(ts[i], st, ts[i]->seq, "a frame's result");
+        ts[i]->seq++;
+        ts[i]->last_stream = st;
+    }
+}
+
+// The pose loops of a stage go out in one of three forms:
+//   GROUPED     every frame in the fused kernel instantiation its OWN list length selects, the frames of one instantiation in one
+//               launch with an index list — a frame's result is the single call's bit for bit (ptam_track_frames_batch)
+//   ONE_LAUNCH  one fused launch shaped by the batch's longest list, no index list (ptam_track_map_frames_batch)
+//   GATHER      the gather pass and the small / general kernel pair of pose_launch_chain_batch for everybody: results equal the single
+//               calls' to rounding
+// The fused kernels hold GS_LIMIT (1024) slots.  GROUPED needs every COARSE list to fit (a fine list that outgrows the kernel is
+// finished on the frame's own queue after the wait, tm_wait_frame); ONE_LAUNCH needs every list of both stages to fit.
+enum TmPoseForm { TM_POSE_GROUPED, TM_POSE_ONE_LAUNCH, TM_POSE_GATHER };
+static TmPoseForm tm_pose_form(bool per_frame, int n_max, int ncc_max) {
+    if (tm_no_fuse || ncc_max > GS_LIMIT) return TM_POSE_GATHER;
+    if (per_frame) return TM_POSE_GROUPED;
+    return n_max <= GS_LIMIT ? TM_POSE_ONE_LAUNCH : TM_POSE_GATHER;
+}
+// GROUPED: index lists 1 (coarse) and 2 (fine) of the block — the frames of every pose-kernel instantiation, n_shape[stage][k] frames
+// from first[stage][k] on
+static void tm_group_by_shape(const TmBatchArgs& a, int nb, TmBatchDims* dm) {
+    int thr;
+    for (int sg = 0; sg < 2; sg++) {
+        const PoseBatchItem* p = a.host<PoseBatchItem>(sg ? TmBatchArgs::POSE_FINE : TmBatchArgs::POSE_COARSE);
+        int* list = a.host_idx(1 + sg);
+        int at = 0;
+        for (int k = 0; k < 3; k++) {
+            dm->first[sg][k] = at;
+            for (int i = 0; i < nb; i++)
+                if (tm_pose_shape(std::min(p[i].n_cap, GS_LIMIT), &thr) == k) list[at++] = i;
+            dm->n_shape[sg][k] = at - dm->first[sg][k];
+        }
+    }
+}
+// stage sg of the chain (0 coarse :519-569, 1 fine :571-643): the search, then the pose loops
+static int tm_enqueue_stage(ptam_ctx* ctx, int nb, const TmBatchArgs& a, const TmBatchDims& dm, const ptam_trackmap_opts& o, int sg,
+                            TmPoseForm form) {
+    hipStream_t st = ctx->stream;
+    const TmBatchItem* d_it = a.dev<TmBatchItem>(TmBatchArgs::ITEMS);
+    const PoseBatchItem* d_p = a.dev<PoseBatchItem>(sg ? TmBatchArgs::POSE_FINE : TmBatchArgs::POSE_COARSE);
+    const int cap = sg ? std::max(dm.n_max, 1) : dm.ncc_max;
+    hipLaunchKernelGGL(tm_search_batch_kernel, dim3(std::max(1, (cap + 3) / 4), nb), dim3(256), 0, st, ctx->cam, d_it, sg, sg ? 0 : (int)o.coarse_subpix_its);
+    const ptam_gn_opts g = tm_gn_opts(sg, o.estimator);
+    int thr;
+    switch (form) {
+    case TM_POSE_GROUPED:
+        for (int k = 0; k < 3; k++) {
+            if (dm.n_shape[sg][k] == 0) continue;
+            hipLaunchKernelGGL(tm_pose_batch_fns[k], dim3(dm.n_shape[sg][k]), dim3(k == 0 ? GS_WAVE_LIMIT : GS_THREADS), 0, st, ctx->cam, d_it, d_p,
+                               a.dev_idx(1 + sg) + dm.first[sg][k], sg, o.coarse_min, g);
+        }
+        return PTAM_OK;
+    case TM_POSE_ONE_LAUNCH: {
+        const tm_pose_batch_fn fn = tm_pose_batch_fns[tm_pose_shape(cap, &thr)];
+        hipLaunchKernelGGL(fn, dim3(nb), dim3(thr), 0, st, ctx->cam, d_it, d_p, (const int*)nullptr, sg, o.coarse_min, g);
+        return PTAM_OK;
+    }
+    default: {
+        const int longest = sg ? dm.n_max : dm.ncc_max;
+        hipLaunchKernelGGL(tm_gather_batch_kernel, dim3(std::max(1, (longest + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS), nb), dim3(TM_GATHER_THREADS), 0, st,
+                           d_it, sg, (int)o.coarse_subpix_its, o.coarse_min);
+        return pose_launch_chain_batch(ctx, nb, cap, d_p, &g);
+    }
+    }
+}
+
+// Wait + result, frame by frame.  long_path: a frame whose fine list outgrew the fused kernel says so in its sequence word
+// (POSE_CHAIN_LONG) and is finished on its own queue (tm_wait_frame; fused: the fine stage went out GROUPED); a batch that never sets
+// the bit waits for the word alone.
+static int tm_collect(int nb, ptam_tracker* const* ts, hipStream_t st, const ptam_trackmap_opts& o, bool long_path, bool fused,
+                      ptam_trackmap_result* outs) {
+    for (int i = 0; i < nb; i++) {
+        const int rc = long_path ? tm_wait_frame(ts[i], st, o, ts[i]->seq, fused) : tm_wait_seq(ts[i], st, ts[i]->seq, "a frame's result");
         if (rc) {
             const std::string e = ptam_last_error();
             ptam_set_error("frame %d of the batch: %s", i, e.c_str());
@@ -1811,20 +1894,52 @@ int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const*
     return PTAM_OK;
 }
 
+// nb frames of nb independent trackers — each with its own map, keyframe and motion-model prediction — as ONE chain of
+// launches on the first tracker's queue (see TmBatchItem).  Per frame the result is what ptam_track_map_frame gives (the same
+// kernel bodies on the same data); opts apply to every frame.  No frame of this batch asks for the general path after the wait:
+// with a map of more than 1024 points the stages go out in the GATHER form.
+int ptam_track_map_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, const double* poses_in,
+                                const ptam_trackmap_opts* opts, ptam_trackmap_result* outs) {
+    ARG_TRY(poses_in && outs);
+    int rc = tm_batch_check(nb, ts, curs, d_frames);
+    ptam_trackmap_opts o;
+    if (!rc) rc = tm_opts(opts, &o);
+    if (rc) return rc;
+    ptam_tracker* lead = ts[0];
+    ptam_ctx* ctx = lead->ctx;
+    hipStream_t st = ctx->stream;
+    if (lead->reloc_count) lead->reloc_count->clear();   // (the argument block is rewritten: ptam_tracker_read_reloc_ssd has no rows)
+    TmBatchArgs a(nb, 0, 0, 0);
+    TmBatchDims dm;
+    rc = tm_batch_join(nb, ts);
+    if (!rc) rc = a.reserve(lead);
+    for (int i = 0; i < nb && !rc; i++) rc = tm_fill_frame(a, i, ts[i], curs[i], d_frames[i], poses_in + 12 * (size_t)i, o, &dm);
+    if (rc) return rc;
+    tm_commit_seqs(nb, ts, st);
+    HIP_TRY(hipMemcpyAsync(lead->batch_dev, a.hb, a.end(TmBatchArgs::POSE_FINE), hipMemcpyHostToDevice, st));
+    // ---- keyframe + PVS + set choice ----
+    const TmBatchItem* d_it = a.dev<TmBatchItem>(TmBatchArgs::ITEMS);
+    const int n_pyr = dm.gx * dm.gy, n_pvs = std::max(1, (dm.n_max + 255) / 256);
+    hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_pyr_pvs_batch_kernel), dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, dm.gx, ctx->cam);
+    kf_launch_detect_batch(nb, curs[0]->L, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L), st);
+    hipLaunchKernelGGL(tm_compact_select_batch_kernel, dim3(1 + fast_compact_blocks(curs[0]->L), nb), dim3(1024), 0, st, d_it, o);
+    // ---- the two stages, the wait ----
+    const TmPoseForm form = tm_pose_form(false, dm.n_max, dm.ncc_max);
+    for (int sg = 0; sg < 2 && !rc; sg++) rc = tm_enqueue_stage(ctx, nb, a, dm, o, sg, form);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return tm_collect(nb, ts, st, o, false, false, outs);
+}
+
 
 // ---- Tracker::TrackFrame's tracking branch (src/Tracker.cc:94-108, :134-137, :1013-1056) for nb cameras in ONE chain ----
 // ptam_track_map_frames_batch with what ptam_track_frame / ptam_track_frame_sbi put around TrackMap: the bTryCoarse heuristics per
 // camera (each frame's TmBatchItem carries its own), the motion model, and — for a frame with a rotation estimator — this frame's
-// SmallBlurryImage, its alignment against last frame's and the prediction from the rotation, all on the device: the align workgroup's
-// thread 0 writes the pose the PVS pass then reads.  The chain (docs/LOG_sbi.md has the arrangements that were measured):
-//   pyramid | PVS of the frames the host predicted  ->  SBI make  ->  align + predict | FAST detect  ->  PVS of the aligned frames
-//   ->  set choice | corner compaction  ->  search, pose (coarse)  ->  search, pose (fine)
-// Every frame's pose loops run in the kernel instantiation its OWN list lengths select (the frames of one instantiation share a
-// launch), so a frame's result is the single call's bit for bit; a fine list that outgrows the fused kernel is finished on the
-// frame's own queue after the wait, as in the single call.
+// SmallBlurryImage, its alignment against last frame's and the prediction from the rotation, all on the device.  In three steps
+// that share a TfbPlan: tfb_plan (host only), tfb_enqueue (the chain), tfb_finish (models, estimators, infos).
 // rv (nullable): ptam_track_frames_recover_batch's recovering cameras — rv->recovering[i] != 0: frame i runs the relocaliser in the
 // chain instead of a prediction, and TrackMap behind it only where the relocaliser's verdict is good (TmBatchItem::gate).  The caller
-// has checked their banks and scratches.  Without rv, or with no camera recovering, nothing below differs from the plain batch.
+// has checked their banks and scratches.  Without rv, or with no camera recovering, nothing differs from the plain batch.
 struct TfbRecover {
     const char* recovering;           // [nb]
     ptam_sbi_bank* const* banks;      // [nb]
@@ -1833,352 +1948,295 @@ struct TfbRecover {
     ptam_reloc_result* reloc;         // out: the recovering frames' results, frame i's reloc_stride bytes behind frame i - 1's
     size_t reloc_stride;
 };
-static int tfb_impl(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_motion_model* models,
-                    ptam_rotation_estimator* const* ests, const ptam_trackmap_opts* opts, ptam_trackmap_result* outs, ptam_track_frame_info* info,
-                    size_t info_stride, const TfbRecover* rv) {
-    // (info_stride: frame i's info lies that many bytes behind frame i - 1's — inside the caller's own per-frame struct, or an array)
-    auto info_at = [&](int i) -> ptam_track_frame_info& { return *(ptam_track_frame_info*)((char*)info + (size_t)i * info_stride); };
-    // ---- everything that needs no device ----
-    ARG_TRY(nb >= 1 && nb <= 4096 && ts && curs && d_frames && models && outs);
-    for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i] && d_frames[i]);
-    ptam_trackmap_opts o;
-    int rc = tm_opts(opts, &o);
+struct TfbPlan {
+    int nb;
+    ptam_rotation_estimator* const* ests;   // nullable, and so is every entry
+    const TfbRecover* rv;
+    ptam_trackmap_opts o;                   // the caller's, checked
+    std::vector<ptam_trackmap_opts> fo;     // per frame: o with the frame's heuristics
+    std::vector<ptam_motion_model> tmp;     // the models, advanced on copies (committed by tfb_finish)
+    std::vector<int> est_of;                // the frames that have an estimator, those of recovering frames last
+    std::vector<int> rr_of;                 // the recovering frames
+    int n_est, n_rr, n_est_align, rr_max_count;
+    bool est(int i) const { return ests && ests[i]; }
+    bool recovering(int i) const { return rv && rv->recovering[i]; }
+};
+
+// Everything that needs no device: the options, the estimators' order and checks, the recovering list, the heuristics and the
+// prediction.  ts / curs / d_frames have passed tm_batch_check.
+static int tfb_plan(int nb, ptam_tracker* const* ts, const ptam_motion_model* models, ptam_rotation_estimator* const* ests,
+                    const ptam_trackmap_opts* opts, const TfbRecover* rv, TfbPlan* p) {
+    p->nb = nb, p->ests = ests, p->rv = rv;
+    int rc = tm_opts(opts, &p->o);
     if (rc) return rc;
-    ptam_tracker* lead = ts[0];
-    ptam_ctx* ctx = lead->ctx;
-    const KfLevels& L0 = curs[0]->L;
-    for (int i = 0; i < nb; i++) {
-        ARG_TRY(ts[i]->ctx->device == ctx->device && curs[i]->device == ctx->device);
-        ARG_TRY(ts[i]->ctx->halfsample == ctx->halfsample && std::memcmp(&ts[i]->ctx->cam, &ctx->cam, sizeof(DevCam)) == 0);
-        ARG_TRY(curs[i]->n_blocks == curs[0]->n_blocks);
-        for (int l = 0; l < PTAM_LEVELS; l++) ARG_TRY(curs[i]->L.w[l] == L0.w[l] && curs[i]->L.h[l] == L0.h[l]);
-        for (int j = 0; j < i; j++) ARG_TRY(ts[j] != ts[i] && curs[j] != curs[i] && ts[j]->ctx != ts[i]->ctx);   // (a context's scratch serves ONE frame)
-    }
     // the estimators: each its tracker's context's, none twice, all of one image size and blur (their images are made in one launch)
     // (those of recovering frames last: their images are made with the others', but nothing is aligned, src/Tracker.cc:94-108 + :168-176)
-    auto recovering = [&](int i) { return rv && rv->recovering[i]; };
-    std::vector<int> est_of;   // the frames that have one
     for (int pass = 0; pass < 2; pass++)
         for (int i = 0; ests && i < nb; i++) {
-            if (!ests[i] || (int)recovering(i) != pass) continue;
+            if (!ests[i] || (int)p->recovering(i) != pass) continue;
             ARG_TRY(sbi_estimator_ctx(ests[i]) == ts[i]->ctx);
-            for (int j : est_of) ARG_TRY(ests[j] != ests[i]);
-            if (!est_of.empty()) ARG_TRY(sbi_estimators_alike(ests[est_of[0]], ests[i]));
-            est_of.push_back(i);
+            for (int j : p->est_of) ARG_TRY(ests[j] != ests[i]);
+            if (!p->est_of.empty()) ARG_TRY(sbi_estimators_alike(ests[p->est_of[0]], ests[i]));
+            p->est_of.push_back(i);
         }
-    const int n_est = (int)est_of.size();
-    std::vector<int> rr_of;    // the recovering frames
     for (int i = 0; i < nb; i++)
-        if (recovering(i)) rr_of.push_back(i);
-    const int n_rr = (int)rr_of.size();
-    int n_est_align = 0, rr_max_count = 0;
-    for (int i : est_of) n_est_align += !recovering(i);
-    const ptam_sbi_bank* bank0 = n_rr ? rv->banks[rr_of[0]] : nullptr;
-    if (lead->reloc_count) lead->reloc_count->clear();
-    for (int i : rr_of) {
+        if (p->recovering(i)) p->rr_of.push_back(i);
+    p->n_est = (int)p->est_of.size(), p->n_rr = (int)p->rr_of.size();
+    p->n_est_align = p->rr_max_count = 0;
+    for (int i : p->est_of) p->n_est_align += !p->recovering(i);
+    if (ts[0]->reloc_count) ts[0]->reloc_count->clear();
+    for (int i : p->rr_of) {
         int c;
         sbi_bank_camera_positions(rv->banks[i], &c);
-        rr_max_count = std::max(rr_max_count, c);
-        if (ests && ests[i]) ARG_TRY(sbi_estimator_fits_bank(ests[i], rv->banks[i]));
+        p->rr_max_count = std::max(p->rr_max_count, c);
+        if (p->est(i)) ARG_TRY(sbi_estimator_fits_bank(ests[i], rv->banks[i]));
     }
-    // the heuristics, per frame, as ptam_track_frame has them (src/Tracker.cc:503-514); the models advance on copies
-    std::vector<ptam_motion_model> tmp(models, models + nb);
-    std::vector<ptam_trackmap_opts> fo((size_t)nb, o);
+    // the heuristics, per frame, as ptam_track_frame has them; a recovering frame follows AttemptRecovery, which sets
+    // mbJustRecoveredSoUseCoarse with TrackMap at once behind it (:171-173, :205, :508-513)
+    p->tmp.assign(models, models + nb);
+    p->fo.assign((size_t)nb, p->o);
     for (int i = 0; i < nb; i++) {
-        ptam_motion_model& m = tmp[(size_t)i];
-        ptam_trackmap_opts& f = fo[(size_t)i];
-        f.try_coarse = 1;
-        if (m.disable_coarse || m.msd_scaled_velocity < m.coarse_min_velocity || f.coarse_max == 0) f.try_coarse = 0;
-        if (recovering(i)) {   // AttemptRecovery sets mbJustRecoveredSoUseCoarse and TrackMap follows at once (:171-173, :205, :508-513)
-            f.try_coarse = 1;
-            f.coarse_max *= 2;
-            f.coarse_range *= 2;
+        ptam_motion_model& m = p->tmp[(size_t)i];
+        if (track_coarse_heuristics(&p->fo[(size_t)i], &m, p->recovering(i))) {
             ptam_trackmap_opts checked;
-            rc = tm_opts(&f, &checked);
-            if (rc) return rc;
-            continue;          // (no prediction: the relocaliser's pose is the start; the model moves after the wait, if at all)
-        }
-        if (m.just_recovered) {
-            f.try_coarse = 1;
-            f.coarse_max *= 2;
-            f.coarse_range *= 2;
-            m.just_recovered = 0;
-            ptam_trackmap_opts checked;
-            rc = tm_opts(&f, &checked);   // (the doubled values, as TrackMap checks them in the single call)
+            rc = tm_opts(&p->fo[(size_t)i], &checked);   // (the doubled values, as TrackMap checks them in the single call)
             if (rc) return rc;
         }
-        if (ests && ests[i]) std::memcpy(m.start_pose, m.pose, 96);   // (the device makes the pose: ptam_motion_predict_sbi's first line)
+        if (p->recovering(i)) continue;   // (no prediction: the relocaliser's pose is the start; the model moves after the wait, if at all)
+        if (p->est(i)) std::memcpy(m.start_pose, m.pose, 96);   // (the device makes the pose: ptam_motion_predict_sbi's first line)
         else ptam_motion_predict(&m);
     }
-    // ---- from here on an error leaves through fail(): the estimators are where they were ----
-    auto fail = [&](int code) {
-        for (int i : est_of) sbi_estimator_rollback(ests[i]);
-        return code;
-    };
-#define TFB_HIP_TRY(expr)                                                          \
-    do {                                                                           \
-        const hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                                    \
-            ptam_set_error("HIP error: %s (%s)", hipGetErrorString(e_), #expr);    \
-            return fail(PTAM_E_HIP);                                               \
-        }                                                                          \
-    } while (0)
-    TFB_HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    for (int i = 1; i < nb; i++)
-        if (ts[i]->ctx != ctx) TFB_HIP_TRY(ptam_stream_wait(ts[i]->ctx->stream));
-    for (int i : rr_of)   // (the recovering cameras' banks are read on this queue: their adds and pose uploads must be done)
-        if (sbi_bank_ctx(rv->banks[i]) != ctx) TFB_HIP_TRY(ptam_stream_wait(sbi_bank_ctx(rv->banks[i])->stream));
-    // ---- the argument arrays: [nb TmBatchItem | nb PoseBatchItem (coarse) | nb (fine) | n_est SbiBatchRec | 3 nb frame indices] ----
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_items = up((size_t)nb * sizeof(TmBatchItem)), b_pose = up((size_t)nb * sizeof(PoseBatchItem)),
-                 b_rec = up((size_t)std::max(n_est + n_rr, 1) * sizeof(SbiBatchRec)), b_idx = up((size_t)nb * 4),
-                 b_rrec = up((size_t)n_rr * sizeof(SbiRelocRec));
-    const size_t b_all = b_items + 2 * b_pose + b_rec + 3 * b_idx + b_rrec;
-    // (device only, behind the uploaded arrays: the recovering cameras' SSD tables and gates)
-    const size_t b_ssd = up((size_t)n_rr * (size_t)rr_max_count * 8), b_dev = b_all + b_ssd + up((size_t)n_rr * 4);
-    void* pin;
-    rc = ctx_pinned(ctx, b_all + 64, &pin);
-    if (rc) return fail(rc);
-    if (lead->batch_cap < b_dev) {
-        TFB_HIP_TRY(ptam_stream_wait(st));
-        if (lead->batch_dev) TFB_HIP_TRY(hipFree(lead->batch_dev));
-        lead->batch_dev = nullptr;
-        lead->batch_cap = 0;
-        TFB_HIP_TRY(hipMalloc(&lead->batch_dev, b_dev * 2));
-        lead->batch_cap = b_dev * 2;
+    return PTAM_OK;
+}
+
+// The block's records, host only: the frames, the estimators' records, the recovering frames' make and relocaliser records, the
+// index lists.  *n_dev_pose: the frames whose pose is made on the device (index list 0: the aligned ones, then the recovering).
+static int tfb_fill(const TfbPlan& p, const TmBatchArgs& a, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames,
+                    TmBatchDims* dm, int* n_dev_pose) {
+    int rc;
+    for (int i = 0; i < p.nb; i++) {
+        const bool host_pose = !p.est(i) && !p.recovering(i);
+        rc = tm_fill_frame(a, i, ts[i], curs[i], d_frames[i], host_pose ? p.tmp[(size_t)i].pose : nullptr, p.fo[(size_t)i], dm);
+        if (rc) return rc;
     }
-    char* hb = (char*)pin;
-    const char* db = (const char*)lead->batch_dev;
-    TmBatchItem* h_it = (TmBatchItem*)hb;
-    PoseBatchItem* h_pc = (PoseBatchItem*)(hb + b_items);
-    PoseBatchItem* h_pf = (PoseBatchItem*)(hb + b_items + b_pose);
-    SbiBatchRec* h_rec = (SbiBatchRec*)(hb + b_items + 2 * b_pose);
-    int* h_idx = (int*)(hb + b_items + 2 * b_pose + b_rec);   // [est frames | coarse stage by instantiation | fine stage by instantiation]
-    const size_t idx_stride = b_idx / 4;
-    const TmBatchItem* d_it = (const TmBatchItem*)db;
-    const PoseBatchItem* d_pc = (const PoseBatchItem*)(db + b_items);
-    const PoseBatchItem* d_pf = (const PoseBatchItem*)(db + b_items + b_pose);
-    const SbiBatchRec* d_rec = (const SbiBatchRec*)(db + b_items + 2 * b_pose);
-    const int* d_idx = (const int*)(db + b_items + 2 * b_pose + b_rec);
-    SbiRelocRec* h_rrec = (SbiRelocRec*)(hb + b_items + 2 * b_pose + b_rec + 3 * b_idx);
-    const SbiRelocRec* d_rrec = (const SbiRelocRec*)(db + b_items + 2 * b_pose + b_rec + 3 * b_idx);
-    double* d_ssd = (double*)((char*)lead->batch_dev + b_all);
-    int* d_gate = (int*)((char*)lead->batch_dev + b_all + b_ssd);
-    if (n_rr > 0) {
-        if (!lead->reloc_count) lead->reloc_count = new std::vector<int>();
-        lead->reloc_ssd = d_ssd;
-        lead->reloc_stride = rr_max_count;
-    }
-    int gx = 0, gy = 0, n_max = 0, ncc_max = 1;
-    std::vector<int> shape_c((size_t)nb), shape_f((size_t)nb);
-    std::vector<unsigned long long> seqs((size_t)nb);
-    int thr;
-    for (int i = 0; i < nb; i++) {
-        ptam_tracker* t = ts[i];
-        const ptam_trackmap_opts& f = fo[(size_t)i];
-        TmBatchItem& it = h_it[i];
-        std::memset(&it, 0, sizeof it);
-        kf_lite_begin(curs[i], d_frames[i], &it.pa, &gx, &gy);
-        it.n_pyr = gx * gy;
-        it.n = t->d.n;
-        it.L = curs[i]->L;
-        it.d = t->d;
-        it.mbox = t->mbox_dev;
-        it.try_coarse = f.try_coarse, it.coarse_max = f.coarse_max, it.coarse_range = f.coarse_range;
-        if (!(ests && ests[i]) && !recovering(i)) {
-            std::memcpy(it.pv.v, tmp[(size_t)i].pose, 96);
-            it.pv.use = 1;
-        }
-        const int n = t->d.n, ncc = std::max(1, std::min(n, (int)f.coarse_max));
-        n_max = std::max(n_max, n);
-        ncc_max = std::max(ncc_max, ncc);
-        shape_c[(size_t)i] = tm_pose_shape(std::min(ncc, GS_LIMIT), &thr);
-        shape_f[(size_t)i] = tm_pose_shape(std::min(std::max(n, 1), GS_LIMIT), &thr);
-        void* sst;
-        double* su;
-        rc = pose_chain_scratch(t->ctx, std::max(n, 1), &sst, &su);
-        if (rc) return fail(rc);
-        seqs[(size_t)i] = t->seq + 1;
-        h_pc[i] = tm_pose_item(t, 0, ncc, su, sst, 0);
-        h_pf[i] = tm_pose_item(t, 1, std::max(n, 1), su, sst, seqs[(size_t)i]);
-    }
-    if (n_rr > 0 && (tm_no_fuse || ncc_max > GS_LIMIT)) {
+    if (p.n_rr > 0 && tm_pose_form(true, dm->n_max, dm->ncc_max) != TM_POSE_GROUPED) {
         ptam_set_error("a recovering camera in a batch whose coarse lists exceed the fused pose kernels' %d entries", GS_LIMIT);
-        return fail(PTAM_E_ARG);
+        return PTAM_E_ARG;
     }
-    for (int k = 0; k < n_est; k++) {
-        const int i = est_of[(size_t)k];
+    SbiBatchRec* h_rec = a.host<SbiBatchRec>(TmBatchArgs::SBI_REC);
+    for (int k = 0; k < p.n_est; k++) {
+        const int i = p.est_of[(size_t)k];
         SbiBatchRec& r = h_rec[k];
         std::memset(&r, 0, sizeof r);
-        rc = sbi_batch_rec(ests[i], curs[i], &r);
-        if (rc) return fail(rc);
-        std::memcpy(r.velocity, tmp[(size_t)i].velocity, sizeof r.velocity);
-        std::memcpy(r.start_pose, tmp[(size_t)i].start_pose, sizeof r.start_pose);
+        rc = sbi_batch_rec(p.ests[i], curs[i], &r);
+        if (rc) return rc;
+        std::memcpy(r.velocity, p.tmp[(size_t)i].velocity, sizeof r.velocity);
+        std::memcpy(r.start_pose, p.tmp[(size_t)i].start_pose, sizeof r.start_pose);
         r.pose_out = ts[i]->d.pose;
         r.h_align = &ts[i]->mbox_dev->align;
         r.h_pose_in = ts[i]->mbox_dev->pose_in;
     }
-    // the recovering frames: a make record behind the estimators', and the relocaliser's record
-    for (int k = 0; k < n_rr; k++) {
-        const int i = rr_of[(size_t)k];
-        SbiBatchRec& mk = h_rec[n_est + k];
-        SbiRelocRec& r = h_rrec[k];
+    // the recovering frames: a make record behind the estimators', and the relocaliser's record; their SSD rows stay readable
+    // through the lead tracker (ptam_tracker_read_reloc_ssd)
+    ptam_tracker* lead = ts[0];
+    double* d_ssd = a.dev<double>(TmBatchArgs::RELOC_SSD);
+    int* d_gate = a.dev<int>(TmBatchArgs::RELOC_GATE);
+    if (p.n_rr > 0) {
+        if (!lead->reloc_count) lead->reloc_count = new std::vector<int>();
+        lead->reloc_ssd = d_ssd;
+        lead->reloc_stride = p.rr_max_count;
+    }
+    for (int k = 0; k < p.n_rr; k++) {
+        const int i = p.rr_of[(size_t)k];
+        SbiBatchRec& mk = h_rec[p.n_est + k];
+        SbiRelocRec& r = a.host<SbiRelocRec>(TmBatchArgs::RELOC_REC)[k];
         std::memset(&mk, 0, sizeof mk);
         std::memset(&r, 0, sizeof r);
-        sbi_reloc_rec(rv->banks[i], rv->scratch[i], curs[i], &mk, &r);
-        r.ssd = d_ssd + (size_t)k * (size_t)rr_max_count;
-        r.max_score = rv->max_score;
+        sbi_reloc_rec(p.rv->banks[i], p.rv->scratch[i], curs[i], &mk, &r);
+        r.ssd = d_ssd + (size_t)k * (size_t)p.rr_max_count;
+        r.max_score = p.rv->max_score;
         r.pose_out = ts[i]->d.pose;
         r.h_reloc = &ts[i]->mbox_dev->reloc;
         r.gate = d_gate + k;
-        h_it[i].gate = d_gate + k;
+        a.host<TmBatchItem>(TmBatchArgs::ITEMS)[i].gate = d_gate + k;
         lead->reloc_count->push_back(r.count);
     }
-    // the frames whose pose is made on the device (their PVS pass runs behind the align launch): the aligned ones, then the recovering
-    int n_dev_pose = 0;
-    for (int k = 0; k < n_est_align; k++) h_idx[n_dev_pose++] = est_of[(size_t)k];
-    for (int i : rr_of) h_idx[n_dev_pose++] = i;
-    // the frames of every pose-kernel instantiation, stage by stage: n_shape[stage][k] frames from first[stage][k] on
-    int n_shape[2][3] = {{0, 0, 0}, {0, 0, 0}}, first[2][3];
-    for (int sg = 0; sg < 2; sg++) {
-        const std::vector<int>& sh = sg ? shape_f : shape_c;
-        int at = 0;
-        for (int k = 0; k < 3; k++) {
-            first[sg][k] = at;
-            for (int i = 0; i < nb; i++)
-                if (sh[(size_t)i] == k) h_idx[(size_t)(1 + sg) * idx_stride + (size_t)at++] = i;
-            n_shape[sg][k] = at - first[sg][k];
-        }
-    }
-    for (int i = 0; i < nb; i++) {
-        ts[i]->seq = seqs[(size_t)i];
-        ts[i]->last_stream = st;
-    }
-    TFB_HIP_TRY(hipMemcpyAsync(lead->batch_dev, pin, b_all, hipMemcpyHostToDevice, st));
-    // ---- keyframe, the estimators' steps, PVS, set choice ----
-    const int n_pyr = gx * gy, n_pvs = std::max(1, (n_max + 255) / 256);
-    hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_pyr_pvs_batch_kernel), dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, gx, ctx->cam);
-    // (the detection shares the align launch: its workgroups fill the chip under the align workgroups' ~100 us of serial chain, and
-    //  a launch boundary goes — 6-9 % per frame up to 64 cameras, 2-4 % slower at 128; docs/LOG_sbi.md)
+    int* h_idx = a.host_idx(0);
+    *n_dev_pose = 0;
+    for (int k = 0; k < p.n_est_align; k++) h_idx[(*n_dev_pose)++] = p.est_of[(size_t)k];
+    for (int i : p.rr_of) h_idx[(*n_dev_pose)++] = i;
+    tm_group_by_shape(a, p.nb, dm);
+    return PTAM_OK;
+}
+
+// The estimators' and the relocaliser's launches between the pyramid and the set choice (docs/LOG_sbi.md has the arrangements that
+// were measured):   SBI make  ->  align + predict | FAST detect  ->  PVS of the frames whose pose the device made
+// The detection shares the align launch: its workgroups fill the chip under the align workgroups' ~100 us of serial chain, and a
+// launch boundary goes — 6-9 % per frame up to 64 cameras, 2-4 % slower at 128.
+static int tfb_enqueue_sbi(const TfbPlan& p, ptam_ctx* ctx, const TmBatchArgs& a, const KfLevels& L0, int n_pvs, int n_dev_pose) {
+    hipStream_t st = ctx->stream;
+    const int nb = p.nb, n_est = p.n_est, n_rr = p.n_rr;
+    const TmBatchItem* d_it = a.dev<TmBatchItem>(TmBatchArgs::ITEMS);
+    const SbiBatchRec* d_rec = a.dev<SbiBatchRec>(TmBatchArgs::SBI_REC);
+    const SbiRelocRec* d_rrec = a.dev<SbiRelocRec>(TmBatchArgs::RELOC_REC);
     const bool share = !tfb_plain && n_est + n_rr > 0;
     if (!share) kf_launch_detect_batch(nb, L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L), st);
+    if (n_est + n_rr == 0) return PTAM_OK;
+    ptam_rotation_estimator* est0 = n_est ? p.ests[p.est_of[0]] : nullptr;
+    int rc = n_est > 0 ? sbi_batch_launch_make(est0, n_est, d_rec, st) : PTAM_OK;
     if (n_rr > 0) {
         // a recovering camera in the batch: the relocaliser's images (a make launch of their own: the weights are a launch argument and
         // the blur is not the estimators'), every recovering camera's SSDs in one launch, and their align workgroups between the
         // estimators' and the detection's
-        if (n_est > 0) rc = sbi_batch_launch_make(ests[est_of[0]], n_est, d_rec, st);
-        if (!rc) rc = sbi_reloc_launch_make(ctx, bank0, rv->blur, n_rr, d_rec + n_est, st);
-        if (!rc) rc = sbi_reloc_launch_ssd(bank0, n_rr, rr_max_count, d_rrec, st);
+        const ptam_sbi_bank* bank0 = p.rv->banks[p.rr_of[0]];
+        if (!rc) rc = sbi_reloc_launch_make(ctx, bank0, p.rv->blur, n_rr, d_rec + n_est, st);
+        if (!rc) rc = sbi_reloc_launch_ssd(bank0, n_rr, p.rr_max_count, d_rrec, st);
         if (!rc)
-            rc = sbi_recover_launch_align(ctx, bank0, n_est_align, d_rec, n_rr, d_rrec, st, share ? nb : 0, &L0, d_it, sizeof(TmBatchItem),
+            rc = sbi_recover_launch_align(ctx, bank0, p.n_est_align, d_rec, n_rr, d_rrec, st, share ? nb : 0, &L0, d_it, sizeof(TmBatchItem),
                                           offsetof(TmBatchItem, L));
-        if (rc) return fail(rc);
-        hipLaunchKernelGGL(tm_pvs_batch_kernel, dim3(n_pvs, n_dev_pose), dim3(256), 0, st, d_it, d_idx, ctx->cam);
-    } else if (n_est > 0) {
-        rc = sbi_batch_launch_make(ests[est_of[0]], n_est, d_rec, st);
-        if (!rc && share) rc = sbi_batch_launch_align(ests[est_of[0]], n_est, d_rec, st, nb, &L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L));
-        else if (!rc) rc = sbi_batch_launch_align(ests[est_of[0]], n_est, d_rec, st);
-        if (rc) return fail(rc);
-        hipLaunchKernelGGL(tm_pvs_batch_kernel, dim3(n_pvs, n_est), dim3(256), 0, st, d_it, d_idx, ctx->cam);
+    } else if (!rc && share) {
+        rc = sbi_batch_launch_align(est0, n_est, d_rec, st, nb, &L0, d_it, sizeof(TmBatchItem), offsetof(TmBatchItem, L));
+    } else if (!rc) {
+        rc = sbi_batch_launch_align(est0, n_est, d_rec, st);
     }
-    hipLaunchKernelGGL(tm_compact_select_batch_kernel, dim3(1 + fast_compact_blocks(L0), nb), dim3(1024), 0, st, d_it, o);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tm_pvs_batch_kernel, dim3(n_pvs, n_dev_pose), dim3(256), 0, st, d_it, a.dev_idx(0), ctx->cam);
+    return PTAM_OK;
+}
+
+// The chain:   pyramid | PVS of the frames the host predicted  ->  tfb_enqueue_sbi  ->  set choice | corner compaction
+//   ->  search, pose (coarse)  ->  search, pose (fine)
+// *form: how the stages went out (tm_collect wants to know).  A non-zero return leaves the estimators stepped: the caller rolls back.
+static int tfb_enqueue(const TfbPlan& p, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, TmPoseForm* form) {
+    const int nb = p.nb;
+    ptam_tracker* lead = ts[0];
+    ptam_ctx* ctx = lead->ctx;
+    hipStream_t st = ctx->stream;
+    int rc = tm_batch_join(nb, ts);
+    if (rc) return rc;
+    for (int i : p.rr_of)   // (the recovering cameras' banks are read on this queue: their adds and pose uploads must be done)
+        if (sbi_bank_ctx(p.rv->banks[i]) != ctx) HIP_TRY(ptam_stream_wait(sbi_bank_ctx(p.rv->banks[i])->stream));
+    TmBatchArgs a(nb, p.n_est, p.n_rr, p.rr_max_count);
+    TmBatchDims dm;
+    int n_dev_pose = 0;
+    rc = a.reserve(lead);
+    if (!rc) rc = tfb_fill(p, a, ts, curs, d_frames, &dm, &n_dev_pose);
+    if (rc) return rc;
+    tm_commit_seqs(nb, ts, st);
+    HIP_TRY(hipMemcpyAsync(lead->batch_dev, a.hb, a.end(TmBatchArgs::RELOC_REC), hipMemcpyHostToDevice, st));
+    // ---- keyframe, the estimators' steps, PVS, set choice ----
+    const TmBatchItem* d_it = a.dev<TmBatchItem>(TmBatchArgs::ITEMS);
+    const KfLevels& L0 = curs[0]->L;
+    const int n_pyr = dm.gx * dm.gy, n_pvs = std::max(1, (dm.n_max + 255) / 256);
+    hipLaunchKernelGGL(TM_HS_KERNEL(ctx, tm_pyr_pvs_batch_kernel), dim3(n_pyr + n_pvs, nb), dim3(256), 0, st, d_it, dm.gx, ctx->cam);
+    rc = tfb_enqueue_sbi(p, ctx, a, L0, n_pvs, n_dev_pose);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tm_compact_select_batch_kernel, dim3(1 + fast_compact_blocks(L0), nb), dim3(1024), 0, st, d_it, p.o);
     // ---- the two stages ----
-    // (per-frame instantiations when every coarse list fits the fused kernels; otherwise — a CoarseMax above 1024 — the gather pass
-    //  and the small / general kernel pair for everybody, as ptam_track_map_frames_batch does it: results then equal the single
-    //  calls' to rounding)
-    const bool grouped = !tm_no_fuse && ncc_max <= GS_LIMIT;
-    static const int shape_threads[3] = {GS_WAVE_LIMIT, GS_THREADS, GS_THREADS};
-    auto gather = [&](int cap, int stage) {
-        hipLaunchKernelGGL(tm_gather_batch_kernel, dim3(std::max(1, (cap + TM_GATHER_THREADS - 1) / TM_GATHER_THREADS), nb), dim3(TM_GATHER_THREADS), 0, st,
-                           d_it, stage, (int)o.coarse_subpix_its, o.coarse_min);
-    };
-    for (int sg = 0; sg < 2; sg++) {
-        const int cap = sg ? std::max(n_max, 1) : ncc_max;
-        hipLaunchKernelGGL(tm_search_batch_kernel, dim3(std::max(1, (cap + 3) / 4), nb), dim3(256), 0, st, ctx->cam, d_it, sg, sg ? 0 : (int)o.coarse_subpix_its);
-        const ptam_gn_opts g = tm_gn_opts(sg, o.estimator);
-        if (grouped) {
-            for (int k = 0; k < 3; k++)
-                if (n_shape[sg][k] > 0)
-                    hipLaunchKernelGGL(tm_pose_batch_fns[k], dim3(n_shape[sg][k]), dim3(shape_threads[k]), 0, st, ctx->cam, d_it, sg ? d_pf : d_pc,
-                                       d_idx + (size_t)(1 + sg) * idx_stride + first[sg][k], sg, o.coarse_min, g);
-        } else {
-            gather(sg ? n_max : ncc_max, sg);
-            rc = pose_launch_chain_batch(ctx, nb, cap, sg ? d_pf : d_pc, &g);
-            if (rc) return fail(rc);
-        }
-    }
-    TFB_HIP_TRY(hipGetLastError());
-#undef TFB_HIP_TRY
-    // ---- wait + result, frame by frame; then, every frame having arrived, the models and the estimators move ----
-    for (int i = 0; i < nb; i++) {
-        rc = tm_wait_frame(ts[i], st, o, seqs[(size_t)i], grouped);
-        if (rc) {
-            const std::string e = ptam_last_error();
-            ptam_set_error("frame %d of the batch: %s", i, e.c_str());
-            return fail(rc);
-        }
-        tm_read_result(ts[i], outs + i);
-    }
-    for (int i = 0; i < nb; i++) {
-        ptam_motion_model& m = tmp[(size_t)i];
-        const bool est = ests && ests[i];
-        if (recovering(i)) {
-            ptam_reloc_result& rr = *(ptam_reloc_result*)((char*)rv->reloc + (size_t)i * rv->reloc_stride);
-            std::memcpy(&rr, (const void*)&ts[i]->mbox->reloc, sizeof rr);
-            if (info) {
-                ptam_track_frame_info& fi = info_at(i);
-                std::memset(&fi, 0, sizeof fi);
-                if (rr.good) std::memcpy(fi.pose_in, rr.pose, 96);
-                fi.try_coarse = fo[(size_t)i].try_coarse;
-                fi.coarse_max = fo[(size_t)i].coarse_max;
-                fi.coarse_range = fo[(size_t)i].coarse_range;
-            }
-            if (rr.good) {
-                // Tracker::AttemptRecovery :203-205, then TrackMap and no UpdateMotionModel (:171-175): the scene depth of :692-696 is
-                // all that ptam_motion_update would do here
-                std::memcpy(m.pose, outs[i].pose, 96);
-                std::memcpy(m.start_pose, rr.pose, 96);
-                std::memset(m.velocity, 0, sizeof m.velocity);
-                m.just_recovered = 0;
-                if (outs[i].depth_n > 20) {
-                    m.scene_depth_mean = outs[i].depth_sum / outs[i].depth_n;
-                    m.scene_depth_sigma = std::sqrt(outs[i].depth_sum_sq / outs[i].depth_n - m.scene_depth_mean * m.scene_depth_mean);
-                }
-                models[i] = m;
-            } else {
-                std::memset(outs + i, 0, sizeof outs[i]);   // (the mailbox still holds the frame before: nothing of TrackMap ran)
-            }
-            sbi_reloc_commit(rv->scratch[i]);
-            if (est) sbi_estimator_commit(ests[i]);
-            continue;
-        }
-        if (est) std::memcpy(m.pose, (const void*)ts[i]->mbox->pose_in, 96);
+    *form = tm_pose_form(true, dm.n_max, dm.ncc_max);
+    for (int sg = 0; sg < 2 && !rc; sg++) rc = tm_enqueue_stage(ctx, nb, a, dm, p.o, sg, *form);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
+// Every frame has arrived: the models and the estimators move, the infos are written (info_stride: frame i's info lies that many
+// bytes behind frame i - 1's — inside the caller's own per-frame struct, or an array).
+static void tfb_finish(const TfbPlan& p, ptam_tracker* const* ts, ptam_motion_model* models, ptam_trackmap_result* outs,
+                       ptam_track_frame_info* info, size_t info_stride) {
+    for (int i = 0; i < p.nb; i++) {
+        ptam_motion_model m = p.tmp[(size_t)i];
+        const bool est = p.est(i), rec = p.recovering(i);
+        ptam_reloc_result* rr = rec ? (ptam_reloc_result*)((char*)p.rv->reloc + (size_t)i * p.rv->reloc_stride) : nullptr;
+        if (rec) std::memcpy(rr, (const void*)&ts[i]->mbox->reloc, sizeof *rr);
+        else if (est) std::memcpy(m.pose, (const void*)ts[i]->mbox->pose_in, 96);
         if (info) {
-            ptam_track_frame_info& fi = info_at(i);
+            ptam_track_frame_info& fi = *(ptam_track_frame_info*)((char*)info + (size_t)i * info_stride);
             std::memset(&fi, 0, sizeof fi);
-            std::memcpy(fi.pose_in, m.pose, 96);
-            if (est) std::memcpy(&fi.align, (const void*)&ts[i]->mbox->align, sizeof fi.align);
-            fi.try_coarse = fo[(size_t)i].try_coarse;
-            fi.coarse_max = fo[(size_t)i].coarse_max;
-            fi.coarse_range = fo[(size_t)i].coarse_range;
+            if (!rec) std::memcpy(fi.pose_in, m.pose, 96);
+            else if (rr->good) std::memcpy(fi.pose_in, rr->pose, 96);
+            if (est && !rec) std::memcpy(&fi.align, (const void*)&ts[i]->mbox->align, sizeof fi.align);
+            fi.try_coarse = p.fo[(size_t)i].try_coarse;
+            fi.coarse_max = p.fo[(size_t)i].coarse_max;
+            fi.coarse_range = p.fo[(size_t)i].coarse_range;
         }
-        ptam_motion_update(&m, outs + i);
-        models[i] = m;
-        if (est) sbi_estimator_commit(ests[i]);
+        if (!rec) {
+            ptam_motion_update(&m, outs + i);
+            models[i] = m;
+        } else if (rr->good) {
+            // Tracker::AttemptRecovery :203-205, then TrackMap and no UpdateMotionModel (:171-175): the scene depth of :692-696 is
+            // all that ptam_motion_update would do here
+            std::memcpy(m.pose, outs[i].pose, 96);
+            std::memcpy(m.start_pose, rr->pose, 96);
+            std::memset(m.velocity, 0, sizeof m.velocity);
+            m.just_recovered = 0;
+            motion_update_scene_depth(&m, outs + i);
+            models[i] = m;
+        } else {
+            std::memset(outs + i, 0, sizeof outs[i]);   // (the mailbox still holds the frame before: nothing of TrackMap ran)
+        }
+        if (rec) sbi_reloc_commit(p.rv->scratch[i]);
+        if (est) sbi_estimator_commit(p.ests[i]);
     }
+}
+
+static int tfb_impl(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_motion_model* models,
+                    ptam_rotation_estimator* const* ests, const ptam_trackmap_opts* opts, ptam_trackmap_result* outs, ptam_track_frame_info* info,
+                    size_t info_stride, const TfbRecover* rv) {
+    TfbPlan p;
+    int rc = tfb_plan(nb, ts, models, ests, opts, rv, &p);
+    if (rc) return rc;
+    TmPoseForm form = TM_POSE_GROUPED;
+    rc = tfb_enqueue(p, ts, curs, d_frames, &form);
+    if (!rc) rc = tm_collect(nb, ts, ts[0]->ctx->stream, p.o, true, form == TM_POSE_GROUPED, outs);
+    if (rc) {   // the estimators are where they were
+        for (int i : p.est_of) sbi_estimator_rollback(ests[i]);
+        return rc;
+    }
+    tfb_finish(p, ts, models, outs, info, info_stride);
     return PTAM_OK;
 }
 
 int ptam_track_frames_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_motion_model* models,
                             ptam_rotation_estimator* const* ests, const ptam_trackmap_opts* opts, ptam_trackmap_result* outs,
                             ptam_track_frame_info* info) {
+    ARG_TRY(models && outs);
+    if (int rc = tm_batch_check(nb, ts, curs, d_frames)) return rc;
     return tfb_impl(nb, ts, curs, d_frames, models, ests, opts, outs, info, sizeof(ptam_track_frame_info), nullptr);
 }
 
-// the camera position of an se3CfromW: se3CfromW.inverse().get_translation() = -R^T t (KeyFrameLinearDist, src/MapMaker.cc:696-703)
-static void tfr_camera_position(const double p[12], double out[3]) {
-    for (int k = 0; k < 3; k++) out[k] = -(p[k] * p[9] + p[3 + k] * p[10] + p[6 + k] * p[11]);
+// One camera's state after its frame of ptam_track_frames_recover_batch (host only): the closest keyframe of the tracked pose,
+// the tracking quality, and — on the tracking branch — IsNeedNewKeyFrame and whether the tracker would hand the frame to the map maker
+static void tfr_advance_state(ptam_track_state& s, ptam_track_frame_state_info& fi, bool rec, const ptam_motion_model& model,
+                              const ptam_sbi_bank* bank, const ptam_trackmap_result& out, const ptam_track_state_opts& so) {
+    if (!rec) std::memset(&fi.reloc, 0, sizeof fi.reloc);
+    fi.closest_kf = -1;
+    fi.closest_kf_dist = 0.0;
+    fi.need_new_keyframe = fi.want_keyframe = 0;
+    fi.branch = !rec ? PTAM_FRAME_TRACKED : fi.reloc.good ? PTAM_FRAME_RECOVERED : PTAM_FRAME_RECOVERY_FAILED;
+    s.frame++;                                         // :111
+    if (fi.branch == PTAM_FRAME_RECOVERY_FAILED) return;
+    s.model = model;
+    // ClosestKeyFrame (src/MapMaker.cc:736-752) of the tracked pose: the first strictly lowest distance
+    int count = 0;
+    const double* kp = bank ? sbi_bank_camera_positions(bank, &count) : nullptr;
+    if (kp && count > 0) {
+        double best = 9999999999.9, here[3];
+        se3_camera_position(out.pose, here);
+        for (int k = 0; k < count; k++) {
+            const double* there = kp + 3 * (size_t)k;
+            const double dx = there[0] - here[0], dy = there[1] - here[1], dz = there[2] - here[2];
+            const double d = std::sqrt(dx * dx + dy * dy + dz * dz);   // KeyFrameLinearDist
+            if (d < best) best = d, fi.closest_kf = k;
+        }
+        if (fi.closest_kf >= 0) fi.closest_kf_dist = best;
+    }
+    ptam_assess_tracking_quality(&s, out.attempted, out.found, fi.closest_kf_dist, &so);
+    if (fi.branch == PTAM_FRAME_TRACKED) {         // :146-161; the recovery branch decides nothing about keyframes
+        if (fi.closest_kf >= 0)                    // IsNeedNewKeyFrame, src/MapMaker.cc:754-763
+            fi.need_new_keyframe = fi.closest_kf_dist * (1.0 / s.model.scene_depth_mean) > so.max_kf_dist_wiggle_mult * so.wiggle_scale_depth_normalized;
+        fi.want_keyframe = s.quality == PTAM_TRACK_GOOD && s.frame - s.last_keyframe_dropped > 20;
+    }
 }
 
 // ---- Tracker::TrackFrame for a good map (src/Tracker.cc:127-176) for nb cameras: ptam_track_frames_batch's chain, in which a camera
@@ -2187,8 +2245,8 @@ int ptam_track_frames_recover_batch(int nb, ptam_tracker* const* ts, ptam_kf* co
                                     ptam_rotation_estimator* const* ests, ptam_sbi_bank* const* banks, ptam_sbi* const* scratch,
                                     const ptam_trackmap_opts* opts, const ptam_track_state_opts* state_opts, ptam_trackmap_result* outs,
                                     ptam_track_frame_state_info* info) {
-    ARG_TRY(nb >= 1 && nb <= 4096 && ts && curs && d_frames && states && outs);
-    for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i] && d_frames[i]);
+    ARG_TRY(states && outs);
+    if (int rc = tm_batch_check(nb, ts, curs, d_frames)) return rc;
     ptam_track_state_opts so;
     ptam_track_state_opts_default(&so);
     if (state_opts) so = *state_opts;
@@ -2220,39 +2278,8 @@ int ptam_track_frames_recover_batch(int nb, ptam_tracker* const* ts, ptam_kf* co
     const TfbRecover rv = {rec.data(), banks, scratch, so.reloc_blur, so.reloc_max_score, &info[0].reloc, stride};
     if (int rc = tfb_impl(nb, ts, curs, d_frames, models.data(), ests, opts, outs, &info[0].frame, stride, n_rr ? &rv : nullptr)) return rc;
     // ---- every frame has arrived: the states move ----
-    for (int i = 0; i < nb; i++) {
-        ptam_track_state& s = states[i];
-        ptam_track_frame_state_info& fi = info[i];
-        if (!rec[(size_t)i]) std::memset(&fi.reloc, 0, sizeof fi.reloc);
-        fi.closest_kf = -1;
-        fi.closest_kf_dist = 0.0;
-        fi.need_new_keyframe = fi.want_keyframe = 0;
-        fi.branch = !rec[(size_t)i] ? PTAM_FRAME_TRACKED : fi.reloc.good ? PTAM_FRAME_RECOVERED : PTAM_FRAME_RECOVERY_FAILED;
-        s.frame++;                                         // :111
-        if (fi.branch != PTAM_FRAME_RECOVERY_FAILED) {
-            s.model = models[(size_t)i];
-            // ClosestKeyFrame (src/MapMaker.cc:736-752) of the tracked pose: the first strictly lowest distance
-            int count = 0;
-            const double* kp = banks && banks[i] ? sbi_bank_camera_positions(banks[i], &count) : nullptr;
-            if (kp && count > 0) {
-                double best = 9999999999.9, here[3];
-                tfr_camera_position(outs[i].pose, here);
-                for (int k = 0; k < count; k++) {
-                    const double* there = kp + 3 * (size_t)k;
-                    const double dx = there[0] - here[0], dy = there[1] - here[1], dz = there[2] - here[2];
-                    const double d = std::sqrt(dx * dx + dy * dy + dz * dz);   // KeyFrameLinearDist
-                    if (d < best) best = d, fi.closest_kf = k;
-                }
-                if (fi.closest_kf >= 0) fi.closest_kf_dist = best;
-            }
-            ptam_assess_tracking_quality(&s, outs[i].attempted, outs[i].found, fi.closest_kf_dist, &so);
-            if (fi.branch == PTAM_FRAME_TRACKED) {         // :146-161; the recovery branch decides nothing about keyframes
-                if (fi.closest_kf >= 0)                    // IsNeedNewKeyFrame, src/MapMaker.cc:754-763
-                    fi.need_new_keyframe = fi.closest_kf_dist * (1.0 / s.model.scene_depth_mean) > so.max_kf_dist_wiggle_mult * so.wiggle_scale_depth_normalized;
-                fi.want_keyframe = s.quality == PTAM_TRACK_GOOD && s.frame - s.last_keyframe_dropped > 20;
-            }
-        }
-    }
+    for (int i = 0; i < nb; i++)
+        tfr_advance_state(states[i], info[i], rec[(size_t)i] != 0, models[(size_t)i], banks ? banks[i] : nullptr, outs[i], so);
     return PTAM_OK;
 }
 

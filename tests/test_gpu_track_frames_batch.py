@@ -352,6 +352,69 @@ def test_maps_beyond_the_fused_pose_kernels(hip):
     ctx0.close()
 
 
+def test_a_refused_plain_batch_leaves_the_trackers_usable(hip):
+    """ptam_track_map_frames_batch, nb = 2 on the rig of test_the_smallest_chain: a call refused for its second slot (a keyframe of
+    another size) and one refused for its options, each followed by a good call — whose results must be those of the same good
+    calls on twin trackers that never saw a refusal"""
+    size = (163, 121)
+    seq = SC.tracking_sequence()[0]
+    f0 = [np.ascontiguousarray(f[:size[1], :size[0]]) for f in seq[:2]]
+    cams = [Camera(hip, size=size, empty=True, frames=f0, estimator=False), Camera(hip, size=size, empty=True, frames=f0[::-1], estimator=False)]
+    big_ctx = host.Context(lib=hip)
+    big_kf = host.KeyFrame(big_ctx)
+    poses = np.stack([np.concatenate([np.eye(3).reshape(9), [0.0, 0.0, 1.5]]), np.concatenate([np.eye(3).reshape(9), [0.01, -0.02, 1.4]])])
+    trs, kfs = [c.tr for c in cams], [c.kf for c in cams]
+    twins, kf_twins = [c.twin for c in cams], [c.kf_twin for c in cams]
+    for k in range(2):
+        d = [c.d_frames[k] for c in cams]
+        with pytest.raises(host.PtamError):
+            host.Tracker.TrackFramesBatch(trs, [kfs[0], big_kf], d, poses)
+        with pytest.raises(host.PtamError):
+            host.Tracker.TrackFramesBatch(trs, kfs, d, poses, trs[0].opts(coarse_range=5000))
+        got = host.Tracker.TrackFramesBatch(trs, kfs, d, poses)
+        want = host.Tracker.TrackFramesBatch(twins, kf_twins, d, poses)
+        for f in got.dtype.names:
+            assert np.array_equal(got[f], want[f]), (k, f)
+        assert np.array_equal(got["pose"], poses) and (got["n_meas"] == 0).all()      # an empty map: the pose that went in
+        for c in cams:
+            assert c.tr.iteration_set().tobytes() == c.twin.iteration_set().tobytes()
+    big_kf.close()
+    big_ctx.close()
+    for c in cams:
+        c.close()
+
+
+def test_coarse_lists_beyond_the_fused_kernels_equal_the_plain_batch(hip):
+    """ptam_track_frames_batch with CoarseMax = 1100 on maps of about 2 000 points, no estimators, both models fast enough for the
+    coarse stage: every coarse list outgrows the fused pose kernels, so both stages go through the gather pass and the small / general
+    kernel pair — the launches of ptam_track_map_frames_batch from the same poses with the same options.  Every result field equal."""
+    seq = SC.tracking_sequence()
+    ctx0 = host.Context(lib=hip)
+    kf0 = host.KeyFrame(ctx0).MakeKeyFrame_Lite(seq[2])
+    big = synth.make_sequence_map([kf0.level(l) for l in range(4)], seq[3], counts=(900, 500, 300, 200))
+    assert len(big["world"]) > 1900
+    cams = [Camera(hip, mapping=big, estimator=False), Camera(hip, mapping=big, estimator=False)]
+    ks = [0, 1]
+    for c, k in zip(cams, ks):
+        c.model = c.tr.motion_model(c.poses[k])
+        c.model.msd_scaled_velocity = 0.05      # (above coarse_min_velocity = 0.006; the velocity itself stays zero)
+    opts = cams[0].tr.opts(coarse_max=1100)
+    res, infos, _ = _batch(cams, ks, opts)
+    print("points", len(big["world"]), "n_coarse", res["n_coarse"], "n_meas", res["n_meas"])
+    for i in range(2):
+        assert (infos[i]["try_coarse"], infos[i]["coarse_max"]) == (1, 1100) and res[i]["did_coarse"] == 1 and res[i]["n_meas"] >= 50, i
+    opts["try_coarse"] = 1
+    plain = host.Tracker.TrackFramesBatch([c.twin for c in cams], [c.kf_twin for c in cams], [c.d_frames[k] for c, k in zip(cams, ks)],
+                                          np.stack([infos[i]["pose_in"] for i in range(2)]), opts)
+    for f in res.dtype.names:
+        assert np.array_equal(res[f], plain[f]), f
+    for c in cams:
+        assert c.tr.iteration_set().tobytes() == c.twin.iteration_set().tobytes()
+        c.close()
+    kf0.close()
+    ctx0.close()
+
+
 def test_closed_loop_against_the_cpu_composition(hip, oracle):
     """a batch of two cameras on the same sequence: frame by frame both start from the CPU loop's model state and must agree with it
     as ptam_track_frame_sbi does (test_gpu_sbi_track.py); and a free-running batch loop against a free-running ptam_track_frame_sbi"""
