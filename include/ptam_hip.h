@@ -718,7 +718,8 @@ int ptam_sbi_calc_rotation(ptam_sbi* current, const ptam_sbi* target, int iterat
 typedef struct ptam_sbi_bank ptam_sbi_bank;
 int ptam_sbi_bank_create(ptam_ctx* ctx, int frame_w, int frame_h, int capacity, ptam_sbi_bank** out);
 int ptam_sbi_bank_destroy(ptam_sbi_bank* b);
-/* one make launch into the next entry, asynchronous; *index (nullable): the entry.  PTAM_E_LIMIT: the bank is full. */
+/* one make launch into the next entry, asynchronous; *index (nullable): the entry.  PTAM_E_LIMIT: the bank is full.  PTAM_E_STATE
+ * (this call and the next): the entries came from ptam_sbi_bank_take_keyframes and the bank has not been cleared since. */
 int ptam_sbi_bank_add(ptam_sbi_bank* b, const ptam_kf* kf, double blur, int* index);
 /* n keyframes into the next n entries with ONE make launch (grid x = n), asynchronous; *first_index (nullable): the first entry.
  * PTAM_E_LIMIT: fewer than n entries are free; nothing is added. */
@@ -1488,7 +1489,9 @@ int ptam_map_snapshot_info(ptam_map_snapshot*, ptam_map_snapshot_info_t* out);
  * ptam_map_snapshot_reserve avoids.
  * PTAM_E_ARG, decided before anything is enqueued, the snapshot keeping its generation: a keyframe of the map without a handle (or
  * with one of another device), a snapshot on another device than the map's.  PTAM_E_STATE: a publish into this snapshot is under way.
- * Moves 64 n_kf bytes up and nothing down: nothing proportional to the points. */
+ * Moves 64 n_kf bytes up and nothing down: nothing proportional to the points.
+ * Into a snapshot with a keyframe section (ptam_snapshot_keyframes_enable, below) the same call also publishes the keyframes'
+ * poses and SmallBlurryImages, with the further refusals and the 8 bytes per made image listed there. */
 int ptam_rmap_publish(ptam_rmap*, ptam_map_snapshot*, ptam_map_publish_result* res);
 /* rows [first, first + count) of the serial column.  PTAM_E_ARG: a range outside the points.  Moves 8 count bytes down. */
 int ptam_rmap_point_serials(ptam_rmap*, int first, int count, int64_t* out);
@@ -1520,6 +1523,71 @@ int ptam_tracker_point_serials(ptam_tracker*, int first, int count, int64_t* out
  * ptam_rmap_resolve_serials turns into the map's numbering of the moment.  out (nullable: *n alone), cap as there.
  * PTAM_E_STATE: the tracker's map did not come from a snapshot. */
 int ptam_tracker_read_iteration_serials(ptam_tracker*, int64_t* out, int cap, int* n);
+
+/* ---- The map's keyframes published to the relocaliser on the device ---------------------------------------------------------------
+ *      The reference's relocaliser and IsNeedNewKeyFrame read Map::vpKeyFrames directly (src/Relocaliser.cc:12-38,
+ *      src/MapMaker.cc:736-763): every keyframe's pSBI (src/KeyFrame.cc:80-81) and se3CfromW.  Here the tracker's thread keeps them
+ *      in a ptam_sbi_bank; with a keyframe section in the snapshot the bank follows the resident map without the host carrying a
+ *      keyframe handle or a pose table between the threads.
+ *      KEYFRAME IDENTITY.  A ptam_rmap only appends keyframes (add_keyframe, insert_keyframe, insert_keyframe_report) or replaces
+ *      them all (ptam_rmap_upload).  The handle counts its successful uploads (the keyframe epoch): (map_id, epoch) and an index
+ *      name a keyframe, and a keyframe's SmallBlurryImage never changes.
+ *      TWO TAKES.  ptam_tracker_take_map and ptam_sbi_bank_take_keyframes are separate calls (batched trackers keep one bank per
+ *      camera), each against its own (snapshot, generation).  A publish can land between the two: each side is then whole in
+ *      itself, of one generation, and the next frame's poll brings the other one up. */
+typedef struct {
+    int64_t generation;                 /* the snapshot's current generation (0: never published into) */
+    int64_t map_id, epoch;              /* of the keyframes it holds (0: none, or published before the section was enabled) */
+    int32_t enabled, max_keyframes;
+    int32_t n_kf, n_made;               /* keyframes in the current generation | SmallBlurryImages its publish had to make */
+    int32_t sbi_w, sbi_h;               /* mirSize for the snapshot's frame size */
+    double blur;
+} ptam_snapshot_keyframes_info_t;
+typedef struct {
+    int32_t changed;                    /* 0: the bank holds this generation already; nothing else was done */
+    int32_t n_kf;                       /* the bank's count after the call */
+    int32_t n_new;                      /* SmallBlurryImages copied into the bank */
+    int32_t link_bytes;                 /* what crossed the host link in this call: 96 n_kf, or 0 */
+    int64_t generation, map_id;
+} ptam_keyframes_take_result;
+/* Room for max_keyframes keyframes in every slot: se3CfromW (12 doubles) and a SmallBlurryImage in the ptam_sbi_bank's layout,
+ * 13 bytes a pixel (about 15.6 kB per keyframe and slot at 640x480); blur: 2.5, the keyframes' (include/ImageProcess.h:57-58).
+ * The publisher's thread, before the threads start or between two publishes; generations published before it hold no keyframes.
+ * PTAM_E_ARG: max_keyframes < 1 (or above 65535), a blur outside (0, 5].  PTAM_E_LIMIT: a frame size whose SmallBlurryImage is
+ * above the library's limit.  PTAM_E_STATE: enabled already, or a publish is under way.
+ * ptam_rmap_publish into an enabled snapshot then also, in the same slot, on the same queue, before its one wait and its commit:
+ *   (a) copies the resident pose table [0, n_kf) into the slot, device to device;
+ *   (b) makes the SmallBlurryImage (src/KeyFrame.cc:80-81) of every keyframe the slot does not hold yet — [slot's count, n_kf) when
+ *       the slot last held keyframes of the same (map_id, epoch), else [0, n_kf) — with ONE make launch, grid x = their number, the
+ *       kernel of ptam_sbi_bank_add_batch: with three slots a keyframe's image is made at most three times in its life;
+ * so the points and the keyframes of a generation belong together.  Further refusals, decided before a slot is taken, the snapshot
+ * keeping its generation: PTAM_E_LIMIT, n_kf > max_keyframes; PTAM_E_ARG, a keyframe of another frame size than the snapshot's.
+ * Moves 8 bytes up per image made (its level-3 address; counted in ptam_rmap_traffic) and nothing down. */
+int ptam_snapshot_keyframes_enable(ptam_map_snapshot*, int max_keyframes, double blur /* 2.5 */);
+/* any thread */
+int ptam_snapshot_keyframes_info(ptam_map_snapshot*, ptam_snapshot_keyframes_info_t* out);
+/* Map::vpKeyFrames as Relocaliser::AttemptRecovery (src/Relocaliser.cc:12-38) and MapMaker::ClosestKeyFrame (src/MapMaker.cc:
+ * 736-763) read it, from the snapshot's current generation into the bank; the tracker's thread, synchronous, one wait.  If the
+ * generation is the one this bank took last: changed = 0, no launch, no copy — the per-frame poll.  Otherwise ONE copy launch moves
+ * the poses [0, n_kf) into the bank's device table and the SmallBlurryImages the bank lacks into its entries — [count, n_kf) when
+ * the bank's entries are keyframes of the same snapshot, map_id and epoch and count <= n_kf, else [0, n_kf) — and the poses come down
+ * once into the bank's host mirror (what ptam_sbi_bank_poses and the closest-keyframe walk of ptam_track_frames_recover_batch
+ * read), behind any pending copy from that mirror; then count = n_kf.
+ * PTAM_E_STATE: the keyframe section is not enabled.  PTAM_E_ARG: a snapshot on another device, of another frame size, or never
+ * published into (since the section was enabled); a bank that holds entries added by hand with another blur than the snapshot's —
+ * the bank is the only record of a blur on the tracker's side (ptam_relocalise and ptam_track_frames_recover_batch take theirs per
+ * call), so entries of blur x mean the bank is used with x.  PTAM_E_LIMIT: n_kf above the bank's capacity.  In every refusal the
+ * bank, its mirror and what it remembers of its last take are as they were.
+ * After a take ptam_sbi_bank_add / _add_batch are refused (PTAM_E_STATE) until ptam_sbi_bank_clear; ptam_sbi_bank_set_poses stays
+ * allowed, and the next changed take overwrites what it set.
+ * Moves 96 n_kf bytes down and nothing up. */
+int ptam_sbi_bank_take_keyframes(ptam_sbi_bank*, ptam_map_snapshot*, ptam_keyframes_take_result* res);
+/* Tracker::Reset / a new map (src/Tracker.cc:49-76; MapMaker::Reset, src/MapMaker.cc:37-43, clears Map::vpKeyFrames): count = 0, and where the entries came from is forgotten: both
+ * ptam_sbi_bank_add and a take work again, a take copying every entry. */
+int ptam_sbi_bank_clear(ptam_sbi_bank*);
+/* entry `index` as ptam_sbi_read gives a single image (mimSmall, mimTemplate, mimImageJacs of Map::vpKeyFrames[index]->pSBI);
+ * NULL pointers are skipped.  PTAM_E_ARG: an index outside [0, count). */
+int ptam_sbi_bank_read(ptam_sbi_bank*, int index, uint8_t* small, float* tmpl, float* jacs);
 
 /* ---- A tracked frame handed to the resident map on the device ----------------------------------------------------------------------
  *      The opposite direction of the snapshot.  The reference's tracker writes into the map on every frame: CalcPoseUpdate bumps

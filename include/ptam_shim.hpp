@@ -699,6 +699,19 @@ public:
         se3CfromW.to12(&poses_[12 * (size_t)i]);
         check(ptam_sbi_bank_set_poses(h_, i, 1, &poses_[12 * (size_t)i]), "ptam_sbi_bank_set_poses");
     }
+    // Map::vpKeyFrames of the snapshot's current generation (MapSnapshot::EnableKeyFrames) becomes the bank, device to device: with
+    // a ResidentMap this replaces AddKeyFrame / SetKeyFramePose.  Call it beside MapTracker::TakeMap, once per frame: a generation the
+    // bank holds already costs one mutex hold.  AttemptRecovery's own table follows the take.
+    ptam_keyframes_take_result TakeKeyFrames(class MapSnapshot& snapshot);   // (defined behind MapSnapshot)
+    void Clear() {   // Tracker::Reset / a new map: AddKeyFrame works again after a take
+        check(ptam_sbi_bank_clear(h_), "ptam_sbi_bank_clear");
+        poses_.clear();
+    }
+    int KeyFrameCount() const {
+        int n = 0;
+        check(ptam_sbi_bank_count(h_, &n), "ptam_sbi_bank_count");
+        return n;
+    }
     SE3 KeyFramePose(int i) const {
         double p[12];
         check(ptam_sbi_bank_poses(h_, i, 1, p), "ptam_sbi_bank_poses");
@@ -773,11 +786,31 @@ public:
         check(ptam_map_snapshot_info(h_, &r), "ptam_map_snapshot_info");
         return r;
     }
+    // Every Publish also carries Map::vpKeyFrames as the relocaliser reads it — se3CfromW and pSBI (src/KeyFrame.cc:80-81) of every
+    // keyframe — for Relocaliser::TakeKeyFrames.  The publisher's thread, before the threads start or between two Publish calls.
+    void EnableKeyFrames(int nMaxKeyFrames, double dBlur = 2.5) {
+        check(ptam_snapshot_keyframes_enable(h_, nMaxKeyFrames, dBlur), "ptam_snapshot_keyframes_enable");
+    }
+    ptam_snapshot_keyframes_info_t KeyFrames() const {
+        ptam_snapshot_keyframes_info_t r{};
+        check(ptam_snapshot_keyframes_info(h_, &r), "ptam_snapshot_keyframes_info");
+        return r;
+    }
     ptam_map_snapshot* handle() const { return h_; }
 
 private:
     ptam_map_snapshot* h_ = nullptr;
 };
+
+inline ptam_keyframes_take_result Relocaliser::TakeKeyFrames(MapSnapshot& snapshot) {
+    ptam_keyframes_take_result r{};
+    check(ptam_sbi_bank_take_keyframes(h_, snapshot.handle(), &r), "ptam_sbi_bank_take_keyframes");
+    if (r.changed) {
+        poses_.resize(12 * (size_t)r.n_kf);
+        if (r.n_kf > 0) check(ptam_sbi_bank_poses(h_, 0, r.n_kf, poses_.data()), "ptam_sbi_bank_poses");
+    }
+    return r;
+}
 
 // One tracked frame for the mapmaker, in device memory (ptam_frame_report, ptam_hip.h): the found entries of the frame's iteration
 // set as records sorted by point serial.  MapTracker::ReportFrame fills it on the tracker's thread (one launch, one wait); the host

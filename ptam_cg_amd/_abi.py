@@ -272,6 +272,18 @@ class MapSnapshotInfo(C.Structure):
     _fields_ = [("generation", C.c_int64), ("map_id", C.c_int64), ("n_points", C.c_int32), ("pad_", C.c_int32)]
 
 
+class SnapshotKeyframesInfo(C.Structure):
+    """ptam_snapshot_keyframes_info_t"""
+    _fields_ = [("generation", C.c_int64), ("map_id", C.c_int64), ("epoch", C.c_int64), ("enabled", C.c_int32), ("max_keyframes", C.c_int32),
+                ("n_kf", C.c_int32), ("n_made", C.c_int32), ("sbi_w", C.c_int32), ("sbi_h", C.c_int32), ("blur", C.c_double)]
+
+
+class KeyframesTakeResult(C.Structure):
+    """ptam_keyframes_take_result"""
+    _fields_ = [("changed", C.c_int32), ("n_kf", C.c_int32), ("n_new", C.c_int32), ("link_bytes", C.c_int32), ("generation", C.c_int64),
+                ("map_id", C.c_int64)]
+
+
 class FrameRecord(C.Structure):
     """ptam_frame_record: one found entry of a tracked frame's iteration set, named by its point's serial"""
     _fields_ = [("serial", C.c_int64), ("level", C.c_int32), ("outlier", C.c_uint8), ("did_subpix", C.c_uint8), ("pad_", C.c_uint8 * 2),
@@ -515,6 +527,11 @@ PROTOTYPES = {
     "map_snapshot_reserve": (_i, [_vp, _i]),
     "map_snapshot_info": (_i, [_vp, C.POINTER(MapSnapshotInfo)]),
     "tracker_take_map": (_i, [_vp, _vp, C.POINTER(MapTakeResult)]),
+    "snapshot_keyframes_enable": (_i, [_vp, _i, _d]),
+    "snapshot_keyframes_info": (_i, [_vp, C.POINTER(SnapshotKeyframesInfo)]),
+    "sbi_bank_take_keyframes": (_i, [_vp, _vp, C.POINTER(KeyframesTakeResult)]),
+    "sbi_bank_clear": (_i, [_vp]),
+    "sbi_bank_read": (_i, [_vp, _i, _vp, _vp, _vp]),
     "tracker_point_serials": (_i, [_vp, _i, _i, _vp]),
     "tracker_read_iteration_serials": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "frame_report_create": (_i, [_vp, _i, _ppv]),

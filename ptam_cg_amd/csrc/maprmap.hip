@@ -15,7 +15,8 @@
 //                                   re-find (mr_run), the closest keyframe, the busy list from the resident measurement table
 //                                   (rm_busy_kernel), the epipolar chain of mapmaker.hip, and mt_add_points_core on the chain's output
 //   ptam_rmap_publish               the map as the tracker wants it into a ptam_map_snapshot's free slot (rm_publish_kernel): rows, patch
-//                                   sources resolved through a per-keyframe level record, serials; the hand-over is snapshot_slots.h
+//                                   sources resolved through a per-keyframe level record, serials; the hand-over is snapshot_slots.h;
+//                                   with a keyframe section in the snapshot also the pose table and the missing keyframe SBIs (sbi.hip)
 //   ptam_rmap_point_serials / resolve_serials   the serial column (one int64 per point, strictly increasing, given by rm_serials_kernel)
 //                                   and a binary search in it (rm_resolve_kernel)
 //   ptam_rmap_note_reports / insert_keyframe_report   the tracker's frame reports (framereport.hip) into the counts (rm_note_reports_kernel)
@@ -35,6 +36,7 @@
 #include "mapmaker_internal.h"    // EpiBusy, EpiRun, the epipolar chain
 #include "refind_internal.h"      // ptam_refinder
 #include "snapshot_internal.h"    // ptam_map_snapshot: ptam_rmap_publish fills its free slot
+#include "sbi.h"                  // the snapshot's keyframe section: ptam_rmap_publish fills it too
 #include "framereport_internal.h" // ptam_frame_report: ptam_rmap_note_reports, ptam_rmap_insert_keyframe_report
 
 namespace {
@@ -67,6 +69,7 @@ struct ptam_rmap {
     RmTable t[PTAM_RMAP_TABLES];
     RmTable serial;                    // the seventh point-side column: one int64 per point, strictly increasing; no table of download
     long long map_id, next_serial;     // process-wide | the next serial this handle gives out (never reused)
+    long long kf_epoch;                // successful uploads: keyframes are appended, or all replaced by an upload (ptam_snapshot_keyframes_enable)
     std::vector<const ptam_kf*> kfs;   // host only
     std::vector<double> h_poses;       // the mirror: K x 12
     std::vector<uint8_t> h_fixed;
@@ -582,6 +585,7 @@ int ptam_rmap_create(ptam_ctx* ctx, ptam_rmap** out) {
     static std::atomic<long long> map_ids{0};
     m->map_id = ++map_ids;
     m->next_serial = 1;
+    m->kf_epoch = 0;
     if (hipMalloc((void**)&m->d_words, RM_WORDS * sizeof(int)) != hipSuccess) {
         delete m;
         ptam_set_error("ptam_rmap_create: no device memory");
@@ -705,6 +709,7 @@ int ptam_rmap_upload(ptam_rmap* m, int n_kf, const ptam_kf* const* kfs, const do
     for (int w = 0; w < PTAM_RMAP_TABLES; w++) m->t[w].cur ^= 1;
     m->serial.cur ^= 1;
     m->next_serial += n_points;
+    m->kf_epoch++;
     for (int i = 0; i < RM_N_COUNTS; i++) m->n[i] = rows[i];
     m->kfs.assign((size_t)n_kf, nullptr);
     if (kfs) std::copy(kfs, kfs + n_kf, m->kfs.begin());
@@ -1307,8 +1312,12 @@ int ptam_rmap_publish(ptam_rmap* m, ptam_map_snapshot* snap, ptam_map_publish_re
             recs[(size_t)k].w[l] = m->kfs[(size_t)k]->L.w[l];
             recs[(size_t)k].h[l] = m->kfs[(size_t)k]->L.h[l];
         }
+    const bool with_kfs = sbi_snapshot_kf_enabled(snap);   // the keyframe section: poses, and the images the slot lacks
+    if (with_kfs)
+        if (int rc = sbi_snapshot_kf_check(snap, K, m->kfs.data())) return rc;
+    const size_t o_l3 = rm_up256((size_t)K * sizeof(RmKfRecord));
     void* sc;
-    if (int rc = ctx_scratch(m->ctx, rm_up256((size_t)K * sizeof(RmKfRecord)), &sc)) return rc;
+    if (int rc = ctx_scratch(m->ctx, o_l3 + rm_up256((size_t)K * sizeof(const uint8_t*)), &sc)) return rc;
     const int s = snap->slots.begin_write();
     if (s < 0) {
         ptam_set_error("ptam_rmap_publish: a publish into this snapshot is under way");
@@ -1319,6 +1328,14 @@ int ptam_rmap_publish(ptam_rmap* m, ptam_map_snapshot* snap, ptam_map_publish_re
     int grew = 0;
     int rc = snap_slot_room(snap, s, (size_t)std::max(N, 1), &grew);
     if (!rc) rc = rm_up(m, sc, recs.data(), (size_t)K * sizeof(RmKfRecord));
+    const int kf_first = with_kfs ? sbi_snapshot_kf_first_missing(snap, s, m->map_id, m->kf_epoch, K) : K;
+    std::vector<const uint8_t*> l3((size_t)(K - kf_first));   // (lives until the wait below)
+    if (!rc && with_kfs) {
+        for (int k = kf_first; k < K; k++) l3[(size_t)(k - kf_first)] = m->kfs[(size_t)k]->L.im[3];
+        const uint8_t** d_l3 = (const uint8_t**)((char*)sc + o_l3);
+        rc = rm_up(m, d_l3, l3.data(), l3.size() * sizeof(l3[0]));
+        if (!rc) rc = sbi_snapshot_kf_enqueue(m->ctx, snap, s, K, rm_now<double>(m, PTAM_RMAP_KF_POSES), kf_first, d_l3);
+    }
     if (!rc && N > 0) {
         SnapSlot& sl = snap->slot[s];
         hipLaunchKernelGGL(rm_publish_kernel, dim3(rm_blocks(N)), dim3(256), 0, m->ctx->stream, N,
@@ -1329,6 +1346,7 @@ int ptam_rmap_publish(ptam_rmap* m, ptam_map_snapshot* snap, ptam_map_publish_re
     if (!rc && ptam_stream_wait(m->ctx->stream) != hipSuccess) rc = PTAM_E_HIP;   // the call's one wait: the slot is whole
     if (rc) {
         if (rc == PTAM_E_HIP) ptam_set_error("ptam_rmap_publish: the gather failed: %s", hipGetErrorString(hipGetLastError()));
+        if (with_kfs) sbi_snapshot_kf_stamp(snap, s, 0, 0, 0, 0, 0);   // (its images may be half of one map, half of another)
         snap->slots.abort_write();
         return rc;
     }
@@ -1336,6 +1354,7 @@ int ptam_rmap_publish(ptam_rmap* m, ptam_map_snapshot* snap, ptam_map_publish_re
     sl.n = N;
     sl.map_id = m->map_id;
     sl.generation = snap->slots.next_generation();
+    if (with_kfs) sbi_snapshot_kf_stamp(snap, s, K, kf_first, m->map_id, m->kf_epoch, sl.generation);
     r.generation = snap->slots.commit_write();
     r.map_id = m->map_id;
     r.n_points = N;

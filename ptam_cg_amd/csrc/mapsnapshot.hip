@@ -56,7 +56,10 @@ int ptam_map_snapshot_create(ptam_ctx* ctx, int max_points, ptam_map_snapshot** 
 int ptam_map_snapshot_destroy(ptam_map_snapshot* s) {
     if (!s) return PTAM_OK;
     (void)hipSetDevice(s->device);
-    for (int k = 0; k < SnapSlots::SLOTS; k++) snap_slot_free(s->slot[k]);
+    for (int k = 0; k < SnapSlots::SLOTS; k++) {
+        snap_slot_free(s->slot[k]);
+        if (s->slot[k].kf_block) (void)hipFree(s->slot[k].kf_block);   // (the keyframe section, sbi.hip)
+    }
     delete s;
     return PTAM_OK;
 }

@@ -65,5 +65,18 @@ int sbi_reloc_launch_ssd(const ptam_sbi_bank* b, int n, int max_count, const Sbi
 // sbi_batch_launch_align with n_reloc relocaliser workgroups between the n_est estimator ones (n_est may be 0) and the detection's
 int sbi_recover_launch_align(ptam_ctx* ctx, const ptam_sbi_bank* b, int n_est, const SbiBatchRec* d_recs, int n_reloc, const SbiRelocRec* d_rrecs,
                              hipStream_t st, int nb_detect, const KfLevels* L, const void* det_items, size_t det_stride, size_t det_off);
+// ---- the keyframe section of a ptam_map_snapshot (ptam_snapshot_keyframes_enable), as ptam_rmap_publish fills it ----
+// Host only, before a slot is taken; all of them return at once for a snapshot that was never enabled.
+struct ptam_map_snapshot;
+bool sbi_snapshot_kf_enabled(ptam_map_snapshot* snap);
+// PTAM_E_LIMIT: n_kf above max_keyframes; PTAM_E_ARG: a keyframe whose level 3 is not the snapshot's frame size / 8
+int sbi_snapshot_kf_check(ptam_map_snapshot* snap, int n_kf, const ptam_kf* const* kfs);
+// the first keyframe of map (map_id, epoch) whose image slot s does not hold: the slot's count for the same map, else 0
+int sbi_snapshot_kf_first_missing(const ptam_map_snapshot* snap, int s, long long map_id, long long epoch, int n_kf);
+// on ctx's queue: the pose table [0, n_kf) device to device into slot s, and ONE make launch (grid x = n_kf - first) for the
+// entries [first, n_kf); d_l3: their level-3 addresses, in device memory
+int sbi_snapshot_kf_enqueue(ptam_ctx* ctx, ptam_map_snapshot* snap, int s, int n_kf, const double* d_poses, int first, const uint8_t* const* d_l3);
+// after the publish's wait, before its commit: what slot s now holds
+void sbi_snapshot_kf_stamp(ptam_map_snapshot* snap, int s, int n_kf, int first, long long map_id, long long epoch, long long generation);
 bool sbi_estimator_fits_bank(const ptam_rotation_estimator* e, const ptam_sbi_bank* b);   // same frame size
 bool sbi_estimators_alike(const ptam_rotation_estimator* a, const ptam_rotation_estimator* b);   // same image size and blur

@@ -9,6 +9,7 @@
 #include "keyframe_device.h"   // half4: the pyramid's halfSample
 #include "patch_device.h"      // nc_*: products and sums that are never contracted; cam_unproject
 #include "wait_mapped.h"
+#include "snapshot_internal.h"   // the keyframe section of a ptam_map_snapshot
 #include "motion_device.h"     // the prediction behind SE3fromSE2 (a batch's frames)
 
 #define SBI_THREADS 256
@@ -128,6 +129,33 @@ __global__ __launch_bounds__(SBI_THREADS) void sbi_ssd_batch_kernel(const SbiRel
         for (int i = 1; i < SBI_THREADS / 64; i++) s += s_part[i];
         r.ssd[blockIdx.x] = s;
     }
+}
+
+// ---- ptam_sbi_bank_take_keyframes ----
+// the take's device side in one launch: entries [first, n_kf) of the three image arrays (one thread per pixel: 1 + 4 + 8 bytes)
+// and the pose table [0, n_kf) (one thread per double), from a slot's section into a bank
+struct SbiTakeArgs {
+    const uint8_t* s_small;
+    const float* s_tmpl;
+    const float2* s_jacs;
+    const double* s_poses;
+    uint8_t* d_small;
+    float* d_tmpl;
+    float2* d_jacs;
+    double* d_poses;
+    long long px_first, px_count;   // the pixels [px_first, px_first + px_count) of the arrays
+    int n_pose;                     // 12 n_kf
+};
+__global__ __launch_bounds__(256) void sbi_take_kernel(SbiTakeArgs a) {
+    const long long stride = (long long)gridDim.x * 256;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    for (long long i = t; i < a.px_count; i += stride) {
+        const long long p = a.px_first + i;
+        a.d_small[p] = a.s_small[p];
+        a.d_tmpl[p] = a.s_tmpl[p];
+        a.d_jacs[p] = a.s_jacs[p];
+    }
+    for (long long i = t; i < a.n_pose; i += stride) a.d_poses[i] = a.s_poses[i];
 }
 
 // ---- align: IteratePosRelToTarget (:313-417) + SE3fromSE2 (:427-476) --------------------------------------------------------
@@ -554,6 +582,11 @@ struct ptam_sbi_bank {
     std::vector<double> h_poses;    // [capacity][12]
     std::vector<double> h_campos;   // [capacity][3]: the camera positions -R^T t of the mirror (the closest-keyframe walk reads these)
     std::vector<char> pose_set;     // [capacity]
+    // where the entries came from.  blur: of the first entry made since the bank was empty (0: empty).  taken: the entries are a
+    // snapshot's keyframes [0, count) of map (map_id, epoch), last taken at (snap_uid, snap_generation) — ptam_sbi_bank_take_keyframes
+    double blur;
+    int taken;
+    long long snap_uid, snap_generation, map_id, epoch;
 };
 struct ptam_rotation_estimator {
     ptam_ctx* ctx;
@@ -668,6 +701,7 @@ void sbi_preload_kernels() {
     ptam_preload((const void*)sbi_ssd_kernel);
     ptam_preload((const void*)sbi_ssd_batch_kernel);
     ptam_preload((const void*)sbi_align_kernel);
+    ptam_preload((const void*)sbi_take_kernel);
 }
 
 int sbi_estimator_step(ptam_rotation_estimator* e, const ptam_kf* kf, ptam_sbi_alignment* out) {
@@ -796,6 +830,66 @@ bool sbi_estimator_fits_bank(const ptam_rotation_estimator* e, const ptam_sbi_ba
     return e->slot[0]->g.fw == b->g.fw && e->slot[0]->g.fh == b->g.fh;
 }
 
+// ---- the map's keyframes through a ptam_map_snapshot: the slots' keyframe sections and the bank's take ----
+// A slot's section is a bank's block (sbi_alloc) with the pose table behind it; sbi_geom of the snapshot's frame size gives the
+// image size, so a slot's entry i and a bank's entry i lie at the same offsets.
+static bool sbi_snapshot_kf_state(ptam_map_snapshot* snap, int* kf_max, double* blur, bool* writing) {
+    std::lock_guard<std::mutex> lk(snap->slots.mu);   // (enable writes the two under the same mutex)
+    if (kf_max) *kf_max = snap->kf_max;
+    if (blur) *blur = snap->kf_blur;
+    if (writing) *writing = snap->slots.writing != SnapSlots::NEVER;
+    return snap->kf_max > 0;
+}
+bool sbi_snapshot_kf_enabled(ptam_map_snapshot* snap) { return sbi_snapshot_kf_state(snap, nullptr, nullptr, nullptr); }
+
+int sbi_snapshot_kf_check(ptam_map_snapshot* snap, int n_kf, const ptam_kf* const* kfs) {
+    int kf_max = 0;
+    if (!sbi_snapshot_kf_state(snap, &kf_max, nullptr, nullptr)) return PTAM_OK;
+    if (n_kf > kf_max) {
+        ptam_set_error("ptam_rmap_publish: the map has %d keyframes, the snapshot's keyframe section room for %d", n_kf, kf_max);
+        return PTAM_E_LIMIT;
+    }
+    SbiGeom g;
+    if (int rc = sbi_geom(snap->width, snap->height, &g)) return rc;
+    for (int k = 0; k < n_kf; k++) ARG_TRY(kfs[k] && kfs[k]->L.w[3] == g.w3 && kfs[k]->L.h[3] == g.h3);
+    return PTAM_OK;
+}
+
+int sbi_snapshot_kf_first_missing(const ptam_map_snapshot* snap, int s, long long map_id, long long epoch, int n_kf) {
+    const SnapSlot& sl = snap->slot[s];
+    return sl.kf_map_id == map_id && sl.kf_epoch == epoch ? std::min(sl.kf_n, n_kf) : 0;
+}
+
+int sbi_snapshot_kf_enqueue(ptam_ctx* ctx, ptam_map_snapshot* snap, int s, int n_kf, const double* d_poses, int first, const uint8_t* const* d_l3) {
+    SnapSlot& sl = snap->slot[s];
+    SbiGeom g;
+    if (int rc = sbi_geom(snap->width, snap->height, &g)) return rc;
+    if (n_kf > 0) HIP_TRY(hipMemcpyAsync(sl.kf_poses, d_poses, (size_t)n_kf * 96, hipMemcpyDeviceToDevice, ctx->stream));
+    if (n_kf > first) {
+        const size_t px = (size_t)g.w * g.h, i = (size_t)first;
+        const SbiImage im = {sl.kf_small + i * px, sl.kf_tmpl + i * px, sl.kf_jacs + i * 2 * px};
+        if (int rc = sbi_launch_make(ctx, g, nullptr, snap->kf_blur, im, n_kf - first, d_l3)) return rc;
+    }
+    return PTAM_OK;
+}
+
+void sbi_snapshot_kf_stamp(ptam_map_snapshot* snap, int s, int n_kf, int first, long long map_id, long long epoch, long long generation) {
+    SnapSlot& sl = snap->slot[s];
+    sl.kf_n = n_kf;
+    sl.kf_made = n_kf - first;
+    sl.kf_map_id = map_id;
+    sl.kf_epoch = epoch;
+    sl.kf_generation = generation;
+}
+
+static int sbi_bank_not_taken(const ptam_sbi_bank* b) {
+    if (b->taken) {
+        ptam_set_error("the bank's entries are a snapshot's keyframes (ptam_sbi_bank_take_keyframes): ptam_sbi_bank_clear before adding by hand");
+        return PTAM_E_STATE;
+    }
+    return PTAM_OK;
+}
+
 extern "C" {
 
 int ptam_sbi_create(ptam_ctx* ctx, int frame_w, int frame_h, ptam_sbi** out) {
@@ -873,6 +967,8 @@ int ptam_sbi_bank_create(ptam_ctx* ctx, int frame_w, int frame_h, int capacity, 
     HIP_TRY(hipSetDevice(ctx->device));
     ptam_sbi_bank* b = new ptam_sbi_bank();
     b->ctx = ctx, b->g = g, b->capacity = capacity, b->count = 0;
+    b->blur = 0.0, b->taken = 0;
+    b->snap_uid = b->snap_generation = b->map_id = b->epoch = 0;
     void* x;
     if (int rc = sbi_alloc(g, capacity, (size_t)capacity * (16 + 96), &b->block, &b->im, &x)) {
         delete b;
@@ -899,6 +995,7 @@ int ptam_sbi_bank_destroy(ptam_sbi_bank* b) {
 
 int ptam_sbi_bank_add(ptam_sbi_bank* b, const ptam_kf* kf, double blur, int* index) {
     ARG_TRY(b && kf);
+    if (int rc = sbi_bank_not_taken(b)) return rc;
     if (b->count >= b->capacity) {
         ptam_set_error("the SmallBlurryImage bank is full (%d entries)", b->capacity);
         return PTAM_E_LIMIT;
@@ -908,12 +1005,14 @@ int ptam_sbi_bank_add(ptam_sbi_bank* b, const ptam_kf* kf, double blur, int* ind
     const SbiImage im = {b->im.small + i * n, b->im.tmpl + i * n, b->im.jacs + i * 2 * n};
     if (int rc = sbi_launch_make(b->ctx, b->g, kf, blur, im)) return rc;
     if (index) *index = b->count;
+    if (b->count == 0) b->blur = blur;
     b->count++;
     return PTAM_OK;
 }
 
 int ptam_sbi_bank_add_batch(ptam_sbi_bank* b, int n, const ptam_kf* const* kfs, double blur, int* first_index) {
     ARG_TRY(b && kfs && n >= 1);
+    if (int rc = sbi_bank_not_taken(b)) return rc;
     if (n > b->capacity - b->count) {
         ptam_set_error("the SmallBlurryImage bank has room for %d more entries, not %d", b->capacity - b->count, n);
         return PTAM_E_LIMIT;
@@ -930,6 +1029,7 @@ int ptam_sbi_bank_add_batch(ptam_sbi_bank* b, int n, const ptam_kf* const* kfs, 
     const SbiImage im = {b->im.small + i * px, b->im.tmpl + i * px, b->im.jacs + i * 2 * px};
     if (int rc = sbi_launch_make(b->ctx, b->g, nullptr, blur, im, n, b->l3_list + b->count)) return rc;
     if (first_index) *first_index = b->count;
+    if (b->count == 0) b->blur = blur;
     b->count += n;
     return PTAM_OK;
 }
@@ -968,6 +1068,185 @@ int ptam_sbi_bank_poses(const ptam_sbi_bank* b, int first, int n, double* poses_
             return PTAM_E_STATE;
         }
     std::memcpy(poses_out12, b->h_poses.data() + (size_t)first * 12, (size_t)n * 96);
+    return PTAM_OK;
+}
+
+int ptam_sbi_bank_read(ptam_sbi_bank* b, int index, uint8_t* small, float* tmpl, float* jacs) {
+    ARG_TRY(b && index >= 0 && index < b->count);
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    const size_t n = (size_t)b->g.w * b->g.h, i = (size_t)index;
+    hipStream_t st = b->ctx->stream;
+    if (small) HIP_TRY(hipMemcpyAsync(small, b->im.small + i * n, n, hipMemcpyDeviceToHost, st));
+    if (tmpl) HIP_TRY(hipMemcpyAsync(tmpl, b->im.tmpl + i * n, n * 4, hipMemcpyDeviceToHost, st));
+    if (jacs) HIP_TRY(hipMemcpyAsync(jacs, b->im.jacs + i * 2 * n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ptam_stream_wait(st));
+    return PTAM_OK;
+}
+
+int ptam_sbi_bank_clear(ptam_sbi_bank* b) {
+    ARG_TRY(b);
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    HIP_TRY(ptam_stream_wait(b->ctx->stream));   // (a pending copy from the mirror, a launch that reads the entries)
+    b->count = 0;
+    b->blur = 0.0, b->taken = 0;
+    b->snap_uid = b->snap_generation = b->map_id = b->epoch = 0;
+    std::fill(b->pose_set.begin(), b->pose_set.end(), 0);
+    return PTAM_OK;
+}
+
+int ptam_snapshot_keyframes_enable(ptam_map_snapshot* snap, int max_keyframes, double blur) {
+    ARG_TRY(snap && max_keyframes >= 1 && max_keyframes <= 65535 && blur > 0.0 && blur <= 5.0);
+    SbiGeom g;
+    if (int rc = sbi_geom(snap->width, snap->height, &g)) return rc;
+    bool writing = false;
+    if (sbi_snapshot_kf_state(snap, nullptr, nullptr, &writing)) {
+        ptam_set_error("ptam_snapshot_keyframes_enable: the snapshot's keyframe section is enabled already");
+        return PTAM_E_STATE;
+    }
+    if (writing) {
+        ptam_set_error("ptam_snapshot_keyframes_enable: a publish into this snapshot is under way");
+        return PTAM_E_STATE;
+    }
+    HIP_TRY(hipSetDevice(snap->device));
+    int rc = PTAM_OK;
+    for (int k = 0; k < SnapSlots::SLOTS && !rc; k++) {
+        SnapSlot& sl = snap->slot[k];
+        SbiImage im;
+        void* x;
+        rc = sbi_alloc(g, max_keyframes, (size_t)max_keyframes * 96, &sl.kf_block, &im, &x);
+        if (rc) break;
+        sl.kf_small = im.small, sl.kf_tmpl = im.tmpl, sl.kf_jacs = im.jacs;
+        sl.kf_poses = (double*)x;
+        sl.kf_n = sl.kf_made = 0;
+        sl.kf_map_id = sl.kf_epoch = sl.kf_generation = 0;
+    }
+    if (rc) {
+        for (int k = 0; k < SnapSlots::SLOTS; k++) {
+            if (snap->slot[k].kf_block) (void)hipFree(snap->slot[k].kf_block);
+            snap->slot[k].kf_block = nullptr;
+        }
+        return rc;
+    }
+    std::lock_guard<std::mutex> lk(snap->slots.mu);
+    snap->kf_max = max_keyframes;
+    snap->kf_blur = blur;
+    return PTAM_OK;
+}
+
+int ptam_snapshot_keyframes_info(ptam_map_snapshot* snap, ptam_snapshot_keyframes_info_t* out) {
+    ARG_TRY(snap && out);
+    ptam_snapshot_keyframes_info_t r = {};
+    int kf_max = 0;
+    double blur = 0.0;
+    if (sbi_snapshot_kf_state(snap, &kf_max, &blur, nullptr)) {
+        SbiGeom g;
+        if (int rc = sbi_geom(snap->width, snap->height, &g)) return rc;
+        r.enabled = 1;
+        r.max_keyframes = kf_max;
+        r.blur = blur;
+        r.sbi_w = g.w, r.sbi_h = g.h;
+        long long gen = 0;
+        const int k = snap->slots.begin_read(-1, &gen);   // (-1 is no generation: the current slot, held while it is read)
+        if (k >= 0) {
+            const SnapSlot& sl = snap->slot[k];
+            r.generation = sl.generation;
+            if (sl.kf_generation == sl.generation) {
+                r.map_id = sl.kf_map_id;
+                r.epoch = sl.kf_epoch;
+                r.n_kf = sl.kf_n;
+                r.n_made = sl.kf_made;
+            }
+            snap->slots.end_read(k);
+        }
+    }
+    *out = r;
+    return PTAM_OK;
+}
+
+int ptam_sbi_bank_take_keyframes(ptam_sbi_bank* b, ptam_map_snapshot* snap, ptam_keyframes_take_result* res) {
+    ARG_TRY(b && snap && res);
+    double blur = 0.0;
+    if (!sbi_snapshot_kf_state(snap, nullptr, &blur, nullptr)) {
+        ptam_set_error("ptam_sbi_bank_take_keyframes: the snapshot's keyframe section is not enabled (ptam_snapshot_keyframes_enable)");
+        return PTAM_E_STATE;
+    }
+    ARG_TRY(snap->device == b->ctx->device);
+    ARG_TRY(snap->width == b->g.fw && snap->height == b->g.fh);
+    if (b->count > 0 && !b->taken && b->blur != blur) {
+        ptam_set_error("bad argument: ptam_sbi_bank_take_keyframes: the bank's entries were added with blur %g, the snapshot's are made with %g", b->blur,
+                       blur);
+        return PTAM_E_ARG;
+    }
+    ptam_keyframes_take_result r = {};
+    long long gen = 0;
+    const int k = snap->slots.begin_read(b->taken && b->snap_uid == snap->uid ? b->snap_generation : -1, &gen);
+    if (k == SnapSlots::NEVER) {
+        ptam_set_error("bad argument: ptam_sbi_bank_take_keyframes: nothing has been published into the snapshot");
+        return PTAM_E_ARG;
+    }
+    if (k == SnapSlots::UNCHANGED) {   // the per-frame poll
+        r.n_kf = b->count;
+        r.generation = gen;
+        r.map_id = b->map_id;
+        *res = r;
+        return PTAM_OK;
+    }
+    const SnapSlot& sl = snap->slot[k];   // ours until end_read: the publisher leaves it alone
+    const int n = sl.kf_n;
+    const long long map_id = sl.kf_map_id, epoch = sl.kf_epoch, generation = sl.generation;
+    if (sl.kf_generation != sl.generation) {
+        snap->slots.end_read(k);
+        ptam_set_error("bad argument: ptam_sbi_bank_take_keyframes: nothing has been published into the snapshot since its keyframe section was enabled");
+        return PTAM_E_ARG;
+    }
+    if (n > b->capacity) {
+        snap->slots.end_read(k);
+        ptam_set_error("ptam_sbi_bank_take_keyframes: the snapshot holds %d keyframes, the bank %d at most", n, b->capacity);
+        return PTAM_E_LIMIT;
+    }
+    // a keyframe's image never changes: the entries the bank holds of this map stay, the others are copied
+    const int first = b->taken && b->snap_uid == snap->uid && b->map_id == map_id && b->epoch == epoch && b->count <= n ? b->count : 0;
+    const size_t px = (size_t)b->g.w * b->g.h;
+    hipStream_t st = b->ctx->stream;
+    int rc = hipSetDevice(b->ctx->device) == hipSuccess ? PTAM_OK : PTAM_E_HIP;
+    // (the mirror may be the source of a pending ptam_sbi_bank_set_poses copy: as there, it is waited for before it is overwritten)
+    if (!rc && ptam_stream_wait(st) != hipSuccess) rc = PTAM_E_HIP;
+    if (!rc && n > 0) {
+        SbiTakeArgs a;
+        a.s_small = sl.kf_small, a.s_tmpl = sl.kf_tmpl, a.s_jacs = (const float2*)sl.kf_jacs, a.s_poses = sl.kf_poses;
+        a.d_small = b->im.small, a.d_tmpl = b->im.tmpl, a.d_jacs = (float2*)b->im.jacs, a.d_poses = b->d_poses;
+        a.px_first = (long long)(first * px);
+        a.px_count = (long long)((size_t)(n - first) * px);
+        a.n_pose = 12 * n;
+        const long long threads = std::max(a.px_count, (long long)a.n_pose);
+        hipLaunchKernelGGL(sbi_take_kernel, dim3((unsigned)std::min((threads + 255) / 256, 4096ll)), dim3(256), 0, st, a);
+        if (hipGetLastError() != hipSuccess) rc = PTAM_E_HIP;
+        if (!rc && hipMemcpyAsync(b->h_poses.data(), sl.kf_poses, (size_t)n * 96, hipMemcpyDeviceToHost, st) != hipSuccess) rc = PTAM_E_HIP;
+        if (!rc && ptam_stream_wait(st) != hipSuccess) rc = PTAM_E_HIP;   // the call's one wait: the slot has been read
+    }
+    snap->slots.end_read(k);
+    if (rc) {
+        ptam_set_error("ptam_sbi_bank_take_keyframes: the copy failed: %s", hipGetErrorString(hipGetLastError()));
+        return rc;
+    }
+    for (int i = 0; i < n; i++) {
+        b->pose_set[(size_t)i] = 1;
+        const double* p = b->h_poses.data() + (size_t)i * 12;   // se3CfromW.inverse().get_translation(), src/MapMaker.cc:698
+        for (int j = 0; j < 3; j++) b->h_campos[(size_t)i * 3 + j] = -(p[j] * p[9] + p[3 + j] * p[10] + p[6 + j] * p[11]);
+    }
+    for (int i = n; i < b->capacity; i++) b->pose_set[(size_t)i] = 0;
+    b->count = n;
+    b->blur = blur;
+    b->taken = 1;
+    b->snap_uid = snap->uid, b->snap_generation = generation;
+    b->map_id = map_id, b->epoch = epoch;
+    r.changed = 1;
+    r.n_kf = n;
+    r.n_new = n - first;
+    r.link_bytes = 96 * n;
+    r.generation = generation;
+    r.map_id = map_id;
+    *res = r;
     return PTAM_OK;
 }
 

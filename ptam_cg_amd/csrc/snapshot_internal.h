@@ -14,6 +14,16 @@ struct SnapSlot {
     // what the slot holds: written by the publisher before its commit, read by a take after begin_read
     int n = 0;
     long long map_id = 0, generation = 0;
+    // the keyframe section (ptam_snapshot_keyframes_enable; sbi.hip owns it): the poses and the SmallBlurryImages of keyframes
+    // [0, kf_n) of map (kf_map_id, kf_epoch), in the layout of a ptam_sbi_bank.  The images outlive a generation: a publish of the
+    // same map makes only the entries from kf_n on.  kf_generation == generation: the section belongs to what the slot holds.
+    void* kf_block = nullptr;
+    uint8_t* kf_small = nullptr;
+    float* kf_tmpl = nullptr;
+    float* kf_jacs = nullptr;
+    double* kf_poses = nullptr;
+    int kf_n = 0, kf_made = 0;   // kf_made: the entries the slot's last publish made
+    long long kf_map_id = 0, kf_epoch = 0, kf_generation = 0;
 };
 
 struct ptam_map_snapshot {
@@ -22,6 +32,8 @@ struct ptam_map_snapshot {
     size_t want;                 // the capacity ptam_map_snapshot_reserve asked for
     SnapSlots slots;
     SnapSlot slot[SnapSlots::SLOTS];
+    int kf_max = 0;              // 0: the keyframe section is not enabled
+    double kf_blur = 0.0;
 };
 
 // slot s holds at least `rows` points (at least snap->want, or double what it held): the caller owns the slot — it is the

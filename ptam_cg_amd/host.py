@@ -1211,6 +1211,18 @@ class MapSnapshot:
         self._check(self.lib.map_snapshot_info(self.h, C.byref(r)), "map_snapshot_info")
         return dict(generation=r.generation, map_id=r.map_id, n_points=r.n_points)
 
+    def enable_keyframes(self, max_keyframes, blur=2.5, check=True):
+        """ptam_snapshot_keyframes_enable: every publish also carries the keyframes' poses and SmallBlurryImages, for
+        Relocaliser.take_keyframes; the publisher's thread, between publishes.  check=False: -> the status of a refused call."""
+        rc = self.lib.snapshot_keyframes_enable(self.h, int(max_keyframes), float(blur))
+        return self._check(rc, "snapshot_keyframes_enable") if check else rc
+
+    def keyframes(self):
+        """ptam_snapshot_keyframes_info -> dict(generation, map_id, epoch, enabled, max_keyframes, n_kf, n_made, sbi_w, sbi_h, blur)"""
+        r = _abi.SnapshotKeyframesInfo()
+        self._check(self.lib.snapshot_keyframes_info(self.h, C.byref(r)), "snapshot_keyframes_info")
+        return _counts(r)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.map_snapshot_destroy(self.h)
@@ -1584,6 +1596,32 @@ class Relocaliser:
         n = C.c_int()
         self.ctx._check(self.lib.sbi_bank_count(self.h, C.byref(n)), "sbi_bank_count")
         return n.value
+
+    def take_keyframes(self, snapshot, check=True):
+        """ptam_sbi_bank_take_keyframes: the keyframes of the snapshot's current generation become the bank's entries, device to
+        device; the poses also come down into the bank's mirror, and AttemptRecovery's host table follows -> dict(changed, n_kf,
+        n_new, link_bytes, generation, map_id); changed == 0 is the per-frame poll.  check=False: -> the status of a refused call."""
+        res = _abi.KeyframesTakeResult()
+        rc = self.lib.sbi_bank_take_keyframes(self.h, snapshot.h, C.byref(res))
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "sbi_bank_take_keyframes")
+        if res.changed:
+            self._keep = [snapshot]
+            self.poses = list(self.bank_poses(0, res.n_kf)) if res.n_kf else []
+        return _counts(res)
+
+    def clear(self):
+        """ptam_sbi_bank_clear (Tracker::Reset / a new map): no entries, and add / add_batch work again after a take"""
+        self.ctx._check(self.lib.sbi_bank_clear(self.h), "sbi_bank_clear")
+        self.poses = []
+
+    def read(self, index):
+        """ptam_sbi_bank_read: entry `index` -> dict(small (h, w) u8, tmpl (h, w) f32, jacs (h, w, 2) f32)"""
+        w, h = self.scratch.size
+        small, tmpl, jacs = np.zeros((h, w), np.uint8), np.zeros((h, w), np.float32), np.zeros((h, w, 2), np.float32)
+        self.ctx._check(self.lib.sbi_bank_read(self.h, int(index), _ptr(small), _ptr(tmpl), _ptr(jacs)), "sbi_bank_read")
+        return dict(small=small, tmpl=tmpl, jacs=jacs)
 
     def AttemptRecovery(self, kf, blur=2.5, max_score=9e6):
         """-> dict(best, good, best_ssd, pose (12,), ssd (count,), align)"""
