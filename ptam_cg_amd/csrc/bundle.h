@@ -24,6 +24,7 @@
 #include <cstddef>
 
 #include "common.h"
+#include "map_stage.h"   // Carver
 
 enum { MS_ALIVE = 0, MS_BAD = 1, MS_DEAD = 2 };
 
@@ -199,21 +200,6 @@ __host__ __device__ __forceinline__ const int& ms_cam(const char* base, size_t i
 __host__ __device__ __forceinline__ const int& ms_pt(const char* base, size_t i) { return ((const int*)(ms_chunk(base, i) + (size_t)MS_CH * 4))[i & (MS_CH - 1)]; }
 __host__ __device__ __forceinline__ const double2& ms_found(const char* base, size_t i) { return ((const double2*)(ms_chunk(base, i) + (size_t)MS_CH * 8))[i & (MS_CH - 1)]; }
 __host__ __device__ __forceinline__ const double& ms_sig(const char* base, size_t i) { return ((const double*)(ms_chunk(base, i) + (size_t)MS_CH * 24))[i & (MS_CH - 1)]; }
-
-// carves one allocation into 256-byte aligned pieces: take() returns the piece's offset, `off` ends as the size of the whole.
-// piece<T>(count) returns the piece itself, so that a layout names each piece once: it is a function of a Carver that is run twice,
-// first without a base for the size of the whole (the pointers it hands out then mean nothing), then with the block's address.
-struct Carver {
-    char* base = nullptr;
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-    template <class T>
-    T* piece(size_t count) { return (T*)((uintptr_t)base + take(count * sizeof(T))); }
-};
 
 // bundle.hip: a bundle whose inputs the caller's kernels write on the device (mapba.hip, ptam_map_bundle_adjust).
 //   ba_dev_meas_chunks  device MeasStore chunks for up to n_max measurements (fill them in the layout above)

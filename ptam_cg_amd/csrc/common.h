@@ -103,13 +103,9 @@ void maprefind_preload_kernels();
 void maptables_preload_kernels();
 void sbi_preload_kernels();
 void maprmap_preload_kernels();
+void maprmap_keyframe_preload_kernels();
+void maprmap_publish_preload_kernels();
 void framereport_preload_kernels();
-// ptam_map_scene_depth behind its upload (mapalign.hip): tables in device memory, n_kf > 0, out on the host; one launch, one wait
-int map_scene_depth_core(ptam_ctx* ctx, int n_kf, const double* d_poses, const double* d_points3, int n_meas, const ptam_map_meas* d_meas,
-                         ptam_scene_depth* out);
-// ptam_map_apply_global_transform's launch on device tables (mapalign.hip): enqueues only
-int map_transform_core(ptam_ctx* ctx, const double se3_new_from_old[12], int K, const double* d_poses, double* d_poses_new, int N,
-                       double* d_points3, const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride);
 int pose_hazards_read_pose(hipStream_t st, unsigned long long* out);
 int pose_hazards_read_trackmap(hipStream_t st, unsigned long long* out);
 int ctx_scratch(ptam_ctx* ctx, size_t bytes, void** out);     // device scratch >= bytes

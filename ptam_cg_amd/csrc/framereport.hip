@@ -115,7 +115,6 @@ __global__ void __launch_bounds__(FR_TILE) fr_fill_kernel(const FrJob* __restric
     }
 }
 
-inline size_t fr_up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }   // namespace
 
@@ -197,30 +196,33 @@ int ptam_frame_report_from_host(ptam_frame_report* r, int64_t map_id, int n_poin
         if (entries[s].found) ARG_TRY(entries[s].point >= 0 && entries[s].point < n_points && entries[s].level >= 0 && entries[s].level < PTAM_LEVELS);
     ptam_ctx* ctx = r->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     if (int rc = fr_mark_room(r, n_points)) return rc;
-    const size_t b_ser = fr_up256((size_t)n_points * sizeof(long long)), b_ent = fr_up256((size_t)n_entries * sizeof(ptam_trackmap_meas)),
-                 b_job = fr_up256(sizeof(FrJob));
-    void *sc, *hp;
-    if (int rc = ctx_scratch(ctx, b_ser + b_ent + b_job + 256, &sc)) return rc;
-    if (int rc = ctx_pinned(ctx, 256, &hp)) return rc;
-    char* b = (char*)sc;
+    long long* d_serials;
+    ptam_trackmap_meas* d_entries;
+    FrJob* d_job;
+    int *d_head, *h;
+    MapStage s(ctx);
+    STAGE_TRY(s.carve([&](Carver& c, Carver& pin) {
+        d_serials = c.piece<long long>((size_t)n_points);
+        d_entries = c.piece<ptam_trackmap_meas>((size_t)n_entries);   // (non-null also for an empty set: the host's form)
+        d_job = c.piece<FrJob>(1);
+        d_head = c.piece<int>(FR_HEAD_WORDS);
+        h = pin.piece<int>(FR_HEAD_WORDS);
+    }));
     FrJob j = {};
     j.n_points = n_points;
-    j.serials = (const long long*)b;
-    j.entries = (const ptam_trackmap_meas*)(b + b_ser);   // (non-null also for an empty set: the host's form)
+    j.serials = d_serials;
+    j.entries = d_entries;
     j.n_entries = n_entries;
     j.mark = r->mark;
     j.rec = r->rec;
     j.max_records = r->max_records;
-    if (n_points > 0) HIP_TRY(hipMemcpyAsync(b, point_serials, (size_t)n_points * sizeof(long long), hipMemcpyHostToDevice, st));
-    if (n_entries > 0) HIP_TRY(hipMemcpyAsync(b + b_ser, entries, (size_t)n_entries * sizeof(ptam_trackmap_meas), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b + b_ser + b_ent, &j, sizeof j, hipMemcpyHostToDevice, st));
-    int* d_head = (int*)(b + b_ser + b_ent + b_job);
-    if (int rc = fr_fill_core(st, 1, (const FrJob*)(b + b_ser + b_ent), d_head)) return rc;
-    HIP_TRY(hipMemcpyAsync(hp, d_head, FR_HEAD_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ptam_stream_wait(st));
-    const int* h = (const int*)hp;
+    STAGE_TRY(s.up(d_serials, point_serials, (size_t)n_points * sizeof(long long)));
+    STAGE_TRY(s.up(d_entries, entries, (size_t)n_entries * sizeof(ptam_trackmap_meas)));
+    STAGE_TRY(s.up(d_job, &j, sizeof j));
+    STAGE_TRY(fr_fill_core(s.st, 1, d_job, d_head));
+    STAGE_TRY(s.down(h, d_head, FR_HEAD_WORDS * sizeof(int)));
+    HIP_TRY(ptam_stream_wait(s.st));
     r->info = ptam_frame_report_info_t{};
     if (h[FR_H_RECORDS] > r->max_records) {
         ptam_set_error("bad argument: ptam_frame_report_from_host: %d found points, the report holds %d records", h[FR_H_RECORDS], r->max_records);

@@ -3,7 +3,7 @@
 // maptables_internal.h: a front says where one frame's iteration set lies (FrJob, every pointer a device pointer) and uploads the
 // job table; the core fr_fill_core only enqueues.
 #pragma once
-#include "common.h"
+#include "map_stage.h"
 
 struct ptam_frame_report {
     ptam_ctx* ctx;

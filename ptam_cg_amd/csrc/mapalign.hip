@@ -19,7 +19,8 @@
 // includes): the sums feed comparisons — a squared distance with zero, a distance with max_dist, one score with another.
 #include <cfloat>
 
-#include "common.h"
+#include "map_stage.h"
+#include "map_tables_check.h"
 
 #pragma clang fp contract(off)
 
@@ -403,8 +404,6 @@ __global__ void __launch_bounds__(ALIGN_THREADS) scene_depth_kernel(DepthArgs a)
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static inline uint64_t splitmix64_next(uint64_t& state) {
     uint64_t z = (state += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -447,43 +446,47 @@ static int align_run(ptam_ctx* ctx, const ptam_plane_opts* o, const double* se3_
                      const ptam_map_point_source* src, ptam_pvs_point* pvs, double se3_out[12], ptam_plane_info* info, uint8_t* inlier_out) {
     const int trials = o ? o->trials : 0;
     const size_t Kz = K > 0 ? K : 1, Nz = N > 0 ? N : 1, Tz = trials > 0 ? trials : 1;
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        const size_t at = off;
-        off += up256(b);
-        return at;
-    };
-    const size_t o_samples = take(Tz * 3 * sizeof(int32_t)), o_pts = take(Nz * 24), o_scores = take(Tz * 8), o_skip = take(Tz * 4),
-                 o_out = take(256 + Nz), o_pose = take(Kz * 96), o_pose_new = take(Kz * 96), o_src = take(Nz * sizeof(ptam_map_point_source)),
-                 o_pvs = take(Nz * sizeof(ptam_pvs_point));
-    void *s, *hp;
-    if (int rc = ctx_scratch(ctx, off, &s)) return rc;
-    const size_t pin_out = up256(Tz * 3 * sizeof(int32_t)), pin_pose = pin_out + 256, pin_pts = pin_pose + up256(Kz * 96),
-                 pin_pvs = pin_pts + up256(Nz * 24), pin_total = pin_pvs + (apply && src ? Nz * sizeof(ptam_pvs_point) : 0);
-    if (int rc = ctx_pinned(ctx, apply ? pin_total : pin_pose, &hp)) return rc;
-    char* d = (char*)s;
-    hipStream_t st = ctx->stream;
-    PlaneOut* h_out = (PlaneOut*)((char*)hp + pin_out);
     PlaneArgs g;
+    ApplyArgs a;
+    int32_t *d_samples, *h_samples;
+    double *d_pts, *d_pose, *d_pose_new;
+    ptam_map_point_source* d_src;
+    ptam_pvs_point* d_pvs;
+    PlaneOut* h_out;
+    char *t_pose = nullptr, *t_pts = nullptr, *t_pvs = nullptr;   // where the tables come down, in the pinned staging
+    MapStage stage(ctx);
+    STAGE_TRY(stage.carve([&](Carver& c, Carver& pin) {
+        g.samples = d_samples = c.piece<int32_t>(Tz * 3);
+        g.pts = d_pts = c.piece<double>(Nz * 3);
+        g.scores = c.piece<double>(Tz);
+        g.skipped = c.piece<int>(Tz);
+        g.out = (PlaneOut*)c.piece<char>(256 + Nz);
+        d_pose = c.piece<double>(Kz * 12);
+        d_pose_new = c.piece<double>(Kz * 12);
+        d_src = c.piece<ptam_map_point_source>(Nz);
+        d_pvs = c.piece<ptam_pvs_point>(Nz);
+        h_samples = pin.piece<int32_t>(Tz * 3);
+        h_out = (PlaneOut*)pin.piece<char>(256);
+        if (apply) {
+            t_pose = pin.piece<char>(Kz * 96);
+            t_pts = pin.piece<char>(Nz * 24);
+            t_pvs = pin.piece<char>(src ? Nz * sizeof(ptam_pvs_point) : 0);
+        }
+    }));
+    hipStream_t st = stage.st;
     g.n = N;
     g.trials = trials;
     g.max_dist = o ? o->max_dist : 0.0;
-    g.pts = (const double*)(d + o_pts);
-    g.samples = (const int32_t*)(d + o_samples);
-    g.scores = (double*)(d + o_scores);
-    g.skipped = (int*)(d + o_skip);
-    g.out = (PlaneOut*)(d + o_out);
-    g.flags = (uint8_t*)(d + o_out + 256);
-    g.h_out = (PlaneOut*)((char*)ctx->d_pinned + pin_out);
-    if (N > 0) HIP_TRY(hipMemcpyAsync(d + o_pts, pts, (size_t)N * 24, hipMemcpyHostToDevice, st));
+    g.flags = (uint8_t*)g.out + 256;
+    g.h_out = stage.pin_dev(h_out);
+    STAGE_TRY(stage.up(d_pts, pts, (size_t)N * 24));
     if (o) {
         if (N >= 10) {
-            int32_t* h_samples = (int32_t*)hp;
             if (o->samples)
                 std::memcpy(h_samples, o->samples, (size_t)trials * 3 * sizeof(int32_t));
             else
                 plane_draw(o->seed, N, trials, h_samples);
-            HIP_TRY(hipMemcpyAsync(d + o_samples, h_samples, (size_t)trials * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            STAGE_TRY(stage.up(d_samples, h_samples, (size_t)trials * 3 * sizeof(int32_t)));
             hipLaunchKernelGGL(plane_score_kernel, dim3(trials), dim3(ALIGN_THREADS), 0, st, g);
         }
         hipLaunchKernelGGL(plane_finish_kernel, dim3(1), dim3(ALIGN_THREADS), 0, st, g);
@@ -491,33 +494,31 @@ static int align_run(ptam_ctx* ctx, const ptam_plane_opts* o, const double* se3_
         *h_out = PlaneOut{};
         h_out->info.status = PTAM_PLANE_OK;
         std::memcpy(h_out->se3, se3_in, sizeof h_out->se3);
-        HIP_TRY(hipMemcpyAsync(g.out, h_out, sizeof(PlaneOut), hipMemcpyHostToDevice, st));
+        STAGE_TRY(stage.up(g.out, h_out, sizeof(PlaneOut)));
     }
     if (apply && K + N > 0) {
-        ApplyArgs a;
         a.K = K;
         a.N = N;
         a.plane = g.out;
-        a.poses = (const double*)(d + o_pose);
-        a.poses_new = (double*)(d + o_pose_new);
-        a.pts = (double*)(d + o_pts);
-        a.src = src ? (const ptam_map_point_source*)(d + o_src) : nullptr;
-        a.pvs = src ? (ptam_pvs_point*)(d + o_pvs) : nullptr;
+        a.poses = d_pose;
+        a.poses_new = d_pose_new;
+        a.pts = d_pts;
+        a.src = src ? d_src : nullptr;
+        a.pvs = src ? d_pvs : nullptr;
         a.pvs_stride = (int)sizeof(ptam_pvs_point);
-        if (K > 0) HIP_TRY(hipMemcpyAsync(d + o_pose, poses, (size_t)K * 96, hipMemcpyHostToDevice, st));
-        if (src && N > 0) HIP_TRY(hipMemcpyAsync(d + o_src, src, (size_t)N * sizeof(ptam_map_point_source), hipMemcpyHostToDevice, st));
+        STAGE_TRY(stage.up(d_pose, poses, (size_t)K * 96));
+        if (src) STAGE_TRY(stage.up(d_src, src, (size_t)N * sizeof(ptam_map_point_source)));
         hipLaunchKernelGGL(map_apply_kernel, dim3((K + N + ALIGN_THREADS - 1) / ALIGN_THREADS), dim3(ALIGN_THREADS), 0, st, a);
     }
     HIP_TRY(hipGetLastError());
     // what the status decides about (the tables, the pixel vectors) comes down into the context's pinned staging and reaches the
     // caller's memory after the wait; the inlier bytes go there directly
-    char *t_pose = (char*)hp + pin_pose, *t_pts = (char*)hp + pin_pts, *t_pvs = (char*)hp + pin_pvs;
     if (apply) {
-        if (K > 0) HIP_TRY(hipMemcpyAsync(t_pose, d + o_pose_new, (size_t)K * 96, hipMemcpyDeviceToHost, st));
-        if (N > 0) HIP_TRY(hipMemcpyAsync(t_pts, d + o_pts, (size_t)N * 24, hipMemcpyDeviceToHost, st));
-        if (src && N > 0) HIP_TRY(hipMemcpyAsync(t_pvs, d + o_pvs, (size_t)N * sizeof(ptam_pvs_point), hipMemcpyDeviceToHost, st));
+        STAGE_TRY(stage.down(t_pose, d_pose_new, (size_t)K * 96));
+        STAGE_TRY(stage.down(t_pts, d_pts, (size_t)N * 24));
+        if (src) STAGE_TRY(stage.down(t_pvs, d_pvs, (size_t)N * sizeof(ptam_pvs_point)));
     }
-    if (o && inlier_out && N >= 10) HIP_TRY(hipMemcpyAsync(inlier_out, g.flags, (size_t)N, hipMemcpyDeviceToHost, st));
+    if (o && inlier_out && N >= 10) STAGE_TRY(stage.down(inlier_out, g.flags, (size_t)N));
     HIP_TRY(ptam_stream_wait(st));
     const int status = o ? h_out->info.status : PTAM_PLANE_OK;
     if (o) {
@@ -579,72 +580,67 @@ int ptam_map_scene_depth(ptam_ctx* ctx, int n_kf, const double* kf_poses12, int 
                          const ptam_map_meas* meas, ptam_scene_depth* out) {
     ARG_TRY(ctx && n_kf >= 0 && n_points >= 0 && n_meas >= 0);
     ARG_TRY((n_kf == 0 || (kf_poses12 && out)) && (n_points == 0 || points3) && (n_meas == 0 || meas));
-    for (int i = 0; i < n_meas; i++) {
-        ARG_TRY(meas[i].kf >= 0 && meas[i].kf < n_kf && meas[i].point >= 0 && meas[i].point < n_points);
-        ARG_TRY(i == 0 || meas[i - 1].kf < meas[i].kf || (meas[i - 1].kf == meas[i].kf && meas[i - 1].point < meas[i].point));
-    }
+    ARG_TRY(mc_sorted_in_range(n_meas, meas, n_kf, n_points));
     if (n_kf == 0) return PTAM_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t Nz = n_points > 0 ? n_points : 1, Mz = n_meas > 0 ? n_meas : 1;
-    const size_t o_pose = 0, o_pts = o_pose + up256((size_t)n_kf * 96), o_meas = o_pts + up256(Nz * 24),
-                 total = o_meas + up256(Mz * sizeof(ptam_map_meas));
-    void *s, *hp;
-    if (int rc = ctx_scratch(ctx, total, &s)) return rc;
-    if (int rc = ctx_pinned(ctx, (size_t)n_kf * sizeof(ptam_scene_depth), &hp)) return rc;   // (before the copies are queued: growing it waits)
-    (void)hp;
-    char* d = (char*)s;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_pose, kf_poses12, (size_t)n_kf * 96, hipMemcpyHostToDevice, st));
-    if (n_points > 0) HIP_TRY(hipMemcpyAsync(d + o_pts, points3, (size_t)n_points * 24, hipMemcpyHostToDevice, st));
-    if (n_meas > 0) HIP_TRY(hipMemcpyAsync(d + o_meas, meas, (size_t)n_meas * sizeof(ptam_map_meas), hipMemcpyHostToDevice, st));
-    return map_scene_depth_core(ctx, n_kf, (const double*)(d + o_pose), (const double*)(d + o_pts), n_meas, (const ptam_map_meas*)(d + o_meas), out);
+    double *d_pose, *d_pts;
+    ptam_map_meas* d_meas;
+    ptam_scene_depth* h_out;
+    MapStage s(ctx);
+    STAGE_TRY(s.carve([&](Carver& c, Carver& pin) {
+        d_pose = c.piece<double>((size_t)n_kf * 12);
+        d_pts = c.room<double>((size_t)n_points * 3);
+        d_meas = c.room<ptam_map_meas>((size_t)n_meas);
+        h_out = pin.piece<ptam_scene_depth>((size_t)n_kf);   // where the kernel writes the result
+    }));
+    STAGE_TRY(s.up(d_pose, kf_poses12, (size_t)n_kf * 96));
+    STAGE_TRY(s.up(d_pts, points3, (size_t)n_points * 24));
+    STAGE_TRY(s.up(d_meas, meas, (size_t)n_meas * sizeof(ptam_map_meas)));
+    return map_scene_depth_core(s, n_kf, d_pose, d_pts, n_meas, d_meas, h_out, out);
 }
 
 }   // extern "C"
 
 // ptam_map_apply_global_transform's launch on tables that are in device memory: poses -> poses_new, the points in place, the pixel
-// vectors (d_src / d_pvs nullable together) into rows pvs_stride bytes apart.  Enqueues only; K + N > 0.
-int map_transform_core(ptam_ctx* ctx, const double se3_new_from_old[12], int K, const double* d_poses, double* d_poses_new, int N,
-                       double* d_points3, const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride) {
-    void *s, *hp;
-    if (int rc = ctx_scratch(ctx, 256, &s)) return rc;
-    if (int rc = ctx_pinned(ctx, 256, &hp)) return rc;
-    PlaneOut* h_out = (PlaneOut*)hp;
+// vectors (d_src / d_pvs nullable together) into rows pvs_stride bytes apart.  d_record / h_record: 256 bytes each of the caller's
+// stage (scratch, pinned) for the aligner's record.  Enqueues only; K + N > 0.
+int map_transform_core(MapStage& s, void* d_record, void* h_record, const double se3_new_from_old[12], int K, const double* d_poses,
+                       double* d_poses_new, int N, double* d_points3, const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride) {
+    PlaneOut* h_out = (PlaneOut*)h_record;
     *h_out = PlaneOut{};
     h_out->info.status = PTAM_PLANE_OK;
     std::memcpy(h_out->se3, se3_new_from_old, sizeof h_out->se3);
-    HIP_TRY(hipMemcpyAsync(s, h_out, sizeof(PlaneOut), hipMemcpyHostToDevice, ctx->stream));
+    STAGE_TRY(s.up(d_record, h_out, sizeof(PlaneOut)));
     ApplyArgs a;
     a.K = K;
     a.N = N;
-    a.plane = (const PlaneOut*)s;
+    a.plane = (const PlaneOut*)d_record;
     a.poses = d_poses;
     a.poses_new = d_poses_new;
     a.pts = d_points3;
     a.src = d_src;
     a.pvs = d_pvs;
     a.pvs_stride = pvs_stride;
-    hipLaunchKernelGGL(map_apply_kernel, dim3((K + N + ALIGN_THREADS - 1) / ALIGN_THREADS), dim3(ALIGN_THREADS), 0, ctx->stream, a);
+    hipLaunchKernelGGL(map_apply_kernel, dim3((K + N + ALIGN_THREADS - 1) / ALIGN_THREADS), dim3(ALIGN_THREADS), 0, s.st, a);
     HIP_TRY(hipGetLastError());
     return PTAM_OK;
 }
 
-// the launch and the wait of ptam_map_scene_depth on tables that are in device memory (n_kf > 0); out: host
-int map_scene_depth_core(ptam_ctx* ctx, int n_kf, const double* d_poses, const double* d_points3, int n_meas, const ptam_map_meas* d_meas,
-                         ptam_scene_depth* out) {
-    void* hp;
-    if (int rc = ctx_pinned(ctx, (size_t)n_kf * sizeof(ptam_scene_depth), &hp)) return rc;
+// the launch and the wait of ptam_map_scene_depth on tables that are in device memory (n_kf > 0); h_out: n_kf records of the
+// caller's pinned stage, which the kernel writes through their device address; out: host
+int map_scene_depth_core(MapStage& s, int n_kf, const double* d_poses, const double* d_points3, int n_meas, const ptam_map_meas* d_meas,
+                         ptam_scene_depth* h_out, ptam_scene_depth* out) {
     DepthArgs a;
     a.K = n_kf;
     a.M = n_meas;
     a.poses = d_poses;
     a.pts = d_points3;
     a.meas = d_meas;
-    a.out = (ptam_scene_depth*)ctx->d_pinned;
-    hipLaunchKernelGGL(scene_depth_kernel, dim3(n_kf), dim3(ALIGN_THREADS), 0, ctx->stream, a);
+    a.out = s.pin_dev(h_out);
+    hipLaunchKernelGGL(scene_depth_kernel, dim3(n_kf), dim3(ALIGN_THREADS), 0, s.st, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(ptam_stream_wait(ctx->stream));
-    std::memcpy(out, hp, (size_t)n_kf * sizeof(ptam_scene_depth));
+    HIP_TRY(ptam_stream_wait(s.st));
+    std::memcpy(out, h_out, (size_t)n_kf * sizeof(ptam_scene_depth));
     return PTAM_OK;
 }
 

@@ -18,15 +18,15 @@
 //   mba_scatter_*       accepted > 0: the bundle's points and poses back into the tables through the id maps
 //   mba_order_kernel    the purged measurements per LM step in insertion order (GetOutlierMeasurements, src/Bundle.cc:540, :623)
 //   mba_route_kernel    one lane per point with outliers walks them in list order: GoodMeasCount / SRC_ROOT rules (:916-932)
-// mba_run is all of the above on tables that are either the caller's host arrays (ptam_map_bundle_adjust: up into the scratch, the
-// adjusted poses and points down) or a resident map's device buffers (ptam_rmap_bundle_adjust, maprmap.hip: adjusted in place,
-// mba_sync_world_kernel copies the points into the point rows' pv.world, the poses come down into the host mirror).
+// mba_core is all of the above on tables in device memory.  ptam_map_bundle_adjust stages the caller's host arrays up into the
+// call's scratch and the adjusted poses and points down; ptam_rmap_bundle_adjust (maprmap.hip) hands it a resident map's buffers:
+// adjusted in place, mba_sync_world_kernel copies the points into the point rows' pv.world, the poses come down into the host mirror.
 #include "common.h"
 #include <climits>
 #include <vector>
 
 #include "bundle.h"
-#include "maptables_internal.h"   // MbaTables, mba_run
+#include "maptables_internal.h"   // MbaTables, MbaWork, mba_core
 #include "kf_dist_device.h"   // mba_centre, mba_linear_dist, mba_pair_less, mba_block_least
 
 namespace {
@@ -330,64 +330,60 @@ __global__ void __launch_bounds__(256) mba_sync_world_kernel(int n, const double
     for (int c = 0; c < 3; c++) rows[i].pv.world[c] = pts[(size_t)3 * i + c];
 }
 
-// ptam_map_bundle_adjust behind its argument checks, on host tables (they go up into the scratch; the adjusted poses and points come
-// down) or on resident ones (written in place; the poses come down into the mirror): maptables_internal.h
-int mba_run(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, const MbaTables& t, const volatile unsigned char* abort_flag,
-            ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids, unsigned long long traffic[2]) {
-    const int n_kf = t.K;
-    const double* kf_poses12 = t.h_poses;
-    const uint8_t* kf_fixed = t.h_fixed;
-    const bool resident = t.d_meas != nullptr || t.d_poses != nullptr;
-    std::memset(res, 0, sizeof *res);
-    if (mode == PTAM_MAP_BA_RECENT && n_kf < 8) return PTAM_OK;   // :790-793
-    HIP_TRY(hipSetDevice(ctx->device));
+// device scratch (the bundle keeps its own memory): [cleared: header | role | point marks | rows per point] then the rest
+void mba_layout(Carver& c, Carver& pin, int K, int N, int M, MbaWork& w) {
+    const size_t Kz = std::max(K, 1), Nz = std::max(N, 1), Mz = std::max(M, 1), nb = ((size_t)M + MBA_BLOCK - 1) / MBA_BLOCK;
+    const size_t clear_from = c.off;
+    w.cleared = (char*)c.piece<MbaHdr>(1);
+    w.role = c.piece<int>(Kz);
+    w.pt_mark = c.piece<int>(Nz);
+    w.pt_rows = c.piece<int>(Nz);
+    w.clear_bytes = c.off - clear_from;
+    w.cam_id = c.piece<int>(Kz);
+    w.cam_kf = c.piece<int>(Kz);
+    w.pt_id = c.piece<int>(Nz);
+    w.pt_of = c.piece<int>(Nz);
+    w.pts_sel = c.piece<double>(Nz * 3);
+    w.blk = c.piece<int>(nb + 1);
+    w.sel_row = c.piece<int>(Mz);
+    // outlier routing (outliers <= bundle measurements <= M)
+    w.ord = c.piece<int>(Mz);
+    w.orow = c.piece<int>(Mz);
+    w.opt = c.piece<int>(Mz);
+    w.first = c.piece<int>(Nz);
+    w.out = c.piece<ptam_map_outlier>(Mz);
+    w.h_sel = pin.piece<char>(sizeof(MbaHdr) + Kz * 4);
+}
+
+int mba_core(MapStage& s, const ptam_ba_opts* opts, int mode, const MbaTables& t, const MbaWork& w, const volatile unsigned char* abort_flag,
+             ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids) {
+    ptam_ctx* ctx = s.ctx;
     const int K = t.K, N = t.N, M = t.M, nb = (M + MBA_BLOCK - 1) / MBA_BLOCK;
     BaGuard g;
     if (int rc = ptam_ba_create(ctx, opts, &g.ba)) return rc;
     char* d_ms = nullptr;
     if (int rc = ba_dev_meas_chunks(g.ba, (size_t)M, &d_ms)) return rc;
-    // device scratch (the bundle keeps its own memory): [cleared: header | role | point marks | rows per point] then the rest
-    const size_t Kz = std::max(K, 1), Nz = std::max(N, 1), Mz = std::max(M, 1);
-    Carver cv;
-    const size_t o_hdr = cv.take(sizeof(MbaHdr)), o_role = cv.take(Kz * 4), o_mark = cv.take(Nz * 4), o_rows = cv.take(Nz * 4);
-    const size_t clear = cv.off;
-    const size_t o_pose = cv.take(resident ? 0 : Kz * 96), o_fixed = cv.take(resident ? 0 : Kz), o_pts = cv.take(resident ? 0 : Nz * 24),
-                 o_meas = cv.take(resident ? 0 : Mz * sizeof(ptam_map_meas)), o_camid = cv.take(Kz * 4), o_camkf = cv.take(Kz * 4), o_ptid = cv.take(Nz * 4), o_ptof = cv.take(Nz * 4), o_ptsel = cv.take(Nz * 24),
-                 o_blk = cv.take(((size_t)nb + 1) * 4), o_selrow = cv.take(Mz * 4);
-    // outlier routing (outliers <= bundle measurements <= M)
-    const size_t o_ord = cv.take(Mz * 4), o_orow = cv.take(Mz * 4), o_opt = cv.take(Mz * 4), o_first = cv.take(Nz * 4),
-                 o_out = cv.take(Mz * sizeof(ptam_map_outlier));
-    void* s = nullptr;
-    if (int rc = ctx_scratch(ctx, cv.off, &s)) return rc;
-    char* b = (char*)s;
     MbaDev a;
     a.mode = mode, a.K = K, a.N = N, a.M = M, a.nb = nb;
-    a.pose = resident ? t.d_poses : (const double*)(b + o_pose);
-    a.fixed = resident ? t.d_fixed : (const uint8_t*)(b + o_fixed);
-    a.pts = resident ? t.d_points3 : (double*)(b + o_pts);
-    a.meas = resident ? t.d_meas : (const ptam_map_meas*)(b + o_meas);
-    a.role = (int*)(b + o_role);
-    a.cam_id = (int*)(b + o_camid);
-    a.cam_kf = (int*)(b + o_camkf);
-    a.pt_mark = (int*)(b + o_mark);
-    a.pt_rows = (int*)(b + o_rows);
-    a.pt_id = (int*)(b + o_ptid);
-    a.pt_of = (int*)(b + o_ptof);
-    a.pts_sel = (double*)(b + o_ptsel);
-    a.blk = (int*)(b + o_blk);
-    a.sel_row = (int*)(b + o_selrow);
+    a.pose = t.d_poses;
+    a.fixed = t.d_fixed;
+    a.pts = t.d_points3;
+    a.meas = t.d_meas;
+    a.role = w.role;
+    a.cam_id = w.cam_id;
+    a.cam_kf = w.cam_kf;
+    a.pt_mark = w.pt_mark;
+    a.pt_rows = w.pt_rows;
+    a.pt_id = w.pt_id;
+    a.pt_of = w.pt_of;
+    a.pts_sel = w.pts_sel;
+    a.blk = w.blk;
+    a.sel_row = w.sel_row;
     a.ms = d_ms;
-    a.hdr = (MbaHdr*)(b + o_hdr);
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemsetAsync(b, 0, clear, st));
-    if (!resident) {
-        if (K > 0) {
-            HIP_TRY(hipMemcpyAsync(b + o_pose, kf_poses12, (size_t)K * 96, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(b + o_fixed, kf_fixed, (size_t)K, hipMemcpyHostToDevice, st));
-        }
-        if (N > 0) HIP_TRY(hipMemcpyAsync(b + o_pts, t.h_points3, (size_t)N * 24, hipMemcpyHostToDevice, st));
-        if (M > 0) HIP_TRY(hipMemcpyAsync(b + o_meas, t.h_meas, (size_t)M * sizeof(ptam_map_meas), hipMemcpyHostToDevice, st));
-    }
+    a.hdr = (MbaHdr*)w.cleared;
+    // ---- the selection and its one wait: error flag, sizes, camera list
+    hipStream_t st = s.st;
+    HIP_TRY(hipMemsetAsync(w.cleared, 0, w.clear_bytes, st));
     hipLaunchKernelGGL(mba_select_kernel, dim3(1), dim3(1024), 0, st, a);
     if (M > 0) {
         hipLaunchKernelGGL(mba_mark_kernel, dim3(nb), dim3(MBA_BLOCK), 0, st, a);
@@ -396,14 +392,10 @@ int mba_run(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, const MbaTables& 
     hipLaunchKernelGGL(mba_ids_kernel, dim3(1), dim3(1024), 0, st, a);
     if (M > 0) hipLaunchKernelGGL(mba_compact_kernel, dim3(nb), dim3(MBA_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
-    void* hp = nullptr;
-    if (int rc = ctx_pinned(ctx, sizeof(MbaHdr) + Kz * 4, &hp)) return rc;
-    HIP_TRY(hipMemcpyAsync(hp, a.hdr, sizeof(MbaHdr), hipMemcpyDeviceToHost, st));
-    if (K > 0) HIP_TRY(hipMemcpyAsync((char*)hp + sizeof(MbaHdr), a.cam_kf, (size_t)K * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ptam_stream_wait(st));   // the one wait of the selection
-    const MbaHdr h = *(const MbaHdr*)hp;
-    unsigned long long down = sizeof(MbaHdr) + (size_t)K * 4;   // what this layer copies over the host link (the bundle's own words apart)
-    if (traffic) traffic[1] = down;                             // (it stands if the call ends early)
+    STAGE_TRY(s.down(w.h_sel, a.hdr, sizeof(MbaHdr)));
+    STAGE_TRY(s.down(w.h_sel + sizeof(MbaHdr), a.cam_kf, (size_t)K * 4));
+    HIP_TRY(ptam_stream_wait(st));
+    const MbaHdr h = *(const MbaHdr*)w.h_sel;
     if (h.err) {
         ptam_set_error("map_bundle_adjust: table row %d is out of range or out of (kf, point) order", h.err_row);
         return PTAM_E_ARG;
@@ -414,59 +406,44 @@ int mba_run(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, const MbaTables& 
                        h.n_meas, M);
         return PTAM_E_STATE;
     }
-    // the bundle's cameras: O(K) host work (:852-861)
-    std::vector<int> ckf((const int*)((char*)hp + sizeof(MbaHdr)), (const int*)((char*)hp + sizeof(MbaHdr)) + C);
+    // ---- the bundle's cameras: O(K) host work (:852-861), then ingest and Compute()
+    std::vector<int> ckf((const int*)(w.h_sel + sizeof(MbaHdr)), (const int*)(w.h_sel + sizeof(MbaHdr)) + C);
     std::vector<double> cpose((size_t)12 * C);
     std::vector<uint8_t> cfix((size_t)C);
     for (int c = 0; c < C; c++) {
         const int k = ckf[(size_t)c];
-        std::memcpy(&cpose[(size_t)12 * c], kf_poses12 + (size_t)12 * k, 96);
-        cfix[(size_t)c] = c < h.n_adjust ? (kf_fixed[k] ? 1 : 0) : 1;
+        std::memcpy(&cpose[(size_t)12 * c], t.h_poses + (size_t)12 * k, 96);
+        cfix[(size_t)c] = c < h.n_adjust ? (t.h_fixed[k] ? 1 : 0) : 1;
     }
     if (int rc = ba_dev_ingest(g.ba, C, cpose.data(), cfix.data(), h.n_points, a.pts_sel, h.n_meas)) return rc;
     int accepted = 0;
     if (int rc = ptam_ba_compute(g.ba, abort_flag, &accepted)) return rc;
     BaDevResult r;
     if (int rc = ba_dev_result(g.ba, &r)) return rc;
-    st = ctx->stream;
-    if (accepted > 0) {   // :895-904
+    // ---- the write-back through the id maps (:895-904)
+    if (accepted > 0) {
         if (h.n_points > 0) hipLaunchKernelGGL(mba_scatter_points_kernel, dim3((h.n_points + 255) / 256), dim3(256), 0, st, a, h.n_points);
         const int nl = std::max(r.P_live, r.C);
-        if (nl > 0) hipLaunchKernelGGL(mba_scatter_live_kernel, dim3((nl + 255) / 256), dim3(256), 0, st, a, r, (double*)a.pose);
+        if (nl > 0) hipLaunchKernelGGL(mba_scatter_live_kernel, dim3((nl + 255) / 256), dim3(256), 0, st, a, r, t.d_poses);
         if (t.d_points && N > 0) hipLaunchKernelGGL(mba_sync_world_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, (const double*)a.pts, t.d_points);
         HIP_TRY(hipGetLastError());
-        if (N > 0 && t.points3_out) HIP_TRY(hipMemcpyAsync(t.points3_out, a.pts, (size_t)N * 24, hipMemcpyDeviceToHost, st));
-        if (K > 0) HIP_TRY(hipMemcpyAsync(t.poses_out, a.pose, (size_t)K * 96, hipMemcpyDeviceToHost, st));
-        down += (size_t)K * 96 + (t.points3_out ? (size_t)N * 24 : 0);
     }
+    // ---- the outlier routing (:916-932)
     const int n_out = std::min(r.n_out, h.n_meas);
-    if (outliers && n_out > 0) {   // :916-932
-        int* ord = (int*)(b + o_ord);
-        int* first = (int*)(b + o_first);
-        ptam_map_outlier* d_out = (ptam_map_outlier*)(b + o_out);
-        void* hs = nullptr;   // the step ends, read by the ordering kernel through host-mapped memory
+    if (outliers && n_out > 0) {
+        void* hs = nullptr;   // the step ends, read by the ordering kernel through host-mapped memory; their number is known only now,
+                              // and the selection's words in the pinned block have been read: a request of its own
         if (int rc = ctx_pinned(ctx, (size_t)std::max(r.n_steps, 1) * 4, &hs)) return rc;
         if (r.n_steps > 0) std::memcpy(hs, r.step_end, (size_t)r.n_steps * 4);
-        HIP_TRY(hipMemsetAsync(first, 0x7f, Nz * 4, st));
+        HIP_TRY(hipMemsetAsync(w.first, 0x7f, (size_t)std::max(N, 1) * 4, st));
         const dim3 grid((n_out + 255) / 256);
-        hipLaunchKernelGGL(mba_order_kernel, grid, dim3(256), 0, st, r.outliers, n_out, (const int*)ctx->d_pinned, r.n_steps, ord);
-        hipLaunchKernelGGL(mba_route_prep_kernel, grid, dim3(256), 0, st, a, (const int*)ord, n_out, h.n_meas, (int*)(b + o_orow),
-                           (int*)(b + o_opt), first);
-        hipLaunchKernelGGL(mba_route_kernel, grid, dim3(256), 0, st, a, n_out, (const int*)(b + o_orow), (const int*)(b + o_opt),
-                           (const int*)first, d_out);
+        hipLaunchKernelGGL(mba_order_kernel, grid, dim3(256), 0, st, r.outliers, n_out, (const int*)ctx->d_pinned, r.n_steps, w.ord);
+        hipLaunchKernelGGL(mba_route_prep_kernel, grid, dim3(256), 0, st, a, (const int*)w.ord, n_out, h.n_meas, w.orow, w.opt, w.first);
+        hipLaunchKernelGGL(mba_route_kernel, grid, dim3(256), 0, st, a, n_out, (const int*)w.orow, (const int*)w.opt, (const int*)w.first, w.out);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(outliers, d_out, (size_t)n_out * sizeof(ptam_map_outlier), hipMemcpyDeviceToHost, st));
-        down += (size_t)n_out * sizeof(ptam_map_outlier);
+        STAGE_TRY(s.down(outliers, w.out, (size_t)n_out * sizeof(ptam_map_outlier)));
     }
-    if (point_ids && h.n_points > 0) {
-        HIP_TRY(hipMemcpyAsync(point_ids, a.pt_of, (size_t)h.n_points * 4, hipMemcpyDeviceToHost, st));
-        down += (size_t)h.n_points * 4;
-    }
-    HIP_TRY(ptam_stream_wait(st));
-    if (traffic) {
-        traffic[0] = (unsigned long long)C * 97;   // the bundle's cameras: pose and flag
-        traffic[1] = down;
-    }
+    if (point_ids) STAGE_TRY(s.down(point_ids, a.pt_of, (size_t)h.n_points * 4));
     if (cam_kf && C > 0) std::memcpy(cam_kf, ckf.data(), (size_t)C * 4);
     res->ran = 1;
     res->accepted = accepted;
@@ -481,6 +458,7 @@ int mba_run(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, const MbaTables& 
 
 extern "C" {
 
+// the host-table form: check, stage up, core, stage down (the table rows themselves are checked by mba_mark_kernel)
 int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, int n_kf, double* kf_poses12, const uint8_t* kf_fixed,
                            int n_points, double* points3, int n_meas, const ptam_map_meas* meas, const volatile unsigned char* abort_flag,
                            ptam_map_ba_result* res, ptam_map_outlier* outliers, int outlier_cap, int32_t* cam_kf, int32_t* point_ids) {
@@ -491,17 +469,37 @@ int ptam_map_bundle_adjust(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, in
     ARG_TRY(n_points == 0 || points3);
     ARG_TRY(n_meas == 0 || meas);
     ARG_TRY(!outliers || outlier_cap >= n_meas);
+    std::memset(res, 0, sizeof *res);
+    if (mode == PTAM_MAP_BA_RECENT && n_kf < 8) return PTAM_OK;   // :790-793
+    HIP_TRY(hipSetDevice(ctx->device));
     MbaTables t = {};
     t.K = n_kf;
     t.N = n_points;
     t.M = n_meas;
     t.h_poses = kf_poses12;
     t.h_fixed = kf_fixed;
-    t.h_points3 = points3;
-    t.h_meas = meas;
-    t.poses_out = kf_poses12;
-    t.points3_out = points3;
-    return mba_run(ctx, opts, mode, t, abort_flag, res, outliers, cam_kf, point_ids, nullptr);
+    uint8_t* d_fixed;
+    ptam_map_meas* d_meas;
+    MbaWork w;
+    MapStage s(ctx);
+    STAGE_TRY(s.carve([&](Carver& c, Carver& pin) {
+        mba_layout(c, pin, n_kf, n_points, n_meas, w);
+        t.d_poses = c.piece<double>((size_t)std::max(n_kf, 1) * 12);
+        t.d_fixed = d_fixed = c.piece<uint8_t>((size_t)std::max(n_kf, 1));
+        t.d_points3 = c.piece<double>((size_t)std::max(n_points, 1) * 3);
+        t.d_meas = d_meas = c.piece<ptam_map_meas>((size_t)std::max(n_meas, 1));
+    }));
+    STAGE_TRY(s.up(t.d_poses, kf_poses12, (size_t)n_kf * 96));
+    STAGE_TRY(s.up(d_fixed, kf_fixed, (size_t)n_kf));
+    STAGE_TRY(s.up(t.d_points3, points3, (size_t)n_points * 24));
+    STAGE_TRY(s.up(d_meas, meas, (size_t)n_meas * sizeof(ptam_map_meas)));
+    STAGE_TRY(mba_core(s, opts, mode, t, w, abort_flag, res, outliers, cam_kf, point_ids));
+    if (res->accepted > 0) {
+        STAGE_TRY(s.down(points3, t.d_points3, (size_t)n_points * 24));
+        STAGE_TRY(s.down(kf_poses12, t.d_poses, (size_t)n_kf * 96));
+    }
+    HIP_TRY(ptam_stream_wait(s.st));
+    return PTAM_OK;
 }
 
 }   // extern "C"

@@ -14,7 +14,6 @@
 #include "refind_internal.h"
 
 enum { MR_FOUND = 0, MR_NEVER = 1, MR_SKIPPED = 2, MR_KEPT = 3, MR_COUNTS = 4 };
-enum { MR_DEFAULT_PASS = 4096 };
 static_assert(sizeof(KfLevels) <= PTAM_RMAP_KF_RECORD_BYTES, "the per-keyframe record ptam_hip.h promises ptam_rmap_refind's callers");
 
 struct MrArgs {
@@ -218,184 +217,81 @@ __global__ void __launch_bounds__(256) mr_merge_kernel(int nA, const Row* __rest
     }
 }
 
-static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-template <class Row>
-static bool table_sorted_in_range(int n, const Row* t, int n_kf, int n_points) {
-    for (int i = 0; i < n; i++) {
-        if (t[i].kf < 0 || t[i].kf >= n_kf || t[i].point < 0 || t[i].point >= n_points) return false;
-        if (i > 0 && !(t[i - 1].kf < t[i].kf || (t[i - 1].kf == t[i].kf && t[i - 1].point < t[i].point))) return false;
-    }
-    return true;
-}
-
-// ptam_map_refind on host tables or on a resident map's (maptables_internal.h)
-int mr_run(ptam_ctx* ctx, ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, const MrTables& t, int n_work, const void* work,
-           const volatile unsigned char* stop_flag, ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix,
-           ptam_map_pair* never_out, int out_cap, ptam_map_meas* meas_merged, ptam_map_pair* never_merged, int* merged_written,
-           unsigned long long traffic[2]) {
-    const int n_kf = t.n_kf, n_points = t.n_points, n_meas = t.n_meas, n_never = t.n_never;
-    const ptam_kf* const* kfs = t.kfs;
-    const double* kf_poses12 = t.h_poses;
-    const ptam_map_refind_point* points = t.h_points;
-    const ptam_map_meas* meas = t.h_meas;
-    const ptam_map_pair* never = t.h_never;
-    const bool resident = t.d_poses != nullptr;
-    unsigned long long up = 0, down = 0;
-    if (merged_written) *merged_written = 0;
-    // ---- refusals: nothing is written and nothing enqueued before all of them have passed
-    ARG_TRY(ctx && finder && finder->ctx->device == ctx->device && res);
+int mr_check_call(ptam_ctx* ctx, const ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, int n_kf, const ptam_kf* const* kfs) {
+    ARG_TRY(ctx && finder && finder->ctx->device == ctx->device);
     ARG_TRY(mode == PTAM_MAP_REFIND_KEYFRAME || mode == PTAM_MAP_REFIND_NEW_POINTS || mode == PTAM_MAP_REFIND_FAILURE_QUEUE);
-    ARG_TRY(n_kf >= 0 && n_points >= 0 && n_meas >= 0 && n_never >= 0 && n_work >= 0 && out_cap >= 0);
-    ARG_TRY((n_kf == 0 || kfs) && (n_work == 0 || work));
-    ARG_TRY(resident || ((n_kf == 0 || kf_poses12) && (n_points == 0 || points) && (n_meas == 0 || meas) && (n_never == 0 || never)));
+    ARG_TRY(n_kf >= 0 && (n_kf == 0 || kfs));
     ARG_TRY(!opts || opts->max_pairs_per_pass >= 0);
     for (int k = 0; k < n_kf; k++) {
         ARG_TRY(kfs[k] && kfs[k]->device == ctx->device);
         ARG_TRY(kfs[k]->L.w[0] == ctx->params.width && kfs[k]->L.h[0] == ctx->params.height);
     }
-    if (!resident) {   // (a resident map's tables have been checked on the device when they went up, and every call keeps the rules)
-        for (int p = 0; p < n_points; p++)
-            ARG_TRY(points[p].src_kf >= 0 && points[p].src_kf < n_kf && points[p].src_level >= 0 && points[p].src_level < PTAM_LEVELS);
-        ARG_TRY(table_sorted_in_range(n_meas, meas, n_kf, n_points));
-        for (int i = 0; i < n_meas; i++)
-            ARG_TRY(meas[i].level >= 0 && meas[i].level < PTAM_LEVELS && meas[i].source >= PTAM_MAP_SRC_TRACKER && meas[i].source <= PTAM_MAP_SRC_EPIPOLAR);
-        ARG_TRY(table_sorted_in_range(n_never, never, n_kf, n_points));
-    }
-    std::vector<int> wpts, wrank, wentry;   // NEW_POINTS: the points that make pairs, their index-order places, their queue entries
-    std::vector<ptam_map_pair> wq;          // FAILURE_QUEUE: sorted (:1074)
-    int kf0 = 0;
-    long long total = 0;                    // the call's pair count
-    if (mode == PTAM_MAP_REFIND_KEYFRAME) {
-        ARG_TRY(n_work <= 1);
-        if (n_work == 1) {
-            kf0 = *(const int32_t*)work;
-            ARG_TRY(kf0 >= 0 && kf0 < n_kf);
-            total = n_points;
-        }
-    } else if (mode == PTAM_MAP_REFIND_NEW_POINTS) {
-        const int32_t* w = (const int32_t*)work;
-        std::vector<uint8_t> seen((size_t)n_points, 0);
-        for (int e = 0; e < n_work; e++) {
-            ARG_TRY(w[e] >= 0 && w[e] < n_points && !seen[(size_t)w[e]]);
-            seen[(size_t)w[e]] = 1;
-            if (t.work_bad ? t.work_bad[e] != 0 : points[w[e]].bad != 0) continue;   // :1056-1059
-            wpts.push_back(w[e]);
-            wentry.push_back(e);
-        }
-        total = (long long)n_kf * n_work;   // (what the capacities are held against: bBad is the table's, not the count's, business)
-    } else {
-        const ptam_map_pair* w = (const ptam_map_pair*)work;
-        for (int e = 0; e < n_work; e++) ARG_TRY(w[e].kf >= 0 && w[e].kf < n_kf && w[e].point >= 0 && w[e].point < n_points);
-        total = n_work;
-    }
-    ARG_TRY(total + n_meas < (1ll << 31) && total + n_never < (1ll << 31));
-    if (!resident || found_out || found_subpix || never_out) {
-        ARG_TRY(total <= (long long)out_cap);
-        ARG_TRY(total == 0 || (found_out && found_subpix && never_out));
-    }
-    if (mode == PTAM_MAP_REFIND_NEW_POINTS) {
-        total = (long long)n_kf * (long long)wpts.size();
-        std::vector<int> by_index(wpts.size());
-        for (size_t i = 0; i < wpts.size(); i++) by_index[i] = (int)i;
-        std::sort(by_index.begin(), by_index.end(), [&](int x, int y) { return wpts[(size_t)x] < wpts[(size_t)y]; });
-        wrank.resize(wpts.size());
-        for (size_t r = 0; r < by_index.size(); r++) wrank[(size_t)by_index[r]] = (int)r;
-    } else if (mode == PTAM_MAP_REFIND_FAILURE_QUEUE) {
-        const ptam_map_pair* w = (const ptam_map_pair*)work;
-        wq.assign(w, w + n_work);
-        std::sort(wq.begin(), wq.end(), [](const ptam_map_pair& x, const ptam_map_pair& y) { return x.kf < y.kf || (x.kf == y.kf && x.point < y.point); });
-    }
-    ptam_map_refind_result r = {};
-    const int P = (int)total;
-    if (P == 0) {   // nothing to visit: the merged tables are copies
-        if (mode == PTAM_MAP_REFIND_NEW_POINTS && !(stop_flag && *stop_flag)) {
-            r.points_consumed = n_work;
-            r.n_bad_points = n_work - (int)wpts.size();
-        } else if (mode == PTAM_MAP_REFIND_NEW_POINTS)
-            r.stopped = n_work > 0;
-        if (!resident && meas_merged && n_meas > 0) std::memcpy(meas_merged, meas, (size_t)n_meas * sizeof(ptam_map_meas));
-        if (!resident && never_merged && n_never > 0) std::memcpy(never_merged, never, (size_t)n_never * sizeof(ptam_map_pair));
-        *res = r;
-        return PTAM_OK;
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
+    return PTAM_OK;
+}
 
-    // ---- device memory: the tables and the call's lists (sized by the call), the pass's work arrays (sized by the pass)
-    int per_pass = opts && opts->max_pairs_per_pass > 0 ? opts->max_pairs_per_pass : MR_DEFAULT_PASS;
-    if (mode == PTAM_MAP_REFIND_NEW_POINTS) per_pass = n_kf * (per_pass / n_kf > 0 ? per_pass / n_kf : 1);   // whole points, at least one
-    if (per_pass > P) per_pass = P;
-    ptam_map_meas* const d_mm_res = resident ? t.d_meas_merged : nullptr;
-    ptam_map_pair* const d_nm_res = resident ? t.d_never_merged : nullptr;
-    const bool want_mm = resident ? d_mm_res != nullptr : meas_merged != nullptr, want_nm = resident ? d_nm_res != nullptr : never_merged != nullptr;
-    const bool merged = want_mm || want_nm, ordered = merged && mode == PTAM_MAP_REFIND_NEW_POINTS;
-    const size_t Pz = (size_t)P, Kz = (size_t)n_kf, Wz = wpts.size() > wq.size() * 2 ? wpts.size() : wq.size() * 2;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += up256(bytes > 0 ? bytes : 1);
-        return at;
-    };
-    const size_t o_pose = take(resident ? 0 : Kz * 96), o_ls = take(Kz * sizeof(KfLevels)),
-                 o_pts = take(resident ? 0 : (size_t)n_points * sizeof(ptam_map_refind_point)),
-                 o_meas = take(resident ? 0 : (size_t)n_meas * sizeof(ptam_map_meas)),
-                 o_never = take(resident ? 0 : (size_t)n_never * sizeof(ptam_map_pair)),
-                 o_w0 = take(Wz * 4), o_w1 = take(Wz * 4), o_cnt = take(MR_COUNTS * 4), o_found = take(Pz * sizeof(ptam_map_meas)),
-                 o_sub = take(Pz * 4), o_nev = take(Pz * sizeof(ptam_map_pair)), o_slot = take(ordered ? Pz * 4 : 0),
-                 o_ordf = take(ordered ? Pz * 4 : 0), o_ordn = take(ordered ? Pz * 4 : 0),
-                 o_mm = take(want_mm && !resident ? (Pz + (size_t)n_meas) * sizeof(ptam_map_meas) : 0),
-                 o_nm = take(want_nm && !resident ? (Pz + (size_t)n_never) * sizeof(ptam_map_pair) : 0), o_pairs = take((size_t)per_pass * sizeof(RpPair));
-    RpDev d;
-    void *sc, *hp;
-    if (int rc = ctx_scratch(ctx, rp_carve(d, nullptr, off, per_pass), &sc)) return rc;
-    if (int rc = ctx_pinned(ctx, 256, &hp)) return rc;
-    char* b = (char*)sc;
-    rp_carve(d, b, off, per_pass);
-    hipStream_t st = ctx->stream;
-    std::vector<KfLevels> hl(Kz);
-    for (int k = 0; k < n_kf; k++) hl[(size_t)k] = kfs[k]->L;
-    HIP_TRY(hipMemcpyAsync(b + o_ls, hl.data(), Kz * sizeof(KfLevels), hipMemcpyHostToDevice, st));
-    up += Kz * sizeof(KfLevels) + wpts.size() * 8 + wq.size() * sizeof(ptam_map_pair);
-    if (!resident) {
-        HIP_TRY(hipMemcpyAsync(b + o_pose, kf_poses12, Kz * 96, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_pts, points, (size_t)n_points * sizeof(ptam_map_refind_point), hipMemcpyHostToDevice, st));
-        if (n_meas > 0) HIP_TRY(hipMemcpyAsync(b + o_meas, meas, (size_t)n_meas * sizeof(ptam_map_meas), hipMemcpyHostToDevice, st));
-        if (n_never > 0) HIP_TRY(hipMemcpyAsync(b + o_never, never, (size_t)n_never * sizeof(ptam_map_pair), hipMemcpyHostToDevice, st));
-    }
-    if (!wpts.empty()) {
-        HIP_TRY(hipMemcpyAsync(b + o_w0, wpts.data(), wpts.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_w1, wrank.data(), wrank.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    if (!wq.empty()) HIP_TRY(hipMemcpyAsync(b + o_w0, wq.data(), wq.size() * sizeof(ptam_map_pair), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(b + o_cnt, 0, MR_COUNTS * 4, st));
-    if (ordered) HIP_TRY(hipMemsetAsync(b + o_slot, 0, Pz * 4, st));   // (a stopped call leaves pairs unvisited)
+// the call's lists (sized by the call), then the pass's work arrays (sized by the pass)
+void mr_layout(Carver& c, Carver& pin, int n_kf, const MrPlan& plan, bool merged, MrWork& w) {
+    const bool ordered = merged && plan.mode == PTAM_MAP_REFIND_NEW_POINTS;   // (visiting order is point-major there: mr_order_kernel)
+    const size_t Pz = (size_t)plan.pairs, Wz = std::max(plan.wpts.size(), plan.wq.size() * 2);
+    w.Ls = c.room<KfLevels>((size_t)n_kf);
+    w.w0 = c.room<int>(Wz);
+    w.w1 = c.room<int>(Wz);
+    w.cnt = c.piece<int>(MR_COUNTS);
+    w.found = c.room<ptam_map_meas>(Pz);
+    w.subpix = c.room<int32_t>(Pz);
+    w.nev = c.room<ptam_map_pair>(Pz);
+    w.slot = c.room<int>(ordered ? Pz : 0);
+    w.ord_f = c.room<int>(ordered ? Pz : 0);
+    w.ord_n = c.room<int>(ordered ? Pz : 0);
+    w.pairs = c.room<RpPair>((size_t)plan.per_pass);
+    c.off = rp_carve(w.chain, c.base, c.off, plan.per_pass);
+    w.h_cnt = pin.piece<int>(MR_COUNTS);
+}
+
+int mr_core(MapStage& s, ptam_refinder* finder, const MrTables& t, const MrPlan& plan, const MrWork& w, const volatile unsigned char* stop_flag,
+            ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix, ptam_map_pair* never_out) {
+    const int P = plan.pairs, n_kf = t.n_kf;
+    const bool merged = t.d_meas_merged || t.d_never_merged, ordered = merged && plan.mode == PTAM_MAP_REFIND_NEW_POINTS;
+    hipStream_t st = s.st;
+    // ---- up: the level records and the work lists
+    std::vector<KfLevels> hl((size_t)n_kf);
+    for (int k = 0; k < n_kf; k++) hl[(size_t)k] = t.kfs[k]->L;
+    STAGE_TRY(s.up(w.Ls, hl.data(), hl.size() * sizeof(KfLevels)));
+    STAGE_TRY(s.up(w.w0, plan.wpts.data(), plan.wpts.size() * 4));
+    STAGE_TRY(s.up(w.w1, plan.wrank.data(), plan.wrank.size() * 4));
+    STAGE_TRY(s.up(w.w0, plan.wq.data(), plan.wq.size() * sizeof(ptam_map_pair)));
+    HIP_TRY(hipMemsetAsync(w.cnt, 0, MR_COUNTS * 4, st));
+    if (ordered) HIP_TRY(hipMemsetAsync(w.slot, 0, (size_t)P * 4, st));   // (a stopped call leaves pairs unvisited)
     MrArgs a;
-    a.mode = mode;
+    a.mode = plan.mode;
     a.n_kf = n_kf;
-    a.kf0 = kf0;
-    a.n_wp = (int)wpts.size();
-    a.wpts = (const int*)(b + o_w0);
-    a.wrank = (const int*)(b + o_w1);
-    a.wq = (const ptam_map_pair*)(b + o_w0);
-    a.poses = resident ? t.d_poses : (const double*)(b + o_pose);
-    a.Ls = (const KfLevels*)(b + o_ls);
-    a.pts = resident ? t.d_points : (const ptam_map_refind_point*)(b + o_pts);
-    a.n_meas = n_meas;
-    a.n_never = n_never;
-    a.meas = resident ? t.d_meas : (const ptam_map_meas*)(b + o_meas);
-    a.never = resident ? t.d_never : (const ptam_map_pair*)(b + o_never);
-    a.pairs = (RpPair*)(b + o_pairs);
-    a.out = d.out;
-    a.kept = d.kept;
-    a.cnt = (int*)(b + o_cnt);
-    a.found = (ptam_map_meas*)(b + o_found);
-    a.subpix = (int32_t*)(b + o_sub);
-    a.nev = (ptam_map_pair*)(b + o_nev);
-    a.slot = ordered ? (int*)(b + o_slot) : nullptr;
+    a.kf0 = plan.kf0;
+    a.n_wp = (int)plan.wpts.size();
+    a.wpts = w.w0;
+    a.wrank = w.w1;
+    a.wq = (const ptam_map_pair*)w.w0;
+    a.poses = t.d_poses;
+    a.Ls = w.Ls;
+    a.pts = t.d_points;
+    a.n_meas = t.n_meas;
+    a.n_never = t.n_never;
+    a.meas = t.d_meas;
+    a.never = t.d_never;
+    a.pairs = w.pairs;
+    a.out = w.chain.out;
+    a.kept = w.chain.kept;
+    a.cnt = w.cnt;
+    a.found = w.found;
+    a.subpix = w.subpix;
+    a.nev = w.nev;
+    a.slot = ordered ? w.slot : nullptr;
+    RpDev d = w.chain;
     d.pairs = a.pairs;
     d.Ls = a.Ls;
     d.st = finder->st;
 
     // ---- the passes: the stop flag is looked at before each one, nothing is waited for between them
+    ptam_map_refind_result r = {};
     int visited = 0;
     while (visited < P) {
         if (stop_flag && *stop_flag) {
@@ -403,79 +299,107 @@ int mr_run(ptam_ctx* ctx, ptam_refinder* finder, const ptam_map_refind_opts* opt
             break;
         }
         a.first = visited;
-        a.n = d.n = P - visited < per_pass ? P - visited : per_pass;
+        a.n = d.n = std::min(P - visited, plan.per_pass);
         hipLaunchKernelGGL(mr_pairs_kernel, dim3((a.n + 255) / 256), dim3(256), 0, st, a);
-        rp_launch_chain(st, ctx->cam, d);
+        rp_launch_chain(st, s.ctx->cam, d);
         hipLaunchKernelGGL(mr_collect_kernel, dim3(1), dim3(1024), 0, st, a);
         visited += a.n;
     }
     r.n_pairs = visited;
-    if (mode == PTAM_MAP_REFIND_NEW_POINTS) {   // queue entries behind the last visited point are popped while the flag is down (:1053-1059)
-        const size_t wp = (size_t)(visited / n_kf);
-        r.points_consumed = r.stopped ? (wp > 0 ? wentry[wp - 1] + 1 : 0) : n_work;
-        r.n_bad_points = r.points_consumed - (int)wp;
-    }
-    const int* order_f = nullptr;
-    const int* order_n = nullptr;
+    mr_plan_consumed(plan, visited, r.stopped != 0, &r.points_consumed, &r.n_bad_points);
+    // ---- the merged tables: the rows' places in (kf, point) order where the visiting order is point-major, then the two merges
+    const int *order_f = nullptr, *order_n = nullptr;
     if (ordered) {
-        order_f = (const int*)(b + o_ordf);
-        order_n = (const int*)(b + o_ordn);
-        hipLaunchKernelGGL(mr_order_kernel, dim3(1), dim3(1024), 0, st, P, (const int*)a.slot, (int*)(b + o_ordf), (int*)(b + o_ordn));
+        order_f = w.ord_f;
+        order_n = w.ord_n;
+        hipLaunchKernelGGL(mr_order_kernel, dim3(1), dim3(1024), 0, st, P, (const int*)a.slot, w.ord_f, w.ord_n);
     }
-    if (want_mm)
-        hipLaunchKernelGGL(mr_merge_kernel<ptam_map_meas>, dim3((n_meas + visited + 255) / 256 + 1), dim3(256), 0, st, n_meas, a.meas,
-                           (const int*)(a.cnt + MR_FOUND), (const ptam_map_meas*)a.found, order_f, resident ? d_mm_res : (ptam_map_meas*)(b + o_mm));
-    if (want_nm)
-        hipLaunchKernelGGL(mr_merge_kernel<ptam_map_pair>, dim3((n_never + visited + 255) / 256 + 1), dim3(256), 0, st, n_never, a.never,
-                           (const int*)(a.cnt + MR_NEVER), (const ptam_map_pair*)a.nev, order_n, resident ? d_nm_res : (ptam_map_pair*)(b + o_nm));
+    if (t.d_meas_merged)
+        hipLaunchKernelGGL(mr_merge_kernel<ptam_map_meas>, dim3((t.n_meas + visited + 255) / 256 + 1), dim3(256), 0, st, t.n_meas, a.meas,
+                           (const int*)(a.cnt + MR_FOUND), (const ptam_map_meas*)a.found, order_f, t.d_meas_merged);
+    if (t.d_never_merged)
+        hipLaunchKernelGGL(mr_merge_kernel<ptam_map_pair>, dim3((t.n_never + visited + 255) / 256 + 1), dim3(256), 0, st, t.n_never, a.never,
+                           (const int*)(a.cnt + MR_NEVER), (const ptam_map_pair*)a.nev, order_n, t.d_never_merged);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hp, a.cnt, MR_COUNTS * 4, hipMemcpyDeviceToHost, st));
+    STAGE_TRY(s.down(w.h_cnt, a.cnt, MR_COUNTS * 4));
     HIP_TRY(ptam_stream_wait(st));   // the counts say how much of the lists to fetch
-    const int* hc = (const int*)hp;
-    r.n_found = hc[MR_FOUND];
-    r.n_never = hc[MR_NEVER];
-    r.n_skipped = hc[MR_SKIPPED];
-    r.n_template_kept = hc[MR_KEPT];
-    const size_t nf = (size_t)r.n_found, nn = (size_t)r.n_never;
-    down += MR_COUNTS * 4;
-    if (merged_written) *merged_written = 1;
-    if (found_out) down += nf * (sizeof(ptam_map_meas) + 4) + nn * sizeof(ptam_map_pair);
-    if (nf > 0 && found_out) {
-        HIP_TRY(hipMemcpyAsync(found_out, a.found, nf * sizeof(ptam_map_meas), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(found_subpix, a.subpix, nf * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (nn > 0 && never_out) HIP_TRY(hipMemcpyAsync(never_out, a.nev, nn * sizeof(ptam_map_pair), hipMemcpyDeviceToHost, st));
-    if (!resident && meas_merged && nf + (size_t)n_meas > 0)
-        HIP_TRY(hipMemcpyAsync(meas_merged, b + o_mm, (nf + (size_t)n_meas) * sizeof(ptam_map_meas), hipMemcpyDeviceToHost, st));
-    if (!resident && never_merged && nn + (size_t)n_never > 0)
-        HIP_TRY(hipMemcpyAsync(never_merged, b + o_nm, (nn + (size_t)n_never) * sizeof(ptam_map_pair), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ptam_stream_wait(st));   // (also keeps the staging vectors alive until their pageable copies have been staged)
-    if (traffic) {
-        traffic[0] = up;
-        traffic[1] = down;
+    r.n_found = w.h_cnt[MR_FOUND];
+    r.n_never = w.h_cnt[MR_NEVER];
+    r.n_skipped = w.h_cnt[MR_SKIPPED];
+    r.n_template_kept = w.h_cnt[MR_KEPT];
+    if (found_out) {
+        STAGE_TRY(s.down(found_out, a.found, (size_t)r.n_found * sizeof(ptam_map_meas)));
+        STAGE_TRY(s.down(found_subpix, a.subpix, (size_t)r.n_found * 4));
+        STAGE_TRY(s.down(never_out, a.nev, (size_t)r.n_never * sizeof(ptam_map_pair)));
     }
     *res = r;
     return PTAM_OK;
 }
 
+// the host-table form: check, stage up, core, stage down
 extern "C" int ptam_map_refind(ptam_ctx* ctx, ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, int n_kf,
                                const ptam_kf* const* kfs, const double* kf_poses12, int n_points, const ptam_map_refind_point* points, int n_meas,
                                const ptam_map_meas* meas, int n_never, const ptam_map_pair* never, int n_work, const void* work,
                                const volatile unsigned char* stop_flag, ptam_map_refind_result* res, ptam_map_meas* found_out,
                                int32_t* found_subpix, ptam_map_pair* never_out, int out_cap, ptam_map_meas* meas_merged,
                                ptam_map_pair* never_merged) {
+    // ---- refusals: nothing is written and nothing enqueued before all of them have passed
+    ARG_TRY(res && n_points >= 0 && n_meas >= 0 && n_never >= 0 && n_work >= 0 && out_cap >= 0);
+    if (int rc = mr_check_call(ctx, finder, opts, mode, n_kf, kfs)) return rc;
+    ARG_TRY((n_work == 0 || work) && (n_kf == 0 || kf_poses12) && (n_points == 0 || points) && (n_meas == 0 || meas) && (n_never == 0 || never));
+    ARG_TRY(mc_points_source_range(n_points, points, n_kf));
+    ARG_TRY(mc_meas_valid(n_meas, meas, n_kf, n_points));
+    ARG_TRY(mc_sorted_in_range(n_never, never, n_kf, n_points));
+    MrPlan plan;
+    ARG_TRY(mr_plan(mode, n_kf, n_points, n_work, work, [&](int, int p) { return points[p].bad != 0; }, opts ? opts->max_pairs_per_pass : 0, &plan));
+    ARG_TRY(plan.bound + n_meas < (1ll << 31) && plan.bound + n_never < (1ll << 31));
+    ARG_TRY(plan.bound <= (long long)out_cap);
+    ARG_TRY(plan.bound == 0 || (found_out && found_subpix && never_out));
+    if (plan.pairs == 0) {   // nothing to visit: the merged tables are copies
+        if (meas_merged && n_meas > 0) std::memcpy(meas_merged, meas, (size_t)n_meas * sizeof(ptam_map_meas));
+        if (never_merged && n_never > 0) std::memcpy(never_merged, never, (size_t)n_never * sizeof(ptam_map_pair));
+        *res = mr_plan_nothing(plan, stop_flag && *stop_flag);
+        return PTAM_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    // ---- the tables up, beside the core's work in the call's one block
+    const size_t Pz = (size_t)plan.pairs, Mz = (size_t)n_meas, Vz = (size_t)n_never;
+    double* d_poses;
+    ptam_map_refind_point* d_points;
+    ptam_map_meas* d_meas;
+    ptam_map_pair* d_never;
     MrTables t = {};
     t.n_kf = n_kf;
     t.n_points = n_points;
     t.n_meas = n_meas;
     t.n_never = n_never;
     t.kfs = kfs;
-    t.h_poses = kf_poses12;
-    t.h_points = points;
-    t.h_meas = meas;
-    t.h_never = never;
-    return mr_run(ctx, finder, opts, mode, t, n_work, work, stop_flag, res, found_out, found_subpix, never_out, out_cap, meas_merged,
-                  never_merged, nullptr, nullptr);
+    MrWork w;
+    MapStage s(ctx);
+    STAGE_TRY(s.carve([&](Carver& c, Carver& pin) {
+        t.d_poses = d_poses = c.piece<double>((size_t)n_kf * 12);
+        t.d_points = d_points = c.room<ptam_map_refind_point>((size_t)n_points);
+        t.d_meas = d_meas = c.room<ptam_map_meas>(Mz);
+        t.d_never = d_never = c.room<ptam_map_pair>(Vz);
+        t.d_meas_merged = c.room<ptam_map_meas>(meas_merged ? Pz + Mz : 0);
+        t.d_never_merged = c.room<ptam_map_pair>(never_merged ? Pz + Vz : 0);
+        mr_layout(c, pin, n_kf, plan, meas_merged || never_merged, w);
+    }));
+    if (!meas_merged) t.d_meas_merged = nullptr;
+    if (!never_merged) t.d_never_merged = nullptr;
+    STAGE_TRY(s.up(d_poses, kf_poses12, (size_t)n_kf * 96));
+    STAGE_TRY(s.up(d_points, points, (size_t)n_points * sizeof(ptam_map_refind_point)));
+    STAGE_TRY(s.up(d_meas, meas, Mz * sizeof(ptam_map_meas)));
+    STAGE_TRY(s.up(d_never, never, Vz * sizeof(ptam_map_pair)));
+    ptam_map_refind_result r;
+    STAGE_TRY(mr_core(s, finder, t, plan, w, stop_flag, &r, found_out, found_subpix, never_out));
+    // ---- down: the merged tables, behind the lists
+    if (meas_merged) STAGE_TRY(s.down(meas_merged, t.d_meas_merged, ((size_t)r.n_found + Mz) * sizeof(ptam_map_meas)));
+    if (never_merged) STAGE_TRY(s.down(never_merged, t.d_never_merged, ((size_t)r.n_never + Vz) * sizeof(ptam_map_pair)));
+    HIP_TRY(ptam_stream_wait(s.st));
+    *res = r;
+    return PTAM_OK;
 }
 
 void maprefind_preload_kernels() {

@@ -299,44 +299,6 @@ __global__ void __launch_bounds__(256) mt_add_points_kernel(MtAdd p) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-static inline size_t mt_up256(size_t b) { return (b + 255) & ~(size_t)255; }
-struct MtCarve {   // offsets into the context's scratch
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t at = off;
-        off += mt_up256(bytes > 0 ? bytes : 1);
-        return at;
-    }
-};
-template <class Row>
-static bool mt_sorted_in_range(int n, const Row* t, int n_kf, int n_points) {
-    for (int i = 0; i < n; i++) {
-        if (t[i].kf < 0 || t[i].kf >= n_kf || t[i].point < 0 || t[i].point >= n_points) return false;
-        if (i > 0 && !(t[i - 1].kf < t[i].kf || (t[i - 1].kf == t[i].kf && t[i - 1].point < t[i].point))) return false;
-    }
-    return true;
-}
-static bool mt_meas_valid(int n, const ptam_map_meas* m, int n_kf, int n_points) {
-    if (!mt_sorted_in_range(n, m, n_kf, n_points)) return false;
-    for (int i = 0; i < n; i++)
-        if (m[i].level < 0 || m[i].level >= PTAM_LEVELS || m[i].source < PTAM_MAP_SRC_TRACKER || m[i].source > PTAM_MAP_SRC_EPIPOLAR) return false;
-    return true;
-}
-static bool mt_pairs_in_range(int n, const ptam_map_pair* q, int n_kf, int n_points) {
-    for (int i = 0; i < n; i++)
-        if (q[i].kf < 0 || q[i].kf >= n_kf || q[i].point < 0 || q[i].point >= n_points) return false;
-    return true;
-}
-static inline bool mt_pair_less(const ptam_map_pair& x, const ptam_map_pair& y) { return x.kf < y.kf || (x.kf == y.kf && x.point < y.point); }
-#define MT_UP(dst, src, bytes)                                                                   \
-    do {                                                                                         \
-        if ((bytes) > 0) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, st)); \
-    } while (0)
-#define MT_DOWN(dst, src, bytes)                                                                 \
-    do {                                                                                         \
-        if ((bytes) > 0) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, st)); \
-    } while (0)
-
 // ---- the cores: device pointers in, launches on the stream, no wait (maptables_internal.h) ---------------------------------------
 // the flags, the three compactions, the merge
 int mt_apply_outliers_core(hipStream_t st, const MtOutliersDev& d) {
@@ -395,74 +357,49 @@ extern "C" int ptam_map_apply_outliers(ptam_ctx* ctx, int n_kf, int n_points, in
     ARG_TRY((n_meas == 0 || (meas && meas_out)) && (n_never == 0 || never) && (n_failure == 0 || failure) && (n_outliers == 0 || outliers) &&
             (n_points == 0 || bad));
     ARG_TRY((n_never + n_outliers == 0 || never_out) && (n_failure + n_outliers == 0 || failure_out));
-    ARG_TRY(mt_meas_valid(n_meas, meas, n_kf, n_points));
-    ARG_TRY(mt_sorted_in_range(n_never, never, n_kf, n_points));
-    ARG_TRY(mt_pairs_in_range(n_failure, failure, n_kf, n_points));
-    ptam_map_outliers_result r = {};
-    {
-        std::vector<uint8_t> named((size_t)n_meas, 0);
-        for (int i = 0; i < n_outliers; i++) {
-            const ptam_map_outlier& o = outliers[i];
-            ARG_TRY(o.action >= PTAM_MAP_OUT_POINT_BAD && o.action <= PTAM_MAP_OUT_NEVER_RETRY);
-            ARG_TRY(o.meas >= 0 && o.meas < n_meas && meas[o.meas].kf == o.kf && meas[o.meas].point == o.point);
-            ARG_TRY(!named[(size_t)o.meas]);
-            named[(size_t)o.meas] = 1;
-            if (o.action == PTAM_MAP_OUT_NEVER_RETRY) {
-                ptam_map_pair q;
-                q.kf = o.kf;
-                q.point = o.point;
-                ARG_TRY(!std::binary_search(never, never + n_never, q, mt_pair_less));   // :947-948: no pair is in both sets
-                r.n_never_added++;
-            } else if (o.action == PTAM_MAP_OUT_FAILURE_QUEUE)
-                r.n_failure_added++;
-            else
-                r.n_point_bad++;
-        }
-    }
-    r.n_meas_out = n_meas - r.n_failure_added - r.n_never_added;
-    r.n_never_out = n_never + r.n_never_added;
-    r.n_failure_out = n_failure + r.n_failure_added;
+    ARG_TRY(mc_meas_valid(n_meas, meas, n_kf, n_points));
+    ARG_TRY(mc_sorted_in_range(n_never, never, n_kf, n_points));
+    ARG_TRY(mc_pairs_in_range(n_failure, failure, n_kf, n_points));
+    ptam_map_outliers_result r;
+    ARG_TRY(mc_outliers_tally(n_outliers, outliers, n_meas, meas, n_never, never, n_failure, &r) < 0);
     HIP_TRY(hipSetDevice(ctx->device));
 
     // ---- device memory
     const size_t Mz = (size_t)n_meas, Vz = (size_t)n_never, Oz = (size_t)n_outliers, Nz = (size_t)n_points;
-    MtCarve c;
-    const size_t o_meas = c.take(Mz * sizeof(ptam_map_meas)), o_never = c.take(Vz * sizeof(ptam_map_pair)),
-                 o_outl = c.take(Oz * sizeof(ptam_map_outlier)), o_bad = c.take(Nz), o_flag = c.take(Mz), o_tot = c.take(3 * sizeof(int)),
-                 o_tiles = c.take((size_t)mt_tiles(std::max(n_meas, n_outliers)) * sizeof(int)), o_mo = c.take(Mz * sizeof(ptam_map_meas)),
-                 o_nn = c.take(Oz * sizeof(ptam_map_pair)), o_no = c.take((Vz + Oz) * sizeof(ptam_map_pair)), o_fo = c.take(Oz * sizeof(ptam_map_pair));
-    void* sc;
-    if (int rc = ctx_scratch(ctx, c.off, &sc)) return rc;
-    char* b = (char*)sc;
-    hipStream_t st = ctx->stream;
-    MT_UP(b + o_meas, meas, Mz * sizeof(ptam_map_meas));
-    MT_UP(b + o_never, never, Vz * sizeof(ptam_map_pair));
-    MT_UP(b + o_outl, outliers, Oz * sizeof(ptam_map_outlier));
-    MT_UP(b + o_bad, bad, Nz);
     MtOutliersDev d = {};
     d.n_meas = n_meas;
     d.n_never = n_never;
     d.n_outliers = n_outliers;
     d.n_never_out = r.n_never_out;
-    d.meas = (const ptam_map_meas*)(b + o_meas);
-    d.never = (const ptam_map_pair*)(b + o_never);
-    d.outliers = (const ptam_map_outlier*)(b + o_outl);
-    d.bad = (uint8_t*)(b + o_bad);
-    d.flag = (uint8_t*)(b + o_flag);
-    d.tot = (int*)(b + o_tot);
-    d.tiles = (int*)(b + o_tiles);
-    d.new_never = (ptam_map_pair*)(b + o_nn);
-    d.meas_out = (ptam_map_meas*)(b + o_mo);
-    d.never_out = (ptam_map_pair*)(b + o_no);
-    d.failure_new = (ptam_map_pair*)(b + o_fo);
-    if (int rc = mt_apply_outliers_core(st, d)) return rc;
+    ptam_map_meas* d_meas;
+    ptam_map_pair* d_never;
+    ptam_map_outlier* d_outl;
+    MapStage s(ctx);
+    STAGE_TRY(s.carve([&](Carver& c, Carver&) {
+        d.meas = d_meas = c.room<ptam_map_meas>(Mz);
+        d.never = d_never = c.room<ptam_map_pair>(Vz);
+        d.outliers = d_outl = c.room<ptam_map_outlier>(Oz);
+        d.bad = c.room<uint8_t>(Nz);
+        d.flag = c.room<uint8_t>(Mz);
+        d.tot = c.piece<int>(3);
+        d.tiles = c.room<int>((size_t)mt_tiles(std::max(n_meas, n_outliers)));
+        d.meas_out = c.room<ptam_map_meas>(Mz);
+        d.new_never = c.room<ptam_map_pair>(Oz);
+        d.never_out = c.room<ptam_map_pair>(Vz + Oz);
+        d.failure_new = c.room<ptam_map_pair>(Oz);
+    }));
+    STAGE_TRY(s.up(d_meas, meas, Mz * sizeof(ptam_map_meas)));
+    STAGE_TRY(s.up(d_never, never, Vz * sizeof(ptam_map_pair)));
+    STAGE_TRY(s.up(d_outl, outliers, Oz * sizeof(ptam_map_outlier)));
+    STAGE_TRY(s.up(d.bad, bad, Nz));
+    STAGE_TRY(mt_apply_outliers_core(s.st, d));
 
     // ---- down: every size is known from the outlier list
-    MT_DOWN(meas_out, b + o_mo, (size_t)r.n_meas_out * sizeof(ptam_map_meas));
-    MT_DOWN(never_out, b + o_no, (size_t)r.n_never_out * sizeof(ptam_map_pair));
-    MT_DOWN(failure_out + n_failure, b + o_fo, (size_t)r.n_failure_added * sizeof(ptam_map_pair));
-    MT_DOWN(bad, b + o_bad, Nz);
-    HIP_TRY(ptam_stream_wait(st));
+    STAGE_TRY(s.down(meas_out, d.meas_out, (size_t)r.n_meas_out * sizeof(ptam_map_meas)));
+    STAGE_TRY(s.down(never_out, d.never_out, (size_t)r.n_never_out * sizeof(ptam_map_pair)));
+    STAGE_TRY(s.down(failure_out + n_failure, d.failure_new, (size_t)r.n_failure_added * sizeof(ptam_map_pair)));
+    STAGE_TRY(s.down(bad, d.bad, Nz));
+    HIP_TRY(ptam_stream_wait(s.st));
     if (n_failure > 0) std::memcpy(failure_out, failure, (size_t)n_failure * sizeof(ptam_map_pair));   // the old queue never left the host
     *res = r;
     return PTAM_OK;
@@ -483,50 +420,15 @@ extern "C" int ptam_map_handle_bad_points(ptam_ctx* ctx, int n_kf, int n_points,
             (n_new == 0 || (new_queue && new_queue_out)) && (n_failure == 0 || (failure && failure_out)));
     for (int k = 0; k < n_columns; k++)
         ARG_TRY(columns[k].row_bytes > 0 && columns[k].row_bytes % 4 == 0 && (n_points == 0 || columns[k].data));
-    ARG_TRY(mt_meas_valid(n_meas, meas, n_kf, n_points));
-    ARG_TRY(mt_sorted_in_range(n_never, never, n_kf, n_points));
-    ARG_TRY(mt_pairs_in_range(n_failure, failure, n_kf, n_points));
-    {
-        std::vector<uint8_t> seen((size_t)n_points, 0);
-        for (int e = 0; e < n_new; e++) {
-            ARG_TRY(new_queue[e] >= 0 && new_queue[e] < n_points && !seen[(size_t)new_queue[e]]);
-            seen[(size_t)new_queue[e]] = 1;
-        }
-    }
+    ARG_TRY(mc_meas_valid(n_meas, meas, n_kf, n_points));
+    ARG_TRY(mc_sorted_in_range(n_never, never, n_kf, n_points));
+    ARG_TRY(mc_pairs_in_range(n_failure, failure, n_kf, n_points));
+    ARG_TRY(mc_queue_unique(n_new, new_queue, n_points));
     HIP_TRY(hipSetDevice(ctx->device));
 
     // ---- device memory
-    enum { T_KEPT = MT_T_KEPT, T_MEAS = MT_T_MEAS, T_NEVER = MT_T_NEVER, T_NEW = MT_T_NEW, T_FAIL = MT_T_FAIL, T_MARKED = MT_T_MARKED,
-           T_COUNT = MT_T_COUNT };
     const size_t Nz = (size_t)n_points, Mz = (size_t)n_meas, Vz = (size_t)n_never, Qz = (size_t)n_new, Fz = (size_t)n_failure;
     const int longest = std::max(std::max(n_points, n_meas), std::max(std::max(n_never, n_new), n_failure));
-    MtCarve c;
-    const size_t o_bad = c.take(bad ? Nz : 0), o_cnt_o = c.take(outlier_count ? Nz * 4 : 0), o_cnt_i = c.take(outlier_count ? Nz * 4 : 0),
-                 o_meas = c.take(Mz * sizeof(ptam_map_meas)), o_never = c.take(Vz * sizeof(ptam_map_pair)), o_new = c.take(Qz * 4),
-                 o_fail = c.take(Fz * sizeof(ptam_map_pair)), o_rem = c.take(Nz), o_tot = c.take(T_COUNT * sizeof(int)),
-                 o_tiles = c.take((size_t)mt_tiles(longest) * sizeof(int)), o_ni = c.take(Nz * 4), o_kept = c.take(Nz * 4),
-                 o_mo = c.take(Mz * sizeof(ptam_map_meas)), o_no = c.take(Vz * sizeof(ptam_map_pair)), o_qo = c.take(Qz * 4),
-                 o_fo = c.take(Fz * sizeof(ptam_map_pair));
-    size_t o_cin[PTAM_MAP_MAX_COLUMNS], o_cout[PTAM_MAP_MAX_COLUMNS];
-    for (int k = 0; k < n_columns; k++) {
-        o_cin[k] = c.take(Nz * (size_t)columns[k].row_bytes);
-        o_cout[k] = c.take(Nz * (size_t)columns[k].row_bytes);
-    }
-    void *sc, *hp;
-    if (int rc = ctx_scratch(ctx, c.off, &sc)) return rc;
-    if (int rc = ctx_pinned(ctx, 256, &hp)) return rc;
-    char* b = (char*)sc;
-    hipStream_t st = ctx->stream;
-    if (bad) MT_UP(b + o_bad, bad, Nz);
-    if (outlier_count) {
-        MT_UP(b + o_cnt_o, outlier_count, Nz * 4);
-        MT_UP(b + o_cnt_i, inlier_count, Nz * 4);
-    }
-    MT_UP(b + o_meas, meas, Mz * sizeof(ptam_map_meas));
-    MT_UP(b + o_never, never, Vz * sizeof(ptam_map_pair));
-    MT_UP(b + o_new, new_queue, Qz * 4);
-    MT_UP(b + o_fail, failure, Fz * sizeof(ptam_map_pair));
-    for (int k = 0; k < n_columns; k++) MT_UP(b + o_cin[k], columns[k].data, Nz * (size_t)columns[k].row_bytes);
     MtBadDev d = {};
     d.n_points = n_points;
     d.n_meas = n_meas;
@@ -534,48 +436,61 @@ extern "C" int ptam_map_handle_bad_points(ptam_ctx* ctx, int n_kf, int n_points,
     d.n_new = n_new;
     d.n_failure = n_failure;
     d.n_columns = n_columns;
-    d.bad = bad ? (const uint8_t*)(b + o_bad) : nullptr;
-    d.outlier_count = outlier_count ? (const int32_t*)(b + o_cnt_o) : nullptr;
-    d.inlier_count = outlier_count ? (const int32_t*)(b + o_cnt_i) : nullptr;
-    d.meas = (const ptam_map_meas*)(b + o_meas);
-    d.never = (const ptam_map_pair*)(b + o_never);
-    d.new_queue = (const int32_t*)(b + o_new);
-    d.failure = (const ptam_map_pair*)(b + o_fail);
-    d.removed = (uint8_t*)(b + o_rem);
-    d.tot = (int*)(b + o_tot);
-    d.tiles = (int*)(b + o_tiles);
-    d.new_index = (int32_t*)(b + o_ni);
-    d.kept = (int32_t*)(b + o_kept);
-    d.meas_out = (ptam_map_meas*)(b + o_mo);
-    d.never_out = (ptam_map_pair*)(b + o_no);
-    d.new_out = (int32_t*)(b + o_qo);
-    d.failure_out = (ptam_map_pair*)(b + o_fo);
-    for (int k = 0; k < n_columns; k++) {
-        d.col_in[k] = b + o_cin[k];
-        d.col_out[k] = b + o_cout[k];
-        d.col_dwords[k] = columns[k].row_bytes / 4;
+    uint8_t* d_bad;
+    int32_t *d_cnt_o, *d_cnt_i, *d_new;
+    ptam_map_meas* d_meas;
+    ptam_map_pair *d_never, *d_fail;
+    int* h_counts;
+    MapStage s(ctx);
+    STAGE_TRY(s.carve([&](Carver& c, Carver& pin) {
+        d_bad = c.room<uint8_t>(bad ? Nz : 0);
+        d_cnt_o = c.room<int32_t>(outlier_count ? Nz : 0);
+        d_cnt_i = c.room<int32_t>(outlier_count ? Nz : 0);
+        d.meas = d_meas = c.room<ptam_map_meas>(Mz);
+        d.never = d_never = c.room<ptam_map_pair>(Vz);
+        d.new_queue = d_new = c.room<int32_t>(Qz);
+        d.failure = d_fail = c.room<ptam_map_pair>(Fz);
+        d.removed = c.room<uint8_t>(Nz);
+        d.tot = c.piece<int>(MT_T_COUNT);
+        d.tiles = c.room<int>((size_t)mt_tiles(longest));
+        d.new_index = c.room<int32_t>(Nz);
+        d.kept = c.room<int32_t>(Nz);
+        d.meas_out = c.room<ptam_map_meas>(Mz);
+        d.never_out = c.room<ptam_map_pair>(Vz);
+        d.new_out = c.room<int32_t>(Qz);
+        d.failure_out = c.room<ptam_map_pair>(Fz);
+        for (int k = 0; k < n_columns; k++) {
+            d.col_in[k] = c.room<char>(Nz * (size_t)columns[k].row_bytes);
+            d.col_out[k] = c.room<char>(Nz * (size_t)columns[k].row_bytes);
+            d.col_dwords[k] = columns[k].row_bytes / 4;
+        }
+        h_counts = pin.piece<int>(MT_T_COUNT);
+    }));
+    d.bad = bad ? d_bad : nullptr;
+    d.outlier_count = outlier_count ? d_cnt_o : nullptr;
+    d.inlier_count = outlier_count ? d_cnt_i : nullptr;
+    if (bad) STAGE_TRY(s.up(d_bad, bad, Nz));
+    if (outlier_count) {
+        STAGE_TRY(s.up(d_cnt_o, outlier_count, Nz * 4));
+        STAGE_TRY(s.up(d_cnt_i, inlier_count, Nz * 4));
     }
-    if (int rc = mt_handle_bad_points_core(st, d)) return rc;
-    HIP_TRY(hipMemcpyAsync(hp, d.tot, T_COUNT * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ptam_stream_wait(st));   // the counts say how much of each table to fetch
-    const int* hc = (const int*)hp;
-    ptam_map_bad_points_result r = {};
-    r.n_marked = hc[T_MARKED];
-    r.n_kept = hc[T_KEPT];
-    r.n_removed = n_points - r.n_kept;
-    r.n_meas_out = hc[T_MEAS];
-    r.n_never_out = hc[T_NEVER];
-    r.n_new_out = hc[T_NEW];
-    r.n_new_dropped = n_new - r.n_new_out;
-    r.n_failure_out = hc[T_FAIL];
-    MT_DOWN(new_index, b + o_ni, Nz * 4);
-    MT_DOWN(kept, b + o_kept, (size_t)r.n_kept * 4);
-    MT_DOWN(meas_out, b + o_mo, (size_t)r.n_meas_out * sizeof(ptam_map_meas));
-    MT_DOWN(never_out, b + o_no, (size_t)r.n_never_out * sizeof(ptam_map_pair));
-    MT_DOWN(new_queue_out, b + o_qo, (size_t)r.n_new_out * 4);
-    MT_DOWN(failure_out, b + o_fo, (size_t)r.n_failure_out * sizeof(ptam_map_pair));
-    for (int k = 0; k < n_columns; k++) MT_DOWN(columns[k].data, b + o_cout[k], (size_t)r.n_kept * (size_t)columns[k].row_bytes);
-    HIP_TRY(ptam_stream_wait(st));
+    STAGE_TRY(s.up(d_meas, meas, Mz * sizeof(ptam_map_meas)));
+    STAGE_TRY(s.up(d_never, never, Vz * sizeof(ptam_map_pair)));
+    STAGE_TRY(s.up(d_new, new_queue, Qz * 4));
+    STAGE_TRY(s.up(d_fail, failure, Fz * sizeof(ptam_map_pair)));
+    for (int k = 0; k < n_columns; k++) STAGE_TRY(s.up(const_cast<void*>(d.col_in[k]), columns[k].data, Nz * (size_t)columns[k].row_bytes));
+    STAGE_TRY(mt_handle_bad_points_core(s.st, d));
+    STAGE_TRY(s.down(h_counts, d.tot, MT_T_COUNT * sizeof(int)));
+    HIP_TRY(ptam_stream_wait(s.st));   // the counts say how much of each table to fetch
+    const ptam_map_bad_points_result r = mt_bad_result(h_counts, n_points, n_new);
+    STAGE_TRY(s.down(new_index, d.new_index, Nz * 4));
+    STAGE_TRY(s.down(kept, d.kept, (size_t)r.n_kept * 4));
+    STAGE_TRY(s.down(meas_out, d.meas_out, (size_t)r.n_meas_out * sizeof(ptam_map_meas)));
+    STAGE_TRY(s.down(never_out, d.never_out, (size_t)r.n_never_out * sizeof(ptam_map_pair)));
+    STAGE_TRY(s.down(new_queue_out, d.new_out, (size_t)r.n_new_out * 4));
+    STAGE_TRY(s.down(failure_out, d.failure_out, (size_t)r.n_failure_out * sizeof(ptam_map_pair)));
+    for (int k = 0; k < n_columns; k++) STAGE_TRY(s.down(columns[k].data, d.col_out[k], (size_t)r.n_kept * (size_t)columns[k].row_bytes));
+    HIP_TRY(ptam_stream_wait(s.st));
     *res = r;
     return PTAM_OK;
 }
@@ -590,22 +505,14 @@ extern "C" int ptam_map_add_points(ptam_ctx* ctx, int n_kf, int n_points, int n_
     ARG_TRY((n_meas == 0 || meas) && (n_made == 0 || made) && (n_meas + n_made == 0 || meas_out));
     ARG_TRY(src_kf >= 0 && src_kf < n_kf && target_kf >= 0 && target_kf < n_kf && src_kf != target_kf);
     ARG_TRY(target_source >= PTAM_MAP_SRC_TRACKER && target_source <= PTAM_MAP_SRC_EPIPOLAR);
-    ARG_TRY(mt_meas_valid(n_meas, meas, n_kf, n_points));
+    ARG_TRY(mc_meas_valid(n_meas, meas, n_kf, n_points));
     for (int i = 0; i < n_made; i++) ARG_TRY(made[i].level >= 0 && made[i].level < PTAM_LEVELS);
     if (n_made == 0) {   // nothing to insert: the table is a copy
         if (n_meas > 0) std::memcpy(meas_out, meas, (size_t)n_meas * sizeof(ptam_map_meas));
         return PTAM_OK;
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    MtAdd p = {};
-    p.n_meas = n_meas;
-    p.n_made = n_made;
-    p.n_points = n_points;
-    p.kf_lo = std::min(src_kf, target_kf);
-    p.kf_hi = std::max(src_kf, target_kf);
-    p.src_is_lo = src_kf < target_kf;
-    p.src_kf = src_kf;
-    p.target_source = target_source;
+    MtAdd p = mt_add_head(src_kf, target_kf, target_source, n_meas, n_made, n_points);
     const auto run_end = [&](int kf) {   // the new indices exceed all old ones: the end of the keyframe's run
         return (int)(std::upper_bound(meas, meas + n_meas, kf, [](int k, const ptam_map_meas& m) { return k < m.kf; }) - meas);
     };
@@ -613,26 +520,27 @@ extern "C" int ptam_map_add_points(ptam_ctx* ctx, int n_kf, int n_points, int n_
     p.b = run_end(p.kf_hi);
 
     const size_t Mz = (size_t)n_meas, Az = (size_t)n_made;
-    MtCarve c;
-    const size_t o_meas = c.take(Mz * sizeof(ptam_map_meas)), o_made = c.take(Az * sizeof(ptam_new_map_point)),
-                 o_mo = c.take((Mz + 2 * Az) * sizeof(ptam_map_meas)), o_pts = c.take(points_out ? Az * sizeof(ptam_map_refind_point) : 0),
-                 o_src = c.take(sources_out ? Az * sizeof(ptam_map_point_source) : 0);
-    void* sc;
-    if (int rc = ctx_scratch(ctx, c.off, &sc)) return rc;
-    char* b = (char*)sc;
-    hipStream_t st = ctx->stream;
-    MT_UP(b + o_meas, meas, Mz * sizeof(ptam_map_meas));
-    MT_UP(b + o_made, made, Az * sizeof(ptam_new_map_point));
-    p.meas = (const ptam_map_meas*)(b + o_meas);
-    p.made = (const ptam_new_map_point*)(b + o_made);
-    p.out = (ptam_map_meas*)(b + o_mo);
-    p.points = points_out ? (ptam_map_refind_point*)(b + o_pts) : nullptr;
-    p.sources = sources_out ? (ptam_map_point_source*)(b + o_src) : nullptr;
-    if (int rc = mt_add_points_core(st, p)) return rc;
-    MT_DOWN(meas_out, b + o_mo, (Mz + 2 * Az) * sizeof(ptam_map_meas));
-    if (points_out) MT_DOWN(points_out, b + o_pts, Az * sizeof(ptam_map_refind_point));
-    if (sources_out) MT_DOWN(sources_out, b + o_src, Az * sizeof(ptam_map_point_source));
-    HIP_TRY(ptam_stream_wait(st));
+    ptam_map_meas* d_meas;
+    ptam_new_map_point* d_made;
+    ptam_map_refind_point* d_pts;
+    ptam_map_point_source* d_src;
+    MapStage s(ctx);
+    STAGE_TRY(s.carve([&](Carver& c, Carver&) {
+        p.meas = d_meas = c.room<ptam_map_meas>(Mz);
+        p.made = d_made = c.piece<ptam_new_map_point>(Az);
+        p.out = c.piece<ptam_map_meas>(Mz + 2 * Az);
+        d_pts = c.room<ptam_map_refind_point>(points_out ? Az : 0);
+        d_src = c.room<ptam_map_point_source>(sources_out ? Az : 0);
+    }));
+    p.points = points_out ? d_pts : nullptr;
+    p.sources = sources_out ? d_src : nullptr;
+    STAGE_TRY(s.up(d_meas, meas, Mz * sizeof(ptam_map_meas)));
+    STAGE_TRY(s.up(d_made, made, Az * sizeof(ptam_new_map_point)));
+    STAGE_TRY(mt_add_points_core(s.st, p));
+    STAGE_TRY(s.down(meas_out, p.out, (Mz + 2 * Az) * sizeof(ptam_map_meas)));
+    if (points_out) STAGE_TRY(s.down(points_out, d_pts, Az * sizeof(ptam_map_refind_point)));
+    if (sources_out) STAGE_TRY(s.down(sources_out, d_src, Az * sizeof(ptam_map_point_source)));
+    HIP_TRY(ptam_stream_wait(s.st));
     return PTAM_OK;
 }
 

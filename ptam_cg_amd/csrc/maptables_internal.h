@@ -1,8 +1,15 @@
-// maptables_internal.h — the device cores of the map-table edits (maptables.hip).  Every pointer is a device pointer; a core only
-// enqueues on the stream.  The host-table entries ptam_map_* wrap them between an upload into the context's scratch and a download,
-// the resident forms ptam_rmap_* (maprmap.hip) hand them the handle's own buffers.
+// maptables_internal.h — the device cores of the map calls: the table edits (mt_*_core, maptables.hip), the re-find (mr_core,
+// maprefind.hip) and the bundle (mba_core, mapba.hip); the scene depth and the global transform are declared with the stage
+// (map_stage.h).  Every table pointer is a device pointer; what is host by nature (the keyframe handles, the pose / fixed mirror) says
+// so.  The host-table entries ptam_map_* check their tables (map_tables_check.h), stage them up into the call's one scratch block
+// beside the core's work (a layout function over a Carver, run twice), run the core and stage the results down; the resident forms
+// ptam_rmap_* (maprmap*.hip) hand the cores the handle's own buffers.
 #pragma once
 #include "common.h"
+#include "map_stage.h"
+#include "map_tables_check.h"
+#include "maprefind_plan.h"
+#include "refind_internal.h"   // RpDev, RpPair, KfLevels: the re-find core's work
 
 enum { MT_TILE = 1024, MT_SCAN_CHUNK = 1024 };
 // what a gate word holds while no refusal has been decided (a memset of 0x7f bytes); a lower value is the offending row
@@ -52,6 +59,19 @@ struct MtBadDev {
     int col_dwords[PTAM_MAP_MAX_COLUMNS];
 };
 int mt_handle_bad_points_core(hipStream_t st, const MtBadDev& d);
+// the call's result from the core's counts as they came down
+static inline ptam_map_bad_points_result mt_bad_result(const int* counts, int n_points, int n_new) {
+    ptam_map_bad_points_result r = {};
+    r.n_marked = counts[MT_T_MARKED];
+    r.n_kept = counts[MT_T_KEPT];
+    r.n_removed = n_points - r.n_kept;
+    r.n_meas_out = counts[MT_T_MEAS];
+    r.n_never_out = counts[MT_T_NEVER];
+    r.n_new_out = counts[MT_T_NEW];
+    r.n_new_dropped = n_new - r.n_new_out;
+    r.n_failure_out = counts[MT_T_FAIL];
+    return r;
+}
 
 // ---- the table side of AddPointEpipolar (:670-685) and of InitFromStereo's point loop (:352-362)
 struct MtAdd {
@@ -73,49 +93,73 @@ struct MtAdd {
     int32_t* new_queue;
 };
 int mt_add_points_core(hipStream_t st, const MtAdd& p);
+// what the keyframes and the counts decide of an MtAdd; a = b = -1 (the kernel searches) until the caller knows better
+static inline MtAdd mt_add_head(int src_kf, int target_kf, int target_source, int n_meas, int n_made, int n_points) {
+    MtAdd p = {};
+    p.n_meas = n_meas;
+    p.n_made = n_made;
+    p.n_points = n_points;
+    p.a = p.b = -1;
+    p.kf_lo = src_kf < target_kf ? src_kf : target_kf;
+    p.kf_hi = src_kf < target_kf ? target_kf : src_kf;
+    p.src_is_lo = src_kf < target_kf;
+    p.src_kf = src_kf;
+    p.target_source = target_source;
+    return p;
+}
 
-// ---- MapMaker::ReFind* (:1028-1081), maprefind.hip: ptam_map_refind behind its pointer checks.  Host tables (h_: checked on the host,
-//      uploaded, the merged tables come down) or resident ones (d_: valid by the handle's invariant; the merged tables are written
-//      into d_meas_merged / d_never_merged, room for n_meas / n_never + the call's pair count, and nothing of them comes down).
+// ---- MapMaker::ReFind* (:1028-1081), maprefind.hip: the re-find on tables in device memory.  The merged tables are written into
+//      d_meas_merged / d_never_merged (each nullable; room for n_meas / n_never + the plan's pair count).
 struct MrTables {
     int n_kf, n_points, n_meas, n_never;
-    const ptam_kf* const* kfs;                  // host, always
-    const double* h_poses;
-    const ptam_map_refind_point* h_points;
-    const ptam_map_meas* h_meas;
-    const ptam_map_pair* h_never;
+    const ptam_kf* const* kfs;                  // host by nature: the level records are read from the handles
     const double* d_poses;
     const ptam_map_refind_point* d_points;
     const ptam_map_meas* d_meas;
     const ptam_map_pair* d_never;
     ptam_map_meas* d_meas_merged;
     ptam_map_pair* d_never_merged;
-    const uint8_t* work_bad;                    // resident NEW_POINTS: bBad of each work entry's point (host)
 };
-// found_out / found_subpix / never_out may be null with resident tables.  *merged_written (nullable): the merged tables were built
-// (not when the call has no pair to visit).  traffic (nullable): bytes this call moved up / down over the host link.
-int mr_run(ptam_ctx* ctx, ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, const MrTables& t, int n_work, const void* work,
-           const volatile unsigned char* stop_flag, ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix,
-           ptam_map_pair* never_out, int out_cap, ptam_map_meas* meas_merged, ptam_map_pair* never_merged, int* merged_written,
-           unsigned long long traffic[2]);
+struct MrWork {   // the core's pieces of the call's stage: mr_layout
+    KfLevels* Ls;
+    int *w0, *w1, *cnt, *slot, *ord_f, *ord_n, *h_cnt;
+    ptam_map_meas* found;
+    int32_t* subpix;
+    ptam_map_pair* nev;
+    RpPair* pairs;
+    RpDev chain;
+};
+// what every form of the call asks of its arguments before the plan
+int mr_check_call(ptam_ctx* ctx, const ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, int n_kf, const ptam_kf* const* kfs);
+void mr_layout(Carver& c, Carver& pin, int n_kf, const MrPlan& plan, bool merged, MrWork& w);   // merged: a merged table is asked for
+// plan.pairs > 0.  Uploads the level records and the work lists, runs the passes, orders and merges, waits for the counts and
+// queues the call's lists to come down (found_out / found_subpix / never_out nullable together).  The call's last wait is the
+// caller's, behind whatever else it brings down.
+int mr_core(MapStage& s, ptam_refinder* finder, const MrTables& t, const MrPlan& plan, const MrWork& w, const volatile unsigned char* stop_flag,
+            ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix, ptam_map_pair* never_out);
 
-// ---- MapMaker::BundleAdjust (:768-933), mapba.hip: ptam_map_bundle_adjust behind its argument checks.  The tables of one call are
-//      on the host (they go up into the scratch, the adjusted poses and points come down) or resident (the d_ pointers; adjusted in
-//      place, the poses come down into the mirror).  The O(K) camera marshalling reads h_poses / h_fixed either way.
+// ---- MapMaker::BundleAdjust (:768-933), mapba.hip: the bundle on tables in device memory, adjusted in place.
 struct MbaTables {
     int K, N, M;
-    const double* h_poses;              // host: the caller's array or the resident map's mirror
+    const double* h_poses;              // host by nature: the pose / fixed mirror the O(K) camera marshalling reads
     const uint8_t* h_fixed;
-    const double* h_points3;            // host tables: null with resident ones
-    const ptam_map_meas* h_meas;
-    double* d_poses;                    // resident tables: all null with host ones
+    double* d_poses;
     const uint8_t* d_fixed;
     double* d_points3;
     const ptam_map_meas* d_meas;
-    ptam_map_refind_point* d_points;    // resident, nullable: pv.world follows points3 after an accepted bundle
-    double* poses_out;                  // host: where the poses come down after an accepted bundle
-    double* points3_out;                // host, nullable: the points
+    ptam_map_refind_point* d_points;    // nullable: pv.world follows points3 after an accepted bundle
 };
-// traffic (nullable): the bytes this layer moved up / down over the host link (the bundle's own result words apart)
-int mba_run(ptam_ctx* ctx, const ptam_ba_opts* opts, int mode, const MbaTables& t, const volatile unsigned char* abort_flag,
-            ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids, unsigned long long traffic[2]);
+struct MbaWork {   // the core's pieces of the call's stage: mba_layout
+    char* cleared;                      // [header | role | point marks | rows per point], zeroed as one
+    size_t clear_bytes;
+    int *role, *pt_mark, *pt_rows, *cam_id, *cam_kf, *pt_id, *pt_of, *blk, *sel_row, *ord, *orow, *opt, *first;
+    double* pts_sel;
+    ptam_map_outlier* out;
+    char* h_sel;                        // pinned: the header and the camera list of the selection's wait
+};
+void mba_layout(Carver& c, Carver& pin, int K, int N, int M, MbaWork& w);
+// Selection, its one wait, the camera marshalling, ingest and Compute(), the scatter and the outlier routing.  The outliers and the
+// point ids are queued to come down; the call's last wait is the caller's, behind whatever it brings down of the adjusted tables
+// (res->accepted > 0).
+int mba_core(MapStage& s, const ptam_ba_opts* opts, int mode, const MbaTables& t, const MbaWork& w, const volatile unsigned char* abort_flag,
+             ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids);

@@ -7,6 +7,7 @@ import pytest
 from ptam_cg_amd import _abi, host, synth
 from tests import map_ba_ref as R
 from tests import map_edit_ref as E
+from tests import map_refind_ref as F
 from tests import plane_ref as PR
 
 pytestmark = pytest.mark.gpu
@@ -611,3 +612,68 @@ def test_a_sequence_of_edits_stays_on_the_device(ctx, case):
     check_invariants(tab)
     assert depth.tobytes() == host.map_scene_depth(ctx, h["poses"], h["points3"], h["meas"]).tobytes()
     m.close()
+
+
+# ---- 9. empty tables: every zero-sized piece of a call's layout ------------------------------------------------------------------
+def test_empty_tables_in_both_forms(ctx):
+    """2 keyframes, 3 points and no row, never pair, queue entry or failure pair: HandleBadPoints, two new points and a KEYFRAME
+    re-find, each on the host tables and on a freshly uploaded resident map, against tests/map_edit_ref.py / tests/map_refind_ref.py
+    and against each other."""
+    scene = F.make_scene(ctx, n_kf=2)
+    K, N = 2, 3
+    pts = scene["points"][:N].copy()
+    src = np.zeros(N, host.MAP_POINT_SOURCE_DT)
+    src["src_kf"] = pts["src_kf"]
+    for f in ("center_nc", "one_right_nc", "one_down_nc"):
+        src[f] = (0.1, -0.2, 1.0)
+    h = dict(poses=np.array(scene["poses"]), fixed=np.array([1, 0], np.uint8), points3=np.ascontiguousarray(pts["pv"]["world"]), points=pts,
+             sources=src, bad=np.zeros(N, np.uint8), meas=np.zeros(0, E.MEAS_DT), never=np.zeros(0, E.PAIR_DT), new_queue=np.zeros(0, np.int32),
+             failure=np.zeros(0, E.PAIR_DT), outlier_count=np.zeros(N, np.int32), inlier_count=np.zeros(N, np.int32))
+
+    def fresh():
+        m = host.ResidentMap(ctx)
+        m.upload(kfs=scene["kfs"], **{k: h[k] for k in UPLOAD_KEYS})
+        return m
+    # HandleBadPoints: nothing is bad, nothing moves
+    want, r = ref_handle_bad_points(h)
+    cols = [h[k] for k in ("points3", "points", "sources", "outlier_count", "inlier_count")]
+    got = host.map_handle_bad_points(ctx, K, N, h["meas"], h["never"], h["bad"], h["outlier_count"], h["inlier_count"], h["new_queue"], h["failure"], cols)
+    E.assert_same(got, r, E.BAD_COUNTS, ("new_index", "kept", "meas", "never", "new_queue", "failure"))
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(got["columns"], r["columns"]))
+    m = fresh()
+    E.assert_same(m.handle_bad_points(kept=True, new_index=True), r, E.BAD_COUNTS, ("kept", "new_index"))
+    assert r["n_kept"] == N and r["n_meas_out"] == 0
+    tab = m.tables()
+    same_tables(tab, tables_of(want))
+    check_invariants(tab)
+    m.close()
+    # two new points
+    made = E.make_made(3, 2)
+    ref = E.np_add_points(K, N, h["meas"], 1, 0, made)
+    E.assert_same(host.map_add_points(ctx, K, N, h["meas"], 1, 0, made), ref, (), ("meas", "points", "sources", "new_queue"))
+    m = fresh()
+    m.add_points(1, 0, made)
+    tab = m.tables()
+    same_tables(tab, tables_of(ref_add_points(h, 1, 0, made)))
+    assert tab["meas"].tobytes() == ref["meas"].tobytes() and len(ref["meas"]) == 4
+    check_invariants(tab)
+    m.close()
+    # a KEYFRAME re-find: three pairs, the merged tables are the found rows and the new never pairs alone
+    work = np.array([0], np.int32)
+    rf = [host.ReFinder(ctx) for _ in range(3)]
+    ref = F.compose(ctx, rf[0], _abi.MAP_REFIND_KEYFRAME, scene["kfs"], h["poses"], h["points"], h["meas"], h["never"], work)
+    got = host.map_refind(ctx, rf[1], _abi.MAP_REFIND_KEYFRAME, scene["kfs"], h["poses"], h["points"], h["meas"], h["never"], work)
+    m = fresh()
+    res = m.refind(rf[2], _abi.MAP_REFIND_KEYFRAME, work)
+    lists = ("found", "found_subpix", "never")
+    assert ref["n_pairs"] == N and ref["n_skipped"] == 0 and ref["n_found"] + ref["n_never"] == N
+    E.assert_same(got, ref, F.COUNTS, lists + ("meas_merged", "never_merged"))
+    E.assert_same(res, ref, F.COUNTS, lists)
+    tab = m.tables()
+    same_tables(tab, tables_of(dict(h, meas=ref["meas_merged"], never=ref["never_merged"])))
+    check_invariants(tab)
+    m.close()
+    for f in rf:
+        f.close()
+    scene["close"]()
+

@@ -194,6 +194,35 @@ def test_global_transform_matches_reference(dev, n, n_kf):
     m.close()
 
 
+def test_global_transform_on_a_fresh_context_grows_the_scratch_once(hip):
+    """a context whose scratch has never been asked for: the aligner's record and the packed rows of the first call are one request.
+    2 keyframes x 300 points; bit for bit the host-table form on a second context; the traffic bound of the test above."""
+    n, n_kf = 300, 2
+    points, poses, sources, meas, _ = PR.make_map(n, 7, n_kf)
+    rng = np.random.default_rng(n)
+    se3 = PR._small_pose(rng, 0.4)
+    right, down = PR.pixel_vectors(poses, points, sources)
+    pts = host.map_refind_points(points, right, down, sources["src_kf"], rng.integers(0, 4, n), rng.integers(0, 400, (n, 2)))
+    h = dict(poses=np.array(poses), fixed=np.zeros(n_kf, np.uint8), points3=np.array(points), points=pts, sources=np.array(sources),
+             bad=np.zeros(n, np.uint8), meas=np.array(meas), never=np.zeros(0, E.PAIR_DT), new_queue=np.zeros(0, np.int32), failure=np.zeros(0, E.PAIR_DT),
+             outlier_count=np.zeros(n, np.int32), inlier_count=np.zeros(n, np.int32))
+    fresh, second = host.Context(lib=hip), host.Context(lib=hip)
+    m = host.ResidentMap(fresh)
+    m.upload(**{k: h[k] for k in UPLOAD_KEYS})
+    up0, down0 = m.traffic()
+    rows = m.apply_global_transform(se3, rows=True)                                # at once: nothing has grown the scratch for it
+    up, down_ = m.traffic()
+    assert up - up0 <= 256 and down_ - down0 <= 96 * n_kf + rows.nbytes
+    tab = m.tables()
+    check_invariants(tab)
+    poses_t, points_t, pvs_t = host.map_apply_global_transform(second, se3, poses, points, sources)
+    assert tab["poses"].tobytes() == poses_t.tobytes() and tab["points3"].tobytes() == points_t.tobytes()
+    assert rows.tobytes() == pvs_t.tobytes() and np.ascontiguousarray(tab["points"]["pv"]).tobytes() == pvs_t.tobytes()
+    m.close()
+    fresh.close()
+    second.close()
+
+
 # ---- 7. / 8. one whole iteration, the tables never downloaded in between, and what crossed the host link ------------------------------
 def test_one_whole_iteration_stays_on_the_device(dev):
     """bundle RECENT, its outliers, re-find the new points, bundle ALL, its outliers, re-find the failure queue, HandleBadPoints, a
