@@ -1436,6 +1436,90 @@ typedef struct {
 int ptam_rmap_insert_keyframe(ptam_rmap*, ptam_refinder*, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows,
                               const ptam_map_kf_row* rows, const ptam_rmap_insert_opts*, ptam_rmap_insert_result*);
 
+/* ---- The first map, made in the resident map: MapMaker::InitFromStereo (src/MapMaker.cc:268-405) as ONE call ----------------------
+ *      first / second: the caller's clones of the two keyframes (*pkFirst = kF, :299-302); the map keeps them as the handles of
+ *      keyframes 0 and 1, and the call runs ptam_make_keyframe_rest on whichever lacks it (:371-372).  trails != NULL: the live
+ *      list is read where it lies on the device, n_matches / matches are ignored.  trails == NULL: matches (host, n_matches rows of
+ *      16 bytes) is the reference's vTrailMatches.
+ *      The stages, each enqueued on the handle's context behind the one before it:
+ *        (1) :272-287  the match table and HomographyInit::Compute: the kernels of ptam_trails_homography.  Not OK: NO_HOMOGRAPHY.
+ *        (2) :290-297  on the host: the baseline test (ZERO_BASELINE), t *= wiggle_scale / |t|.
+ *        (3) :299-367  the point loop (the kernel of ptam_init_points_from_trails) on the device list; the made records compacted in
+ *                      match order on the device (tile counts, scan, scatter: no atomic decides a place) and added with
+ *                      src_kf = 0, target_kf = 1, PTAM_MAP_SRC_TRAIL as ptam_rmap_add_points adds them.  Fewer than 3: TOO_FEW_POINTS.
+ *        (4) :374-375  first_bundles x (ptam_rmap_bundle_adjust(ALL), ptam_rmap_apply_outliers).
+ *        (5) :378-380  ptam_rmap_scene_depth; keyframe 1's mean and sigma become the epipolar options' depth.
+ *        (6) :382-385  steps (d)-(g) of ptam_rmap_insert_keyframe for kSrc = keyframe 1 (its run is the table's tail), kTarget = 0.
+ *        (7) :387-394  stage (4)'s step until the bundle reports convergence; *stop_flag (nullable) is the bundle's abort flag and is
+ *                      read after each bundle: STOPPED.  max_bundles > 0: STOPPED when that many bundles of this loop have not converged.
+ *        (8) :397      ptam_rmap_align_to_plane.
+ *      TRANSACTION.  The call replaces the whole map as ptam_rmap_upload does (new serials, a new keyframe epoch, first / second the
+ *      only handles).  NO_HOMOGRAPHY, ZERO_BASELINE, TOO_FEW_POINTS and every PTAM_E_ARG / PTAM_E_STATE refusal leave the previous
+ *      map exactly as it was: stages (1)-(3) work in the context's scratch until stage (3)'s count is known.  STOPPED leaves the
+ *      handle empty (the reference's Reset() after `return false`).  The outcomes are result->status; the return value is PTAM_OK.
+ *      REFUSALS, decided before anything is enqueued, the result struct untouched.  PTAM_E_ARG: a null handle, keyframe, options or
+ *      result; trails of another context or image size than the map's; keyframes of another device or size; fewer than 4 matches
+ *      (or trails == NULL with matches == NULL); the option refusals of ptam_trails_homography, ptam_add_map_points_epipolar's level
+ *      list and ptam_calc_plane_aligner; wiggle_scale <= 0, subpix_max_its < 1, first_bundles < 0, max_bundles < 0; plane.samples
+ *      (the point count is not known to the caller: a seed is).  PTAM_E_STATE: trails not started.
+ *      HOST WAITS and the decision each serves: (1) stage 1's result — NO_HOMOGRAPHY, the baseline, the scaling; (2) stage 3's
+ *      counts — TOO_FEW_POINTS, the rows to make room for; (3) the add's wait, after which the counts move; (4) per bundle, the
+ *      selection's and Compute()'s waits of ptam_rmap_bundle_adjust and, with outliers, the wait of ptam_rmap_apply_outliers —
+ *      converged, the outlier list, the stop flag; (5) the two depth rows — the epipolar depth range; (6) the epipolar header — the
+ *      made count, then the add's wait; (7) the plane record and the poses — the status, the tracker's pose.
+ *      ptam_rmap_traffic counts, for the call: up, 16 n_matches with trails == NULL, 16 x trials for stage 1's samples (n_matches >= 10),
+ *      192 + 2 for the two poses and flags, per bundle 2 x 97 and 16 per outlier, the plane call's bytes (below); down, 256 for stage 1's
+ *      result, PTAM_RMAP_WORD_BYTES for stage 3's counts, per bundle 32 + 4 x 2, 192 when accepted, 16 per outlier and, with outliers,
+ *      PTAM_RMAP_WORD_BYTES, 2 sizeof(ptam_scene_depth), 16 + 4 sizeof(ptam_epipolar_level_stats), the plane call's bytes.  With
+ *      trails != NULL nothing proportional to the matches, the points or the measurement table crosses in either direction. */
+enum { PTAM_INIT_MAP_OK = 0, PTAM_INIT_MAP_NO_HOMOGRAPHY = 1, PTAM_INIT_MAP_ZERO_BASELINE = 2, PTAM_INIT_MAP_TOO_FEW_POINTS = 3,
+       PTAM_INIT_MAP_STOPPED = 4 };
+typedef struct {
+    ptam_homography_opts homography;    /* 5.0 / 300 / seed or samples */
+    double wiggle_scale;                /* MapMaker.WiggleScale, 0.1 (:34) */
+    int32_t subpix_max_its;             /* 10 (:333) */
+    int32_t first_bundles;              /* 5 (:374) */
+    int32_t max_bundles;                /* 0: the reference's unbounded while (:390-394) */
+    int32_t pad_;
+    ptam_ba_opts ba;
+    ptam_epipolar_opts epipolar;        /* levels {0,3,1,2} (:382-385); depth_mean / depth_sigma are ignored (stage 5 gives them) */
+    ptam_plane_opts plane;
+} ptam_rmap_init_opts;
+typedef struct {
+    int32_t status;                     /* PTAM_INIT_MAP_* */
+    int32_t n_matches;
+    ptam_homography_info homography;
+    double baseline;                    /* dTransMagn (:290) */
+    int32_t n_made, n_subpix_failed, n_behind_camera, n_template_bad;   /* stage 3, by PTAM_INIT_* status */
+    int32_t n_bundles, n_accepted, n_outliers, n_outlier_bundles;       /* over stages 4 and 7; the bundles that had outliers */
+    int32_t converged, pad_;                                            /* the last bundle's flag */
+    ptam_scene_depth depth[2];
+    double wiggle_scale_depth_normalized;   /* mdWiggleScaleDepthNormalized (:380) */
+    int32_t first_epipolar_point, n_epipolar;
+    ptam_epipolar_level_stats levels[4];
+    ptam_plane_info plane;
+    double se3_aligner[12];
+    double tracker_pose[12];            /* se3TrackerPose = pkSecond->se3CfromW (:400) */
+    ptam_rmap_counts_t counts;          /* the map as the call leaves it */
+} ptam_rmap_init_result;
+/* PTAM_E_ARG: a null pointer */
+int ptam_rmap_init_opts_default(ptam_rmap_init_opts*);
+int ptam_rmap_init_from_stereo(ptam_rmap*, const ptam_kf* first, ptam_kf* second, ptam_trails* trails, int n_matches,
+                               const ptam_trail* matches, const ptam_rmap_init_opts*, const volatile unsigned char* stop_flag,
+                               ptam_rmap_init_result*);
+/* ptam_map_align_to_plane on the resident tables (the re-anchoring of a running session, and stage 8 above): plane_score_kernel /
+ * plane_finish_kernel on the resident points, the apply kernel reading the aligner from device memory.  The same kernels and bits
+ * as ptam_map_align_to_plane, and every info->status with that call's meaning: OK, the poses go into the second buffer (and the
+ * mirror) and the points move in place; TOO_FEW and DEGENERATE, poses and points stay.  In every case the point rows' pixel vectors
+ * end as RefreshPixelVectors against the final poses leaves them (DEGENERATE: by a second launch that moves nothing).
+ * out_rows (nullable, n_points ptam_pvs_point): the rows for ptam_tracker_set_map.  opts->samples as ptam_calc_plane_aligner.
+ * An empty map: PTAM_PLANE_TOO_FEW, the identity, nothing enqueued.
+ * Moves 12 x trials bytes up (n_points >= 10) and 256 more when DEGENERATE; 256 (the info and the aligner), 96 n_kf and out_rows down. */
+int ptam_rmap_align_to_plane(ptam_rmap*, const ptam_plane_opts*, double se3_aligner[12], ptam_plane_info*, ptam_pvs_point* out_rows);
+/* MapMaker::Reset (src/MapMaker.cc:37-43) for the tables: all counts 0, no keyframe handles, a new keyframe epoch.  The capacities,
+ * the serial counter and the traffic sums stay.  Moves nothing. */
+int ptam_rmap_clear(ptam_rmap*);
+
 /* ---- The resident map published to the tracker on the device --------------------------------------------------------------------
  *      Replaces the one table-sized trip left between the two threads: ptam_rmap_download of the point rows and `kept`, the host
  *      loop that composes prev_index, ptam_tracker_update_map's upload.

@@ -345,6 +345,7 @@ public:
         se3SecondFromFirst = SE3::from12(p);
         return true;
     }
+    ptam_trails* handle() const { return h_; }
 
 private:
     ptam_trails* h_ = nullptr;
@@ -1405,6 +1406,42 @@ public:
               "ptam_rmap_insert_keyframe_report");
         return r;
     }
+    // MapMaker::InitFromStereo   src/MapMaker.cc:268-405 as one call: kF / kS the caller's clones of the two keyframes (they become the
+    // map's keyframes 0 and 1 and must outlive it), the live trails read on the device.  Returns false where the reference does (no
+    // homography, zero baseline, too few points: the previous map stays; stopped: the map is empty); LastInit() says which.
+    using InitOpts = ptam_rmap_init_opts;
+    static InitOpts InitOptsDefault() {
+        InitOpts o;
+        ptam_rmap_init_opts_default(&o);
+        return o;
+    }
+    bool InitFromStereo(KeyFrame& kF, KeyFrame& kS, TrailTracker& trails, SE3& se3TrackerPose, const InitOpts& opts,
+                        const volatile bool* stop = nullptr) {
+        check(ptam_rmap_init_from_stereo(h_, kF.handle(), kS.handle(), trails.handle(), 0, nullptr, &opts,
+                                         reinterpret_cast<const volatile unsigned char*>(stop), &init_),
+              "ptam_rmap_init_from_stereo");
+        return InitDone(kF, kS, se3TrackerPose);
+    }
+    // ... from the reference's vTrailMatches argument
+    bool InitFromStereo(KeyFrame& kF, KeyFrame& kS, const std::vector<ptam_trail>& vTrailMatches, SE3& se3TrackerPose, const InitOpts& opts,
+                        const volatile bool* stop = nullptr) {
+        check(ptam_rmap_init_from_stereo(h_, kF.handle(), kS.handle(), nullptr, (int)vTrailMatches.size(), vTrailMatches.data(), &opts,
+                                         reinterpret_cast<const volatile unsigned char*>(stop), &init_),
+              "ptam_rmap_init_from_stereo");
+        return InitDone(kF, kS, se3TrackerPose);
+    }
+    const ptam_rmap_init_result& LastInit() const { return init_; }
+    // ApplyGlobalTransformationToMap(CalcPlaneAligner())   src/MapMaker.cc:397 on the resident tables; pvRows: the tracker's rows
+    PlaneAligner AlignToPlane(const ptam_plane_opts* opts = nullptr, std::vector<ptam_pvs_point>* pvRows = nullptr) {
+        const ptam_plane_opts o = PlaneOptsOrDefault(opts);
+        PlaneAligner a;
+        double p[12];
+        if (pvRows) pvRows->resize((size_t)Counts().n_points);
+        check(ptam_rmap_align_to_plane(h_, &o, p, &a.info, pvRows ? pvRows->data() : nullptr), "ptam_rmap_align_to_plane");
+        a.se3 = SE3::from12(p);
+        return a;
+    }
+    void Clear() { check(ptam_rmap_clear(h_), "ptam_rmap_clear"); }   // MapMaker::Reset
     // The map as it stands into the snapshot, as its next generation (the mapmaker's thread): after HandleBadPoints, InsertKeyFrame and
     // every accepted bundle.  vKept no longer has to come down for the tracker.  The keyframes need handles (Upload / AddKeyFrame).
     ptam_map_publish_result Publish(MapSnapshot& snapshot) {
@@ -1428,7 +1465,14 @@ public:
     ptam_rmap* handle() const { return h_; }
 
 private:
+    bool InitDone(KeyFrame& kF, KeyFrame& kS, SE3& se3TrackerPose) {
+        if (init_.status != PTAM_INIT_MAP_OK) return false;
+        kF.se3CfromW = SE3::Identity();
+        kS.se3CfromW = se3TrackerPose = SE3::from12(init_.tracker_pose);
+        return true;
+    }
     ptam_rmap* h_ = nullptr;
+    ptam_rmap_init_result init_{};
 };
 
 // class Bundle (include/Bundle.h:106-152)

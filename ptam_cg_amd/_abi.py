@@ -255,6 +255,25 @@ class RmapInsertResult(C.Structure):
                 ("first_point", C.c_int32), ("n_made", C.c_int32), ("levels", EpipolarLevelStats * 4)]
 
 
+INIT_MAP_OK, INIT_MAP_NO_HOMOGRAPHY, INIT_MAP_ZERO_BASELINE, INIT_MAP_TOO_FEW_POINTS, INIT_MAP_STOPPED = range(5)
+
+
+class RmapInitOpts(C.Structure):
+    """ptam_rmap_init_opts (MapMaker::InitFromStereo, src/MapMaker.cc:268-405)"""
+    _fields_ = [("homography", HomographyOpts), ("wiggle_scale", C.c_double), ("subpix_max_its", C.c_int32), ("first_bundles", C.c_int32),
+                ("max_bundles", C.c_int32), ("pad_", C.c_int32), ("ba", BaOpts), ("epipolar", EpipolarOpts), ("plane", PlaneOpts)]
+
+
+class RmapInitResult(C.Structure):
+    """ptam_rmap_init_result"""
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("homography", HomographyInfo), ("baseline", C.c_double),
+                ("n_made", C.c_int32), ("n_subpix_failed", C.c_int32), ("n_behind_camera", C.c_int32), ("n_template_bad", C.c_int32),
+                ("n_bundles", C.c_int32), ("n_accepted", C.c_int32), ("n_outliers", C.c_int32), ("n_outlier_bundles", C.c_int32),
+                ("converged", C.c_int32), ("pad_", C.c_int32), ("depth", SceneDepth * 2), ("wiggle_scale_depth_normalized", C.c_double),
+                ("first_epipolar_point", C.c_int32), ("n_epipolar", C.c_int32), ("levels", EpipolarLevelStats * 4), ("plane", PlaneInfo),
+                ("se3_aligner", C.c_double * 12), ("tracker_pose", C.c_double * 12), ("counts", RmapCounts)]
+
+
 class MapPublishResult(C.Structure):
     """ptam_map_publish_result"""
     _fields_ = [("generation", C.c_int64), ("map_id", C.c_int64), ("n_points", C.c_int32), ("n_kf", C.c_int32), ("grew", C.c_int32),
@@ -519,6 +538,10 @@ PROTOTYPES = {
     "rmap_scene_depth": (_i, [_vp, _vp]),
     "rmap_closest_keyframes": (_i, [_vp, _i, _i, _vp, _pd, C.POINTER(C.c_int32)]),
     "rmap_insert_keyframe": (_i, [_vp, _vp, _vp, _pd, _i, _i, _vp, C.POINTER(RmapInsertOpts), C.POINTER(RmapInsertResult)]),
+    "rmap_init_opts_default": (_i, [C.POINTER(RmapInitOpts)]),
+    "rmap_init_from_stereo": (_i, [_vp, _vp, _vp, _vp, _i, _vp, C.POINTER(RmapInitOpts), _vp, C.POINTER(RmapInitResult)]),
+    "rmap_align_to_plane": (_i, [_vp, C.POINTER(PlaneOpts), _pd, C.POINTER(PlaneInfo), _vp]),
+    "rmap_clear": (_i, [_vp]),
     "rmap_publish": (_i, [_vp, _vp, C.POINTER(MapPublishResult)]),
     "rmap_point_serials": (_i, [_vp, _i, _i, _vp]),
     "rmap_resolve_serials": (_i, [_vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),

@@ -105,6 +105,7 @@ void sbi_preload_kernels();
 void maprmap_preload_kernels();
 void maprmap_keyframe_preload_kernels();
 void maprmap_publish_preload_kernels();
+void maprmap_init_preload_kernels();
 void framereport_preload_kernels();
 int pose_hazards_read_pose(hipStream_t st, unsigned long long* out);
 int pose_hazards_read_trackmap(hipStream_t st, unsigned long long* out);

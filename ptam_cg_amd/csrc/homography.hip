@@ -629,7 +629,8 @@ int homog_run(ptam_ctx* ctx, int n, const ptam_homography_match* d_matches, cons
     hipLaunchKernelGGL(homog_finish_kernel, dim3(1), dim3(HOMOG_THREADS), 0, ctx->stream, g);
     HIP_TRY(hipGetLastError());
     char* h_out = (char*)hp + L.pin_out;
-    HIP_TRY(hipMemcpyAsync(h_out, d + L.out, 256 + (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    // (the n inlier bytes come down only for the caller that asked for them)
+    HIP_TRY(hipMemcpyAsync(h_out, d + L.out, 256 + (inlier_out ? (size_t)n : 0), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ptam_stream_wait(ctx->stream));
     const HomogOut* r = (const HomogOut*)h_out;
     *info = r->info;

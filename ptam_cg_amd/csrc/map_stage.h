@@ -74,3 +74,24 @@ int map_scene_depth_core(MapStage& s, int n_kf, const double* d_poses, const dou
 // ptam_map_apply_global_transform's launch on device tables (mapalign.hip), its 256-byte record in the caller's stage: enqueues only
 int map_transform_core(MapStage& s, void* d_record, void* h_record, const double se3_new_from_old[12], int K, const double* d_poses,
                        double* d_poses_new, int N, double* d_points3, const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride);
+// ... and the launch alone, on an aligner's record that is in device memory already (the plane stage's, or one uploaded): K + N > 0
+int map_apply_core(MapStage& s, const void* d_record, int K, const double* d_poses, double* d_poses_new, int N, double* d_points3,
+                   const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride);
+// CalcPlaneAligner (mapalign.hip) on a point table in device memory.  The pieces of the caller's stage (map_plane_layout), then
+// map_plane_core: the draw (or the caller's samples) up, plane_score_kernel and plane_finish_kernel; enqueues only.  The aligner's
+// 256-byte record is left at w.d_record for map_apply_core and arrives, through host-mapped memory, at w.h_record: after the
+// caller's wait map_plane_result reads the info and the aligner there.  Options checked by the caller (map_plane_check).
+struct MapPlaneWork {
+    int32_t *d_samples, *h_samples;
+    double* scores;
+    int* skipped;
+    char* d_record;   // 256 bytes, then the n inlier bytes
+    char* h_record;   // pinned, 256 bytes
+};
+int map_plane_check(int n, const ptam_plane_opts* o);   // PTAM_E_ARG as ptam_calc_plane_aligner refuses its options
+void map_plane_layout(Carver& c, Carver& pin, int n, int trials, MapPlaneWork& w);
+int map_plane_core(MapStage& s, const MapPlaneWork& w, const ptam_plane_opts* o, int n, const double* d_points3);
+void map_plane_result(const MapPlaneWork& w, ptam_plane_info* info, double se3_aligner[12]);
+// the record of a caller's own aligner (status PTAM_PLANE_OK), or of no move at all (status PTAM_PLANE_TOO_FEW: map_apply_core then
+// copies the poses, leaves the points and refreshes the pixel vectors alone), into 256 pinned bytes and up to d_record
+int map_record_up(MapStage& s, void* d_record, void* h_record, int status, const double se3_new_from_old[12]);

@@ -422,8 +422,8 @@ static void plane_draw(uint64_t seed, int n, int trials, int32_t* out) {   // th
     }
 }
 
-static int plane_check(int n, const double* points3, const ptam_plane_opts* o) {
-    ARG_TRY(o && n >= 0 && (n == 0 || points3) && o->trials >= 1 && o->max_dist > 0.0);
+int map_plane_check(int n, const ptam_plane_opts* o) {
+    ARG_TRY(o && n >= 0 && o->trials >= 1 && o->max_dist > 0.0);
     if (o->samples && n >= 10)   // (below ten points nothing is drawn, :1103-1106)
         for (int r = 0; r < o->trials; r++) {
             const int32_t* s = o->samples + 3 * r;
@@ -431,6 +431,10 @@ static int plane_check(int n, const double* points3, const ptam_plane_opts* o) {
             ARG_TRY(s[0] != s[1] && s[0] != s[2] && s[1] != s[2]);
         }
     return PTAM_OK;
+}
+static int plane_check(int n, const double* points3, const ptam_plane_opts* o) {
+    ARG_TRY(n <= 0 || points3);
+    return map_plane_check(n, o);
 }
 static int tables_check(int K, const double* poses, int N, const double* points3, const ptam_map_point_source* src, const ptam_pvs_point* out) {
     ARG_TRY(K >= 0 && N >= 0 && (K == 0 || poses) && (N == 0 || points3));
@@ -440,33 +444,95 @@ static int tables_check(int K, const double* poses, int N, const double* points3
     return PTAM_OK;
 }
 
+// ---- the stage's cores: tables in device memory, launches on the stage's stream, no wait (map_stage.h) -----------------------------
+void map_plane_layout(Carver& c, Carver& pin, int n, int trials, MapPlaneWork& w) {
+    const size_t Nz = n > 0 ? n : 1, Tz = trials > 0 ? trials : 1;
+    w.d_samples = c.piece<int32_t>(Tz * 3);
+    w.scores = c.piece<double>(Tz);
+    w.skipped = c.piece<int>(Tz);
+    w.d_record = c.piece<char>(256 + Nz);
+    w.h_samples = pin.piece<int32_t>(Tz * 3);
+    w.h_record = pin.piece<char>(256);
+}
+int map_plane_core(MapStage& s, const MapPlaneWork& w, const ptam_plane_opts* o, int n, const double* d_points3) {
+    PlaneArgs g;
+    g.n = n;
+    g.trials = o->trials;
+    g.max_dist = o->max_dist;
+    g.pts = d_points3;
+    g.samples = w.d_samples;
+    g.scores = w.scores;
+    g.skipped = w.skipped;
+    g.out = (PlaneOut*)w.d_record;
+    g.flags = (uint8_t*)w.d_record + 256;
+    g.h_out = s.pin_dev((PlaneOut*)w.h_record);
+    if (n >= 10) {
+        if (o->samples)
+            std::memcpy(w.h_samples, o->samples, (size_t)o->trials * 3 * sizeof(int32_t));
+        else
+            plane_draw(o->seed, n, o->trials, w.h_samples);
+        STAGE_TRY(s.up(w.d_samples, w.h_samples, (size_t)o->trials * 3 * sizeof(int32_t)));
+        hipLaunchKernelGGL(plane_score_kernel, dim3(o->trials), dim3(ALIGN_THREADS), 0, s.st, g);
+    }
+    hipLaunchKernelGGL(plane_finish_kernel, dim3(1), dim3(ALIGN_THREADS), 0, s.st, g);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+void map_plane_result(const MapPlaneWork& w, ptam_plane_info* info, double se3_aligner[12]) {
+    const PlaneOut* r = (const PlaneOut*)w.h_record;
+    *info = r->info;
+    std::memcpy(se3_aligner, r->se3, sizeof r->se3);
+}
+int map_record_up(MapStage& s, void* d_record, void* h_record, int status, const double se3_new_from_old[12]) {
+    PlaneOut* h_out = (PlaneOut*)h_record;
+    *h_out = PlaneOut{};
+    h_out->info.status = status;
+    std::memcpy(h_out->se3, se3_new_from_old, sizeof h_out->se3);
+    return s.up(d_record, h_out, sizeof(PlaneOut));
+}
+// poses -> poses_new, the points in place, the pixel vectors (d_src / d_pvs nullable together) into rows pvs_stride bytes apart
+int map_apply_core(MapStage& s, const void* d_record, int K, const double* d_poses, double* d_poses_new, int N, double* d_points3,
+                   const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride) {
+    ApplyArgs a;
+    a.K = K;
+    a.N = N;
+    a.plane = (const PlaneOut*)d_record;
+    a.poses = d_poses;
+    a.poses_new = d_poses_new;
+    a.pts = d_points3;
+    a.src = d_src;
+    a.pvs = d_pvs;
+    a.pvs_stride = pvs_stride;
+    hipLaunchKernelGGL(map_apply_kernel, dim3((K + N + ALIGN_THREADS - 1) / ALIGN_THREADS), dim3(ALIGN_THREADS), 0, s.st, a);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+// ptam_map_apply_global_transform's launch on tables that are in device memory.  d_record / h_record: 256 bytes each of the caller's
+// stage (scratch, pinned) for the aligner's record.  Enqueues only; K + N > 0.
+int map_transform_core(MapStage& s, void* d_record, void* h_record, const double se3_new_from_old[12], int K, const double* d_poses,
+                       double* d_poses_new, int N, double* d_points3, const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride) {
+    STAGE_TRY(map_record_up(s, d_record, h_record, PTAM_PLANE_OK, se3_new_from_old));
+    return map_apply_core(s, d_record, K, d_poses, d_poses_new, N, d_points3, d_src, d_pvs, pvs_stride);
+}
+
 // The three calls of stage (8) are one routine: the plane stage when `o` is given (else the aligner is se3_in), the apply stage when
-// `apply`.  Arguments checked by the caller.  Uploads, up to three launches, the copies down, one host wait.
+// `apply`.  Arguments checked by the caller.  Uploads, up to three launches (the cores above), the copies down, one host wait.
 static int align_run(ptam_ctx* ctx, const ptam_plane_opts* o, const double* se3_in, bool apply, int K, double* poses, int N, double* pts,
                      const ptam_map_point_source* src, ptam_pvs_point* pvs, double se3_out[12], ptam_plane_info* info, uint8_t* inlier_out) {
-    const int trials = o ? o->trials : 0;
-    const size_t Kz = K > 0 ? K : 1, Nz = N > 0 ? N : 1, Tz = trials > 0 ? trials : 1;
-    PlaneArgs g;
-    ApplyArgs a;
-    int32_t *d_samples, *h_samples;
+    const size_t Kz = K > 0 ? K : 1, Nz = N > 0 ? N : 1;
+    MapPlaneWork w;
     double *d_pts, *d_pose, *d_pose_new;
     ptam_map_point_source* d_src;
     ptam_pvs_point* d_pvs;
-    PlaneOut* h_out;
     char *t_pose = nullptr, *t_pts = nullptr, *t_pvs = nullptr;   // where the tables come down, in the pinned staging
     MapStage stage(ctx);
     STAGE_TRY(stage.carve([&](Carver& c, Carver& pin) {
-        g.samples = d_samples = c.piece<int32_t>(Tz * 3);
-        g.pts = d_pts = c.piece<double>(Nz * 3);
-        g.scores = c.piece<double>(Tz);
-        g.skipped = c.piece<int>(Tz);
-        g.out = (PlaneOut*)c.piece<char>(256 + Nz);
+        map_plane_layout(c, pin, N, o ? o->trials : 0, w);
+        d_pts = c.piece<double>(Nz * 3);
         d_pose = c.piece<double>(Kz * 12);
         d_pose_new = c.piece<double>(Kz * 12);
         d_src = c.piece<ptam_map_point_source>(Nz);
         d_pvs = c.piece<ptam_pvs_point>(Nz);
-        h_samples = pin.piece<int32_t>(Tz * 3);
-        h_out = (PlaneOut*)pin.piece<char>(256);
         if (apply) {
             t_pose = pin.piece<char>(Kz * 96);
             t_pts = pin.piece<char>(Nz * 24);
@@ -474,43 +540,17 @@ static int align_run(ptam_ctx* ctx, const ptam_plane_opts* o, const double* se3_
         }
     }));
     hipStream_t st = stage.st;
-    g.n = N;
-    g.trials = trials;
-    g.max_dist = o ? o->max_dist : 0.0;
-    g.flags = (uint8_t*)g.out + 256;
-    g.h_out = stage.pin_dev(h_out);
     STAGE_TRY(stage.up(d_pts, pts, (size_t)N * 24));
-    if (o) {
-        if (N >= 10) {
-            if (o->samples)
-                std::memcpy(h_samples, o->samples, (size_t)trials * 3 * sizeof(int32_t));
-            else
-                plane_draw(o->seed, N, trials, h_samples);
-            STAGE_TRY(stage.up(d_samples, h_samples, (size_t)trials * 3 * sizeof(int32_t)));
-            hipLaunchKernelGGL(plane_score_kernel, dim3(trials), dim3(ALIGN_THREADS), 0, st, g);
-        }
-        hipLaunchKernelGGL(plane_finish_kernel, dim3(1), dim3(ALIGN_THREADS), 0, st, g);
-    } else {   // the caller's aligner takes the plane stage's place
-        *h_out = PlaneOut{};
-        h_out->info.status = PTAM_PLANE_OK;
-        std::memcpy(h_out->se3, se3_in, sizeof h_out->se3);
-        STAGE_TRY(stage.up(g.out, h_out, sizeof(PlaneOut)));
-    }
+    if (o)
+        STAGE_TRY(map_plane_core(stage, w, o, N, d_pts));
+    else   // the caller's aligner takes the plane stage's place
+        STAGE_TRY(map_record_up(stage, w.d_record, w.h_record, PTAM_PLANE_OK, se3_in));
     if (apply && K + N > 0) {
-        a.K = K;
-        a.N = N;
-        a.plane = g.out;
-        a.poses = d_pose;
-        a.poses_new = d_pose_new;
-        a.pts = d_pts;
-        a.src = src ? d_src : nullptr;
-        a.pvs = src ? d_pvs : nullptr;
-        a.pvs_stride = (int)sizeof(ptam_pvs_point);
         STAGE_TRY(stage.up(d_pose, poses, (size_t)K * 96));
         if (src) STAGE_TRY(stage.up(d_src, src, (size_t)N * sizeof(ptam_map_point_source)));
-        hipLaunchKernelGGL(map_apply_kernel, dim3((K + N + ALIGN_THREADS - 1) / ALIGN_THREADS), dim3(ALIGN_THREADS), 0, st, a);
+        STAGE_TRY(map_apply_core(stage, w.d_record, K, d_pose, d_pose_new, N, d_pts, src ? d_src : nullptr, src ? d_pvs : nullptr,
+                                 (int)sizeof(ptam_pvs_point)));
     }
-    HIP_TRY(hipGetLastError());
     // what the status decides about (the tables, the pixel vectors) comes down into the context's pinned staging and reaches the
     // caller's memory after the wait; the inlier bytes go there directly
     if (apply) {
@@ -518,13 +558,13 @@ static int align_run(ptam_ctx* ctx, const ptam_plane_opts* o, const double* se3_
         STAGE_TRY(stage.down(t_pts, d_pts, (size_t)N * 24));
         if (src) STAGE_TRY(stage.down(t_pvs, d_pvs, (size_t)N * sizeof(ptam_pvs_point)));
     }
-    if (o && inlier_out && N >= 10) STAGE_TRY(stage.down(inlier_out, g.flags, (size_t)N));
+    if (o && inlier_out && N >= 10) STAGE_TRY(stage.down(inlier_out, w.d_record + 256, (size_t)N));
     HIP_TRY(ptam_stream_wait(st));
-    const int status = o ? h_out->info.status : PTAM_PLANE_OK;
+    int status = PTAM_PLANE_OK;
     if (o) {
-        *info = h_out->info;
-        std::memcpy(se3_out, h_out->se3, sizeof h_out->se3);
-        if (inlier_out && (N < 10 || h_out->info.best_trial < 0)) std::memset(inlier_out, 0, (size_t)N);   // (no inlier pass ran)
+        map_plane_result(w, info, se3_out);
+        status = info->status;
+        if (inlier_out && (N < 10 || info->best_trial < 0)) std::memset(inlier_out, 0, (size_t)N);   // (no inlier pass ran)
     }
     if (apply && status == PTAM_PLANE_OK) {
         if (K > 0) std::memcpy(poses, t_pose, (size_t)K * 96);
@@ -600,31 +640,6 @@ int ptam_map_scene_depth(ptam_ctx* ctx, int n_kf, const double* kf_poses12, int 
 }
 
 }   // extern "C"
-
-// ptam_map_apply_global_transform's launch on tables that are in device memory: poses -> poses_new, the points in place, the pixel
-// vectors (d_src / d_pvs nullable together) into rows pvs_stride bytes apart.  d_record / h_record: 256 bytes each of the caller's
-// stage (scratch, pinned) for the aligner's record.  Enqueues only; K + N > 0.
-int map_transform_core(MapStage& s, void* d_record, void* h_record, const double se3_new_from_old[12], int K, const double* d_poses,
-                       double* d_poses_new, int N, double* d_points3, const ptam_map_point_source* d_src, ptam_pvs_point* d_pvs, int pvs_stride) {
-    PlaneOut* h_out = (PlaneOut*)h_record;
-    *h_out = PlaneOut{};
-    h_out->info.status = PTAM_PLANE_OK;
-    std::memcpy(h_out->se3, se3_new_from_old, sizeof h_out->se3);
-    STAGE_TRY(s.up(d_record, h_out, sizeof(PlaneOut)));
-    ApplyArgs a;
-    a.K = K;
-    a.N = N;
-    a.plane = (const PlaneOut*)d_record;
-    a.poses = d_poses;
-    a.poses_new = d_poses_new;
-    a.pts = d_points3;
-    a.src = d_src;
-    a.pvs = d_pvs;
-    a.pvs_stride = pvs_stride;
-    hipLaunchKernelGGL(map_apply_kernel, dim3((K + N + ALIGN_THREADS - 1) / ALIGN_THREADS), dim3(ALIGN_THREADS), 0, s.st, a);
-    HIP_TRY(hipGetLastError());
-    return PTAM_OK;
-}
 
 // the launch and the wait of ptam_map_scene_depth on tables that are in device memory (n_kf > 0); h_out: n_kf records of the
 // caller's pinned stage, which the kernel writes through their device address; out: host

@@ -262,6 +262,8 @@ int ptam_rmap_create(ptam_ctx* ctx, ptam_rmap** out) {
     m->map_id = ++map_ids;
     m->next_serial = 1;
     m->kf_epoch = 0;
+    m->d_init = nullptr;
+    m->d_init_bytes = 0;
     if (hipMalloc((void**)&m->d_words, RM_WORDS * sizeof(int)) != hipSuccess) {
         delete m;
         ptam_set_error("ptam_rmap_create: no device memory");
@@ -279,6 +281,7 @@ int ptam_rmap_destroy(ptam_rmap* m) {
         for (int k = 0; k < 2; k++)
             if (m->t[w].buf[k]) (void)hipFree(m->t[w].buf[k]);
     if (m->d_words) (void)hipFree(m->d_words);
+    if (m->d_init) (void)hipFree(m->d_init);
     delete m;
     return PTAM_OK;
 }

@@ -6,6 +6,8 @@
 //                                   (rm_busy_kernel), the epipolar chain of mapmaker.hip, and mt_add_points_core on the chain's output
 //   ptam_rmap_insert_keyframe_report   the same with the rows taken from a tracker's frame report where it lies (rm_report_rows_kernel:
 //                                   records resolved by serial)
+//   rm_epipolar_points              steps (d)-(g) of an insertion — busy list, epipolar chain, its count, the new points' rows — for
+//                                   ptam_rmap_init_from_stereo's AddSomeMapPoints as well (maprmap_init.hip)
 // Each step of an insertion that ends in a wait of its own stages for itself; nothing of one step's scratch is read after its wait.
 #include <algorithm>
 
@@ -199,6 +201,40 @@ int rm_closest(ptam_rmap* m, int K, int self, int only, int n_pick, const int** 
 
 }   // namespace
 
+// Steps (d)-(g) of a keyframe's insertion, as AddSomeMapPoints runs them for kSrc = keyframe `src_kf` of the map (handle `src`, pose
+// src_pose) against keyframe target_kf: rows [busy_first, busy_first + n_busy) of the resident measurement table are kSrc's run.
+// run: sized by epi_sizes.  The made points become points [n_points, n_points + *n_made); levels: run.nl entries.
+int rm_epipolar_points(ptam_rmap* m, int src_kf, const ptam_kf* src, const double src_pose[12], int target_kf, const ptam_epipolar_opts* epi,
+                       EpiRun& run, int busy_first, int n_busy, int32_t* n_made, ptam_epipolar_level_stats* levels) {
+    ptam_ctx* ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    // ---- (d) the busy list
+    ptam_kf* target = const_cast<ptam_kf*>(m->kfs[(size_t)target_kf]);   // (its implane tables are cached on the handle)
+    if (int rc = epi_carve(ctx, target, epi, n_busy, run)) return rc;
+    HIP_TRY(hipMemsetAsync(run.d_hdr, 0, EPI_HDR_BYTES, st));
+    hipLaunchKernelGGL(rm_busy_kernel, dim3(std::max(MapStage::blocks(n_busy), 1u)), dim3(256), 0, st, n_busy, rm_meas(m) + busy_first, run.d_busy,
+                       run.d_hdr);
+    HIP_TRY(hipGetLastError());
+    // ---- (e) the epipolar chain, (f) its count and stats
+    if (int rc = epi_launch_chain(ctx, src, src_pose, target, m->h_poses.data() + (size_t)12 * target_kf, epi, run)) return rc;
+    char* hp;
+    MapStage s = rm_stage(m);
+    STAGE_TRY(s.carve([&](Carver&, Carver& pin) { hp = pin.piece<char>(EPI_HDR_BYTES); }));
+    STAGE_TRY(s.down(hp, run.d_hdr, EPI_HDR_BYTES));
+    HIP_TRY(ptam_stream_wait(st));
+    const int made = ((const int*)hp)[1];
+    if (made < 0 || made > run.sum) {
+        ptam_set_error("ptam_rmap: %d epipolar points made, room for %d", made, run.sum);
+        return PTAM_E_STATE;
+    }
+    std::memcpy(levels, hp + 16, sizeof(ptam_epipolar_level_stats) * (size_t)run.nl);
+    *n_made = made;
+    // ---- (g) the made points into the tables, straight from the chain's output
+    if (made > 0)
+        if (int rc = rm_add_points_device(m, src_kf, target_kf, PTAM_MAP_SRC_EPIPOLAR, made, run.d_out)) return rc;
+    return PTAM_OK;
+}
+
 extern "C" {
 
 int ptam_rmap_add_keyframe(ptam_rmap* m, const ptam_kf* kf, const double pose12[12], int fixed, int n_rows, const ptam_map_kf_row* rows) {
@@ -299,30 +335,8 @@ static int rm_insert_keyframe(ptam_rmap* m, ptam_refinder* finder, const ptam_kf
         *res = r;
         return PTAM_OK;
     }
-    // ---- (d) the busy list: the new keyframe's run is the tail of the table as (b) left it
-    const int n_busy = m->n[RM_N_MEAS] - M;
-    ptam_kf* target = const_cast<ptam_kf*>(m->kfs[(size_t)r.target_kf]);   // (its implane tables are cached on the handle)
-    if (int rc = epi_carve(ctx, target, &opts->epipolar, n_busy, run)) return rc;
-    HIP_TRY(hipMemsetAsync(run.d_hdr, 0, EPI_HDR_BYTES, st));
-    hipLaunchKernelGGL(rm_busy_kernel, dim3(std::max(MapStage::blocks(n_busy), 1u)), dim3(256), 0, st, n_busy, rm_meas(m) + M, run.d_busy, run.d_hdr);
-    HIP_TRY(hipGetLastError());
-    // ---- (e) the epipolar chain, (f) its count and stats
-    if (int rc = epi_launch_chain(ctx, kf, pose12, target, m->h_poses.data() + (size_t)12 * r.target_kf, &opts->epipolar, run)) return rc;
-    char* hp;
-    MapStage s = rm_stage(m);
-    STAGE_TRY(s.carve([&](Carver&, Carver& pin) { hp = pin.piece<char>(EPI_HDR_BYTES); }));
-    STAGE_TRY(s.down(hp, run.d_hdr, EPI_HDR_BYTES));
-    HIP_TRY(ptam_stream_wait(st));
-    const int made = ((const int*)hp)[1];
-    if (made < 0 || made > run.sum) {
-        ptam_set_error("ptam_rmap_insert_keyframe: %d points made, room for %d", made, run.sum);
-        return PTAM_E_STATE;
-    }
-    std::memcpy(r.levels, hp + 16, sizeof(ptam_epipolar_level_stats) * (size_t)run.nl);
-    r.n_made = made;
-    // ---- (g) the made points into the tables, straight from the chain's output
-    if (made > 0)
-        if (int rc = rm_add_points_device(m, K, r.target_kf, PTAM_MAP_SRC_EPIPOLAR, made, run.d_out)) return rc;
+    // ---- (d)-(g): the busy list from the new keyframe's run (the tail of the table as (b) left it), the chain, the made points
+    if (int rc = rm_epipolar_points(m, K, kf, pose12, r.target_kf, &opts->epipolar, run, M, m->n[RM_N_MEAS] - M, &r.n_made, r.levels)) return rc;
     *res = r;
     return PTAM_OK;
 }

@@ -2,6 +2,8 @@
 //   ptam_map_apply_outliers     the outlier loop of MapMaker::BundleAdjust (src/MapMaker.cc:916-932)
 //   ptam_map_handle_bad_points  MapMaker::HandleBadPoints (:131-153) with Map::MoveBadPointsToTrash (src/Map.cc:20-30)
 //   ptam_map_add_points         the table side of AddPointEpipolar (:670-685) and of InitFromStereo's point loop (:352-362)
+// and, for ptam_rmap_init_from_stereo (maprmap_init.hip), mt_made_records_core: the made records of InitFromStereo's point loop
+// (:310-367) compacted in match order, with the count of every status.
 // All three set a flag per row, compact or merge the rows in order and remap the point column.  The one primitive is the ordered
 // compaction mt_compact over a row source (keep / put / drop), three launches:
 //   mt_count_kernel    one workgroup per tile of MT_TILE = 1024 rows, one row per thread: __ballot / __popcll per 64-lane wave,
@@ -9,7 +11,7 @@
 //   mt_scan_kernel     one workgroup: the tile counts -> exclusive offsets and the total, MT_SCAN_CHUNK = 1024 tile counts per
 //                      round with the running sum carried from round to round (it walks the tile counts, not the table)
 //   mt_scatter_kernel  the tiling of mt_count_kernel again: row -> tile offset + offset inside the tile
-// No atomic decides where a row lands; the only atomic of the file adds up a count (n_marked).
+// No atomic decides where a row lands; the only atomics of the file add up counts (n_marked, the point loop's status counts).
 // Sizes at which the compaction changes path (tests/test_gpu_map_edit.py runs n - 1, n, n + 1 of each):
 //   64          rows: a second wave inside the tile
 //   1024        rows (MT_TILE): a second workgroup
@@ -163,6 +165,14 @@ struct MtRemapQueue {   // mqNewQueue
     __device__ void put(int i, int at) const { out[at] = new_index[in[i]]; }
     __device__ void drop(int) const {}
 };
+struct MtMadeRecords {   // InitFromStereo's point loop: the records whose status is PTAM_INIT_MADE, in match order
+    const int32_t* status;
+    const ptam_new_map_point* in;
+    ptam_new_map_point* out;
+    __device__ bool keep(int i) const { return status[i] == PTAM_INIT_MADE; }
+    __device__ void put(int i, int at) const { out[at] = in[i]; }
+    __device__ void drop(int) const {}
+};
 
 // ---- the kernels around it -----------------------------------------------------------------------------------------------------
 // :916-932, one thread per outlier: the row's flag (no row is named twice) and bBad (the same byte may be set more than once).
@@ -298,6 +308,18 @@ __global__ void __launch_bounds__(256) mt_add_points_kernel(MtAdd p) {
     if (p.new_queue) p.new_queue[i] = p.n_points + i;
 }
 
+// one thread per match: how many of each status 0..3 (a ballot per status and wave, one integer atomicAdd per wave and status
+// that occurs: exact in any order).  counts: four ints, zeroed by the caller
+__global__ void __launch_bounds__(256) mt_status_count_kernel(int n, const int32_t* __restrict__ status, int* __restrict__ counts) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int code = i < n ? status[i] : -1;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const unsigned long long mk = __ballot(code == c);
+        if ((threadIdx.x & 63) == 0 && mk) atomicAdd(counts + c, __popcll(mk));
+    }
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 // ---- the cores: device pointers in, launches on the stream, no wait (maptables_internal.h) ---------------------------------------
 // the flags, the three compactions, the merge
@@ -342,6 +364,15 @@ int mt_add_points_core(hipStream_t st, const MtAdd& p) {
     hipLaunchKernelGGL(mt_add_rows_kernel, dim3((unsigned)(((long long)p.n_meas + 2ll * p.n_made + 255) / 256)), dim3(256), 0, st, p);
     if (p.points || p.sources || p.points3 || p.bad || p.outlier_count || p.inlier_count || p.new_queue)
         hipLaunchKernelGGL(mt_add_points_kernel, dim3((p.n_made + 255) / 256), dim3(256), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
+// tot: {made, then the four per-status counts}
+int mt_made_records_core(hipStream_t st, int n, const int32_t* status, const ptam_new_map_point* in, ptam_new_map_point* out, int* tiles, int* tot) {
+    HIP_TRY(hipMemsetAsync(tot, 0, MT_MADE_WORDS * sizeof(int), st));
+    if (n > 0) hipLaunchKernelGGL(mt_status_count_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, st, n, status, tot + 1);
+    mt_compact(st, MtMadeRecords{status, in, out}, n, tiles, tot);
     HIP_TRY(hipGetLastError());
     return PTAM_OK;
 }
@@ -560,6 +591,9 @@ void maptables_preload_kernels() {
     ptam_preload((const void*)mt_scatter_kernel<MtRemapRows<ptam_map_pair>>);
     ptam_preload((const void*)mt_count_kernel<MtRemapQueue>);
     ptam_preload((const void*)mt_scatter_kernel<MtRemapQueue>);
+    ptam_preload((const void*)mt_count_kernel<MtMadeRecords>);
+    ptam_preload((const void*)mt_scatter_kernel<MtMadeRecords>);
+    ptam_preload((const void*)mt_status_count_kernel);
     ptam_preload((const void*)mt_outliers_kernel);
     ptam_preload((const void*)mt_merge_kernel);
     ptam_preload((const void*)mt_mark_kernel);

@@ -108,6 +108,12 @@ static inline MtAdd mt_add_head(int src_kf, int target_kf, int target_source, in
     return p;
 }
 
+// ---- InitFromStereo's point loop (:310-367) behind its kernel: the records whose status is PTAM_INIT_MADE compacted in match order
+//      (the ordered compaction, tiles of MT_TILE matches), and how many matches ended in each status.
+//      tot: MT_MADE_WORDS ints = {made, count of status 0..3}; tiles: mt_tiles(n); in / out: n records each
+enum { MT_MADE_WORDS = 5 };
+int mt_made_records_core(hipStream_t st, int n, const int32_t* status, const ptam_new_map_point* in, ptam_new_map_point* out, int* tiles, int* tot);
+
 // ---- MapMaker::ReFind* (:1028-1081), maprefind.hip: the re-find on tables in device memory.  The merged tables are written into
 //      d_meas_merged / d_never_merged (each nullable; room for n_meas / n_never + the plan's pair count).
 struct MrTables {

@@ -1,6 +1,6 @@
-// rmap_internal.h — ptam_rmap, the resident map, as its three files share it: maprmap.hip (the handle, upload / download, the edits,
-// the resident forms of bundle, re-find and transform), maprmap_keyframe.hip (a keyframe into the map) and maprmap_publish.hip
-// (serials, frame reports, the map to the tracker).
+// rmap_internal.h — ptam_rmap, the resident map, as its four files share it: maprmap.hip (the handle, upload / download, the edits,
+// the resident forms of bundle, re-find and transform), maprmap_keyframe.hip (a keyframe into the map), maprmap_publish.hip
+// (serials, frame reports, the map to the tracker) and maprmap_init.hip (the first map: InitFromStereo, the plane alignment, clear).
 // Every table has two buffers of one capacity.  A kernel that rebuilds a table reads buf[cur] and writes buf[cur ^ 1]; the host
 // flips cur after the call's wait has read the refusal word.  Rows appended behind a table's count change nothing until the count
 // moves, which it does after the same wait.
@@ -45,6 +45,8 @@ struct ptam_rmap {
     int* d_words;
     unsigned long long h2d, d2h;
     int refusal_table, refusal_row;
+    void* d_init;                      // ptam_rmap_init_from_stereo from a host match table: the trails and their matches (grown on demand)
+    size_t d_init_bytes;
 };
 
 // typed access: rm_meas(m) is the table as it stands, rm_meas_alt(m) the buffer a rebuilding kernel writes
@@ -78,6 +80,12 @@ int rm_words_wait(MapStage& s, ptam_rmap* m, int* h_words);
 int rm_refuse(ptam_rmap* m, int table, int row);
 // mt_add_points_core on the handle's buffers; d_made: the records in device memory.  One wait, then the counts move.
 int rm_add_points_device(ptam_rmap* m, int src_kf, int target_kf, int target_source, int n_made, const ptam_new_map_point* d_made);
+// ---- maprmap_keyframe.hip
+// steps (d)-(g) of ptam_rmap_insert_keyframe for kSrc = keyframe src_kf (rows [busy_first, busy_first + n_busy) of the measurement
+// table are its run) against keyframe target_kf; run: sized by epi_sizes; levels: run.nl entries
+struct EpiRun;
+int rm_epipolar_points(ptam_rmap* m, int src_kf, const ptam_kf* src, const double src_pose[12], int target_kf, const ptam_epipolar_opts* epi,
+                       EpiRun& run, int busy_first, int n_busy, int32_t* n_made, ptam_epipolar_level_stats* levels);
 // ---- maprmap_publish.hip
 // out[i] = first + i: the serials of points that a call appends (or, at an upload, of all of them)
 void rm_give_serials(hipStream_t st, int n, long long first, long long* out);

@@ -26,6 +26,7 @@
 #include "patch_device.h"
 #include "mapmaker_device.h"
 #include "homography.h"
+#include "trails_internal.h"
 
 #define TRAIL_MAX_SSD 100000   // MiniPatch::FindPatch's default nMaxSSD (include/ImageProcess.h)
 #define TRAIL_RANGE 10         // src/Tracker.cc:400
@@ -356,6 +357,34 @@ __global__ void __launch_bounds__(256) init_points_kernel(InitArgs a, KfLevels F
     }
 }
 
+// ---- the same launches for ptam_rmap_init_from_stereo (trails_internal.h) ----------------------------------------------------------
+void trails_view(const ptam_trails* t, TrailsView* out) {
+    out->ctx = t->ctx;
+    out->w = t->w;
+    out->h = t->h;
+    out->started = t->started;
+    out->n_live = t->n_live;
+    out->d_trails = t->trails[t->cur];
+    out->d_out = (ptam_homography_match*)t->out;
+}
+int trails_matches_enqueue(ptam_ctx* ctx, int n, const ptam_trail* d_trails, ptam_homography_match* d_out) {
+    hipLaunchKernelGGL(trails_matches_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->cam, n, d_trails, d_out);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+int init_points_enqueue(ptam_ctx* ctx, const ptam_kf* first, const ptam_kf* second, const double se3_second_from_first[12], int subpix_max_its,
+                        int n, const ptam_trail* d_matches, int* d_status, ptam_new_map_point* d_pts) {
+    InitArgs a;
+    a.cam = ctx->cam;
+    for (int i = 0; i < 9; i++) a.R[i] = se3_second_from_first[i];
+    for (int i = 0; i < 3; i++) a.t[i] = se3_second_from_first[9 + i];
+    a.its = subpix_max_its;
+    a.n = n;
+    hipLaunchKernelGGL(init_points_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, first->L, second->L, d_matches, d_status, d_pts);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
 extern "C" {
 
 int ptam_trails_create(ptam_ctx* ctx, int max_trails, ptam_trails** out) {
@@ -581,14 +610,8 @@ int ptam_init_points_from_trails(ptam_ctx* ctx, const ptam_kf* first, ptam_kf* s
     ptam_new_map_point* d_pts = (ptam_new_map_point*)((char*)s + b_m + b_st);
     // (pageable: staged before the call returns, which is after the final wait)
     HIP_TRY(hipMemcpyAsync(d_m, matches, sizeof(ptam_trail) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    InitArgs a;
-    a.cam = ctx->cam;
-    for (int i = 0; i < 9; i++) a.R[i] = se3_second_from_first[i];
-    for (int i = 0; i < 3; i++) a.t[i] = se3_second_from_first[9 + i];
-    a.its = subpix_max_its;
-    a.n = n;
-    hipLaunchKernelGGL(init_points_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, first->L, second->L, (const ptam_trail*)d_m, d_st, d_pts);
-    HIP_TRY(hipGetLastError());
+    rc = init_points_enqueue(ctx, first, second, se3_second_from_first, subpix_max_its, n, d_m, d_st, d_pts);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(hp, d_st, b_st + b_pts, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ptam_stream_wait(ctx->stream));
     const int* h_st = (const int*)hp;

@@ -1118,6 +1118,74 @@ class ResidentMap:
         self.ctx._check(rc, "rmap_note_reports")
         return _counts(res)
 
+    def init_opts(self, **kw):
+        """ptam_rmap_init_opts with the reference's defaults.  Keywords: wiggle_scale, subpix_max_its, first_bundles, max_bundles;
+        homography=dict(max_pixel_error, seed, samples, trials); ba=dict of ptam_ba_opts fields; epipolar=dict as MapMaker.opts
+        takes it; plane=dict(max_dist, seed, trials)."""
+        o = _abi.RmapInitOpts()
+        self.ctx._check(self.lib.rmap_init_opts_default(C.byref(o)), "rmap_init_opts_default")
+        for k, v in kw.items():
+            if k == "homography":
+                h = dict(max_pixel_error=o.homography.max_pixel_error, seed=o.homography.seed, samples=None, trials=o.homography.trials)
+                h.update(v)
+                o.homography, keep = _homography_opts(h["max_pixel_error"], h["seed"], h["samples"], h["trials"])
+                o._keep = keep     # (the table lives as long as the options)
+            elif k == "ba":
+                for f, x in v.items():
+                    setattr(o.ba, f, x)
+            elif k == "epipolar":
+                for f, x in v.items():
+                    if f == "levels":
+                        o.epipolar.n_levels = len(x)
+                        for i, l in enumerate(x):
+                            o.epipolar.levels[i] = l
+                    else:
+                        setattr(o.epipolar, f, x)
+            elif k == "plane":
+                for f, x in v.items():
+                    setattr(o.plane, f, x)
+            else:
+                setattr(o, k, v)
+        return o
+
+    def InitFromStereo(self, first, second, trails=None, matches=None, opts=None, stop=None, check=True):
+        """MapMaker::InitFromStereo (src/MapMaker.cc:268-405) as ONE call on the resident map (ptam_rmap_init_from_stereo): first /
+        second the caller's KeyFrame clones (they become keyframes 0 and 1), trails a started Trails (its live list is read on the
+        device) or matches TRAIL_DT, opts from init_opts(), stop a uint8 array of one flag -> dict of the result (status one of
+        _abi.INIT_MAP_*).  check=False: -> the status of a refused call instead of raising."""
+        opts = opts if opts is not None else self.init_opts()
+        m = None if matches is None else np.ascontiguousarray(matches, dtype=TRAIL_DT)
+        res = _abi.RmapInitResult()
+        rc = self.lib.rmap_init_from_stereo(self.h, first.h if first is not None else None, second.h if second is not None else None,
+                                            trails.h if trails is not None else None, 0 if m is None else len(m), _ptr(m), C.byref(opts),
+                                            _ptr(stop), C.byref(res))
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "rmap_init_from_stereo")
+        if res.status == _abi.INIT_MAP_OK:
+            self._kfs = [first, second]
+        elif res.status == _abi.INIT_MAP_STOPPED:
+            self._kfs = []
+        return init_result(res, opts)
+
+    def align_to_plane(self, max_dist=0.05, seed=0, samples=None, trials=100, rows=True, check=True):
+        """map_align_to_plane on the resident tables (ptam_rmap_align_to_plane) -> dict: "se3", "info", and "pvs" (PVS_POINT_DT, the
+        point rows' pixel vectors after the call) when rows is set"""
+        opts = _plane_opts(self.lib, max_dist, seed, samples, trials)
+        n = self.counts()["n_points"]
+        se3, info = np.zeros(12), _abi.PlaneInfo()
+        out = np.zeros(max(n, 1), PVS_POINT_DT) if rows else None
+        rc = self.lib.rmap_align_to_plane(self.h, C.byref(opts), _pd(se3), C.byref(info), _ptr(out))
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "rmap_align_to_plane")
+        return dict(se3=se3, info=_plane_info(info), pvs=(out[:n] if rows else None))
+
+    def clear(self):
+        """MapMaker::Reset for the tables (ptam_rmap_clear): an empty map, the capacities kept"""
+        self.ctx._check(self.lib.rmap_clear(self.h), "rmap_clear")
+        self._kfs = []
+
     def publish(self, snapshot, check=True):
         """ptam_rmap_publish: the map as it stands into `snapshot` (a MapSnapshot) as its next generation -> dict(generation, map_id,
         n_points, n_kf, grew); nothing table-sized crosses the host link.  check=False: -> the status of a refused call."""
@@ -1149,6 +1217,24 @@ class ResidentMap:
         if getattr(self, "h", None):
             self.lib.rmap_destroy(self.h)
             self.h = None
+
+
+def init_result(res, opts=None):
+    """ptam_rmap_init_result as a dict: every scalar by its name, "homography" / "plane" as the info dicts of the stage calls, "depth"
+    SCENE_DEPTH_DT[2], "levels" EPIPOLAR_STATS_DT per visited level, "se3_aligner" / "tracker_pose" (12,), "counts" a dict"""
+    d = {f: getattr(res, f) for f in ("status", "n_matches", "baseline", "n_made", "n_subpix_failed", "n_behind_camera", "n_template_bad",
+                                      "n_bundles", "n_accepted", "n_outliers", "n_outlier_bundles", "converged",
+                                      "wiggle_scale_depth_normalized", "first_epipolar_point", "n_epipolar")}
+    h = res.homography
+    d["homography"] = {f: getattr(h, f) for f in ("status", "n_matches", "n_inliers", "best_trial", "ambiguous", "best_score")}
+    d["homography"].update(homography=np.array(h.homography).reshape(3, 3), sampson=np.array(h.sampson))
+    d["plane"] = _plane_info(res.plane)
+    d["depth"] = np.frombuffer(bytes(res.depth), dtype=SCENE_DEPTH_DT).copy()
+    nl = _abi.LEVELS if opts is None else min(max(opts.epipolar.n_levels, 0), _abi.LEVELS)
+    d["levels"] = np.frombuffer(bytes(res.levels), dtype=EPIPOLAR_STATS_DT)[:nl].copy()
+    d["se3_aligner"], d["tracker_pose"] = np.array(res.se3_aligner), np.array(res.tracker_pose)
+    d["counts"] = _counts(res.counts)
+    return d
 
 
 class FrameReport:
