@@ -1360,6 +1360,25 @@ int ptam_rmap_bundle_adjust(ptam_rmap*, const ptam_ba_opts* opts, int mode, cons
 int ptam_rmap_refind(ptam_rmap*, ptam_refinder*, const ptam_map_refind_opts*, int mode, int n_work, const void* work,
                      const volatile unsigned char* stop_flag, ptam_map_refind_result* res, ptam_map_meas* found_out,
                      int32_t* found_subpix, ptam_map_pair* never_out, int out_cap);
+/* ptam_rmap_refind(work = NULL) — MapMaker::ReFindNewlyMade / ReFindFromFailureQueue on the resident queue — with the visiting
+ * order decided on the device: neither queue comes down and no work list goes up.  mode: PTAM_MAP_REFIND_NEW_POINTS or
+ * PTAM_MAP_REFIND_FAILURE_QUEUE.  The result, the merged tables and the queue afterwards are those of ptam_rmap_refind(work = NULL);
+ * no list comes down (ptam_rmap_refind is the call that returns them).
+ *   NEW_POINTS      each entry's bBad byte is read where it lies; the good entries are compacted in queue order (the ordered
+ *                   compaction of the table edits: tile counts, scan, scatter) into the points and their entry numbers; each
+ *                   point's place among the good points in index order comes from a sort of the keys (point << 32 | place).
+ *                   The host reads the count of good points — one word, in one wait — for the pair count and the passes
+ *   FAILURE_QUEUE   the keys (kf << 32 | point) are sorted (:1074); duplicates stay, the pair kernel skips them as it does
+ * The sort: tiles of 1024 keys, each sorted by one workgroup of 1024 threads (a bitonic network: lane exchanges inside a wave, LDS
+ * across waves), then merge passes that place every key by a binary search in the sibling run.  Equal keys are equal records, so
+ * the output is a function of the input alone.
+ * A NEW_POINTS call that *stop_flag ended after it had visited a point reads one more word: that point's entry number, which says
+ * how many entries are popped.
+ * Moves up one level record per keyframe (at most PTAM_RMAP_KF_RECORD_BYTES each) when there is a pair to visit, and nothing else.
+ * Moves down 4 bytes in NEW_POINTS with a non-empty queue, 16 bytes of counts when there is a pair to visit, and 4 bytes more in
+ * the stopped case above.  No term grows with a queue's length. */
+int ptam_rmap_refind_queue(ptam_rmap*, ptam_refinder*, const ptam_map_refind_opts*, int mode, const volatile unsigned char* stop_flag,
+                           ptam_map_refind_result* res);
 /* ptam_map_apply_global_transform on the resident tables (the re-anchoring call): the poses are written into the second buffer
  * and come down into the mirror, the points move in place, and every point's RefreshPixelVectors runs against its source
  * keyframe's new pose straight into the point rows' pv (pv.world included).  out_rows (nullable, n_points ptam_pvs_point): the
@@ -1371,6 +1390,23 @@ int ptam_rmap_apply_global_transform(ptam_rmap*, const double se3_new_from_old[1
  * never (binary search).  PTAM_E_ARG with ptam_rmap_last_refusal = (PTAM_RMAP_OUTLIERS, the lowest offending list index).
  * Moves n_outliers * 16 bytes up and PTAM_RMAP_WORD_BYTES down. */
 int ptam_rmap_apply_outliers(ptam_rmap*, int n_outliers, const ptam_map_outlier* outliers, ptam_map_outliers_result* res);
+/* ptam_rmap_bundle_adjust followed by ptam_rmap_apply_outliers on the list it routed, as ONE call (MapMaker::BundleAdjust with its
+ * outlier loop, src/MapMaker.cc:768-933): the routed list stays where the routing kernel wrote it, in the call's work memory, and
+ * the outlier stage's kernels read it there.  What ptam_rmap_apply_outliers reads off the list on the host — the outliers per action
+ * — a kernel adds up (a ballot per wave and action, integer atomic adds: exact in any order; no atomic decides a position) into the
+ * call's count words, which come down with the stage's one wait.  Every entry of the routed list names a row of the bundle's
+ * selection and one of the three actions by construction; the checks that need the tables (the row's pair, no row twice, no
+ * NEVER_RETRY pair already in never) run as in ptam_rmap_apply_outliers.  The bundle's outlier count is on the host when Compute()
+ * returns: never and failure get room for that many more rows before the stage's first launch.
+ * res: as ptam_rmap_bundle_adjust.  outliers_res: as ptam_rmap_apply_outliers on that list; of an empty list (zero outliers per
+ * action, the three row counts as they stand) when the bundle did not run or reported none.
+ * The tables and the mirror end exactly as after the two calls.  A refusal by the outlier stage (PTAM_E_ARG, ptam_rmap_last_refusal =
+ * (PTAM_RMAP_OUTLIERS, the lowest offending list index)) leaves measurements, never, failure and bad as they were, while the accepted
+ * bundle's scatter has happened and the mirror has followed it: what the two calls leave.
+ * Moves a NOMINAL 97 bytes per bundle camera up, as ptam_rmap_bundle_adjust; down 32 + 4 n_kf bytes, 96 n_kf more when the bundle
+ * was accepted, and PTAM_RMAP_WORD_BYTES more when the bundle reported an outlier.  No term grows with the outlier count. */
+int ptam_rmap_bundle_adjust_routed(ptam_rmap*, const ptam_ba_opts* opts, int mode, const volatile unsigned char* abort_flag,
+                                   ptam_map_ba_result* res, ptam_map_outliers_result* outliers_res);
 /* ptam_map_handle_bad_points on the resident tables: the columns are the handle's six point-side tables (the surviving points'
  * bad bytes are zero by construction) and the serial column.  kept_out (nullable, room for n_points; the tracker's prevIndex) and new_index_out
  * (nullable, n_points) come down only when asked for.  Moves PTAM_RMAP_WORD_BYTES down, and what was asked for. */
@@ -1750,6 +1786,100 @@ int ptam_rmap_note_reports(ptam_rmap*, int n, ptam_frame_report* const* reports,
 int ptam_rmap_insert_keyframe_report(ptam_rmap*, ptam_refinder*, const ptam_kf* kf, const double pose12[12], int fixed,
                                      ptam_frame_report* report, const ptam_rmap_insert_opts*, ptam_rmap_insert_result*, int32_t* n_rows,
                                      int32_t* n_gone);
+
+/* ---- The mapmaker: one iteration of MapMaker::run() (src/MapMaker.cc:57-114) as ONE call on a resident map --------------------------
+ *      A ptam_mapmaker wraps a ptam_rmap, the ptam_refinder its re-finds go through and, optionally, the ptam_map_snapshot it
+ *      publishes into; it owns none of them (destroy it first).  It keeps what the reference's MapMaker keeps beside the map: the
+ *      keyframe queue (mvpKeyFrameQueue), the flags mbBundleConverged_Recent / _Full, mbBundleRunning and mbBundleAbortRequested,
+ *      the reset request, and the tracked frames' reports that wait to be counted.
+ *      THREADS.  ptam_mapmaker_step, _flags, _set_flags and _destroy belong to the mapmaker's thread, the thread of the map's
+ *      context.  ptam_mapmaker_add_keyframe, _note_frame, _queue_size, _request_reset, _reset_done and _released may be called from
+ *      the tracker's thread: they take the handle's mutex and touch no device.
+ *      LIFETIMES.  A keyframe clone and a report handed over stay the caller's objects and must stay alive and unchanged until
+ *      their tag comes back from ptam_mapmaker_released (a keyframe that has entered the map: as ptam_rmap_insert_keyframe_report
+ *      says, for as long as the map names it).  Every tag handed over comes back exactly once: after the step that used it, or
+ *      after the reset that dropped it.
+ *      ptam_mapmaker_step runs the body of the loop once, in the reference's order, each condition asked when its stage is
+ *      reached, with the queue as it stands then:
+ *        CHECK_RESET (before every stage): a requested reset runs ptam_rmap_clear, empties the keyframe queue and the pending
+ *          reports and releases their tags, sets the flags as Reset() does (:37-51: both converged, nothing running) and ends
+ *          the step with status PTAM_MM_RESET.
+ *        a map without a keyframe (:79) ends the step with status PTAM_MM_IDLE.
+ *        :88   !converged_recent && queue == 0: BundleAdjustRecent = ptam_rmap_bundle_adjust_routed(RECENT) under the handle's
+ *              abort byte.  With fewer than 8 keyframes it does not run and sets converged_recent (:790-793).  After Compute()
+ *              (:895-913): accepted clears converged_recent and converged_full, converged sets converged_recent.
+ *        :93   converged_recent && queue == 0: ReFindNewlyMade = ptam_rmap_refind_queue(NEW_POINTS), stopped by the byte that says
+ *              the keyframe queue is not empty (:1053).
+ *        :98   converged_recent && !converged_full && queue == 0: BundleAdjustAll = ptam_rmap_bundle_adjust_routed(ALL): accepted
+ *              clears converged_full, converged sets both.
+ *        :103  converged_recent && converged_full && draw && queue == 0: ReFindFromFailureQueue = ptam_rmap_refind_queue(
+ *              FAILURE_QUEUE).  The draw is splitmix64(failure_seed, n) % failure_period == 0 for the n-th draw, in place of
+ *              rand() % 20; as the reference's && does, a draw is made (and counted in `draws`) only when both flags are set.
+ *        :107  the pending reports of ptam_mapmaker_note_frame, all in one ptam_rmap_note_reports launch; then HandleBadPoints =
+ *              ptam_rmap_handle_bad_points.
+ *        :111  queue > 0: AddKeyFrameFromTopOfQueue: the front leaves the queue, ptam_make_keyframe_rest runs on a keyframe that
+ *              lacks it, ptam_rmap_insert_keyframe_report with the handle's insert options and the keyframe's depth; both
+ *              converged flags are cleared (:516-517).
+ *        with a snapshot: one ptam_rmap_publish at the end if a bundle was accepted, points were removed or a keyframe was inserted.
+ *      AddKeyFrame (:480-488) raises the abort byte only while a bundle runs, decided under the mutex that the step holds when it
+ *      sets and clears `bundle_running`.
+ *      The result: status; `stages`, a mask of the PTAM_MM_STAGE_* that ran (a RECENT bundle that did not run for want of
+ *      keyframes is not in it); each stage's own result struct, zero where it did not run; the flags, the queue size and the
+ *      draw count afterwards.  A stage's error is the step's return value; the tags of what that stage consumed are released, and
+ *      the result still says which stages had run and holds the flags, the queue size and the draw count as they stand.
+ *      Moves what its stages move, and nothing else. */
+typedef struct ptam_mapmaker ptam_mapmaker;
+typedef struct {
+    ptam_ba_opts ba;
+    ptam_map_refind_opts refind;
+    ptam_rmap_insert_opts insert;       /* epipolar.depth_mean / depth_sigma are the keyframe's own: ptam_mapmaker_add_keyframe */
+    int32_t failure_period;             /* 20: rand() % 20 (:103) */
+    uint64_t failure_seed;
+} ptam_mapmaker_opts;
+enum { PTAM_MM_RAN = 0, PTAM_MM_IDLE = 1, PTAM_MM_RESET = 2 };
+enum {
+    PTAM_MM_STAGE_BUNDLE_RECENT = 1, PTAM_MM_STAGE_REFIND_NEW = 2, PTAM_MM_STAGE_BUNDLE_ALL = 4, PTAM_MM_STAGE_REFIND_FAILURE = 8,
+    PTAM_MM_STAGE_NOTES = 16, PTAM_MM_STAGE_BAD_POINTS = 32, PTAM_MM_STAGE_ADD_KEYFRAME = 64, PTAM_MM_STAGE_PUBLISH = 128
+};
+typedef struct {
+    int32_t status, stages;
+    ptam_map_ba_result recent;
+    ptam_map_outliers_result recent_outliers;
+    ptam_map_refind_result refind_new;
+    ptam_map_ba_result all;
+    ptam_map_outliers_result all_outliers;
+    ptam_map_refind_result refind_failure;
+    ptam_rmap_note_result notes;
+    ptam_map_bad_points_result bad_points;
+    ptam_rmap_insert_result insert;
+    int32_t insert_rows, insert_gone;
+    ptam_map_publish_result publish;
+    int32_t converged_recent, converged_full, queue_size, pad_;
+    uint64_t draws;
+} ptam_mapmaker_step_result;
+/* the reference's: ptam_ba_opts_default, max_pairs_per_pass 0, ptam_epipolar_opts_default with the levels {3,0,1,2} of :511-514,
+ * target_kf -1, nothing skipped, failure_period 20, failure_seed 0.  PTAM_E_ARG: a null pointer. */
+int ptam_mapmaker_opts_default(ptam_mapmaker_opts*);
+/* snapshot, opts: nullable (no publish; the defaults).  The flags start as Reset() leaves them.  PTAM_E_ARG: a null map, finder
+ * or out; failure_period < 1. */
+int ptam_mapmaker_create(ptam_rmap*, ptam_refinder*, ptam_map_snapshot* snapshot, const ptam_mapmaker_opts* opts, ptam_mapmaker** out);
+int ptam_mapmaker_destroy(ptam_mapmaker*);
+/* MapMaker::AddKeyFrame (:480-488): the clone, its pose and flag, the tracker's report of the frame, the scene depth the
+ * epipolar search of this keyframe uses, and the tag that names clone and report in ptam_mapmaker_released.  PTAM_E_ARG: a null
+ * handle, clone, pose or report. */
+int ptam_mapmaker_add_keyframe(ptam_mapmaker*, const ptam_kf* clone, const double pose12[12], int fixed, ptam_frame_report* report,
+                               double depth_mean, double depth_sigma, int64_t tag);
+/* a tracked frame's report, to be counted by the next step's ptam_rmap_note_reports */
+int ptam_mapmaker_note_frame(ptam_mapmaker*, ptam_frame_report* report, int64_t tag);
+int ptam_mapmaker_queue_size(ptam_mapmaker*, int32_t* out);
+int ptam_mapmaker_request_reset(ptam_mapmaker*);   /* MapMaker::RequestReset (:116-120) */
+int ptam_mapmaker_reset_done(ptam_mapmaker*, int32_t* out);   /* MapMaker::ResetDone */
+int ptam_mapmaker_flags(ptam_mapmaker*, int32_t* converged_recent, int32_t* converged_full, int32_t* bundle_running);
+/* for tests, and for a host that resumes a map */
+int ptam_mapmaker_set_flags(ptam_mapmaker*, int converged_recent, int converged_full);
+/* up to cap tags the mapmaker has finished with, oldest first, removed from its list; *n: how many */
+int ptam_mapmaker_released(ptam_mapmaker*, int cap, int64_t* tags, int32_t* n);
+int ptam_mapmaker_step(ptam_mapmaker*, ptam_mapmaker_step_result*);
 
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,

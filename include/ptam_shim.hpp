@@ -11,10 +11,13 @@
 #define PTAM_SHIM_HPP
 
 #include <array>
+#include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -1315,6 +1318,24 @@ public:
         }
         return r;
     }
+    // BundleAdjust followed by ApplyBundleOutliers on the list it routed, as one call: the list stays on the device
+    struct BundleAdjustRoutedResult {
+        ptam_map_ba_result result;
+        ptam_map_outliers_result outliers;
+    };
+    BundleAdjustRoutedResult BundleAdjustRouted(int mode, const ptam_ba_opts* opts = nullptr, const volatile unsigned char* abort_flag = nullptr) {
+        BundleAdjustRoutedResult r{};
+        check(ptam_rmap_bundle_adjust_routed(h_, opts, mode, abort_flag, &r.result, &r.outliers), "ptam_rmap_bundle_adjust_routed");
+        return r;
+    }
+    // ReFind(pWork == nullptr) with the visiting order decided on the device: ReFindNewlyMade (PTAM_MAP_REFIND_NEW_POINTS) or
+    // ReFindFromFailureQueue (PTAM_MAP_REFIND_FAILURE_QUEUE) straight from the resident queue, which is popped / cleared
+    ptam_map_refind_result ReFindQueue(ReFinder& finder, int mode, const bool* pbStop = nullptr, const ptam_map_refind_opts* opts = nullptr) {
+        ptam_map_refind_result r{};
+        check(ptam_rmap_refind_queue(h_, finder.handle(), opts, mode, reinterpret_cast<const volatile unsigned char*>(pbStop), &r),
+              "ptam_rmap_refind_queue");
+        return r;
+    }
     // ApplyGlobalTransformationToMap on the resident poses, points and point rows; the ptam_pvs_point rows when bRows is set
     std::vector<ptam_pvs_point> ApplyGlobalTransformationToMap(const SE3& se3NewFromOld, bool bRows = true) {
         std::vector<ptam_pvs_point> rows(bRows ? (size_t)Counts().n_points : 0);
@@ -1473,6 +1494,69 @@ private:
     }
     ptam_rmap* h_ = nullptr;
     ptam_rmap_init_result init_{};
+};
+
+// class MapMaker   include/MapMaker.h:61, src/MapMaker.cc:57-114 — the mapmaker's thread over a ResidentMap (ptam_mapmaker): the keyframe
+// queue, the mbBundleConverged_* flags and one iteration of run() as Step().  AddKeyFrame, NoteFrame, QueueSize, RequestReset,
+// ResetDone and Released may be called from the tracker's thread; Step and Run belong to the thread of the map's context.  A
+// keyframe clone and a report handed over stay alive until their tag comes back from Released().
+class MapMaker {
+public:
+    MapMaker(ResidentMap& map, ReFinder& finder, MapSnapshot* snapshot = nullptr, const ptam_mapmaker_opts* opts = nullptr) {
+        check(ptam_mapmaker_create(map.handle(), finder.handle(), snapshot ? snapshot->handle() : nullptr, opts, &h_), "ptam_mapmaker_create");
+    }
+    ~MapMaker() { ptam_mapmaker_destroy(h_); }
+    MapMaker(const MapMaker&) = delete;
+    MapMaker& operator=(const MapMaker&) = delete;
+    static ptam_mapmaker_opts DefaultOpts() {
+        ptam_mapmaker_opts o;
+        check(ptam_mapmaker_opts_default(&o), "ptam_mapmaker_opts_default");
+        return o;
+    }
+    // void MapMaker::AddKeyFrame(KeyFrame &k)   src/MapMaker.cc:480-488: k is the caller's clone
+    void AddKeyFrame(const KeyFrame& k, const SE3& se3CfromW, bool bFixed, FrameReport& report, double dSceneDepthMean, double dSceneDepthSigma,
+                     int64_t nTag) {
+        check(ptam_mapmaker_add_keyframe(h_, k.handle(), reinterpret_cast<const double*>(&se3CfromW), bFixed, report.handle(), dSceneDepthMean,
+                                         dSceneDepthSigma, nTag),
+              "ptam_mapmaker_add_keyframe");
+    }
+    void NoteFrame(FrameReport& report, int64_t nTag) { check(ptam_mapmaker_note_frame(h_, report.handle(), nTag), "ptam_mapmaker_note_frame"); }
+    int QueueSize() const {
+        int32_t n = 0;
+        check(ptam_mapmaker_queue_size(h_, &n), "ptam_mapmaker_queue_size");
+        return n;
+    }
+    void RequestReset() { check(ptam_mapmaker_request_reset(h_), "ptam_mapmaker_request_reset"); }
+    bool ResetDone() const {
+        int32_t n = 0;
+        check(ptam_mapmaker_reset_done(h_, &n), "ptam_mapmaker_reset_done");
+        return n != 0;
+    }
+    std::vector<int64_t> Released() {
+        std::vector<int64_t> out, buf(64);
+        for (int32_t n = 64; n == 64;) {
+            check(ptam_mapmaker_released(h_, 64, buf.data(), &n), "ptam_mapmaker_released");
+            out.insert(out.end(), buf.begin(), buf.begin() + n);
+        }
+        return out;
+    }
+    // the body of run()'s loop, once (:86-112)
+    ptam_mapmaker_step_result Step() {
+        ptam_mapmaker_step_result r;
+        check(ptam_mapmaker_step(h_, &r), "ptam_mapmaker_step");
+        return r;
+    }
+    // void MapMaker::run()   src/MapMaker.cc:57-114, until `stop` is set, with the reference's sleep(5) (:69)
+    void Run(const std::atomic<bool>& stop) {
+        while (!stop.load()) {
+            std::this_thread::sleep_for(std::chrono::milliseconds(5));
+            Step();
+        }
+    }
+    ptam_mapmaker* handle() const { return h_; }
+
+private:
+    ptam_mapmaker* h_ = nullptr;
 };
 
 // class Bundle (include/Bundle.h:106-152)

@@ -320,6 +320,27 @@ class RmapNoteResult(C.Structure):
     _fields_ = [("n_records", C.c_int32), ("n_gone", C.c_int32)]
 
 
+MM_RAN, MM_IDLE, MM_RESET = range(3)
+(MM_STAGE_BUNDLE_RECENT, MM_STAGE_REFIND_NEW, MM_STAGE_BUNDLE_ALL, MM_STAGE_REFIND_FAILURE, MM_STAGE_NOTES, MM_STAGE_BAD_POINTS,
+ MM_STAGE_ADD_KEYFRAME, MM_STAGE_PUBLISH) = (1 << i for i in range(8))
+
+
+class MapmakerOpts(C.Structure):
+    """ptam_mapmaker_opts"""
+    _fields_ = [("ba", BaOpts), ("refind", MapRefindOpts), ("insert", RmapInsertOpts), ("failure_period", C.c_int32),
+                ("failure_seed", C.c_uint64)]
+
+
+class MapmakerStepResult(C.Structure):
+    """ptam_mapmaker_step_result (one iteration of MapMaker::run(), src/MapMaker.cc:57-114)"""
+    _fields_ = [("status", C.c_int32), ("stages", C.c_int32), ("recent", MapBaResult), ("recent_outliers", MapOutliersResult),
+                ("refind_new", MapRefindResult), ("all", MapBaResult), ("all_outliers", MapOutliersResult),
+                ("refind_failure", MapRefindResult), ("notes", RmapNoteResult), ("bad_points", MapBadPointsResult),
+                ("insert", RmapInsertResult), ("insert_rows", C.c_int32), ("insert_gone", C.c_int32), ("publish", MapPublishResult),
+                ("converged_recent", C.c_int32), ("converged_full", C.c_int32), ("queue_size", C.c_int32), ("pad_", C.c_int32),
+                ("draws", C.c_uint64)]
+
+
 class SbiAlignment(C.Structure):
     """ptam_sbi_alignment (SmallBlurryImage::CalcSBIRotation, src/ImageProcess.cc:313-495)"""
     _fields_ = [("se2_rot", C.c_double * 4), ("se2_trans", C.c_double * 2), ("score", C.c_double), ("mean_offset", C.c_double),
@@ -529,8 +550,10 @@ PROTOTYPES = {
     "rmap_traffic": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "rmap_bundle_adjust": (_i, [_vp, C.POINTER(BaOpts), _i, _vp, C.POINTER(MapBaResult), _vp, _i, _vp, _vp]),
     "rmap_refind": (_i, [_vp, _vp, C.POINTER(MapRefindOpts), _i, _i, _vp, _vp, C.POINTER(MapRefindResult), _vp, _vp, _vp, _i]),
+    "rmap_refind_queue": (_i, [_vp, _vp, C.POINTER(MapRefindOpts), _i, _vp, C.POINTER(MapRefindResult)]),
     "rmap_apply_global_transform": (_i, [_vp, _pd, _vp]),
     "rmap_apply_outliers": (_i, [_vp, _i, _vp, C.POINTER(MapOutliersResult)]),
+    "rmap_bundle_adjust_routed": (_i, [_vp, C.POINTER(BaOpts), _i, _vp, C.POINTER(MapBaResult), C.POINTER(MapOutliersResult)]),
     "rmap_handle_bad_points": (_i, [_vp, C.POINTER(MapBadPointsResult), _vp, _vp]),
     "rmap_add_points": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "rmap_add_keyframe": (_i, [_vp, _vp, _pd, _i, _i, _vp]),
@@ -566,6 +589,18 @@ PROTOTYPES = {
     "rmap_note_reports": (_i, [_vp, _i, _vp, C.POINTER(RmapNoteResult)]),
     "rmap_insert_keyframe_report": (_i, [_vp, _vp, _vp, _pd, _i, _vp, C.POINTER(RmapInsertOpts), C.POINTER(RmapInsertResult),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mapmaker_opts_default": (_i, [C.POINTER(MapmakerOpts)]),
+    "mapmaker_create": (_i, [_vp, _vp, _vp, C.POINTER(MapmakerOpts), _ppv]),
+    "mapmaker_destroy": (_i, [_vp]),
+    "mapmaker_add_keyframe": (_i, [_vp, _vp, _pd, _i, _vp, _d, _d, C.c_int64]),
+    "mapmaker_note_frame": (_i, [_vp, _vp, C.c_int64]),
+    "mapmaker_queue_size": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "mapmaker_request_reset": (_i, [_vp]),
+    "mapmaker_reset_done": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "mapmaker_flags": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mapmaker_set_flags": (_i, [_vp, _i, _i]),
+    "mapmaker_released": (_i, [_vp, _i, _vp, C.POINTER(C.c_int32)]),
+    "mapmaker_step": (_i, [_vp, C.POINTER(MapmakerStepResult)]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

@@ -356,7 +356,7 @@ void mba_layout(Carver& c, Carver& pin, int K, int N, int M, MbaWork& w) {
 }
 
 int mba_core(MapStage& s, const ptam_ba_opts* opts, int mode, const MbaTables& t, const MbaWork& w, const volatile unsigned char* abort_flag,
-             ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids) {
+             ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids, int* n_routed) {
     ptam_ctx* ctx = s.ctx;
     const int K = t.K, N = t.N, M = t.M, nb = (M + MBA_BLOCK - 1) / MBA_BLOCK;
     BaGuard g;
@@ -430,7 +430,7 @@ int mba_core(MapStage& s, const ptam_ba_opts* opts, int mode, const MbaTables& t
     }
     // ---- the outlier routing (:916-932)
     const int n_out = std::min(r.n_out, h.n_meas);
-    if (outliers && n_out > 0) {
+    if ((outliers || n_routed) && n_out > 0) {
         void* hs = nullptr;   // the step ends, read by the ordering kernel through host-mapped memory; their number is known only now,
                               // and the selection's words in the pinned block have been read: a request of its own
         if (int rc = ctx_pinned(ctx, (size_t)std::max(r.n_steps, 1) * 4, &hs)) return rc;
@@ -441,8 +441,9 @@ int mba_core(MapStage& s, const ptam_ba_opts* opts, int mode, const MbaTables& t
         hipLaunchKernelGGL(mba_route_prep_kernel, grid, dim3(256), 0, st, a, (const int*)w.ord, n_out, h.n_meas, w.orow, w.opt, w.first);
         hipLaunchKernelGGL(mba_route_kernel, grid, dim3(256), 0, st, a, n_out, (const int*)w.orow, (const int*)w.opt, (const int*)w.first, w.out);
         HIP_TRY(hipGetLastError());
-        STAGE_TRY(s.down(outliers, w.out, (size_t)n_out * sizeof(ptam_map_outlier)));
+        if (outliers) STAGE_TRY(s.down(outliers, w.out, (size_t)n_out * sizeof(ptam_map_outlier)));
     }
+    if (n_routed) *n_routed = n_out;
     if (point_ids) STAGE_TRY(s.down(point_ids, a.pt_of, (size_t)h.n_points * 4));
     if (cam_kf && C > 0) std::memcpy(cam_kf, ckf.data(), (size_t)C * 4);
     res->ran = 1;

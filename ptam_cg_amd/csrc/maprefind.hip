@@ -8,6 +8,8 @@
 // and after the last pass the merged tables: mr_order_kernel (NEW_POINTS only, where visiting order is point-major: the rows'
 // places in (kf, point) order by one ordered compaction over the transposed pair grid) and mr_merge_kernel (two sorted lists
 // into one, each row placed by a binary search in the other list).  Every order is fixed: the same input gives the same bits.
+// mr_core uploads the work lists of a host plan (maprefind_plan.h) and calls mr_run, which is everything behind the lists;
+// ptam_rmap_refind_queue (maprmap.hip) has kernels build the lists from the resident queue and calls mr_run itself.
 #include <algorithm>
 
 #include "maptables_internal.h"
@@ -229,10 +231,22 @@ int mr_check_call(ptam_ctx* ctx, const ptam_refinder* finder, const ptam_map_ref
     return PTAM_OK;
 }
 
+// what the layout and the passes need of a host plan
+MrShape mr_shape(const MrPlan& plan) {
+    MrShape sh;
+    sh.mode = plan.mode;
+    sh.kf0 = plan.kf0;
+    sh.n_wp = (int)plan.wpts.size();
+    sh.n_wq = (int)plan.wq.size();
+    sh.pairs = plan.pairs;
+    sh.per_pass = plan.per_pass;
+    return sh;
+}
+void mr_layout(Carver& c, Carver& pin, int n_kf, const MrPlan& plan, bool merged, MrWork& w) { mr_layout_shape(c, pin, n_kf, mr_shape(plan), merged, w); }
 // the call's lists (sized by the call), then the pass's work arrays (sized by the pass)
-void mr_layout(Carver& c, Carver& pin, int n_kf, const MrPlan& plan, bool merged, MrWork& w) {
+void mr_layout_shape(Carver& c, Carver& pin, int n_kf, const MrShape& plan, bool merged, MrWork& w) {
     const bool ordered = merged && plan.mode == PTAM_MAP_REFIND_NEW_POINTS;   // (visiting order is point-major there: mr_order_kernel)
-    const size_t Pz = (size_t)plan.pairs, Wz = std::max(plan.wpts.size(), plan.wq.size() * 2);
+    const size_t Pz = (size_t)plan.pairs, Wz = std::max((size_t)plan.n_wp, (size_t)plan.n_wq * 2);
     w.Ls = c.room<KfLevels>((size_t)n_kf);
     w.w0 = c.room<int>(Wz);
     w.w1 = c.room<int>(Wz);
@@ -248,25 +262,33 @@ void mr_layout(Carver& c, Carver& pin, int n_kf, const MrPlan& plan, bool merged
     w.h_cnt = pin.piece<int>(MR_COUNTS);
 }
 
+// the work lists of a host plan up, then mr_run; what the stop leaves of the queue is the plan's to say
 int mr_core(MapStage& s, ptam_refinder* finder, const MrTables& t, const MrPlan& plan, const MrWork& w, const volatile unsigned char* stop_flag,
             ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix, ptam_map_pair* never_out) {
-    const int P = plan.pairs, n_kf = t.n_kf;
-    const bool merged = t.d_meas_merged || t.d_never_merged, ordered = merged && plan.mode == PTAM_MAP_REFIND_NEW_POINTS;
-    hipStream_t st = s.st;
-    // ---- up: the level records and the work lists
-    std::vector<KfLevels> hl((size_t)n_kf);
-    for (int k = 0; k < n_kf; k++) hl[(size_t)k] = t.kfs[k]->L;
-    STAGE_TRY(s.up(w.Ls, hl.data(), hl.size() * sizeof(KfLevels)));
     STAGE_TRY(s.up(w.w0, plan.wpts.data(), plan.wpts.size() * 4));
     STAGE_TRY(s.up(w.w1, plan.wrank.data(), plan.wrank.size() * 4));
     STAGE_TRY(s.up(w.w0, plan.wq.data(), plan.wq.size() * sizeof(ptam_map_pair)));
+    STAGE_TRY(mr_run(s, finder, t, mr_shape(plan), w, stop_flag, res, found_out, found_subpix, never_out));
+    mr_plan_consumed(plan, res->n_pairs, res->stopped != 0, &res->points_consumed, &res->n_bad_points);
+    return PTAM_OK;
+}
+
+int mr_run(MapStage& s, ptam_refinder* finder, const MrTables& t, const MrShape& plan, const MrWork& w, const volatile unsigned char* stop_flag,
+           ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix, ptam_map_pair* never_out) {
+    const int P = plan.pairs, n_kf = t.n_kf;
+    const bool merged = t.d_meas_merged || t.d_never_merged, ordered = merged && plan.mode == PTAM_MAP_REFIND_NEW_POINTS;
+    hipStream_t st = s.st;
+    // ---- up: the level records
+    std::vector<KfLevels> hl((size_t)n_kf);
+    for (int k = 0; k < n_kf; k++) hl[(size_t)k] = t.kfs[k]->L;
+    STAGE_TRY(s.up(w.Ls, hl.data(), hl.size() * sizeof(KfLevels)));
     HIP_TRY(hipMemsetAsync(w.cnt, 0, MR_COUNTS * 4, st));
     if (ordered) HIP_TRY(hipMemsetAsync(w.slot, 0, (size_t)P * 4, st));   // (a stopped call leaves pairs unvisited)
     MrArgs a;
     a.mode = plan.mode;
     a.n_kf = n_kf;
     a.kf0 = plan.kf0;
-    a.n_wp = (int)plan.wpts.size();
+    a.n_wp = plan.n_wp;
     a.wpts = w.w0;
     a.wrank = w.w1;
     a.wq = (const ptam_map_pair*)w.w0;
@@ -306,7 +328,6 @@ int mr_core(MapStage& s, ptam_refinder* finder, const MrTables& t, const MrPlan&
         visited += a.n;
     }
     r.n_pairs = visited;
-    mr_plan_consumed(plan, visited, r.stopped != 0, &r.points_consumed, &r.n_bad_points);
     // ---- the merged tables: the rows' places in (kf, point) order where the visiting order is point-major, then the two merges
     const int *order_f = nullptr, *order_n = nullptr;
     if (ordered) {

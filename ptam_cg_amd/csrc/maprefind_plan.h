@@ -20,6 +20,14 @@ struct MrPlan {
     int per_pass = 0;                     // NEW_POINTS: whole points, at least one
 };
 
+// the pairs in flight per pass: the caller's bound (0: the default), in NEW_POINTS whole points and at least one, never more than
+// the call visits
+inline int mr_per_pass(int mode, int n_kf, int max_pairs_per_pass, int pairs) {
+    int per_pass = max_pairs_per_pass > 0 ? max_pairs_per_pass : (int)MR_DEFAULT_PASS;
+    if (mode == PTAM_MAP_REFIND_NEW_POINTS && n_kf > 0) per_pass = n_kf * (per_pass / n_kf > 0 ? per_pass / n_kf : 1);
+    return per_pass > pairs ? pairs : per_pass;
+}
+
 // bad_of(entry, point): bBad of a NEW_POINTS entry's point (:1056-1059).  false: the work list is refused.
 template <class BadOf>
 inline bool mr_plan(int mode, int n_kf, int n_points, int n_work, const void* work, BadOf bad_of, int max_pairs_per_pass, MrPlan* out) {
@@ -60,9 +68,7 @@ inline bool mr_plan(int mode, int n_kf, int n_points, int n_work, const void* wo
         return false;
     if (p.bound >= (1ll << 31)) return false;
     p.pairs = (int)total;
-    int per_pass = max_pairs_per_pass > 0 ? max_pairs_per_pass : (int)MR_DEFAULT_PASS;
-    if (mode == PTAM_MAP_REFIND_NEW_POINTS && n_kf > 0) per_pass = n_kf * (per_pass / n_kf > 0 ? per_pass / n_kf : 1);
-    p.per_pass = per_pass > p.pairs ? p.pairs : per_pass;
+    p.per_pass = mr_per_pass(mode, n_kf, max_pairs_per_pass, p.pairs);
     *out = std::move(p);
     return true;
 }

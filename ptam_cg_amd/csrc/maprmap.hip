@@ -7,12 +7,15 @@
 //   ptam_rmap_note_tracked          the tracker's iteration set into the two counts (src/Tracker.cc:987-998)
 //   ptam_rmap_scene_depth           ptam_map_scene_depth's kernel (mapalign.hip)
 //   ptam_rmap_bundle_adjust         mba_core (mapba.hip) on the handle's buffers: adjusted in place, the poses into the mirror
+//   ptam_rmap_bundle_adjust_routed  the two above as one call: the routed outlier list stays in the bundle's work memory
 //   ptam_rmap_refind                mr_core (maprefind.hip): the merged tables into the second buffers, the resident queue popped
+//   ptam_rmap_refind_queue          the same from the resident queue, the work lists built by kernels (maptables.hip): mr_run
 //   ptam_rmap_apply_global_transform  map_apply_kernel (mapalign.hip): the pixel vectors straight into the point rows
 // A keyframe into the map is maprmap_keyframe.hip; serials, frame reports and the map to the tracker are maprmap_publish.hip; the
 // handle itself and the rule of its two buffers per table are rmap_internal.h.
-// The kernels here check (rm_check_*) and count (rm_note_tracked_kernel).  Their atomics: atomicMin on a refusal word (only a
-// thread that has found an offence issues one), atomicMin on an owner word per point / per row, integer atomicAdd on the counts.
+// The kernels here check (rm_check_*) and count (rm_note_tracked_kernel, rm_outliers_tally_kernel).  Their atomics: atomicMin on a
+// refusal word (only a thread that has found an offence issues one), atomicMin on an owner word per point / per row, integer
+// atomicAdd on the counts.
 // Nothing is handed between workgroups inside a launch: an owner word is written by one launch and compared by the next.
 #include <algorithm>
 #include <atomic>
@@ -102,6 +105,19 @@ __global__ void __launch_bounds__(256) rm_outliers_twice_kernel(int n, const pta
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     if (owner[o[i].meas] != (unsigned)i) rm_offend(err, i);
+}
+
+// ptam_rmap_bundle_adjust_routed: what mc_outliers_tally counts on the host, one thread per routed outlier: how many of each action
+// (a ballot per action and wave, one integer atomicAdd per wave and action that occurs: exact in any order).  tally: three ints,
+// zeroed by the caller, in the order of the actions
+__global__ void __launch_bounds__(256) rm_outliers_tally_kernel(int n, const ptam_map_outlier* __restrict__ o, int* __restrict__ tally) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int action = i < n ? o[i].action : 0;
+#pragma unroll
+    for (int a = PTAM_MAP_OUT_POINT_BAD; a <= PTAM_MAP_OUT_NEVER_RETRY; a++) {
+        const unsigned long long mk = __ballot(action == a);
+        if ((threadIdx.x & 63) == 0 && mk) atomicAdd(tally + (a - PTAM_MAP_OUT_POINT_BAD), __popcll(mk));
+    }
 }
 
 // NEW_POINTS from the resident queue: bBad of each entry's point, for the host's walk of :1056-1059
@@ -244,6 +260,46 @@ static int rm_refind_work(ptam_rmap* m, int mode, int* n_work, const void** work
         STAGE_TRY(s.down(bad.data(), d_bad, (size_t)n));
     }
     HIP_TRY(ptam_stream_wait(s.st));
+    return PTAM_OK;
+}
+
+// ---- what ptam_rmap_refind and ptam_rmap_refind_queue share around mr_core / mr_run
+// the handle's tables as the re-find core takes them: the merged tables go into the second buffers
+static MrTables rm_refind_tables(ptam_rmap* m) {
+    MrTables t = {};
+    t.n_kf = m->n[RM_N_KF];
+    t.n_points = m->n[RM_N_POINTS];
+    t.n_meas = m->n[RM_N_MEAS];
+    t.n_never = m->n[RM_N_NEVER];
+    t.kfs = m->kfs.data();
+    t.d_poses = rm_poses(m);
+    t.d_points = rm_points(m);
+    t.d_meas = rm_meas(m);
+    t.d_never = rm_never(m);
+    t.d_meas_merged = rm_meas_alt(m);
+    t.d_never_merged = rm_never_alt(m);
+    return t;
+}
+// after the call's wait: the merged tables become the map's
+static void rm_refind_commit(ptam_rmap* m, const ptam_map_refind_result& r) {
+    m->t[PTAM_RMAP_MEAS].cur ^= 1;
+    m->t[PTAM_RMAP_NEVER].cur ^= 1;
+    m->n[RM_N_MEAS] += r.n_found;
+    m->n[RM_N_NEVER] += r.n_never;
+}
+// the resident queue was the work: points_consumed entries leave mqNewQueue from the front (:1055); mvFailureQueue is cleared
+// unless the call was stopped (:1080)
+static int rm_queue_consumed(ptam_rmap* m, int mode, const ptam_map_refind_result& r) {
+    if (mode == PTAM_MAP_REFIND_NEW_POINTS && r.points_consumed > 0) {
+        const int left = m->n[RM_N_NEW] - r.points_consumed;
+        if (left > 0) {
+            HIP_TRY(hipMemcpyAsync(rm_new_queue_alt(m), rm_new_queue(m) + r.points_consumed, (size_t)left * 4, hipMemcpyDeviceToDevice, m->ctx->stream));
+            HIP_TRY(ptam_stream_wait(m->ctx->stream));
+            m->t[PTAM_RMAP_NEW_QUEUE].cur ^= 1;
+        }
+        m->n[RM_N_NEW] = left;
+    }
+    if (mode == PTAM_MAP_REFIND_FAILURE_QUEUE && !r.stopped) m->n[RM_N_FAILURE] = 0;
     return PTAM_OK;
 }
 
@@ -437,7 +493,7 @@ int ptam_rmap_refind(ptam_rmap* m, ptam_refinder* finder, const ptam_map_refind_
     ARG_TRY(mode == PTAM_MAP_REFIND_KEYFRAME || mode == PTAM_MAP_REFIND_NEW_POINTS || mode == PTAM_MAP_REFIND_FAILURE_QUEUE);
     ARG_TRY(work || n_work == 0);
     ARG_TRY(work || mode != PTAM_MAP_REFIND_KEYFRAME);
-    const int K = m->n[RM_N_KF], N = m->n[RM_N_POINTS], M = m->n[RM_N_MEAS], V = m->n[RM_N_NEVER], Q = m->n[RM_N_NEW];
+    const int K = m->n[RM_N_KF], N = m->n[RM_N_POINTS], M = m->n[RM_N_MEAS], V = m->n[RM_N_NEVER];
     if (K == 0) {
         ARG_TRY(n_work == 0 || mode != PTAM_MAP_REFIND_KEYFRAME);
         *res = ptam_map_refind_result{};
@@ -461,39 +517,100 @@ int ptam_rmap_refind(ptam_rmap* m, ptam_refinder* finder, const ptam_map_refind_
     if (int rc = rm_room(m, PTAM_RMAP_NEVER, V + plan.bound)) return rc;
     ptam_map_refind_result r = mr_plan_nothing(plan, stop_flag && *stop_flag);
     if (plan.pairs > 0) {
-        MrTables t = {};
-        t.n_kf = K;
-        t.n_points = N;
-        t.n_meas = M;
-        t.n_never = V;
-        t.kfs = m->kfs.data();
-        t.d_poses = rm_poses(m);
-        t.d_points = rm_points(m);
-        t.d_meas = rm_meas(m);
-        t.d_never = rm_never(m);
-        t.d_meas_merged = rm_meas_alt(m);
-        t.d_never_merged = rm_never_alt(m);
+        const MrTables t = rm_refind_tables(m);
         MrWork w;
         MapStage s = rm_stage(m);
         STAGE_TRY(s.carve([&](Carver& c, Carver& pin) { mr_layout(c, pin, K, plan, true, w); }));
         STAGE_TRY(mr_core(s, finder, t, plan, w, stop_flag, &r, found_out, found_subpix, never_out));
         HIP_TRY(ptam_stream_wait(s.st));
-        // the merged tables become the map's
-        m->t[PTAM_RMAP_MEAS].cur ^= 1;
-        m->t[PTAM_RMAP_NEVER].cur ^= 1;
-        m->n[RM_N_MEAS] = M + r.n_found;
-        m->n[RM_N_NEVER] = V + r.n_never;
+        rm_refind_commit(m, r);
     }
-    if (from_queue && mode == PTAM_MAP_REFIND_NEW_POINTS && r.points_consumed > 0) {   // popped from the front (:1055)
-        const int left = Q - r.points_consumed;
-        if (left > 0) {
-            HIP_TRY(hipMemcpyAsync(rm_new_queue_alt(m), rm_new_queue(m) + r.points_consumed, (size_t)left * 4, hipMemcpyDeviceToDevice, m->ctx->stream));
-            HIP_TRY(ptam_stream_wait(m->ctx->stream));
-            m->t[PTAM_RMAP_NEW_QUEUE].cur ^= 1;
+    if (from_queue)
+        if (int rc = rm_queue_consumed(m, mode, r)) return rc;
+    *res = r;
+    return PTAM_OK;
+}
+
+// ptam_rmap_refind(work = NULL) with the work lists built where the queue lies: neither queue comes down, no list goes up.  The
+// host learns the count of good new points (one word, one wait), from which pairs, per_pass and the passes follow; the layout is for
+// the queue's length, known before.
+int ptam_rmap_refind_queue(ptam_rmap* m, ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, const volatile unsigned char* stop_flag,
+                           ptam_map_refind_result* res) {
+    ARG_TRY(m && finder && res);
+    ARG_TRY(mode == PTAM_MAP_REFIND_NEW_POINTS || mode == PTAM_MAP_REFIND_FAILURE_QUEUE);
+    const int K = m->n[RM_N_KF], M = m->n[RM_N_MEAS], V = m->n[RM_N_NEVER], Q = m->n[RM_N_NEW], F = m->n[RM_N_FAILURE];
+    *res = ptam_map_refind_result{};
+    if (K == 0) return PTAM_OK;
+    if (int rc = mr_check_call(m->ctx, finder, opts, mode, K, m->kfs.data())) return rc;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    const bool new_points = mode == PTAM_MAP_REFIND_NEW_POINTS;
+    const int n_work = new_points ? Q : F;
+    const long long bound = new_points ? (long long)K * Q : (long long)F;   // the pair count the capacities are held against (mr_plan)
+    ARG_TRY(bound < (1ll << 31) && bound + M < (1ll << 31) && bound + V < (1ll << 31));
+    if (int rc = rm_room(m, PTAM_RMAP_MEAS, M + bound)) return rc;
+    if (int rc = rm_room(m, PTAM_RMAP_NEVER, V + bound)) return rc;
+    const int max_per_pass = opts ? opts->max_pairs_per_pass : 0;
+    const bool stop_now = stop_flag && *stop_flag;
+    ptam_map_refind_result r = {};
+    MrShape sh = {};
+    sh.mode = mode;
+    int n_good = 0;
+    if (n_work > 0) {
+        sh.n_wp = new_points ? Q : 0;
+        sh.n_wq = new_points ? 0 : F;
+        sh.pairs = (int)bound;
+        sh.per_pass = mr_per_pass(mode, K, max_per_pass, sh.pairs);
+        MrWork w;
+        int *wentry, *tiles, *d_good, *h_word;
+        unsigned long long *keys_a, *keys_b;
+        MapStage s = rm_stage(m);
+        STAGE_TRY(s.carve([&](Carver& c, Carver& pin) {
+            mr_layout_shape(c, pin, K, sh, true, w);
+            wentry = c.room<int>(new_points ? (size_t)Q : 0);
+            tiles = c.room<int>(new_points ? (size_t)mt_tiles(Q) : 0);
+            keys_a = c.piece<unsigned long long>((size_t)n_work);
+            keys_b = c.piece<unsigned long long>((size_t)n_work);
+            d_good = c.piece<int>(1);
+            h_word = pin.piece<int>(1);
+        }));
+        // ---- the work lists, into w.w0 / w.w1
+        if (new_points) {
+            if (int rc = mt_queue_good_core(s.st, Q, rm_new_queue(m), rm_bad(m), w.w0, wentry, tiles, d_good)) return rc;
+            STAGE_TRY(s.down(h_word, d_good, sizeof(int)));
+            HIP_TRY(ptam_stream_wait(s.st));
+            n_good = *h_word;
+            if (n_good < 0 || n_good > Q) {
+                ptam_set_error("ptam_rmap_refind_queue: %d good points of %d queue entries", n_good, Q);
+                return PTAM_E_STATE;
+            }
+            if (int rc = mt_queue_rank_core(s.st, n_good, w.w0, w.w1, keys_a, keys_b)) return rc;
+            sh.n_wp = n_good;
+            sh.pairs = K * n_good;
+        } else if (int rc = mt_failure_sorted_core(s.st, F, rm_failure(m), (ptam_map_pair*)w.w0, keys_a, keys_b))
+            return rc;
+        sh.per_pass = mr_per_pass(mode, K, max_per_pass, sh.pairs);
+        if (sh.pairs > 0) {
+            const MrTables t = rm_refind_tables(m);
+            STAGE_TRY(mr_run(s, finder, t, sh, w, stop_flag, &r, nullptr, nullptr, nullptr));
+            // a stopped walk of the new queue: the entries up to the last visited point are popped (mr_plan_consumed), and the
+            // entry of that point is the one word of the list the host reads
+            const int wp = r.n_pairs / K;
+            if (new_points && r.stopped && wp > 0) {
+                STAGE_TRY(s.down(h_word, wentry + (wp - 1), sizeof(int)));
+                HIP_TRY(ptam_stream_wait(s.st));
+                r.points_consumed = *h_word + 1;
+                r.n_bad_points = r.points_consumed - wp;
+            }
+            HIP_TRY(ptam_stream_wait(s.st));
+            rm_refind_commit(m, r);
+        } else
+            r.stopped = new_points && stop_now;   // (mr_plan_nothing)
+        if (new_points && !r.stopped) {
+            r.points_consumed = Q;
+            r.n_bad_points = Q - n_good;
         }
-        m->n[RM_N_NEW] = left;
     }
-    if (from_queue && mode == PTAM_MAP_REFIND_FAILURE_QUEUE && !r.stopped) m->n[RM_N_FAILURE] = 0;   // mvFailureQueue.clear() (:1080)
+    if (int rc = rm_queue_consumed(m, mode, r)) return rc;
     *res = r;
     return PTAM_OK;
 }
@@ -584,6 +701,104 @@ int ptam_rmap_apply_outliers(ptam_rmap* m, int n_outliers, const ptam_map_outlie
     m->n[RM_N_NEVER] = r.n_never_out;
     m->n[RM_N_FAILURE] = r.n_failure_out;
     *res = r;
+    return PTAM_OK;
+}
+
+// ptam_rmap_bundle_adjust, then ptam_rmap_apply_outliers on the list mba_route_kernel left in the bundle's work memory: the list
+// is neither brought down nor sent up.  What the host read off the list there — the counts per action — a kernel adds up here; the
+// action and row ranges need no check, mba_route_kernel writes a row of the selection and one of the three actions in every entry.
+int ptam_rmap_bundle_adjust_routed(ptam_rmap* m, const ptam_ba_opts* opts, int mode, const volatile unsigned char* abort_flag,
+                                   ptam_map_ba_result* res, ptam_map_outliers_result* outliers_res) {
+    ARG_TRY(m && res && outliers_res);
+    ARG_TRY(mode == PTAM_MAP_BA_ALL || mode == PTAM_MAP_BA_RECENT);
+    const int K = m->n[RM_N_KF], N = m->n[RM_N_POINTS], M = m->n[RM_N_MEAS], V = m->n[RM_N_NEVER], F = m->n[RM_N_FAILURE];
+    std::memset(res, 0, sizeof *res);
+    ptam_map_outliers_result r = {};   // of an empty list, until the bundle has routed one
+    r.n_meas_out = M;
+    r.n_never_out = V;
+    r.n_failure_out = F;
+    *outliers_res = r;
+    if (mode == PTAM_MAP_BA_RECENT && K < 8) return PTAM_OK;   // :790-793
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    MbaTables t = {};
+    t.K = K;
+    t.N = N;
+    t.M = M;
+    t.h_poses = m->h_poses.data();
+    t.h_fixed = m->h_fixed.data();
+    t.d_poses = rm_poses(m);
+    t.d_fixed = rm_fixed(m);
+    t.d_points3 = rm_points3(m);
+    t.d_meas = rm_meas(m);
+    t.d_points = rm_points(m);
+    // the outlier stage's work beside the bundle's, in the call's one carve: a bundle has at most M outliers
+    const size_t Mz = (size_t)std::max(M, 1);
+    MbaWork w;
+    MtOutliersDev d = {};
+    unsigned* owner;
+    int* hw;
+    MapStage s = rm_stage(m);
+    STAGE_TRY(s.carve([&](Carver& c, Carver& pin) {
+        mba_layout(c, pin, K, N, M, w);
+        d.flag = c.piece<uint8_t>(Mz);
+        owner = c.piece<unsigned>(Mz);
+        d.tiles = c.piece<int>((size_t)mt_tiles((int)Mz));
+        d.new_never = c.piece<ptam_map_pair>(Mz);
+        hw = pin.piece<int>(RM_WORDS);
+    }));
+    const size_t hw_off = (size_t)((char*)hw - (char*)m->ctx->h_pinned);
+    int n_out = 0;
+    if (int rc = mba_core(s, opts, mode, t, w, abort_flag, res, nullptr, nullptr, nullptr, &n_out)) return rc;
+    m->h2d += (unsigned long long)(res->n_adjust + res->n_fixed) * 97;   // the bundle's cameras, pose and flag: copied inside ba_dev_ingest
+    if (res->accepted > 0) STAGE_TRY(s.down(m->h_poses.data(), t.d_poses, (size_t)K * 96));   // the mirror, whatever the outlier stage decides
+    if (n_out == 0) {
+        HIP_TRY(ptam_stream_wait(s.st));
+        return PTAM_OK;
+    }
+    // ---- the outlier stage.  n_out has been on the host since Compute() returned: the room of both tables before its launches
+    ARG_TRY((long long)V + n_out < (1ll << 31) && (long long)F + n_out < (1ll << 31));
+    if (int rc = rm_room(m, PTAM_RMAP_NEVER, (long long)V + n_out)) return rc;
+    if (int rc = rm_room(m, PTAM_RMAP_FAILURE, (long long)F + n_out)) return rc;
+    // the words' landing place is a piece of the call's pinned layout.  mba_core has asked the context for pinned memory since (the
+    // step ends, a request of its own): had that grown the block, it waited for the stream, and the piece lies at its offset in the
+    // new, larger block
+    hw = (int*)((char*)m->ctx->h_pinned + hw_off);
+    hipStream_t st = s.st;
+    if (int rc = rm_words_reset(m)) return rc;
+    HIP_TRY(hipMemsetAsync(owner, 0xff, Mz * sizeof(unsigned), st));
+    int* err = m->d_words + RM_W_CALL;
+    d.n_meas = M;
+    d.n_never = V;
+    d.n_outliers = n_out;
+    d.n_never_out = V + n_out;   // (the merge's launch bound: its kernel reads the live count of new pairs on the device)
+    d.outliers = w.out;
+    hipLaunchKernelGGL(rm_outliers_tally_kernel, dim3(s.blocks(n_out)), dim3(256), 0, st, n_out, d.outliers, m->d_words + RM_W_TALLY);
+    hipLaunchKernelGGL(rm_outliers_check_kernel, dim3(s.blocks(n_out)), dim3(256), 0, st, n_out, d.outliers, rm_meas(m), V, rm_never(m), owner, err);
+    hipLaunchKernelGGL(rm_outliers_twice_kernel, dim3(s.blocks(n_out)), dim3(256), 0, st, n_out, d.outliers, owner, err);
+    d.meas = rm_meas(m);
+    d.never = rm_never(m);
+    d.bad = rm_bad(m);
+    d.points = rm_points(m);
+    d.gate = err;
+    d.tot = m->d_words + RM_W_TOT;
+    d.meas_out = rm_meas_alt(m);
+    d.never_out = rm_never_alt(m);
+    d.failure_new = rm_failure(m) + F;   // behind the count
+    if (int rc = mt_apply_outliers_core(st, d)) return rc;
+    if (int rc = rm_words_wait(s, m, hw)) return rc;
+    if (hw[RM_W_CALL] != RM_NO_ROW) return rm_refuse(m, PTAM_RMAP_OUTLIERS, hw[RM_W_CALL]);
+    r.n_point_bad = hw[RM_W_TALLY + 0];
+    r.n_failure_added = hw[RM_W_TALLY + 1];
+    r.n_never_added = hw[RM_W_TALLY + 2];
+    r.n_meas_out = M - r.n_failure_added - r.n_never_added;
+    r.n_never_out = V + r.n_never_added;
+    r.n_failure_out = F + r.n_failure_added;
+    m->t[PTAM_RMAP_MEAS].cur ^= 1;
+    m->t[PTAM_RMAP_NEVER].cur ^= 1;
+    m->n[RM_N_MEAS] = r.n_meas_out;
+    m->n[RM_N_NEVER] = r.n_never_out;
+    m->n[RM_N_FAILURE] = r.n_failure_out;
+    *outliers_res = r;
     return PTAM_OK;
 }
 
@@ -709,6 +924,7 @@ void maprmap_preload_kernels() {
     ptam_preload((const void*)rm_check_points_kernel);
     ptam_preload((const void*)rm_outliers_check_kernel);
     ptam_preload((const void*)rm_outliers_twice_kernel);
+    ptam_preload((const void*)rm_outliers_tally_kernel);
     ptam_preload((const void*)rm_note_tracked_kernel);
     ptam_preload((const void*)rm_queue_bad_kernel);
     ptam_preload((const void*)rm_pack_pvs_kernel);

@@ -3,7 +3,9 @@
 //   ptam_map_handle_bad_points  MapMaker::HandleBadPoints (:131-153) with Map::MoveBadPointsToTrash (src/Map.cc:20-30)
 //   ptam_map_add_points         the table side of AddPointEpipolar (:670-685) and of InitFromStereo's point loop (:352-362)
 // and, for ptam_rmap_init_from_stereo (maprmap_init.hip), mt_made_records_core: the made records of InitFromStereo's point loop
-// (:310-367) compacted in match order, with the count of every status.
+// (:310-367) compacted in match order, with the count of every status; and, for ptam_rmap_refind_queue (maprmap.hip), the work lists
+// of the re-find built from the resident queues: the good new points compacted in queue order and ranked by index, the failure
+// pairs sorted — both through one sort of 64-bit keys (mt_sort_keys: a bitonic sort per tile in LDS, then merge passes by rank).
 // All three set a flag per row, compact or merge the rows in order and remap the point column.  The one primitive is the ordered
 // compaction mt_compact over a row source (keep / put / drop), three launches:
 //   mt_count_kernel    one workgroup per tile of MT_TILE = 1024 rows, one row per thread: __ballot / __popcll per 64-lane wave,
@@ -320,8 +322,133 @@ __global__ void __launch_bounds__(256) mt_status_count_kernel(int n, const int32
     }
 }
 
+// ---- the sort of 64-bit keys -----------------------------------------------------------------------------------------------------
+// Ascending, for the work lists of the re-find from the resident queues: (kf << 32 | point) of a failure pair, (point << 32 | place)
+// of a good new point.  Equal keys are equal records, so no tie can change a byte: the output is a function of the input alone.
+//   mt_sort_tile_kernel   one workgroup of MT_TILE threads per tile of MT_TILE keys, one key per thread, a bitonic network: the
+//                         exchanges at a distance below 64 are lane exchanges inside the wave, the others go through LDS (8 KB a
+//                         workgroup; thread t reads slot t ^ distance, distance >= 64: each 32-lane half reads 32 consecutive
+//                         8-byte slots, one 256-byte bank row, so no two lanes of a half meet on a bank).  A short last tile is
+//                         filled with ~0, above every key (a key's top bit is clear)
+//   mt_sort_merge_kernel  one pass per doubling of the run length, one thread per key: runs 2j and 2j + 1 into one, each key placed
+//                         by a binary search in the sibling run (the left run's keys before equal keys of the right run: the count
+//                         of smaller keys for a left key, of smaller or equal keys for a right one) — the rule of mt_merge_kernel
+// Sizes at which the path changes: 64 keys (a second wave), MT_TILE (a second tile: the first merge pass), 2 MT_TILE (a second pass).
+__global__ void __launch_bounds__(MT_TILE) mt_sort_tile_kernel(int n, const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long ks[MT_TILE];
+    const int tid = threadIdx.x;
+    const long long g = (long long)blockIdx.x * MT_TILE + tid;
+    unsigned long long v = g < n ? in[g] : ~0ull;
+    for (int size = 2; size <= MT_TILE; size <<= 1)
+        for (int dist = size >> 1; dist > 0; dist >>= 1) {
+            unsigned long long o;
+            if (dist >= 64) {   // (the same for every thread)
+                ks[tid] = v;
+                __syncthreads();
+                o = ks[tid ^ dist];
+                __syncthreads();
+            } else
+                o = __shfl_xor(v, dist, 64);
+            const bool lower = (tid & dist) == 0, ascending = (tid & size) == 0;
+            v = (lower == ascending) ? (v < o ? v : o) : (v < o ? o : v);
+        }
+    if (g < n) out[g] = v;
+}
+
+__global__ void __launch_bounds__(256) mt_sort_merge_kernel(int n, int run, const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const long long base = g / (2ll * run) * (2ll * run), mid = base + run;
+    const bool right = g >= mid;
+    // the sibling run, cut at the table's end (a left run without a sibling: empty)
+    long long lo = right ? base : (mid < n ? mid : (long long)n), hi = right ? mid : (mid + run < n ? mid + run : (long long)n);
+    const long long sib = lo;
+    const unsigned long long key = in[g];
+    while (lo < hi) {
+        const long long m = lo + (hi - lo) / 2;
+        if (right ? in[m] <= key : in[m] < key) lo = m + 1;
+        else hi = m;
+    }
+    out[base + (g - (right ? mid : base)) + (lo - sib)] = key;
+}
+
+// n keys in a, ascending, into a or b (n keys of room each): the buffer that holds them
+static unsigned long long* mt_sort_keys(hipStream_t st, int n, unsigned long long* a, unsigned long long* b) {
+    if (n == 0) return a;
+    hipLaunchKernelGGL(mt_sort_tile_kernel, dim3(mt_tiles(n)), dim3(MT_TILE), 0, st, n, (const unsigned long long*)a, b);
+    unsigned long long *src = b, *dst = a;
+    for (long long run = MT_TILE; run < n; run *= 2) {
+        hipLaunchKernelGGL(mt_sort_merge_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, st, n, (int)run,
+                           (const unsigned long long*)src, dst);
+        std::swap(src, dst);
+    }
+    return src;
+}
+
+// ---- the work lists of the re-find, from the resident queues (MapMaker::ReFindNewlyMade / ReFindFromFailureQueue, :1048-1081) -------
+struct MtGoodQueue {   // mqNewQueue's entries whose point is not bad (:1056-1059), in queue order: the point and the entry
+    const int32_t* q;
+    const uint8_t* bad;
+    int* wpts;
+    int* wentry;
+    __device__ bool keep(int i) const { return bad[q[i]] == 0; }
+    __device__ void put(int i, int at) const {
+        wpts[at] = q[i];
+        wentry[at] = i;
+    }
+    __device__ void drop(int) const {}
+};
+__global__ void __launch_bounds__(256) mt_point_keys_kernel(int n, const int* __restrict__ wpts, unsigned long long* __restrict__ keys) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) keys[i] = ((unsigned long long)(unsigned)wpts[i] << 32) | (unsigned)i;
+}
+// the sorted keys are the good points in index order: the key at place r belongs to the list's entry in its low word
+__global__ void __launch_bounds__(256) mt_point_ranks_kernel(int n, const unsigned long long* __restrict__ keys, int* __restrict__ wrank) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r < n) wrank[(unsigned)keys[r]] = r;
+}
+__global__ void __launch_bounds__(256) mt_pair_keys_kernel(int n, const ptam_map_pair* __restrict__ q, unsigned long long* __restrict__ keys) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) keys[i] = mt_key(q[i].kf, q[i].point);
+}
+__global__ void __launch_bounds__(256) mt_key_pairs_kernel(int n, const unsigned long long* __restrict__ keys, ptam_map_pair* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    ptam_map_pair q;
+    q.kf = (int)(keys[i] >> 32);
+    q.point = (int)(unsigned)keys[i];
+    out[i] = q;
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 // ---- the cores: device pointers in, launches on the stream, no wait (maptables_internal.h) ---------------------------------------
+int mt_queue_good_core(hipStream_t st, int n_new, const int32_t* new_queue, const uint8_t* bad, int* wpts, int* wentry, int* tiles, int* total) {
+    HIP_TRY(hipMemsetAsync(total, 0, sizeof(int), st));
+    mt_compact(st, MtGoodQueue{new_queue, bad, wpts, wentry}, n_new, tiles, total);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+int mt_queue_rank_core(hipStream_t st, int n_good, const int* wpts, int* wrank, unsigned long long* keys_a, unsigned long long* keys_b) {
+    if (n_good == 0) return PTAM_OK;
+    const dim3 grid((n_good + 255) / 256);
+    hipLaunchKernelGGL(mt_point_keys_kernel, grid, dim3(256), 0, st, n_good, wpts, keys_a);
+    const unsigned long long* sorted = mt_sort_keys(st, n_good, keys_a, keys_b);
+    hipLaunchKernelGGL(mt_point_ranks_kernel, grid, dim3(256), 0, st, n_good, sorted, wrank);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+int mt_failure_sorted_core(hipStream_t st, int n_failure, const ptam_map_pair* failure, ptam_map_pair* out, unsigned long long* keys_a,
+                           unsigned long long* keys_b) {
+    if (n_failure == 0) return PTAM_OK;
+    const dim3 grid((n_failure + 255) / 256);
+    hipLaunchKernelGGL(mt_pair_keys_kernel, grid, dim3(256), 0, st, n_failure, failure, keys_a);
+    const unsigned long long* sorted = mt_sort_keys(st, n_failure, keys_a, keys_b);
+    hipLaunchKernelGGL(mt_key_pairs_kernel, grid, dim3(256), 0, st, n_failure, sorted, out);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
+
 // the flags, the three compactions, the merge
 int mt_apply_outliers_core(hipStream_t st, const MtOutliersDev& d) {
     HIP_TRY(hipMemsetAsync(d.flag, 0, d.n_meas > 0 ? (size_t)d.n_meas : 1, st));
@@ -593,6 +720,14 @@ void maptables_preload_kernels() {
     ptam_preload((const void*)mt_scatter_kernel<MtRemapQueue>);
     ptam_preload((const void*)mt_count_kernel<MtMadeRecords>);
     ptam_preload((const void*)mt_scatter_kernel<MtMadeRecords>);
+    ptam_preload((const void*)mt_count_kernel<MtGoodQueue>);
+    ptam_preload((const void*)mt_scatter_kernel<MtGoodQueue>);
+    ptam_preload((const void*)mt_sort_tile_kernel);
+    ptam_preload((const void*)mt_sort_merge_kernel);
+    ptam_preload((const void*)mt_point_keys_kernel);
+    ptam_preload((const void*)mt_point_ranks_kernel);
+    ptam_preload((const void*)mt_pair_keys_kernel);
+    ptam_preload((const void*)mt_key_pairs_kernel);
     ptam_preload((const void*)mt_status_count_kernel);
     ptam_preload((const void*)mt_outliers_kernel);
     ptam_preload((const void*)mt_merge_kernel);

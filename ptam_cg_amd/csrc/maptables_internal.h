@@ -114,6 +114,16 @@ static inline MtAdd mt_add_head(int src_kf, int target_kf, int target_source, in
 enum { MT_MADE_WORDS = 5 };
 int mt_made_records_core(hipStream_t st, int n, const int32_t* status, const ptam_new_map_point* in, ptam_new_map_point* out, int* tiles, int* tot);
 
+// ---- the work lists of mr_run from the resident queues (maptables.hip); keys_a / keys_b: n 64-bit keys of room each
+//      mqNewQueue's entries whose point is not bad, in queue order (the ordered compaction): wpts = the points, wentry = their
+//      entries; *total = how many.  tiles: mt_tiles(n_new)
+int mt_queue_good_core(hipStream_t st, int n_new, const int32_t* new_queue, const uint8_t* bad, int* wpts, int* wentry, int* tiles, int* total);
+//      wrank[i] = the place of wpts[i] among the n_good points in index order (no point twice: the queue's rule)
+int mt_queue_rank_core(hipStream_t st, int n_good, const int* wpts, int* wrank, unsigned long long* keys_a, unsigned long long* keys_b);
+//      mvFailureQueue sorted by (kf, point), duplicates kept (:1074)
+int mt_failure_sorted_core(hipStream_t st, int n_failure, const ptam_map_pair* failure, ptam_map_pair* out, unsigned long long* keys_a,
+                           unsigned long long* keys_b);
+
 // ---- MapMaker::ReFind* (:1028-1081), maprefind.hip: the re-find on tables in device memory.  The merged tables are written into
 //      d_meas_merged / d_never_merged (each nullable; room for n_meas / n_never + the plan's pair count).
 struct MrTables {
@@ -138,9 +148,23 @@ struct MrWork {   // the core's pieces of the call's stage: mr_layout
 // what every form of the call asks of its arguments before the plan
 int mr_check_call(ptam_ctx* ctx, const ptam_refinder* finder, const ptam_map_refind_opts* opts, int mode, int n_kf, const ptam_kf* const* kfs);
 void mr_layout(Carver& c, Carver& pin, int n_kf, const MrPlan& plan, bool merged, MrWork& w);   // merged: a merged table is asked for
-// plan.pairs > 0.  Uploads the level records and the work lists, runs the passes, orders and merges, waits for the counts and
-// queues the call's lists to come down (found_out / found_subpix / never_out nullable together).  The call's last wait is the
-// caller's, behind whatever else it brings down.
+// what the layout and the passes need of a plan: a host plan's (mr_shape), or that of work lists kernels have built into w.w0 /
+// w.w1 (ptam_rmap_refind_queue, which lays out for the queue's length and runs for the count of good points)
+struct MrShape {
+    int mode, kf0;
+    int n_wp;                           // NEW_POINTS: the points that make pairs
+    int n_wq;                           // FAILURE_QUEUE: the pairs
+    int pairs, per_pass;
+};
+MrShape mr_shape(const MrPlan& plan);
+void mr_layout_shape(Carver& c, Carver& pin, int n_kf, const MrShape& shape, bool merged, MrWork& w);
+// shape.pairs > 0; the work lists are in w.w0 / w.w1 (NEW_POINTS: wpts, wrank; FAILURE_QUEUE: the sorted pairs in w.w0).  Uploads
+// the level records, runs the passes, orders and merges, waits for the counts and queues the call's lists to come down (found_out /
+// found_subpix / never_out nullable together).  points_consumed and n_bad_points are left zero: the owner of the work list knows
+// them.  The call's last wait is the caller's, behind whatever else it brings down.
+int mr_run(MapStage& s, ptam_refinder* finder, const MrTables& t, const MrShape& shape, const MrWork& w, const volatile unsigned char* stop_flag,
+           ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix, ptam_map_pair* never_out);
+// plan.pairs > 0.  The work lists of a host plan up, then mr_run, then what the plan says of a stopped queue.
 int mr_core(MapStage& s, ptam_refinder* finder, const MrTables& t, const MrPlan& plan, const MrWork& w, const volatile unsigned char* stop_flag,
             ptam_map_refind_result* res, ptam_map_meas* found_out, int32_t* found_subpix, ptam_map_pair* never_out);
 
@@ -166,6 +190,7 @@ struct MbaWork {   // the core's pieces of the call's stage: mba_layout
 void mba_layout(Carver& c, Carver& pin, int K, int N, int M, MbaWork& w);
 // Selection, its one wait, the camera marshalling, ingest and Compute(), the scatter and the outlier routing.  The outliers and the
 // point ids are queued to come down; the call's last wait is the caller's, behind whatever it brings down of the adjusted tables
-// (res->accepted > 0).
+// (res->accepted > 0).  n_routed (nullable): the routing runs whether or not `outliers` is given, the routed list stays in w.out for
+// the launches the caller queues behind it, and *n_routed is its length.
 int mba_core(MapStage& s, const ptam_ba_opts* opts, int mode, const MbaTables& t, const MbaWork& w, const volatile unsigned char* abort_flag,
-             ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids);
+             ptam_map_ba_result* res, ptam_map_outlier* outliers, int32_t* cam_kf, int32_t* point_ids, int* n_routed = nullptr);

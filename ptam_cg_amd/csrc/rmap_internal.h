@@ -15,6 +15,10 @@ enum { RM_NO_ROW = MT_GATE_OPEN };
 enum { RM_W_MEAS = 0, RM_W_NEVER, RM_W_NEW, RM_W_FAILURE, RM_W_POINTS, RM_W_CALL, RM_W_ERRS = 8, RM_W_TOT = 8, RM_WORDS = 16 };
 static_assert(RM_WORDS * sizeof(int) == PTAM_RMAP_WORD_BYTES, "the word block is what the header says a call brings down");
 static_assert(RM_W_TOT + MT_T_COUNT <= RM_WORDS, "the cores' counts fit behind the refusal words");
+// ptam_rmap_bundle_adjust_routed: the routed list's outliers per action (POINT_BAD, FAILURE_QUEUE, NEVER_RETRY), behind the three
+// counts of mt_apply_outliers_core
+enum { RM_W_TALLY = RM_W_TOT + 3 };
+static_assert(RM_W_TALLY + 3 <= RM_WORDS, "the tally fits behind the outlier core's counts");
 
 // the tables of ptam_rmap_download, then the serial column: one int64 per point, strictly increasing, the seventh point-side column
 enum { RM_SERIALS = PTAM_RMAP_TABLES, RM_TABLES };

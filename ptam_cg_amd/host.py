@@ -349,10 +349,119 @@ class MapMaker:
     """MapMaker::AddSomeMapPoints (src/MapMaker.cc:448-457) for a list of levels in ONE device call
     (ptam_add_map_points_epipolar): ThinCandidates + AddPointEpipolar of every kept candidate"""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, rmap=None, finder=None, snapshot=None, opts=None):
+        """with rmap (a ResidentMap) and finder (a ReFinder): also the ptam_mapmaker handle over them — the keyframe queue, the
+        flags and Step, one iteration of MapMaker::run() (src/MapMaker.cc:57-114) as one call; snapshot (a MapSnapshot, optional):
+        what Step publishes into; opts: from mapmaker_opts()"""
         self.ctx, self.lib = ctx, ctx.lib
         if not self.lib.has("add_map_points_epipolar"):
             raise PtamError("this library has no ptam_add_map_points_epipolar")
+        self.h = None
+        if rmap is not None:
+            self.rmap, self.finder, self.snapshot = rmap, finder, snapshot
+            self._held = {}                  # tag -> the objects handed over with it, alive until the tag is released
+            self._queued = []                # the queued keyframes, oldest first: the map holds one from the step that inserts it
+            self.h = C.c_void_p()
+            ctx._check(self.lib.mapmaker_create(rmap.h, finder.h, snapshot.h if snapshot is not None else None,
+                                                C.byref(opts) if opts is not None else None, C.byref(self.h)), "mapmaker_create")
+
+    def _handle(self):
+        if not self.h:
+            raise PtamError("this MapMaker has no ptam_mapmaker handle: construct it with a ResidentMap and a ReFinder")
+        return self.h
+
+    @staticmethod
+    def mapmaker_opts(ctx, failure_period=20, failure_seed=0, max_pairs_per_pass=0, ba=None, **epipolar):
+        """ptam_mapmaker_opts: the reference's defaults, then ba (a dict of ptam_ba_opts fields) and the epipolar options as opts()
+        takes them (the depth is each keyframe's own: AddKeyFrame)"""
+        self = MapMaker(ctx)
+        o = _abi.MapmakerOpts()
+        ctx._check(ctx.lib.mapmaker_opts_default(C.byref(o)), "mapmaker_opts_default")
+        for k, v in (ba or {}).items():
+            setattr(o.ba, k, v)
+        if epipolar:
+            if "levels" not in epipolar:
+                epipolar = dict(epipolar, levels=[o.insert.epipolar.levels[i] for i in range(o.insert.epipolar.n_levels)])
+            o.insert.epipolar = self.opts(**epipolar)
+        o.refind = o.insert.refind = _abi.MapRefindOpts(int(max_pairs_per_pass), 0)
+        o.failure_period, o.failure_seed = int(failure_period), int(failure_seed)
+        return o
+
+    def AddKeyFrame(self, kf, pose, fixed, report, depth_mean, depth_sigma, tag):
+        """MapMaker::AddKeyFrame (:480-488): queues the clone kf with the tracker's FrameReport of its frame; callable from the
+        tracker's thread"""
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        self._held[int(tag)] = (kf, report)
+        self._queued.append(kf)
+        self.ctx._check(self.lib.mapmaker_add_keyframe(self._handle(), kf.h, _pd(pose), int(bool(fixed)), report.h, float(depth_mean), float(depth_sigma),
+                                                       int(tag)), "mapmaker_add_keyframe")
+
+    def NoteFrame(self, report, tag):
+        self._held[int(tag)] = (report,)
+        self.ctx._check(self.lib.mapmaker_note_frame(self._handle(), report.h, int(tag)), "mapmaker_note_frame")
+
+    def QueueSize(self):
+        n = C.c_int32()
+        self.ctx._check(self.lib.mapmaker_queue_size(self._handle(), C.byref(n)), "mapmaker_queue_size")
+        return n.value
+
+    def RequestReset(self):
+        self.ctx._check(self.lib.mapmaker_request_reset(self._handle()), "mapmaker_request_reset")
+
+    def ResetDone(self):
+        n = C.c_int32()
+        self.ctx._check(self.lib.mapmaker_reset_done(self._handle(), C.byref(n)), "mapmaker_reset_done")
+        return bool(n.value)
+
+    def flags(self):
+        r, f, b = C.c_int32(), C.c_int32(), C.c_int32()
+        self.ctx._check(self.lib.mapmaker_flags(self._handle(), C.byref(r), C.byref(f), C.byref(b)), "mapmaker_flags")
+        return dict(converged_recent=r.value, converged_full=f.value, bundle_running=b.value)
+
+    def set_flags(self, converged_recent, converged_full):
+        self.ctx._check(self.lib.mapmaker_set_flags(self._handle(), int(bool(converged_recent)), int(bool(converged_full))), "mapmaker_set_flags")
+
+    def released(self, cap=64):
+        """the tags the mapmaker has finished with since the last call, oldest first"""
+        out = []
+        while True:
+            tags, n = np.zeros(cap, np.int64), C.c_int32()
+            self.ctx._check(self.lib.mapmaker_released(self._handle(), cap, _ptr(tags), C.byref(n)), "mapmaker_released")
+            out += [int(t) for t in tags[:n.value]]
+            if n.value < cap:
+                break
+        for t in out:
+            self._held.pop(t, None)
+        return out
+
+    def Step(self, check=True):
+        """ptam_mapmaker_step -> dict(status, stages, draws, converged_recent, converged_full, queue_size, and each stage's counts:
+        recent, recent_outliers, refind_new, all, all_outliers, refind_failure, notes, bad_points, insert (with n_rows, n_gone),
+        publish)"""
+        res = _abi.MapmakerStepResult()
+        rc = self.lib.mapmaker_step(self._handle(), C.byref(res))
+        if rc < 0 and not check:
+            return rc
+        self.ctx._check(rc, "mapmaker_step")
+        d = {k: getattr(res, k) for k in ("status", "stages", "converged_recent", "converged_full", "queue_size", "draws")}
+        for k in ("recent", "recent_outliers", "refind_new", "all", "all_outliers", "refind_failure", "notes", "bad_points"):
+            d[k] = _counts(getattr(res, k))
+        i = res.insert
+        d["insert"] = dict(kf=i.kf, target_kf=i.target_kf, target_dist=i.target_dist, refind=_counts(i.refind), first_point=i.first_point,
+                           n_made=i.n_made, n_rows=res.insert_rows, n_gone=res.insert_gone)
+        d["publish"] = {k: getattr(res.publish, k) for k in ("generation", "map_id", "n_points", "n_kf", "grew")}
+        if res.status == _abi.MM_RESET:
+            self._queued = []
+        if res.stages & _abi.MM_STAGE_ADD_KEYFRAME:
+            self.rmap._kfs.append(self._queued.pop(0))
+        if self.snapshot is not None and res.stages & _abi.MM_STAGE_PUBLISH:
+            self.snapshot._kfs = list(self.rmap._kfs)
+        return d
+
+    def close(self):
+        if self.h:
+            self.lib.mapmaker_destroy(self.h)
+            self.h = None
 
     def opts(self, **kw):
         o = EpipolarOpts()
@@ -991,6 +1100,13 @@ class ResidentMap:
             d.update(found=found[:res.n_found].copy(), found_subpix=subpix[:res.n_found].copy(), never=nev[:res.n_never].copy())
         return d
 
+    def refind_queue(self, finder, mode, stop=None, max_pairs_per_pass=0):
+        """refind(work=None) with the work lists built on the device from the resident queue (NEW_POINTS / FAILURE_QUEUE): nothing
+        of the queue crosses the host link -> the result counts; the merged tables stay on the device"""
+        o, res = _abi.MapRefindOpts(int(max_pairs_per_pass), 0), _abi.MapRefindResult()
+        self.ctx._check(self.lib.rmap_refind_queue(self.h, finder.h, C.byref(o), int(mode), _ptr(stop), C.byref(res)), "rmap_refind_queue")
+        return _counts(res)
+
     def apply_global_transform(self, se3_new_from_old, rows=True):
         """map_apply_global_transform on the resident tables -> the pvs rows (PVS_POINT_DT) when asked for, else None"""
         se3 = np.ascontiguousarray(se3_new_from_old, dtype=np.float64).reshape(12)
@@ -1008,6 +1124,20 @@ class ResidentMap:
             return rc
         self.ctx._check(rc, "rmap_apply_outliers")
         return _counts(res)
+
+    def bundle_adjust_routed(self, mode, abort=None, check=True, **ba_opts):
+        """bundle_adjust and apply_outliers on the list it routed as one call; the list stays on the device -> (the bundle's
+        counts, the outlier stage's counts).  check=False: -> the status instead of raising when the outlier stage refuses"""
+        o = BaOpts()
+        self.lib.ba_opts_default(C.byref(o))
+        for k, v in ba_opts.items():
+            setattr(o, k, v)
+        res, ores = _abi.MapBaResult(), _abi.MapOutliersResult()
+        rc = self.lib.rmap_bundle_adjust_routed(self.h, C.byref(o), int(mode), _ptr(abort), C.byref(res), C.byref(ores))
+        if not check and rc < 0:
+            return rc
+        self.ctx._check(rc, "rmap_bundle_adjust_routed")
+        return _counts(res), _counts(ores)
 
     def handle_bad_points(self, kept=False, new_index=False):
         """map_handle_bad_points on the resident tables -> its counts, with "kept" / "new_index" when asked for"""
