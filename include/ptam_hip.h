@@ -96,6 +96,13 @@ int ptam_make_keyframe_lite_dev(ptam_ctx* ctx, ptam_kf* kf, const uint8_t* d_im)
 /* Level::operator= deep copy (include/KeyFrame.h:66-75) for the tracker->mapmaker hand-off
  * (src/MapMaker.cc:480-488), device to device. */
 int ptam_kf_clone(ptam_ctx* ctx, const ptam_kf* src, ptam_kf** out);
+/* The same copy into an EXISTING keyframe of the same image size: device to device on the context's queue, asynchronous, no
+ * allocation (a keyframe pool for the hand-off: allocating under queued kernels costs milliseconds).  Afterwards dst reads
+ * byte for byte as ptam_kf_clone(src) does: every level's image, corners and row LUT, and the MakeKeyFrame_Rest data if src
+ * has it.  Whatever dst held is gone: its own rest data counts as not made (the next ptam_make_keyframe_rest /
+ * ptam_mapmaker_step makes it, as for a fresh clone of a tracker's keyframe) and its in-plane corner cache is stale.
+ * PTAM_E_ARG: another size, another device, src == dst. */
+int ptam_kf_copy(ptam_ctx* ctx, const ptam_kf* src, ptam_kf* dst);
 int ptam_kf_level_info(ptam_ctx* ctx, const ptam_kf* kf, int level, int* w, int* h, int* n_corners);
 /* host read-back of aLevels[level].im / vCorners / vCornerRowLUT; NULL pointers are skipped.
  * px: w*h bytes; corners: n_corners entries (raster order); rowlut: h ints. */
@@ -621,6 +628,23 @@ int ptam_tracker_update_map(ptam_tracker* t, int n, const ptam_pvs_point* points
  * its members appear in shuffle_levels (replaces std::random_shuffle of avPVS[l], :483-484), the chop of the fine set to
  * MaxPatchesPerFrame in the order of shuffle_fine (:597-600).  Identity until set. */
 int ptam_tracker_set_shuffle(ptam_tracker* t, const int32_t* shuffle_levels, const int32_t* shuffle_fine);
+/* The same two orders drawn ON THE DEVICE, on the tracker's queue: nothing proportional to the map is made, checked or uploaded
+ * by the host, and the call waits for nothing.  For order w (0: shuffle_levels, 1: shuffle_fine) and point i the key is
+ *     (hi32(splitmix64(seed, ((2 * frame + w) << 32) | i)) << 32) | i
+ * with splitmix64(seed, k) the k-th output of the generator whose state starts at seed (as ptam_mapmaker_opts' failure draw;
+ * 2 * frame + w is taken modulo 2^32); the order is the low words of the n keys sorted ascending.  The keys are distinct, so the
+ * order is total and a permutation by construction.  Maps of at most 8192 points: one launch, a workgroup per order, keys made
+ * and sorted in LDS; larger maps: one launch for the keys, the device's 64-bit key sort per order, one launch for the low words.
+ * n == 0: nothing happens.  ptam_tracker_set_shuffle afterwards replaces the orders and the other way round; a new map of
+ * another size resets them to the identity, as before. */
+int ptam_tracker_draw_shuffles(ptam_tracker* t, uint64_t seed, uint64_t frame);
+/* The two orders the tracker's next frame will use, n entries each, however they were set: a copy on the tracker's queue, which is
+ * waited for — from the device arrays after a draw, a take or a set_shuffle of a map of more than 8192 points; after a set_shuffle
+ * of a smaller map from the host-mapped copy that call keeps (read through the queue as well, so behind whatever is enqueued). */
+int ptam_tracker_read_shuffle(ptam_tracker* t, int32_t* shuffle_levels, int32_t* shuffle_fine);
+/* The definition the device is held to, in plain host code (no device, no tracker): order `which` (0 / 1) of n points into
+ * out[0..n-1].  PTAM_E_ARG: which outside 0..1, n < 0, out NULL with n > 0. */
+int ptam_shuffle_order_host(uint64_t seed, uint64_t frame, int which, int n, int32_t* out);
 int ptam_track_map(ptam_tracker* t, const ptam_kf* current, const double pose_in[12], const ptam_trackmap_opts* opts,
                    ptam_trackmap_result* out);
 /* A whole tracked frame in one call: KeyFrame::MakeKeyFrame_Lite (src/KeyFrame.cc:18-54) of the device-resident image
@@ -1765,6 +1789,51 @@ int ptam_tracker_report_frames(int nb, ptam_tracker* const* trackers, ptam_frame
 int ptam_frame_report_from_host(ptam_frame_report*, int64_t map_id, int n_points, const int64_t* point_serials, int n_entries,
                                 const ptam_trackmap_meas* entries);
 
+/* ptam_track_frames_recover_batch with the frames' reports filled INSIDE the chain and, optionally, the frames' two random orders
+ * drawn there: one call and one host wait per camera where the sequence set_shuffle / recover_batch / report_frames has two calls
+ * with a launch and a queue wait behind the frame's.  The first twelve arguments are ptam_track_frames_recover_batch's and mean the
+ * same; results, states, infos and iteration sets are that call's bit for bit (the same kernels on the same data), the reports'
+ * records and infos those of ptam_tracker_report_frames called behind it.
+ *   reports        nullable, as is every entry: camera i's frame goes into reports[i].  The fill (one workgroup per report, the
+ *                  kernel body of ptam_tracker_report_frames) is one more launch behind the fine pose loops on the chain's queue; its
+ *                  jobs ride in the batch's one argument upload (184 bytes a report), and its head words land in the frame's
+ *                  host-mapped result block under the frame's sequence number: the host waits for them as it waits for the frame.
+ *   tags           nullable: reports[i]'s tag (0 without).
+ *   shuffle_seeds  nullable: the caller has set the shuffles (on a map of more than 8192 points ptam_tracker_set_shuffle uploads them
+ *                  asynchronously from the context's pinned staging block, which a batch call fills next: wait for the tracker's
+ *                  queue between the two).  Otherwise EVERY camera's two orders are drawn in front of the set
+ *                  choice exactly as ptam_tracker_draw_shuffles(trackers[i], shuffle_seeds[i], states[i].frame) would, states[i].frame
+ *                  as it is at entry — one launch for all maps of at most 8192 points, the larger ones one by one.
+ *   report_info    nullable: per camera the report's info as ptam_frame_report_info gives it (zero without a report) and
+ *                  report_in_chain.
+ * What happens to a report:
+ *   PTAM_FRAME_RECOVERY_FAILED   the frame tracked nothing: the report comes back EMPTY (map_id 0, n_records 0, tag 0).  The fill
+ *                                workgroup reads the relocaliser's verdict as the TrackMap kernels do and does not look at the
+ *                                tracker's control block, which still holds the frame before.
+ *   a frame on the long path     its fine pose loop outgrew the fused kernel and is finished by launches the host enqueues on the
+ *                                frame's own queue behind the wait: the report cannot be in the chain.  It is filled behind those
+ *                                passes by ptam_tracker_report_frames itself, with a second wait; report_in_chain is 0.
+ *   a report too small           for its frame's found points: every frame is delivered and every state moves, THAT report comes
+ *                                back empty with report_too_small set, the call returns PTAM_E_ARG (as ptam_tracker_report_frames).
+ *                                A refused call writes no report_info: a caller that zeroes it first tells the two PTAM_E_ARG apart
+ *                                by that flag.
+ * Refused before the first enqueue with everything where it was, beyond ptam_track_frames_recover_batch's own refusals:
+ * PTAM_E_STATE a camera with a report whose tracker's map did not come from ptam_tracker_take_map; PTAM_E_ARG a report on another
+ * device, a report named twice.  As there, states and estimators advance on copies and commit when every frame has arrived.
+ * A failure BEHIND the first enqueue (PTAM_E_HIP, a wait that times out) leaves states and estimators where they were too, but not
+ * everything: every report of the call comes back empty (its records may be half rewritten), and with seeds the trackers' orders
+ * are the drawn ones. */
+typedef struct {
+    ptam_frame_report_info_t report;
+    int32_t report_in_chain;    /* 1: filled at the chain's end; 0: no report, or filled behind the long path's passes */
+    int32_t report_too_small;   /* 1: the report could not hold the frame's found points and is empty (the call returns PTAM_E_ARG) */
+} ptam_track_report_info;
+int ptam_track_frames_report_batch(int nb, ptam_tracker* const* trackers, ptam_kf* const* current, const uint8_t* const* d_frames,
+                                   ptam_track_state* states, ptam_rotation_estimator* const* estimators, ptam_sbi_bank* const* banks,
+                                   ptam_sbi* const* scratch, const ptam_trackmap_opts* opts, const ptam_track_state_opts* state_opts,
+                                   ptam_trackmap_result* out, ptam_track_frame_state_info* info, ptam_frame_report* const* reports,
+                                   const int64_t* tags, const uint64_t* shuffle_seeds, ptam_track_report_info* report_info);
+
 /* The consumers, on the mapmaker's thread.  Both refuse, on the host with every table as it was (PTAM_E_ARG): a null or empty
  * report (n_records == 0), a report whose map_id is not this handle's, a report on another device. */
 typedef struct { int32_t n_records, n_gone; } ptam_rmap_note_result;
@@ -1880,6 +1949,80 @@ int ptam_mapmaker_set_flags(ptam_mapmaker*, int converged_recent, int converged_
 /* up to cap tags the mapmaker has finished with, oldest first, removed from its list; *n: how many */
 int ptam_mapmaker_released(ptam_mapmaker*, int cap, int64_t* tags, int32_t* n);
 int ptam_mapmaker_step(ptam_mapmaker*, ptam_mapmaker_step_result*);
+
+/* ---- The tracker: one frame of Tracker::TrackFrame for a good map (src/Tracker.cc:127-176) as ONE call, hand-over included --------------
+ *      A ptam_camera_tracker OWNS what the reference's Tracker owns for that branch — the ptam_tracker, the current keyframe
+ *      (mCurrentKF), the rotation estimator (optional), the relocaliser's bank with its scratch image, the ptam_track_state, a pool
+ *      of frame reports and a pool of keyframe clones — all created by _create, so a frame allocates nothing.  It BORROWS the
+ *      ptam_map_snapshot the map is published into (keyframe section enabled) and the ptam_mapmaker (destroy the handle first).
+ *      It lives on the tracker's thread, in `ctx`; of the mapmaker it uses only the entries that thread may call
+ *      (ptam_mapmaker_released, _queue_size, _add_keyframe, _note_frame), so it touches neither the map's context nor its queue.
+ *      TrackForInitialMap (:181) is not here: a session starts with ptam_rmap_init_from_stereo, a publish and _reset(tracker pose).
+ *      ptam_camera_tracker_track_frames, for nb handles in different contexts on one device (as ptam_track_frames_recover_batch asks)
+ *      whose trackmap and state options are the same (PTAM_E_ARG otherwise: a chain takes them once):
+ *        per camera   (a) ptam_mapmaker_released: a report whose tag came back is free again; a CLONE whose tag came back has been
+ *                         inserted by the mapmaker's step and stays with the map until _reset / _destroy.  Handles that share a
+ *                         mapmaker must be tracked in the same call (the tags are read once per mapmaker and dealt out).
+ *                         PTAM_E_STATE, before anything is enqueued: no free report; no free clone while the frame could end in
+ *                         AddKeyFrame (the camera is not lost and frame + 1 - last_keyframe_dropped > keyframe_gap).
+ *                     (b) ptam_tracker_take_map and ptam_sbi_bank_take_keyframes from the snapshot.  PTAM_E_STATE "no map": nothing
+ *                         was ever published, or the map has no point: this handle tracks a map that exists.
+ *        together     (c) ptam_track_frames_report_batch with every camera's report, tag and seed (opts.shuffle_seed): the orders
+ *                         are drawn on the device, the report is filled inside the chain.
+ *        per camera   (d) :146-166.  ADD when the branch is PTAM_FRAME_TRACKED, the quality GOOD, frame - last_keyframe_dropped >
+ *                         keyframe_gap, ptam_mapmaker_queue_size < max_queue and the report has records: ptam_kf_copy of the current
+ *                         keyframe into a pooled clone (waited for: the mapmaker reads it on another queue),
+ *                         ptam_mapmaker_add_keyframe(clone, the tracked pose, 0, report, the model's scene depth mean and sigma, tag),
+ *                         last_keyframe_dropped = frame.  Otherwise NOTE for a TRACKED or RECOVERED frame whose report has records:
+ *                         ptam_mapmaker_note_frame(report, tag).  A report that was not handed over is free again at once.
+ *                     (e) the result.  tag = opts.tag_base + the state's frame at entry.
+ *      Errors: a refusal in (a) or (b), or of the chain, leaves every state, estimator and pool where it was (tags that were released
+ *      stay released, a take that succeeded stays taken: both only bring the handle up to date).  A failure in (d) — the mapmaker
+ *      refusing — is returned behind the frames that were delivered; that camera's report is free again. */
+typedef struct ptam_camera_tracker ptam_camera_tracker;
+typedef struct {
+    int32_t max_points;              /* the largest map the tracker takes */
+    int32_t width, height;           /* of the frames: the context's image size */
+    int32_t max_keyframes;           /* the relocaliser bank's capacity: the most keyframes a published map may hold */
+    ptam_trackmap_opts trackmap;
+    ptam_track_state_opts state;
+    int32_t use_rotation_estimator;  /* 1: Tracker.UseRotationEstimator */
+    int32_t keyframe_gap;            /* 20 (:148) */
+    double rotation_blur;            /* 0.75: Tracker.RotationEstimatorBlur */
+    uint64_t shuffle_seed;
+    int64_t tag_base;
+    int32_t max_queue;               /* 3 (:149) */
+    int32_t reports, keyframes;      /* pool sizes; a keyframe clone that entered the map does not come back before _reset */
+    int32_t pad_;
+} ptam_camera_tracker_opts;
+typedef struct {
+    ptam_trackmap_result track;
+    ptam_track_frame_state_info info;
+    ptam_frame_report_info_t report;         /* as filled; the report itself may have gone to the mapmaker */
+    ptam_map_take_result map_take;
+    ptam_keyframes_take_result keyframes_take;
+    int32_t added_keyframe, noted_frame, report_in_chain, queue_size;   /* queue_size: as asked in (d), before an add */
+    int64_t tag;
+} ptam_camera_track_result;
+/* the reference's: trackmap and state defaults, estimator on, blur 0.75, gap 20, queue 3; max_points 8192, max_keyframes 64,
+ * 8 reports, 32 keyframes, seed 0, tag_base 0; width / height 640 x 480 */
+int ptam_camera_tracker_opts_default(ptam_camera_tracker_opts*);
+int ptam_camera_tracker_create(ptam_ctx* ctx, const ptam_camera_tracker_opts* opts, ptam_map_snapshot* snapshot, ptam_mapmaker* mapmaker,
+                               ptam_camera_tracker** out);
+int ptam_camera_tracker_destroy(ptam_camera_tracker*);
+/* Tracker::Reset (:52-62): the state at pose12 (ptam_track_state_reset), the estimator and the relocaliser's bank cleared, every
+ * report and clone back in its pool (the map that named them is gone: ptam_mapmaker_request_reset is the caller's, before). */
+int ptam_camera_tracker_reset(ptam_camera_tracker*, const double pose12[12]);
+int ptam_camera_tracker_state(const ptam_camera_tracker*, ptam_track_state* out);
+/* the inner handles, for drawing and tests; they stay the handle's.  _last_report: the report of the last frame (null before the
+ * first); the next frame may refill it unless it went to the mapmaker. */
+ptam_tracker* ptam_camera_tracker_tracker(ptam_camera_tracker*);
+ptam_kf* ptam_camera_tracker_current_keyframe(ptam_camera_tracker*);
+ptam_frame_report* ptam_camera_tracker_last_report(ptam_camera_tracker*);
+/* free reports and free clones, for a caller that watches its pools */
+int ptam_camera_tracker_pool(const ptam_camera_tracker*, int32_t* free_reports, int32_t* free_keyframes);
+int ptam_camera_tracker_track_frames(int nb, ptam_camera_tracker* const* handles, const uint8_t* const* d_frames,
+                                     ptam_camera_track_result* results);
 
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,

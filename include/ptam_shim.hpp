@@ -109,6 +109,13 @@ public:
         }
         return *this;
     }
+    // the same deep copy into THIS keyframe's own memory (same image size): no allocation — the pooled clone of the tracker's
+    // current keyframe for MapMaker::AddKeyFrame (ptam_kf_copy).  Asynchronous on the context's queue.
+    KeyFrame& CopyFrom(const KeyFrame& o) {
+        check(ptam_kf_copy(ctx_->handle(), o.h_, h_), "ptam_kf_copy");
+        fetched_ = 0;
+        return *this;
+    }
     // void MakeKeyFrame_Lite(CVD::BasicImage<CVD::byte>& im)   include/KeyFrame.h:141, src/KeyFrame.cc:18
     void MakeKeyFrame_Lite(const uint8_t* im, int stride) {
         check(ptam_make_keyframe_lite(ctx_->handle(), h_, im, stride), "ptam_make_keyframe_lite");
@@ -892,6 +899,22 @@ public:
     void SetShuffle(const std::vector<int32_t>& vLevels, const std::vector<int32_t>& vFine) {
         check(ptam_tracker_set_shuffle(h_, vLevels.data(), vFine.data()), "ptam_tracker_set_shuffle");
     }
+    // The two orders drawn on the device instead (ptam_tracker_draw_shuffles): asynchronous on the tracker's queue, nothing the size
+    // of the map is made or sent by the host.  ShuffleOrder is what they are, in host code.
+    void DrawShuffles(uint64_t nSeed, uint64_t nFrame) { check(ptam_tracker_draw_shuffles(h_, nSeed, nFrame), "ptam_tracker_draw_shuffles"); }
+    static std::vector<int32_t> ShuffleOrder(uint64_t nSeed, uint64_t nFrame, int nWhich, int nPoints) {
+        std::vector<int32_t> v((size_t)(nPoints > 0 ? nPoints : 0));
+        check(ptam_shuffle_order_host(nSeed, nFrame, nWhich, nPoints, v.data()), "ptam_shuffle_order_host");
+        return v;
+    }
+    // the orders the next frame will use, however they were set (nPoints: the map's size)
+    void ReadShuffle(int nPoints, std::vector<int32_t>& vLevels, std::vector<int32_t>& vFine) {
+        vLevels.assign((size_t)(nPoints > 0 ? nPoints : 1), 0);
+        vFine.assign(vLevels.size(), 0);
+        check(ptam_tracker_read_shuffle(h_, vLevels.data(), vFine.data()), "ptam_tracker_read_shuffle");
+        vLevels.resize((size_t)(nPoints > 0 ? nPoints : 0));
+        vFine.resize(vLevels.size());
+    }
     ptam_trackmap_result TrackMap(KeyFrame& kfCurrent, const SE3& se3Predicted, const ptam_trackmap_opts* pOpts = nullptr) {
         double in[12];
         se3Predicted.to12(in);
@@ -1006,6 +1029,49 @@ public:
               "ptam_track_frames_recover_batch");
         for (size_t i = 0; i < n; i++) static_cast<ptam_track_state&>(vStates[i]) = st[i];
         return r;
+    }
+    // TrackFramesRecoverBatch with every camera's FrameReport filled inside the chain (vReports[i] may be null) and, with vSeeds, the
+    // frames' two orders drawn there (frame index: the state's frame) — one call and one wait per camera for what SetShuffle,
+    // TrackFramesRecoverBatch and ReportFramesBatch are together (ptam_track_frames_report_batch).  vReportInfo: per camera the report's
+    // info and whether it was filled in the chain.  -> false where a report was too small for its frame: everything is delivered, that
+    // report is empty.
+    static bool TrackFramesReportBatch(const std::vector<MapTracker*>& vTrackers, const std::vector<KeyFrame*>& vCurrent,
+                                       const std::vector<const uint8_t*>& vdFrames, std::vector<TrackState>& vStates,
+                                       const std::vector<RotationEstimator*>& vEstimators, const std::vector<Relocaliser*>& vRelocalisers,
+                                       const std::vector<FrameReport*>& vReports, const std::vector<int64_t>& vTags, const std::vector<uint64_t>& vSeeds,
+                                       std::vector<ptam_trackmap_result>& vResults, std::vector<ptam_track_frame_state_info>& vInfo,
+                                       std::vector<ptam_track_report_info>& vReportInfo, const ptam_trackmap_opts* pOpts = nullptr,
+                                       const ptam_track_state_opts* pStateOpts = nullptr) {
+        const size_t n = vTrackers.size();
+        if (n == 0 || vCurrent.size() != n || vdFrames.size() != n || vStates.size() != n || (!vEstimators.empty() && vEstimators.size() != n) ||
+            (!vRelocalisers.empty() && vRelocalisers.size() != n) || (!vReports.empty() && vReports.size() != n) ||
+            (!vTags.empty() && vTags.size() != n) || (!vSeeds.empty() && vSeeds.size() != n))
+            throw std::runtime_error("TrackFramesReportBatch: sizes differ");
+        std::vector<ptam_tracker*> t(n);
+        std::vector<ptam_kf*> k(n);
+        std::vector<ptam_rotation_estimator*> e(n, nullptr);
+        std::vector<ptam_sbi_bank*> b(n, nullptr);
+        std::vector<ptam_sbi*> s(n, nullptr);
+        std::vector<ptam_frame_report*> rp(n, nullptr);
+        std::vector<ptam_track_state> st(vStates.begin(), vStates.end());
+        for (size_t i = 0; i < n; i++) {
+            t[i] = vTrackers[i]->h_;
+            k[i] = vCurrent[i]->handle();
+            if (!vEstimators.empty() && vEstimators[i]) e[i] = vEstimators[i]->handle();
+            if (!vRelocalisers.empty() && vRelocalisers[i]) b[i] = vRelocalisers[i]->handle(), s[i] = vRelocalisers[i]->scratch();
+            if (!vReports.empty() && vReports[i]) rp[i] = vReports[i]->handle();
+        }
+        vResults.assign(n, ptam_trackmap_result{});
+        vInfo.assign(n, ptam_track_frame_state_info{});
+        vReportInfo.assign(n, ptam_track_report_info{});
+        const int rc = ptam_track_frames_report_batch((int)n, t.data(), k.data(), vdFrames.data(), st.data(), e.data(), b.data(), s.data(), pOpts,
+                                                      pStateOpts, vResults.data(), vInfo.data(), rp.data(), vTags.empty() ? nullptr : vTags.data(),
+                                                      vSeeds.empty() ? nullptr : vSeeds.data(), vReportInfo.data());
+        bool delivered = rc == PTAM_OK;   // ... or PTAM_E_ARG with a report marked too small (a refused call writes no info)
+        for (size_t i = 0; i < n && rc == PTAM_E_ARG; i++) delivered = delivered || vReportInfo[i].report_too_small != 0;
+        if (!delivered) check(rc, "ptam_track_frames_report_batch");
+        for (size_t i = 0; i < n; i++) static_cast<ptam_track_state&>(vStates[i]) = st[i];
+        return rc == PTAM_OK;
     }
     // vIterationSet of the last frame: what :667-676 turns into mCurrentKF.mMeasurements and what routes the outlier flags
     // back to MapPoint::nMEstimatorOutlierCount
@@ -1557,6 +1623,74 @@ public:
 
 private:
     ptam_mapmaker* h_ = nullptr;
+};
+
+// class Tracker   include/Tracker.h, src/Tracker.cc:86-188 for a map that is good (:127-176) — ptam_camera_tracker: one TrackFrame is
+// ONE call that takes the published map and its keyframes, draws the frame's random orders, tracks or recovers, fills the frame's
+// report inside the chain and hands the frame to the MapMaker (AddKeyFrame with a pooled clone of the current keyframe, or NoteFrame).
+// It owns the MapTracker, the current KeyFrame, the rotation estimator, the relocaliser, the state and the pools; it borrows the
+// snapshot and the MapMaker, which must outlive it, and lives on the tracker's thread in its own Context.  TrackForInitialMap is
+// not here: start from ResidentMap::InitFromStereo, a Publish and Reset(the tracker's pose).
+class Tracker {
+public:
+    // the reference's options with the Context's image size
+    static ptam_camera_tracker_opts DefaultOpts(const Context& c) {
+        ptam_camera_tracker_opts o;
+        check(ptam_camera_tracker_opts_default(&o), "ptam_camera_tracker_opts_default");
+        o.width = c.size().x, o.height = c.size().y;
+        return o;
+    }
+    Tracker(Context& c, MapSnapshot& snapshot, MapMaker& mapmaker, const ptam_camera_tracker_opts* pOpts = nullptr) {
+        const ptam_camera_tracker_opts o = pOpts ? *pOpts : DefaultOpts(c);
+        check(ptam_camera_tracker_create(c.handle(), &o, snapshot.handle(), mapmaker.handle(), &h_), "ptam_camera_tracker_create");
+    }
+    ~Tracker() { ptam_camera_tracker_destroy(h_); }
+    Tracker(const Tracker&) = delete;
+    Tracker& operator=(const Tracker&) = delete;
+    // void Tracker::TrackFrame(Image<byte> &imFrame, bool bDraw)   :86 — dFrame: the frame in device memory (stride == width)
+    ptam_camera_track_result TrackFrame(const uint8_t* dFrame) {
+        ptam_camera_track_result r;
+        check(ptam_camera_tracker_track_frames(1, &h_, &dFrame, &r), "ptam_camera_tracker_track_frames");
+        return r;
+    }
+    // several cameras in ONE chain: Contexts of their own on one device, the same trackmap / state options
+    static std::vector<ptam_camera_track_result> TrackFrames(const std::vector<Tracker*>& vTrackers, const std::vector<const uint8_t*>& vdFrames) {
+        const size_t n = vTrackers.size();
+        if (n == 0 || vdFrames.size() != n) throw std::runtime_error("TrackFrames: sizes differ");
+        std::vector<ptam_camera_tracker*> h(n);
+        for (size_t i = 0; i < n; i++) h[i] = vTrackers[i]->h_;
+        std::vector<ptam_camera_track_result> r(n);
+        check(ptam_camera_tracker_track_frames((int)n, h.data(), vdFrames.data(), r.data()), "ptam_camera_tracker_track_frames");
+        return r;
+    }
+    TrackState State() const {
+        TrackState s;
+        check(ptam_camera_tracker_state(h_, &s), "ptam_camera_tracker_state");
+        return s;
+    }
+    SE3 GetCurrentPose() const { return SE3::from12(State().model.pose); }   // mse3CamFromWorld
+    int Quality() const { return State().quality; }                          // mTrackingQuality: PTAM_TRACK_BAD / PTAM_TRACK_GOOD
+    int LostFrames() const { return State().lost_frames; }                   // mnLostFrames
+    // void Tracker::Reset()   :52-62 (MapMaker::RequestReset is the caller's, before)
+    void Reset(const SE3& se3CfromW = SE3::Identity()) {
+        double p[12];
+        se3CfromW.to12(p);
+        check(ptam_camera_tracker_reset(h_, p), "ptam_camera_tracker_reset");
+    }
+    // free reports and free keyframe clones
+    void Pool(int& nFreeReports, int& nFreeKeyFrames) const {
+        int32_t a = 0, b = 0;
+        check(ptam_camera_tracker_pool(h_, &a, &b), "ptam_camera_tracker_pool");
+        nFreeReports = a, nFreeKeyFrames = b;
+    }
+    // the inner handles, for drawing: they stay the Tracker's
+    ptam_tracker* tracker() const { return ptam_camera_tracker_tracker(h_); }
+    ptam_kf* current_keyframe() const { return ptam_camera_tracker_current_keyframe(h_); }
+    ptam_frame_report* last_report() const { return ptam_camera_tracker_last_report(h_); }
+    ptam_camera_tracker* handle() const { return h_; }
+
+private:
+    ptam_camera_tracker* h_ = nullptr;
 };
 
 // class Bundle (include/Bundle.h:106-152)

@@ -315,6 +315,25 @@ class FrameReportInfo(C.Structure):
                 ("pad_", C.c_int32)]
 
 
+class TrackReportInfo(C.Structure):
+    """ptam_track_report_info (ptam_track_frames_report_batch)"""
+    _fields_ = [("report", FrameReportInfo), ("report_in_chain", C.c_int32), ("report_too_small", C.c_int32)]
+
+
+class TrackmapOpts(C.Structure):
+    """ptam_trackmap_opts"""
+    _fields_ = [("try_coarse", C.c_int32), ("coarse_min", C.c_uint32), ("coarse_max", C.c_uint32), ("coarse_range", C.c_uint32),
+                ("coarse_subpix_its", C.c_int32), ("max_patches", C.c_int32), ("estimator", C.c_int32), ("pad_", C.c_int32)]
+
+
+class TrackmapResult(C.Structure):
+    """ptam_trackmap_result"""
+    _fields_ = [("pose", C.c_double * 12), ("did_coarse", C.c_int32), ("n_pvs", C.c_int32 * 4), ("attempted", C.c_int32 * 4),
+                ("found", C.c_int32 * 4), ("n_coarse", C.c_int32), ("n_top", C.c_int32), ("n_fine", C.c_int32), ("n_meas", C.c_int32),
+                ("depth_n", C.c_int32), ("templates_reused", C.c_int32), ("pad_", C.c_int32), ("depth_sum", C.c_double),
+                ("depth_sum_sq", C.c_double)]
+
+
 class RmapNoteResult(C.Structure):
     """ptam_rmap_note_result"""
     _fields_ = [("n_records", C.c_int32), ("n_gone", C.c_int32)]
@@ -382,6 +401,21 @@ class TrackFrameStateInfo(C.Structure):
                 ("want_keyframe", C.c_int32), ("frame", TrackFrameInfo), ("reloc", RelocResult)]
 
 
+class CameraTrackerOpts(C.Structure):
+    """ptam_camera_tracker_opts"""
+    _fields_ = [("max_points", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("max_keyframes", C.c_int32),
+                ("trackmap", TrackmapOpts), ("state", TrackStateOpts), ("use_rotation_estimator", C.c_int32), ("keyframe_gap", C.c_int32),
+                ("rotation_blur", C.c_double), ("shuffle_seed", C.c_uint64), ("tag_base", C.c_int64), ("max_queue", C.c_int32),
+                ("reports", C.c_int32), ("keyframes", C.c_int32), ("pad_", C.c_int32)]
+
+
+class CameraTrackResult(C.Structure):
+    """ptam_camera_track_result"""
+    _fields_ = [("track", TrackmapResult), ("info", TrackFrameStateInfo), ("report", FrameReportInfo), ("map_take", MapTakeResult),
+                ("keyframes_take", KeyframesTakeResult), ("added_keyframe", C.c_int32), ("noted_frame", C.c_int32),
+                ("report_in_chain", C.c_int32), ("queue_size", C.c_int32), ("tag", C.c_int64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p)
 
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
@@ -407,6 +441,7 @@ PROTOTYPES = {
     "make_keyframe_lite": (_i, [_vp, _vp, _vp, _i]),
     "make_keyframe_lite_dev": (_i, [_vp, _vp, _vp]),
     "kf_clone": (_i, [_vp, _vp, _ppv]),
+    "kf_copy": (_i, [_vp, _vp, _vp]),
     "kf_level_info": (_i, [_vp, _vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "kf_read_level": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "make_keyframe_rest": (_i, [_vp, _vp]),
@@ -478,6 +513,9 @@ PROTOTYPES = {
     "tracker_set_map": (_i, [_vp, _i, _vp, _vp]),
     "tracker_update_map": (_i, [_vp, _i, _vp, _vp, _vp]),
     "tracker_set_shuffle": (_i, [_vp, _vp, _vp]),
+    "tracker_draw_shuffles": (_i, [_vp, C.c_uint64, C.c_uint64]),
+    "tracker_read_shuffle": (_i, [_vp, _vp, _vp]),
+    "shuffle_order_host": (_i, [C.c_uint64, C.c_uint64, _i, _i, _vp]),
     "track_map": (_i, [_vp, _vp, _pd, _vp, _vp]),
     "track_map_frame": (_i, [_vp, _vp, _vp, _pd, _vp, _vp]),
     "motion_reset": (None, [C.POINTER(MotionModel), _pd]),
@@ -519,6 +557,18 @@ PROTOTYPES = {
     "tracker_read_reloc_ssd": (_i, [_vp, _i, _i, _pd]),
     "track_frames_recover_batch": (_i, [_i, _vp, _vp, _vp, C.POINTER(TrackState), _vp, _vp, _vp, _vp, C.POINTER(TrackStateOpts), _vp,
                                         C.POINTER(TrackFrameStateInfo)]),
+    "track_frames_report_batch": (_i, [_i, _vp, _vp, _vp, C.POINTER(TrackState), _vp, _vp, _vp, _vp, C.POINTER(TrackStateOpts), _vp,
+                                       C.POINTER(TrackFrameStateInfo), _vp, _vp, _vp, C.POINTER(TrackReportInfo)]),
+    "camera_tracker_opts_default": (_i, [C.POINTER(CameraTrackerOpts)]),
+    "camera_tracker_create": (_i, [_vp, C.POINTER(CameraTrackerOpts), _vp, _vp, _ppv]),
+    "camera_tracker_destroy": (_i, [_vp]),
+    "camera_tracker_reset": (_i, [_vp, _pd]),
+    "camera_tracker_state": (_i, [_vp, C.POINTER(TrackState)]),
+    "camera_tracker_tracker": (_vp, [_vp]),
+    "camera_tracker_current_keyframe": (_vp, [_vp]),
+    "camera_tracker_last_report": (_vp, [_vp]),
+    "camera_tracker_pool": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "camera_tracker_track_frames": (_i, [_i, _vp, _vp, C.POINTER(CameraTrackResult)]),
     "bench_track_batch": (_i, [_i, _vp, _vp, _vp, _pd, _vp, _vp, _vp, _i, _i, _pd]),
     "tracker_read_iteration_set": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "ba_bench_jacobian_rotating": (_i, [_vp, _i, _i, _pd]),

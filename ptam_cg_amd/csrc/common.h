@@ -107,6 +107,7 @@ void maprmap_keyframe_preload_kernels();
 void maprmap_publish_preload_kernels();
 void maprmap_init_preload_kernels();
 void framereport_preload_kernels();
+void tracker_run_preload_kernels();
 int pose_hazards_read_pose(hipStream_t st, unsigned long long* out);
 int pose_hazards_read_trackmap(hipStream_t st, unsigned long long* out);
 int ctx_scratch(ptam_ctx* ctx, size_t bytes, void** out);     // device scratch >= bytes

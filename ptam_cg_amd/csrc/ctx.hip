@@ -256,6 +256,7 @@ int ptam_ctx_create(const ptam_cam_params* cam, int device, ptam_ctx** out) {
     maprmap_publish_preload_kernels();
     maprmap_init_preload_kernels();
     framereport_preload_kernels();
+    tracker_run_preload_kernels();
     if (const int rc = ba_preload_kernels()) {   // (its error text stands)
         hipStreamDestroy(c->stream);
         delete c;

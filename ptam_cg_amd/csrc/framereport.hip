@@ -65,9 +65,10 @@ __device__ __forceinline__ ptam_frame_record fr_record(const FrJob& j, int p, in
     return r;
 }
 
-__global__ void __launch_bounds__(FR_TILE) fr_fill_kernel(const FrJob* __restrict__ jobs, int* __restrict__ heads) {
+// one workgroup fills job jobs[at]; heads + at * FR_HEAD_WORDS: the job's head words, written by thread 0 as the workgroup's last act
+__device__ __forceinline__ void fr_fill_body(const FrJob* __restrict__ jobs, int* __restrict__ heads, unsigned at) {
     __shared__ int ws[2][FR_TILE / 64];
-    const FrJob j = jobs[blockIdx.y];
+    const FrJob j = jobs[at];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int n = j.n_points;
     const int ns = j.entries ? j.n_entries : min(max(*j.n_slots, 0), j.cap);
@@ -107,11 +108,36 @@ __global__ void __launch_bounds__(FR_TILE) fr_fill_kernel(const FrJob* __restric
         __syncthreads();   // (the wave counts are rewritten by the next tile)
     }
     if (tid == 0) {
-        int* h = heads + (size_t)blockIdx.y * FR_HEAD_WORDS;
+        int* h = heads + (size_t)at * FR_HEAD_WORDS;
         h[FR_H_RECORDS] = run;
         h[FR_H_OUTLIERS] = n_out;
         h[FR_H_ENTRIES] = ns;
         h[FR_H_PAD] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(FR_TILE) fr_fill_kernel(const FrJob* __restrict__ jobs, int* __restrict__ heads) {
+    fr_fill_body(jobs, heads, blockIdx.y);
+}
+
+// The fill at the end of a batch chain (ptam_track_frames_report_batch): the head words go to the frame's host-mapped block and the
+// frame's sequence number behind them — what the host waits for.  A frame whose recovery failed (the gate, read as the TrackMap
+// kernels read it) has tracked nothing: its head is zero and the tracker's control block, which still holds the frame before, is
+// not looked at.  A frame whose fine pose loop asked for the long path (its sequence word says so) is not finished yet: nothing is
+// filled or published, the host fills it behind the passes it enqueues.
+__global__ void __launch_bounds__(FR_TILE) fr_fill_chain_kernel(const FrChainJob* __restrict__ jobs) {
+    const FrChainJob& c = jobs[blockIdx.y];
+    if (*(volatile const unsigned long long*)c.frame_word & FR_FRAME_LONG) return;
+    if (c.gate && !*c.gate) {
+        if (threadIdx.x < FR_HEAD_WORDS) c.head[threadIdx.x] = 0;
+    } else {
+        fr_fill_body(&c.job, c.head, 0);
+    }
+    __threadfence();   // (the records: whoever the host hands the report to may read them on another queue)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence_system();
+        *(volatile unsigned long long*)c.head_seq = c.seq;
     }
 }
 
@@ -120,6 +146,12 @@ __global__ void __launch_bounds__(FR_TILE) fr_fill_kernel(const FrJob* __restric
 
 int fr_fill_core(hipStream_t st, int nb, const FrJob* d_jobs, int* d_heads) {
     hipLaunchKernelGGL(fr_fill_kernel, dim3(1, (unsigned)nb), dim3(FR_TILE), 0, st, d_jobs, d_heads);
+    HIP_TRY(hipGetLastError());
+    return PTAM_OK;
+}
+
+int fr_fill_chain_core(hipStream_t st, int nb, const FrChainJob* d_jobs) {
+    hipLaunchKernelGGL(fr_fill_chain_kernel, dim3(1, (unsigned)nb), dim3(FR_TILE), 0, st, d_jobs);
     HIP_TRY(hipGetLastError());
     return PTAM_OK;
 }
@@ -238,4 +270,7 @@ int ptam_frame_report_from_host(ptam_frame_report* r, int64_t map_id, int n_poin
 
 }   // extern "C"
 
-void framereport_preload_kernels() { ptam_preload((const void*)fr_fill_kernel); }
+void framereport_preload_kernels() {
+    ptam_preload((const void*)fr_fill_kernel);
+    ptam_preload((const void*)fr_fill_chain_kernel);
+}

@@ -38,5 +38,17 @@ enum { FR_H_RECORDS = 0, FR_H_OUTLIERS, FR_H_ENTRIES, FR_H_PAD, FR_HEAD_WORDS };
 // d_jobs: nb jobs in device memory; d_heads: nb x FR_HEAD_WORDS.  One launch, one workgroup per job.  FR_H_RECORDS is the found
 // points' count even where it exceeds max_records (nothing is written behind max_records).
 int fr_fill_core(hipStream_t st, int nb, const FrJob* d_jobs, int* d_heads);
+// A job of the fill that closes a batch chain: the heads go to host-mapped words, the sequence number behind them.
+struct FrChainJob {
+    FrJob job;
+    const int* gate;                          // nullable: *gate == 0 — the frame tracked nothing, the head is zero, job is not looked at
+    const unsigned long long* frame_word;     // the frame's published sequence word: FR_FRAME_LONG in it — not finished, nothing is done
+    int* head;                                // FR_HEAD_WORDS words, host-mapped
+    unsigned long long* head_seq;             // host-mapped: = seq once head and the records are written
+    unsigned long long seq;
+};
+static_assert(sizeof(FrChainJob) == 184, "what ptam_hip.h says the chain's fill sends up per report");
+#define FR_FRAME_LONG (1ull << 63)   // POSE_CHAIN_LONG (track_internal.h)
+int fr_fill_chain_core(hipStream_t st, int nb, const FrChainJob* d_jobs);
 // the report's mark array holds n_points words (the one allocation a fill may make)
 int fr_mark_room(ptam_frame_report* r, int n_points);

@@ -402,6 +402,23 @@ int ptam_kf_clone(ptam_ctx* ctx, const ptam_kf* src, ptam_kf** out) {
     return PTAM_OK;
 }
 
+int ptam_kf_copy(ptam_ctx* ctx, const ptam_kf* src, ptam_kf* dst) {
+    ARG_TRY(ctx && src && dst && src != dst);
+    ARG_TRY(src->device == ctx->device && dst->device == ctx->device);
+    // (one size, one layout: kf_alloc derives every offset from the image size)
+    ARG_TRY(src->L.w[0] == dst->L.w[0] && src->L.h[0] == dst->L.h[0] && src->bytes_total == dst->bytes_total);
+    HIP_TRY(hipSetDevice(ctx->device));
+    // pixels | masks | corners | row LUTs | counts; the MakeKeyFrame_Rest half only if src has made it (a tracker's keyframe has
+    // not: dst's own is then left as it is and counts as not made — ptam_make_keyframe_rest clears what it accumulates into)
+    const size_t bytes = src->rest_made ? src->bytes_total : src->off_rest_clear;
+    HIP_TRY(hipMemcpyAsync(dst->base, src->base, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    dst->counts_valid = 0;
+    dst->rest_valid = 0;
+    dst->rest_made = src->rest_made;
+    for (int l = 0; l < PTAM_LEVELS; l++) dst->implane_valid[l] = 0;
+    return PTAM_OK;
+}
+
 int ptam_kf_level_info(ptam_ctx* ctx, const ptam_kf* kf, int level, int* w, int* h, int* n_corners) {
     ARG_TRY(ctx && kf && level >= 0 && level < PTAM_LEVELS);
     HIP_TRY(hipSetDevice(ctx->device));

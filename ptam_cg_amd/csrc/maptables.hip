@@ -372,8 +372,8 @@ __global__ void __launch_bounds__(256) mt_sort_merge_kernel(int n, int run, cons
     out[base + (g - (right ? mid : base)) + (lo - sib)] = key;
 }
 
-// n keys in a, ascending, into a or b (n keys of room each): the buffer that holds them
-static unsigned long long* mt_sort_keys(hipStream_t st, int n, unsigned long long* a, unsigned long long* b) {
+// n keys in a, ascending, into a or b (n keys of room each): the buffer that holds them (maptables_internal.h)
+unsigned long long* mt_sort_keys(hipStream_t st, int n, unsigned long long* a, unsigned long long* b) {
     if (n == 0) return a;
     hipLaunchKernelGGL(mt_sort_tile_kernel, dim3(mt_tiles(n)), dim3(MT_TILE), 0, st, n, (const unsigned long long*)a, b);
     unsigned long long *src = b, *dst = a;

@@ -114,6 +114,10 @@ static inline MtAdd mt_add_head(int src_kf, int target_kf, int target_source, in
 enum { MT_MADE_WORDS = 5 };
 int mt_made_records_core(hipStream_t st, int n, const int32_t* status, const ptam_new_map_point* in, ptam_new_map_point* out, int* tiles, int* tot);
 
+// ---- the sort of 64-bit keys (maptables.hip): n keys in a, ascending, into a or b (n keys of room each) -> the buffer that holds
+//      them.  Only enqueues on st.  Every key must lie below ~0 (a short last tile is filled with it).
+unsigned long long* mt_sort_keys(hipStream_t st, int n, unsigned long long* a, unsigned long long* b);
+
 // ---- the work lists of mr_run from the resident queues (maptables.hip); keys_a / keys_b: n 64-bit keys of room each
 //      mqNewQueue's entries whose point is not bad, in queue order (the ordered compaction): wpts = the points, wentry = their
 //      entries; *total = how many.  tiles: mt_tiles(n_new)

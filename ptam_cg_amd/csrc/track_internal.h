@@ -39,6 +39,18 @@ void kf_lite_begin(ptam_kf* kf, const uint8_t* d_src, PyrArgs* a_out, int* gx, i
 void kf_launch_detect(ptam_kf* kf, hipStream_t stream);
 // FAST detection for nb keyframes of equal geometry in one launch: their KfLevels sit at d_items + i * stride + off_levels
 void kf_launch_detect_batch(int nb, const KfLevels& L, const void* d_items, size_t stride, size_t off_levels, hipStream_t stream);   // (L: the common geometry)
+// tracker_run.hip: a frame's two random orders drawn on the device (ptam_tracker_draw_shuffles), enqueued on st: n entries into each
+// of perm_a / perm_b.  keys: 4 n 64-bit words of work for a map of more than TR_DRAW_LDS_MAX points (not looked at otherwise)
+enum { TR_DRAW_LDS_MAX = 8192 };
+int tr_draw_shuffles_on(hipStream_t st, int n, uint64_t seed, uint64_t frame, int* perm_a, int* perm_b, unsigned long long* keys);
+// the same for the cameras of a batch chain whose maps hold at most TR_DRAW_LDS_MAX points: a job table in device memory, one launch
+struct TrDrawJob {
+    unsigned long long seed, frame;
+    int* perm_a;
+    int* perm_b;
+    int n, pad_;
+};
+int tr_draw_shuffles_batch_on(hipStream_t st, int nb, int n_max, const TrDrawJob* d_jobs);
 // trackmap.hip: the context a tracker was created with
 ptam_ctx* tracker_ctx(const ptam_tracker* t);
 // motion.hip

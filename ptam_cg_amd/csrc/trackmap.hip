@@ -18,6 +18,7 @@
 // with its re-projection at the post-coarse pose and the camera derivatives of the PVS pass (ProjectAndDerivs only
 // refreshes them for found points, include/Tracker.h:89-94).
 #include <climits>
+#include <memory>
 
 #include "track_internal.h"
 #include "sbi.h"                  // ptam_track_frames_batch: the estimators' steps of a batch
@@ -481,6 +482,10 @@ struct TmMailbox {
     double pose_in[12];
     // ptam_track_frames_recover_batch, a recovering frame: the relocaliser's result, written by the frame's align workgroup likewise
     ptam_reloc_result reloc;
+    // ptam_track_frames_report_batch: the head words of the frame's report, written by the fill at the chain's end (framereport.hip),
+    // and the frame's sequence number behind them
+    unsigned long long report_seq;
+    int report_head[4];
 };
 // the last act of a gather pass: thread 0 books the per-level counts and the stage's outcome (coarse: mbDidCoarse and the
 // fine range; fine: everything of the frame's result but the pose and the depth sums)
@@ -913,6 +918,7 @@ struct ptam_tracker {
     int* perm_host;        // [2][cap], host address
     int* perm_host_dev;    // device address of the same memory
     int *perm_dev_a, *perm_dev_b;
+    unsigned long long* draw_keys;   // ptam_tracker_draw_shuffles' sort of a map of more than TR_DRAW_LDS_MAX points: [4][cap]; null for a smaller tracker
     // argument arrays of the batches this tracker leads (ptam_track_map_frames_batch): grown on demand
     void* batch_dev;
     size_t batch_cap;
@@ -1002,7 +1008,8 @@ static void tm_read_result(const ptam_tracker* t, ptam_trackmap_result* out) {
 // Wait for frame `seq` of t, whose chain was enqueued on `st` (the tracker's own queue, or a batch's): the frame's last kernel
 // publishes the sequence number — or, for a list of more than 1024 entries, asks for the general path, which the tracker's own queue
 // then runs and which publishes it.  fused: the fine stage went out as the fused bookkeeping + pose kernel.
-static int tm_wait_frame(ptam_tracker* t, hipStream_t st, const ptam_trackmap_opts& o, unsigned long long seq, bool fused) {
+// *went_long (nullable) is set when the general path ran.
+static int tm_wait_frame(ptam_tracker* t, hipStream_t st, const ptam_trackmap_opts& o, unsigned long long seq, bool fused, bool* went_long = nullptr) {
     ptam_ctx* ctx = t->ctx;
     const TmDev& d = t->d;
     const int n = d.n, n_fine = std::max(n, 1);
@@ -1014,10 +1021,15 @@ static int tm_wait_frame(ptam_tracker* t, hipStream_t st, const ptam_trackmap_op
         int rc = tm_wait_seq(t, st, seq, "the frame's result", &v);
         if (rc) return rc;
         if (!(v & POSE_CHAIN_LONG)) break;
+        if (went_long) *went_long = true;
         if (pass == 2) return PTAM_E_STATE;
         if (st != ctx->stream) {   // (a batch: the other frames' kernels still run there, and this frame goes on on its own queue)
             HIP_TRY(ptam_stream_wait(st));
             st = ctx->stream;
+        } else if (went_long) {
+            // (the report batch: the chain's fill kernel, queued behind the fine loop, reads this word to see that the frame is not
+            //  finished — it must have run before the word is cleared)
+            HIP_TRY(ptam_stream_wait(st));
         }
         t->mbox->seq = 0;   // (the stream is idle: nobody else writes the word until the next kernel does)
         if (fused) {
@@ -1072,7 +1084,8 @@ int ptam_tracker_create(ptam_ctx* ctx, int max_points, ptam_tracker** out) {
                  o_sr = take(cap * sizeof(ptam_subpix_result)), o_sf = take(cap * 4), o_st = take(cap * 4), o_ss = take(cap * 4), o_sv = take(cap * 16), o_rec = take(cap * TM_REC_F * 8), o_rect = take(cap * 8),
                  o_me = take(cap * sizeof(ptam_pose_meas)), o_en = take(cap * sizeof(ptam_projection)), o_mi = take(cap * 4),
                  o_ms = take(cap * 4), o_ou = take(cap * 4), o_ctl = take(sizeof(TmCtl)), o_pose = take(96),
-                 o_fs = take(cap * sizeof(TmFinder)), o_ser = take(cap * sizeof(long long));
+                 o_fs = take(cap * sizeof(TmFinder)), o_ser = take(cap * sizeof(long long)),
+                 o_dk = take(max_points > TR_DRAW_LDS_MAX ? cap * 32 : 0);
     // every failure past this point leaves through ONE path that releases what exists so far
     auto fail = [&](const char* what) {
         ptam_set_error("ptam_tracker_create: %s failed", what);
@@ -1115,6 +1128,7 @@ int ptam_tracker_create(ptam_ctx* ctx, int max_points, ptam_tracker** out) {
     d.pose = (double*)(b + o_pose);
     d.finder = (TmFinder*)(b + o_fs);   // (cleared with the block: no finder has made a template yet)
     t->serials = (long long*)(b + o_ser);
+    t->draw_keys = max_points > TR_DRAW_LDS_MAX ? (unsigned long long*)(b + o_dk) : nullptr;
     void* h = nullptr;
     if (hipHostMalloc(&h, sizeof(TmMailbox), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail("hipHostMalloc");
     t->mbox = (TmMailbox*)h;
@@ -1523,6 +1537,32 @@ int ptam_tracker_set_shuffle(ptam_tracker* t, const int32_t* shuffle_levels, con
     return PTAM_OK;
 }
 
+int ptam_tracker_draw_shuffles(ptam_tracker* t, uint64_t seed, uint64_t frame) {
+    ARG_TRY(t);
+    const int n = t->d.n;
+    if (n == 0) return PTAM_OK;
+    HIP_TRY(hipSetDevice(t->ctx->device));
+    // The draw runs on the tracker's own queue, where its next frame runs too (a batch joins the queues of its trackers first).  Only a
+    // frame that another tracker's queue still holds could read the arrays while they are written: every entry that tracks returns
+    // behind the frame's result, so this does not happen unless a caller broke that order
+    if (t->last_stream && t->last_stream != t->ctx->stream && t->mbox->seq != t->seq) HIP_TRY(ptam_stream_wait(t->last_stream));
+    t->d.perm_a = t->perm_dev_a;
+    t->d.perm_b = t->perm_dev_b;
+    return tr_draw_shuffles_on(t->ctx->stream, n, seed, frame, t->d.perm_a, t->d.perm_b, t->draw_keys);
+}
+
+int ptam_tracker_read_shuffle(ptam_tracker* t, int32_t* shuffle_levels, int32_t* shuffle_fine) {
+    ARG_TRY(t && shuffle_levels && shuffle_fine);
+    const int n = t->d.n;
+    if (n == 0) return PTAM_OK;
+    HIP_TRY(hipSetDevice(t->ctx->device));
+    // (wherever the orders live: the device arrays, or the host-mapped copy of ptam_tracker_set_shuffle)
+    HIP_TRY(hipMemcpyAsync(shuffle_levels, t->d.perm_a, (size_t)n * 4, hipMemcpyDefault, t->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(shuffle_fine, t->d.perm_b, (size_t)n * 4, hipMemcpyDefault, t->ctx->stream));
+    HIP_TRY(ptam_stream_wait(t->ctx->stream));
+    return PTAM_OK;
+}
+
 // d_new_frame (nullable): the current keyframe is made first — KeyFrame::MakeKeyFrame_Lite of this device-resident image, in
 // the same queue.  (Measured and dropped: the keyframe kernels on a second queue beside the PVS pass and the set choice, which
 // do not look at the image — the two cross-queue event waits cost more than the 13 us of overlap: 207-218 vs 193-200 us.)
@@ -1706,23 +1746,26 @@ static int tm_batch_join(int nb, ptam_tracker* const* ts) {
 // The argument block of a batch: a pinned copy the host fills and the device copy in the lead tracker's batch_dev, section by
 // section at the same offsets, every section 256-byte aligned:
 //   nb TmBatchItem | nb PoseBatchItem (coarse) | nb (fine) | n_est + n_rr SbiBatchRec | 3 x nb frame indices | n_rr SbiRelocRec
+//   | n_rep FrChainJob | n_draw TrDrawJob          (ptam_track_frames_report_batch: the reports' fill and the shuffles' draw)
 // and behind what is uploaded, on the device only, the recovering cameras' SSD tables (n_rr x rr_max_count) and gates.
 // The frame indices: [frames whose pose is made on the device | coarse stage by instantiation | fine stage by instantiation],
 // idx_stride ints apart.  ptam_track_map_frames_batch has n_est = n_rr = 0 and uploads the first three sections.
 extern "C++" {   // (member templates, inside this file's extern "C")
 struct TmBatchArgs {
-    enum Section { ITEMS, POSE_COARSE, POSE_FINE, SBI_REC, FRAME_IDX, RELOC_REC, RELOC_SSD, RELOC_GATE, N_SECTIONS };
+    enum Section { ITEMS, POSE_COARSE, POSE_FINE, SBI_REC, FRAME_IDX, RELOC_REC, REPORT_JOB, DRAW_JOB, RELOC_SSD, RELOC_GATE, N_SECTIONS };
+    enum { LAST_UPLOADED = DRAW_JOB };
     size_t off[N_SECTIONS + 1];
     size_t idx_stride;
     char* hb = nullptr;
     char* db = nullptr;
 
-    TmBatchArgs(int nb, int n_est, int n_rr, int rr_max_count) {
+    TmBatchArgs(int nb, int n_est, int n_rr, int rr_max_count, int n_rep = 0, int n_draw = 0) {
         auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
         const size_t b_idx = up((size_t)nb * 4);
         const size_t n = (size_t)nb, rr = (size_t)n_rr;
         const size_t bytes[N_SECTIONS] = {n * sizeof(TmBatchItem), n * sizeof(PoseBatchItem), n * sizeof(PoseBatchItem),
                                           (size_t)std::max(n_est + n_rr, 1) * sizeof(SbiBatchRec), 3 * b_idx, rr * sizeof(SbiRelocRec),
+                                          (size_t)n_rep * sizeof(FrChainJob), (size_t)n_draw * sizeof(TrDrawJob),
                                           rr * (size_t)rr_max_count * 8, rr * 4};
         idx_stride = b_idx / 4;
         off[0] = 0;
@@ -1737,7 +1780,7 @@ struct TmBatchArgs {
     // the pinned copy from the lead tracker's context, and its batch_dev grown on demand
     int reserve(ptam_tracker* lead) {
         void* pin;
-        const int rc = ctx_pinned(lead->ctx, end(RELOC_REC) + 64, &pin);
+        const int rc = ctx_pinned(lead->ctx, end((Section)LAST_UPLOADED) + 64, &pin);
         if (rc) return rc;
         if (lead->batch_cap < end(RELOC_GATE)) {
             HIP_TRY(ptam_stream_wait(lead->ctx->stream));
@@ -1880,10 +1923,12 @@ static int tm_enqueue_stage(ptam_ctx* ctx, int nb, const TmBatchArgs& a, const T
 // Wait + result, frame by frame.  long_path: a frame whose fine list outgrew the fused kernel says so in its sequence word
 // (POSE_CHAIN_LONG) and is finished on its own queue (tm_wait_frame; fused: the fine stage went out GROUPED); a batch that never sets
 // the bit waits for the word alone.
+// went_long (nullable): nb flags, set for the frames that were finished on their own queue.
 static int tm_collect(int nb, ptam_tracker* const* ts, hipStream_t st, const ptam_trackmap_opts& o, bool long_path, bool fused,
-                      ptam_trackmap_result* outs) {
+                      ptam_trackmap_result* outs, bool* went_long = nullptr) {
     for (int i = 0; i < nb; i++) {
-        const int rc = long_path ? tm_wait_frame(ts[i], st, o, ts[i]->seq, fused) : tm_wait_seq(ts[i], st, ts[i]->seq, "a frame's result");
+        const int rc = long_path ? tm_wait_frame(ts[i], st, o, ts[i]->seq, fused, went_long ? went_long + i : nullptr)
+                                 : tm_wait_seq(ts[i], st, ts[i]->seq, "a frame's result");
         if (rc) {
             const std::string e = ptam_last_error();
             ptam_set_error("frame %d of the batch: %s", i, e.c_str());
@@ -1947,6 +1992,17 @@ struct TfbRecover {
     double blur, max_score;
     ptam_reloc_result* reloc;         // out: the recovering frames' results, frame i's reloc_stride bytes behind frame i - 1's
     size_t reloc_stride;
+};
+// rp (nullable): ptam_track_frames_report_batch's extras — the frames' reports filled at the chain's end, the shuffles drawn at its
+// start.  The caller has checked the reports and made room for their marks.  Without rp nothing differs.
+struct TfbReport {
+    ptam_frame_report* const* reports;   // [nb], entries nullable
+    const int64_t* tags;                 // nullable
+    const uint64_t* seeds;               // nullable: no draw
+    const int64_t* frames;               // [nb]: the draw's frame index
+    ptam_track_report_info* infos;       // out, nullable
+    int too_small;                       // out: the first camera whose report was too small for its frame, or -1
+    bool enqueued;                       // out: the chain went out (the reports' records are being rewritten)
 };
 struct TfbPlan {
     int nb;
@@ -2107,7 +2163,39 @@ static int tfb_enqueue_sbi(const TfbPlan& p, ptam_ctx* ctx, const TmBatchArgs& a
 // The chain:   pyramid | PVS of the frames the host predicted  ->  tfb_enqueue_sbi  ->  set choice | corner compaction
 //   ->  search, pose (coarse)  ->  search, pose (fine)
 // *form: how the stages went out (tm_collect wants to know).  A non-zero return leaves the estimators stepped: the caller rolls back.
-static int tfb_enqueue(const TfbPlan& p, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, TmPoseForm* form) {
+// The report of frame i of the chain: where ptam_tracker_report_frames says the iteration set lies, where the fill's head words go
+static FrChainJob tfb_report_job(ptam_tracker* t, const ptam_frame_report* r, const int* d_gate) {
+    const TmDev& d = t->d;
+    FrChainJob c = {};
+    FrJob& j = c.job;
+    j.n_points = d.n;
+    j.serials = t->serials;
+    j.cap = d.cap;
+    j.n_slots = &d.ctl->n_slots;
+    j.n_meas = &d.ctl->n_meas;
+    j.outlier_by_slot = &d.ctl->outlier_by_slot;
+    j.list = d.list;
+    j.slot_found = d.slot_found;
+    j.slot_subpix = d.slot_subpix;
+    j.q = d.q;
+    j.tres = d.tres;
+    j.slot_v2 = d.slot_v2;
+    j.outlier = d.outlier;
+    j.mslot = d.mslot;
+    j.mark = r->mark;
+    j.rec = r->rec;
+    j.max_records = r->max_records;
+    c.gate = d_gate;
+    c.frame_word = &t->mbox_dev->seq;
+    c.head = t->mbox_dev->report_head;
+    c.head_seq = &t->mbox_dev->report_seq;
+    c.seq = t->seq;
+    return c;
+}
+static_assert(FR_FRAME_LONG == POSE_CHAIN_LONG, "the fill reads the frame's sequence word");
+
+static int tfb_enqueue(const TfbPlan& p, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, TmPoseForm* form,
+                       TfbReport* rp) {
     const int nb = p.nb;
     ptam_tracker* lead = ts[0];
     ptam_ctx* ctx = lead->ctx;
@@ -2116,14 +2204,45 @@ static int tfb_enqueue(const TfbPlan& p, ptam_tracker* const* ts, ptam_kf* const
     if (rc) return rc;
     for (int i : p.rr_of)   // (the recovering cameras' banks are read on this queue: their adds and pose uploads must be done)
         if (sbi_bank_ctx(p.rv->banks[i]) != ctx) HIP_TRY(ptam_stream_wait(sbi_bank_ctx(p.rv->banks[i])->stream));
-    TmBatchArgs a(nb, p.n_est, p.n_rr, p.rr_max_count);
+    int n_rep = 0, n_draw = 0, n_draw_max = 0;
+    for (int i = 0; rp && i < nb; i++) {
+        n_rep += rp->reports && rp->reports[i];
+        n_draw += rp->seeds && ts[i]->d.n > 0 && ts[i]->d.n <= TR_DRAW_LDS_MAX;
+    }
+    TmBatchArgs a(nb, p.n_est, p.n_rr, p.rr_max_count, n_rep, n_draw);
     TmBatchDims dm;
     int n_dev_pose = 0;
     rc = a.reserve(lead);
     if (!rc) rc = tfb_fill(p, a, ts, curs, d_frames, &dm, &n_dev_pose);
     if (rc) return rc;
     tm_commit_seqs(nb, ts, st);
-    HIP_TRY(hipMemcpyAsync(lead->batch_dev, a.hb, a.end(TmBatchArgs::RELOC_REC), hipMemcpyHostToDevice, st));
+    if (rp) {   // (host only)
+        rp->enqueued = true;
+        FrChainJob* h_rep = a.host<FrChainJob>(TmBatchArgs::REPORT_JOB);
+        TrDrawJob* h_draw = a.host<TrDrawJob>(TmBatchArgs::DRAW_JOB);
+        TmBatchItem* h_it = a.host<TmBatchItem>(TmBatchArgs::ITEMS);
+        for (int i = 0, kr = 0, kd = 0; i < nb; i++) {
+            if (rp->seeds && ts[i]->d.n > 0) {   // the frame reads the orders where the draw writes them
+                h_it[i].d.perm_a = ts[i]->perm_dev_a;
+                h_it[i].d.perm_b = ts[i]->perm_dev_b;
+                if (ts[i]->d.n <= TR_DRAW_LDS_MAX) {
+                    h_draw[kd++] = TrDrawJob{rp->seeds[i], (unsigned long long)rp->frames[i], ts[i]->perm_dev_a, ts[i]->perm_dev_b, ts[i]->d.n, 0};
+                    n_draw_max = std::max(n_draw_max, ts[i]->d.n);
+                }
+            }
+            if (rp->reports && rp->reports[i]) h_rep[kr++] = tfb_report_job(ts[i], rp->reports[i], h_it[i].gate);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(lead->batch_dev, a.hb, a.end((TmBatchArgs::Section)TmBatchArgs::LAST_UPLOADED), hipMemcpyHostToDevice, st));
+    if (rp && rp->seeds) {   // the frames' orders, in front of everything that could read them (the set choice)
+        rc = tr_draw_shuffles_batch_on(st, n_draw, n_draw_max, a.dev<TrDrawJob>(TmBatchArgs::DRAW_JOB));
+        for (int i = 0; i < nb && !rc; i++)
+            if (ts[i]->d.n > TR_DRAW_LDS_MAX)
+                rc = tr_draw_shuffles_on(st, ts[i]->d.n, rp->seeds[i], (uint64_t)rp->frames[i], ts[i]->perm_dev_a, ts[i]->perm_dev_b, ts[i]->draw_keys);
+        if (rc) return rc;
+        for (int i = 0; i < nb; i++)   // the draws are enqueued: from here on the trackers' orders are the drawn ones
+            if (ts[i]->d.n > 0) ts[i]->d.perm_a = ts[i]->perm_dev_a, ts[i]->d.perm_b = ts[i]->perm_dev_b;
+    }
     // ---- keyframe, the estimators' steps, PVS, set choice ----
     const TmBatchItem* d_it = a.dev<TmBatchItem>(TmBatchArgs::ITEMS);
     const KfLevels& L0 = curs[0]->L;
@@ -2137,6 +2256,55 @@ static int tfb_enqueue(const TfbPlan& p, ptam_tracker* const* ts, ptam_kf* const
     for (int sg = 0; sg < 2 && !rc; sg++) rc = tm_enqueue_stage(ctx, nb, a, dm, p.o, sg, *form);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
+    if (n_rep > 0) return fr_fill_chain_core(st, n_rep, a.dev<FrChainJob>(TmBatchArgs::REPORT_JOB));   // behind the fine pose loops
+    return PTAM_OK;
+}
+
+// The reports of a chain that has delivered every frame.  A frame that stayed in the chain: its head words arrive behind the frame's own
+// result, under the frame's sequence number — a wait on host-mapped words, as the frame's.  A frame that was finished on its own queue
+// (went_long): ptam_tracker_report_frames behind its passes.  A frame whose recovery failed: an empty report.
+static int tfb_collect_reports(const TfbPlan& p, ptam_tracker* const* ts, hipStream_t st, const bool* went_long, TfbReport* rp) {
+    rp->too_small = -1;
+    for (int i = 0; i < p.nb; i++) {
+        ptam_frame_report* r = rp->reports ? rp->reports[i] : nullptr;
+        ptam_track_report_info ri = {};
+        if (r) {
+            ptam_tracker* t = ts[i];
+            const int64_t tag = rp->tags ? rp->tags[i] : 0;
+            if (went_long[i]) {
+                const int rc = ptam_tracker_report_frames(1, &t, &r, &tag);
+                if (rc == PTAM_E_ARG) {   // (the arguments were checked before the chain: the report is too small)
+                    if (rp->too_small < 0) rp->too_small = i;
+                    ri.report_too_small = 1;
+                } else if (rc) return rc;
+            } else {
+                const unsigned long long seq = t->seq;
+                const int rc = ptam_wait_mapped(st, "a frame's report", [&] { return *(volatile unsigned long long*)&t->mbox->report_seq == seq; });
+                if (rc) return rc;
+                int h[FR_HEAD_WORDS];
+                std::memcpy(h, (const void*)t->mbox->report_head, sizeof h);
+                r->info = ptam_frame_report_info_t{};
+                const bool tracked = !p.recovering(i) || t->mbox->reloc.good;
+                if (h[FR_H_RECORDS] > r->max_records) {
+                    ri.report_too_small = 1;
+                    if (rp->too_small < 0) {
+                        rp->too_small = i;
+                        ptam_set_error("bad argument: ptam_track_frames_report_batch: frame %d found %d points, its report holds %d records", i,
+                                       h[FR_H_RECORDS], r->max_records);
+                    }
+                } else if (tracked) {
+                    r->info.map_id = t->map_id;
+                    r->info.tag = tag;
+                    r->info.n_records = h[FR_H_RECORDS];
+                    r->info.n_entries = h[FR_H_ENTRIES];
+                    r->info.n_outliers = h[FR_H_OUTLIERS];
+                }
+                ri.report_in_chain = 1;
+            }
+            ri.report = r->info;
+        }
+        if (rp->infos) rp->infos[i] = ri;
+    }
     return PTAM_OK;
 }
 
@@ -2182,15 +2350,21 @@ static void tfb_finish(const TfbPlan& p, ptam_tracker* const* ts, ptam_motion_mo
 
 static int tfb_impl(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_motion_model* models,
                     ptam_rotation_estimator* const* ests, const ptam_trackmap_opts* opts, ptam_trackmap_result* outs, ptam_track_frame_info* info,
-                    size_t info_stride, const TfbRecover* rv) {
+                    size_t info_stride, const TfbRecover* rv, TfbReport* rp = nullptr) {
     TfbPlan p;
     int rc = tfb_plan(nb, ts, models, ests, opts, rv, &p);
     if (rc) return rc;
     TmPoseForm form = TM_POSE_GROUPED;
-    rc = tfb_enqueue(p, ts, curs, d_frames, &form);
-    if (!rc) rc = tm_collect(nb, ts, ts[0]->ctx->stream, p.o, true, form == TM_POSE_GROUPED, outs);
+    std::unique_ptr<bool[]> went_long(rp ? new bool[(size_t)nb]() : nullptr);
+    rc = tfb_enqueue(p, ts, curs, d_frames, &form, rp);
+    if (!rc) rc = tm_collect(nb, ts, ts[0]->ctx->stream, p.o, true, form == TM_POSE_GROUPED, outs, went_long.get());
+    if (!rc && rp) rc = tfb_collect_reports(p, ts, ts[0]->ctx->stream, went_long.get(), rp);
     if (rc) {   // the estimators are where they were
         for (int i : p.est_of) sbi_estimator_rollback(ests[i]);
+        // a failure behind the first enqueue (the HIP runtime's): the reports' records may be half rewritten, so none of the call's
+        // reports keeps an info that describes them — all of them are empty, whichever camera the failure was met at
+        for (int i = 0; rp && rp->enqueued && rp->reports && i < nb; i++)
+            if (rp->reports[i]) rp->reports[i]->info = ptam_frame_report_info_t{};
         return rc;
     }
     tfb_finish(p, ts, models, outs, info, info_stride);
@@ -2241,12 +2415,10 @@ static void tfr_advance_state(ptam_track_state& s, ptam_track_frame_state_info& 
 
 // ---- Tracker::TrackFrame for a good map (src/Tracker.cc:127-176) for nb cameras: ptam_track_frames_batch's chain, in which a camera
 // that is lost runs the relocaliser instead of the prediction (tfb_impl with a TfbRecover); the state machine around it is host code ----
-int ptam_track_frames_recover_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_track_state* states,
-                                    ptam_rotation_estimator* const* ests, ptam_sbi_bank* const* banks, ptam_sbi* const* scratch,
-                                    const ptam_trackmap_opts* opts, const ptam_track_state_opts* state_opts, ptam_trackmap_result* outs,
-                                    ptam_track_frame_state_info* info) {
-    ARG_TRY(states && outs);
-    if (int rc = tm_batch_check(nb, ts, curs, d_frames)) return rc;
+// rp (nullable): the report batch's extras, checked
+static int tfr_impl(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_track_state* states,
+                    ptam_rotation_estimator* const* ests, ptam_sbi_bank* const* banks, ptam_sbi* const* scratch, const ptam_trackmap_opts* opts,
+                    const ptam_track_state_opts* state_opts, ptam_trackmap_result* outs, ptam_track_frame_state_info* info, TfbReport* rp) {
     ptam_track_state_opts so;
     ptam_track_state_opts_default(&so);
     if (state_opts) so = *state_opts;
@@ -2276,11 +2448,49 @@ int ptam_track_frames_recover_batch(int nb, ptam_tracker* const* ts, ptam_kf* co
     }
     const size_t stride = sizeof(ptam_track_frame_state_info);
     const TfbRecover rv = {rec.data(), banks, scratch, so.reloc_blur, so.reloc_max_score, &info[0].reloc, stride};
-    if (int rc = tfb_impl(nb, ts, curs, d_frames, models.data(), ests, opts, outs, &info[0].frame, stride, n_rr ? &rv : nullptr)) return rc;
+    if (int rc = tfb_impl(nb, ts, curs, d_frames, models.data(), ests, opts, outs, &info[0].frame, stride, n_rr ? &rv : nullptr, rp)) return rc;
     // ---- every frame has arrived: the states move ----
     for (int i = 0; i < nb; i++)
         tfr_advance_state(states[i], info[i], rec[(size_t)i] != 0, models[(size_t)i], banks ? banks[i] : nullptr, outs[i], so);
     return PTAM_OK;
+}
+
+int ptam_track_frames_recover_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_track_state* states,
+                                    ptam_rotation_estimator* const* ests, ptam_sbi_bank* const* banks, ptam_sbi* const* scratch,
+                                    const ptam_trackmap_opts* opts, const ptam_track_state_opts* state_opts, ptam_trackmap_result* outs,
+                                    ptam_track_frame_state_info* info) {
+    ARG_TRY(states && outs);
+    if (int rc = tm_batch_check(nb, ts, curs, d_frames)) return rc;
+    return tfr_impl(nb, ts, curs, d_frames, states, ests, banks, scratch, opts, state_opts, outs, info, nullptr);
+}
+
+// ---- the same frame with its report filled inside the chain and its two orders drawn there (framereport.hip, tracker_run.hip) ----
+int ptam_track_frames_report_batch(int nb, ptam_tracker* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, ptam_track_state* states,
+                                   ptam_rotation_estimator* const* ests, ptam_sbi_bank* const* banks, ptam_sbi* const* scratch,
+                                   const ptam_trackmap_opts* opts, const ptam_track_state_opts* state_opts, ptam_trackmap_result* outs,
+                                   ptam_track_frame_state_info* info, ptam_frame_report* const* reports, const int64_t* tags,
+                                   const uint64_t* shuffle_seeds, ptam_track_report_info* report_info) {
+    ARG_TRY(states && outs);
+    if (int rc = tm_batch_check(nb, ts, curs, d_frames)) return rc;
+    // ---- the reports' refusals: nothing is enqueued, and no report is touched, before all of them have passed
+    for (int i = 0; reports && i < nb; i++) {
+        if (!reports[i]) continue;
+        ARG_TRY(reports[i]->ctx->device == ts[i]->ctx->device);
+        for (int j = 0; j < i; j++) ARG_TRY(reports[j] != reports[i]);
+    }
+    for (int i = 0; reports && i < nb; i++)
+        if (reports[i] && !ts[i]->has_serials) {
+            ptam_set_error("ptam_track_frames_report_batch: the map of tracker %d did not come from a snapshot", i);
+            return PTAM_E_STATE;
+        }
+    for (int i = 0; reports && i < nb; i++)
+        if (reports[i])
+            if (int rc = fr_mark_room(reports[i], ts[i]->d.n)) return rc;
+    std::vector<int64_t> frames((size_t)nb);
+    for (int i = 0; i < nb; i++) frames[(size_t)i] = states[i].frame;
+    TfbReport rp = {reports, tags, shuffle_seeds, frames.data(), report_info, -1, false};
+    if (int rc = tfr_impl(nb, ts, curs, d_frames, states, ests, banks, scratch, opts, state_opts, outs, info, &rp)) return rc;
+    return rp.too_small < 0 ? PTAM_OK : PTAM_E_ARG;   // (every frame is delivered and every state has moved; that report is empty)
 }
 
 int ptam_tracker_read_reloc_ssd(ptam_tracker* lead, int row, int count, double* ssd_out) {

@@ -245,6 +245,11 @@ class KeyFrame:
         self.ctx._check(self.lib.kf_clone(self.ctx.h, self.h, C.byref(out)), "kf_clone")
         return KeyFrame(self.ctx, out)
 
+    def copy_from(self, src):
+        """ptam_kf_copy: this keyframe becomes what src.clone() would be, without an allocation (same image size) -> self"""
+        self.ctx._check(self.lib.kf_copy(self.ctx.h, src.h, self.h), "kf_copy")
+        return self
+
     def level(self, l):
         """-> dict(im, corners (n,2) int32 [x,y] raster order, rowlut)"""
         w, h, n = C.c_int(), C.c_int(), C.c_int()
@@ -659,6 +664,15 @@ MAP_POINT_SOURCE_DT = np.dtype([("src_kf", "<i4"), ("pad_", "<i4"), ("center_nc"
                                 ("one_down_nc", "<f8", (3,))])
 SCENE_DEPTH_DT = np.dtype([("depth_mean", "<f8"), ("depth_sigma", "<f8"), ("n_meas", "<i4"), ("pad_", "<i4")])
 assert MAP_POINT_SOURCE_DT.itemsize == C.sizeof(_abi.MapPointSource) == 80 and SCENE_DEPTH_DT.itemsize == C.sizeof(_abi.SceneDepth) == 24
+
+
+def shuffle_order(lib, seed, frame, which, n):
+    """order `which` (0: the level lists, 1: the chop of the fine set) of a frame's draw (ptam_shuffle_order_host, host only): (n,) int32"""
+    out = np.zeros(max(int(n), 1), np.int32)
+    rc = lib.shuffle_order_host(int(seed), int(frame), int(which), int(n), _ptr(out))
+    if rc < 0:
+        raise PtamError(f"shuffle_order_host failed ({rc}): {lib.last_error().decode()}")
+    return out[:max(int(n), 0)]
 
 
 def plane_samples(lib, seed, n_points, trials=100):
@@ -1485,6 +1499,18 @@ class Tracker:
         b = np.ascontiguousarray(shuffle_fine, dtype=np.int32)
         self.ctx._check(self.lib.tracker_set_shuffle(self.h, _ptr(a), _ptr(b)), "tracker_set_shuffle")
 
+    def draw_shuffles(self, seed, frame):
+        """ptam_tracker_draw_shuffles: the frame's two orders drawn on the device (shuffle_order is what they are)"""
+        self.ctx._check(self.lib.tracker_draw_shuffles(self.h, int(seed), int(frame)), "tracker_draw_shuffles")
+
+    def read_shuffle(self, n=None):
+        """ptam_tracker_read_shuffle: the two orders of the next frame, for a map of n points (default: the map set through this
+        object) -> (levels, fine), (n,) int32 each"""
+        n = self.n if n is None else int(n)
+        a, b = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        self.ctx._check(self.lib.tracker_read_shuffle(self.h, _ptr(a), _ptr(b)), "tracker_read_shuffle")
+        return a[:n], b[:n]
+
     def opts(self, **kw):
         o = np.zeros(1, dtype=TRACKMAP_OPTS_DT)
         self.lib.trackmap_opts_default(_ptr(o))
@@ -1627,6 +1653,21 @@ class Tracker:
         each) are updated in place -> (array of TRACKMAP_RESULT_DT, list of dict(branch, closest_kf, closest_kf_dist,
         need_new_keyframe, want_keyframe, pose_in, align, try_coarse, coarse_max, coarse_range, reloc)).  An error leaves states,
         estimators and banks as they were; check=False: -> the status of a refused call."""
+        return Tracker._recover_batch(trackers, kfs, d_frames, states, estimators, relocalisers, opts, state_opts, check, None)
+
+    @staticmethod
+    def track_frames_report_batch(trackers, kfs, d_frames, states, estimators=None, relocalisers=None, opts=None, state_opts=None,
+                                  reports=None, tags=None, shuffle_seeds=None, check=True):
+        """ptam_track_frames_report_batch: track_frames_recover_batch with every camera's frame report (reports[i]: a FrameReport or
+        None) filled inside the chain and, with shuffle_seeds, the frames' two orders drawn there (frame index: states[i].frame)
+        -> (results, infos, report infos: list of dict(map_id, tag, n_records, n_entries, n_outliers, report_in_chain, report_too_small), status).
+        status is PTAM_E_ARG (-1) with everything delivered when a report was too small for its frame (that report is empty); a
+        refused call raises, or with check=False returns its status alone."""
+        return Tracker._recover_batch(trackers, kfs, d_frames, states, estimators, relocalisers, opts, state_opts, check,
+                                      dict(reports=reports, tags=tags, seeds=shuffle_seeds))
+
+    @staticmethod
+    def _recover_batch(trackers, kfs, d_frames, states, estimators, relocalisers, opts, state_opts, check, extra):
         k = len(trackers)
         raw = lambda h: h.value if hasattr(h, "value") else int(h)
         arr = lambda xs, f: None if xs is None else (C.c_void_p * k)(*[None if x is None or f(x) is None else raw(f(x)) for x in xs])
@@ -1640,11 +1681,23 @@ class Tracker:
         res = np.zeros(k, dtype=TRACKMAP_RESULT_DT)
         inf = (_abi.TrackFrameStateInfo * k)()
         t0 = trackers[0]
-        rc = t0.lib.track_frames_recover_batch(k, trs, kf_, dis, ss, es, bs, sc, _ptr(opts) if opts is not None else None,
-                                               C.byref(state_opts) if state_opts is not None else None, _ptr(res), inf)
-        if rc < 0 and not check:
-            return rc
-        t0.ctx._check(rc, "track_frames_recover_batch")
+        head = (k, trs, kf_, dis, ss, es, bs, sc, _ptr(opts) if opts is not None else None,
+                C.byref(state_opts) if state_opts is not None else None, _ptr(res), inf)
+        if extra is None:
+            rc, name = t0.lib.track_frames_recover_batch(*head), "track_frames_recover_batch"
+        else:
+            name = "track_frames_report_batch"
+            rs = arr(extra["reports"], lambda r: r.h)
+            tg = None if extra["tags"] is None else (C.c_int64 * k)(*[int(x) for x in extra["tags"]])
+            sd = None if extra["seeds"] is None else (C.c_uint64 * k)(*[int(x) for x in extra["seeds"]])
+            rinf = (_abi.TrackReportInfo * k)()
+            rc = t0.lib.track_frames_report_batch(*head, rs, tg, sd, rinf)
+            if rc == -1 and any(r.report_too_small for r in rinf):   # PTAM_E_ARG with everything delivered (a refused call writes no info)
+                name = None
+        if rc < 0 and name is not None:
+            if not check:
+                return rc
+            t0.ctx._check(rc, name)
         for s_, new in zip(states, ss):
             C.memmove(C.byref(s_), C.byref(new), C.sizeof(_abi.TrackState))
         infos = [dict(branch=f.branch, closest_kf=f.closest_kf, closest_kf_dist=f.closest_kf_dist, need_new_keyframe=f.need_new_keyframe,
@@ -1652,7 +1705,11 @@ class Tracker:
                       try_coarse=f.frame.try_coarse, coarse_max=f.frame.coarse_max, coarse_range=f.frame.coarse_range,
                       reloc=dict(best=f.reloc.best, good=bool(f.reloc.good), best_ssd=f.reloc.best_ssd, pose=np.array(f.reloc.pose),
                                  align=_alignment(f.reloc.align))) for f in inf]
-        return res, infos
+        if extra is None:
+            return res, infos
+        rinfos = [dict(map_id=r.report.map_id, tag=r.report.tag, n_records=r.report.n_records, n_entries=r.report.n_entries,
+                       n_outliers=r.report.n_outliers, report_in_chain=r.report_in_chain, report_too_small=r.report_too_small) for r in rinf]
+        return res, infos, rinfos, rc
 
     def reloc_ssd(self, row, count):
         """ptam_tracker_read_reloc_ssd: the SSD table of the row-th recovering camera of the last recover batch this tracker led"""
@@ -1721,6 +1778,104 @@ class Tracker:
     def close(self):
         if getattr(self, "h", None):
             self.lib.tracker_destroy(self.h)
+            self.h = None
+
+
+class CameraTracker:
+    """ptam_camera_tracker: Tracker::TrackFrame for a good map (src/Tracker.cc:127-176) with its hand-over as one call.  Owns the
+    tracker, the current keyframe, the estimator, the relocaliser's bank, the state and the pools of reports and keyframe clones;
+    borrows `snapshot` (a MapSnapshot with its keyframe section enabled) and `mapmaker` (a MapMaker with a handle).  opts: keyword
+    fields of ptam_camera_tracker_opts (trackmap / state: dicts of their fields); the image size is the context's."""
+
+    def __init__(self, ctx, snapshot, mapmaker, **opts):
+        self.ctx, self.lib, self.snapshot, self.mapmaker = ctx, ctx.lib, snapshot, mapmaker
+        o = CameraTracker.opts(ctx, **opts)
+        self.h = C.c_void_p()
+        ctx._check(self.lib.camera_tracker_create(ctx.h, C.byref(o), snapshot.h, mapmaker._handle(), C.byref(self.h)), "camera_tracker_create")
+        self.o = o
+
+    @staticmethod
+    def opts(ctx, trackmap=None, state=None, **kw):
+        o = _abi.CameraTrackerOpts()
+        ctx._check(ctx.lib.camera_tracker_opts_default(C.byref(o)), "camera_tracker_opts_default")
+        o.width, o.height = ctx.size
+        for k, v in (trackmap or {}).items():
+            setattr(o.trackmap, k, v)
+        for k, v in (state or {}).items():
+            setattr(o.state, k, v)
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        return o
+
+    def reset(self, pose):
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        self.ctx._check(self.lib.camera_tracker_reset(self.h, _pd(pose)), "camera_tracker_reset")
+
+    def state(self):
+        s = _abi.TrackState()
+        self.ctx._check(self.lib.camera_tracker_state(self.h, C.byref(s)), "camera_tracker_state")
+        return s
+
+    def pool(self):
+        """-> (free reports, free keyframe clones)"""
+        a, b = C.c_int32(), C.c_int32()
+        self.ctx._check(self.lib.camera_tracker_pool(self.h, C.byref(a), C.byref(b)), "camera_tracker_pool")
+        return a.value, b.value
+
+    def tracker(self):
+        """the inner ptam_tracker as a Tracker that does not own it (iteration_set, read_shuffle, point_serials(count=...))"""
+        t = Tracker.__new__(Tracker)
+        t.ctx, t.lib, t.h, t._keep, t.n, t._serials = self.ctx, self.lib, C.c_void_p(self.lib.camera_tracker_tracker(self.h)), [], 0, True
+        return t
+
+    def current_keyframe(self):
+        return KeyFrame(self.ctx, C.c_void_p(self.lib.camera_tracker_current_keyframe(self.h)))     # (not owned: do not close)
+
+    def last_report(self):
+        """the last frame's FrameReport (not owned), or None"""
+        p = self.lib.camera_tracker_last_report(self.h)
+        if not p:
+            return None
+        r = FrameReport.__new__(FrameReport)
+        r.ctx, r.lib, r.h = self.ctx, self.lib, C.c_void_p(p)
+        return r
+
+    def TrackFrame(self, d_frame, check=True):
+        return CameraTracker.track_frames([self], [d_frame], check)[0] if check else CameraTracker.track_frames([self], [d_frame], check)
+
+    @staticmethod
+    def track_frames(handles, d_frames, check=True):
+        """ptam_camera_tracker_track_frames -> per camera dict(track (TRACKMAP_RESULT_DT scalar), branch, quality, lost_frames, frame,
+        report (info dict), map_take, keyframes_take, added_keyframe, noted_frame, report_in_chain, queue_size, tag, info (the
+        ptam_track_frame_state_info)); check=False: -> the status of a refused call"""
+        k = len(handles)
+        raw = lambda h: h.value if hasattr(h, "value") else int(h)
+        hs = (C.c_void_p * k)(*[raw(h.h) for h in handles])
+        dis = (C.c_void_p * k)(*[raw(d.p if isinstance(d, DevBuf) else d) for d in d_frames])
+        res = (_abi.CameraTrackResult * k)()
+        h0 = handles[0]
+        rc = h0.lib.camera_tracker_track_frames(k, hs, dis, res)
+        if rc < 0 and not check:
+            return rc
+        h0.ctx._check(rc, "camera_tracker_track_frames")
+        out = []
+        for h, r in zip(handles, res):
+            st = h.state()
+            if r.added_keyframe:      # (the Python MapMaker keeps what its queue names alive: the clone is this handle's)
+                h.mapmaker._queued.append(h)
+            track = np.frombuffer(bytes(r.track), dtype=TRACKMAP_RESULT_DT)[0]
+            rep = r.report
+            out.append(dict(track=track, branch=r.info.branch, quality=st.quality, lost_frames=st.lost_frames, frame=st.frame,
+                            report=dict(map_id=rep.map_id, tag=rep.tag, n_records=rep.n_records, n_entries=rep.n_entries, n_outliers=rep.n_outliers),
+                            map_take=_counts(r.map_take), keyframes_take=_counts(r.keyframes_take), added_keyframe=r.added_keyframe,
+                            noted_frame=r.noted_frame, report_in_chain=r.report_in_chain, queue_size=r.queue_size, tag=r.tag,
+                            info=_abi.TrackFrameStateInfo.from_buffer_copy(bytes(r.info))))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.camera_tracker_destroy(self.h)
             self.h = None
 
 
