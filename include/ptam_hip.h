@@ -404,6 +404,23 @@ int ptam_trails_start(ptam_trails* t, const ptam_kf* first, double min_shi_tomas
  * `nGoodTrails < 10 -> Reset()` (:329) — and *n_alive the length of the list afterwards.  Survivors keep their order.  The
  * current frame's level-0 data is then copied into the object as the previous frame (:430).  Two kernel launches. */
 int ptam_trails_advance(ptam_trails* t, const ptam_kf* current, int* n_good, int* n_alive);
+/* TrailTracking_Advance (src/Tracker.cc:376-432) behind MakeKeyFrame_Lite (src/KeyFrame.cc:17-59, as TrackFrame calls it, :87) for
+ * nb cameras — trails[i] with its keyframe current[i] — as ONE chain of launches on the queue of trails[0]'s context: the pyramid
+ * and the corners of d_frames[i] (a device-resident frame) into current[i], one launch of the search for all cameras' trails, one
+ * launch of the compaction and the kept frames.  d_frames == NULL or d_frames[i] == NULL: current[i] has been made already.  The
+ * counts come back through a host-mapped block of each object (allocated by ptam_trails_create), written behind the camera's last
+ * workgroup: one wait per camera on those words, no copy.  Camera i's list, patches, kept frame, n_good[i], n_alive[i] and
+ * current[i] are, to the bit, what ptam_make_keyframe_lite_dev + ptam_trails_advance leave, for every nb; an object without live
+ * trails is legal (0 / 0, its frame is kept).
+ * Conditions, those of ptam_track_map_frames_batch: nb in 1..4096; one device, one image size and one halfSample variant; every
+ * object in a DIFFERENT context; no object and no keyframe twice; each keyframe of its object's device and image size (a keyframe
+ * carries no context of its own).  The call first waits for the queues of the other objects' contexts.  PTAM_E_ARG for a broken
+ * condition or a null entry, PTAM_E_STATE for an object before its ptam_trails_start — both decided before anything is enqueued,
+ * with every object and keyframe as it was.  PTAM_E_HIP (the queue failed): no object is committed — each still names its list of
+ * before the call, though keyframes and kept frames may have been written; the next batch clears what the dead chain left in the
+ * objects' headers.  Start the trails again after such a failure. */
+int ptam_trails_advance_batch(int nb, ptam_trails* const* trails, ptam_kf* const* current, const uint8_t* const* d_frames,
+                              int32_t* n_good, int32_t* n_alive);
 /* mlTrails in list order.  cap < the live count: PTAM_E_ARG and nothing is written. */
 int ptam_trails_read(ptam_trails* t, ptam_trail* out, int cap, int* n);
 /* Trail::mPatch.mimOrigPatch of the live trails in list order: 81 bytes each (9 rows of 9); cap in trails */
@@ -1862,8 +1879,8 @@ int ptam_rmap_insert_keyframe_report(ptam_rmap*, ptam_refinder*, const ptam_kf* 
  *      keyframe queue (mvpKeyFrameQueue), the flags mbBundleConverged_Recent / _Full, mbBundleRunning and mbBundleAbortRequested,
  *      the reset request, and the tracked frames' reports that wait to be counted.
  *      THREADS.  ptam_mapmaker_step, _flags, _set_flags and _destroy belong to the mapmaker's thread, the thread of the map's
- *      context.  ptam_mapmaker_add_keyframe, _note_frame, _queue_size, _request_reset, _reset_done and _released may be called from
- *      the tracker's thread: they take the handle's mutex and touch no device.
+ *      context.  ptam_mapmaker_add_keyframe, _note_frame, _queue_size, _request_reset, _reset_done, _released, _request_init and
+ *      _init_poll may be called from the tracker's thread: they take the handle's mutex and touch no device.
  *      LIFETIMES.  A keyframe clone and a report handed over stay the caller's objects and must stay alive and unchanged until
  *      their tag comes back from ptam_mapmaker_released (a keyframe that has entered the map: as ptam_rmap_insert_keyframe_report
  *      says, for as long as the map names it).  Every tag handed over comes back exactly once: after the step that used it, or
@@ -1910,6 +1927,10 @@ enum {
     PTAM_MM_STAGE_BUNDLE_RECENT = 1, PTAM_MM_STAGE_REFIND_NEW = 2, PTAM_MM_STAGE_BUNDLE_ALL = 4, PTAM_MM_STAGE_REFIND_FAILURE = 8,
     PTAM_MM_STAGE_NOTES = 16, PTAM_MM_STAGE_BAD_POINTS = 32, PTAM_MM_STAGE_ADD_KEYFRAME = 64, PTAM_MM_STAGE_PUBLISH = 128
 };
+/* a step that made the first map (ptam_mapmaker_request_init): the status behind PTAM_MM_RESET (3), the stage bit behind
+ * PTAM_MM_STAGE_PUBLISH (256); and what ptam_mapmaker_init_poll says of a request (0, 1, 2) */
+enum { PTAM_MM_INIT = PTAM_MM_RESET + 1, PTAM_MM_STAGE_INIT = PTAM_MM_STAGE_PUBLISH << 1 };
+enum { PTAM_MM_INIT_NONE, PTAM_MM_INIT_PENDING, PTAM_MM_INIT_DONE };
 typedef struct {
     int32_t status, stages;
     ptam_map_ba_result recent;
@@ -1943,6 +1964,31 @@ int ptam_mapmaker_note_frame(ptam_mapmaker*, ptam_frame_report* report, int64_t 
 int ptam_mapmaker_queue_size(ptam_mapmaker*, int32_t* out);
 int ptam_mapmaker_request_reset(ptam_mapmaker*);   /* MapMaker::RequestReset (:116-120) */
 int ptam_mapmaker_reset_done(ptam_mapmaker*, int32_t* out);   /* MapMaker::ResetDone */
+/* MapMaker::InitFromStereo (src/MapMaker.cc:268-405) asked for by the tracker's thread (src/Tracker.cc:338-341).  The reference runs
+ * it on the tracker's thread while run() idles (:79); here the resident map belongs to the mapmaker's context, so the tracker hands
+ * over a REQUEST, as it hands over a keyframe: first / second (the caller's clones, under the lifetime rule of
+ * ptam_rmap_init_from_stereo: the map names them until the next reset), a copy of the matches (the reference's vMatches, built on the
+ * host at src/Tracker.cc:338-340; at most 16 bytes per trail), the options (nullable: ptam_rmap_init_opts_default) and a tag.
+ * Callable from the tracker's thread: it takes the handle's mutex and touches no device.
+ * The next ptam_mapmaker_step runs it in front of the :79 idle test, behind its first CHECK_RESET:
+ *   ptam_rmap_init_from_stereo(map, first, second, NULL, n_matches, matches, opts, stop, &result), stop a byte that
+ *   ptam_mapmaker_request_reset raises (mbResetRequested at :392).
+ *   PTAM_INIT_MAP_OK: the flags are what the loop of :387-394 leaves (both converged, nothing running); with a snapshot the step
+ *   publishes; the step ends with status PTAM_MM_INIT and PTAM_MM_STAGE_INIT (| PTAM_MM_STAGE_PUBLISH) in `stages`.
+ *   Any other outcome: the map is as ptam_rmap_init_from_stereo leaves it (empty), the flags as Reset() leaves them (:45-50);
+ *   PTAM_MM_STAGE_INIT is set and the step goes on to its idle test (PTAM_MM_IDLE), or to the reset that stopped it (PTAM_MM_RESET).
+ *   The tag comes back through ptam_mapmaker_released after the step that ran the request.
+ * A reset requested while a request is pending drops it: the tag is released by the step's reset, the outcome is
+ * PTAM_INIT_MAP_STOPPED.  A step without a request enqueues and returns what it did before this entry existed.
+ * PTAM_E_ARG: a null handle, keyframe or matches, n_matches < 4.  PTAM_E_STATE: a request is pending; the map has a keyframe (its
+ * count is a host word that only the mapmaker's thread writes, while it makes, grows or clears a map: a tracker asks while no map
+ * exists, when that thread idles at :79). */
+int ptam_mapmaker_request_init(ptam_mapmaker*, const ptam_kf* first, ptam_kf* second, int n_matches, const ptam_trail* matches,
+                               const ptam_rmap_init_opts* opts, int64_t tag);
+/* *state: PTAM_MM_INIT_NONE (no request yet), _PENDING, _DONE.  DONE is set after the step's publish, so a tracker that reads it
+ * finds the map in the snapshot; *out (nullable) is then the request's full result, readable until the next request.  Callable from
+ * the tracker's thread.  PTAM_E_ARG: a null handle or state. */
+int ptam_mapmaker_init_poll(ptam_mapmaker*, int32_t* state, ptam_rmap_init_result* out);
 int ptam_mapmaker_flags(ptam_mapmaker*, int32_t* converged_recent, int32_t* converged_full, int32_t* bundle_running);
 /* for tests, and for a host that resumes a map */
 int ptam_mapmaker_set_flags(ptam_mapmaker*, int converged_recent, int converged_full);
@@ -1957,7 +2003,8 @@ int ptam_mapmaker_step(ptam_mapmaker*, ptam_mapmaker_step_result*);
  *      ptam_map_snapshot the map is published into (keyframe section enabled) and the ptam_mapmaker (destroy the handle first).
  *      It lives on the tracker's thread, in `ctx`; of the mapmaker it uses only the entries that thread may call
  *      (ptam_mapmaker_released, _queue_size, _add_keyframe, _note_frame), so it touches neither the map's context nor its queue.
- *      TrackForInitialMap (:181) is not here: a session starts with ptam_rmap_init_from_stereo, a publish and _reset(tracker pose).
+ *      TrackForInitialMap (:181) is the session entry below (ptam_camera_tracker_enable_session, _session_frames); without it a
+ *      session starts with ptam_rmap_init_from_stereo, a publish and _reset(tracker pose).
  *      ptam_camera_tracker_track_frames, for nb handles in different contexts on one device (as ptam_track_frames_recover_batch asks)
  *      whose trackmap and state options are the same (PTAM_E_ARG otherwise: a chain takes them once):
  *        per camera   (a) ptam_mapmaker_released: a report whose tag came back is free again; a CLONE whose tag came back has been
@@ -2023,6 +2070,77 @@ ptam_frame_report* ptam_camera_tracker_last_report(ptam_camera_tracker*);
 int ptam_camera_tracker_pool(const ptam_camera_tracker*, int32_t* free_reports, int32_t* free_keyframes);
 int ptam_camera_tracker_track_frames(int nb, ptam_camera_tracker* const* handles, const uint8_t* const* d_frames,
                                      ptam_camera_track_result* results);
+
+/* ---- A session from the first frame: Tracker::TrackForInitialMap (src/Tracker.cc:181, :311-347) in the handle ---------------------------
+ *      ptam_camera_tracker_enable_session gives the handle the reference's mnInitialStage state machine: it allocates the trails
+ *      object (ptam_trails, max_initial_trails) and mFirstKF up front, so that a frame still allocates nothing, and puts the handle
+ *      in TRAIL_TRACKING_NOT_STARTED with the state of Tracker::Reset (:49-65) at the identity.  PTAM_E_STATE while a report or a
+ *      clone is out, or when the session is enabled already.  A handle WITHOUT it behaves as before: it tracks a map that exists,
+ *      "no map" is PTAM_E_STATE, in ptam_camera_tracker_track_frames and in the session entry alike.
+ *      ptam_camera_tracker_restart is the tracker's side of Tracker::Reset (:49-65): ptam_camera_tracker_reset at the identity plus
+ *      stage NOT_STARTED; ptam_mapmaker_request_reset stays the caller's, before, as for _reset.
+ *      ptam_camera_tracker_session_frames, for nb handles (pokes: nullable; pokes[i] != 0 is mbUserPressedSpacebar of camera i for
+ *      this frame).  Each handle takes the branch its stage selects (:311-347); mnFrame counts in every stage (:111) and is NOT reset
+ *      when the map is made:
+ *        NOT_STARTED  no poke: MakeKeyFrame_Lite (:92) of the frame, nothing else (:321-323).  Poke (:315-320): MakeKeyFrame_Lite,
+ *                     ptam_make_keyframe_rest (:354), ptam_kf_copy into mFirstKF (:355), ptam_trails_start (:356-369); STARTED.
+ *        STARTED      all such cameras of the call go through ONE ptam_trails_advance_batch (:328); one such camera alone takes
+ *                     ptam_make_keyframe_lite_dev + ptam_trails_advance, the same bits and the shorter path for one.  n_good < min_good_trails
+ *                     (:329): the tracker's side of Reset() — trail_reset = 1, NOT_STARTED; no mapmaker reset is requested: the map
+ *                     is empty in this stage by construction (a handle gets here only from NOT_STARTED, and leaves a map only
+ *                     through _restart or a failed initialisation, which leaves the map empty).  Otherwise, with a poke
+ *                     (:335-343): ptam_trails_read (vMatches, :338-340); two pooled clones receive mFirstKF and the current
+ *                     keyframe (ptam_kf_copy, one ptam_ctx_sync: the mapmaker reads them on its queue);
+ *                     ptam_mapmaker_request_init(first clone, second clone, the matches, opts.init, tag); COMPLETE, the request
+ *                     pending.  Fewer than two free clones: PTAM_E_STATE, decided at the call's entry for every STARTED handle that
+ *                     is poked, before anything is enqueued.
+ *        COMPLETE, request pending: ptam_mapmaker_init_poll.  PENDING: MakeKeyFrame_Lite and the frame count, no error (the
+ *                     reference's tracker is inside InitFromStereo meanwhile).  DONE and PTAM_INIT_MAP_OK: the motion model is
+ *                     reset at result.tracker_pose (mse3CamFromWorld, :341; zero velocity) with `frame` and
+ *                     `last_keyframe_dropped` kept, the estimator is reset, and THIS frame goes on to the tracking branch.  DONE
+ *                     and not OK: the handle does the tracker's side of Reset(), the two clones go back to the pool and
+ *                     init_status says why.  DEVIATION: the reference stays in COMPLETE without a map for ever (:127 never holds).
+ *        COMPLETE with a map: the body of ptam_camera_tracker_track_frames on that subset, the same code.
+ *      The trail-stage cameras run first, then the tracking subset; each subset obeys its batch call's conditions (different
+ *      contexts, one device, one image size; for the tracking subset one set of options).  A refusal of the tracking subset is
+ *      returned behind the trail-stage cameras' frames, which have been delivered (their session rows say so).
+ *      A camera whose map has just been made and whose tracking call is refused keeps its request pending and its state: the next
+ *      call reads the outcome again (init_done is reported with the frame that is delivered).
+ *      results[i] is zero for a camera that did not track.  tag of a request: opts.tag_base + the state's frame at entry.  Reset()
+ *      puts the frame count back to 0 (:63), so tags repeat from one session of a handle to the next.  The tag of a request that
+ *      made no map stays in the mapmaker's released list until a tracking call of this handle's mapmaker reads it; it then names
+ *      nothing here (the clones were freed when the outcome was read), or the clones of a later request that has made its map, which
+ *      are the map's by then: either reading is right. */
+enum { PTAM_TRAIL_TRACKING_NOT_STARTED, PTAM_TRAIL_TRACKING_STARTED, PTAM_TRAIL_TRACKING_COMPLETE };   /* mnInitialStage */
+typedef struct {
+    int32_t max_initial_trails;      /* 1000: Tracker.MaxInitialTrails (:360) */
+    int32_t min_good_trails;         /* 10 (:329) */
+    double min_shi_tomasi;           /* 70: the candidates' threshold (src/KeyFrame.cc:66-76) */
+    ptam_rmap_init_opts init;
+} ptam_camera_session_opts;
+typedef struct {
+    int32_t stage_before, stage_after;   /* PTAM_TRAIL_TRACKING_* */
+    int32_t poked;                       /* the poke was consumed (:317, :337, :52) */
+    int32_t n_trails;                    /* a start: the trails made */
+    int32_t n_good, n_alive;             /* an advance: nGoodTrails, the list's length afterwards */
+    int32_t trail_reset;                 /* :329-332 */
+    int32_t init_requested, init_done;   /* the request went out with this frame | its outcome was read with this frame */
+    int32_t init_status;                 /* PTAM_INIT_MAP_*, with init_done */
+    int32_t tracked, pad_;               /* the frame went through the tracking branch: results[i] is filled */
+    int64_t init_tag;                    /* with init_requested */
+} ptam_camera_session_result;
+/* 1000 / 10 / 70, ptam_rmap_init_opts_default.  PTAM_E_ARG: a null pointer */
+int ptam_camera_session_opts_default(ptam_camera_session_opts*);
+/* opts nullable: the defaults.  PTAM_E_ARG: a null handle, max_initial_trails < 1, min_good_trails < 0 */
+int ptam_camera_tracker_enable_session(ptam_camera_tracker*, const ptam_camera_session_opts* opts);
+int ptam_camera_tracker_restart(ptam_camera_tracker*);
+int ptam_camera_tracker_session_frames(int nb, ptam_camera_tracker* const* handles, const uint8_t* const* d_frames, const uint8_t* pokes,
+                                       ptam_camera_track_result* results, ptam_camera_session_result* session);
+/* the inner trails object (null without a session) and the last request's full result (PTAM_E_STATE before one was read), for drawing
+ * and tests; *stage (nullable): mnInitialStage, PTAM_TRAIL_TRACKING_COMPLETE without a session */
+ptam_trails* ptam_camera_tracker_trails(ptam_camera_tracker*);
+int ptam_camera_tracker_init_result(const ptam_camera_tracker*, ptam_rmap_init_result* out);
+int ptam_camera_tracker_stage(const ptam_camera_tracker*, int32_t* stage);
 
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,

@@ -323,6 +323,21 @@ public:
         return good;
     }
     int Alive() const { return alive_; }
+    // MakeKeyFrame_Lite of vdFrames[i] (null: vCurrent[i] is made already) and Advance for every camera as ONE chain on the first
+    // tracker's queue (ptam_trails_advance_batch): Contexts of their own on one device.  -> nGoodTrails per camera; Alive() each
+    static std::vector<int> AdvanceBatch(const std::vector<TrailTracker*>& vTrails, const std::vector<KeyFrame*>& vCurrent,
+                                         const std::vector<const uint8_t*>& vdFrames) {
+        const size_t n = vTrails.size();
+        if (n == 0 || vCurrent.size() != n || (!vdFrames.empty() && vdFrames.size() != n)) throw std::runtime_error("AdvanceBatch: sizes differ");
+        std::vector<ptam_trails*> t(n);
+        std::vector<ptam_kf*> k(n);
+        for (size_t i = 0; i < n; i++) t[i] = vTrails[i]->h_, k[i] = vCurrent[i]->handle();
+        std::vector<int32_t> good(n), alive(n);
+        check(ptam_trails_advance_batch((int)n, t.data(), k.data(), vdFrames.empty() ? nullptr : vdFrames.data(), good.data(), alive.data()),
+              "ptam_trails_advance_batch");
+        for (size_t i = 0; i < n; i++) vTrails[i]->alive_ = alive[i];
+        return std::vector<int>(good.begin(), good.end());
+    }
     std::vector<ptam_trail> Trails() {   // mlTrails: irInitialPos, irCurrentPos
         std::vector<ptam_trail> v((size_t)max_);
         int n = 0;
@@ -1598,6 +1613,19 @@ public:
         check(ptam_mapmaker_reset_done(h_, &n), "ptam_mapmaker_reset_done");
         return n != 0;
     }
+    // bool MapMaker::InitFromStereo(kF, kS, vMatches, se3TrackerPose)   src/MapMaker.cc:268-405, left for the next Step() by the tracker's
+    // thread: kFirst / kSecond are the caller's clones (the map names them until the next reset), pOpts nullable (the defaults)
+    void RequestInit(const KeyFrame& kFirst, KeyFrame& kSecond, const std::vector<ptam_trail>& vMatches, const ptam_rmap_init_opts* pOpts,
+                     int64_t nTag) {
+        check(ptam_mapmaker_request_init(h_, kFirst.handle(), kSecond.handle(), (int)vMatches.size(), vMatches.data(), pOpts, nTag),
+              "ptam_mapmaker_request_init");
+    }
+    // PTAM_MM_INIT_NONE / _PENDING / _DONE; DONE: *pResult (nullable) is the request's result, se3TrackerPose in tracker_pose
+    int InitPoll(ptam_rmap_init_result* pResult = nullptr) const {
+        int32_t s = 0;
+        check(ptam_mapmaker_init_poll(h_, &s, pResult), "ptam_mapmaker_init_poll");
+        return s;
+    }
     std::vector<int64_t> Released() {
         std::vector<int64_t> out, buf(64);
         for (int32_t n = 64; n == 64;) {
@@ -1629,8 +1657,9 @@ private:
 // ONE call that takes the published map and its keyframes, draws the frame's random orders, tracks or recovers, fills the frame's
 // report inside the chain and hands the frame to the MapMaker (AddKeyFrame with a pooled clone of the current keyframe, or NoteFrame).
 // It owns the MapTracker, the current KeyFrame, the rotation estimator, the relocaliser, the state and the pools; it borrows the
-// snapshot and the MapMaker, which must outlive it, and lives on the tracker's thread in its own Context.  TrackForInitialMap is
-// not here: start from ResidentMap::InitFromStereo, a Publish and Reset(the tracker's pose).
+// snapshot and the MapMaker, which must outlive it, and lives on the tracker's thread in its own Context.  TrackForInitialMap
+// (:181) comes with EnableSession() and PokeTracker(); without them start from ResidentMap::InitFromStereo, a Publish and Reset(the
+// tracker's pose).
 class Tracker {
 public:
     // the reference's options with the Context's image size
@@ -1648,9 +1677,16 @@ public:
     Tracker(const Tracker&) = delete;
     Tracker& operator=(const Tracker&) = delete;
     // void Tracker::TrackFrame(Image<byte> &imFrame, bool bDraw)   :86 — dFrame: the frame in device memory (stride == width)
+    // With EnableSession the frame goes through the session entry: TrackForInitialMap (:181, :311-347) until a map exists, then the
+    // same tracking branch; the poke of PokeTracker() is consumed by the frame.  Session(): what the last frame did.
     ptam_camera_track_result TrackFrame(const uint8_t* dFrame) {
         ptam_camera_track_result r;
-        check(ptam_camera_tracker_track_frames(1, &h_, &dFrame, &r), "ptam_camera_tracker_track_frames");
+        if (session_) {
+            const uint8_t poke = poke_ ? 1 : 0;
+            poke_ = false;
+            check(ptam_camera_tracker_session_frames(1, &h_, &dFrame, &poke, &r, &last_), "ptam_camera_tracker_session_frames");
+        } else
+            check(ptam_camera_tracker_track_frames(1, &h_, &dFrame, &r), "ptam_camera_tracker_track_frames");
         return r;
     }
     // several cameras in ONE chain: Contexts of their own on one device, the same trackmap / state options
@@ -1658,10 +1694,37 @@ public:
         const size_t n = vTrackers.size();
         if (n == 0 || vdFrames.size() != n) throw std::runtime_error("TrackFrames: sizes differ");
         std::vector<ptam_camera_tracker*> h(n);
-        for (size_t i = 0; i < n; i++) h[i] = vTrackers[i]->h_;
+        bool session = false;
+        for (size_t i = 0; i < n; i++) h[i] = vTrackers[i]->h_, session = session || vTrackers[i]->session_;
         std::vector<ptam_camera_track_result> r(n);
-        check(ptam_camera_tracker_track_frames((int)n, h.data(), vdFrames.data(), r.data()), "ptam_camera_tracker_track_frames");
+        if (!session) {
+            check(ptam_camera_tracker_track_frames((int)n, h.data(), vdFrames.data(), r.data()), "ptam_camera_tracker_track_frames");
+            return r;
+        }
+        std::vector<uint8_t> pokes(n);
+        std::vector<ptam_camera_session_result> s(n);
+        for (size_t i = 0; i < n; i++) pokes[i] = vTrackers[i]->poke_ ? 1 : 0, vTrackers[i]->poke_ = false;
+        check(ptam_camera_tracker_session_frames((int)n, h.data(), vdFrames.data(), pokes.data(), r.data(), s.data()),
+              "ptam_camera_tracker_session_frames");
+        for (size_t i = 0; i < n; i++) vTrackers[i]->last_ = s[i];
         return r;
+    }
+    // TrackForInitialMap in the handle (ptam_camera_tracker_enable_session): pOpts nullable (1000 trails, 10 good, 70, the init defaults)
+    void EnableSession(const ptam_camera_session_opts* pOpts = nullptr) {
+        check(ptam_camera_tracker_enable_session(h_, pOpts), "ptam_camera_tracker_enable_session");
+        session_ = true;
+    }
+    void PokeTracker() { poke_ = true; }   // the GUI command "PokeTracker" (src/Tracker.cc:283-287): mbUserPressedSpacebar for the next frame
+    // the tracker's side of Tracker::Reset (:49-65); MapMaker::RequestReset is the caller's, before
+    void Restart() {
+        check(ptam_camera_tracker_restart(h_), "ptam_camera_tracker_restart");
+        poke_ = false;
+    }
+    const ptam_camera_session_result& Session() const { return last_; }
+    int Stage() const {   // mnInitialStage: PTAM_TRAIL_TRACKING_*
+        int32_t s = 0;
+        check(ptam_camera_tracker_stage(h_, &s), "ptam_camera_tracker_stage");
+        return s;
     }
     TrackState State() const {
         TrackState s;
@@ -1691,6 +1754,8 @@ public:
 
 private:
     ptam_camera_tracker* h_ = nullptr;
+    bool session_ = false, poke_ = false;
+    ptam_camera_session_result last_{};
 };
 
 // class Bundle (include/Bundle.h:106-152)

@@ -339,9 +339,10 @@ class RmapNoteResult(C.Structure):
     _fields_ = [("n_records", C.c_int32), ("n_gone", C.c_int32)]
 
 
-MM_RAN, MM_IDLE, MM_RESET = range(3)
+MM_RAN, MM_IDLE, MM_RESET, MM_INIT = range(4)
 (MM_STAGE_BUNDLE_RECENT, MM_STAGE_REFIND_NEW, MM_STAGE_BUNDLE_ALL, MM_STAGE_REFIND_FAILURE, MM_STAGE_NOTES, MM_STAGE_BAD_POINTS,
- MM_STAGE_ADD_KEYFRAME, MM_STAGE_PUBLISH) = (1 << i for i in range(8))
+ MM_STAGE_ADD_KEYFRAME, MM_STAGE_PUBLISH, MM_STAGE_INIT) = (1 << i for i in range(9))
+MM_INIT_NONE, MM_INIT_PENDING, MM_INIT_DONE = range(3)   # ptam_mapmaker_init_poll
 
 
 class MapmakerOpts(C.Structure):
@@ -407,6 +408,21 @@ class CameraTrackerOpts(C.Structure):
                 ("trackmap", TrackmapOpts), ("state", TrackStateOpts), ("use_rotation_estimator", C.c_int32), ("keyframe_gap", C.c_int32),
                 ("rotation_blur", C.c_double), ("shuffle_seed", C.c_uint64), ("tag_base", C.c_int64), ("max_queue", C.c_int32),
                 ("reports", C.c_int32), ("keyframes", C.c_int32), ("pad_", C.c_int32)]
+
+
+TRAIL_TRACKING_NOT_STARTED, TRAIL_TRACKING_STARTED, TRAIL_TRACKING_COMPLETE = range(3)   # mnInitialStage
+
+
+class CameraSessionOpts(C.Structure):
+    """ptam_camera_session_opts"""
+    _fields_ = [("max_initial_trails", C.c_int32), ("min_good_trails", C.c_int32), ("min_shi_tomasi", C.c_double), ("init", RmapInitOpts)]
+
+
+class CameraSessionResult(C.Structure):
+    """ptam_camera_session_result"""
+    _fields_ = [("stage_before", C.c_int32), ("stage_after", C.c_int32), ("poked", C.c_int32), ("n_trails", C.c_int32),
+                ("n_good", C.c_int32), ("n_alive", C.c_int32), ("trail_reset", C.c_int32), ("init_requested", C.c_int32),
+                ("init_done", C.c_int32), ("init_status", C.c_int32), ("tracked", C.c_int32), ("pad_", C.c_int32), ("init_tag", C.c_int64)]
 
 
 class CameraTrackResult(C.Structure):
@@ -498,6 +514,7 @@ PROTOTYPES = {
     "trails_destroy": (_i, [_vp]),
     "trails_start": (_i, [_vp, _vp, _d, _i, C.POINTER(_i)]),
     "trails_advance": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "trails_advance_batch": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "trails_read": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "trails_read_patches": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "trails_matches": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
@@ -569,6 +586,13 @@ PROTOTYPES = {
     "camera_tracker_last_report": (_vp, [_vp]),
     "camera_tracker_pool": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "camera_tracker_track_frames": (_i, [_i, _vp, _vp, C.POINTER(CameraTrackResult)]),
+    "camera_session_opts_default": (_i, [C.POINTER(CameraSessionOpts)]),
+    "camera_tracker_enable_session": (_i, [_vp, C.POINTER(CameraSessionOpts)]),
+    "camera_tracker_restart": (_i, [_vp]),
+    "camera_tracker_session_frames": (_i, [_i, _vp, _vp, _vp, C.POINTER(CameraTrackResult), C.POINTER(CameraSessionResult)]),
+    "camera_tracker_trails": (_vp, [_vp]),
+    "camera_tracker_init_result": (_i, [_vp, C.POINTER(RmapInitResult)]),
+    "camera_tracker_stage": (_i, [_vp, C.POINTER(C.c_int32)]),
     "bench_track_batch": (_i, [_i, _vp, _vp, _vp, _pd, _vp, _vp, _vp, _i, _i, _pd]),
     "tracker_read_iteration_set": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "ba_bench_jacobian_rotating": (_i, [_vp, _i, _i, _pd]),
@@ -647,6 +671,8 @@ PROTOTYPES = {
     "mapmaker_queue_size": (_i, [_vp, C.POINTER(C.c_int32)]),
     "mapmaker_request_reset": (_i, [_vp]),
     "mapmaker_reset_done": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "mapmaker_request_init": (_i, [_vp, _vp, _vp, _i, _vp, C.POINTER(RmapInitOpts), C.c_int64]),
+    "mapmaker_init_poll": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(RmapInitResult)]),
     "mapmaker_flags": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mapmaker_set_flags": (_i, [_vp, _i, _i]),
     "mapmaker_released": (_i, [_vp, _i, _vp, C.POINTER(C.c_int32)]),

@@ -64,3 +64,21 @@ inline void mm_reset(MmFlags& f) {   // :45-50
     f.converged_full = f.converged_recent = true;
     f.abort_requested = false;
 }
+
+// ---- MapMaker::InitFromStereo (:268-405) run by the step for the tracker's thread (ptam_mapmaker_request_init)
+enum { MM_INIT_NONE = 0, MM_INIT_PENDING = 1, MM_INIT_DONE = 2 };   // PTAM_MM_INIT_* (ptam_hip.h)
+// one request at a time, and only for a map without a keyframe (the reference calls InitFromStereo while !mMap.IsGood())
+inline bool mm_init_request_allowed(int init_state, bool map_has_keyframe) { return init_state != MM_INIT_PENDING && !map_has_keyframe; }
+// the step runs a pending request in front of the :79 idle test; a request that a reset finds pending is dropped
+inline bool mm_want_init(int init_state) { return init_state == MM_INIT_PENDING; }
+// A map was made: the flags as the loop of :387-394 leaves them — BundleAdjustAll converged, which sets both (:905-910), and nothing
+// runs.  No map (`return false` at :286, :294 or :393; too few points): the caller's Reset(), :45-50.
+inline void mm_init_end(MmFlags& f, bool map_made) {
+    if (!map_made) {
+        mm_reset(f);
+        return;
+    }
+    f.converged_recent = f.converged_full = true;
+    f.bundle_running = false;
+    f.abort_requested = false;
+}

@@ -3,7 +3,9 @@
 // ptam_rmap_note_reports, ptam_rmap_handle_bad_points, ptam_rmap_insert_keyframe_report, ptam_rmap_publish, ptam_rmap_clear), and
 // every decision is a function of mapmaker_plan.h.  What is the handle's own: the keyframe queue, the pending reports and the
 // released tags under one mutex; the flags, written by the step and by AddKeyFrame under that mutex; the two bytes the device calls
-// poll from the host between their launches (the bundle's abort, the re-find's stop).
+// poll from the host between their launches (the bundle's abort, the re-find's stop).  The first map is made here too: the tracker's
+// thread leaves a request (ptam_mapmaker_request_init: the two keyframes and a copy of the matches), the step runs
+// ptam_rmap_init_from_stereo on the map's own thread and publishes, and the tracker's thread polls for the outcome.
 #include <atomic>
 #include <deque>
 #include <mutex>
@@ -26,6 +28,13 @@ struct MmNote {
     ptam_frame_report* report;
     int64_t tag;
 };
+struct MmInit {   // MapMaker::InitFromStereo's arguments, as the tracker's thread left them
+    const ptam_kf* first;
+    ptam_kf* second;
+    std::vector<ptam_trail> matches;
+    ptam_rmap_init_opts opts;
+    int64_t tag;
+};
 }   // namespace
 
 struct ptam_mapmaker {
@@ -42,11 +51,29 @@ struct ptam_mapmaker {
     volatile unsigned char abort_byte;       // mbBundleAbortRequested, as ptam_ba_compute polls it
     volatile unsigned char queue_nonempty;   // !mvpKeyFrameQueue.empty(), as the re-find polls it (:1053)
     std::atomic<bool> reset_requested, reset_done;
+    // the initialisation the tracker's thread asks for
+    int init_state;                          // MM_INIT_*
+    MmInit init;
+    ptam_rmap_init_result init_result;       // of the last request, readable until the next one
+    volatile unsigned char init_stop;        // mbResetRequested as InitFromStereo's last loop reads it (:392): raised by request_reset
 };
 
 static int mm_queue_size(ptam_mapmaker* mm) {
     std::lock_guard<std::mutex> g(mm->mu);
     return (int)mm->queue.size();
+}
+
+// a request ends (under the mutex): its tag goes home and the outcome becomes readable.  r == nullptr: it never ran — STOPPED
+static void mm_init_finish(ptam_mapmaker* mm, const ptam_rmap_init_result* r) {
+    if (r) mm->init_result = *r;
+    else {
+        std::memset(&mm->init_result, 0, sizeof mm->init_result);
+        mm->init_result.status = PTAM_INIT_MAP_STOPPED;
+        mm->init_result.n_matches = (int)mm->init.matches.size();
+    }
+    mm->released.push_back(mm->init.tag);
+    mm->init.matches.clear();
+    mm->init_state = MM_INIT_DONE;
 }
 
 // MapMaker::Reset (:37-51)
@@ -57,6 +84,8 @@ static int mm_do_reset(ptam_mapmaker* mm) {
     for (const MmNote& n : mm->notes) mm->released.push_back(n.tag);
     mm->queue.clear();
     mm->notes.clear();
+    if (mm_want_init(mm->init_state)) mm_init_finish(mm, nullptr);   // a pending request is dropped
+    mm->init_stop = 0;
     mm_reset(mm->flags);
     mm->abort_byte = mm->queue_nonempty = 0;
     mm->reset_done = true;
@@ -116,6 +145,9 @@ int ptam_mapmaker_create(ptam_rmap* map, ptam_refinder* finder, ptam_map_snapsho
     mm->abort_byte = mm->queue_nonempty = 0;
     mm->reset_requested = false;
     mm->reset_done = true;
+    mm->init_state = MM_INIT_NONE;
+    std::memset(&mm->init_result, 0, sizeof mm->init_result);
+    mm->init_stop = 0;
     *out = mm;
     return PTAM_OK;
 }
@@ -162,6 +194,38 @@ int ptam_mapmaker_request_reset(ptam_mapmaker* mm) {
     std::lock_guard<std::mutex> g(mm->mu);   // (against mm_do_reset's two stores: a request between them would be wiped)
     mm->reset_done = false;
     mm->reset_requested = true;
+    mm->init_stop = 1;
+    return PTAM_OK;
+}
+
+int ptam_mapmaker_request_init(ptam_mapmaker* mm, const ptam_kf* first, ptam_kf* second, int n_matches, const ptam_trail* matches,
+                               const ptam_rmap_init_opts* opts, int64_t tag) {
+    ARG_TRY(mm && first && second && matches && n_matches >= 4);
+    MmInit in;
+    in.first = first;
+    in.second = second;
+    in.matches.assign(matches, matches + n_matches);
+    in.tag = tag;
+    if (opts) in.opts = *opts;
+    else if (int rc = ptam_rmap_init_opts_default(&in.opts)) return rc;
+    std::lock_guard<std::mutex> g(mm->mu);
+    // (the map's keyframe count is a host word that only the mapmaker's thread writes, and only while it makes, grows or clears a map:
+    // a tracker asks here while no map exists, when that thread idles at :79)
+    const bool has_kf = __atomic_load_n(&mm->map->n[RM_N_KF], __ATOMIC_RELAXED) > 0;
+    if (!mm_init_request_allowed(mm->init_state, has_kf)) {
+        ptam_set_error("mapmaker_request_init: %s", mm->init_state == MM_INIT_PENDING ? "a request is pending" : "the map has a keyframe");
+        return PTAM_E_STATE;
+    }
+    mm->init = std::move(in);
+    mm->init_state = MM_INIT_PENDING;
+    return PTAM_OK;
+}
+
+int ptam_mapmaker_init_poll(ptam_mapmaker* mm, int32_t* state, ptam_rmap_init_result* out) {
+    ARG_TRY(mm && state);
+    std::lock_guard<std::mutex> g(mm->mu);
+    *state = mm->init_state;
+    if (out && mm->init_state == MM_INIT_DONE) *out = mm->init_result;
     return PTAM_OK;
 }
 
@@ -212,9 +276,38 @@ static int mm_step_stages(ptam_mapmaker* mm, ptam_mapmaker_step_result* res) {
         return finish(PTAM_MM_RESET);                 \
     }
     MM_CHECK_RESET;
+    bool want;
+    {
+        std::lock_guard<std::mutex> g(mm->mu);
+        want = mm_want_init(mm->init_state);
+    }
+    if (want) {   // InitFromStereo, which the reference runs on the tracker's thread while this loop idles (src/Tracker.cc:341)
+        // (mm->init is the step's until the state changes: a second request is refused while this one is pending)
+        ptam_rmap_init_result r;
+        std::memset(&r, 0, sizeof r);
+        int rc = ptam_rmap_init_from_stereo(mm->map, mm->init.first, mm->init.second, nullptr, (int)mm->init.matches.size(),
+                                            mm->init.matches.data(), &mm->init.opts, &mm->init_stop, &r);
+        if (rc) r.status = PTAM_INIT_MAP_STOPPED;   // (refused or failed: no map, the error is the step's)
+        const bool made = !rc && r.status == PTAM_INIT_MAP_OK;
+        res->stages |= PTAM_MM_STAGE_INIT;
+        {
+            std::lock_guard<std::mutex> g(mm->mu);
+            mm_init_end(mm->flags, made);
+        }
+        if (made && mm->snapshot) {
+            rc = ptam_rmap_publish(mm->map, mm->snapshot, &res->publish);
+            if (!rc) res->stages |= PTAM_MM_STAGE_PUBLISH;
+        }
+        {
+            std::lock_guard<std::mutex> g(mm->mu);
+            mm_init_finish(mm, &r);   // (DONE only now: a tracker that reads it takes a snapshot that holds the map)
+        }
+        if (rc) return rc;
+        if (made) return finish(PTAM_MM_INIT);
+        MM_CHECK_RESET;   // (STOPPED: the reset that stopped it)
+    }
     if (mm->map->n[RM_N_KF] == 0) return finish(PTAM_MM_IDLE);   // :79
     bool changed = false;   // what a tracker has to see: an accepted bundle, removed points, a new keyframe
-    bool want;
 
     MM_CHECK_RESET;   // :86-89
     {

@@ -38,6 +38,35 @@ inline int tp_decide(int branch, int quality, int frame, int last_dropped, int g
 // could the frame that is about to be tracked end in TP_ADD?  (asked before the chain: a keyframe clone must be free then)
 inline bool tp_may_add(int lost_frames, int frame_before, int last_dropped, int gap) { return lost_frames < 3 && frame_before + 1 - last_dropped > gap; }
 
+// ---- Tracker::TrackForInitialMap (src/Tracker.cc:311-347) and what TrackFrame does around it: the stage rule of a session ---------------
+// stage: mnInitialStage.  poke: mbUserPressedSpacebar.  n_good: TrailTracking_Advance's return value (looked at in STARTED only).
+// init_state / init_status: what ptam_mapmaker_init_poll says of the handle's request — MM_INIT_NONE when it has none out, which in
+// COMPLETE means that it tracks its map; init_status PTAM_INIT_MAP_* (0: a map was made).
+enum { TP_TRAILS_NOT_STARTED = 0, TP_TRAILS_STARTED = 1, TP_TRAILS_COMPLETE = 2 };
+enum {
+    TP_S_IDLE = 0,         // :321-323  nothing but MakeKeyFrame_Lite and the frame count
+    TP_S_START = 1,        // :315-320  TrailTracking_Start, stage STARTED
+    TP_S_RESET = 2,        // :329-332  too few good trails: Reset(), stage NOT_STARTED (the poke is cleared with it, :52)
+    TP_S_KEEP = 3,         // :344-345  the trails advanced, nothing else
+    TP_S_REQUEST = 4,      // :335-343  the matches and the two keyframes go to the mapmaker, stage COMPLETE
+    TP_S_WAIT = 5,         // the request has not been run yet: as IDLE (the reference's tracker is inside InitFromStereo meanwhile)
+    TP_S_BEGIN = 6,        // a map was made: the model at the tracker's pose (:341), then this frame is tracked
+    TP_S_INIT_FAILED = 7,  // no map was made: the tracker's side of Reset() (the reference stays in COMPLETE without a map for ever)
+    TP_S_TRACK = 8         // src/Tracker.cc:127-176
+};
+inline int tp_session_action(int stage, bool poke, int n_good, int min_good, int init_state, int init_status) {
+    if (stage == TP_TRAILS_NOT_STARTED) return poke ? TP_S_START : TP_S_IDLE;
+    if (stage == TP_TRAILS_STARTED) {
+        if (n_good < min_good) return TP_S_RESET;
+        return poke ? TP_S_REQUEST : TP_S_KEEP;
+    }
+    if (init_state == MM_INIT_NONE) return TP_S_TRACK;
+    if (init_state == MM_INIT_PENDING) return TP_S_WAIT;
+    return init_status == 0 ? TP_S_BEGIN : TP_S_INIT_FAILED;
+}
+// does the action consume the poke (mbUserPressedSpacebar = false at :317, :337 and in Reset(), :52)?
+inline bool tp_session_consumes_poke(int action, bool poke) { return poke && (action == TP_S_START || action == TP_S_REQUEST || action == TP_S_RESET); }
+
 // The reports and the keyframe clones of one camera, by index.  A report is FREE, HELD by the frame in flight, or OUT with the
 // mapmaker under a tag.  A clone is FREE, OUT under a tag, or IN_MAP: its tag came back, so the mapmaker's step has inserted it and
 // the map names it — it returns only with reset().  (A tag that a mapmaker reset dropped also comes back; the tracker's reset that
@@ -84,6 +113,11 @@ struct TpPool {
         for (size_t i = 0; i < clone_state.size(); i++)
             if (clone_state[i] == OUT && clone_tag[i] == tag) clone_state[i] = IN_MAP, n++;
         return n;
+    }
+    // the two keyframes of an initialisation request go out under its tag, without a report
+    void clones_out(int a, int b, int64_t tag) {
+        clone_state[(size_t)a] = clone_state[(size_t)b] = OUT;
+        clone_tag[(size_t)a] = clone_tag[(size_t)b] = tag;
     }
     void reset() {
         std::fill(report_state.begin(), report_state.end(), (int)FREE);

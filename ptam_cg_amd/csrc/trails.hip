@@ -17,6 +17,12 @@
 //                          per pass), nGoodTrails and the live count; the other workgroups copy the current frame into the object
 //                          (:430) — the searches of this frame have all ended, the launch is behind them on the queue.
 // A trail's patch never moves: the trail record carries its slot in the patch table.
+// Advance for nb cameras, each with its own object in its own context (ptam_trails_advance_batch) — ONE chain on the lead's queue:
+//   MakeKeyFrame_Lite per camera, then
+//   trails_search_batch_kernel   the search above with the camera as the grid's second dimension and a job table (TrailJob) in
+//                                device memory; a row past its camera's live count returns.
+//   trails_compact_batch_kernel  per camera the compaction and the kept frame as above; the counts also go to the object's
+//                                host-mapped block, and the call's sequence number behind them is what the host waits for.
 #include "common.h"
 
 #include <algorithm>
@@ -27,6 +33,7 @@
 #include "mapmaker_device.h"
 #include "homography.h"
 #include "trails_internal.h"
+#include "wait_mapped.h"
 
 #define TRAIL_MAX_SSD 100000   // MiniPatch::FindPatch's default nMaxSSD (include/ImageProcess.h)
 #define TRAIL_RANGE 10         // src/Tracker.cc:400
@@ -45,7 +52,27 @@ struct PrevFrame {   // mPreviousFrameKF.aLevels[0]: im, vCorners, vCornerRowLUT
     int corner_cap;
 };
 enum { TRAIL_UNFOUND = 0, TRAIL_UNMARRIED = 1, TRAIL_KEPT = 2 };
-enum { HDR_GOOD = 0, HDR_LIVE = 1 };
+enum { HDR_GOOD = 0, HDR_LIVE = 1, HDR_ARRIVED = 4 };   // (HDR_ARRIVED: workgroups of a batch's compaction that have ended; words 8.. are the kept frame's)
+
+struct TrailDone {   // host-mapped, one per object: what a batch's compaction leaves for the host
+    int good, live;
+    unsigned long long seq;
+};
+struct TrailJob {    // one camera of ptam_trails_advance_batch: the arguments of the two per-camera kernels
+    KfLevels C;
+    PrevFrame P;
+    int n, pad_;
+    const ptam_trail* tin;
+    const int* sin;
+    const uint8_t* patches;
+    int* status;
+    ptam_int2* newpos;
+    ptam_trail* tout;
+    int* sout;
+    int* hdr;
+    TrailDone* done;
+    unsigned long long seq;
+};
 
 }   // namespace
 
@@ -62,6 +89,13 @@ struct ptam_trails {
     ptam_int2* newpos;
     int* hdr;
     void* out;                  // read-back staging on the device: the match table / the patches in list order
+    // ptam_trails_advance_batch
+    TrailDone* done;            // host-mapped and coherent; done_dev: the same block as the device sees it
+    TrailDone* done_dev;
+    unsigned long long seq;     // the last batch call's sequence number
+    void* batch_dev;            // the job table of the batches this object leads: grown on demand
+    size_t batch_cap;
+    int in_flight;              // a batch was enqueued for this object and has not been committed: it died on the way (see the batch)
 };
 
 __device__ __forceinline__ void keep_frame(const KfLevels& C, const PrevFrame& P, int w, int h, int part, int nparts) {
@@ -242,6 +276,97 @@ __global__ void __launch_bounds__(1024) trails_compact_kernel(KfLevels C, PrevFr
     if (tid == 0) {
         hdr[HDR_GOOD] = good;
         hdr[HDR_LIVE] = base;
+    }
+}
+
+// ---- the two launches for the cameras of a batch (ptam_trails_advance_batch): blockIdx.y = camera, its arguments in jobs[] ------
+__global__ void __launch_bounds__(256) trails_search_batch_kernel(const TrailJob* __restrict__ jobs, int w, int h) {
+    __shared__ unsigned lds[4][2][TRAIL_PATCH_WORDS];
+    const TrailJob& j = jobs[blockIdx.y];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int t = blockIdx.x * 4 + wv;
+    if (t >= j.n) return;   // (the grid is shaped by the batch's longest list)
+    const KfLevels& C = j.C;
+    const PrevFrame& P = j.P;
+    const ptam_trail tr = j.tin[t];
+    unsigned stt = wave_load_minipatch(j.patches + (size_t)j.sin[t] * TRAIL_PATCH_BYTES, TRAIL_PATCH, lds[wv][0], lane);
+    int ex, ey, st = TRAIL_UNFOUND;
+    const bool found = wave_find_minipatch(C.im[0], w, h, C.corners[0], C.rowlut[0], C.ncorners[0], lds[wv][0], stt, tr.current_x, tr.current_y,
+                                           lane, ex, ey);
+    if (found) {
+        st = TRAIL_UNMARRIED;
+        stt = wave_load_minipatch(C.im[0] + (size_t)(ey - 4) * w + (ex - 4), (size_t)w, lds[wv][1], lane);
+        int bx, by;
+        const bool back = wave_find_minipatch(P.im, w, h, P.corners, P.rowlut, *P.ncorners, lds[wv][1], stt, ex, ey, lane, bx, by);
+        const int dx = bx - tr.current_x, dy = by - tr.current_y;
+        if (back && dx * dx + dy * dy <= 2) st = TRAIL_KEPT;
+    }
+    if (lane == 0) {
+        j.status[t] = st;
+        ptam_int2 e;
+        e.x = found ? ex : tr.current_x;
+        e.y = found ? ey : tr.current_y;
+        j.newpos[t] = e;
+    }
+}
+
+// Workgroup 0 of a camera compacts and leaves the counts in the device header and in the object's host-mapped block; the others keep
+// the frame.  The sequence word goes out in fr_fill_chain_kernel's order — fence, barrier, system fence, the word — by the camera's
+// LAST workgroup to end (a count in the header), so that a host which has seen the word may use the kept frame on another queue.
+__global__ void __launch_bounds__(1024) trails_compact_batch_kernel(const TrailJob* __restrict__ jobs, int w, int h) {
+    const TrailJob& j = jobs[blockIdx.y];
+    const int tid = threadIdx.x;
+    if (blockIdx.x > 0) {
+        keep_frame(j.C, j.P, w, h, blockIdx.x - 1, gridDim.x - 1);
+    } else {
+        __shared__ int wk[16], wg[16];
+        const int lane = tid & 63, wid = tid >> 6, n = j.n;
+        const unsigned long long lt = (1ull << lane) - 1ull;
+        int base = 0, good = 0;
+        for (int start = 0; start < n; start += 1024) {
+            const int i = start + tid;
+            const int st = i < n ? j.status[i] : TRAIL_UNFOUND;
+            const bool keep = st == TRAIL_KEPT;
+            const unsigned long long mk = __ballot(keep), mg = __ballot(st != TRAIL_UNFOUND);
+            if (lane == 0) {
+                wk[wid] = __popcll(mk);
+                wg[wid] = __popcll(mg);
+            }
+            __syncthreads();
+            int pk = 0, tk = 0;
+            for (int v = 0; v < 16; v++) {
+                if (v < wid) pk += wk[v];
+                tk += wk[v];
+                good += wg[v];
+            }
+            if (keep) {
+                ptam_trail t = j.tin[i];
+                const ptam_int2 e = j.newpos[i];
+                t.current_x = e.x;
+                t.current_y = e.y;
+                const int o = base + pk + __popcll(mk & lt);
+                j.tout[o] = t;
+                j.sout[o] = j.sin[i];
+            }
+            base += tk;
+            __syncthreads();   // (wk / wg are rewritten by the next pass)
+        }
+        if (tid == 0) {
+            j.hdr[HDR_GOOD] = good;
+            j.hdr[HDR_LIVE] = base;
+            j.done->good = good;
+            j.done->live = base;
+        }
+    }
+    __threadfence();   // (the list and the kept frame: the object's next call may read them on its own queue)
+    __syncthreads();
+    if (tid == 0) {
+        __threadfence_system();
+        if (atomicAdd(&j.hdr[HDR_ARRIVED], 1) == (int)gridDim.x - 1) {
+            j.hdr[HDR_ARRIVED] = 0;   // (for the next batch; nobody else of this launch looks at it any more)
+            __threadfence_system();
+            *(volatile unsigned long long*)&j.done->seq = j.seq;
+        }
     }
 }
 
@@ -430,11 +555,23 @@ int ptam_trails_create(ptam_ctx* ctx, int max_trails, ptam_trails** out) {
     homog_sizes(max_trails, 300, &homog_scratch, &homog_pinned);
     int rc = ctx_pinned(ctx, std::max(256 + b_out + n * sizeof(ptam_trail), homog_pinned), &hp);
     if (!rc) rc = ctx_scratch(ctx, homog_scratch, &hs);
+    // the block a batch's compaction reports into, and the header's arrival count at zero
+    void *hd = nullptr, *dd = nullptr;
+    if (!rc && (hipHostMalloc(&hd, sizeof(TrailDone), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+                hipHostGetDevicePointer(&dd, hd, 0) != hipSuccess || hipMemsetAsync(t->hdr, 0, b_hdr, ctx->stream) != hipSuccess ||
+                ptam_stream_wait(ctx->stream) != hipSuccess)) {   // (on the object's own queue, and done before anyone uses the object)
+        ptam_set_error("ptam_trails_create: no host-mapped block: %s", hipGetErrorString(hipGetLastError()));
+        rc = PTAM_E_HIP;
+    }
     if (rc) {
+        if (hd) hipHostFree(hd);
         hipFree(t->base);
         delete t;
         return rc;
     }
+    std::memset(hd, 0, sizeof(TrailDone));
+    t->done = (TrailDone*)hd;
+    t->done_dev = (TrailDone*)dd;
     *out = t;
     return PTAM_OK;
 }
@@ -444,6 +581,8 @@ int ptam_trails_destroy(ptam_trails* t) {
     hipSetDevice(t->ctx->device);
     hipDeviceSynchronize();
     hipFree(t->base);
+    if (t->batch_dev) hipFree(t->batch_dev);
+    hipHostFree(t->done);
     delete t;
     return PTAM_OK;
 }
@@ -512,6 +651,101 @@ int ptam_trails_advance(ptam_trails* t, const ptam_kf* current, int* n_good, int
     t->n_live = ((const int*)hp)[HDR_LIVE];
     *n_good = ((const int*)hp)[HDR_GOOD];
     *n_alive = t->n_live;
+    return PTAM_OK;
+}
+
+// What ptam_trails_advance_batch refuses before it looks further (no HIP call, nothing written): the conditions of the tracker's batch
+// calls — one device, one image geometry and halfSample variant, no object, keyframe or context twice — and a start on every object.
+static int trails_batch_check(int nb, ptam_trails* const* ts, ptam_kf* const* curs, const int32_t* n_good, const int32_t* n_alive) {
+    ARG_TRY(nb >= 1 && nb <= 4096 && ts && curs && n_good && n_alive);
+    for (int i = 0; i < nb; i++) ARG_TRY(ts[i] && curs[i]);
+    const ptam_ctx* ctx = ts[0]->ctx;
+    const KfLevels& L0 = curs[0]->L;
+    for (int i = 0; i < nb; i++) {
+        ARG_TRY(ts[i]->ctx->device == ctx->device && ts[i]->ctx->halfsample == ctx->halfsample);
+        ARG_TRY(ts[i]->w == ts[0]->w && ts[i]->h == ts[0]->h);
+        if (int rc = trails_check_kf(ts[i], curs[i])) return rc;
+        ARG_TRY(curs[i]->n_blocks == curs[0]->n_blocks);
+        for (int l = 0; l < PTAM_LEVELS; l++) ARG_TRY(curs[i]->L.w[l] == L0.w[l] && curs[i]->L.h[l] == L0.h[l]);
+        for (int j = 0; j < i; j++) ARG_TRY(ts[j] != ts[i] && curs[j] != curs[i] && ts[j]->ctx != ts[i]->ctx);
+    }
+    for (int i = 0; i < nb; i++)
+        if (int rc = trails_need_start(ts[i], "trails_advance_batch")) return rc;
+    return PTAM_OK;
+}
+
+int ptam_trails_advance_batch(int nb, ptam_trails* const* ts, ptam_kf* const* curs, const uint8_t* const* d_frames, int32_t* n_good,
+                              int32_t* n_alive) {
+    int rc = trails_batch_check(nb, ts, curs, n_good, n_alive);
+    if (rc) return rc;
+    ptam_trails* lead = ts[0];
+    ptam_ctx* ctx = lead->ctx;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the chain runs on the lead's queue: whatever the other objects' own queues still hold (a start, a keyframe) must be done
+    for (int i = 1; i < nb; i++) HIP_TRY(ptam_stream_wait(ts[i]->ctx->stream));
+    const size_t bytes = (size_t)nb * sizeof(TrailJob);
+    void* pin;
+    rc = ctx_pinned(ctx, bytes, &pin);
+    if (rc) return rc;
+    if (lead->batch_cap < bytes) {
+        HIP_TRY(ptam_stream_wait(st));
+        if (lead->batch_dev) HIP_TRY(hipFree(lead->batch_dev));
+        lead->batch_dev = nullptr;
+        lead->batch_cap = 0;
+        HIP_TRY(hipMalloc(&lead->batch_dev, bytes * 2));
+        lead->batch_cap = bytes * 2;
+    }
+    TrailJob* hj = (TrailJob*)pin;
+    const TrailJob* dj = (const TrailJob*)lead->batch_dev;
+    int n_max = 0;
+    for (int i = 0; i < nb; i++) {
+        ptam_trails* t = ts[i];
+        const int a = t->cur, b = 1 - t->cur;
+        TrailJob& j = hj[i];
+        std::memset(&j, 0, sizeof j);
+        j.C = curs[i]->L;
+        j.P = t->prev;
+        j.n = t->n_live;
+        j.tin = t->trails[a];
+        j.sin = t->slot[a];
+        j.patches = t->patches;
+        j.status = t->status;
+        j.newpos = t->newpos;
+        j.tout = t->trails[b];
+        j.sout = t->slot[b];
+        j.hdr = t->hdr;
+        j.done = t->done_dev;
+        j.seq = t->seq + 1;
+        n_max = std::max(n_max, t->n_live);
+    }
+    HIP_TRY(hipMemcpyAsync(lead->batch_dev, hj, bytes, hipMemcpyHostToDevice, st));
+    for (int i = 0; i < nb; i++) {
+        // an object whose last batch never came back (PTAM_E_HIP below): its arrival count may stand anywhere
+        if (ts[i]->in_flight) HIP_TRY(hipMemsetAsync(ts[i]->hdr + HDR_ARRIVED, 0, sizeof(int), st));
+        if (d_frames && d_frames[i]) {   // (a failure here leaves the keyframes before it made and every trails object as it was)
+            rc = kf_make_lite_on(ts[i]->ctx, curs[i], d_frames[i], st);
+            if (rc) return rc;
+        }
+    }
+    for (int i = 0; i < nb; i++) ts[i]->seq++, ts[i]->in_flight = 1;   // (from here on the device may write the word)
+    if (n_max > 0) hipLaunchKernelGGL(trails_search_batch_kernel, dim3((n_max + 3) / 4, nb), dim3(256), 0, st, dj, lead->w, lead->h);
+    hipLaunchKernelGGL(trails_compact_batch_kernel, dim3(1 + KEEP_BLOCKS, nb), dim3(1024), 0, st, dj, lead->w, lead->h);
+    HIP_TRY(hipGetLastError());
+    for (int i = 0; i < nb; i++) {
+        const volatile unsigned long long* word = &ts[i]->done->seq;
+        const unsigned long long seq = ts[i]->seq;
+        rc = ptam_wait_mapped(st, "a camera's trail counts", [&] { return *word == seq; });
+        if (rc) return rc;   // (the queue died: no object is committed, each keeps its list of before; the next batch clears the counts)
+    }
+    for (int i = 0; i < nb; i++) {   // every camera has arrived: the lists change hands
+        ptam_trails* t = ts[i];
+        t->cur = 1 - t->cur;
+        t->in_flight = 0;
+        t->n_live = t->done->live;
+        n_good[i] = t->done->good;
+        n_alive[i] = t->done->live;
+    }
     return PTAM_OK;
 }
 
@@ -632,6 +866,8 @@ void trails_preload_kernels() {
     ptam_preload((const void*)trails_keep_kernel);
     ptam_preload((const void*)trails_search_kernel);
     ptam_preload((const void*)trails_compact_kernel);
+    ptam_preload((const void*)trails_search_batch_kernel);
+    ptam_preload((const void*)trails_compact_batch_kernel);
     ptam_preload((const void*)trails_matches_kernel);
     ptam_preload((const void*)trails_gather_patches_kernel);
     ptam_preload((const void*)init_points_kernel);

@@ -418,6 +418,24 @@ class MapMaker:
         self.ctx._check(self.lib.mapmaker_reset_done(self._handle(), C.byref(n)), "mapmaker_reset_done")
         return bool(n.value)
 
+    def RequestInit(self, first, second, matches, opts=None, tag=0):
+        """ptam_mapmaker_request_init: MapMaker::InitFromStereo (src/MapMaker.cc:268-405) of the clones first / second and the
+        matches (TRAIL_DT) left for the next Step; opts from ResidentMap.init_opts() or None; callable from the tracker's thread"""
+        m = np.ascontiguousarray(matches, dtype=TRAIL_DT)
+        self.ctx._check(self.lib.mapmaker_request_init(self._handle(), first.h, second.h, len(m), _ptr(m),
+                                                       C.byref(opts) if opts is not None else None, int(tag)), "mapmaker_request_init")
+        self._held[int(tag)] = (first, second)
+        self._init = (first, second, opts)
+
+    def InitPoll(self):
+        """ptam_mapmaker_init_poll -> (state, result): state one of _abi.MM_INIT_NONE / _PENDING / _DONE, result the dict of
+        ResidentMap.InitFromStereo once DONE (None before)"""
+        st, res = C.c_int32(), _abi.RmapInitResult()
+        self.ctx._check(self.lib.mapmaker_init_poll(self._handle(), C.byref(st), C.byref(res)), "mapmaker_init_poll")
+        if st.value != _abi.MM_INIT_DONE:
+            return st.value, None
+        return st.value, init_result(res, self._init[2] if getattr(self, "_init", None) else None)
+
     def flags(self):
         r, f, b = C.c_int32(), C.c_int32(), C.c_int32()
         self.ctx._check(self.lib.mapmaker_flags(self._handle(), C.byref(r), C.byref(f), C.byref(b)), "mapmaker_flags")
@@ -457,6 +475,11 @@ class MapMaker:
         d["publish"] = {k: getattr(res.publish, k) for k in ("generation", "map_id", "n_points", "n_kf", "grew")}
         if res.status == _abi.MM_RESET:
             self._queued = []
+        if res.status == _abi.MM_INIT:     # (a CameraTracker's request names clones of its own pool: nothing to keep alive here)
+            self.rmap._kfs = list(self._init[:2]) if getattr(self, "_init", None) else []
+            self._init = None
+        elif res.stages & _abi.MM_STAGE_INIT:
+            self.rmap._kfs = []
         if res.stages & _abi.MM_STAGE_ADD_KEYFRAME:
             self.rmap._kfs.append(self._queued.pop(0))
         if self.snapshot is not None and res.stages & _abi.MM_STAGE_PUBLISH:
@@ -535,6 +558,23 @@ class Trails:
         g, a = C.c_int(), C.c_int()
         self.ctx._check(self.lib.trails_advance(self.h, kf.h, C.byref(g), C.byref(a)), "trails_advance")
         return g.value, a.value
+
+    @staticmethod
+    def advance_batch(trails, kfs, d_frames=None):
+        """MakeKeyFrame_Lite of d_frames[i] (DevBuf, raw pointer or None: kfs[i] is made already) into kfs[i] and
+        TrailTracking_Advance for every camera as ONE chain on trails[0]'s queue (ptam_trails_advance_batch)
+        -> [(nGoodTrails, trails alive afterwards)] per camera"""
+        k = len(trails)
+        assert len(kfs) == k and (d_frames is None or len(d_frames) == k)
+        raw = lambda h: h.value if hasattr(h, "value") else int(h)
+        ths = (C.c_void_p * k)(*[raw(t.h) for t in trails])
+        khs = (C.c_void_p * k)(*[raw(kf.h) for kf in kfs])
+        dis = None if d_frames is None else (C.c_void_p * k)(*[None if d is None else raw(d.p if isinstance(d, DevBuf) else d)
+                                                               for d in d_frames])
+        g, a = np.zeros(k, np.int32), np.zeros(k, np.int32)
+        lead = trails[0]
+        lead.ctx._check(lead.lib.trails_advance_batch(k, ths, khs, dis, _ptr(g), _ptr(a)), "trails_advance_batch")
+        return [(int(x), int(y)) for x, y in zip(g, a)]
 
     def _table(self, fn, what, dtype, cap):
         cap = self.max_trails if cap is None else cap
@@ -1859,18 +1899,79 @@ class CameraTracker:
         if rc < 0 and not check:
             return rc
         h0.ctx._check(rc, "camera_tracker_track_frames")
+        return [h._result(r) for h, r in zip(handles, res)]
+
+    def _result(self, r):
+        """a ptam_camera_track_result of this handle as the dict of track_frames"""
+        st = self.state()
+        if r.added_keyframe:      # (the Python MapMaker keeps what its queue names alive: the clone is this handle's)
+            self.mapmaker._queued.append(self)
+        track = np.frombuffer(bytes(r.track), dtype=TRACKMAP_RESULT_DT)[0]
+        rep = r.report
+        return dict(track=track, branch=r.info.branch, quality=st.quality, lost_frames=st.lost_frames, frame=st.frame,
+                    report=dict(map_id=rep.map_id, tag=rep.tag, n_records=rep.n_records, n_entries=rep.n_entries, n_outliers=rep.n_outliers),
+                    map_take=_counts(r.map_take), keyframes_take=_counts(r.keyframes_take), added_keyframe=r.added_keyframe,
+                    noted_frame=r.noted_frame, report_in_chain=r.report_in_chain, queue_size=r.queue_size, tag=r.tag,
+                    info=_abi.TrackFrameStateInfo.from_buffer_copy(bytes(r.info)))
+
+    # ---- a session from the first frame: Tracker::TrackForInitialMap (src/Tracker.cc:311-347) ----
+    def EnableSession(self, max_initial_trails=1000, min_good_trails=10, min_shi_tomasi=70.0, init=None):
+        """ptam_camera_tracker_enable_session; init: a ptam_rmap_init_opts from ResidentMap.init_opts() (None: the defaults)"""
+        o = _abi.CameraSessionOpts()
+        self.ctx._check(self.lib.camera_session_opts_default(C.byref(o)), "camera_session_opts_default")
+        o.max_initial_trails, o.min_good_trails, o.min_shi_tomasi = int(max_initial_trails), int(min_good_trails), float(min_shi_tomasi)
+        if init is not None:
+            o.init = init
+            self._init_keep = init     # (a sample table of the options lives as long as they do)
+        self.ctx._check(self.lib.camera_tracker_enable_session(self.h, C.byref(o)), "camera_tracker_enable_session")
+        self.session_opts = o
+
+    def Restart(self):
+        """the tracker's side of Tracker::Reset (:49-65); MapMaker.RequestReset is the caller's, before"""
+        self.ctx._check(self.lib.camera_tracker_restart(self.h), "camera_tracker_restart")
+
+    def stage(self):
+        s = C.c_int32()
+        self.ctx._check(self.lib.camera_tracker_stage(self.h, C.byref(s)), "camera_tracker_stage")
+        return s.value
+
+    def trails(self):
+        """the inner ptam_trails as a Trails that does not own it (read, patches, matches), or None without a session"""
+        p = self.lib.camera_tracker_trails(self.h)
+        if not p:
+            return None
+        t = Trails.__new__(Trails)
+        t.ctx, t.lib, t.h, t.max_trails = self.ctx, self.lib, C.c_void_p(p), self.session_opts.max_initial_trails
+        return t
+
+    def init_result(self):
+        """the outcome of the last initialisation request this handle has read, as ResidentMap.InitFromStereo's dict"""
+        res = _abi.RmapInitResult()
+        self.ctx._check(self.lib.camera_tracker_init_result(self.h, C.byref(res)), "camera_tracker_init_result")
+        return init_result(res, self.session_opts.init)
+
+    def SessionFrame(self, d_frame, poke=False, check=True):
+        r = CameraTracker.session_frames([self], [d_frame], [poke], check)
+        return r[0] if check or not isinstance(r, int) else r
+
+    @staticmethod
+    def session_frames(handles, d_frames, pokes=None, check=True):
+        """ptam_camera_tracker_session_frames -> per camera (track, session): track the dict of track_frames for a camera that tracked
+        (None otherwise), session a dict of ptam_camera_session_result; check=False: -> the status of a refused call"""
+        k = len(handles)
+        raw = lambda h: h.value if hasattr(h, "value") else int(h)
+        hs = (C.c_void_p * k)(*[raw(h.h) for h in handles])
+        dis = (C.c_void_p * k)(*[raw(d.p if isinstance(d, DevBuf) else d) for d in d_frames])
+        pk = None if pokes is None else (C.c_uint8 * k)(*[int(bool(p)) for p in pokes])
+        res, ses = (_abi.CameraTrackResult * k)(), (_abi.CameraSessionResult * k)()
+        h0 = handles[0]
+        rc = h0.lib.camera_tracker_session_frames(k, hs, dis, pk, res, ses)
+        if rc < 0 and not check:
+            return rc
+        h0.ctx._check(rc, "camera_tracker_session_frames")
         out = []
-        for h, r in zip(handles, res):
-            st = h.state()
-            if r.added_keyframe:      # (the Python MapMaker keeps what its queue names alive: the clone is this handle's)
-                h.mapmaker._queued.append(h)
-            track = np.frombuffer(bytes(r.track), dtype=TRACKMAP_RESULT_DT)[0]
-            rep = r.report
-            out.append(dict(track=track, branch=r.info.branch, quality=st.quality, lost_frames=st.lost_frames, frame=st.frame,
-                            report=dict(map_id=rep.map_id, tag=rep.tag, n_records=rep.n_records, n_entries=rep.n_entries, n_outliers=rep.n_outliers),
-                            map_take=_counts(r.map_take), keyframes_take=_counts(r.keyframes_take), added_keyframe=r.added_keyframe,
-                            noted_frame=r.noted_frame, report_in_chain=r.report_in_chain, queue_size=r.queue_size, tag=r.tag,
-                            info=_abi.TrackFrameStateInfo.from_buffer_copy(bytes(r.info))))
+        for h, r, s in zip(handles, res, ses):
+            out.append((h._result(r) if s.tracked else None, _counts(s)))
         return out
 
     def close(self):
