@@ -2142,6 +2142,81 @@ ptam_trails* ptam_camera_tracker_trails(ptam_camera_tracker*);
 int ptam_camera_tracker_init_result(const ptam_camera_tracker*, ptam_rmap_init_result* out);
 int ptam_camera_tracker_stage(const ptam_camera_tracker*, int32_t* stage);
 
+/* ---- The camera calibrator's optimiser: CameraCalibrator::OptimizeOneStep (src/CameraCalibrator.cc:215-269) with
+ *      CalibImage::GuessInitialPose and CalibImage::Project (src/CalibImage.cc:514-648) and ATANCamera::RefreshParams /
+ *      GetCameraParameterDerivs / UpdateParams / DisableRadialDistortion (src/ATANCamera.cc:27-66, 211-252), fp64 throughout.
+ *      The checkerboard finder (CalibImage::MakeFromImage, CalibCornerPatch) is NOT here: the corners come from the caller's
+ *      detector, each a pixel position (Params.v2Pos) and an integer grid position (irGridPos); the world point of a corner is
+ *      (gx, gy, 0).  A ptam_calibrator lives on a ptam_ctx and uses its device, its queue and its image size; the context's own
+ *      camera plays no part.  All its memory is allocated by ptam_calib_create.
+ *      The camera of the moment — the five parameters, RefreshParams of them and of params + 0.001 e_i (the forward
+ *      differences of GetCameraParameterDerivs) — lives on the device and is refreshed there by every step; the host never
+ *      holds it between steps.
+ *      ptam_calib_add_images: GuessInitialPose with the camera of the moment (src/CameraCalibrator.cc:105-106), one workgroup
+ *      per image: UnProject of every corner, the 2n x 9 DLT matrix, its right null vector by one-sided Jacobi (as the DLT of
+ *      ptam_homography_init), the 2x2 top-left fix-up (:563-583), Gram-Schmidt and the translation (:586-605).
+ *      DEVIATION (sign): the reference takes get_VT()[8] with whatever sign LAPACK gives it, so a camera can end up BEHIND the
+ *      grid; Project then skips every corner and mdMeanPixelError is 0 / 0.  Here the null vector has the sign for which the
+ *      translation's z is positive.  An image whose guess is not finite or whose z is 0 gets PTAM_CALIB_GUESS_REFUSED in
+ *      status_out and is not added (the images after it move up).
+ *      ptam_calib_optimize: `steps` times OptimizeOneStep, one kernel launch per step plus one closing launch, enqueued back to
+ *      back, ONE host wait at the end.  Per measurement the skip tests (v3Cam[2] <= 0.001, Camera.Invalid()), the error, the
+ *      2x6 pose Jacobian (GetProjectionDerivs, generator_field) and the 2x5 camera Jacobian by the reference's forward
+ *      differences of 0.001 (column 4 zero when w == 0).  The system has an arrowhead shape — a 6x6 block D_n = I + sum Jp^T Jp
+ *      per view, the shared 5x5 block C = I + sum Jc^T Jc, 6x5 couplings B_n — and is solved by block elimination: Cholesky of
+ *      every D_n, the 5x5 reduced system (C - sum B_n^T D_n^-1 B_n) delta_c = (Jc^T e - sum B_n^T D_n^-1 e_n), then
+ *      delta_n = D_n^-1 (e_n - B_n delta_c); params += 0.1 delta_c, pose_n = SE3::exp(0.1 delta_n) * pose_n (:265-268).
+ *      DEVIATION (no truncation): the reference takes the SVD of the dense (6 views + 5)^2 matrix and back-substitutes with
+ *      TooN's condition cut, which drops singular values below 1e-9 of the largest.  The matrix is I + J^T J, so nothing is ever
+ *      singular; the two solutions agree while the condition number stays well below 1e9 and differ beyond it.
+ *      With disable_distortion, params[4] is 0 at the start of every step (:226); with w == 0 its column is zero and its row of
+ *      the 5x5 system is the prior alone, so it stays exactly 0.
+ *      DEVIATION (nothing to adjust): when no measurement survives the skip tests the reference divides by zero (:260).  Here
+ *      such a step changes nothing — the update is gated on the device by the step's own count — and a call whose FIRST step
+ *      finds no measurement returns status PTAM_CALIB_NO_MEASUREMENTS with parameters and poses as they were.
+ *      Every sum is reduced in a fixed order: two runs on the same input give the same bits, and `steps` steps in one call give
+ *      the same bits as `steps` calls of one step. */
+typedef struct ptam_calibrator ptam_calibrator;
+enum { PTAM_CALIB_OK = 0, PTAM_CALIB_NO_MEASUREMENTS = 1 };
+enum { PTAM_CALIB_GUESS_OK = 0, PTAM_CALIB_GUESS_REFUSED = 1 };
+enum { PTAM_CALIB_MAX_IMAGES = 65536, PTAM_CALIB_MAX_CORNERS = 4194304, PTAM_CALIB_MAX_STEPS = 65536 };
+typedef struct { int32_t gx, gy; double u, v; } ptam_calib_corner;   /* irGridPos, Params.v2Pos */
+typedef struct {
+    int32_t status;               /* PTAM_CALIB_OK / PTAM_CALIB_NO_MEASUREMENTS */
+    int32_t n_measurements;       /* nTotalMeas of the last step */
+    int32_t steps;                /* the steps of this call */
+    int32_t pad_;
+    double  params[5];            /* Camera.Parameters after the call */
+    double  rms;                  /* mdMeanPixelError of the last step: computed before that step's update (:260) */
+    double  pixel_aspect_ratio;   /* ATANCamera::PixelAspectRatio: fy * height / (fx * width) */
+} ptam_calib_result;
+/* PTAM_E_ARG: max_images outside [1, PTAM_CALIB_MAX_IMAGES], max_corners_total outside [4, PTAM_CALIB_MAX_CORNERS].  The handle
+ * starts as after ptam_calib_reset(h, NULL, 0). */
+int ptam_calib_create(ptam_ctx*, int max_images, int max_corners_total, ptam_calibrator** out);
+int ptam_calib_destroy(ptam_calibrator*);
+/* CameraCalibrator::Reset (:156-165): params (NULL: mvDefaultParams = 0.5, 0.75, 0.5, 0.5, 0.1), DisableRadialDistortion when
+ * disable_distortion, no images.  PTAM_E_ARG: a non-finite parameter, fx or fy of 0. */
+int ptam_calib_reset(ptam_calibrator*, const double* params /* 5 or NULL */, int disable_distortion);
+int ptam_calib_counts(ptam_calibrator*, int32_t* n_images, int32_t* n_corners);
+/* n images; image k's corners are corners[first_corner[k] .. first_corner[k + 1]), first_corner[0] == 0.  status_out: n entries of
+ * PTAM_CALIB_GUESS_*.  One host wait (a second one only when an image was refused by the device). */
+int ptam_calib_add_images(ptam_calibrator*, int n, const int32_t* first_corner /* n + 1 */, const ptam_calib_corner* corners,
+                          int32_t* status_out);
+/* mse3CamFromWorld of every image, 12 doubles each: R row-major, then t. */
+int ptam_calib_set_poses(ptam_calibrator*, const double* poses /* 12 x images */);
+int ptam_calib_read_poses(ptam_calibrator*, double* poses /* 12 x images */);
+/* rms_history (nullable): `steps` entries, mdMeanPixelError of every step; written with status PTAM_CALIB_OK only. */
+int ptam_calib_optimize(ptam_calibrator*, int steps, ptam_calib_result* result, double* rms_history);
+int ptam_calib_params(ptam_calibrator*, double params[5]);
+/* What Draw3DGrid(Camera, true) draws for one image (src/CalibImage.cc:493-501): Camera.Project(project(mse3CamFromWorld * v3)) of
+ * every corner, 2 doubles each, and valid = the corner passes Project's skip tests.  A corner with v3Cam[2] <= 0.001 has
+ * (0, 0) and valid 0; the error the reference draws is the corner's own position minus projected_uv. */
+int ptam_calib_residuals(ptam_calibrator*, int image, double* projected_uv /* 2 x corners */, int32_t* valid);
+/* PTAM_E_ARG, with nothing written and the handle byte for byte as it was: a null pointer (rms_history excepted); an image with
+ * fewer than 4 corners; a grid position twice in one image; a non-finite corner position, pose or parameter; steps < 1 or
+ * > PTAM_CALIB_MAX_STEPS; more images or corners than the handle was created for; fx or fy of 0; an image index outside the
+ * handle's images.  PTAM_E_STATE: ptam_calib_optimize or ptam_calib_set_poses without images. */
+
 /* ---- sharded global BA: measurements sharded by point across ranks ----------- */
 /* A collective hook: all-reduce (sum) `count` doubles in place at device pointer `dptr`,
  * ordered on `stream` (hipStream_t).  Return 0 on success. */

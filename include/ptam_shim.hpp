@@ -14,6 +14,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -419,6 +420,99 @@ private:
     ptam_homography_info info_{};
     std::vector<int32_t> samples_;
     std::vector<uint8_t> inliers_;
+};
+
+// CalibImage (include/CalibImage.h) without the checkerboard finder: the corners come from the caller's detector.
+struct CalibGridCorner {
+    ImageRef irGridPos;
+    struct {
+        Vec<2> v2Pos;
+    } Params;
+};
+struct CalibImage {
+    std::vector<CalibGridCorner> mvGridCorners;
+    SE3 mse3CamFromWorld = SE3::Identity();   // as of the calibrator's last call
+};
+// CameraCalibrator's optimiser (src/CameraCalibrator.cc:156-165, 215-269) on the device, ptam_calib_*: AddImage is the
+// push_back + GuessInitialPose of Run (:105-106), OptimizeOneStep the call of :114.  The camera lives on the device; Params()
+// reads it.  After every call mvCalibImgs[i].mse3CamFromWorld is the device's pose of image i.
+class CameraCalibrator {
+public:
+    CameraCalibrator(Context& c, int nMaxImages = 64, int nMaxCornersTotal = 64 * 256) : ctx_(&c) {
+        check(ptam_calib_create(c.handle(), nMaxImages, nMaxCornersTotal, &h_), "ptam_calib_create");
+    }
+    ~CameraCalibrator() { ptam_calib_destroy(h_); }
+    CameraCalibrator(const CameraCalibrator&) = delete;
+    CameraCalibrator& operator=(const CameraCalibrator&) = delete;
+    ptam_calibrator* handle() const { return h_; }
+
+    void Reset(bool bDisableDistortion = false) {   // *mCamera.mgvvCameraParams = ATANCamera::mvDefaultParams
+        check(ptam_calib_reset(h_, nullptr, bDisableDistortion ? 1 : 0), "ptam_calib_reset");
+        mvCalibImgs.clear();
+        result_ = ptam_calib_result{};
+    }
+    void Reset(const Vec<5>& vParams, bool bDisableDistortion = false) {
+        check(ptam_calib_reset(h_, vParams.data(), bDisableDistortion ? 1 : 0), "ptam_calib_reset");
+        mvCalibImgs.clear();
+        result_ = ptam_calib_result{};
+    }
+    // false: the image's initial pose was refused (ptam_hip.h) and the image is not kept
+    bool AddImage(const CalibImage& c) {
+        std::vector<ptam_calib_corner> v(c.mvGridCorners.size());
+        for (size_t i = 0; i < v.size(); i++) {
+            const CalibGridCorner& g = c.mvGridCorners[i];
+            v[i] = ptam_calib_corner{g.irGridPos.x, g.irGridPos.y, g.Params.v2Pos[0], g.Params.v2Pos[1]};
+        }
+        const int32_t first[2] = {0, (int32_t)v.size()};
+        int32_t status = PTAM_CALIB_GUESS_REFUSED;
+        check(ptam_calib_add_images(h_, 1, first, v.data(), &status), "ptam_calib_add_images");
+        if (status != PTAM_CALIB_GUESS_OK) return false;
+        mvCalibImgs.push_back(c);
+        ReadPoses();
+        return true;
+    }
+    bool OptimizeOneStep() { return Optimize(1); }
+    // nSteps x OptimizeOneStep in one device call; false: nothing to adjust (PTAM_CALIB_NO_MEASUREMENTS)
+    bool Optimize(int nSteps) {
+        rms_.assign((size_t)(nSteps > 0 ? nSteps : 0), 0.0);
+        check(ptam_calib_optimize(h_, nSteps, &result_, rms_.data()), "ptam_calib_optimize");
+        ReadPoses();
+        return result_.status == PTAM_CALIB_OK;
+    }
+    double MeanPixelError() const { return result_.rms; }   // mdMeanPixelError of the last step
+    Vec<5> Params() const {
+        Vec<5> v;
+        check(ptam_calib_params(h_, v.data()), "ptam_calib_params");
+        return v;
+    }
+    const ptam_calib_result& Result() const { return result_; }
+    const std::vector<double>& RMSHistory() const { return rms_; }
+    // the one line GVars reads from camera.cfg (GV2.PrintVar("Camera.Parameters", ofs), :190-200)
+    static std::string ConfigLine(const Vec<5>& v) {
+        char buf[256];
+        std::snprintf(buf, sizeof buf, "Camera.Parameters=[ %.17g %.17g %.17g %.17g %.17g ]\n", v[0], v[1], v[2], v[3], v[4]);
+        return buf;
+    }
+    bool SaveCalib(const std::string& sPath = "camera.cfg") const {
+        FILE* f = std::fopen(sPath.c_str(), "w");
+        if (!f) return false;
+        const std::string s = ConfigLine(Params());
+        const bool ok = std::fwrite(s.data(), 1, s.size(), f) == s.size();
+        return std::fclose(f) == 0 && ok;
+    }
+    std::vector<CalibImage> mvCalibImgs;
+
+private:
+    void ReadPoses() {
+        if (mvCalibImgs.empty()) return;
+        std::vector<double> p(mvCalibImgs.size() * 12);
+        check(ptam_calib_read_poses(h_, p.data()), "ptam_calib_read_poses");
+        for (size_t i = 0; i < mvCalibImgs.size(); i++) mvCalibImgs[i].mse3CamFromWorld = SE3::from12(&p[i * 12]);
+    }
+    Context* ctx_;
+    ptam_calibrator* h_ = nullptr;
+    ptam_calib_result result_{};
+    std::vector<double> rms_;
 };
 
 // The point loop of MapMaker::InitFromStereo (src/MapMaker.cc:310-367) in ONE device call (ptam_init_points_from_trails):

@@ -434,6 +434,21 @@ class CameraTrackResult(C.Structure):
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p)
 
+class CalibCorner(C.Structure):
+    """ptam_calib_corner (CalibGridCorner: irGridPos, Params.v2Pos; include/CalibImage.h)"""
+    _fields_ = [("gx", C.c_int32), ("gy", C.c_int32), ("u", C.c_double), ("v", C.c_double)]
+
+
+class CalibResult(C.Structure):
+    """ptam_calib_result (CameraCalibrator::OptimizeOneStep, src/CameraCalibrator.cc:215-269)"""
+    _fields_ = [("status", C.c_int32), ("n_measurements", C.c_int32), ("steps", C.c_int32), ("pad_", C.c_int32),
+                ("params", C.c_double * 5), ("rms", C.c_double), ("pixel_aspect_ratio", C.c_double)]
+
+
+CALIB_OK, CALIB_NO_MEASUREMENTS = 0, 1
+CALIB_GUESS_OK, CALIB_GUESS_REFUSED = 0, 1
+CALIB_MAX_IMAGES, CALIB_MAX_CORNERS, CALIB_MAX_STEPS = 65536, 4194304, 65536
+
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
 _pd, _pi, _pu8 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
 _ppv = C.POINTER(C.c_void_p)
@@ -677,6 +692,16 @@ PROTOTYPES = {
     "mapmaker_set_flags": (_i, [_vp, _i, _i]),
     "mapmaker_released": (_i, [_vp, _i, _vp, C.POINTER(C.c_int32)]),
     "mapmaker_step": (_i, [_vp, C.POINTER(MapmakerStepResult)]),
+    "calib_create": (_i, [_vp, _i, _i, _ppv]),
+    "calib_destroy": (_i, [_vp]),
+    "calib_reset": (_i, [_vp, _pd, _i]),
+    "calib_counts": (_i, [_vp, _pi, _pi]),
+    "calib_add_images": (_i, [_vp, _i, _pi, _vp, _pi]),
+    "calib_set_poses": (_i, [_vp, _pd]),
+    "calib_read_poses": (_i, [_vp, _pd]),
+    "calib_optimize": (_i, [_vp, _i, C.POINTER(CalibResult), _pd]),
+    "calib_params": (_i, [_vp, _pd]),
+    "calib_residuals": (_i, [_vp, _i, _pd, _pi]),
     "rccl_unique_id": (_i, [_vp]),
     "rccl_create": (_i, [_vp, _vp, _i, _i, _ppv]),
     "rccl_destroy": (_i, [_vp]),

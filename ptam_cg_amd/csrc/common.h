@@ -102,6 +102,7 @@ void refind_preload_kernels();
 void maprefind_preload_kernels();
 void maptables_preload_kernels();
 void sbi_preload_kernels();
+void calib_preload_kernels();
 void maprmap_preload_kernels();
 void maprmap_keyframe_preload_kernels();
 void maprmap_publish_preload_kernels();
@@ -166,6 +167,54 @@ PTAM_HD void cam_derivs(const DevCam& c, double x, double y, double r_in, double
     D[2] = c.fy * (dx * y);
     D[1] = c.fx * (dy * x);
     D[3] = c.fy * (dy * y + f);
+}
+
+// RefreshParams src/ATANCamera.cc:27-66 (only the members the hot path reads), on the host for a context's camera and on the
+// device for the calibrator's, whose parameters change there (calib.hip)
+PTAM_HD void devcam_unproject_plain(const DevCam& c, double one_over_two_tan, double u, double v, double out[2]) {
+    const double dx = (u - c.cx) * c.inv_fx, dy = (v - c.cy) * c.inv_fy;
+    const double dr = sqrt(dx * dx + dy * dy);
+    const double rr = (c.w == 0.0) ? dr : tan(dr * c.w) * one_over_two_tan;
+    const double f = dr > 0.01 ? rr / dr : 1.0;
+    out[0] = f * dx;
+    out[1] = f * dy;
+}
+PTAM_HD DevCam devcam_refresh(double width, double height, double pfx, double pfy, double pcx, double pcy, double pw) {
+    DevCam c;
+    c.width = width;
+    c.height = height;
+    c.fx = c.width * pfx;
+    c.fy = c.height * pfy;
+    c.cx = c.width * pcx - 0.5;
+    c.cy = c.height * pcy - 0.5;
+    c.w = pw;
+    double one_over_two_tan;
+    if (c.w != 0.0) {
+        c.two_tan = 2.0 * tan(c.w / 2.0);
+        one_over_two_tan = 1.0 / c.two_tan;
+        c.w_inv = 1.0 / c.w;
+        c.dist_enabled = 1.0;
+    } else {
+        c.w_inv = 0.0;
+        c.two_tan = 0.0;
+        one_over_two_tan = 0.0;
+        c.dist_enabled = 0.0;
+    }
+    const double vx = fmax(pcx, 1.0 - pcx) / pfx;
+    const double vy = fmax(pcy, 1.0 - pcy) / pfy;
+    const double r = sqrt(vx * vx + vy * vy);
+    c.largest_radius = (c.w == 0.0) ? r : tan(r * c.w) * one_over_two_tan;   // invrtrans
+    c.max_r = 1.5 * c.largest_radius;
+    c.inv_fx = 1.0 / c.fx;   // :38-39
+    c.inv_fy = 1.0 / c.fy;
+    c.one_over_two_tan = one_over_two_tan;
+    // mdOnePixelDist :69-75 — UnProject at the image centre and one pixel down-right of it
+    double a[2], b[2];
+    devcam_unproject_plain(c, one_over_two_tan, width / 2.0, height / 2.0, a);   // mvImageSize is a Vector<2> of doubles
+    devcam_unproject_plain(c, one_over_two_tan, width / 2.0 + 1, height / 2.0 + 1, b);
+    const double ddx = a[0] - b[0], ddy = a[1] - b[1];
+    c.one_pixel_dist = sqrt(ddx * ddx + ddy * ddy) / sqrt(2.0);
+    return c;
 }
 
 // pose = R row-major (9) + t (3)

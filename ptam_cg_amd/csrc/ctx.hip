@@ -108,52 +108,8 @@ int ctx_pinned(ptam_ctx* ctx, size_t bytes, void** out) {
     return PTAM_OK;
 }
 
-// RefreshParams src/ATANCamera.cc:27-66 (only the members the hot path reads)
-static DevCam make_devcam(const ptam_cam_params& p) {
-    DevCam c;
-    c.width = p.width;
-    c.height = p.height;
-    c.fx = c.width * p.fx;
-    c.fy = c.height * p.fy;
-    c.cx = c.width * p.cx - 0.5;
-    c.cy = c.height * p.cy - 0.5;
-    c.w = p.w;
-    double one_over_two_tan;
-    if (c.w != 0.0) {
-        c.two_tan = 2.0 * std::tan(c.w / 2.0);
-        one_over_two_tan = 1.0 / c.two_tan;
-        c.w_inv = 1.0 / c.w;
-        c.dist_enabled = 1.0;
-    } else {
-        c.w_inv = 0.0;
-        c.two_tan = 0.0;
-        one_over_two_tan = 0.0;
-        c.dist_enabled = 0.0;
-    }
-    const double vx = std::fmax(p.cx, 1.0 - p.cx) / p.fx;
-    const double vy = std::fmax(p.cy, 1.0 - p.cy) / p.fy;
-    const double r = std::sqrt(vx * vx + vy * vy);
-    c.largest_radius = (c.w == 0.0) ? r : std::tan(r * c.w) * one_over_two_tan;   // invrtrans
-    c.max_r = 1.5 * c.largest_radius;
-    c.inv_fx = 1.0 / c.fx;   // :38-39
-    c.inv_fy = 1.0 / c.fy;
-    c.one_over_two_tan = one_over_two_tan;
-    // mdOnePixelDist :69-75 — UnProject at the image centre and one pixel down-right of it
-    auto unproject = [&](double u, double v, double out[2]) {
-        const double dx = (u - c.cx) * c.inv_fx, dy = (v - c.cy) * c.inv_fy;
-        const double dr = std::sqrt(dx * dx + dy * dy);
-        const double rr = (c.w == 0.0) ? dr : std::tan(dr * c.w) * one_over_two_tan;
-        const double f = dr > 0.01 ? rr / dr : 1.0;
-        out[0] = f * dx;
-        out[1] = f * dy;
-    };
-    double a[2], b[2];
-    unproject(p.width / 2.0, p.height / 2.0, a);           // mvImageSize is a Vector<2> of doubles
-    unproject(p.width / 2.0 + 1, p.height / 2.0 + 1, b);
-    const double ddx = a[0] - b[0], ddy = a[1] - b[1];
-    c.one_pixel_dist = std::sqrt(ddx * ddx + ddy * ddy) / std::sqrt(2.0);
-    return c;
-}
+// RefreshParams src/ATANCamera.cc:27-66 (only the members the hot path reads): devcam_refresh, common.h
+static DevCam make_devcam(const ptam_cam_params& p) { return devcam_refresh(p.width, p.height, p.fx, p.fy, p.cx, p.cy, p.w); }
 
 // TrackerData::Project + GetProjectionDerivs (include/Tracker.h:70-94)
 __global__ void project_points_kernel(DevCam cam, int n, const double* __restrict__ world,
@@ -273,6 +229,7 @@ int ptam_ctx_create(const ptam_cam_params* cam, int device, ptam_ctx** out) {
     kf_preload_kernels();
     pvs_preload_kernels();
     sbi_preload_kernels();
+    calib_preload_kernels();
     *out = c;
     return PTAM_OK;
 }

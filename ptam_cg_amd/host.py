@@ -655,6 +655,109 @@ class HomographyInit:
         return _homography_call(self.ctx, lambda *a: self.lib.homography_init(self.ctx.h, len(m), _ptr(m), *a), "homography_init", opts, len(m))
 
 
+CALIB_CORNER_DT = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("u", "<f8"), ("v", "<f8")])
+assert CALIB_CORNER_DT.itemsize == C.sizeof(_abi.CalibCorner) == 24
+
+
+class CameraCalibrator:
+    """CameraCalibrator's optimiser (src/CameraCalibrator.cc:156-165, 215-269; CalibImage::GuessInitialPose / Project,
+    src/CalibImage.cc:514-648) on the device: ptam_calib_*.  The grid corners come from the caller's detector."""
+
+    def __init__(self, ctx, max_images=64, max_corners_total=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        if not self.lib.has("calib_create"):
+            raise PtamError("this library has no ptam_calib_create")
+        self.max_images = int(max_images)
+        self.max_corners = int(max_corners_total if max_corners_total is not None else 256 * max_images)
+        h = C.c_void_p()
+        ctx._check(self.lib.calib_create(ctx.h, self.max_images, self.max_corners, C.byref(h)), "calib_create")
+        self.h = h
+        self.last = None
+        self._sizes = []
+
+    def Reset(self, params=None, disable_distortion=False):
+        p = None if params is None else np.ascontiguousarray(params, dtype=np.float64).reshape(5)
+        self.ctx._check(self.lib.calib_reset(self.h, None if p is None else _pd(p), int(bool(disable_distortion))), "calib_reset")
+        self.last = None
+        self._sizes = []
+
+    def counts(self):
+        a, b = C.c_int32(), C.c_int32()
+        self.ctx._check(self.lib.calib_counts(self.h, C.byref(a), C.byref(b)), "calib_counts")
+        return a.value, b.value
+
+    def AddImages(self, images):
+        """images: a list of CALIB_CORNER_DT arrays -> status (n,) of _abi.CALIB_GUESS_*; a refused image is not added"""
+        imgs = [np.ascontiguousarray(c, dtype=CALIB_CORNER_DT).reshape(-1) for c in images]
+        first = np.zeros(len(imgs) + 1, np.int32)
+        first[1:] = np.cumsum([len(c) for c in imgs])
+        allc = np.concatenate(imgs) if imgs else np.zeros(0, CALIB_CORNER_DT)
+        status = np.zeros(max(len(imgs), 1), np.int32)
+        self.ctx._check(self.lib.calib_add_images(self.h, len(imgs), first.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(allc),
+                                                  status.ctypes.data_as(C.POINTER(C.c_int32))), "calib_add_images")
+        status = status[:len(imgs)]
+        self._sizes += [len(c) for c, st in zip(imgs, status) if st == _abi.CALIB_GUESS_OK]
+        return status
+
+    def AddImage(self, corners):
+        return int(self.AddImages([corners])[0])
+
+    def Optimize(self, steps):
+        """steps x OptimizeOneStep in one call -> dict(status, params, rms, n_measurements, pixel_aspect_ratio, steps, history)"""
+        res = _abi.CalibResult()
+        hist = np.zeros(max(int(steps), 1))
+        self.ctx._check(self.lib.calib_optimize(self.h, int(steps), C.byref(res), _pd(hist)), "calib_optimize")
+        self.last = dict(status=res.status, params=np.array(res.params), rms=res.rms, n_measurements=res.n_measurements,
+                         pixel_aspect_ratio=res.pixel_aspect_ratio, steps=res.steps,
+                         history=hist[:int(steps)] if res.status == _abi.CALIB_OK else None)
+        return self.last
+
+    def OptimizeOneStep(self):
+        return self.Optimize(1)
+
+    def Params(self):
+        out = np.zeros(5)
+        self.ctx._check(self.lib.calib_params(self.h, _pd(out)), "calib_params")
+        return out
+
+    def MeanPixelError(self):
+        """mdMeanPixelError of the last step taken"""
+        return float("nan") if self.last is None or self.last["status"] != _abi.CALIB_OK else self.last["rms"]
+
+    def Poses(self):
+        n = self.counts()[0]
+        out = np.zeros((max(n, 1), 12))
+        self.ctx._check(self.lib.calib_read_poses(self.h, _pd(out)), "calib_read_poses")
+        return out[:n]
+
+    def SetPoses(self, poses):
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+        if len(p) != self.counts()[0]:
+            raise PtamError("SetPoses: one pose per image")
+        self.ctx._check(self.lib.calib_set_poses(self.h, _pd(p)), "calib_set_poses")
+
+    def Residuals(self, image):
+        """-> (projected (n, 2), valid (n,) bool) of one image's corners"""
+        n = self._sizes[image] if 0 <= image < len(self._sizes) else 1
+        uv, valid = np.zeros((n, 2)), np.zeros(n, np.int32)
+        self.ctx._check(self.lib.calib_residuals(self.h, int(image), _pd(uv), valid.ctypes.data_as(C.POINTER(C.c_int32))), "calib_residuals")
+        return uv, valid.astype(bool)
+
+    def SaveCalib(self, path):
+        """the one line of camera.cfg that GVars reads: Camera.Parameters=[ a b c d e ] (src/CameraCalibrator.cc:190-200)"""
+        with open(path, "w") as f:
+            f.write(calib_cfg_line(self.Params()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.calib_destroy(self.h)
+            self.h = None
+
+
+def calib_cfg_line(params):
+    return "Camera.Parameters=[ " + " ".join("%.17g" % float(v) for v in params) + " ]\n"
+
+
 def init_points_from_trails(ctx, first_kf, second_kf, se3_second_from_first, matches, subpix_max_its=10):
     """the point loop of MapMaker::InitFromStereo (src/MapMaker.cc:310-367) in one device call: matches TRAIL_DT (initial in
     the first keyframe, current in the second) -> (points NEW_MAP_POINT_DT in match order, status (n,) of _abi.INIT_*)"""

@@ -507,3 +507,44 @@ def load_into(bundle, prob):
     bundle.add_problem(prob["poses"], prob["fixed"], prob["points"], prob["cam_idx"], prob["pt_idx"],
                        prob["found"], prob["sigma_sq"])
     return bundle
+
+
+# ---------------------------------------------------------------------------------------------
+# calibration grids (CameraCalibrator: the corners of a checkerboard seen by a known ATAN camera)
+# ---------------------------------------------------------------------------------------------
+CALIB_CORNER_DT = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("u", "<f8"), ("v", "<f8")])
+
+
+def make_calib_grids(truth_params, size, n_images, grid_w, grid_h, seed, noise_px=0.0, distance=(6.0, 10.0), tilt=0.6):
+    """n_images views of a grid_w x grid_h grid (corner (gx, gy) at the world point (gx, gy, 0)) from random poses in front of
+    the ATAN camera truth_params: the camera looks at a point near the grid's middle from `distance` grid units away, up to
+    `tilt` radians off the grid's normal, with any roll.  Only corners that fall inside the image are kept.
+    -> [(corners CALIB_CORNER_DT, true camera-from-world pose (12,))]"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    cam = AtanCam(truth_params, size)
+    gx, gy = np.meshgrid(np.arange(grid_w), np.arange(grid_h))
+    gx, gy = gx.ravel(), gy.ravel()
+    world = np.stack([gx, gy, np.zeros(len(gx))], axis=1).astype(np.float64)
+    mid = np.array([(grid_w - 1) / 2.0, (grid_h - 1) / 2.0, 0.0])
+    out = []
+    while len(out) < n_images:
+        d = rng.uniform(*distance)
+        th, ph, roll = rng.uniform(0.15, tilt), rng.uniform(0, 2 * np.pi), rng.uniform(-np.pi, np.pi)
+        off = np.array([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), -np.cos(th)])
+        target = mid + np.concatenate([rng.uniform(-0.5, 0.5, 2), [0.0]])
+        pose = look_at(mid + d * off, target, up=(0.0, 1.0, 0.0))
+        cr, sr = np.cos(roll), np.sin(roll)
+        pose = se3_mul(np.concatenate([np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1.0]]).ravel(), np.zeros(3)]), pose)
+        Xc = world @ pose[:9].reshape(3, 3).T + pose[9:]
+        if not (Xc[:, 2] > 0.5).all():
+            continue
+        im, r = cam.project(Xc[:, :2] / Xc[:, 2:3])
+        if noise_px:
+            im = im + rng.normal(0.0, noise_px, im.shape)
+        ok = (r <= cam.largest_radius) & (im[:, 0] >= 0) & (im[:, 1] >= 0) & (im[:, 0] <= size[0] - 1) & (im[:, 1] <= size[1] - 1)
+        if ok.sum() < 4:
+            continue
+        c = np.zeros(int(ok.sum()), CALIB_CORNER_DT)
+        c["gx"], c["gy"], c["u"], c["v"] = gx[ok], gy[ok], im[ok, 0], im[ok, 1]
+        out.append((c, pose))
+    return out
