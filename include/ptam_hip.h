@@ -1922,14 +1922,14 @@ typedef struct {
     int32_t failure_period;             /* 20: rand() % 20 (:103) */
     uint64_t failure_seed;
 } ptam_mapmaker_opts;
-enum { PTAM_MM_RAN = 0, PTAM_MM_IDLE = 1, PTAM_MM_RESET = 2 };
+/* PTAM_MM_INIT, PTAM_MM_STAGE_INIT: the status and the stage bit of a step that made the first map (ptam_mapmaker_request_init) */
+enum { PTAM_MM_RAN = 0, PTAM_MM_IDLE = 1, PTAM_MM_RESET = 2, PTAM_MM_INIT = 3 };
 enum {
     PTAM_MM_STAGE_BUNDLE_RECENT = 1, PTAM_MM_STAGE_REFIND_NEW = 2, PTAM_MM_STAGE_BUNDLE_ALL = 4, PTAM_MM_STAGE_REFIND_FAILURE = 8,
-    PTAM_MM_STAGE_NOTES = 16, PTAM_MM_STAGE_BAD_POINTS = 32, PTAM_MM_STAGE_ADD_KEYFRAME = 64, PTAM_MM_STAGE_PUBLISH = 128
+    PTAM_MM_STAGE_NOTES = 16, PTAM_MM_STAGE_BAD_POINTS = 32, PTAM_MM_STAGE_ADD_KEYFRAME = 64, PTAM_MM_STAGE_PUBLISH = 128,
+    PTAM_MM_STAGE_INIT = 256
 };
-/* a step that made the first map (ptam_mapmaker_request_init): the status behind PTAM_MM_RESET (3), the stage bit behind
- * PTAM_MM_STAGE_PUBLISH (256); and what ptam_mapmaker_init_poll says of a request (0, 1, 2) */
-enum { PTAM_MM_INIT = PTAM_MM_RESET + 1, PTAM_MM_STAGE_INIT = PTAM_MM_STAGE_PUBLISH << 1 };
+/* what ptam_mapmaker_init_poll says of a request (0, 1, 2) */
 enum { PTAM_MM_INIT_NONE, PTAM_MM_INIT_PENDING, PTAM_MM_INIT_DONE };
 typedef struct {
     int32_t status, stages;

@@ -1,4 +1,7 @@
-"""ctypes view of include/ptam_hip.h: struct layouts and prototypes.
+"""ctypes view of include/ptam_hip.h and include/ptam_hip_bench.h, and their only statement in Python: a class for every struct
+(ptam_foo_bar or ptam_foo_bar_t -> FooBar, the header's field names), a constant for every enumerator and integer #define (the
+header's name without PTAM_), a PROTOTYPES entry for every function.  host.py derives its numpy record types from the classes;
+tests/test_abi.py compares all of it with the headers as a C compiler reads them.
 
 `bind(lib, prefix)` attaches argtypes/restypes for every entry point that the given shared library
 exports under `prefix` ("ptam_" for libptam_hip.so).  The binding is prefix-generic so that the
@@ -8,7 +11,9 @@ ever loads libptam_hip.so (see _lib.py).
 import ctypes as C
 
 LEVELS = 4
+PATCH = 8
 MAX_SSD = 8 * 8 * 500
+OK, E_ARG, E_HIP, E_STATE, E_LIMIT, E_COMM = 0, -1, -2, -3, -4, -5
 HALFSAMPLE_R, HALFSAMPLE_T = 0, 1
 EST_TUKEY, EST_CAUCHY, EST_HUBER = 0, 1, 2
 K_PROJECT, K_SELECT, K_JACOBIAN, K_VINV, K_SCHUR, K_SOLVE, K_UPDATE, K_EXCHANGE, K_COUNT = range(9)
@@ -69,6 +74,19 @@ class EpipolarResult(C.Structure):
 
 class PvsPoint(C.Structure):
     _fields_ = [("world", C.c_double * 3), ("pixel_right_w", C.c_double * 3), ("pixel_down_w", C.c_double * 3)]
+
+
+class PvsResult(C.Structure):
+    _fields_ = [("proj", Projection), ("warp_inverse", C.c_double * 4), ("level", C.c_int32), ("pad_", C.c_int32)]
+
+
+class RefindResult(C.Structure):
+    _fields_ = [("found", C.c_int32), ("level", C.c_int32), ("sub_pix", C.c_int32), ("never_retry", C.c_int32), ("root_pos", C.c_double * 2)]
+
+
+class RefindPair(C.Structure):
+    _fields_ = [("kf", C.c_void_p), ("kf_pose", C.c_double * 12), ("point", PvsPoint), ("source", TemplateQuery), ("point_id", C.c_int64),
+                ("skip", C.c_int32), ("pad_", C.c_int32)]
 
 
 class EpipolarOpts(C.Structure):
@@ -142,14 +160,28 @@ class MotionModel(C.Structure):
 
 
 class BaTrial(C.Structure):
-    _fields_ = [("lambda_", C.c_double), ("sigma_sq", C.c_double), ("err_old", C.c_double),
+    """ptam_ba_trial (`lambda` is read with getattr)"""
+    _fields_ = [("lambda", C.c_double), ("sigma_sq", C.c_double), ("err_old", C.c_double),
                 ("err_new", C.c_double), ("sum_sq_update", C.c_double), ("n_bad", C.c_int32),
                 ("accepted", C.c_int32)]
 
 
 MAP_BA_ALL, MAP_BA_RECENT = 0, 1
-SRC_TRACKER, SRC_REFIND, SRC_ROOT, SRC_TRAIL, SRC_EPIPOLAR = range(5)   # Measurement::Source, include/KeyFrame.h:50
-OUT_POINT_BAD, OUT_FAILURE_QUEUE, OUT_NEVER_RETRY = 1, 2, 3
+MAP_SRC_TRACKER, MAP_SRC_REFIND, MAP_SRC_ROOT, MAP_SRC_TRAIL, MAP_SRC_EPIPOLAR = range(5)   # Measurement::Source, include/KeyFrame.h:50
+MAP_OUT_POINT_BAD, MAP_OUT_FAILURE_QUEUE, MAP_OUT_NEVER_RETRY = 1, 2, 3
+# (the shorter names the map code and its tests say)
+SRC_TRACKER, SRC_REFIND, SRC_ROOT, SRC_TRAIL, SRC_EPIPOLAR = MAP_SRC_TRACKER, MAP_SRC_REFIND, MAP_SRC_ROOT, MAP_SRC_TRAIL, MAP_SRC_EPIPOLAR
+OUT_POINT_BAD, OUT_FAILURE_QUEUE, OUT_NEVER_RETRY = MAP_OUT_POINT_BAD, MAP_OUT_FAILURE_QUEUE, MAP_OUT_NEVER_RETRY
+
+
+class MapMeas(C.Structure):
+    """ptam_map_meas: one row of the table of all keyframes' mMeasurements"""
+    _fields_ = [("kf", C.c_int32), ("point", C.c_int32), ("level", C.c_int32), ("source", C.c_int32), ("root_pos", C.c_double * 2)]
+
+
+class MapOutlier(C.Structure):
+    """ptam_map_outlier: one outlier measurement with the action the host applies"""
+    _fields_ = [("point", C.c_int32), ("kf", C.c_int32), ("action", C.c_int32), ("meas", C.c_int32)]
 
 
 class MapBaResult(C.Structure):
@@ -334,6 +366,12 @@ class TrackmapResult(C.Structure):
                 ("depth_sum_sq", C.c_double)]
 
 
+class TrackmapMeas(C.Structure):
+    """ptam_trackmap_meas"""
+    _fields_ = [("point", C.c_int32), ("level", C.c_int32), ("found", C.c_int32), ("did_subpix", C.c_int32), ("outlier", C.c_int32),
+                ("pad_", C.c_int32), ("v2_found", C.c_double * 2)]
+
+
 class RmapNoteResult(C.Structure):
     """ptam_rmap_note_result"""
     _fields_ = [("n_records", C.c_int32), ("n_gone", C.c_int32)]
@@ -434,6 +472,7 @@ class CameraTrackResult(C.Structure):
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p)
 
+
 class CalibCorner(C.Structure):
     """ptam_calib_corner (CalibGridCorner: irGridPos, Params.v2Pos; include/CalibImage.h)"""
     _fields_ = [("gx", C.c_int32), ("gy", C.c_int32), ("u", C.c_double), ("v", C.c_double)]
@@ -448,6 +487,15 @@ class CalibResult(C.Structure):
 CALIB_OK, CALIB_NO_MEASUREMENTS = 0, 1
 CALIB_GUESS_OK, CALIB_GUESS_REFUSED = 0, 1
 CALIB_MAX_IMAGES, CALIB_MAX_CORNERS, CALIB_MAX_STEPS = 65536, 4194304, 65536
+
+# include/ptam_hip_bench.h: the stages of ptam_tracker_stage_time, the lists of ptam_ba_debug_lists, the bits of ptam_ba_solve_plan
+(TS_PYR_PVS, TS_DETECT, TS_COMPACT_SELECT, TS_SEARCH_COARSE, TS_GATHER_COARSE, TS_POSE_COARSE, TS_SEARCH_FINE, TS_GATHER_FINE, TS_POSE_FINE,
+ TS_COUNT) = range(10)
+(BL_COUNTS, BL_ROWPTR, BL_M_CAM, BL_M_PT, BL_M_ORIG, BL_M_FIDX, BL_M_FOUND, BL_M_S, BL_PT_ORIG, BL_POINTS, BL_CHUNKS, BL_S_ENTRIES, BL_S_SEGS,
+ BL_S_WG_SEG, BL_S_PAIR_BEGIN, BL_S_WG_HEAD, BL_CAM_PTR, BL_CAM_MEAS) = range(18)
+(SP_SMALL, SP_CHAIN_FWD_INV, SP_CHAIN_BW_IN_LAUNCH, SP_CHAIN_SEPARATE_BW, SP_STEPS, SP_TWO_CHAINS, SP_TWIN_STEPS, SP_MID_CHAIN, SP_MID_STEPS,
+ SP_BW_TWO_WG, SP_BW_GLOBAL) = (1 << i for i in range(11))
+SOLVE_PER_COLUMN, SOLVE_POISON_UPPER = 1, 2
 
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
 _pd, _pi, _pu8 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)

@@ -10,56 +10,45 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (BaOpts, BaTrial, CamParams, EpipolarLevelStats, EpipolarOpts, GnOpts, Int2, MotionModel, NewMapPoint, PatchQuery,
-                   PatchResult, PoseMeas, PoseUpdateMeas, Projection)
+from ._abi import BaOpts, CamParams, EpipolarOpts, GnOpts, MotionModel
 
 # config/camera.cfg:7
 DEFAULT_CAMERA = (1.0803, 1.43987, 0.519983, 0.548655, 0.244943)
 
-PATCH_QUERY_DT = np.dtype([("x", "<i4"), ("y", "<i4"), ("level", "<i4"), ("range", "<u4")])
-PATCH_RESULT_DT = np.dtype([("found", "<i4"), ("best_ssd", "<i4"), ("best_x", "<i4"), ("best_y", "<i4"),
-                            ("n_scored", "<i4"), ("pad_", "<i4"), ("pos", "<f8", (2,))])
-PROJECTION_DT = np.dtype([("cam", "<f8", (3,)), ("image", "<f8", (2,)), ("derivs", "<f8", (4,)),
-                          ("in_image", "<i4"), ("pad_", "<i4")])
-POSE_MEAS_DT = np.dtype([("world", "<f8", (3,)), ("found", "<f8", (2,)), ("sqrt_inv_noise", "<f8")])
-POSE_UPDATE_MEAS_DT = np.dtype([("found", "<f8", (2,)), ("image", "<f8", (2,)), ("sqrt_inv_noise", "<f8"),
-                                ("jac", "<f8", (12,))])
-SUBPIX_QUERY_DT = np.dtype([("coarse_pos", "<f8", (2,)), ("level", "<i4"), ("max_its", "<i4")])
-SUBPIX_RESULT_DT = np.dtype([("converged", "<i4"), ("iterations", "<i4"), ("pos", "<f8", (2,)), ("mean_diff", "<f8")])
-TEMPLATE_QUERY_DT = np.dtype([("src_kf", "<u8"), ("src_level", "<i4"), ("search_level", "<i4"), ("center_x", "<i4"),
-                              ("center_y", "<i4"), ("warp_inverse", "<f8", (4,))])
-EPIPOLAR_QUERY_DT = np.dtype([("level_x", "<i4"), ("level_y", "<i4"), ("normal", "<f8", (2,)), ("norm_dist", "<f8"),
-                              ("along", "<f8", (2,)), ("min_len", "<f8"), ("max_len", "<f8"), ("max_dist_sq", "<f8")])
-EPIPOLAR_RESULT_DT = np.dtype([("best", "<i4"), ("best_zmssd", "<i4"), ("n_scored", "<i4"), ("template_bad", "<i4")])
-TEMPLATE_RESULT_DT = np.dtype([("bad", "<i4"), ("n_outside", "<i4"), ("sum", "<i4"), ("sum_sq", "<i4"), ("m2", "<f8", (4,))])
-PVS_POINT_DT = np.dtype([("world", "<f8", (3,)), ("pixel_right_w", "<f8", (3,)), ("pixel_down_w", "<f8", (3,))])
-PVS_RESULT_DT = np.dtype([("proj", PROJECTION_DT), ("warp_inverse", "<f8", (4,)), ("level", "<i4"), ("pad_", "<i4")])
-BA_TRIAL_DT = np.dtype([("lambda", "<f8"), ("sigma_sq", "<f8"), ("err_old", "<f8"), ("err_new", "<f8"),
-                        ("sum_sq_update", "<f8"), ("n_bad", "<i4"), ("accepted", "<i4")])
-REFIND_RESULT_DT = np.dtype([("found", "<i4"), ("level", "<i4"), ("sub_pix", "<i4"), ("never_retry", "<i4"), ("root_pos", "<f8", (2,))])
-REFIND_PAIR_DT = np.dtype([("kf", "<u8"), ("kf_pose", "<f8", (12,)), ("point", PVS_POINT_DT), ("source", TEMPLATE_QUERY_DT),
-                           ("point_id", "<i8"), ("skip", "<i4"), ("pad_", "<i4")])
-assert REFIND_PAIR_DT.itemsize == 248
-NEW_MAP_POINT_DT = np.dtype([("point", PVS_POINT_DT), ("center_nc", "<f8", (3,)), ("one_right_nc", "<f8", (3,)),
-                             ("one_down_nc", "<f8", (3,)), ("src_root_pos", "<f8", (2,)), ("target_pos", "<f8", (2,)), ("level", "<i4"),
-                             ("center_x", "<i4"), ("center_y", "<i4"), ("candidate", "<i4"), ("target_corner", "<i4"), ("best_zmssd", "<i4")])
-EPIPOLAR_STATS_FIELDS = ("candidates", "kept_after_thinning", "ray_rejected", "line_rejected", "template_bad", "no_match",
-                         "subpix_failed", "made")
-EPIPOLAR_STATS_DT = np.dtype([(f, "<i4") for f in EPIPOLAR_STATS_FIELDS])
-assert NEW_MAP_POINT_DT.itemsize == C.sizeof(NewMapPoint) == 200 and EPIPOLAR_STATS_DT.itemsize == C.sizeof(EpipolarLevelStats)
-TRACKMAP_OPTS_DT = np.dtype([("try_coarse", "<i4"), ("coarse_min", "<u4"), ("coarse_max", "<u4"), ("coarse_range", "<u4"),
-                             ("coarse_subpix_its", "<i4"), ("max_patches", "<i4"), ("estimator", "<i4"), ("pad_", "<i4")])
-TRACKMAP_RESULT_DT = np.dtype([("pose", "<f8", (12,)), ("did_coarse", "<i4"), ("n_pvs", "<i4", (4,)), ("attempted", "<i4", (4,)),
-                               ("found", "<i4", (4,)), ("n_coarse", "<i4"), ("n_top", "<i4"), ("n_fine", "<i4"), ("n_meas", "<i4"),
-                               ("depth_n", "<i4"), ("templates_reused", "<i4"), ("pad_", "<i4"), ("depth_sum", "<f8"), ("depth_sum_sq", "<f8")])
-TRACKMAP_MEAS_DT = np.dtype([("point", "<i4"), ("level", "<i4"), ("found", "<i4"), ("did_subpix", "<i4"), ("outlier", "<i4"),
-                             ("pad_", "<i4"), ("v2_found", "<f8", (2,))])
-assert TRACKMAP_RESULT_DT.itemsize == 96 + 4 * 20 + 16 and TRACKMAP_MEAS_DT.itemsize == 40
-assert PATCH_RESULT_DT.itemsize == C.sizeof(PatchResult)
-assert PROJECTION_DT.itemsize == C.sizeof(Projection)
-assert POSE_MEAS_DT.itemsize == C.sizeof(PoseMeas)
-assert POSE_UPDATE_MEAS_DT.itemsize == C.sizeof(PoseUpdateMeas)
-assert BA_TRIAL_DT.itemsize == C.sizeof(BaTrial)
+# the records the library reads and writes as whole tables: each the numpy form of its struct's class in _abi, nested structs nested
+PATCH_QUERY_DT = np.dtype(_abi.PatchQuery)
+PATCH_RESULT_DT = np.dtype(_abi.PatchResult)
+PROJECTION_DT = np.dtype(_abi.Projection)
+POSE_MEAS_DT = np.dtype(_abi.PoseMeas)
+POSE_UPDATE_MEAS_DT = np.dtype(_abi.PoseUpdateMeas)
+SUBPIX_QUERY_DT = np.dtype(_abi.SubpixQuery)
+SUBPIX_RESULT_DT = np.dtype(_abi.SubpixResult)
+TEMPLATE_QUERY_DT = np.dtype(_abi.TemplateQuery)
+EPIPOLAR_QUERY_DT = np.dtype(_abi.EpipolarQuery)
+EPIPOLAR_RESULT_DT = np.dtype(_abi.EpipolarResult)
+TEMPLATE_RESULT_DT = np.dtype(_abi.TemplateResult)
+PVS_POINT_DT = np.dtype(_abi.PvsPoint)
+PVS_RESULT_DT = np.dtype(_abi.PvsResult)
+BA_TRIAL_DT = np.dtype(_abi.BaTrial)
+REFIND_RESULT_DT = np.dtype(_abi.RefindResult)
+REFIND_PAIR_DT = np.dtype(_abi.RefindPair)
+NEW_MAP_POINT_DT = np.dtype(_abi.NewMapPoint)
+EPIPOLAR_STATS_DT = np.dtype(_abi.EpipolarLevelStats)
+EPIPOLAR_STATS_FIELDS = EPIPOLAR_STATS_DT.names
+TRACKMAP_OPTS_DT = np.dtype(_abi.TrackmapOpts)
+TRACKMAP_RESULT_DT = np.dtype(_abi.TrackmapResult)
+TRACKMAP_MEAS_DT = np.dtype(_abi.TrackmapMeas)
+TRAIL_DT = np.dtype(_abi.Trail)
+HOMOGRAPHY_MATCH_DT = np.dtype(_abi.HomographyMatch)
+CALIB_CORNER_DT = np.dtype(_abi.CalibCorner)
+MAP_MEAS_DT = np.dtype(_abi.MapMeas)
+MAP_OUTLIER_DT = np.dtype(_abi.MapOutlier)
+MAP_POINT_SOURCE_DT = np.dtype(_abi.MapPointSource)
+SCENE_DEPTH_DT = np.dtype(_abi.SceneDepth)
+MAP_PAIR_DT = np.dtype(_abi.MapPair)
+MAP_REFIND_POINT_DT = np.dtype(_abi.MapRefindPoint)
+MAP_KF_ROW_DT = np.dtype(_abi.MapKfRow)
+FRAME_RECORD_DT = np.dtype(_abi.FrameRecord)
 
 
 class PtamError(RuntimeError):
@@ -529,11 +518,6 @@ class MapMaker:
         return out[:n.value].copy(), stats[:opts.n_levels].copy()
 
 
-TRAIL_DT = np.dtype([("initial_x", "<i4"), ("initial_y", "<i4"), ("current_x", "<i4"), ("current_y", "<i4")])
-HOMOGRAPHY_MATCH_DT = np.dtype([("first", "<f8", (2,)), ("second", "<f8", (2,)), ("jac", "<f8", (4,))])
-assert TRAIL_DT.itemsize == C.sizeof(_abi.Trail) == 16 and HOMOGRAPHY_MATCH_DT.itemsize == C.sizeof(_abi.HomographyMatch) == 64
-
-
 class Trails:
     """Tracker::TrailTracking_Start / TrailTracking_Advance (src/Tracker.cc:352-432) on device keyframes: the trail list of
     TrackForInitialMap, and the match table InitFromStereo hands to HomographyInit (src/MapMaker.cc:272-279)"""
@@ -655,10 +639,6 @@ class HomographyInit:
         return _homography_call(self.ctx, lambda *a: self.lib.homography_init(self.ctx.h, len(m), _ptr(m), *a), "homography_init", opts, len(m))
 
 
-CALIB_CORNER_DT = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("u", "<f8"), ("v", "<f8")])
-assert CALIB_CORNER_DT.itemsize == C.sizeof(_abi.CalibCorner) == 24
-
-
 class CameraCalibrator:
     """CameraCalibrator's optimiser (src/CameraCalibrator.cc:156-165, 215-269; CalibImage::GuessInitialPose / Project,
     src/CalibImage.cc:514-648) on the device: ptam_calib_*.  The grid corners come from the caller's detector."""
@@ -772,10 +752,6 @@ def init_points_from_trails(ctx, first_kf, second_kf, se3_second_from_first, mat
     return out[:made.value].copy(), status[:n].copy()
 
 
-MAP_MEAS_DT = np.dtype([("kf", "<i4"), ("point", "<i4"), ("level", "<i4"), ("source", "<i4"), ("root_pos", "<f8", (2,))])
-MAP_OUTLIER_DT = np.dtype([("point", "<i4"), ("kf", "<i4"), ("action", "<i4"), ("meas", "<i4")])
-
-
 def map_bundle_adjust(ctx, mode, poses, fixed, points, meas, abort=None, **ba_opts):
     """MapMaker::BundleAdjustRecent (mode _abi.MAP_BA_RECENT) / BundleAdjustAll (_abi.MAP_BA_ALL) in ONE device call
     (ptam_map_bundle_adjust, src/MapMaker.cc:768-933) on the map tables: poses (K, 12) se3CfromW with the newest keyframe last,
@@ -801,12 +777,6 @@ def map_bundle_adjust(ctx, mode, poses, fixed, points, meas, abort=None, **ba_op
     d.update(poses=poses, points=points, outliers=out[:res.n_outliers].copy(), cam_kf=cam_kf[:res.n_adjust + res.n_fixed].copy(),
              point_ids=point_ids[:res.n_points].copy())
     return d
-
-
-MAP_POINT_SOURCE_DT = np.dtype([("src_kf", "<i4"), ("pad_", "<i4"), ("center_nc", "<f8", (3,)), ("one_right_nc", "<f8", (3,)),
-                                ("one_down_nc", "<f8", (3,))])
-SCENE_DEPTH_DT = np.dtype([("depth_mean", "<f8"), ("depth_sigma", "<f8"), ("n_meas", "<i4"), ("pad_", "<i4")])
-assert MAP_POINT_SOURCE_DT.itemsize == C.sizeof(_abi.MapPointSource) == 80 and SCENE_DEPTH_DT.itemsize == C.sizeof(_abi.SceneDepth) == 24
 
 
 def shuffle_order(lib, seed, frame, which, n):
@@ -971,12 +941,6 @@ class ReFinder:
             self.h = None
 
 
-MAP_PAIR_DT = np.dtype([("kf", "<i4"), ("point", "<i4")])
-MAP_REFIND_POINT_DT = np.dtype([("pv", PVS_POINT_DT), ("src_kf", "<i4"), ("src_level", "<i4"), ("center_x", "<i4"), ("center_y", "<i4"),
-                                ("bad", "<i4"), ("pad_", "<i4")])
-assert MAP_PAIR_DT.itemsize == C.sizeof(_abi.MapPair) == 8 and MAP_REFIND_POINT_DT.itemsize == C.sizeof(_abi.MapRefindPoint) == 96
-
-
 def map_refind_points(world, pixel_right_w, pixel_down_w, src_kf, src_level, centers, bad=None):
     """the point table of map_refind (MAP_REFIND_POINT_DT): src_kf is an index into the keyframe table"""
     n = len(world)
@@ -1027,9 +991,6 @@ def map_refind(ctx, finder, mode, kfs, poses, points, meas, never, work, stop=No
     if merged:
         d.update(meas_merged=mm[:M + res.n_found].copy(), never_merged=nm[:V + res.n_never].copy())
     return d
-
-
-assert C.sizeof(_abi.MapColumn) == 16 and C.sizeof(_abi.MapOutliersResult) == 24 and C.sizeof(_abi.MapBadPointsResult) == 32
 
 
 def _counts(res):
@@ -1119,13 +1080,6 @@ def map_add_points(ctx, n_kf, n_points, meas, src_kf, target_kf, made, target_so
                                       _ptr(made), _ptr(mo), _ptr(pts), _ptr(src)), "map_add_points")
     return dict(meas=mo[:M + 2 * A].copy(), points=pts[:A].copy(), sources=src[:A].copy(),
                 new_queue=np.arange(int(n_points), int(n_points) + A, dtype=np.int32))
-
-
-MAP_KF_ROW_DT = np.dtype([("point", "<i4"), ("level", "<i4"), ("root_pos", "<f8", (2,))])
-FRAME_RECORD_DT = np.dtype([("serial", "<i8"), ("level", "<i4"), ("outlier", "u1"), ("did_subpix", "u1"), ("pad_", "u1", (2,)),
-                            ("root_pos", "<f8", (2,))])
-assert FRAME_RECORD_DT.itemsize == 32
-assert MAP_KF_ROW_DT.itemsize == C.sizeof(_abi.MapKfRow) == 24 and C.sizeof(_abi.RmapCounts) == 24
 
 
 class ResidentMap:

@@ -2,6 +2,8 @@
 bundle problems.  Pure numpy; used by tests/ and bench.py.  Nothing here depends on the oracle."""
 import numpy as np
 
+from . import _abi
+
 SEED_FRAME = 0x5EED0001
 SEED_QUERIES = 0x5EED0002
 SEED_POSE = 0x5EED0003
@@ -512,7 +514,7 @@ def load_into(bundle, prob):
 # ---------------------------------------------------------------------------------------------
 # calibration grids (CameraCalibrator: the corners of a checkerboard seen by a known ATAN camera)
 # ---------------------------------------------------------------------------------------------
-CALIB_CORNER_DT = np.dtype([("gx", "<i4"), ("gy", "<i4"), ("u", "<f8"), ("v", "<f8")])
+CALIB_CORNER_DT = np.dtype(_abi.CalibCorner)
 
 
 def make_calib_grids(truth_params, size, n_images, grid_w, grid_h, seed, noise_px=0.0, distance=(6.0, 10.0), tilt=0.6):

@@ -19,19 +19,21 @@ Class I (ill conditioned, as a lightly damped bundle's S): S = L0 D0 L0^T, L0 un
 """
 import numpy as np
 
+from ptam_cg_amd import _abi
+
 NB = 32
 LD = np.longdouble
 
 # ---- the plan bits (include/ptam_hip_bench.h) -----------------------------------------------------------------------------------
-SMALL, CHAIN_FWD_INV, CHAIN_BW_IN_LAUNCH, CHAIN_SEPARATE_BW, STEPS, TWO_CHAINS, TWIN_STEPS, MID_CHAIN, MID_STEPS, BW_TWO_WG, BW_GLOBAL = (
-    1 << i for i in range(11))
 BIT_NAMES = ["SMALL", "CHAIN_FWD_INV", "CHAIN_BW_IN_LAUNCH", "CHAIN_SEPARATE_BW", "STEPS", "TWO_CHAINS", "TWIN_STEPS", "MID_CHAIN",
              "MID_STEPS", "BW_TWO_WG", "BW_GLOBAL"]
-PER_COLUMN, POISON_UPPER = 1, 2   # flags of ptam_ba_solve_plan / ptam_ba_debug_solve
+SMALL, CHAIN_FWD_INV, CHAIN_BW_IN_LAUNCH, CHAIN_SEPARATE_BW, STEPS, TWO_CHAINS, TWIN_STEPS, MID_CHAIN, MID_STEPS, BW_TWO_WG, BW_GLOBAL = (
+    getattr(_abi, "SP_" + n) for n in BIT_NAMES)
+PER_COLUMN, POISON_UPPER = _abi.SOLVE_PER_COLUMN, _abi.SOLVE_POISON_UPPER   # flags of ptam_ba_solve_plan / ptam_ba_debug_solve
 
 
 def plan_names(mask):
-    return "|".join(n for i, n in enumerate(BIT_NAMES) if mask >> i & 1) or "0"
+    return "|".join(n for n in BIT_NAMES if mask & getattr(_abi, "SP_" + n)) or "0"
 
 
 # (nblk, band) -> free cameras, the whole mask ba_solve must choose (persistent forms allowed), and with flags bit 0.

@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 from ptam_cg_amd import host, synth
+from ptam_cg_amd._abi import (BL_CAM_MEAS, BL_CAM_PTR, BL_CHUNKS, BL_COUNTS, BL_M_CAM, BL_M_FIDX, BL_M_FOUND, BL_M_ORIG, BL_M_PT, BL_M_S, BL_POINTS,
+                              BL_PT_ORIG, BL_ROWPTR, BL_S_ENTRIES, BL_S_PAIR_BEGIN, BL_S_SEGS, BL_S_WG_HEAD, BL_S_WG_SEG)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-(BL_COUNTS, BL_ROWPTR, BL_M_CAM, BL_M_PT, BL_M_ORIG, BL_M_FIDX, BL_M_FOUND, BL_M_S, BL_PT_ORIG, BL_POINTS, BL_CHUNKS, BL_S_ENTRIES,
- BL_S_SEGS, BL_S_WG_SEG, BL_S_PAIR_BEGIN, BL_S_WG_HEAD, BL_CAM_PTR, BL_CAM_MEAS) = range(18)
 SOLVE_NB, BA_CHUNK, TC, DET_TILE = 32, 256, 8, 1024
 CFG = dict(seg_cost=4900, second_lag=7000, min_room=4900, min_seg=16, n_first=32, cost_model=36, slots=64, greedy=0)
 

@@ -13,12 +13,12 @@ import numpy as np
 import pytest
 
 from ptam_cg_amd import host, synth
+from ptam_cg_amd._abi import BL_COUNTS
 from tests import solve_ref as R
 from tests import util
 
 pytestmark = pytest.mark.gpu
 ROWS = [pytest.param(r, id=R.row_id(r)) for r in R.TABLE]
-BL_COUNTS = 0
 
 
 def covisibility_problem(n_free, band):

@@ -1,64 +1,32 @@
-"""CPU: the Python side of ptam_mapmaker matches include/ptam_hip.h — the field order and sizes of ptam_mapmaker_opts and
-ptam_mapmaker_step_result, the status and stage numbers, the argument counts — the defaults ptam_mapmaker_opts_default writes are the
-reference's (src/MapMaker.cc:103, :511-514), and the handle's host-only entries (queue, flags, reset request, released tags) do what
-the header says without a device."""
+"""CPU: ptam_mapmaker's host side (its structs, status and stage numbers and argument counts are checked with the whole header in
+tests/test_abi.py): the wrappers exist, the defaults ptam_mapmaker_opts_default writes are the reference's (src/MapMaker.cc:103,
+:511-514), and the handle's host-only entries (queue, flags, reset request, released tags) do what the header says without a device."""
 import ctypes
-import os
 import re
 
 from ptam_cg_amd import _abi, host
+from tests import abi_header as H
+from tests.abi_header import lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ptam_hip.h")).read(), flags=re.S)
-LIB = os.path.join(ROOT, "ptam_cg_amd", "csrc", "libptam_hip.so")
-ENTRIES = {"mapmaker_opts_default": 1, "mapmaker_create": 5, "mapmaker_destroy": 1, "mapmaker_add_keyframe": 8, "mapmaker_note_frame": 3,
-           "mapmaker_queue_size": 2, "mapmaker_request_reset": 1, "mapmaker_reset_done": 2, "mapmaker_flags": 4, "mapmaker_set_flags": 3,
-           "mapmaker_released": 4, "mapmaker_step": 2}
-
-
-def header_fields(struct):
-    """the field names of `typedef struct { ... } struct;`, in order, arrays without their bounds"""
-    body = re.search(r"typedef\s+struct\s*{([^{}]*)}\s*" + struct + r"\s*;", HEADER).group(1)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            first, *rest = decl.split(",")
-            names.append(re.sub(r"\[.*", "", first.split()[-1]).lstrip("*"))
-            names += [re.sub(r"\[.*", "", r.strip()).lstrip("*") for r in rest]
-    return names
-
-
-def test_struct_fields_and_sizes_match_the_header():
-    assert header_fields("ptam_mapmaker_opts") == [f for f, _ in _abi.MapmakerOpts._fields_]
-    assert header_fields("ptam_mapmaker_step_result") == [f for f, _ in _abi.MapmakerStepResult._fields_]
-    S = ctypes.sizeof
-    assert S(_abi.MapmakerOpts) == S(_abi.BaOpts) + S(_abi.MapRefindOpts) + S(_abi.RmapInsertOpts) + 4 + 4 + 8
-    parts = (_abi.MapBaResult, _abi.MapOutliersResult, _abi.MapRefindResult, _abi.MapBaResult, _abi.MapOutliersResult, _abi.MapRefindResult,
-             _abi.RmapNoteResult, _abi.MapBadPointsResult, _abi.RmapInsertResult, _abi.MapPublishResult)
-    assert S(_abi.MapmakerStepResult) == 8 + sum(S(p) for p in parts) + 8 + 16 + 8
-    assert _abi.MapmakerStepResult.insert.offset % 8 == 0 and _abi.MapmakerStepResult.draws.offset % 8 == 0
+ENTRIES = ("mapmaker_opts_default", "mapmaker_create", "mapmaker_destroy", "mapmaker_add_keyframe", "mapmaker_note_frame",
+           "mapmaker_queue_size", "mapmaker_request_reset", "mapmaker_reset_done", "mapmaker_flags", "mapmaker_set_flags",
+           "mapmaker_released", "mapmaker_step")
 
 
 def test_numbers_and_argument_counts_match_the_header():
-    enum = dict((k, int(v)) for k, v in re.findall(r"\b(PTAM_MM_[A-Z_]+)\s*=\s*(\d+)", HEADER))
-    assert sorted(enum) == sorted(["PTAM_MM_RAN", "PTAM_MM_IDLE", "PTAM_MM_RESET"] + ["PTAM_MM_STAGE_" + s for s in (
-        "BUNDLE_RECENT", "REFIND_NEW", "BUNDLE_ALL", "REFIND_FAILURE", "NOTES", "BAD_POINTS", "ADD_KEYFRAME", "PUBLISH")])
-    for k, v in enum.items():
+    """the PTAM_MM_ names of the header are the pinned ones (PTAM_MM_INIT = 3 and PTAM_MM_STAGE_INIT = 256 among them, plain numbers in
+    their enums) with the pinned values in _abi, and the handle's entries take the pinned numbers of arguments"""
+    mm = {k: v for k, v in H.PINNED_NUMBERS.items() if k.startswith("PTAM_MM_")}
+    assert sorted(mm) == sorted(n for n in H.NUMBERS if n.startswith("PTAM_MM_")) and len(mm) == 16
+    assert (mm["PTAM_MM_INIT"], mm["PTAM_MM_STAGE_INIT"]) == (3, 256)
+    assert re.search(r"\bPTAM_MM_INIT\s*=\s*3\b", H.HEADER) and re.search(r"\bPTAM_MM_STAGE_INIT\s*=\s*256\b", H.HEADER)
+    for k, v in mm.items():
         assert getattr(_abi, k[len("PTAM_"):]) == v, k
-    for name, n_args in ENTRIES.items():
-        args = re.search(r"\bint\s+ptam_" + name + r"\s*\(([^;]*?)\)\s*;", HEADER, flags=re.S).group(1)
-        assert len([a for a in args.split(",") if a.strip()]) == n_args == len(_abi.PROTOTYPES[name][1]), name
+    for name in ENTRIES:
+        assert len(H.PROTOTYPES["ptam_" + name][1]) == H.PINNED_ENTRIES[name] == len(_abi.PROTOTYPES[name][1]), name
         assert _abi.PROTOTYPES[name][0] is ctypes.c_int
     for method in ("AddKeyFrame", "NoteFrame", "QueueSize", "RequestReset", "ResetDone", "Step", "flags", "set_flags", "released", "mapmaker_opts"):
         assert callable(getattr(host.MapMaker, method))
-
-
-def lib():
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _abi.bind(ctypes.CDLL(LIB), "ptam_")
 
 
 def test_defaults_are_the_reference_s():
